@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """bench.py -- LM iterations/s and ms/frame of the embedded-deformation LM hot path.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload C2] [--frames-per-gpu B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload C2] [--frames-per-gpu B] [--full]
+                    [--dump-outputs DIR]
 
 One *step* = one pass of the hot path over one batch of synthetic input: for each of the
 B independent frames resident on a GPU, bind the frame (``loss_term.prepare``), run
@@ -11,7 +12,11 @@ before the timed region starts.  N > 1: one process per GPU (torchrun), frames s
 across ranks (weak scaling, B frames per GPU), end-of-frame RCCL all-gather of beta
 (SURVEY.md section 8e); rank 0 prints ONE JSON line.
 
-`value` = whole-job LM iterations per second.  `roofline` = the TIME-DOMINANT phase, the float64
+`value` = whole-job LM iterations per second, `ms_per_step` = milliseconds of one timed step.  A plain run does only
+what that headline needs: set up, warm up, time K steps, write the outputs of the last step when `--dump-outputs DIR`
+is given (`dump_outputs`), print the line.  Everything below but `host` is measured with `--full` only.
+
+`roofline` = the TIME-DOMINANT phase, the float64
 multifrontal factor + substitutions (f64-MFMA bound; FLOPs from the plan, padded and unpadded),
 timed with HIP events on its launch stream inside the timed region; `roofline_data` = the fused
 data-term Jacobian pass (one launch per LM iteration, HBM bound); `whole_step_hbm_frac` = the
@@ -48,12 +53,20 @@ def parse():
     ap.add_argument("--frames-per-gpu", type=int, default=8)
     ap.add_argument("--streams", type=int, default=1,
                     help="split the frames of a GPU over this many solver handles / HIP streams")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-profile", action="store_true", help="skip HIP-event phase timing")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: HIP-event phase timing and the rooflines in the timed "
+                         "region, latency_b1 / batch legs, bind timing, CPU baselines, oracle parity, GraphFit and the other rows")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(with --full) skip the CPU baselines and the parity check")
+    ap.add_argument("--no-profile", action="store_true", help="(with --full) skip HIP-event phase timing")
     ap.add_argument("--no-latency-b1", action="store_true",
-                    help="skip the one-frame-per-launch leg (profiles/collect.sh: keeps the kernel statistics of a "
+                    help="(with --full) skip the one-frame-per-launch leg (profiles/collect.sh: keeps the kernel statistics of a "
                          "profiled run to the launches of the headline configuration)")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
 
 
 def workload_dims(name):
@@ -822,6 +835,36 @@ def fusion_timing(device):
             "achieved_GBps": nbytes / ms / 1e6, "note": "C calls with resident buffers; one count read-back per call (2 per frame)"}
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(path, beta, state, losses):
+    """`--dump-outputs DIR`: what the timed path handed back in its last step, one DIR/<name>.npy per array -- `beta`
+    (frames, J, 7) float64 (all global frames after the all-gather when ranks exchange), the four state arrays
+    Surfels.update moved (frames, N or J, 3; frames of other sizes are concatenated
+    along the rows) in their storage dtype, `lm_loss` (frames, iterations) float64.  The inputs
+    are seeded, so two builds run with the same arguments can be compared array by array.  Above 64 MB in all, the
+    surfel arrays keep a fixed, seeded sample of their rows (the same rows in every frame and array)."""
+    import numpy as np
+    out = {"beta": np.asarray(beta, dtype=np.float64), "lm_loss": np.asarray(losses, dtype=np.float64)}
+    for nm, arr in state.items():
+        out[nm] = arr.astype(np.float64 if arr.dtype == np.float64 else np.float32, copy=False)
+    total = sum(v.nbytes for v in out.values())
+    budget = DUMP_BUDGET_BYTES - 1024 * len(out)          # (room for the .npy headers)
+    if total > budget:
+        rows = out["sf_points"].shape[-2]
+        big = [nm for nm in out if nm.startswith("sf_")]
+        per_row = sum(out[nm].nbytes // rows for nm in big)
+        keep = max(1, min(rows, (budget - (total - per_row * rows)) // per_row))
+        idx = np.sort(np.random.default_rng(0).choice(rows, size=keep, replace=False))
+        for nm in big:
+            out[nm] = np.ascontiguousarray(out[nm][..., idx, :])
+    os.makedirs(path, exist_ok=True)
+    for nm, arr in out.items():
+        np.save(os.path.join(path, nm + ".npy"), arr)
+    return sorted(out)
+
+
 def main():
     a = parse()
     import numpy as np
@@ -939,10 +982,12 @@ def main():
             dist.barrier()
         torch.cuda.synchronize(device)
 
+    # HIP-event phase timing inside the timed region (the roofline figures): --full only
+    profiled = a.full and not a.no_profile
     for _ in range(a.warmup):
         step()
     fence()
-    if not a.no_profile:
+    if profiled:
         for e in engs:
             e.profile(True)
     del step_events[:]
@@ -974,7 +1019,7 @@ def main():
     evs = [ev0] + step_events
     step_ms = sorted(a_.elapsed_time(b_) for a_, b_ in zip(evs, evs[1:]))
     prof = None
-    if not a.no_profile:
+    if profiled:
         for e in engs:
             pr = e.profile_read()
             if prof is None:
@@ -1006,6 +1051,14 @@ def main():
         dump = os.environ.get("BENCH_DUMP_BETAS")
         if dump and rank == 0 and gathered[0] is not None:
             np.save(dump, gathered[0].cpu().numpy())
+
+    dumped = None
+    if a.dump_outputs and rank == 0:
+        state = {nm: (work_big[nm] if same_shape else torch.cat([getattr(w, nm) for w in work])).cpu().numpy()
+                 for nm in reset_fields}
+        losses = [[r["loss"] for r in e.records(i)] for e in engs for i in range(Bs)]
+        beta_out = gathered[0] if gathered[0] is not None else torch.stack(betas)
+        dumped = dump_outputs(a.dump_outputs, beta_out.cpu().numpy(), state, losses)
 
     recs = eng.records(0)
     final_loss = [r["loss"] for r in recs if r["status"] == 0]
@@ -1039,7 +1092,10 @@ def main():
             "distributed": {"backend": backend if use_dist else None, "world": world,
                             "launched_by": "torchrun" if launched else None},
             "worst_iter_status_all_ranks": worst_status,
+            "full": bool(a.full),
         }
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
         if per_rank_steps is not None:
             out["distributed"]["per_rank_step_ms"] = {"columns": ["min", "median", "max", "timed_region_wall_ms"],
                                                       "ranks": per_rank_steps}
@@ -1089,7 +1145,7 @@ def main():
             # whole step against the HBM peak: algorithmic bytes of one LM iteration x iterations x frames
             step_bytes = world * B * iters * (144.0 * N + 3205.0 * J)
             out["whole_step_hbm_frac"] = step_bytes / (elapsed / a.steps) / 1e9 / HBM_PEAK_GBS
-        if world == 1 and not a.no_profile and not a.no_latency_b1:
+        if a.full and world == 1 and not a.no_profile and not a.no_latency_b1:
             out["latency_b1"] = latency_b1(dims, device, iters)
             out["latency_b1_sequence"] = latency_b1_sequence(device)
             if a.workload in ("C1", "C2") and S == 1:
@@ -1099,9 +1155,9 @@ def main():
         out["host"] = host_info()
         out["host"]["cpu_cores_busy_per_rank"] = round(cpu_busy, 2)   # (rank 0; timed region; user + system time of all threads)
         out["host"]["cpu_cores_busy_all_ranks"] = round(cpu_busy_all, 2)   # (sum over the ranks: what the job costs of the node's CPU quota)
-        if world == 1 and not a.no_profile:
+        if a.full and world == 1 and not a.no_profile:
             out["bind"] = bind_timing(dims, device, B)
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"], oracle_beta, oracle_trace = cpu_baseline(dims, seed=0)
             out["parity_" + a.workload.lower()] = parity_check(dims, device, oracle_beta, oracle_trace, B)
             assert out["parity_" + a.workload.lower()]["ok"], out["parity_" + a.workload.lower()]

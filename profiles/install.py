@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Copy what `profiles/collect.sh <tag>` left under gpurun_out/ into profiles/ (tracked):
+"""Copy what `profiles/collect.sh <tag>` left under $PROFILE_OUT (default profile_out/) into profiles/ (tracked):
     python profiles/install.py r02
 bench lines, kernel-stat summaries (8 frames and 1 frame per launch), the two HBM PMC passes trimmed to the columns
 used, the per-kernel traffic summary (re-made here so that its tag is the hash of the sources in this tree:
@@ -13,7 +13,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 tag = sys.argv[1] if len(sys.argv) > 1 else "r03"
-G = os.path.join(ROOT, "gpurun_out")
+G = os.environ.get("PROFILE_OUT", os.path.join(ROOT, "profile_out"))
 P = os.path.join(ROOT, "profiles")
 KEEP = ["Dispatch_Id", "Grid_Size", "Kernel_Name", "Workgroup_Size", "LDS_Block_Size", "VGPR_Count", "Accum_VGPR_Count",
         "Counter_Name", "Counter_Value", "Start_Timestamp", "End_Timestamp"]
@@ -23,7 +23,7 @@ def one(pattern):
     m = glob.glob(os.path.join(G, pattern), recursive=True)
     if not m:
         raise SystemExit("missing " + pattern)
-    return max(m, key=os.path.getmtime)      # gpurun merges into gpurun_out/: older collections may still be there
+    return max(m, key=os.path.getmtime)      # older collections may still be in the output folder
 
 
 shutil.copy(os.path.join(G, f"{tag}_bench.json"), os.path.join(P, f"{tag}_C2_b8_bench.json"))
