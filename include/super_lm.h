@@ -401,7 +401,8 @@ int slm_gf_bind_semantic(slm_gf* g, int32_t slot, const slm_gf_semantic* sem, in
  * of the reference's models.optical_flow(src.rgb, inputs[("color",0)]) (super/deform_mesh.py:286-320), which stays
  * with the caller.  The term samples it at each surfel's unrounded projection exactly like
  * F.grid_sample(flow, grid.float()) (bilinear, zero padding, align_corners=False; super/loss.py:318-323), moves
- * the projection by it and evaluates the 4-tap residual there; the gradient includes d(flow)/d(u,v). */
+ * the projection by it and evaluates the 4-tap residual there; the gradient includes d(flow)/d(u,v).  May be called
+ * again between the iterations of a frame (slm_gf_eval_* / slm_gf_step): it replaces the flow only. */
 int slm_gf_bind_flow(slm_gf* g, int32_t slot, const float* flow_device, void* stream);
 /* Copies the slot's boundary pixels of `class_id` ((x,y) float pairs, row-major pixel order) to
  * device memory `xy_out_device` (capacity max_points pairs). */
@@ -601,6 +602,53 @@ int slm_fuse_input_data(slm_fuse* f, const slm_fuse_config* cfg, slm_surfel_mode
  * of every old row or -1 (the reference's id_map, super/nodes.py:578-581). */
 int slm_fuse_swap_stable(slm_fuse* f, const slm_fuse_config* cfg, slm_surfel_model* model, int32_t time,
                          const int32_t* keep_ids, int32_t n_keep, int32_t* new_index, void* stream);
+
+/* ===================================================================================
+ * Forward surfel renderer (Pulsar's blend at the reference's parameters)
+ *   slm_render_points  <- Pulsar.forward                      renderer/renderer.py:12-78
+ *   slm_gf_render      <- models.renderer(inputs, new_data)   super/deform_mesh.py:292-298
+ * Every point is a sphere of radius `radius`.  Pixel (i,j) casts the line through the camera centre and
+ * (u,v) = (j,i); sphere k is hit when the distance rho_k from its centre to that line is < radius.  Centres
+ * with Z outside [z_near, z_far] are culled.  Of the hits of a pixel, the n_track with the largest
+ * zt = (z_far - Z)/(z_far - z_near) take part (equal zt: lower row first); with zt_max the first of them,
+ *   w_k = (1 - rho_k/radius) exp((zt_k - zt_max)/gamma),   w_bg = exp((bg_eps - zt_max)/gamma),
+ *   colour = (sum w_k c_k + w_bg bg) / (sum w_k + w_bg),   bg where nothing is hit.
+ * Positions are rounded to float32 first (Pulsar is called with points.float()).  The image is written
+ * (height,width,3) float32, channels last.  Results are bitwise reproducible.  Each call synchronises
+ * `stream` once (a 8-byte read-back that sizes the tile lists).
+ * =================================================================================== */
+typedef struct slm_render slm_render; /* opaque: per-surfel projections, tile lists and their scratch */
+
+#define SLM_RENDER_MAX_TRACK 64
+typedef struct slm_render_params {
+  int32_t width, height;   /* w = int(W view_scale), h = int(H view_scale) */
+  int32_t n_track;         /* hits that take part per pixel, 1..SLM_RENDER_MAX_TRACK (64) */
+  int32_t points_f64;      /* slm_render_points: positions are float64 (else float32) */
+  double focal;            /* f = K[0,0] view_scale (one focal length: fy is not used) */
+  double ccx, ccy;         /* principal point: u = f X/Z + ccx, v = f Y/Z + ccy */
+  double radius;           /* opt.renderer_rad, the same for every point */
+  double z_near, z_far;    /* 0.01, 15.0 */
+  double gamma;            /* 1e-5 */
+  double bg_eps;           /* 1e-9 */
+  float bg[3];             /* background colour */
+  int32_t pad;
+} slm_render_params;
+
+/* Renders of up to H x W pixels and max_points points. */
+int slm_render_create(int32_t H, int32_t W, int32_t max_points, slm_render** out);
+int slm_render_destroy(slm_render* r);
+/* points (N,3) device, float32 or float64 (p->points_f64); colors (N,3) device float32, row i at
+ * colors + i * color_stride (color_stride >= 3).  image (height,width,3) device float32.  front_id (height,width)
+ * int32 (the row of the first hit, -1 where nothing is hit) and hit_count (height,width) int32 (hits that took
+ * part, <= n_track) may be NULL. */
+int slm_render_points(slm_render* r, const slm_render_params* p, int32_t N, const void* points, const float* colors,
+                      int32_t color_stride, float* image, int32_t* front_id, int32_t* hit_count, void* stream);
+/* The same for the CURRENT deformed stable surfels of GraphFit slot `slot` (deform_source's new_data.points,
+ * global row included, super/deform_mesh.py:198-230), computed on the device from the slot's deform_verts.
+ * Colours are indexed by surfel row like sf_points (pass sf.colors; rows of unstable surfels are not read),
+ * front_id holds surfel rows.  p->points_f64 is ignored. */
+int slm_gf_render(slm_gf* g, int32_t slot, slm_render* r, const slm_render_params* p, const float* colors,
+                  int32_t color_stride, float* image, int32_t* front_id, int32_t* hit_count, void* stream);
 
 /* ===================================================================================
  * "Next" row f3: ED-graph construction at frame 0

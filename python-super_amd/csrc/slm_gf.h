@@ -190,3 +190,7 @@ __device__ __forceinline__ d3 gf_skin_pos(const GfSlotDev& s, int i) {
   d3 P = quat_apply(bgl[0], {bgl[1], bgl[2], bgl[3]}, T);
   return {P.x + bgl[4], P.y + bgl[5], P.z + bgl[6]};
 }
+
+// slm_gf_render (slm_render.hip): the device descriptor of bound slot `slot` (its current deform_verts) and its
+// surfel count; SLM_OK or an error status with the text set.
+int gf_render_slot(slm_gf* g, int32_t slot, GfSlot** dev, int32_t* n_surfels);

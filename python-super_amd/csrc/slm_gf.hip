@@ -907,7 +907,9 @@ int slm_gf_bind_flow(slm_gf* g, int32_t slot, const float* flow, void* stream) {
   if (!s.bound) return gf_fail(SLM_ERR_UNBOUND, "slm_gf_bind_flow: slm_gf_bind_frame first");
   hipStream_t st = (hipStream_t)stream;
   s.flow = flow;
-  GFCHK(hipMemcpyAsync(g->dev + slot, &s, sizeof(GfSlot), hipMemcpyHostToDevice, st));
+  // the pointer alone: the device copy of the slot also holds the optimiser's step count, which the host copy does not
+  // follow (sf_corr_match_renderimg binds a new flow between the iterations of one frame)
+  GFCHK(hipMemcpyAsync(&g->dev[slot].flow, &s.flow, sizeof(s.flow), hipMemcpyHostToDevice, st));
   GFCHK(hipStreamSynchronize(st));
   return SLM_OK;
 }
@@ -1083,3 +1085,11 @@ int slm_apply_update_gf_f64(int32_t N, int32_t J, int32_t K, double* sf_points, 
 }
 
 }  // extern "C"
+
+int gf_render_slot(slm_gf* g, int32_t slot, GfSlot** dev, int32_t* n_surfels) {
+  if (!g || slot < 0 || slot >= (int)g->host.size()) return gf_fail(SLM_ERR_INVALID, "slm_gf_render: bad slot");
+  if (!g->host[slot].bound) return gf_fail(SLM_ERR_UNBOUND, "slm_gf_render: slm_gf_bind_frame first");
+  *dev = g->dev + slot;
+  *n_surfels = g->host[slot].f.base.N;
+  return SLM_OK;
+}

@@ -1,0 +1,425 @@
+// slm_render.hip -- forward surfel renderer: Pulsar's blend (Lassner & Zollhoefer, CVPR 2021) at the parameters of
+// the reference's call (renderer/renderer.py:23-78).  The image it computes is specified in include/super_lm.h and
+// DESIGN.md section "Renderer"; tests/render_model.py restates it on the CPU.
+//
+// Four launches and one 8-byte read-back per render:
+//   k_rn_project  per point: float32 position, cull, pixel box of the sphere's silhouette, count per 16x16 tile
+//   k_rn_scan     one workgroup: exclusive scan of the tile counts -> list offsets and scatter cursors
+//   (host)        the list total sizes the key buffers
+//   k_rn_scatter  per point: key (float bits of Z << 32 | row) into the list of every tile its box touches
+//   k_rn_tile     one workgroup per tile: sort the tile's keys front to back (bitonic in LDS; a list longer than
+//                 RN_SORT_CAP is sorted in LDS chunk by chunk and merged in global memory), then every lane walks its
+//                 pixel's list front to back in LDS chunks, keeps the first n_track hits and blends in float64.
+// The keys are unique (one per point and tile), so the sorted order -- and with it every float64 sum, taken by one
+// lane in list order -- does not depend on the order the atomic cursors handed out slots: renders are bitwise
+// reproducible.  The only atomics are integer ones (tile counts, cursors).
+#include <cmath>
+#include <string>
+
+#include "slm_gf.h"
+
+#define RN_TILE 16            // tile edge in pixels: one lane per pixel, 256 lanes per workgroup
+#define RN_SORT_CAP 4096      // keys a workgroup sorts in LDS at once (32 KB)
+#define RN_CHUNK 256          // list entries staged in LDS per step of the walk
+
+void slm_set_error_text(const char* msg);   // slm_api.hip
+
+struct slm_render {
+  int H = 0, W = 0, cap = 0;
+  float4* pos = nullptr;                 // (cap) float32 centre, w unused
+  int4* box = nullptr;                   // (cap) inclusive pixel box x0, x1, y0, y1 (x0 > x1: culled)
+  unsigned int* cnt = nullptr;           // (tiles) entries per tile
+  unsigned long long* off = nullptr;     // (tiles + 1) exclusive scan of cnt
+  unsigned long long* cur = nullptr;     // (tiles) scatter cursors
+  unsigned long long* keys = nullptr;    // (cap_keys) tile lists
+  unsigned long long* tmp = nullptr;     // (cap_keys) merge scratch of the overflow path
+  size_t cap_keys = 0;
+  unsigned long long* h_total = nullptr; // pinned host copy of off[tiles]
+};
+
+namespace {
+
+struct RnCam {
+  int w, h, tiles_x, n_track;
+  double f, ccx, ccy, r, zn, zf, gamma, eps;
+  float bg0, bg1, bg2;
+};
+
+enum { RN_SRC_F32 = 0, RN_SRC_F64 = 1, RN_SRC_GF = 2 };
+
+// inclusive pixel range [lo, hi] of the lines whose slope t (x/z or y/z) lies strictly inside the silhouette
+// (c z -+ r sqrt(c^2 + z^2 - r^2)) / (z^2 - r^2) of a sphere seen from the origin, padded by 1e-3 px
+__device__ __forceinline__ void rn_range(double c, double z, double r, double f, double cc, int n, int& lo, int& hi) {
+  const double den = z * z - r * r, disc = c * c + den;
+  if (!(den > 0.0) || !(disc > 0.0)) {   // the sphere reaches the camera plane: every pixel is a candidate
+    lo = 0;
+    hi = n - 1;
+    return;
+  }
+  const double s = r * sqrt(disc);
+  double a = f * (c * z - s) / den + cc - 1e-3, b = f * (c * z + s) / den + cc + 1e-3;
+  a = fmin(fmax(a, -1.0), (double)n);
+  b = fmin(fmax(b, -1.0), (double)n);
+  lo = max((int)ceil(a), 0);
+  hi = min((int)floor(b), n - 1);
+}
+
+template <int SRC>
+__global__ void __launch_bounds__(256) k_rn_project(int N, const void* __restrict__ pts, GfSlot* __restrict__ gslot, RnCam cam,
+                                                    float4* __restrict__ pos, int4* __restrict__ box,
+                                                    unsigned int* __restrict__ cnt) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= N) return;
+  float X, Y, Z;
+  bool live = true;
+  if constexpr (SRC == RN_SRC_F32) {
+    const float* p = static_cast<const float*>(pts) + 3 * (size_t)i;
+    X = p[0]; Y = p[1]; Z = p[2];
+  } else if constexpr (SRC == RN_SRC_F64) {
+    const double* p = static_cast<const double*>(pts) + 3 * (size_t)i;
+    X = (float)p[0]; Y = (float)p[1]; Z = (float)p[2];   // tensor.float(): round to nearest
+  } else {
+    const GfSlotDev& s = *gf_dev(gslot);
+    const uint8_t* st = s.f.sf_stable;
+    live = !st || st[i];
+    X = Y = Z = 0.f;
+    if (live) {
+      const d3 P = gf_skin_pos(s, i);
+      X = (float)P.x; Y = (float)P.y; Z = (float)P.z;
+    }
+  }
+  int4 b = make_int4(1, 0, 1, 0);   // empty
+  if (live && (double)Z >= cam.zn && (double)Z <= cam.zf) {
+    int x0, x1, y0, y1;
+    rn_range((double)X, (double)Z, cam.r, cam.f, cam.ccx, cam.w, x0, x1);
+    rn_range((double)Y, (double)Z, cam.r, cam.f, cam.ccy, cam.h, y0, y1);
+    if (x0 <= x1 && y0 <= y1) {
+      b = make_int4(x0, x1, y0, y1);
+      for (int ty = y0 / RN_TILE; ty <= y1 / RN_TILE; ++ty)
+        for (int tx = x0 / RN_TILE; tx <= x1 / RN_TILE; ++tx) atomicAdd(cnt + ty * cam.tiles_x + tx, 1u);
+    }
+  }
+  pos[i] = make_float4(X, Y, Z, 0.f);
+  box[i] = b;
+}
+
+// exclusive scan of n tile counts, one workgroup of 1024 lanes, 1024 counts per round
+__global__ void __launch_bounds__(1024) k_rn_scan(int n, const unsigned int* __restrict__ cnt,
+                                                  unsigned long long* __restrict__ off, unsigned long long* __restrict__ cur) {
+  __shared__ unsigned long long s[1024];
+  __shared__ unsigned long long carry;
+  const int t = threadIdx.x;
+  if (t == 0) carry = 0;
+  __syncthreads();
+  for (int base = 0; base < n; base += 1024) {
+    const unsigned long long v = base + t < n ? cnt[base + t] : 0ull;
+    s[t] = v;
+    __syncthreads();
+    for (int d = 1; d < 1024; d <<= 1) {
+      const unsigned long long a = t >= d ? s[t - d] : 0ull;
+      __syncthreads();
+      s[t] += a;
+      __syncthreads();
+    }
+    const unsigned long long ex = carry + s[t] - v;
+    if (base + t < n) {
+      off[base + t] = ex;
+      cur[base + t] = ex;
+    }
+    __syncthreads();
+    if (t == 1023) carry += s[1023];
+    __syncthreads();
+  }
+  if (t == 0) off[n] = carry;
+}
+
+__global__ void __launch_bounds__(256) k_rn_scatter(int N, int tiles_x, const float4* __restrict__ pos,
+                                                    const int4* __restrict__ box, unsigned long long* __restrict__ cur,
+                                                    unsigned long long* __restrict__ keys) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= N) return;
+  const int4 b = box[i];
+  if (b.x > b.y) return;
+  const unsigned long long key = ((unsigned long long)__float_as_uint(pos[i].z) << 32) | (unsigned int)i;   // Z > 0
+  for (int ty = b.z / RN_TILE; ty <= b.w / RN_TILE; ++ty)
+    for (int tx = b.x / RN_TILE; tx <= b.y / RN_TILE; ++tx) {
+      const unsigned long long at = atomicAdd(cur + ty * tiles_x + tx, 1ull);
+      keys[at] = key;
+    }
+}
+
+// ascending bitonic sort of s[0, n2), n2 a power of two, all 256 lanes
+__device__ __forceinline__ void rn_bitonic(unsigned long long* s, int n2) {
+  for (int k = 2; k <= n2; k <<= 1)
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      for (int q = threadIdx.x; q < (n2 >> 1); q += 256) {
+        const int a = ((q & ~(j - 1)) << 1) | (q & (j - 1)), c = a | j;
+        const unsigned long long x = s[a], y = s[c];
+        if ((x > y) == ((a & k) == 0)) {
+          s[a] = y;
+          s[c] = x;
+        }
+      }
+      __syncthreads();
+    }
+}
+
+// load m keys into LDS, pad to a power of two with ~0, sort
+__device__ __forceinline__ void rn_sort_lds(unsigned long long* s, const unsigned long long* g, int m) {
+  int n2 = 2;
+  while (n2 < m) n2 <<= 1;
+  for (int e = threadIdx.x; e < n2; e += 256) s[e] = e < m ? g[e] : ~0ull;
+  __syncthreads();
+  rn_bitonic(s, n2);
+}
+
+__global__ void __launch_bounds__(256) k_rn_tile(RnCam cam, const unsigned long long* __restrict__ off,
+                                                 unsigned long long* __restrict__ keys, unsigned long long* __restrict__ tmp,
+                                                 const float4* __restrict__ pos, const int4* __restrict__ box,
+                                                 const float* __restrict__ colors, int cstride, float* __restrict__ image,
+                                                 int* __restrict__ front_id, int* __restrict__ hit_count) {
+  __shared__ unsigned long long skey[RN_SORT_CAP];
+  __shared__ float4 spos[RN_CHUNK];
+  __shared__ int4 sbox[RN_CHUNK];
+  __shared__ int sid[RN_CHUNK];
+  const int tile = blockIdx.y * cam.tiles_x + blockIdx.x;
+  const unsigned long long base = off[tile];
+  const int n = (int)(off[tile + 1] - base);
+  unsigned long long* list = keys + base;
+  const unsigned long long* gl = list;   // the sorted list when it does not fit in LDS
+  if (n > 0 && n <= RN_SORT_CAP) {
+    rn_sort_lds(skey, list, n);
+  } else if (n > RN_SORT_CAP) {
+    // overflow path: sorted runs of RN_SORT_CAP, then pairwise merges (rank of every key in the partner run by
+    // binary search -- the keys are unique) ping-ponging between the list and the scratch
+    for (int c = 0; c < n; c += RN_SORT_CAP) {
+      const int m = min(RN_SORT_CAP, n - c);
+      rn_sort_lds(skey, list + c, m);
+      for (int e = threadIdx.x; e < m; e += 256) list[c + e] = skey[e];
+      __syncthreads();
+    }
+    unsigned long long *src = list, *dst = tmp + base;
+    for (int wdt = RN_SORT_CAP; wdt < n; wdt <<= 1) {
+      for (int e = threadIdx.x; e < n; e += 256) {
+        const int run = e / wdt, lo = run * wdt, pb = (run & ~1) * wdt;
+        const int plo = (run & 1) ? lo - wdt : lo + wdt, phi = (run & 1) ? lo : min(lo + 2 * wdt, n);
+        const unsigned long long k = src[e];
+        int a = plo, b = max(plo, phi);
+        while (a < b) {
+          const int mid = (a + b) >> 1;
+          if (src[mid] < k) a = mid + 1; else b = mid;
+        }
+        dst[pb + (e - lo) + (a - plo)] = k;
+      }
+      __syncthreads();
+      unsigned long long* t = src;
+      src = dst;
+      dst = t;
+    }
+    gl = src;
+  }
+  const bool in_lds = n <= RN_SORT_CAP;
+
+  const int j = blockIdx.x * RN_TILE + (threadIdx.x & (RN_TILE - 1));
+  const int i = blockIdx.y * RN_TILE + (threadIdx.x / RN_TILE);
+  const bool inside = i < cam.h && j < cam.w;
+  const double dx = ((double)j - cam.ccx) / cam.f, dy = ((double)i - cam.ccy) / cam.f;
+  const double inv_dn = 1.0 / sqrt(dx * dx + dy * dy + 1.0);
+  const double zspan = cam.zf - cam.zn;
+  int nh = 0, first = -1;
+  double zt_max = 0.0, sw = 0.0, s0 = 0.0, s1 = 0.0, s2 = 0.0;
+  bool active = inside;
+  for (int c0 = 0; c0 < n; c0 += RN_CHUNK) {
+    const int m = min(RN_CHUNK, n - c0);
+    if (threadIdx.x < m) {
+      const unsigned long long k = in_lds ? skey[c0 + threadIdx.x] : gl[c0 + threadIdx.x];
+      const int id = (int)(unsigned int)k;
+      sid[threadIdx.x] = id;
+      spos[threadIdx.x] = pos[id];
+      sbox[threadIdx.x] = box[id];
+    }
+    __syncthreads();
+    if (active) {
+      for (int e = 0; e < m; ++e) {
+        const int4 b = sbox[e];
+        if (j < b.x || j > b.y || i < b.z || i > b.w) continue;
+        const float4 p = spos[e];
+        const double X = p.x, Y = p.y, Z = p.z;
+        // |P x d| / |d| with d = (dx, dy, 1)
+        const double cx = Y - Z * dy, cy = Z * dx - X, cz = X * dy - Y * dx;
+        const double rho = sqrt(cx * cx + cy * cy + cz * cz) * inv_dn;
+        if (!(rho < cam.r)) continue;
+        const double zt = (cam.zf - Z) / zspan;
+        const int id = sid[e];
+        if (nh == 0) {
+          zt_max = zt;
+          first = id;
+        }
+        const double wk = (1.0 - rho / cam.r) * exp((zt - zt_max) / cam.gamma);
+        const float* c = colors + (size_t)id * cstride;
+        sw += wk;
+        s0 += wk * (double)c[0];
+        s1 += wk * (double)c[1];
+        s2 += wk * (double)c[2];
+        if (++nh == cam.n_track) {
+          active = false;
+          break;
+        }
+      }
+    }
+    if (!__syncthreads_or(active && c0 + RN_CHUNK < n)) break;
+  }
+  if (!inside) return;
+  const size_t px = (size_t)i * cam.w + j;
+  float o0 = cam.bg0, o1 = cam.bg1, o2 = cam.bg2;
+  if (nh > 0) {
+    const double wbg = exp((cam.eps - zt_max) / cam.gamma), den = sw + wbg;
+    o0 = (float)((s0 + wbg * (double)cam.bg0) / den);
+    o1 = (float)((s1 + wbg * (double)cam.bg1) / den);
+    o2 = (float)((s2 + wbg * (double)cam.bg2) / den);
+  }
+  image[3 * px] = o0;
+  image[3 * px + 1] = o1;
+  image[3 * px + 2] = o2;
+  if (front_id) front_id[px] = first;
+  if (hit_count) hit_count[px] = nh;
+}
+
+int rfail(int code, const char* msg) {
+  slm_set_error_text(msg);
+  return code;
+}
+
+#define RNCHK(expr)                                                                   \
+  do {                                                                                \
+    hipError_t e_ = (expr);                                                           \
+    if (e_ != hipSuccess) {                                                           \
+      slm_set_error_text((std::string(#expr) + ": " + hipGetErrorString(e_)).c_str()); \
+      return SLM_ERR_HIP;                                                             \
+    }                                                                                 \
+  } while (0)
+
+int rn_tiles_x(int w) { return (w + RN_TILE - 1) / RN_TILE; }
+
+int render_common(slm_render* r, const slm_render_params* p, int N, int src, const void* pts, GfSlot* gslot,
+                  const float* colors, int cstride, float* image, int32_t* front_id, int32_t* hit_count, void* stream,
+                  const char* who) {
+  std::string w(who);
+  if (!r || !p || !image) return rfail(SLM_ERR_INVALID, (w + ": null argument").c_str());
+  if (p->width < 1 || p->height < 1 || p->width > r->W || p->height > r->H)
+    return rfail(SLM_ERR_INVALID, (w + ": image size outside the context's H x W").c_str());
+  if (p->n_track < 1 || p->n_track > SLM_RENDER_MAX_TRACK) return rfail(SLM_ERR_INVALID, (w + ": n_track must be 1..64").c_str());
+  if (!(p->focal > 0.0) || !(p->radius > 0.0) || !(p->gamma > 0.0) || !(p->z_near > 0.0) || !(p->z_far > p->z_near) ||
+      !std::isfinite(p->focal) || !std::isfinite(p->ccx) || !std::isfinite(p->ccy) || !std::isfinite(p->z_far) ||
+      !std::isfinite(p->radius) || !std::isfinite(p->bg_eps))
+    return rfail(SLM_ERR_INVALID, (w + ": bad camera or blend parameters").c_str());
+  if (N < 0 || N > r->cap) return rfail(SLM_ERR_INVALID, (w + ": more points than the context holds").c_str());
+  if (N > 0 && ((src != RN_SRC_GF && !pts) || !colors || cstride < 3))
+    return rfail(SLM_ERR_INVALID, (w + ": null points / colours or color_stride < 3").c_str());
+  hipStream_t st = (hipStream_t)stream;
+  RnCam cam;
+  cam.w = p->width;
+  cam.h = p->height;
+  cam.tiles_x = rn_tiles_x(p->width);
+  cam.n_track = p->n_track;
+  cam.f = p->focal;
+  cam.ccx = p->ccx;
+  cam.ccy = p->ccy;
+  cam.r = p->radius;
+  cam.zn = p->z_near;
+  cam.zf = p->z_far;
+  cam.gamma = p->gamma;
+  cam.eps = p->bg_eps;
+  cam.bg0 = p->bg[0];
+  cam.bg1 = p->bg[1];
+  cam.bg2 = p->bg[2];
+  const int tiles_y = (p->height + RN_TILE - 1) / RN_TILE, tiles = cam.tiles_x * tiles_y;
+  RNCHK(hipMemsetAsync(r->cnt, 0, sizeof(unsigned int) * tiles, st));
+  const dim3 gp((N + 255) / 256);
+  if (N > 0) {
+    if (src == RN_SRC_F32)
+      hipLaunchKernelGGL(k_rn_project<RN_SRC_F32>, gp, dim3(256), 0, st, N, pts, gslot, cam, r->pos, r->box, r->cnt);
+    else if (src == RN_SRC_F64)
+      hipLaunchKernelGGL(k_rn_project<RN_SRC_F64>, gp, dim3(256), 0, st, N, pts, gslot, cam, r->pos, r->box, r->cnt);
+    else
+      hipLaunchKernelGGL(k_rn_project<RN_SRC_GF>, gp, dim3(256), 0, st, N, pts, gslot, cam, r->pos, r->box, r->cnt);
+  }
+  hipLaunchKernelGGL(k_rn_scan, dim3(1), dim3(1024), 0, st, tiles, r->cnt, r->off, r->cur);
+  RNCHK(hipGetLastError());
+  RNCHK(hipMemcpyAsync(r->h_total, r->off + tiles, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+  RNCHK(hipStreamSynchronize(st));
+  const unsigned long long total = *r->h_total;
+  if (total > (1ull << 31)) return rfail(SLM_ERR_UNSUPPORTED, (w + ": more than 2^31 tile entries").c_str());
+  if (total > r->cap_keys) {
+    if (r->keys) RNCHK(hipFree(r->keys));
+    if (r->tmp) RNCHK(hipFree(r->tmp));
+    r->keys = r->tmp = nullptr;
+    r->cap_keys = 0;
+    const size_t c = (size_t)total + total / 4 + 1024;
+    RNCHK(hipMalloc((void**)&r->keys, sizeof(unsigned long long) * c));
+    RNCHK(hipMalloc((void**)&r->tmp, sizeof(unsigned long long) * c));
+    r->cap_keys = c;
+  }
+  if (total > 0)
+    hipLaunchKernelGGL(k_rn_scatter, gp, dim3(256), 0, st, N, cam.tiles_x, r->pos, r->box, r->cur, r->keys);
+  hipLaunchKernelGGL(k_rn_tile, dim3(cam.tiles_x, tiles_y), dim3(256), 0, st, cam, r->off, r->keys, r->tmp, r->pos, r->box,
+                     colors, cstride, image, front_id, hit_count);
+  RNCHK(hipGetLastError());
+  return SLM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int slm_render_create(int32_t H, int32_t W, int32_t max_points, slm_render** out) {
+  if (!out || H < 1 || W < 1 || max_points < 0) return rfail(SLM_ERR_INVALID, "slm_render_create: bad argument");
+  if (slm_device_count() < 1) return rfail(SLM_ERR_NO_DEVICE, "slm_render_create: no HIP device visible");
+  slm_render* r = new slm_render();
+  r->H = H;
+  r->W = W;
+  r->cap = max_points;
+  const size_t cap = (size_t)max_points + 1, tiles = (size_t)rn_tiles_x(W) * ((H + RN_TILE - 1) / RN_TILE);
+  hipError_t e = hipMalloc((void**)&r->pos, sizeof(float4) * cap);
+  if (e == hipSuccess) e = hipMalloc((void**)&r->box, sizeof(int4) * cap);
+  if (e == hipSuccess) e = hipMalloc((void**)&r->cnt, sizeof(unsigned int) * tiles);
+  if (e == hipSuccess) e = hipMalloc((void**)&r->off, sizeof(unsigned long long) * (tiles + 1));
+  if (e == hipSuccess) e = hipMalloc((void**)&r->cur, sizeof(unsigned long long) * tiles);
+  if (e == hipSuccess) e = hipHostMalloc((void**)&r->h_total, sizeof(unsigned long long), hipHostMallocDefault);
+  if (e != hipSuccess) {
+    slm_set_error_text((std::string("slm_render_create: ") + hipGetErrorString(e)).c_str());
+    slm_render_destroy(r);
+    return SLM_ERR_HIP;
+  }
+  *out = r;
+  return SLM_OK;
+}
+
+int slm_render_destroy(slm_render* r) {
+  if (!r) return SLM_OK;
+  void* ptrs[] = {r->pos, r->box, r->cnt, r->off, r->cur, r->keys, r->tmp};
+  for (void* q : ptrs)
+    if (q) (void)hipFree(q);
+  if (r->h_total) (void)hipHostFree(r->h_total);
+  delete r;
+  return SLM_OK;
+}
+
+int slm_render_points(slm_render* r, const slm_render_params* p, int32_t N, const void* points, const float* colors,
+                      int32_t color_stride, float* image, int32_t* front_id, int32_t* hit_count, void* stream) {
+  if (!p) return rfail(SLM_ERR_INVALID, "slm_render_points: null argument");
+  return render_common(r, p, N, p->points_f64 ? RN_SRC_F64 : RN_SRC_F32, points, nullptr, colors, color_stride, image,
+                       front_id, hit_count, stream, "slm_render_points");
+}
+
+int slm_gf_render(slm_gf* g, int32_t slot, slm_render* r, const slm_render_params* p, const float* colors,
+                  int32_t color_stride, float* image, int32_t* front_id, int32_t* hit_count, void* stream) {
+  GfSlot* dev = nullptr;
+  int32_t n = 0;
+  const int rc = gf_render_slot(g, slot, &dev, &n);
+  if (rc != SLM_OK) return rc;
+  return render_common(r, p, n, RN_SRC_GF, nullptr, dev, colors, color_stride, image, front_id, hit_count, stream,
+                       "slm_gf_render");
+}
+
+}  // extern "C"

@@ -36,6 +36,7 @@ EXPORTS = [
     "slm_gf_get_deform", "slm_gf_loss_grad", "slm_apply_update_gf",
     "slm_apply_update_f64", "slm_apply_update_gf_f64", "slm_debug_read", "slm_debug_dag_trace",
     "slm_abi_version", "slm_abi_check", "slm_debug_dag_timeout", "slm_debug_dag_abort", "slm_prepare_model", "slm_discard_prepared", "slm_debug_read_plan",
+    "slm_render_create", "slm_render_destroy", "slm_render_points", "slm_gf_render",
 ]
 
 
@@ -137,6 +138,16 @@ class SlmGraphOutputs(C.Structure):
                 ("triangles", C.c_void_p), ("triangles_areas", C.c_void_p)]
 
 
+SLM_RENDER_MAX_TRACK = 64   # include/super_lm.h
+
+
+class SlmRenderParams(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("n_track", C.c_int32), ("points_f64", C.c_int32),
+                ("focal", C.c_double), ("ccx", C.c_double), ("ccy", C.c_double), ("radius", C.c_double),
+                ("z_near", C.c_double), ("z_far", C.c_double), ("gamma", C.c_double), ("bg_eps", C.c_double),
+                ("bg", C.c_float * 3), ("pad", C.c_int32)]
+
+
 class SlmIterRecord(C.Structure):
     _fields_ = [("loss", C.c_double), ("u", C.c_double), ("accepted", C.c_int32),
                 ("status", C.c_int32), ("M_grad", C.c_int32), ("M_loss", C.c_int32)]
@@ -234,6 +245,10 @@ def load():
         "slm_depth_destroy": [vp],
         "slm_depth_preprocess": [vp, C.POINTER(SlmDepthConfig), C.POINTER(SlmDepthInputs),
                                  C.POINTER(SlmDepthOutputs), C.POINTER(C.c_int32), vp],
+        "slm_render_create": [i32, i32, i32, C.POINTER(vp)],
+        "slm_render_destroy": [vp],
+        "slm_render_points": [vp, C.POINTER(SlmRenderParams), i32, vp, vp, i32, vp, vp, vp, vp],
+        "slm_gf_render": [vp, i32, vp, C.POINTER(SlmRenderParams), vp, i32, vp, vp, vp, vp],
         "slm_gf_get_deform": [vp, i32, vp, vp],
         "slm_gf_loss_grad": [vp, i32, vp, vp, vp, vp],
         "slm_apply_update_gf": [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp],

@@ -14,10 +14,14 @@ term that ``depth_model == "raft_stereo"`` switches on, ``optimizer`` in {"SGD",
 ``learning_rate``, ``num_optimize_iterations``, and the surfel-correspondence term ``sf_corr``
 (+ ``sf_corr_weight``, ``sf_corr_loss_type``): the flow network stays the caller's -- like the reference
 (deform_mesh.py:19-23,302-309) ``forward`` calls ``models.optical_flow(src.rgb, inputs[("color",0)])`` once per
-frame and hands the (1,2,H,W) flow to the library.  ``sf_corr_match_renderimg`` (flow re-inferred from the
-rendered image every iteration) and the (unused) render loss raise ``NotImplementedError``.
-The renderer call the reference makes every iteration (deform_mesh.py:294-298) only feeds those two and is
-not needed here.
+frame and hands the (1,2,H,W) flow to the library.  With ``sf_corr_match_renderimg`` (needs ``opt.renderer ==
+"pulsar"``, radius ``opt.renderer_rad``) the flow is re-inferred every iteration from the rendered deformed model
+instead (deform_mesh.py:292-305): iteration i renders the current deformed stable surfels on the device
+(slm_gf_render, super_amd.renderer's blend), calls ``models.optical_flow(render (1,3,H,W), inputs[("color",0)])``,
+binds the flow and takes one evaluation and step.  The (unused) render loss needs the renderer's backward pass and
+raises ``NotImplementedError``.  The reference also renders every iteration without that flag (the ``if True:`` at
+deform_mesh.py:294), but no output depends on that render, so this mirror does not make it: without the flag the
+path is the single ``infer_flow`` on ``src.rgb`` and one ``slm_gf_run``.
 """
 from __future__ import annotations
 
@@ -42,9 +46,17 @@ class GraphFit:
         self.lib = _lib.load()
         if not torch.cuda.is_available():
             raise _lib.SuperLMError("no HIP device visible: super_amd has no CPU fallback")
-        for flag in ("sf_corr_match_renderimg", "render_loss"):
-            if getattr(opt, flag, False) and (flag == "render_loss" or getattr(opt, "sf_corr", False)):
-                raise NotImplementedError(f"super_amd.GraphFit: opt.{flag} is not supported")
+        if getattr(opt, "render_loss", False):
+            raise NotImplementedError("super_amd.GraphFit: opt.render_loss is not supported")
+        self.match_render = bool(getattr(opt, "sf_corr", False) and getattr(opt, "sf_corr_match_renderimg", False))
+        if self.match_render:
+            # the reference renders with models.renderer, which InitNets only builds for opt.renderer == "pulsar"
+            if getattr(opt, "renderer", None) != "pulsar":
+                raise NotImplementedError("super_amd.GraphFit: opt.sf_corr_match_renderimg renders with opt.renderer; "
+                                          f"only 'pulsar' is implemented (got {getattr(opt, 'renderer', None)!r})")
+            if shard_surfels or world is not None:
+                raise NotImplementedError("super_amd.GraphFit: opt.sf_corr_match_renderimg on surfel-sharded frames")
+        self._render_ctx = None
         self.valid_margin = 1
         self.optim = opt.optimizer
         self.Niter = opt.num_optimize_iterations
@@ -110,7 +122,7 @@ class GraphFit:
             flow = flow[-1]
         return flow.detach()
 
-    def _bind(self, slot, inputs, src, trg, models=None, flow=None):
+    def _bind(self, slot, inputs, src, trg, models=None, flow=None, defer_flow=False):
         new_data = trg
         if not hasattr(trg, "valid"):            # not read on this path
             trg = type("T", (), {})()
@@ -170,7 +182,7 @@ class GraphFit:
             _lib.check(self.lib.slm_gf_bind_semantic(self.h, slot, C.byref(sem), counts, _stream_ptr(dev)),
                        "slm_gf_bind_semantic")
             self.edge_counts = list(counts)[:nc]
-        if self.cfg.corr_mode:
+        if self.cfg.corr_mode and not defer_flow:
             if flow is None:
                 if models is None or not hasattr(models, "optical_flow"):
                     raise ValueError("opt.sf_corr needs models.optical_flow (or flow=...)")   # the reference asserts
@@ -188,6 +200,8 @@ class GraphFit:
         """(reference ``deform_mesh.py:232-247``) returns deform_verts (J+1,7) float64."""
         if getattr(self.opt, "deform_udpate_method", "super_edg") != "super_edg":
             raise NotImplementedError("only deform_udpate_method == 'super_edg'")
+        if self.match_render:
+            return self._forward_match_render(inputs, src, trg, models)
         bf = self._bind(0, inputs, src, trg, models)
         st = _stream_ptr(bf.device)
         if self.sharded:
@@ -206,6 +220,46 @@ class GraphFit:
         return out
 
     __call__ = forward
+
+    def _forward_match_render(self, inputs, src, trg, models):
+        """deform_mesh.py:286-330 with sf_corr_match_renderimg: per iteration render -> flow -> bind -> step."""
+        if models is None or not hasattr(models, "optical_flow"):
+            raise ValueError("opt.sf_corr needs models.optical_flow")   # the reference asserts
+        bf = self._bind(0, inputs, src, trg, models, defer_flow=True)
+        colors = src.colors.detach().to(device=bf.device, dtype=torch.float32).contiguous()   # bound once per frame
+        self._keep[0].append(colors)
+        for _ in range(int(self.Niter)):
+            img = self.render_deformed(inputs, colors)
+            self.flow = self.infer_flow(models, img, inputs[("color", 0)])
+            self._bind_flow(bf, self.flow)
+            self.eval_morph()
+            self.eval_losses()
+            self.step()
+        return self.deform_verts()
+
+    def _bind_flow(self, bf, flow):
+        fl = _as(flow, torch.float32, bf.device)
+        if tuple(fl.shape) != (1, 2, bf.c.H, bf.c.W):
+            raise ValueError(f"flow must be (1,2,{bf.c.H},{bf.c.W}), got {tuple(fl.shape)}")
+        self._keep[0].append(fl)         # read by the next evaluation
+        _lib.check(self.lib.slm_gf_bind_flow(self.h, 0, _dev_ptr(fl), _stream_ptr(bf.device)), "slm_gf_bind_flow")
+
+    def render_deformed(self, inputs, colors):
+        """The current deformed stable surfels of the bound frame (deform_source's new_data, global row included)
+        rendered like ``models.renderer(inputs, new_data, rad=opt.renderer_rad)``: (1,3,H,W) float32, permuted
+        like the reference (deform_mesh.py:295-298).  ``colors`` (N,3) float32 is indexed by surfel row."""
+        from .renderer import DEFAULT_RAD, RenderContext, render_params
+        bf = self._keep[0][0]
+        H, W = bf.c.H, bf.c.W
+        if self._render_ctx is None or self._render_ctx.H < H or self._render_ctx.W < W:
+            self._render_ctx = RenderContext(H, W)
+        ctx = self._render_ctx
+        ctx.reserve(bf.c.N)
+        p = render_params(inputs["K"], H, W, 1.0, getattr(self.opt, "renderer_rad", DEFAULT_RAD))
+        img = torch.empty((p.height, p.width, 3), dtype=torch.float32, device=bf.device)
+        _lib.check(self.lib.slm_gf_render(self.h, 0, ctx.h, C.byref(p), _dev_ptr(colors), int(colors.stride(0)),
+                                          _dev_ptr(img), None, None, _stream_ptr(bf.device)), "slm_gf_render")
+        return img.permute(2, 0, 1).unsqueeze(0)
 
     # ---- stepwise evaluation (surfel-sharded frames; also usable with world == 1) -------------
     def _st(self):

@@ -1,0 +1,87 @@
+"""Timing: one surfel render (slm_render_points) at 480x640 for 300 k make_scene surfels at the default radius
+(opt.renderer_rad = 2e-4) and at 10x, and one GraphFit frame (10 SGD iterations, sf_corr) with and without
+sf_corr_match_renderimg, the flow network an identity stand-in (returns a zero flow at once).
+
+    python tools/time_render.py [--reps 30] [--out gpu_out.json]
+
+HIP events around each call after warm-up; median and maximum over --reps runs.  A render synchronises once
+inside (the tile-list total is read back), so a timed call includes that round trip.  Kernel times: run it under
+``rocprofv3 --kernel-trace --stats -- python tools/time_render.py``."""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "python-super_amd"), os.path.join(ROOT, "tests")):
+    sys.path.insert(0, p)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+
+def _time(fn, reps, warm=3):
+    for _ in range(warm):
+        fn()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        ts.append(a.elapsed_time(b) * 1e3)
+    return {"median_us": float(np.median(ts)), "max_us": float(np.max(ts)), "reps": reps}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=30)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    from types import SimpleNamespace
+
+    from helpers import torch_frame
+    from oracle import graphfit_oracle as gfo
+    from super_amd import synth
+    from super_amd.deform_mesh import GraphFit
+    from super_amd.renderer import Pulsar
+
+    res = {}
+    sc = synth.make_scene(N=300_000, J=512, H=480, W=640, seed=5, src_border=2)
+    pts = torch.from_numpy(sc.sf_points).cuda()
+    cols = torch.from_numpy(np.random.default_rng(2).uniform(size=(sc.N, 3)).astype(np.float32)).cuda()
+    inputs = {"K": torch.from_numpy(sc.K).float()[None].cuda(), ("color", 0): torch.zeros(1, 3, sc.H, sc.W, device="cuda")}
+    r = Pulsar(SimpleNamespace(height=sc.H, width=sc.W))
+    data = SimpleNamespace(points=pts, colors=cols)
+    for name, rad in (("render_rad2e-4", 2e-4), ("render_rad2e-3", 2e-3)):
+        res[name] = _time(lambda: r(inputs, data, rad=rad), a.reps)
+        _, _, cnt = r.render(inputs, data, rad=rad, with_info=True)
+        res[name]["pixels_hit"] = float((cnt > 0).float().mean())
+        res[name]["hits_per_pixel_max"] = int(cnt.max())
+    res["render_points"] = sc.N
+    # algorithmic bytes: positions (f64) + colours read, one 8-byte key per tile entry written and read, image written
+    res["algorithmic_bytes_rad2e-4"] = sc.N * (24 + 12) + sc.H * sc.W * 12
+
+    gsc = synth.make_scene(seed=0, **synth.WORKLOADS["C2"])
+    sf, ginputs, new_data = torch_frame(gsc)
+    sf.colors = torch.rand(gsc.N, 3, device="cuda", generator=torch.Generator("cuda").manual_seed(1))
+    sf.rgb = torch.zeros(1, 3, gsc.H, gsc.W, device="cuda")
+    zero = torch.zeros(1, 2, gsc.H, gsc.W, device="cuda")
+    models = SimpleNamespace(optical_flow=lambda x, y: zero)
+    for name, flag in (("graphfit_corr", False), ("graphfit_corr_match_renderimg", True)):
+        opt = gfo.default_opt(sf_corr=True, sf_corr_weight=0.05, sf_corr_match_renderimg=flag, renderer="pulsar",
+                              renderer_rad=2e-4)
+        opt.deform_udpate_method = "super_edg"
+        gf = GraphFit(opt)
+        res[name] = _time(lambda: gf(ginputs, sf, new_data, models), max(5, a.reps // 3))
+    res["graphfit_surfels"] = gsc.N
+    print(json.dumps(res, indent=1))
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
