@@ -124,10 +124,11 @@ typedef struct slm_frame {
   int32_t K_ED;             /* node->node neighbours (opt.num_ED_neighbors), 1..8 */
   float fx, fy, cx, cy;     /* inputs["K"][0] entries [0,0],[1,1],[0,2],[1,2] (float32 like the reference) */
   const void* sf_points;      /* device (N,3)      sf.points            float32, or float64 with state_f64 */
-  const int32_t* sf_knn_idx;  /* device (N,K)      sf.knn_indices */
+  const int32_t* sf_knn_idx;  /* device (N,K)      sf.knn_indices: a row holds K DISTINCT ids in [0, J), so J >= K (a top-k in
+                              * the reference); the binds refuse any other table with SLM_ERR_INVALID */
   const void* sf_knn_w;       /* device (N,K)      sf.knn_w             float32 / float64 */
   const void* ed_points;      /* device (J,3)      sf.ED_nodes.points   float32 / float64 */
-  const int32_t* ed_knn_idx;  /* device (J,K_ED)   sf.ED_nodes.knn_indices */
+  const int32_t* ed_knn_idx;  /* device (J,K_ED)   sf.ED_nodes.knn_indices: ids in [0, J) (refused otherwise) */
   const float* tgt_points;    /* device (T,3)      new_data.points */
   const float* tgt_norms;     /* device (T,3)      new_data.norms */
   const int32_t* index_map;   /* device (H,W)      new_data.index_map, -1 = invalid */
@@ -157,8 +158,9 @@ int slm_device_count(void);
 /* Binds device pointers to `slot`, builds the frame's assembly plan (tuple-sorted surfel copies, coupled node pairs)
  * and the symbolic plan of the solver (kept while the coupling graph is unchanged), (re)sizes the slot's workspace and
  * resets beta to identity.  Stream-synchronising (one small device->host read when the slot's plan still applies).
- * A surfel KNN index outside [0, J) -- an IndexError in the reference, super/loss.py:189-197 -- is found on the device
- * and refused on every data path: SLM_ERR_INVALID, nothing was read out of bounds.  A bind that fails leaves the slot UNBOUND (slm_run
+ * A KNN index outside [0, J) -- an IndexError in the reference, super/loss.py:189-197 -- in sf_knn_idx or ed_knn_idx, a
+ * surfel row of sf_knn_idx that repeats an id, or J < K with N > 0 (the reference's top-k gives neither) is found and
+ * refused on every data path: SLM_ERR_INVALID, nothing was read out of bounds.  A bind that fails leaves the slot UNBOUND (slm_run
  * and friends return SLM_ERR_UNBOUND for it) until a later bind succeeds. */
 int slm_bind_frame(slm_solver* s, int32_t slot, const slm_frame* frame, void* stream);
 /* The same for the n_frames frames of a batch, slots [first_slot, first_slot + n_frames), `frames` an array in
@@ -388,7 +390,9 @@ typedef struct slm_gf_semantic {
 
 int slm_gf_create(const slm_gf_config* cfg, slm_gf** out);
 int slm_gf_destroy(slm_gf* g);
-/* Binds device pointers to `slot` and resets deform_verts to identity, optimiser state to 0. */
+/* Binds device pointers to `slot` and resets deform_verts to identity, optimiser state to 0.  The KNN tables are
+ * checked as slm_bind_frame checks them (distinct sf_knn_idx ids per row, every id in [0, J), J >= K): SLM_ERR_INVALID
+ * and an unbound slot otherwise.  Stream-synchronising. */
 int slm_gf_bind_frame(slm_gf* g, int32_t slot, const slm_gf_frame* frame, void* stream);
 /* After slm_gf_bind_frame: binds the semantic inputs of the slot and extracts, per class, the
  * class-boundary pixels of img_seg in row-major order (find_edge_region with kernel 3 +

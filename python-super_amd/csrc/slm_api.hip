@@ -80,6 +80,9 @@ static int fail(int code, const char* msg) {
   g_err = msg;
   return code;
 }
+// what the reference could never have been given (its KNN ids come from a top-k: distinct and inside [0, J))
+static const char* const kBadKnn =
+    "slm_bind_frame: a KNN index (sf_knn_idx or ed_knn_idx) lies outside [0, J) or a surfel's row of sf_knn_idx repeats an id";
 
 // other translation units (slm_gf.hip) report through the same slm_last_error()
 void slm_set_error_text(const char* msg) { g_err = msg; }
@@ -524,10 +527,10 @@ int slm_create(const slm_config* cfg, slm_solver** out) {
   }
   hipError_t e = hipMalloc((void**)&s->frames_dev, sizeof(FrameDev) * cfg->max_frames);
   if (e == hipSuccess) e = hipMemset(s->frames_dev, 0, sizeof(FrameDev) * cfg->max_frames);
-  if (e == hipSuccess) e = hipMalloc((void**)&s->bw_dev, sizeof(int));
+  if (e == hipSuccess) e = hipMalloc((void**)&s->bw_dev, 2 * sizeof(int));   // {half-bandwidth, bad KNN table}
   if (e == hipSuccess) e = hipMalloc((void**)&s->reuse_dev, sizeof(int) * cfg->max_frames);
   if (e == hipSuccess) e = hipMemset(s->reuse_dev, 0, sizeof(int) * cfg->max_frames);
-  if (e == hipSuccess) e = hipHostMalloc((void**)&s->bw_host, sizeof(int), hipHostMallocDefault);
+  if (e == hipSuccess) e = hipHostMalloc((void**)&s->bw_host, 2 * sizeof(int), hipHostMallocDefault);
   if (e == hipSuccess) {
     s->prep = prep_create();
     if (!s->prep) e = hipErrorOutOfMemory;
@@ -613,14 +616,15 @@ int slm_destroy(slm_solver* s) {
 }
 
 // Block-banded path on demand: tile half-bandwidth of the normal matrix from the KNN tables (one
-// 4-byte read-back), band + diagonal-inverse storage, refreshed device copy of the slot.
+// 8-byte read-back, with the tables' check), band + diagonal-inverse storage, refreshed device copy of the slot.
 static int ensure_band(slm_solver* s, int slot, hipStream_t st) {
   Slot& sl = s->slots[slot];
   if (sl.band_ready) return SLM_OK;
   FrameDev& h = sl.h;
   launch_bandwidth(h.f, s->bw_dev, st);
-  HIPCHK(hipMemcpyAsync(s->bw_host, s->bw_dev, sizeof(int), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(s->bw_host, s->bw_dev, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
+  if (s->bw_host[1]) return fail(SLM_ERR_INVALID, kBadKnn);
   int wb = *s->bw_host;
   if (wb > h.nt - 1) wb = h.nt - 1;
   h.wb = wb;
@@ -677,6 +681,8 @@ static int bind_model_part(slm_solver* s, int32_t slot, const slm_frame* f, hipS
   if (f->K_ED < 1 || f->K_ED > SLM_MAX_KED)
     return fail(SLM_ERR_UNSUPPORTED, "slm_bind_frame: num_ED_neighbors must be in 1..8");
   if (f->N < 0 || f->J < 1) return fail(SLM_ERR_INVALID, "slm_bind_frame: bad sizes");
+  if (f->N > 0 && f->J < f->K)   // (the reference's top-k of K among J nodes raises; the device checks below assume J >= K)
+    return fail(SLM_ERR_INVALID, "slm_bind_frame: fewer nodes (J) than num_neighbors: sf_knn_idx cannot hold K distinct ids");
   if ((f->N > 0 && (!f->sf_points || !f->sf_knn_idx || !f->sf_knn_w)) || !f->ed_points || !f->ed_knn_idx)
     return fail(SLM_ERR_INVALID, "slm_bind_frame: null device pointer");
   Slot& sl = s->slots[slot];
@@ -737,7 +743,7 @@ static int bind_model_part(slm_solver* s, int32_t slot, const slm_frame* f, hipS
     V1Sizes sz;
     HIPCHK(prep_v1(prep, *f, sl.plan, &sz, st));
     if (sz.bad_knn)
-      return fail(SLM_ERR_INVALID, "slm_bind_frame: a surfel KNN index (sf_knn_idx) lies outside [0, J)");
+      return fail(SLM_ERR_INVALID, kBadKnn);
     dev_knn_hash = sz.knn_hash;
     dev_graph_hash = sz.graph_hash;
     bt_mark();                                 // [1] tuple-sorted plan done (its size read-backs included)
@@ -776,7 +782,7 @@ static int bind_model_part(slm_solver* s, int32_t slot, const slm_frame* f, hipS
     PairSizes sz;
     HIPCHK(prep_pairs(prep, *f, sl.pplan, &sz, st));
     if (sz.bad_knn)
-      return fail(SLM_ERR_INVALID, "slm_bind_frame: a surfel KNN index (sf_knn_idx) lies outside [0, J)");
+      return fail(SLM_ERR_INVALID, kBadKnn);
     dev_knn_hash = sz.knn_hash;
     dev_graph_hash = sz.graph_hash;
     bt_mark();
@@ -788,10 +794,11 @@ static int bind_model_part(slm_solver* s, int32_t slot, const slm_frame* f, hipS
       h.vk_ready = 1;
     }
   } else if (s->cfg.use_data && f->N > 0) {
-    // the per-entry atomics path (data_path 1, J >= 65536) dereferences the table too: same refusal
+    // the per-entry atomics path (data_path 1, J >= 65536) dereferences the tables too: same refusal
+    // (use_data 0: ensure_band's pass over the tables checks them)
     bool bad = false;
     HIPCHK(prep_check_knn(prep, *f, &bad, st));
-    if (bad) return fail(SLM_ERR_INVALID, "slm_bind_frame: a surfel KNN index (sf_knn_idx) lies outside [0, J)");
+    if (bad) return fail(SLM_ERR_INVALID, kBadKnn);
   }
   // share of this rank when the frame is sharded over several GPUs (whole frame otherwise)
   {
@@ -1061,7 +1068,12 @@ static int bind_target_part(slm_solver* s, int32_t slot, const slm_frame* f, hip
   if (!h.nd_ready) {
     std::lock_guard<std::mutex> lock(s->band_mutex);
     int rc = ensure_band(s, slot, st);
-    if (rc) return rc;
+    if (rc) {   // (a refused table: the slot stays unbound, on the device too)
+      h.bound = 0;
+      memcpy(sl.h_pin, &h, sizeof(FrameDev));
+      (void)hipMemcpyAsync(s->frames_dev + slot, sl.h_pin, sizeof(FrameDev), hipMemcpyHostToDevice, st);
+      return rc;
+    }
   }
   launch_init_slot(s->frames_dev, slot, f->J, s->cfg, st);
   HIPCHK(hipMemsetAsync(s->reuse_dev + slot, 0, sizeof(int), st));   // a new frame: nothing to reuse
@@ -1442,17 +1454,25 @@ int enqueue_front_solve(slm_solver* s, const FrameDev* fr, int n, const BatchDim
 }
 
 // zero the fronts of slots [first, first+n) and assemble JtJ / jtl into them
-hipError_t enqueue_assemble_nd(slm_solver* s, int first, int n, const BatchDims& d, hipStream_t st) {
+// (the data term takes the same path as enqueue_lm_iteration's: tuple-sorted for K = 4, the pair records otherwise)
+int enqueue_assemble_nd(slm_solver* s, int first, int n, const BatchDims& d, hipStream_t st) {
   const FrameDev* fr = s->frames_dev + first;
+  if (s->cfg.use_data && !d.v1 && !d.vk)   // (nd_ready requires one of the two: unreachable today)
+    return fail(SLM_ERR_UNSUPPORTED, "slm_solve: a multifrontal slot without a multifrontal data path");
   launch_iter_begin_nd(fr, n, st, nullptr, -2);   // zeroes the pivot columns of the fronts of all n slots in one launch
   if (s->cfg.use_data) {
-    launch_data_eval(fr, n, kLossBlocks, s->cfg.w_data, 2, st);   // {r, c} at the current beta (clobbers the loss partials)
-    launch_data_gram(fr, n, d.max_pos, s->cfg.w_data, d.gram_variants, st);
-    launch_front_assemble(fr, n, d.max_blocks, st);
+    if (d.v1) {
+      launch_data_eval(fr, n, kLossBlocks, s->cfg.w_data, 2, st);   // {r, c} at the current beta (clobbers the loss partials)
+      launch_data_gram(fr, n, d.max_pos, s->cfg.w_data, d.gram_variants, st);
+      launch_front_assemble(fr, n, d.max_blocks, st);
+    } else {
+      launch_data_grad_pairs(fr, n, d.maxN, d.K, s->cfg.w_data, st);   // K-generic: per-pair records (zeroed, then filled)
+      launch_pair_scatter(fr, n, d.max_blocks, st);                    // records -> fronts + jtl
+    }
   }
   launch_reg_grad_nd(fr, n, d.maxP / 7, s->cfg.use_arap, s->cfg.w_arap, s->cfg.use_rot, s->cfg.w_rot, st);
   if (!s->cfg.use_arap && !s->cfg.use_rot) launch_front_load_rhs(fr, n, d.maxP, st);   // (else k_reg_grad_nd did it)
-  return hipSuccess;
+  return SLM_OK;
 }
 
 void enqueue_assemble(slm_solver* s, const FrameDev* fr, int n, const BatchDims& d, hipStream_t st) {
@@ -1898,7 +1918,8 @@ int slm_solve(slm_solver* s, int32_t slot, double u, double* delta, int32_t* sta
   const BatchDims d = dims_of(s, slot, 1);
   const FrameDev& h = s->slots[slot].h;
   if (d.nd) {
-    HIPCHK(enqueue_assemble_nd(s, slot, 1, d, st));
+    rc = enqueue_assemble_nd(s, slot, 1, d, st);
+    if (rc) return rc;
     enqueue_front_solve(s, s->frames_dev + slot, 1, d, u, st);
   } else {
     enqueue_assemble(s, s->frames_dev + slot, 1, d, st);

@@ -19,10 +19,14 @@
 // Tile half-bandwidth from the KNN tables: max over coupled node pairs (a >= b) of
 // tile(7a+6) - tile(7b).  Surfel tuples couple all pairs among their K nodes
 // (loss.py:277-288); ARAP couples (j, k) (loss.py:414-426).
+// out[1]: the tables hold a row or an index the binds refuse (knn_row_bad, an ed_knn_idx entry outside [0, J)) -- the
+// check of the frames that take no data-term preparation (use_data 0); nothing here indexes with the ids.
 __global__ void __launch_bounds__(256) k_bandwidth(slm_frame f, int* __restrict__ out) {
   int wmax = 0;
+  bool bad = false;
   const int stride = gridDim.x * blockDim.x;
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < f.N; i += stride) {
+    bad |= knn_row_bad(f.sf_knn_idx + (size_t)f.K * i, f.K, f.J);
     int lo = f.sf_knn_idx[(size_t)f.K * i], hi = lo;
     for (int k = 1; k < f.K; ++k) {   // (K = num_neighbors, any value)
       const int id = f.sf_knn_idx[(size_t)f.K * i + k];
@@ -33,9 +37,11 @@ __global__ void __launch_bounds__(256) k_bandwidth(slm_frame f, int* __restrict_
   }
   for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < f.J * f.K_ED; t += stride) {
     const int j = t / f.K_ED, k = f.ed_knn_idx[t];
+    bad |= (unsigned)k >= (unsigned)f.J;
     int lo = min(j, k), hi = max(j, k);
     wmax = max(wmax, (7 * hi + 6) / NB - (7 * lo) / NB);
   }
+  if (bad) out[1] = 1;
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) wmax = max(wmax, __shfl_down(wmax, o, 64));
   if ((threadIdx.x & 63) == 0 && wmax > 0) atomicMax(out, wmax);
@@ -253,7 +259,7 @@ void launch_dense_to_band(const FrameDev* frames_dev, const double* A, const dou
 }
 
 void launch_bandwidth(const slm_frame& f, int* out_dev, hipStream_t st) {
-  (void)hipMemsetAsync(out_dev, 0, sizeof(int), st);
+  (void)hipMemsetAsync(out_dev, 0, 2 * sizeof(int), st);
   hipLaunchKernelGGL(k_bandwidth, dim3(256), dim3(256), 0, st, f, out_dev);
 }
 

@@ -201,6 +201,30 @@ static_assert(offsetof(FrameIn, fx) == offsetof(slm_frame, fx) && offsetof(Frame
               offsetof(FrameIn, state_f64) == offsetof(slm_frame, state_f64), "FrameIn mirrors slm_frame");
 __device__ __forceinline__ const FrameIn& frame_in(const FrameDev& fd) { return reinterpret_cast<const FrameIn&>(fd.f); }
 
+// A surfel's KNN row the reference can never produce (its ids come from a top-k over the J nodes): an id outside [0, J)
+// or an id that repeats.  The binds refuse such tables; the kernels downstream assume K distinct in-range ids.
+template <int KK>
+__device__ __forceinline__ bool knn_row_bad(const int (&id)[KK], int J) {
+  bool bad = false;
+#pragma unroll
+  for (int a = 0; a < KK; ++a) {
+    bad |= (unsigned)id[a] >= (unsigned)J;
+#pragma unroll
+    for (int b = 0; b < a; ++b) bad |= id[b] == id[a];
+  }
+  return bad;
+}
+// (runtime K <= 8: the check kernels of the binds)
+__device__ __forceinline__ bool knn_row_bad(const int* __restrict__ row, int K, int J) {
+  for (int a = 0; a < K; ++a) {
+    const int x = row[a];
+    if ((unsigned)x >= (unsigned)J) return true;
+    for (int b = 0; b < a; ++b)
+      if (row[b] == x) return true;
+  }
+  return false;
+}
+
 #define SLM_SLAB_STRIDE 768
 #define SLM_WREC 56          // doubles per (workgroup, pair) record
 #define SLM_LB_MAX 96        // records a workgroup can hold in LDS

@@ -129,7 +129,7 @@ __global__ void __launch_bounds__(64) k_data_grad_pairs(const FrameDev* __restri
     if (ev.match) {
 #pragma unroll
       for (int k = 0; k < KK; ++k) {
-        int rank = 0;
+        int rank = 0;   // (canonical slot: the ids are distinct, slm_bind_frame refuses a row that repeats one)
 #pragma unroll
         for (int j = 0; j < KK; ++j) rank += (ev.id[j] < ev.id[k]) ? 1 : 0;
 #pragma unroll

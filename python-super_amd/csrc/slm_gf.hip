@@ -371,7 +371,8 @@ __global__ void __launch_bounds__(256, (EXTRA || KK > 4) ? 3 : 4) k_gf_data(GfSl
             }
             const double wk = k.w[a];
             // canonical slot of neighbour a: its rank among the surfel's node ids (two surfels with the same neighbour SET
-            // have the same node in every slot, whatever the distance order of their KNN lists)
+            // have the same node in every slot, whatever the distance order of their KNN lists; the ids are distinct:
+            // slm_gf_bind_frame refuses a row that repeats one)
             int rank = 0;
 #pragma unroll
             for (int b2 = 0; b2 < KK; ++b2) rank += (k.id[b2] < k.id[a]) ? 1 : 0;
@@ -620,6 +621,15 @@ __global__ void k_gf_advance(GfSlot* __restrict__ slots, int inc) {
   if (s.bound && threadIdx.x == 0) s.step += inc;
 }
 
+// slm_gf_bind_frame's test of the KNN tables (knn_row_bad for every surfel row, the range of every ed_knn_idx entry):
+// *bad = 1 when the frame must be refused.  Reads the tables only.
+__global__ void __launch_bounds__(256) k_gf_check_knn(int N, int K, int J, const int* __restrict__ knn, int n_ed,
+                                                       const int* __restrict__ ed_knn, int* __restrict__ bad) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < N && knn_row_bad(knn + (size_t)K * i, K, J)) *bad = 1;
+  if (i < n_ed && (unsigned)ed_knn[i] >= (unsigned)J) *bad = 1;
+}
+
 __global__ void __launch_bounds__(256) k_gf_init(GfSlot* __restrict__ slots, int slot) {
   GfSlotDev& s = gf_dev(slots)[slot];
   const int n = (s.f.base.J + 1) * 7;
@@ -723,6 +733,7 @@ struct slm_gf {
   std::vector<size_t> cap;
   std::vector<SemScratch> sem;
   GfSlot* dev = nullptr;
+  int* knn_bad = nullptr;    // device flag of slm_gf_bind_frame's table check
   int rank = 0, world = 1;   // surfel sharding of every slot (slm_gf_set_shard)
 };
 
@@ -811,8 +822,10 @@ int slm_gf_create(const slm_gf_config* cfg, slm_gf** out) {
   g->sem.assign(cfg->max_frames, SemScratch());
   hipError_t e = hipMalloc((void**)&g->dev, sizeof(GfSlot) * cfg->max_frames);
   if (e == hipSuccess) e = hipMemset(g->dev, 0, sizeof(GfSlot) * cfg->max_frames);
+  if (e == hipSuccess) e = hipMalloc((void**)&g->knn_bad, sizeof(int));
   if (e != hipSuccess) {
     slm_set_error_text((std::string("slm_gf_create: ") + hipGetErrorString(e)).c_str());
+    if (g->dev) (void)hipFree(g->dev);
     delete g;
     return SLM_ERR_HIP;
   }
@@ -827,6 +840,7 @@ int slm_gf_destroy(slm_gf* g) {
   }
   for (SemScratch& sc : g->sem) sem_free(sc);
   if (g->dev) (void)hipFree(g->dev);
+  if (g->knn_bad) (void)hipFree(g->knn_bad);
   delete g;
   return SLM_OK;
 }
@@ -842,6 +856,8 @@ int slm_gf_bind_frame(slm_gf* g, int32_t slot, const slm_gf_frame* fr, void* str
       !f.tgt_norms || !f.index_map || (g->cfg.use_arap && !fr->ed_knn_w) ||
       (g->cfg.use_face && (!fr->ed_triangles || !fr->ed_triangle_areas)))
     return gf_fail(SLM_ERR_INVALID, "slm_gf_bind_frame: null device pointer");
+  if (f.N > 0 && f.J < f.K)   // (the reference's top-k of K among J nodes raises)
+    return gf_fail(SLM_ERR_INVALID, "slm_gf_bind_frame: fewer nodes (J) than num_neighbors: sf_knn_idx cannot hold K distinct ids");
   hipStream_t st = (hipStream_t)stream;
   GfSlot& s = g->host[slot];
   const size_t n = (size_t)(f.J + 1) * 7;
@@ -862,8 +878,25 @@ int slm_gf_bind_frame(slm_gf* g, int32_t slot, const slm_gf_frame* fr, void* str
   s.flow = nullptr;
   s.shard_lo = (int32_t)((int64_t)f.N * g->rank / g->world);
   s.shard_hi = (int32_t)((int64_t)f.N * (g->rank + 1) / g->world);
+  // The KNN tables as the reference's top-k makes them: distinct ids in [0, J) (k_gf_data's row pass gives every id of a
+  // row an LDS slot of its own and indexes the nodes with them).  The flag comes back with the descriptor's wait below.
+  int bad_host = 0;
+  {
+    const int n_ed = f.J * f.K_ED, n_thr = n_ed > f.N ? n_ed : f.N;
+    GFCHK(hipMemsetAsync(g->knn_bad, 0, sizeof(int), st));
+    hipLaunchKernelGGL(k_gf_check_knn, dim3((unsigned)((n_thr + 255) / 256)), dim3(256), 0, st, f.N, f.K, f.J, f.sf_knn_idx, n_ed,
+                       f.ed_knn_idx, g->knn_bad);
+    GFCHK(hipMemcpyAsync(&bad_host, g->knn_bad, sizeof(int), hipMemcpyDeviceToHost, st));
+  }
   GFCHK(hipMemcpyAsync(g->dev + slot, &s, sizeof(GfSlot), hipMemcpyHostToDevice, st));
   GFCHK(hipStreamSynchronize(st));
+  if (bad_host) {   // refused: the slot stays unbound, on the device too
+    s.bound = 0;
+    GFCHK(hipMemcpyAsync(g->dev + slot, &s, sizeof(GfSlot), hipMemcpyHostToDevice, st));
+    GFCHK(hipStreamSynchronize(st));
+    return gf_fail(SLM_ERR_INVALID, "slm_gf_bind_frame: a KNN index (sf_knn_idx or ed_knn_idx) lies outside [0, J) or a "
+                                    "surfel's row of sf_knn_idx repeats an id");
+  }
   hipLaunchKernelGGL(k_gf_init, dim3((n + 255) / 256), dim3(256), 0, st, g->dev, slot);
   GFCHK(hipGetLastError());
   return SLM_OK;

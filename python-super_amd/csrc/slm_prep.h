@@ -39,7 +39,7 @@ struct V1Sizes {
   // hashes of the coupling graph, computed on the device: (J, K_ED, node KNN table) and the same continued over the
   // coupled-pair keys -- what the cached symbolic plan of a slot is compared with
   uint64_t knn_hash = 0, graph_hash = 0;
-  bool bad_knn = false;          // a surfel KNN index outside [0, J) was seen: the frame must be refused
+  bool bad_knn = false;          // a KNN index outside [0, J) or a surfel's repeated id was seen: the frame must be refused
 };
 
 // ---- K-generic pair plan (any opt.num_neighbors in 1..8; reference super/loss.py:213-220 is K-generic) ----------------
@@ -69,7 +69,7 @@ PrepBuffers* prep_create();
 void prep_destroy(PrepBuffers*);
 // Builds the plan for frame f (stream-synchronising: one small read-back, two for a plan's first frame).
 hipError_t prep_v1(PrepBuffers*, const slm_frame& f, V1Plan& plan, V1Sizes* out, hipStream_t st);
-// The range test of the surfel KNN table on its own (frames that do not take the tuple-sorted path): *bad = an index
-// outside [0, J) exists.  Stream-synchronising (one 4-byte read-back).
+// The tests of the KNN tables on their own (frames that do not take the tuple-sorted path): *bad = an index of either
+// table outside [0, J), or a surfel row with a repeated id, exists.  Stream-synchronising (one 4-byte read-back).
 hipError_t prep_check_knn(PrepBuffers*, const slm_frame& f, bool* bad, hipStream_t st);
 void plan_free(V1Plan& plan);

@@ -30,8 +30,9 @@ __device__ __forceinline__ void sort4(int& a, int& b, int& c, int& d) {
 #undef CSWAP
 }
 
-// (a node index outside [0, J) -- the reference would raise an IndexError -- is reported through *bad and clamped, so
-//  that nothing downstream reads out of bounds before the host has seen the flag)
+// (a row the reference could not produce -- a node index outside [0, J), where it would raise an IndexError, or a repeated
+//  id, which its top-k never returns -- is reported through *bad and replaced by the ids 0..3 (J >= K is checked on the
+//  host), so that nothing downstream reads out of bounds or meets a repeated id before the host has seen the flag)
 __global__ void __launch_bounds__(256) k_tuple_keys(int N, int J, const int* __restrict__ knn,
                                                      unsigned long long* __restrict__ keys,
                                                      int* __restrict__ ids, int* __restrict__ bad) {
@@ -39,9 +40,10 @@ __global__ void __launch_bounds__(256) k_tuple_keys(int N, int J, const int* __r
   if (i >= N) return;
   int4 v = *reinterpret_cast<const int4*>(knn + 4 * i);
   int a = v.x, b = v.y, c = v.z, d = v.w;
-  if ((unsigned)a >= (unsigned)J || (unsigned)b >= (unsigned)J || (unsigned)c >= (unsigned)J || (unsigned)d >= (unsigned)J) {
+  const int row[4] = {a, b, c, d};
+  if (knn_row_bad<4>(row, J)) {
     *bad = 1;
-    a = min(max(a, 0), J - 1); b = min(max(b, 0), J - 1); c = min(max(c, 0), J - 1); d = min(max(d, 0), J - 1);
+    a = 0; b = 1; c = 2; d = 3;
   }
   sort4(a, b, c, d);
   keys[i] = ((unsigned long long)a << 48) | ((unsigned long long)b << 32) |
@@ -49,12 +51,13 @@ __global__ void __launch_bounds__(256) k_tuple_keys(int N, int J, const int* __r
   ids[i] = i;
 }
 
-// the same range test on its own, for the frames that do not take the tuple-sorted path (data_path 1, J >= 65536)
-// (n = N * K table entries: any num_neighbors)
-__global__ void __launch_bounds__(256) k_check_knn(long long n, int J, const int* __restrict__ knn, int* __restrict__ bad) {
+// the same row test on its own, for the frames that do not take the tuple-sorted path (data_path 1, J >= 65536), and the
+// range test of the node KNN table (n_ed = J * K_ED entries)
+__global__ void __launch_bounds__(256) k_check_knn(int N, int K, int J, const int* __restrict__ knn, long long n_ed,
+                                                    const int* __restrict__ ed_knn, int* __restrict__ bad) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  if ((unsigned)knn[i] >= (unsigned)J) *bad = 1;
+  if (i < N && knn_row_bad(knn + (size_t)K * i, K, J)) *bad = 1;
+  if (i < n_ed && (unsigned)ed_knn[i] >= (unsigned)J) *bad = 1;
 }
 
 __global__ void __launch_bounds__(256) k_padded_counts(const int* __restrict__ d_nt,
@@ -263,14 +266,22 @@ __device__ __forceinline__ unsigned long long plan_mix(unsigned long long w, uns
   z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
   return z ^ (z >> 31);
 }
+// (also the range test of the node KNN table: an id outside [0, J) raises scal[13], the bad-KNN flag of the read-back that
+//  follows; nothing before it indexes with the table)
 __global__ void __launch_bounds__(256) k_plan_hash(int J, int K_ED, const int32_t* __restrict__ ed_knn,
-                                                    const int32_t* __restrict__ blk_key, const int* __restrict__ scal,
+                                                    const int32_t* __restrict__ blk_key, int* __restrict__ scal,
                                                     unsigned long long* __restrict__ out) {
   const int n_knn = J * K_ED, n_pairs = scal[3];
   unsigned long long h0 = 0, h1 = 0;
+  bool bad = false;
   const int tid = blockIdx.x * blockDim.x + threadIdx.x, nthr = gridDim.x * blockDim.x;
   if (tid == 0) h0 = plan_mix((unsigned long long)(unsigned)J << 32 | (unsigned)K_ED, ~0ull);
-  for (int i = tid; i < n_knn; i += nthr) h0 += plan_mix((unsigned)ed_knn[i], (unsigned long long)i);
+  for (int i = tid; i < n_knn; i += nthr) {
+    const int e = ed_knn[i];
+    bad |= (unsigned)e >= (unsigned)J;
+    h0 += plan_mix((unsigned)e, (unsigned long long)i);
+  }
+  if (bad) scal[13] = 1;
   for (int i = tid; i < n_pairs; i += nthr) h1 += plan_mix((unsigned)blk_key[i], (1ull << 40) + (unsigned long long)i);
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
@@ -292,16 +303,13 @@ __global__ void __launch_bounds__(256) k_pair_keys(int N, int J, const int* __re
   if (i >= N) return;
   constexpr int NP = KK * (KK + 1) / 2;
   int id[KK];
-  bool b = false;
 #pragma unroll
-  for (int k = 0; k < KK; ++k) {
-    id[k] = knn[(size_t)KK * i + k];
-    if ((unsigned)id[k] >= (unsigned)J) {
-      b = true;
-      id[k] = min(max(id[k], 0), J - 1);
-    }
+  for (int k = 0; k < KK; ++k) id[k] = knn[(size_t)KK * i + k];
+  if (knn_row_bad<KK>(id, J)) {   // (as k_tuple_keys: reported, and the ids 0..K-1 meanwhile -- J >= K is checked on the host)
+    *bad = 1;
+#pragma unroll
+    for (int k = 0; k < KK; ++k) id[k] = k;
   }
-  if (b) *bad = 1;
 #pragma unroll
   for (int ka = 0; ka < KK; ++ka)
 #pragma unroll
@@ -310,7 +318,7 @@ __global__ void __launch_bounds__(256) k_pair_keys(int N, int J, const int* __re
       keys[(size_t)NP * i + ka * (ka + 1) / 2 + kb] = (unsigned)a * (unsigned)J + (unsigned)c;
     }
 }
-// Canonical neighbour order of a surfel: its K node ids ascending (they are distinct).  Slot (ra, rb <= ra) of the surfel is
+// Canonical neighbour order of a surfel: its K node ids ascending (they are distinct: k_pair_keys refuses a repeated id).  Slot (ra, rb <= ra) of the surfel is
 // the pair (c[ra], c[rb]) -- the larger id first, as in the pair keys -- so two surfels with the same neighbour SET have the
 // same pair in every slot whatever the distance order of their KNN lists, and no block is ever transposed.
 template <int KK>
@@ -487,9 +495,10 @@ __global__ void __launch_bounds__(256) kb_keys(int N, int J, const int* __restri
     int4 v = *reinterpret_cast<const int4*>(knn + 4 * (size_t)i);
     int b = v.y, c = v.z, d = v.w;
     a = v.x;
-    if ((unsigned)a >= (unsigned)J || (unsigned)b >= (unsigned)J || (unsigned)c >= (unsigned)J || (unsigned)d >= (unsigned)J) {
+    const int row[4] = {a, b, c, d};
+    if (knn_row_bad<4>(row, J)) {   // (as k_tuple_keys)
       *bad = 1;
-      a = min(max(a, 0), J - 1); b = min(max(b, 0), J - 1); c = min(max(c, 0), J - 1); d = min(max(d, 0), J - 1);
+      a = 0; b = 1; c = 2; d = 3;
     }
     sort4(a, b, c, d);
     keys[i] = ((unsigned long long)a << 48) | ((unsigned long long)b << 32) | ((unsigned long long)c << 16) | (unsigned long long)d;
@@ -1081,8 +1090,9 @@ hipError_t prep_check_knn(PrepBuffers* p, const slm_frame& f, bool* bad, hipStre
   *bad = false;
   if (f.N <= 0) return hipSuccess;
   PCHK(hipMemsetAsync(p->scal + 13, 0, sizeof(int), st));
-  const long long n_ent = (long long)f.N * f.K;
-  hipLaunchKernelGGL(k_check_knn, dim3((unsigned)((n_ent + 255) / 256)), dim3(256), 0, st, n_ent, f.J, f.sf_knn_idx, p->scal + 13);
+  const long long n_ed = (long long)f.J * f.K_ED, n_thr = n_ed > f.N ? n_ed : (long long)f.N;
+  hipLaunchKernelGGL(k_check_knn, dim3((unsigned)((n_thr + 255) / 256)), dim3(256), 0, st, f.N, f.K, f.J, f.sf_knn_idx, n_ed,
+                     f.ed_knn_idx, p->scal + 13);
   PCHK(hipMemcpyAsync(p->scal_host + 13, p->scal + 13, sizeof(int), hipMemcpyDeviceToHost, st));
   PCHK(hipStreamSynchronize(st));
   *bad = p->scal_host[13] != 0;

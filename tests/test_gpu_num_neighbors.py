@@ -128,9 +128,9 @@ def test_update_and_knn_feeder_match_reference_golden(name, state):
     np.testing.assert_array_equal(sf.isStable.cpu().numpy(), g["knn_sf_stable"])
 
 
-@pytest.mark.parametrize("K", [2, 3, 5, 8])
+@pytest.mark.parametrize("K", [1, 2, 3, 5, 7, 8])
 def test_other_neighbour_counts_against_the_oracle(K):
-    """K = 2, 3, 5, 8 on a synthetic scene: three LM iterations against the (K-generic, golden-pinned) oracle."""
+    """K = 1, 2, 3, 5, 7, 8 on a synthetic scene: three LM iterations against the (K-generic, golden-pinned) oracle."""
     from super_amd import synth
     sc = synth.make_scene(N=2500, J=60, H=60, W=80, seed=20 + K, src_border=5, tgt_border=3, n_neighbors=K)
     opt = orc.default_opt(num_optimize_iterations=3)
