@@ -654,6 +654,39 @@ int slm_render_points(slm_render* r, const slm_render_params* p, int32_t N, cons
 int slm_gf_render(slm_gf* g, int32_t slot, slm_render* r, const slm_render_params* p, const float* colors,
                   int32_t color_stride, float* image, int32_t* front_id, int32_t* hit_count, void* stream);
 
+/* Renderer backward and the render loss of GraphFit (opt.render_loss, super/deform_mesh.py:113-123)
+ *   slm_render_backward   <- the gradient Pulsar's backward feeds into new_data.points   super/deform_mesh.py:115,317
+ *   slm_render_ssim_loss  <- SSIM(kernel=11) + mask + selection + weighted sum           super/deform_mesh.py:115-121,
+ *                                                                                        depth/monodepth2/layers.py:217-247
+ * slm_render_backward: dL/dP of the image of the LAST forward on `r` (slm_render_points or slm_gf_render), the exact
+ * derivative of the blend above.  With W = sum w_k + w_bg, C the float64 colour and g = dL/dC of the pixel,
+ *   dL/dP_k = sum over the pixels k takes part in of  g.(c_k - C)/W ( -(e_k/radius) drho_k/dP - w_k/(gamma (z_far - z_near)) z )
+ * with e_k = exp((zt_k - zt_max)/gamma), drho/dP = (P - (P.d)d)/rho for the pixel's unit ray d (0 at rho = 0).  Hit
+ * membership, rho < radius and the n_track cut are the forward's (discrete); zt_max cancels.  P is the float32-rounded
+ * centre and the gradient passes the rounding unchanged.  grad_image (height,width,3) float64 device; grad_points
+ * (N,3) float64 device, N the forward's point count -- for slm_gf_render surfel rows, 0 on unstable rows and on culled
+ * points.  p must equal the forward's parameters field by field.  SLM_ERR_INVALID when no forward completed on `r` or
+ * p differs.  Bitwise reproducible (no float atomics); does not synchronise. */
+int slm_render_backward(slm_render* r, const slm_render_params* p, const double* grad_image, double* grad_points,
+                        void* stream);
+/* The render loss at the image (h,w,3) float32 `image_hwc` (a render) against the target (3,h,w) float32 `target_chw`
+ * (inputs[("color",0)][0]): per channel monodepth2's SSIM with kernel 11 -- reflection padding 5, 11x11 box means of
+ * x, y, x^2, y^2, xy, C1 = 0.01^2, C2 = 0.03^2, clamp((1 - n/d)/2, 0, 1) -- then m = mean_c(SSIM_c)^2; a pixel is kept
+ * when every pixel of its border-clipped 11x11 window has all three image channels > 0 (maxpool11(-min_c x) < 0) and
+ * m < 0.1.  loss_out (device, 2 doubles) = weight sum_kept m (fixed summation order), kept pixel count.  grad_image
+ * (h,w,3) float64 device, may be NULL: dL/dimage with the mask and the selection constant and the clamp passing the
+ * gradient where 0 <= value <= 1; the target gets none.  Arithmetic is float64 on the float32 inputs (the reference
+ * runs float32).  h, w >= 6.  Allocates its scratch stream-ordered; does not synchronise. */
+int slm_render_ssim_loss(int32_t h, int32_t w, const float* image_hwc, const float* target_chw, double weight,
+                         double* loss_out, double* grad_image, void* stream);
+/* After slm_gf_bind_frame: binds dL/dP (N,3) float64 device, by surfel row, of an outside term (the render loss:
+ * slm_render_backward of an slm_gf_render).  Every later evaluation of the slot -- slm_gf_eval_losses, slm_gf_loss_grad,
+ * each iteration of slm_gf_run -- adds it to each stable surfel's dL/dP before the chain rule to the node rows and the
+ * global row (the global row's gradient is then divided by J as for every term).  The gradient belongs to the current
+ * deform_verts: bind it again before every evaluation.  NULL clears it; slm_gf_bind_frame clears it too.  The buffer
+ * is read, not copied.  Synchronises `stream`. */
+int slm_gf_bind_point_grad(slm_gf* g, int32_t slot, const double* grad_device, void* stream);
+
 /* ===================================================================================
  * "Next" row f3: ED-graph construction at frame 0
  *   slm_graph_init  <- init_graph + DirectDeformGraph (grid_mesh)   super/graph_encoder.py:11-67,128-195

@@ -139,6 +139,7 @@ __device__ __forceinline__ void gf_reg_body(GfSlotDev& s, const int bx, const Gf
 // seg_mode: 0 none, 1 hard, 2 soft semantic weight on the squared residual (loss.py:379-399);
 // pp_max > 0 (and no seg_mode): squared residuals >= pp_max are dropped (loss.py:369-370);
 // use_morph: adds the back-propagation of the morphing term prepared by k_gf_morph (2: the kept count is still in the spread partials).
+// pgrad_ (EXTRA only): per slot of the launch a bound (N,3) dL/dP or null, added where morph_g is.
 // KK = opt.num_neighbors of the launch's slots (deform_source is K-generic, super/deform_mesh.py:198-221)
 #define GF_TAB 128   // LDS gradient table: slots per workgroup (power of two)
 // EXTRA = false: the plain point-plane term only (no segmentation weight, clip, morphing or correspondence term) -- the
@@ -147,7 +148,8 @@ __device__ __forceinline__ void gf_reg_body(GfSlotDev& s, const int bx, const Gf
 template <int KK, bool EXTRA>
 __global__ void __launch_bounds__(256, (EXTRA || KK > 4) ? 3 : 4) k_gf_data(GfSlot* __restrict__ slots, int use_pp, double lam, int seg_mode_,
                                                      double pp_max_, int use_morph_, double w_morph, int corr_mode_,
-                                                     double lam_c, int n_data_blocks, GfRegArgs ra) {
+                                                     double lam_c, int n_data_blocks, GfRegArgs ra,
+                                                     const double* const* __restrict__ pgrad_) {
   const int seg_mode = EXTRA ? seg_mode_ : 0, use_morph = EXTRA ? use_morph_ : 0, corr_mode = EXTRA ? corr_mode_ : 0;
   const double pp_max = EXTRA ? pp_max_ : 0.0;
   __shared__ double sm[16];
@@ -298,6 +300,17 @@ __global__ void __launch_bounds__(256, (EXTRA || KK > 4) ? 3 : 4) k_gf_data(GfSl
         gP = {gP.x + sc * (mg.x * Pi0.x + mg.y * Pi1.x), gP.y + sc * (mg.x * Pi0.y + mg.y * Pi1.y),
               gP.z + sc * (mg.x * Pi0.z + mg.y * Pi1.z)};
         any = true;
+      }
+    }
+    if (EXTRA && pgrad_) {
+      // an outside term's dL/dP by surfel row (slm_gf_bind_point_grad: the render loss through slm_render_backward)
+      const double* pg = pgrad_[blockIdx.y];
+      if (pg) {
+        const double ax = pg[3 * (size_t)i], ay = pg[3 * (size_t)i + 1], az = pg[3 * (size_t)i + 2];
+        if (ax != 0.0 || ay != 0.0 || az != 0.0) {
+          gP = {gP.x + ax, gP.y + ay, gP.z + az};
+          any = true;
+        }
       }
     }
     if (any) {
@@ -735,6 +748,8 @@ struct slm_gf {
   GfSlot* dev = nullptr;
   int* knn_bad = nullptr;    // device flag of slm_gf_bind_frame's table check
   int rank = 0, world = 1;   // surfel sharding of every slot (slm_gf_set_shard)
+  const double** pgrad = nullptr;             // (max_frames) device: slm_gf_bind_point_grad's buffer per slot, or null
+  std::vector<const double*> pgrad_host;      // the same on the host: selects the EXTRA launch
 };
 
 #define GFCHK(expr)                                                       \
@@ -769,16 +784,19 @@ static void gf_enqueue_losses(slm_gf* g, GfSlot* slots, int n, int maxN, int max
   const bool reg = g->rank == 0 && (c.use_arap || c.use_rot || c.use_face) && maxReg > 0;
   const GfRegArgs ra = {c.use_arap, c.use_rot, c.use_face, 0, c.w_arap, c.w_rot, c.w_face};
   const int nd = (maxN + 255) / 256, nr = reg ? (maxReg + 255) / 256 : 0;
-  if (data) {
+  const int first = (int)(slots - g->dev);   // (slots of the launch: first .. first + n - 1)
+  bool pg = false;
+  for (int k = first; k < first + n; ++k) pg = pg || g->pgrad_host[k] != nullptr;
+  if (data || (pg && maxN > 0)) {
     // the node terms ride on this launch as its tail blocks
-    const bool extra = c.seg_mode || c.use_bn_morph || c.corr_mode || c.pp_max > 0.0;
+    const bool extra = c.seg_mode || c.use_bn_morph || c.corr_mode || c.pp_max > 0.0 || pg;
     if (extra) {
       GF_K_DISPATCH(g->batch_K, hipLaunchKernelGGL((k_gf_data<KK, true>), dim3(nd + nr, n), dim3(256), 0, st, slots, use_pp, c.w_data,
                                                    c.seg_mode, c.seg_mode ? 0.0 : c.pp_max, c.use_bn_morph ? (morph_in_partials ? 2 : 1) : 0, c.w_bn_morph, c.corr_mode, c.w_corr,
-                                                   nd, ra));
+                                                   nd, ra, pg ? g->pgrad + first : nullptr));
     } else {
       GF_K_DISPATCH(g->batch_K, hipLaunchKernelGGL((k_gf_data<KK, false>), dim3(nd + nr, n), dim3(256), 0, st, slots, use_pp, c.w_data,
-                                                   0, 0.0, 0, 0.0, 0, 0.0, nd, ra));
+                                                   0, 0.0, 0, 0.0, 0, 0.0, nd, ra, nullptr));
     }
   } else if (reg) {
     hipLaunchKernelGGL(k_gf_reg, dim3(nr, n), dim3(256), 0, st, slots, ra);
@@ -820,12 +838,17 @@ int slm_gf_create(const slm_gf_config* cfg, slm_gf** out) {
   g->host.assign(cfg->max_frames, GfSlot{});
   g->cap.assign(cfg->max_frames, 0);
   g->sem.assign(cfg->max_frames, SemScratch());
+  g->pgrad_host.assign(cfg->max_frames, nullptr);
   hipError_t e = hipMalloc((void**)&g->dev, sizeof(GfSlot) * cfg->max_frames);
   if (e == hipSuccess) e = hipMemset(g->dev, 0, sizeof(GfSlot) * cfg->max_frames);
   if (e == hipSuccess) e = hipMalloc((void**)&g->knn_bad, sizeof(int));
+  if (e == hipSuccess) e = hipMalloc((void**)&g->pgrad, sizeof(const double*) * cfg->max_frames);
+  if (e == hipSuccess) e = hipMemset(g->pgrad, 0, sizeof(const double*) * cfg->max_frames);
   if (e != hipSuccess) {
     slm_set_error_text((std::string("slm_gf_create: ") + hipGetErrorString(e)).c_str());
     if (g->dev) (void)hipFree(g->dev);
+    if (g->knn_bad) (void)hipFree(g->knn_bad);
+    if (g->pgrad) (void)hipFree(g->pgrad);
     delete g;
     return SLM_ERR_HIP;
   }
@@ -841,6 +864,7 @@ int slm_gf_destroy(slm_gf* g) {
   for (SemScratch& sc : g->sem) sem_free(sc);
   if (g->dev) (void)hipFree(g->dev);
   if (g->knn_bad) (void)hipFree(g->knn_bad);
+  if (g->pgrad) (void)hipFree(g->pgrad);
   delete g;
   return SLM_OK;
 }
@@ -874,8 +898,10 @@ int slm_gf_bind_frame(slm_gf* g, int32_t slot, const slm_gf_frame* fr, void* str
   s.f = *fr;
   s.bound = 1;
   s.step = 0;
-  s.sem_bound = 0;   // semantic inputs and the flow belong to the frame: bind them again
+  s.sem_bound = 0;   // semantic inputs, the flow and a point gradient belong to the frame: bind them again
   s.flow = nullptr;
+  g->pgrad_host[slot] = nullptr;
+  GFCHK(hipMemcpyAsync(g->pgrad + slot, &g->pgrad_host[slot], sizeof(const double*), hipMemcpyHostToDevice, st));
   s.shard_lo = (int32_t)((int64_t)f.N * g->rank / g->world);
   s.shard_hi = (int32_t)((int64_t)f.N * (g->rank + 1) / g->world);
   // The KNN tables as the reference's top-k makes them: distinct ids in [0, J) (k_gf_data's row pass gives every id of a
@@ -943,6 +969,17 @@ int slm_gf_bind_flow(slm_gf* g, int32_t slot, const float* flow, void* stream) {
   // the pointer alone: the device copy of the slot also holds the optimiser's step count, which the host copy does not
   // follow (sf_corr_match_renderimg binds a new flow between the iterations of one frame)
   GFCHK(hipMemcpyAsync(&g->dev[slot].flow, &s.flow, sizeof(s.flow), hipMemcpyHostToDevice, st));
+  GFCHK(hipStreamSynchronize(st));
+  return SLM_OK;
+}
+
+int slm_gf_bind_point_grad(slm_gf* g, int32_t slot, const double* grad, void* stream) {
+  if (!g) return gf_fail(SLM_ERR_INVALID, "slm_gf_bind_point_grad: null argument");
+  if (slot < 0 || slot >= (int)g->host.size()) return gf_fail(SLM_ERR_INVALID, "slm_gf_bind_point_grad: bad slot");
+  if (!g->host[slot].bound) return gf_fail(SLM_ERR_UNBOUND, "slm_gf_bind_point_grad: slm_gf_bind_frame first");
+  hipStream_t st = (hipStream_t)stream;
+  g->pgrad_host[slot] = grad;
+  GFCHK(hipMemcpyAsync(g->pgrad + slot, &g->pgrad_host[slot], sizeof(const double*), hipMemcpyHostToDevice, st));
   GFCHK(hipStreamSynchronize(st));
   return SLM_OK;
 }

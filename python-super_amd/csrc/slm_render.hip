@@ -13,7 +13,16 @@
 // The keys are unique (one per point and tile), so the sorted order -- and with it every float64 sum, taken by one
 // lane in list order -- does not depend on the order the atomic cursors handed out slots: renders are bitwise
 // reproducible.  The only atomics are integer ones (tile counts, cursors).
+//
+// Every forward leaves on the context what slm_render_backward needs: the float32 centres and pixel boxes, a copy of the
+// colours, the sorted tile lists (written back to `keys` on both sort paths) and per pixel the float64 blend (zt_max, W,
+// C) with the list position of its n_track-th hit.  The backward is two launches, store-and-sum, no float atomics:
+//   k_rn_bwd_entry  one workgroup per tile: the tile's pixel coefficients g/W, g.C/W in LDS, then per list entry the
+//                   contributions of the pixels of its box inside the tile, summed in row-major pixel order -> `slab`
+//   k_rn_bwd_point  per point: the slab entries of its tiles, found by binary search of its key, summed in tile order
+#include <climits>
 #include <cmath>
+#include <cstring>
 #include <string>
 
 #include "slm_gf.h"
@@ -35,6 +44,22 @@ struct slm_render {
   unsigned long long* tmp = nullptr;     // (cap_keys) merge scratch of the overflow path
   size_t cap_keys = 0;
   unsigned long long* h_total = nullptr; // pinned host copy of off[tiles]
+  // ---- state of the last forward, read by slm_render_backward ----
+  float4* col = nullptr;                 // (cap) colours of the points, w unused
+  struct RnPix* pix = nullptr;           // (H * W) per-pixel blend record
+  double* slab = nullptr;                // (3 cap_slab) per tile-list entry dL/dP partials
+  size_t cap_slab = 0;
+  slm_render_params last{};              // parameters of the last forward
+  int n_last = 0;                        // its point count
+  unsigned long long total_last = 0;     // its tile-list entries
+  int has_fwd = 0;                       // 1 after a forward that completed; cleared when one starts
+};
+
+// the per-pixel record of a forward: float64 blend of the taken hits, and `cut`, the list position of the n_track-th hit
+// (INT_MAX: fewer hits) -- entries behind it do not reach the pixel
+struct RnPix {
+  double zt_max, W, c0, c1, c2;
+  int cut, pad;
 };
 
 namespace {
@@ -64,10 +89,24 @@ __device__ __forceinline__ void rn_range(double c, double z, double r, double f,
   hi = min((int)floor(b), n - 1);
 }
 
+// pixel (i, j)'s ray direction d = (dx, dy, 1) and 1 / |d|
+__device__ __forceinline__ void rn_ray(const RnCam& cam, int i, int j, double& dx, double& dy, double& inv_dn) {
+  dx = ((double)j - cam.ccx) / cam.f;
+  dy = ((double)i - cam.ccy) / cam.f;
+  inv_dn = 1.0 / sqrt(dx * dx + dy * dy + 1.0);
+}
+
+// |P x d| / |d|: the one expression the forward's and the backward's coverage tests share
+__device__ __forceinline__ double rn_rho(double X, double Y, double Z, double dx, double dy, double inv_dn) {
+  const double cx = Y - Z * dy, cy = Z * dx - X, cz = X * dy - Y * dx;
+  return sqrt(cx * cx + cy * cy + cz * cz) * inv_dn;
+}
+
 template <int SRC>
 __global__ void __launch_bounds__(256) k_rn_project(int N, const void* __restrict__ pts, GfSlot* __restrict__ gslot, RnCam cam,
                                                     float4* __restrict__ pos, int4* __restrict__ box,
-                                                    unsigned int* __restrict__ cnt) {
+                                                    unsigned int* __restrict__ cnt, const float* __restrict__ colors,
+                                                    int cstride, float4* __restrict__ col) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= N) return;
   float X, Y, Z;
@@ -87,6 +126,10 @@ __global__ void __launch_bounds__(256) k_rn_project(int N, const void* __restric
       const d3 P = gf_skin_pos(s, i);
       X = (float)P.x; Y = (float)P.y; Z = (float)P.z;
     }
+  }
+  if (live) {   // the backward's copy of the colours (rows of unstable surfels are not read)
+    const float* c = colors + (size_t)i * cstride;
+    col[i] = make_float4(c[0], c[1], c[2], 0.f);
   }
   int4 b = make_int4(1, 0, 1, 0);   // empty
   if (live && (double)Z >= cam.zn && (double)Z <= cam.zf) {
@@ -177,7 +220,7 @@ __global__ void __launch_bounds__(256) k_rn_tile(RnCam cam, const unsigned long 
                                                  unsigned long long* __restrict__ keys, unsigned long long* __restrict__ tmp,
                                                  const float4* __restrict__ pos, const int4* __restrict__ box,
                                                  const float* __restrict__ colors, int cstride, float* __restrict__ image,
-                                                 int* __restrict__ front_id, int* __restrict__ hit_count) {
+                                                 int* __restrict__ front_id, int* __restrict__ hit_count, RnPix* __restrict__ pix) {
   __shared__ unsigned long long skey[RN_SORT_CAP];
   __shared__ float4 spos[RN_CHUNK];
   __shared__ int4 sbox[RN_CHUNK];
@@ -189,6 +232,7 @@ __global__ void __launch_bounds__(256) k_rn_tile(RnCam cam, const unsigned long 
   const unsigned long long* gl = list;   // the sorted list when it does not fit in LDS
   if (n > 0 && n <= RN_SORT_CAP) {
     rn_sort_lds(skey, list, n);
+    for (int e = threadIdx.x; e < n; e += 256) list[e] = skey[e];   // the backward finds its keys in the sorted list
   } else if (n > RN_SORT_CAP) {
     // overflow path: sorted runs of RN_SORT_CAP, then pairwise merges (rank of every key in the partner run by
     // binary search -- the keys are unique) ping-ponging between the list and the scratch
@@ -216,17 +260,20 @@ __global__ void __launch_bounds__(256) k_rn_tile(RnCam cam, const unsigned long 
       src = dst;
       dst = t;
     }
-    gl = src;
+    if (src != list) {   // the sorted list ends in `keys` on every path
+      for (int e = threadIdx.x; e < n; e += 256) list[e] = src[e];
+      __syncthreads();
+    }
   }
   const bool in_lds = n <= RN_SORT_CAP;
 
   const int j = blockIdx.x * RN_TILE + (threadIdx.x & (RN_TILE - 1));
   const int i = blockIdx.y * RN_TILE + (threadIdx.x / RN_TILE);
   const bool inside = i < cam.h && j < cam.w;
-  const double dx = ((double)j - cam.ccx) / cam.f, dy = ((double)i - cam.ccy) / cam.f;
-  const double inv_dn = 1.0 / sqrt(dx * dx + dy * dy + 1.0);
+  double dx, dy, inv_dn;
+  rn_ray(cam, i, j, dx, dy, inv_dn);
   const double zspan = cam.zf - cam.zn;
-  int nh = 0, first = -1;
+  int nh = 0, first = -1, cut = INT_MAX;
   double zt_max = 0.0, sw = 0.0, s0 = 0.0, s1 = 0.0, s2 = 0.0;
   bool active = inside;
   for (int c0 = 0; c0 < n; c0 += RN_CHUNK) {
@@ -245,9 +292,7 @@ __global__ void __launch_bounds__(256) k_rn_tile(RnCam cam, const unsigned long 
         if (j < b.x || j > b.y || i < b.z || i > b.w) continue;
         const float4 p = spos[e];
         const double X = p.x, Y = p.y, Z = p.z;
-        // |P x d| / |d| with d = (dx, dy, 1)
-        const double cx = Y - Z * dy, cy = Z * dx - X, cz = X * dy - Y * dx;
-        const double rho = sqrt(cx * cx + cy * cy + cz * cz) * inv_dn;
+        const double rho = rn_rho(X, Y, Z, dx, dy, inv_dn);
         if (!(rho < cam.r)) continue;
         const double zt = (cam.zf - Z) / zspan;
         const int id = sid[e];
@@ -262,6 +307,7 @@ __global__ void __launch_bounds__(256) k_rn_tile(RnCam cam, const unsigned long 
         s1 += wk * (double)c[1];
         s2 += wk * (double)c[2];
         if (++nh == cam.n_track) {
+          cut = c0 + e;
           active = false;
           break;
         }
@@ -272,17 +318,133 @@ __global__ void __launch_bounds__(256) k_rn_tile(RnCam cam, const unsigned long 
   if (!inside) return;
   const size_t px = (size_t)i * cam.w + j;
   float o0 = cam.bg0, o1 = cam.bg1, o2 = cam.bg2;
+  RnPix rec = {0.0, 0.0, 0.0, 0.0, 0.0, cut, 0};
   if (nh > 0) {
     const double wbg = exp((cam.eps - zt_max) / cam.gamma), den = sw + wbg;
-    o0 = (float)((s0 + wbg * (double)cam.bg0) / den);
-    o1 = (float)((s1 + wbg * (double)cam.bg1) / den);
-    o2 = (float)((s2 + wbg * (double)cam.bg2) / den);
+    rec.zt_max = zt_max;
+    rec.W = den;
+    rec.c0 = (s0 + wbg * (double)cam.bg0) / den;
+    rec.c1 = (s1 + wbg * (double)cam.bg1) / den;
+    rec.c2 = (s2 + wbg * (double)cam.bg2) / den;
+    o0 = (float)rec.c0;
+    o1 = (float)rec.c1;
+    o2 = (float)rec.c2;
   }
+  pix[px] = rec;
   image[3 * px] = o0;
   image[3 * px + 1] = o1;
   image[3 * px + 2] = o2;
   if (front_id) front_id[px] = first;
   if (hit_count) hit_count[px] = nh;
+}
+
+// Backward, pass 1 (see the top of the file): one workgroup per tile.  Lane t stages pixel t of the tile -- its ray and the
+// coefficients a = g / W, b = g.C / W of s_k = g.(c_k - C) / W, or cut = -1 when the pixel has no hit or g = 0 -- then every
+// lane takes list entries e = t, t + 256, ... and sums, in row-major order over the pixels of the entry's box inside the tile
+// that it reaches (position <= cut, rho < r: the forward's decisions), s_k ( -(e_k / r) drho/dP - w_k / (gamma zspan) z ).
+__global__ void __launch_bounds__(256) k_rn_bwd_entry(RnCam cam, const unsigned long long* __restrict__ off,
+                                                      const unsigned long long* __restrict__ keys, const float4* __restrict__ pos,
+                                                      const int4* __restrict__ box, const float4* __restrict__ col,
+                                                      const RnPix* __restrict__ pix, const double* __restrict__ gimg,
+                                                      double* __restrict__ slab) {
+  __shared__ double sdx[256], sdy[256], sinv[256], szt[256], sa0[256], sa1[256], sa2[256], sb[256];
+  __shared__ int scut[256];
+  const int tile = blockIdx.y * cam.tiles_x + blockIdx.x;
+  const unsigned long long base = off[tile];
+  const int n = (int)(off[tile + 1] - base);
+  if (n == 0) return;
+  const int tx0 = blockIdx.x * RN_TILE, ty0 = blockIdx.y * RN_TILE;
+  {
+    const int t = threadIdx.x, j = tx0 + (t & (RN_TILE - 1)), i = ty0 + t / RN_TILE;
+    int cut = -1;
+    if (i < cam.h && j < cam.w) {
+      const size_t px = (size_t)i * cam.w + j;
+      const RnPix rec = pix[px];
+      const double g0 = gimg[3 * px], g1 = gimg[3 * px + 1], g2 = gimg[3 * px + 2];
+      if (rec.W > 0.0 && (g0 != 0.0 || g1 != 0.0 || g2 != 0.0)) {
+        cut = rec.cut;
+        sa0[t] = g0 / rec.W;
+        sa1[t] = g1 / rec.W;
+        sa2[t] = g2 / rec.W;
+        sb[t] = (g0 * rec.c0 + g1 * rec.c1 + g2 * rec.c2) / rec.W;
+        szt[t] = rec.zt_max;
+        double dx, dy, inv_dn;
+        rn_ray(cam, i, j, dx, dy, inv_dn);
+        sdx[t] = dx;
+        sdy[t] = dy;
+        sinv[t] = inv_dn;
+      }
+    }
+    scut[t] = cut;
+  }
+  __syncthreads();
+  const double zspan = cam.zf - cam.zn, kz = 1.0 / (cam.gamma * zspan);
+  for (int e = threadIdx.x; e < n; e += 256) {
+    const int id = (int)(unsigned int)keys[base + e];
+    const int4 b = box[id];
+    const float4 p = pos[id];
+    const float4 c = col[id];
+    const double X = p.x, Y = p.y, Z = p.z;
+    const double zt = (cam.zf - Z) / zspan;
+    double gx = 0.0, gy = 0.0, gz = 0.0;
+    const int i0 = max(b.z, ty0), i1 = min(b.w, ty0 + RN_TILE - 1), j0 = max(b.x, tx0), j1 = min(b.y, tx0 + RN_TILE - 1);
+    for (int i = i0; i <= i1; ++i)
+      for (int j = j0; j <= j1; ++j) {
+        const int t = (i - ty0) * RN_TILE + (j - tx0);
+        if (e > scut[t]) continue;
+        const double dx = sdx[t], dy = sdy[t], inv_dn = sinv[t];
+        const double rho = rn_rho(X, Y, Z, dx, dy, inv_dn);
+        if (!(rho < cam.r)) continue;
+        const double ek = exp((zt - szt[t]) / cam.gamma), wk = (1.0 - rho / cam.r) * ek;
+        const double sk = sa0[t] * (double)c.x + sa1[t] * (double)c.y + sa2[t] * (double)c.z - sb[t];
+        if (rho > 0.0) {
+          // drho/dP = (P - (P.d^) d^) / rho, d^ = d / |d|
+          const double hx = dx * inv_dn, hy = dy * inv_dn, hz = inv_dn;
+          const double pd = X * hx + Y * hy + Z * hz;
+          const double q = -sk * ek / (cam.r * rho);
+          gx += q * (X - pd * hx);
+          gy += q * (Y - pd * hy);
+          gz += q * (Z - pd * hz);
+        }
+        gz -= sk * wk * kz;
+      }
+    double* o = slab + 3 * (base + e);
+    o[0] = gx;
+    o[1] = gy;
+    o[2] = gz;
+  }
+}
+
+// Backward, pass 2: per point, the slab entries of the tiles its box touches (the scatter's order), each found by binary
+// search of the point's key -- unique in its tile's sorted list.  Culled points (and unstable surfels) get 0.
+__global__ void __launch_bounds__(256) k_rn_bwd_point(int N, int tiles_x, const unsigned long long* __restrict__ off,
+                                                      const unsigned long long* __restrict__ keys, const float4* __restrict__ pos,
+                                                      const int4* __restrict__ box, const double* __restrict__ slab,
+                                                      double* __restrict__ out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= N) return;
+  const int4 b = box[i];
+  double gx = 0.0, gy = 0.0, gz = 0.0;
+  if (b.x <= b.y) {
+    const unsigned long long key = ((unsigned long long)__float_as_uint(pos[i].z) << 32) | (unsigned int)i;
+    for (int ty = b.z / RN_TILE; ty <= b.w / RN_TILE; ++ty)
+      for (int tx = b.x / RN_TILE; tx <= b.y / RN_TILE; ++tx) {
+        const int t = ty * tiles_x + tx;
+        unsigned long long lo = off[t], hi = off[t + 1];
+        while (lo < hi) {
+          const unsigned long long mid = (lo + hi) >> 1;
+          if (keys[mid] < key) lo = mid + 1; else hi = mid;
+        }
+        if (lo < off[t + 1] && keys[lo] == key) {
+          gx += slab[3 * lo];
+          gy += slab[3 * lo + 1];
+          gz += slab[3 * lo + 2];
+        }
+      }
+  }
+  out[3 * (size_t)i] = gx;
+  out[3 * (size_t)i + 1] = gy;
+  out[3 * (size_t)i + 2] = gz;
 }
 
 int rfail(int code, const char* msg) {
@@ -301,22 +463,7 @@ int rfail(int code, const char* msg) {
 
 int rn_tiles_x(int w) { return (w + RN_TILE - 1) / RN_TILE; }
 
-int render_common(slm_render* r, const slm_render_params* p, int N, int src, const void* pts, GfSlot* gslot,
-                  const float* colors, int cstride, float* image, int32_t* front_id, int32_t* hit_count, void* stream,
-                  const char* who) {
-  std::string w(who);
-  if (!r || !p || !image) return rfail(SLM_ERR_INVALID, (w + ": null argument").c_str());
-  if (p->width < 1 || p->height < 1 || p->width > r->W || p->height > r->H)
-    return rfail(SLM_ERR_INVALID, (w + ": image size outside the context's H x W").c_str());
-  if (p->n_track < 1 || p->n_track > SLM_RENDER_MAX_TRACK) return rfail(SLM_ERR_INVALID, (w + ": n_track must be 1..64").c_str());
-  if (!(p->focal > 0.0) || !(p->radius > 0.0) || !(p->gamma > 0.0) || !(p->z_near > 0.0) || !(p->z_far > p->z_near) ||
-      !std::isfinite(p->focal) || !std::isfinite(p->ccx) || !std::isfinite(p->ccy) || !std::isfinite(p->z_far) ||
-      !std::isfinite(p->radius) || !std::isfinite(p->bg_eps))
-    return rfail(SLM_ERR_INVALID, (w + ": bad camera or blend parameters").c_str());
-  if (N < 0 || N > r->cap) return rfail(SLM_ERR_INVALID, (w + ": more points than the context holds").c_str());
-  if (N > 0 && ((src != RN_SRC_GF && !pts) || !colors || cstride < 3))
-    return rfail(SLM_ERR_INVALID, (w + ": null points / colours or color_stride < 3").c_str());
-  hipStream_t st = (hipStream_t)stream;
+RnCam rn_cam(const slm_render_params* p) {
   RnCam cam;
   cam.w = p->width;
   cam.h = p->height;
@@ -333,16 +480,45 @@ int render_common(slm_render* r, const slm_render_params* p, int N, int src, con
   cam.bg0 = p->bg[0];
   cam.bg1 = p->bg[1];
   cam.bg2 = p->bg[2];
+  return cam;
+}
+
+// the parameters a backward must repeat: those of its forward, field by field (pad excluded)
+bool rn_same_params(const slm_render_params& a, const slm_render_params& b) {
+  return a.width == b.width && a.height == b.height && a.n_track == b.n_track && a.points_f64 == b.points_f64 &&
+         a.focal == b.focal && a.ccx == b.ccx && a.ccy == b.ccy && a.radius == b.radius && a.z_near == b.z_near &&
+         a.z_far == b.z_far && a.gamma == b.gamma && a.bg_eps == b.bg_eps && a.bg[0] == b.bg[0] && a.bg[1] == b.bg[1] &&
+         a.bg[2] == b.bg[2];
+}
+
+int render_common(slm_render* r, const slm_render_params* p, int N, int src, const void* pts, GfSlot* gslot,
+                  const float* colors, int cstride, float* image, int32_t* front_id, int32_t* hit_count, void* stream,
+                  const char* who) {
+  std::string w(who);
+  if (!r || !p || !image) return rfail(SLM_ERR_INVALID, (w + ": null argument").c_str());
+  if (p->width < 1 || p->height < 1 || p->width > r->W || p->height > r->H)
+    return rfail(SLM_ERR_INVALID, (w + ": image size outside the context's H x W").c_str());
+  if (p->n_track < 1 || p->n_track > SLM_RENDER_MAX_TRACK) return rfail(SLM_ERR_INVALID, (w + ": n_track must be 1..64").c_str());
+  if (!(p->focal > 0.0) || !(p->radius > 0.0) || !(p->gamma > 0.0) || !(p->z_near > 0.0) || !(p->z_far > p->z_near) ||
+      !std::isfinite(p->focal) || !std::isfinite(p->ccx) || !std::isfinite(p->ccy) || !std::isfinite(p->z_far) ||
+      !std::isfinite(p->radius) || !std::isfinite(p->bg_eps))
+    return rfail(SLM_ERR_INVALID, (w + ": bad camera or blend parameters").c_str());
+  if (N < 0 || N > r->cap) return rfail(SLM_ERR_INVALID, (w + ": more points than the context holds").c_str());
+  if (N > 0 && ((src != RN_SRC_GF && !pts) || !colors || cstride < 3))
+    return rfail(SLM_ERR_INVALID, (w + ": null points / colours or color_stride < 3").c_str());
+  r->has_fwd = 0;
+  hipStream_t st = (hipStream_t)stream;
+  const RnCam cam = rn_cam(p);
   const int tiles_y = (p->height + RN_TILE - 1) / RN_TILE, tiles = cam.tiles_x * tiles_y;
   RNCHK(hipMemsetAsync(r->cnt, 0, sizeof(unsigned int) * tiles, st));
   const dim3 gp((N + 255) / 256);
   if (N > 0) {
     if (src == RN_SRC_F32)
-      hipLaunchKernelGGL(k_rn_project<RN_SRC_F32>, gp, dim3(256), 0, st, N, pts, gslot, cam, r->pos, r->box, r->cnt);
+      hipLaunchKernelGGL(k_rn_project<RN_SRC_F32>, gp, dim3(256), 0, st, N, pts, gslot, cam, r->pos, r->box, r->cnt, colors, cstride, r->col);
     else if (src == RN_SRC_F64)
-      hipLaunchKernelGGL(k_rn_project<RN_SRC_F64>, gp, dim3(256), 0, st, N, pts, gslot, cam, r->pos, r->box, r->cnt);
+      hipLaunchKernelGGL(k_rn_project<RN_SRC_F64>, gp, dim3(256), 0, st, N, pts, gslot, cam, r->pos, r->box, r->cnt, colors, cstride, r->col);
     else
-      hipLaunchKernelGGL(k_rn_project<RN_SRC_GF>, gp, dim3(256), 0, st, N, pts, gslot, cam, r->pos, r->box, r->cnt);
+      hipLaunchKernelGGL(k_rn_project<RN_SRC_GF>, gp, dim3(256), 0, st, N, pts, gslot, cam, r->pos, r->box, r->cnt, colors, cstride, r->col);
   }
   hipLaunchKernelGGL(k_rn_scan, dim3(1), dim3(1024), 0, st, tiles, r->cnt, r->off, r->cur);
   RNCHK(hipGetLastError());
@@ -363,8 +539,12 @@ int render_common(slm_render* r, const slm_render_params* p, int N, int src, con
   if (total > 0)
     hipLaunchKernelGGL(k_rn_scatter, gp, dim3(256), 0, st, N, cam.tiles_x, r->pos, r->box, r->cur, r->keys);
   hipLaunchKernelGGL(k_rn_tile, dim3(cam.tiles_x, tiles_y), dim3(256), 0, st, cam, r->off, r->keys, r->tmp, r->pos, r->box,
-                     colors, cstride, image, front_id, hit_count);
+                     colors, cstride, image, front_id, hit_count, r->pix);
   RNCHK(hipGetLastError());
+  r->last = *p;
+  r->n_last = N;
+  r->total_last = total;
+  r->has_fwd = 1;
   return SLM_OK;
 }
 
@@ -386,6 +566,8 @@ int slm_render_create(int32_t H, int32_t W, int32_t max_points, slm_render** out
   if (e == hipSuccess) e = hipMalloc((void**)&r->off, sizeof(unsigned long long) * (tiles + 1));
   if (e == hipSuccess) e = hipMalloc((void**)&r->cur, sizeof(unsigned long long) * tiles);
   if (e == hipSuccess) e = hipHostMalloc((void**)&r->h_total, sizeof(unsigned long long), hipHostMallocDefault);
+  if (e == hipSuccess) e = hipMalloc((void**)&r->col, sizeof(float4) * cap);
+  if (e == hipSuccess) e = hipMalloc((void**)&r->pix, sizeof(RnPix) * (size_t)H * W);
   if (e != hipSuccess) {
     slm_set_error_text((std::string("slm_render_create: ") + hipGetErrorString(e)).c_str());
     slm_render_destroy(r);
@@ -397,7 +579,7 @@ int slm_render_create(int32_t H, int32_t W, int32_t max_points, slm_render** out
 
 int slm_render_destroy(slm_render* r) {
   if (!r) return SLM_OK;
-  void* ptrs[] = {r->pos, r->box, r->cnt, r->off, r->cur, r->keys, r->tmp};
+  void* ptrs[] = {r->pos, r->box, r->cnt, r->off, r->cur, r->keys, r->tmp, r->col, r->pix, r->slab};
   for (void* q : ptrs)
     if (q) (void)hipFree(q);
   if (r->h_total) (void)hipHostFree(r->h_total);
@@ -420,6 +602,36 @@ int slm_gf_render(slm_gf* g, int32_t slot, slm_render* r, const slm_render_param
   if (rc != SLM_OK) return rc;
   return render_common(r, p, n, RN_SRC_GF, nullptr, dev, colors, color_stride, image, front_id, hit_count, stream,
                        "slm_gf_render");
+}
+
+int slm_render_backward(slm_render* r, const slm_render_params* p, const double* grad_image, double* grad_points,
+                        void* stream) {
+  if (!r || !p || !grad_image) return rfail(SLM_ERR_INVALID, "slm_render_backward: null argument");
+  if (!r->has_fwd) return rfail(SLM_ERR_INVALID, "slm_render_backward: no completed forward on this context");
+  if (!rn_same_params(*p, r->last))
+    return rfail(SLM_ERR_INVALID, "slm_render_backward: parameters differ from those of the last forward");
+  const int N = r->n_last;
+  if (N == 0) return SLM_OK;
+  if (!grad_points) return rfail(SLM_ERR_INVALID, "slm_render_backward: null grad_points");
+  hipStream_t st = (hipStream_t)stream;
+  const RnCam cam = rn_cam(p);
+  const int tiles_y = (p->height + RN_TILE - 1) / RN_TILE;
+  const unsigned long long total = r->total_last;
+  if (total > r->cap_slab) {
+    if (r->slab) RNCHK(hipFree(r->slab));
+    r->slab = nullptr;
+    r->cap_slab = 0;
+    const size_t c = (size_t)total + total / 4 + 1024;
+    RNCHK(hipMalloc((void**)&r->slab, 3 * sizeof(double) * c));
+    r->cap_slab = c;
+  }
+  if (total > 0)
+    hipLaunchKernelGGL(k_rn_bwd_entry, dim3(cam.tiles_x, tiles_y), dim3(256), 0, st, cam, r->off, r->keys, r->pos, r->box,
+                       r->col, r->pix, grad_image, r->slab);
+  hipLaunchKernelGGL(k_rn_bwd_point, dim3((N + 255) / 256), dim3(256), 0, st, N, cam.tiles_x, r->off, r->keys, r->pos, r->box,
+                     r->slab, grad_points);
+  RNCHK(hipGetLastError());
+  return SLM_OK;
 }
 
 }  // extern "C"

@@ -18,10 +18,17 @@ frame and hands the (1,2,H,W) flow to the library.  With ``sf_corr_match_renderi
 "pulsar"``, radius ``opt.renderer_rad``) the flow is re-inferred every iteration from the rendered deformed model
 instead (deform_mesh.py:292-305): iteration i renders the current deformed stable surfels on the device
 (slm_gf_render, super_amd.renderer's blend), calls ``models.optical_flow(render (1,3,H,W), inputs[("color",0)])``,
-binds the flow and takes one evaluation and step.  The (unused) render loss needs the renderer's backward pass and
-raises ``NotImplementedError``.  The reference also renders every iteration without that flag (the ``if True:`` at
-deform_mesh.py:294), but no output depends on that render, so this mirror does not make it: without the flag the
-path is the single ``infer_flow`` on ``src.rgb`` and one ``slm_gf_run``.
+binds the flow and takes one evaluation and step.  The reference also renders every iteration without that flag (the
+``if True:`` at deform_mesh.py:294), but no output depends on that render, so this mirror does not make it: without
+the flag (and without the render loss) the path is the single ``infer_flow`` on ``src.rgb`` and one ``slm_gf_run``.
+
+The render loss ``opt.render_loss`` (+ ``render_loss_weight``, default 1e-4; deform_mesh.py:113-123) is opt-in:
+``GraphFit(opt, native_render_loss=True)``.  Its gradient is the exact derivative of super_amd.renderer's blend
+(slm_render_backward), not Pulsar's own backward, which cannot be pinned without pytorch3d; plain ``GraphFit(opt)``
+raises for the flag.  Every iteration renders the deformed stable surfels (slm_gf_render) -- with
+``sf_corr_match_renderimg`` that one render also feeds the flow network -- scores the SSIM-11 loss against
+``inputs[("color",0)]`` with its image gradient (slm_render_ssim_loss), back-propagates it to the surfels
+(slm_render_backward), binds that (slm_gf_bind_point_grad) and takes one evaluation and step.
 """
 from __future__ import annotations
 
@@ -41,13 +48,26 @@ class GraphFit:
     partial gradient / loss sums are all-reduced (RCCL) twice per optimiser iteration and every
     rank takes the same step (BASELINE configs[4])."""
 
-    def __init__(self, opt, max_frames=1, shard_surfels=False, rank=None, world=None, all_reduce=None):
+    def __init__(self, opt, max_frames=1, shard_surfels=False, rank=None, world=None, all_reduce=None,
+                 native_render_loss=False):
         self.opt = opt
         self.lib = _lib.load()
         if not torch.cuda.is_available():
             raise _lib.SuperLMError("no HIP device visible: super_amd has no CPU fallback")
-        if getattr(opt, "render_loss", False):
-            raise NotImplementedError("super_amd.GraphFit: opt.render_loss is not supported")
+        self.render_loss = bool(getattr(opt, "render_loss", False))
+        if self.render_loss:
+            if not native_render_loss:
+                raise NotImplementedError(
+                    "super_amd.GraphFit: opt.render_loss needs GraphFit(opt, native_render_loss=True): its gradient is "
+                    "the exact derivative of super_amd.renderer's blend, not Pulsar's own backward, which is unpinned "
+                    "(pytorch3d has no ROCm build)")
+            if getattr(opt, "renderer", None) != "pulsar":
+                raise NotImplementedError("super_amd.GraphFit: opt.render_loss renders with opt.renderer; "
+                                          f"only 'pulsar' is implemented (got {getattr(opt, 'renderer', None)!r})")
+            if shard_surfels or world is not None:
+                raise NotImplementedError("super_amd.GraphFit: opt.render_loss on surfel-sharded frames")
+        self.render_loss_weight = float(getattr(opt, "render_loss_weight", 1e-4))
+        self.last_render_kept = None
         self.match_render = bool(getattr(opt, "sf_corr", False) and getattr(opt, "sf_corr_match_renderimg", False))
         if self.match_render:
             # the reference renders with models.renderer, which InitNets only builds for opt.renderer == "pulsar"
@@ -200,6 +220,8 @@ class GraphFit:
         """(reference ``deform_mesh.py:232-247``) returns deform_verts (J+1,7) float64."""
         if getattr(self.opt, "deform_udpate_method", "super_edg") != "super_edg":
             raise NotImplementedError("only deform_udpate_method == 'super_edg'")
+        if self.render_loss:
+            return self._forward_render_loss(inputs, src, trg, models)
         if self.match_render:
             return self._forward_match_render(inputs, src, trg, models)
         bf = self._bind(0, inputs, src, trg, models)
@@ -237,6 +259,38 @@ class GraphFit:
             self.step()
         return self.deform_verts()
 
+    def _forward_render_loss(self, inputs, src, trg, models):
+        """deform_mesh.py:286-330 with opt.render_loss: per iteration render -> (flow of that render, with
+        sf_corr_match_renderimg) -> SSIM loss and its image gradient -> renderer backward -> bind -> step."""
+        if self.match_render and (models is None or not hasattr(models, "optical_flow")):
+            raise ValueError("opt.sf_corr needs models.optical_flow")   # the reference asserts
+        # without sf_corr_match_renderimg the flow (sf_corr) is inferred once from src.rgb at the bind (iteration 0)
+        bf = self._bind(0, inputs, src, trg, models, defer_flow=self.match_render)
+        colors = src.colors.detach().to(device=bf.device, dtype=torch.float32).contiguous()
+        self._keep[0].append(colors)
+        for _ in range(int(self.Niter)):
+            img, p = self._render_deformed_hwc(inputs, colors)
+            if self.match_render:
+                self.flow = self.infer_flow(models, img.permute(2, 0, 1).unsqueeze(0), inputs[("color", 0)])
+                self._bind_flow(bf, self.flow)
+            self._bind_render_grad(bf, inputs, img, p)
+            self.eval_morph()
+            self.eval_losses()
+            self.step()
+        _lib.check(self.lib.slm_gf_bind_point_grad(self.h, 0, None, _stream_ptr(bf.device)), "slm_gf_bind_point_grad")
+        return self.deform_verts()
+
+    def _bind_render_grad(self, bf, inputs, img, p):
+        """SSIM loss of the render ``img`` (h,w,3) and its gradient, back through the renderer, bound as the slot's
+        point gradient; returns the (2,) device [weighted loss, kept pixels]."""
+        from .renderer import render_backward, ssim_render_loss_device
+        out, gimg = ssim_render_loss_device(img, inputs[("color", 0)], self.render_loss_weight, with_grad=True)
+        gp = render_backward(self._render_ctx, p, gimg)
+        self._keep[0].append(gp)         # read by the next evaluation
+        _lib.check(self.lib.slm_gf_bind_point_grad(self.h, 0, _dev_ptr(gp), _stream_ptr(bf.device)),
+                   "slm_gf_bind_point_grad")
+        return out
+
     def _bind_flow(self, bf, flow):
         fl = _as(flow, torch.float32, bf.device)
         if tuple(fl.shape) != (1, 2, bf.c.H, bf.c.W):
@@ -248,6 +302,10 @@ class GraphFit:
         """The current deformed stable surfels of the bound frame (deform_source's new_data, global row included)
         rendered like ``models.renderer(inputs, new_data, rad=opt.renderer_rad)``: (1,3,H,W) float32, permuted
         like the reference (deform_mesh.py:295-298).  ``colors`` (N,3) float32 is indexed by surfel row."""
+        return self._render_deformed_hwc(inputs, colors)[0].permute(2, 0, 1).unsqueeze(0)
+
+    def _render_deformed_hwc(self, inputs, colors):
+        """``render_deformed`` as the (h,w,3) float32 image, with the render parameters."""
         from .renderer import DEFAULT_RAD, RenderContext, render_params
         bf = self._keep[0][0]
         H, W = bf.c.H, bf.c.W
@@ -257,9 +315,11 @@ class GraphFit:
         ctx.reserve(bf.c.N)
         p = render_params(inputs["K"], H, W, 1.0, getattr(self.opt, "renderer_rad", DEFAULT_RAD))
         img = torch.empty((p.height, p.width, 3), dtype=torch.float32, device=bf.device)
+        ctx.last_n = 0
         _lib.check(self.lib.slm_gf_render(self.h, 0, ctx.h, C.byref(p), _dev_ptr(colors), int(colors.stride(0)),
                                           _dev_ptr(img), None, None, _stream_ptr(bf.device)), "slm_gf_render")
-        return img.permute(2, 0, 1).unsqueeze(0)
+        ctx.last_n = bf.c.N
+        return img, p
 
     # ---- stepwise evaluation (surfel-sharded frames; also usable with world == 1) -------------
     def _st(self):
@@ -299,14 +359,26 @@ class GraphFit:
     def loss_and_grad(self, inputs, src, trg, deform_verts, models=None, flow=None):
         """One evaluation of ``deform_source`` + ``get_losses`` + backward at ``deform_verts``:
         returns (dict of weighted loss terms, matched count, gradient (J+1,7) with the global
-        row divided by J)."""
+        row divided by J).  With the render loss (``native_render_loss``) the dict also holds ``render_loss``
+        (weighted; the render is made at ``deform_verts`` from ``src.colors``), the gradient includes it and
+        ``self.last_render_kept`` is its kept pixel count."""
         bf = self._bind(0, inputs, src, trg, models, flow)
         st = _stream_ptr(bf.device)
         dv = _as(deform_verts, torch.float64, bf.device)
         terms = torch.zeros(_lib.GF_NTERMS, dtype=torch.float64, device=bf.device)
         grad = torch.zeros((bf.J + 1, 7), dtype=torch.float64, device=bf.device)
+        rl = None
+        if self.render_loss:
+            # a first evaluation puts deform_verts into the slot, where slm_gf_render reads it
+            _lib.check(self.lib.slm_gf_loss_grad(self.h, 0, _dev_ptr(dv), None, None, st), "slm_gf_loss_grad")
+            colors = src.colors.detach().to(device=bf.device, dtype=torch.float32).contiguous()
+            self._keep[0].append(colors)
+            img, p = self._render_deformed_hwc(inputs, colors)
+            rl = self._bind_render_grad(bf, inputs, img, p)
         _lib.check(self.lib.slm_gf_loss_grad(self.h, 0, _dev_ptr(dv), _dev_ptr(terms), _dev_ptr(grad), st),
                    "slm_gf_loss_grad")
+        if rl is not None:
+            _lib.check(self.lib.slm_gf_bind_point_grad(self.h, 0, None, st), "slm_gf_bind_point_grad")
         t = terms.cpu().tolist()
         d = dict(face_losses=t[0], arap_loss=t[1], rot_loss=t[2], point_plane_loss=t[3])
         if self.cfg.use_bn_morph and t[7] != 0.0:       # the reference only adds the key when a class contributes
@@ -315,6 +387,10 @@ class GraphFit:
         if self.cfg.corr_mode:
             d["corr_loss"] = t[8]
             self.last_corr_kept = int(t[9])
+        if rl is not None:
+            loss, kept = rl.cpu().tolist()
+            d["render_loss"] = loss
+            self.last_render_kept = int(kept)
         return d, int(t[4]), grad
 
     def edge_points(self, class_id):

@@ -7,8 +7,13 @@ the two ``Surfels`` methods that call it (``super/nodes.py:630-650``), over libs
 The image is the forward blend of Pulsar's paper (Lassner & Zollhoefer, CVPR 2021) at the parameters of the
 reference's call; include/super_lm.h and DESIGN.md ("Renderer") state it.  pytorch3d is not available on ROCm, so
 parity with Pulsar itself is NOT pinned: every convention that is only a reading of Pulsar is one constant or one
-short function below, marked "unpinned".  Forward only: there is no backward pass (``render_loss`` stays
-unsupported), and inputs that require grad are refused.
+short function below, marked "unpinned".  ``Pulsar`` is forward only: inputs that require grad are refused.
+
+The render loss of GraphFit (``opt.render_loss``, deform_mesh.py:113-123) has two native pieces here:
+``render_backward`` -- dL/dpoints of the last render on a context, the exact derivative of THIS blend (Pulsar's own
+backward is not pinned) -- and ``ssim_render_loss`` -- monodepth2's SSIM-11 loss with the reference's mask,
+selection and weight, and its image gradient, in float64 (the reference runs float32).  ``GraphFit(opt,
+native_render_loss=True)`` chains them; there is no autograd ``Function`` around the renderer.
 """
 from __future__ import annotations
 
@@ -66,6 +71,7 @@ class RenderContext:
         if not torch.cuda.is_available():
             raise _lib.SuperLMError("no HIP device visible: super_amd has no CPU fallback")
         self.H, self.W, self.cap = int(H), int(W), 0
+        self.last_n = 0          # point count of the last render (the rows render_backward writes)
         self.h = C.c_void_p()
         self.reserve(max_points)
 
@@ -103,8 +109,8 @@ def _colors_arg(colors, n, device):
 def _check_no_grad(*ts):
     for t in ts:
         if torch.is_tensor(t) and t.requires_grad:
-            raise RuntimeError("super_amd.renderer: the renderer is forward only (no backward pass); "
-                               "pass tensors that do not require grad")
+            raise RuntimeError("super_amd.renderer: the renderer is forward only (no autograd; the render loss's "
+                               "gradient is render_backward); pass tensors that do not require grad")
 
 
 def render_points(ctx, params, points, colors, with_info=False):
@@ -128,9 +134,64 @@ def render_points(ctx, params, points, colors, with_info=False):
         fid = torch.empty((params.height, params.width), dtype=torch.int32, device=dev)
         cnt = torch.empty_like(fid)
     ptr = lambda t: _dev_ptr(t) if t is not None and t.numel() else None
+    ctx.last_n = 0
     _lib.check(ctx.lib.slm_render_points(ctx.h, C.byref(params), n, ptr(pts), ptr(col), stride, _dev_ptr(img),
                                          ptr(fid), ptr(cnt), _stream_ptr(dev)), "slm_render_points")
+    ctx.last_n = n
     return (img, fid, cnt) if with_info else img
+
+
+def render_backward(ctx, params, grad_image):
+    """dL/dpoints (N,3) float64 of the last render on ``ctx`` (``render_points`` or GraphFit's ``slm_gf_render``:
+    then by surfel row, 0 on unstable rows) for ``grad_image`` = dL/dimage (h,w,3).  ``params`` must be the render's.
+    The exact derivative of the blend (include/super_lm.h ``slm_render_backward``): hit sets and the n_track cut are
+    the forward's, positions the float32-rounded ones; not Pulsar's own backward (unpinned)."""
+    g = torch.as_tensor(grad_image).detach()
+    dev = g.device
+    if tuple(g.shape) != (params.height, params.width, 3):
+        raise ValueError(f"grad_image must be ({params.height},{params.width},3), got {tuple(g.shape)}")
+    g = g.to(dtype=torch.float64).contiguous()
+    out = torch.empty((ctx.last_n, 3), dtype=torch.float64, device=dev)
+    _lib.check(ctx.lib.slm_render_backward(ctx.h, C.byref(params), _dev_ptr(g), _dev_ptr(out) if out.numel() else None,
+                                           _stream_ptr(dev)), "slm_render_backward")
+    return out
+
+
+def _ssim_args(img_hwc, target_chw):
+    img = img_hwc.detach()
+    if img.dim() != 3 or img.shape[2] != 3:
+        raise ValueError(f"img_hwc must be (h,w,3), got {tuple(img.shape)}")
+    h, w = int(img.shape[0]), int(img.shape[1])
+    tgt = target_chw.detach()
+    tgt = tgt.reshape(tgt.shape[-3:]) if tgt.dim() == 4 else tgt
+    if tuple(tgt.shape) != (3, h, w):
+        raise ValueError(f"target_chw must be (3,{h},{w}) or (1,3,{h},{w}), got {tuple(target_chw.shape)}")
+    img = img.to(dtype=torch.float32).contiguous()
+    tgt = tgt.to(device=img.device, dtype=torch.float32).contiguous()
+    return img, tgt, h, w
+
+
+def ssim_render_loss_device(img_hwc, target_chw, weight, with_grad=True):
+    """``ssim_render_loss`` without the read-back: ((2,) float64 device [loss, kept], grad or None)."""
+    img, tgt, h, w = _ssim_args(img_hwc, target_chw)
+    dev = img.device
+    out = torch.empty(2, dtype=torch.float64, device=dev)
+    grad = torch.empty((h, w, 3), dtype=torch.float64, device=dev) if with_grad else None
+    lib = _lib.load()
+    _lib.check(lib.slm_render_ssim_loss(h, w, _dev_ptr(img), _dev_ptr(tgt), float(weight), _dev_ptr(out),
+                                        _dev_ptr(grad) if grad is not None else None, _stream_ptr(dev)),
+               "slm_render_ssim_loss")
+    return out, grad
+
+
+def ssim_render_loss(img_hwc, target_chw, weight, with_grad=True):
+    """The reference's render loss (deform_mesh.py:115-121) of the render ``img_hwc`` (h,w,3) against
+    ``target_chw`` (3,h,w) or (1,3,h,w) = inputs[("color",0)]: (weight * sum of the kept m, kept pixel count,
+    dL/dimg (h,w,3) float64 or None).  SSIM-11 with reflection padding, m = mean_c(SSIM)^2, kept where the
+    border-clipped 11x11 window of the render is > 0 in every channel and m < 0.1; float64 on the float32 inputs."""
+    out, grad = ssim_render_loss_device(img_hwc, target_chw, weight, with_grad)
+    loss, kept = out.cpu().tolist()
+    return loss, int(kept), grad
 
 
 class Pulsar:
