@@ -669,6 +669,17 @@ int slm_gf_render(slm_gf* g, int32_t slot, slm_render* r, const slm_render_param
  * p differs.  Bitwise reproducible (no float atomics); does not synchronise. */
 int slm_render_backward(slm_render* r, const slm_render_params* p, const double* grad_image, double* grad_points,
                         void* stream);
+/* slm_render_backward_ex: slm_render_backward with the colour gradient as well (Pulsar's autograd gives both).  With W and
+ * g as above,
+ *   dL/dc_k = sum over the pixels k takes part in of  g w_k / W    (per channel)
+ * at the forward's hit sets (rho < radius, the n_track cut).  Colours are the forward's float32 copy and the gradient
+ * passes that cast unchanged.  grad_points and grad_colors: (N,3) float64 device, rows as for slm_render_backward (0 on
+ * unstable rows and on culled points); either may be NULL, not both.  grad_points equals slm_render_backward's bitwise,
+ * and grad_colors does not depend on whether grad_points is requested.  The same two passes and the same refusals; the
+ * slab grows from 3 to 6 doubles per tile-list entry when both are requested.  Bitwise reproducible; does not
+ * synchronise. */
+int slm_render_backward_ex(slm_render* r, const slm_render_params* p, const double* grad_image, double* grad_points,
+                           double* grad_colors, void* stream);
 /* The render loss at the image (h,w,3) float32 `image_hwc` (a render) against the target (3,h,w) float32 `target_chw`
  * (inputs[("color",0)][0]): per channel monodepth2's SSIM with kernel 11 -- reflection padding 5, 11x11 box means of
  * x, y, x^2, y^2, xy, C1 = 0.01^2, C2 = 0.03^2, clamp((1 - n/d)/2, 0, 1) -- then m = mean_c(SSIM_c)^2; a pixel is kept

@@ -20,6 +20,8 @@
 //   k_rn_bwd_entry  one workgroup per tile: the tile's pixel coefficients g/W, g.C/W in LDS, then per list entry the
 //                   contributions of the pixels of its box inside the tile, summed in row-major pixel order -> `slab`
 //   k_rn_bwd_point  per point: the slab entries of its tiles, found by binary search of its key, summed in tile order
+// slm_render_backward_ex adds the colour gradient in the same two passes (k_rn_bwd_entry<MODE>, k_rn_bwd_point_ex<MODE>):
+// the slab holds 6 doubles per entry with both gradients, 3 with one.
 #include <climits>
 #include <cmath>
 #include <cstring>
@@ -47,7 +49,7 @@ struct slm_render {
   // ---- state of the last forward, read by slm_render_backward ----
   float4* col = nullptr;                 // (cap) colours of the points, w unused
   struct RnPix* pix = nullptr;           // (H * W) per-pixel blend record
-  double* slab = nullptr;                // (3 cap_slab) per tile-list entry dL/dP partials
+  double* slab = nullptr;                // (cap_slab doubles) per tile-list entry partials: dL/dP and / or dL/dc
   size_t cap_slab = 0;
   slm_render_params last{};              // parameters of the last forward
   int n_last = 0;                        // its point count
@@ -338,16 +340,24 @@ __global__ void __launch_bounds__(256) k_rn_tile(RnCam cam, const unsigned long 
   if (hit_count) hit_count[px] = nh;
 }
 
+// What a backward computes: the point gradient, the colour gradient, or both (template parameter of the backward kernels).
+// The slab holds 3 doubles per tile-list entry and output: the point partials first.
+enum { RN_BWD_POINTS = 1, RN_BWD_COLORS = 2 };
+
 // Backward, pass 1 (see the top of the file): one workgroup per tile.  Lane t stages pixel t of the tile -- its ray and the
 // coefficients a = g / W, b = g.C / W of s_k = g.(c_k - C) / W, or cut = -1 when the pixel has no hit or g = 0 -- then every
 // lane takes list entries e = t, t + 256, ... and sums, in row-major order over the pixels of the entry's box inside the tile
-// that it reaches (position <= cut, rho < r: the forward's decisions), s_k ( -(e_k / r) drho/dP - w_k / (gamma zspan) z ).
+// that it reaches (position <= cut, rho < r: the forward's decisions), s_k ( -(e_k / r) drho/dP - w_k / (gamma zspan) z )
+// (RN_BWD_POINTS) and a w_k = g w_k / W (RN_BWD_COLORS).
+template <int MODE>
 __global__ void __launch_bounds__(256) k_rn_bwd_entry(RnCam cam, const unsigned long long* __restrict__ off,
                                                       const unsigned long long* __restrict__ keys, const float4* __restrict__ pos,
                                                       const int4* __restrict__ box, const float4* __restrict__ col,
                                                       const RnPix* __restrict__ pix, const double* __restrict__ gimg,
                                                       double* __restrict__ slab) {
-  __shared__ double sdx[256], sdy[256], sinv[256], szt[256], sa0[256], sa1[256], sa2[256], sb[256];
+  constexpr bool GP = (MODE & RN_BWD_POINTS) != 0, GC = (MODE & RN_BWD_COLORS) != 0;
+  constexpr int S = (GP ? 3 : 0) + (GC ? 3 : 0);
+  __shared__ double sdx[256], sdy[256], sinv[256], szt[256], sa0[256], sa1[256], sa2[256], sb[GP ? 256 : 1];
   __shared__ int scut[256];
   const int tile = blockIdx.y * cam.tiles_x + blockIdx.x;
   const unsigned long long base = off[tile];
@@ -366,7 +376,7 @@ __global__ void __launch_bounds__(256) k_rn_bwd_entry(RnCam cam, const unsigned 
         sa0[t] = g0 / rec.W;
         sa1[t] = g1 / rec.W;
         sa2[t] = g2 / rec.W;
-        sb[t] = (g0 * rec.c0 + g1 * rec.c1 + g2 * rec.c2) / rec.W;
+        if constexpr (GP) sb[t] = (g0 * rec.c0 + g1 * rec.c1 + g2 * rec.c2) / rec.W;
         szt[t] = rec.zt_max;
         double dx, dy, inv_dn;
         rn_ray(cam, i, j, dx, dy, inv_dn);
@@ -383,10 +393,11 @@ __global__ void __launch_bounds__(256) k_rn_bwd_entry(RnCam cam, const unsigned 
     const int id = (int)(unsigned int)keys[base + e];
     const int4 b = box[id];
     const float4 p = pos[id];
-    const float4 c = col[id];
+    float4 c = make_float4(0.f, 0.f, 0.f, 0.f);
+    if constexpr (GP) c = col[id];
     const double X = p.x, Y = p.y, Z = p.z;
     const double zt = (cam.zf - Z) / zspan;
-    double gx = 0.0, gy = 0.0, gz = 0.0;
+    double gx = 0.0, gy = 0.0, gz = 0.0, q0 = 0.0, q1 = 0.0, q2 = 0.0;
     const int i0 = max(b.z, ty0), i1 = min(b.w, ty0 + RN_TILE - 1), j0 = max(b.x, tx0), j1 = min(b.y, tx0 + RN_TILE - 1);
     for (int i = i0; i <= i1; ++i)
       for (int j = j0; j <= j1; ++j) {
@@ -396,27 +407,66 @@ __global__ void __launch_bounds__(256) k_rn_bwd_entry(RnCam cam, const unsigned 
         const double rho = rn_rho(X, Y, Z, dx, dy, inv_dn);
         if (!(rho < cam.r)) continue;
         const double ek = exp((zt - szt[t]) / cam.gamma), wk = (1.0 - rho / cam.r) * ek;
-        const double sk = sa0[t] * (double)c.x + sa1[t] * (double)c.y + sa2[t] * (double)c.z - sb[t];
-        if (rho > 0.0) {
-          // drho/dP = (P - (P.d^) d^) / rho, d^ = d / |d|
-          const double hx = dx * inv_dn, hy = dy * inv_dn, hz = inv_dn;
-          const double pd = X * hx + Y * hy + Z * hz;
-          const double q = -sk * ek / (cam.r * rho);
-          gx += q * (X - pd * hx);
-          gy += q * (Y - pd * hy);
-          gz += q * (Z - pd * hz);
+        if constexpr (GP) {
+          const double sk = sa0[t] * (double)c.x + sa1[t] * (double)c.y + sa2[t] * (double)c.z - sb[t];
+          if (rho > 0.0) {
+            // drho/dP = (P - (P.d^) d^) / rho, d^ = d / |d|
+            const double hx = dx * inv_dn, hy = dy * inv_dn, hz = inv_dn;
+            const double pd = X * hx + Y * hy + Z * hz;
+            const double q = -sk * ek / (cam.r * rho);
+            gx += q * (X - pd * hx);
+            gy += q * (Y - pd * hy);
+            gz += q * (Z - pd * hz);
+          }
+          gz -= sk * wk * kz;
         }
-        gz -= sk * wk * kz;
+        if constexpr (GC) {
+          q0 += sa0[t] * wk;
+          q1 += sa1[t] * wk;
+          q2 += sa2[t] * wk;
+        }
       }
-    double* o = slab + 3 * (base + e);
-    o[0] = gx;
-    o[1] = gy;
-    o[2] = gz;
+    double* o = slab + S * (base + e);
+    if constexpr (GP) {
+      o[0] = gx;
+      o[1] = gy;
+      o[2] = gz;
+    }
+    if constexpr (GC) {
+      o[S - 3] = q0;
+      o[S - 2] = q1;
+      o[S - 1] = q2;
+    }
   }
 }
 
-// Backward, pass 2: per point, the slab entries of the tiles its box touches (the scatter's order), each found by binary
-// search of the point's key -- unique in its tile's sorted list.  Culled points (and unstable surfels) get 0.
+// Backward, pass 2, for one point: the S-double slab entries of the tiles its box touches (the scatter's order), each found
+// by binary search of the point's key -- unique in its tile's sorted list -- summed into acc.  Culled points (and unstable
+// surfels) get 0.
+template <int S>
+__device__ __forceinline__ void rn_bwd_gather(int i, int tiles_x, const unsigned long long* __restrict__ off,
+                                              const unsigned long long* __restrict__ keys, const float4* __restrict__ pos,
+                                              const int4* __restrict__ box, const double* __restrict__ slab, double (&acc)[S]) {
+  for (int q = 0; q < S; ++q) acc[q] = 0.0;
+  const int4 b = box[i];
+  if (b.x <= b.y) {
+    const unsigned long long key = ((unsigned long long)__float_as_uint(pos[i].z) << 32) | (unsigned int)i;
+    for (int ty = b.z / RN_TILE; ty <= b.w / RN_TILE; ++ty)
+      for (int tx = b.x / RN_TILE; tx <= b.y / RN_TILE; ++tx) {
+        const int t = ty * tiles_x + tx;
+        unsigned long long lo = off[t], hi = off[t + 1];
+        while (lo < hi) {
+          const unsigned long long mid = (lo + hi) >> 1;
+          if (keys[mid] < key) lo = mid + 1; else hi = mid;
+        }
+        if (lo < off[t + 1] && keys[lo] == key)
+          for (int q = 0; q < S; ++q) acc[q] += slab[S * lo + q];
+      }
+  }
+}
+
+// Backward, pass 2 of slm_render_backward (RN_BWD_POINTS): per point, dL/dP -- rn_bwd_gather<3> written out (this
+// form keeps its registers).
 __global__ void __launch_bounds__(256) k_rn_bwd_point(int N, int tiles_x, const unsigned long long* __restrict__ off,
                                                       const unsigned long long* __restrict__ keys, const float4* __restrict__ pos,
                                                       const int4* __restrict__ box, const double* __restrict__ slab,
@@ -445,6 +495,24 @@ __global__ void __launch_bounds__(256) k_rn_bwd_point(int N, int tiles_x, const 
   out[3 * (size_t)i] = gx;
   out[3 * (size_t)i + 1] = gy;
   out[3 * (size_t)i + 2] = gz;
+}
+
+// Backward, pass 2 of slm_render_backward_ex with colours (MODE has RN_BWD_COLORS): per point, dL/dc and, with
+// RN_BWD_POINTS, dL/dP; either output may be NULL.
+template <int MODE>
+__global__ void __launch_bounds__(256) k_rn_bwd_point_ex(int N, int tiles_x, const unsigned long long* __restrict__ off,
+                                                         const unsigned long long* __restrict__ keys, const float4* __restrict__ pos,
+                                                         const int4* __restrict__ box, const double* __restrict__ slab,
+                                                         double* __restrict__ out_p, double* __restrict__ out_c) {
+  constexpr int S = (MODE & RN_BWD_POINTS) ? 6 : 3;
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= N) return;
+  double g[S];
+  rn_bwd_gather<S>(i, tiles_x, off, keys, pos, box, slab, g);
+  if (out_p)
+    for (int q = 0; q < 3; ++q) out_p[3 * (size_t)i + q] = g[q];
+  if (out_c)
+    for (int q = 0; q < 3; ++q) out_c[3 * (size_t)i + q] = g[S - 3 + q];
 }
 
 int rfail(int code, const char* msg) {
@@ -548,6 +616,46 @@ int render_common(slm_render* r, const slm_render_params* p, int N, int src, con
   return SLM_OK;
 }
 
+// the two backward launches of the last forward on r (checked by the caller; N > 0), S = 3 or 6 slab doubles per entry
+int rn_backward(slm_render* r, const slm_render_params* p, const double* grad_image, double* grad_points,
+                double* grad_colors, hipStream_t st) {
+  const int N = r->n_last;
+  const RnCam cam = rn_cam(p);
+  const int tiles_y = (p->height + RN_TILE - 1) / RN_TILE;
+  const int mode = (grad_points ? RN_BWD_POINTS : 0) | (grad_colors ? RN_BWD_COLORS : 0);
+  const size_t S = mode == (RN_BWD_POINTS | RN_BWD_COLORS) ? 6 : 3;
+  const unsigned long long total = r->total_last;
+  if (S * total > r->cap_slab) {
+    if (r->slab) RNCHK(hipFree(r->slab));
+    r->slab = nullptr;
+    r->cap_slab = 0;
+    const size_t c = S * ((size_t)total + total / 4 + 1024);
+    RNCHK(hipMalloc((void**)&r->slab, sizeof(double) * c));
+    r->cap_slab = c;
+  }
+  const dim3 gt(cam.tiles_x, tiles_y), gp((N + 255) / 256), b(256);
+  if (mode == RN_BWD_POINTS) {
+    if (total > 0)
+      hipLaunchKernelGGL(k_rn_bwd_entry<RN_BWD_POINTS>, gt, b, 0, st, cam, r->off, r->keys, r->pos, r->box, r->col, r->pix,
+                         grad_image, r->slab);
+    hipLaunchKernelGGL(k_rn_bwd_point, gp, b, 0, st, N, cam.tiles_x, r->off, r->keys, r->pos, r->box, r->slab, grad_points);
+  } else if (mode == RN_BWD_COLORS) {
+    if (total > 0)
+      hipLaunchKernelGGL(k_rn_bwd_entry<RN_BWD_COLORS>, gt, b, 0, st, cam, r->off, r->keys, r->pos, r->box, r->col, r->pix,
+                         grad_image, r->slab);
+    hipLaunchKernelGGL(k_rn_bwd_point_ex<RN_BWD_COLORS>, gp, b, 0, st, N, cam.tiles_x, r->off, r->keys, r->pos, r->box,
+                       r->slab, grad_points, grad_colors);
+  } else {
+    if (total > 0)
+      hipLaunchKernelGGL(k_rn_bwd_entry<RN_BWD_POINTS | RN_BWD_COLORS>, gt, b, 0, st, cam, r->off, r->keys, r->pos, r->box,
+                         r->col, r->pix, grad_image, r->slab);
+    hipLaunchKernelGGL(k_rn_bwd_point_ex<RN_BWD_POINTS | RN_BWD_COLORS>, gp, b, 0, st, N, cam.tiles_x, r->off, r->keys,
+                       r->pos, r->box, r->slab, grad_points, grad_colors);
+  }
+  RNCHK(hipGetLastError());
+  return SLM_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -613,25 +721,18 @@ int slm_render_backward(slm_render* r, const slm_render_params* p, const double*
   const int N = r->n_last;
   if (N == 0) return SLM_OK;
   if (!grad_points) return rfail(SLM_ERR_INVALID, "slm_render_backward: null grad_points");
-  hipStream_t st = (hipStream_t)stream;
-  const RnCam cam = rn_cam(p);
-  const int tiles_y = (p->height + RN_TILE - 1) / RN_TILE;
-  const unsigned long long total = r->total_last;
-  if (total > r->cap_slab) {
-    if (r->slab) RNCHK(hipFree(r->slab));
-    r->slab = nullptr;
-    r->cap_slab = 0;
-    const size_t c = (size_t)total + total / 4 + 1024;
-    RNCHK(hipMalloc((void**)&r->slab, 3 * sizeof(double) * c));
-    r->cap_slab = c;
-  }
-  if (total > 0)
-    hipLaunchKernelGGL(k_rn_bwd_entry, dim3(cam.tiles_x, tiles_y), dim3(256), 0, st, cam, r->off, r->keys, r->pos, r->box,
-                       r->col, r->pix, grad_image, r->slab);
-  hipLaunchKernelGGL(k_rn_bwd_point, dim3((N + 255) / 256), dim3(256), 0, st, N, cam.tiles_x, r->off, r->keys, r->pos, r->box,
-                     r->slab, grad_points);
-  RNCHK(hipGetLastError());
-  return SLM_OK;
+  return rn_backward(r, p, grad_image, grad_points, nullptr, (hipStream_t)stream);
+}
+
+int slm_render_backward_ex(slm_render* r, const slm_render_params* p, const double* grad_image, double* grad_points,
+                           double* grad_colors, void* stream) {
+  if (!r || !p || !grad_image) return rfail(SLM_ERR_INVALID, "slm_render_backward_ex: null argument");
+  if (!r->has_fwd) return rfail(SLM_ERR_INVALID, "slm_render_backward_ex: no completed forward on this context");
+  if (!rn_same_params(*p, r->last))
+    return rfail(SLM_ERR_INVALID, "slm_render_backward_ex: parameters differ from those of the last forward");
+  if (r->n_last == 0) return SLM_OK;
+  if (!grad_points && !grad_colors) return rfail(SLM_ERR_INVALID, "slm_render_backward_ex: null grad_points and grad_colors");
+  return rn_backward(r, p, grad_image, grad_points, grad_colors, (hipStream_t)stream);
 }
 
 }  // extern "C"

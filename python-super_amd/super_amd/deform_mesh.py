@@ -316,6 +316,7 @@ class GraphFit:
         p = render_params(inputs["K"], H, W, 1.0, getattr(self.opt, "renderer_rad", DEFAULT_RAD))
         img = torch.empty((p.height, p.width, 3), dtype=torch.float32, device=bf.device)
         ctx.last_n = 0
+        ctx.serial += 1
         _lib.check(self.lib.slm_gf_render(self.h, 0, ctx.h, C.byref(p), _dev_ptr(colors), int(colors.stride(0)),
                                           _dev_ptr(img), None, None, _stream_ptr(bf.device)), "slm_gf_render")
         ctx.last_n = bf.c.N

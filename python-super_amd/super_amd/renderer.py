@@ -7,13 +7,17 @@ the two ``Surfels`` methods that call it (``super/nodes.py:630-650``), over libs
 The image is the forward blend of Pulsar's paper (Lassner & Zollhoefer, CVPR 2021) at the parameters of the
 reference's call; include/super_lm.h and DESIGN.md ("Renderer") state it.  pytorch3d is not available on ROCm, so
 parity with Pulsar itself is NOT pinned: every convention that is only a reading of Pulsar is one constant or one
-short function below, marked "unpinned".  ``Pulsar`` is forward only: inputs that require grad are refused.
+short function below, marked "unpinned".  ``Pulsar(opt)`` is forward only: inputs that require grad are refused.
+``Pulsar(opt, differentiable=True)`` puts the render in the autograd graph (``render_differentiable``): gradients go to
+the points and the colours, the exact derivative of THIS blend (``slm_render_backward_ex``), not Pulsar's own backward
+(unpinned, hence opt-in).  The context keeps only its last forward; the backward of an earlier render re-renders its
+saved inputs first (renders are bitwise reproducible, so the hit sets are the same).
 
 The render loss of GraphFit (``opt.render_loss``, deform_mesh.py:113-123) has two native pieces here:
 ``render_backward`` -- dL/dpoints of the last render on a context, the exact derivative of THIS blend (Pulsar's own
 backward is not pinned) -- and ``ssim_render_loss`` -- monodepth2's SSIM-11 loss with the reference's mask,
 selection and weight, and its image gradient, in float64 (the reference runs float32).  ``GraphFit(opt,
-native_render_loss=True)`` chains them; there is no autograd ``Function`` around the renderer.
+native_render_loss=True)`` chains them.
 """
 from __future__ import annotations
 
@@ -21,6 +25,7 @@ import ctypes as C
 import math
 
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import _lib
 from ._lib import SlmRenderParams
@@ -72,6 +77,7 @@ class RenderContext:
             raise _lib.SuperLMError("no HIP device visible: super_amd has no CPU fallback")
         self.H, self.W, self.cap = int(H), int(W), 0
         self.last_n = 0          # point count of the last render (the rows render_backward writes)
+        self.serial = 0          # bumped by every render on this context (render_differentiable's recompute rule)
         self.h = C.c_void_p()
         self.reserve(max_points)
 
@@ -117,6 +123,10 @@ def render_points(ctx, params, points, colors, with_info=False):
     """Render (N,3) ``points`` (float32 or float64) with (N,3) ``colors``: (h,w,3) float32 on the device, and with
     ``with_info`` also the (h,w) int32 front-most row (-1: nothing hit) and hit count (<= n_track)."""
     _check_no_grad(points, colors)
+    return _render(ctx, params, points, colors, with_info)
+
+
+def _render(ctx, params, points, colors, with_info=False):
     dev = points.device
     n = int(points.shape[0])
     if points.dim() != 2 or points.shape[1] != 3:
@@ -135,6 +145,7 @@ def render_points(ctx, params, points, colors, with_info=False):
         cnt = torch.empty_like(fid)
     ptr = lambda t: _dev_ptr(t) if t is not None and t.numel() else None
     ctx.last_n = 0
+    ctx.serial += 1
     _lib.check(ctx.lib.slm_render_points(ctx.h, C.byref(params), n, ptr(pts), ptr(col), stride, _dev_ptr(img),
                                          ptr(fid), ptr(cnt), _stream_ptr(dev)), "slm_render_points")
     ctx.last_n = n
@@ -155,6 +166,69 @@ def render_backward(ctx, params, grad_image):
     _lib.check(ctx.lib.slm_render_backward(ctx.h, C.byref(params), _dev_ptr(g), _dev_ptr(out) if out.numel() else None,
                                            _stream_ptr(dev)), "slm_render_backward")
     return out
+
+
+def render_backward_ex(ctx, params, grad_image, points=True, colors=True):
+    """``render_backward`` with the colour gradient: (dL/dpoints or None, dL/dcolors or None), each (N,3) float64, for
+    the last render on ``ctx`` (include/super_lm.h ``slm_render_backward_ex``: dL/dc_k = sum over the pixels k takes
+    part in of g w_k / W; the gradient passes the float32 cast of the colours).  Rows as ``render_backward``."""
+    if not (points or colors):
+        raise ValueError("render_backward_ex: request the points' gradient, the colours' or both")
+    g = torch.as_tensor(grad_image).detach()
+    dev = g.device
+    if tuple(g.shape) != (params.height, params.width, 3):
+        raise ValueError(f"grad_image must be ({params.height},{params.width},3), got {tuple(g.shape)}")
+    g = g.to(dtype=torch.float64).contiguous()
+    gp = torch.empty((ctx.last_n, 3), dtype=torch.float64, device=dev) if points else None
+    gc = torch.empty((ctx.last_n, 3), dtype=torch.float64, device=dev) if colors else None
+    ptr = lambda t: _dev_ptr(t) if t is not None and t.numel() else None
+    _lib.check(ctx.lib.slm_render_backward_ex(ctx.h, C.byref(params), _dev_ptr(g), ptr(gp), ptr(gc), _stream_ptr(dev)),
+               "slm_render_backward_ex")
+    return gp, gc
+
+
+class _Render(torch.autograd.Function):
+    """The render as an autograd node.  It keeps its inputs (``save_for_backward``: autograd's version check catches an
+    in-place change after the forward), a copy of its parameters, its context object and the context's serial after
+    its forward.  If another render has run on that context since -- any render, on the same handle or on one
+    ``reserve`` recreated -- the backward re-renders the saved inputs into it first."""
+
+    @staticmethod
+    def forward(fctx, rctx, params, points, colors):
+        img = _render(rctx, params, points, colors)
+        fctx.rctx, fctx.params, fctx.serial = rctx, SlmRenderParams.from_buffer_copy(params), rctx.serial
+        fctx.save_for_backward(points, colors)
+        return img
+
+    @staticmethod
+    @once_differentiable
+    def backward(fctx, grad_image):
+        points, colors = fctx.saved_tensors
+        want_p, want_c = fctx.needs_input_grad[2], fctx.needs_input_grad[3]
+        if not (want_p or want_c):
+            return None, None, None, None
+        rctx, params = fctx.rctx, fctx.params
+        if rctx.serial != fctx.serial:
+            _render(rctx, params, points, colors)
+            fctx.serial = rctx.serial
+        gp, gc = render_backward_ex(rctx, params, grad_image, want_p, want_c)
+        if gp is not None:
+            gp = gp.to(device=points.device, dtype=points.dtype)
+        if gc is not None:
+            full = torch.zeros(colors.shape, dtype=colors.dtype, device=colors.device)
+            full[:, :3] = gc
+            gc = full
+        return None, None, gp, gc
+
+
+def render_differentiable(ctx, params, points, colors):
+    """``render_points`` as a node of the autograd graph: (h,w,3) float32 image; gradients to ``points`` (N,3) float32
+    or float64 and to ``colors`` (N,>=3) of any float dtype (columns beyond 3 get 0), each in its input's dtype and
+    shape and only where ``needs_input_grad`` asks.  The gradient is ``render_backward_ex``'s, for the grad_image cast
+    to float64; computed on the current stream.  ``ctx`` may be shared with other renders (see ``_Render``)."""
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError(f"points must be (N,3), got {tuple(points.shape)}")
+    return _Render.apply(ctx, params, points, colors)
 
 
 def _ssim_args(img_hwc, target_chw):
@@ -196,12 +270,18 @@ def ssim_render_loss(img_hwc, target_chw, weight, with_grad=True):
 
 class Pulsar:
     """``Pulsar(opt)`` as in the reference: ``forward(inputs, data, colors=None, view_scale=1.0, rad=0.01,
-    bg_col=...)`` returns the (h,w,3) float32 image on the device, channels last (callers permute it)."""
+    bg_col=...)`` returns the (h,w,3) float32 image on the device, channels last (callers permute it).
 
-    def __init__(self, opt) -> None:
+    ``Pulsar(opt, differentiable=True)``: with grad enabled and points or colours that require grad, the image is in
+    the autograd graph (``render_differentiable``); other inputs take the plain forward.  ``bg_col`` and ``rad`` are
+    constants: a tensor of either that requires grad is refused.  Plain ``Pulsar(opt)`` refuses inputs that require
+    grad (its gradient is this blend's, not Pulsar's own backward, which is unpinned)."""
+
+    def __init__(self, opt, differentiable=False) -> None:
         self.height = opt.height
         self.width = opt.width
         self.gamma = GAMMA
+        self.differentiable = bool(differentiable)
         self._ctx = None
 
     def to(self, *args, **kwargs):      # models.renderer = Pulsar(opt).to(device) in InitNets
@@ -219,9 +299,22 @@ class Pulsar:
                with_info=False):
         if colors is None:
             colors = data.colors
+        points = data.points
+        if self.differentiable and torch.is_grad_enabled():
+            for name, t in (("bg_col", bg_col), ("rad", rad)):
+                if torch.is_tensor(t) and t.requires_grad:
+                    raise RuntimeError(f"super_amd.renderer.Pulsar: {name} is a constant of the render (no gradient); "
+                                       f"pass a {name} that does not require grad")
+            if any(torch.is_tensor(t) and t.requires_grad for t in (points, colors)):
+                if with_info:
+                    raise ValueError("super_amd.renderer.Pulsar: with_info is not available for a render in the graph")
+                params = render_params(inputs["K"], self.height, self.width, view_scale, rad, bg_col)
+                return render_differentiable(self.context(view_scale), params, points, colors)
+        if self.differentiable:        # not in the graph: the plain forward of the detached inputs
+            points, colors = points.detach(), colors.detach()
         with torch.no_grad():
             params = render_params(inputs["K"], self.height, self.width, view_scale, rad, bg_col)
-            return render_points(self.context(view_scale), params, data.points, colors, with_info)
+            return render_points(self.context(view_scale), params, points, colors, with_info)
 
     def forward(self, inputs, data, colors=None, view_scale=1.0, rad=0.01, bg_col=torch.tensor([0.0, 0.0, 0.0])):
         return self.render(inputs, data, colors, view_scale, rad, bg_col)

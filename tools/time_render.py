@@ -2,7 +2,9 @@
 (opt.renderer_rad = 2e-4) and at 10x, and one GraphFit frame (10 SGD iterations, sf_corr) with and without
 sf_corr_match_renderimg, the flow network an identity stand-in (returns a zero flow at once).  The render loss: at
 both radii one forward + SSIM loss with its image gradient + renderer backward (and the loss + backward alone, after
-a forward), and one GraphFit frame (10 SGD iterations) with opt.render_loss (native_render_loss=True).
+a forward), the same with the colour gradient as well (slm_render_backward_ex), one differentiable render + backward
+through torch (Pulsar(opt, differentiable=True), gradients to the points and the colours), and one GraphFit frame
+(10 SGD iterations) with opt.render_loss (native_render_loss=True).
 
     python tools/time_render.py [--reps 30] [--out gpu_out.json]
 
@@ -48,7 +50,7 @@ def main():
     from oracle import graphfit_oracle as gfo
     from super_amd import synth
     from super_amd.deform_mesh import GraphFit
-    from super_amd.renderer import Pulsar, render_backward, render_params, ssim_render_loss_device
+    from super_amd.renderer import Pulsar, render_backward, render_backward_ex, render_params, ssim_render_loss_device
 
     res = {}
     sc = synth.make_scene(N=300_000, J=512, H=480, W=640, seed=5, src_border=2)
@@ -84,8 +86,25 @@ def main():
         res["render_fwd_ssim_bwd_" + name] = _time(fwd_loss_bwd, a.reps)
         fwd_loss_bwd()
         res["render_ssim_bwd_" + name] = _time(loss_bwd, a.reps)
+        def loss_bwd_colors():
+            _, g = ssim_render_loss_device(loss_bwd.img, tgt, 1e-4)
+            return render_backward_ex(ctx, p, g)
+
+        fwd_loss_bwd()
+        res["render_ssim_bwd_colors_" + name] = _time(loss_bwd_colors, a.reps)
         img = loss_bwd.img
         res["render_ssim_" + name] = _time(lambda: ssim_render_loss_device(img, tgt, 1e-4), a.reps)
+        # through torch: Pulsar(opt, differentiable=True), the SSIM image gradient as the image's grad
+        rd = Pulsar(SimpleNamespace(height=sc.H, width=sc.W), differentiable=True)
+        pts_g, cols_g = pts.clone().requires_grad_(True), cols.clone().requires_grad_(True)
+        _, g_img = ssim_render_loss_device(img, tgt, 1e-4)
+        g_img32 = g_img.float()
+
+        def autograd_fwd_bwd():
+            out = rd(inputs, SimpleNamespace(points=pts_g, colors=cols_g), rad=rad)
+            out.backward(g_img32)
+
+        res["render_autograd_fwd_bwd_colors_" + name] = _time(autograd_fwd_bwd, a.reps)
         out, _ = ssim_render_loss_device(img, tgt, 1e-4, with_grad=False)
         res["render_ssim_" + name]["kept"] = int(out[1])
     # algorithmic bytes: positions (f64) + colours read, one 8-byte key per tile entry written and read, image written
