@@ -126,6 +126,21 @@ struct PinnedBuf {
 constexpr int kLossBlocks = 512;   // data-loss partial sums per slot
 constexpr int kRegBlocksMax = 64;
 
+// The form of the data term: which plan the bind prepares and which kernels the LM entry points launch.
+enum class DataForm {
+  none,        // no data term (use_data 0) or no surfels
+  tuple,       // num_neighbors 4: tuple-sorted positions, k_data_eval + k_data_gram, then k_front_assemble / k_band_assemble
+  pairs,       // any other num_neighbors on the multifrontal solver: k_data_grad_pairs into per-pair records, k_pair_scatter
+  per_entry,   // data_path 1, J >= 65 536, a K-generic frame on the block-banded solver: k_data_grad<K>'s atomics
+};
+// a frame's form, decided at bind (a plan that comes out empty leaves the slot per_entry: bind_model_part)
+DataForm data_form_of(const slm_config& c, const slm_frame& f) {
+  if (!c.use_data || f.N <= 0) return DataForm::none;
+  if (c.data_path == 1 || f.J >= 65536) return DataForm::per_entry;
+  if (f.K == SLM_K) return DataForm::tuple;
+  return c.solver_path != 1 ? DataForm::pairs : DataForm::per_entry;
+}
+
 struct Slot {
   FrameDev h{};                 // host mirror of the device descriptor
   size_t cap_beta = 0, cap_vec = 0, cap_band = 0, cap_linv = 0, cap_npk = 0, cap_tpn = 0, cap_tpx = 0, cap_ev = 0;
@@ -675,8 +690,8 @@ int slm_bind_frame(slm_solver* s, int32_t slot, const slm_frame* f, void* stream
 static int bind_model_part(slm_solver* s, int32_t slot, const slm_frame* f, hipStream_t st, PrepBuffers* prep) {
   if (slot < 0 || slot >= (int)s->slots.size()) return fail(SLM_ERR_INVALID, "slm_bind_frame: bad slot");
   // num_neighbors (reference options.py:49, README.md:175; super/loss.py:213-220 and super/utils.py:30-36 are K-generic):
-  // 4 takes the tuple-sorted MFMA path; any other value in 1..8 the per-entry-atomics data path with the block-banded
-  // solve (what data_path = 1 runs), like a frame of >= 65 536 nodes
+  // 4 takes the tuple-sorted MFMA path; any other value in 1..8 the K-generic pair path on the multifrontal solver, or
+  // the per-entry atomics on the block-banded one (data_form_of)
   if (f->K < 1 || f->K > 8) return fail(SLM_ERR_UNSUPPORTED, "slm_bind_frame: num_neighbors must be in 1..8");
   if (f->K_ED < 1 || f->K_ED > SLM_MAX_KED)
     return fail(SLM_ERR_UNSUPPORTED, "slm_bind_frame: num_ED_neighbors must be in 1..8");
@@ -739,7 +754,8 @@ static int bind_model_part(slm_solver* s, int32_t slot, const slm_frame* f, hipS
   h.v1_ready = 0;
   h.vk_ready = 0;
   uint64_t dev_knn_hash = 0, dev_graph_hash = 0;   // coupling-graph hashes computed by prep_v1 on the device
-  if (s->cfg.use_data && s->cfg.data_path != 1 && f->K == SLM_K && f->J < 65536 && f->N > 0) {
+  DataForm form = data_form_of(s->cfg, *f);
+  if (form == DataForm::tuple) {
     V1Sizes sz;
     HIPCHK(prep_v1(prep, *f, sl.plan, &sz, st));
     if (sz.bad_knn)
@@ -776,7 +792,7 @@ static int bind_model_part(slm_solver* s, int32_t slot, const slm_frame* f, hipS
         h.v2_ready = 1;
       }
     }
-  } else if (s->cfg.use_data && s->cfg.data_path != 1 && s->cfg.solver_path != 1 && f->J < 65536 && f->N > 0) {
+  } else if (form == DataForm::pairs) {
     // num_neighbors != 4 (round 6): the K-generic pair path -- the coupled-pair list and every surfel's pair indices from
     // one sort (prep_pairs), the multifrontal solver on that list, the data term through per-pair records (pairbuf)
     PairSizes sz;
@@ -793,38 +809,40 @@ static int bind_model_part(slm_solver* s, int32_t slot, const slm_frame* f, hipS
       h.sf_perm = sl.pplan.sf_perm;
       h.vk_ready = 1;
     }
-  } else if (s->cfg.use_data && f->N > 0) {
-    // the per-entry atomics path (data_path 1, J >= 65536) dereferences the tables too: same refusal
+  } else if (form == DataForm::per_entry) {
+    // the per-entry atomics dereference the tables too: same refusal
     // (use_data 0: ensure_band's pass over the tables checks them)
     bool bad = false;
     HIPCHK(prep_check_knn(prep, *f, &bad, st));
     if (bad) return fail(SLM_ERR_INVALID, kBadKnn);
   }
+  // an empty plan: the slot runs without one, as dims_of counts it
+  if ((form == DataForm::tuple && !h.v1_ready) || (form == DataForm::pairs && !h.vk_ready)) form = DataForm::per_entry;
   // share of this rank when the frame is sharded over several GPUs (whole frame otherwise)
   {
-    const int n_wg = (h.v1_ready ? h.n_pos + 255 : 0) / 256;
+    const int n_wg = (form == DataForm::tuple ? h.n_pos + 255 : 0) / 256;
     h.wg_lo = (int32_t)((int64_t)n_wg * s->rank / s->world);
     h.wg_hi = (int32_t)((int64_t)n_wg * (s->rank + 1) / s->world);
     h.sf_lo = (int32_t)((int64_t)f->N * s->rank / s->world);
     h.sf_hi = (int32_t)((int64_t)f->N * (s->rank + 1) / s->world);
     h.pairbuf = nullptr;
     if (s->shard_mode) {
-      if (!h.v1_ready && !h.vk_ready)
+      if (form != DataForm::tuple && form != DataForm::pairs)
         return fail(SLM_ERR_UNSUPPORTED, "slm_bind_frame: sharded frames need the multifrontal data paths "
                                          "(data_path 0 or 2, J < 65536)");
       HIPCHK(grow(sl.pairbuf, sl.cap_pairbuf, (size_t)h.n_blocks * SLM_WREC + SLM_VK_TAIL + 2));
       h.pairbuf = sl.pairbuf;
       // records (or per-run Grams) of the other ranks' workgroups stay zero for the whole frame
       if (h.v2_ready) HIPCHK(hipMemsetAsync(h.wgslab, 0, sizeof(double) * SLM_WREC * (size_t)h.n_wblk, st));
-      else if (h.v1_ready) HIPCHK(hipMemsetAsync(h.slab, 0, sizeof(double) * SLM_SLAB_STRIDE * (size_t)h.n_runs, st));
-    } else if (h.vk_ready) {   // the K-generic pair path always assembles through the pair records
+      else if (form == DataForm::tuple) HIPCHK(hipMemsetAsync(h.slab, 0, sizeof(double) * SLM_SLAB_STRIDE * (size_t)h.n_runs, st));
+    } else if (form == DataForm::pairs) {   // the K-generic pair path always assembles through the pair records
       HIPCHK(grow(sl.pairbuf, sl.cap_pairbuf, (size_t)h.n_blocks * SLM_WREC + SLM_VK_TAIL + 2));
       h.pairbuf = sl.pairbuf;
     }
   }
   // nested-dissection plan (symbolic analysis on the host from the coupled-pair list)
   h.nd_ready = 0;
-  if ((h.v1_ready || h.vk_ready) && s->cfg.solver_path != 1) {
+  if ((form == DataForm::tuple || form == DataForm::pairs) && s->cfg.solver_path != 1) {
     // The symbolic plan depends only on the coupling graph (node KNN table + coupled-pair list): reuse it while the
     // graph is unchanged.  The graph's hash comes from the device with the sizes (prep_v1's one read-back): a frame
     // whose graph is the slot's cached one reads nothing else back -- the lists only travel to the host when the
@@ -1331,17 +1349,22 @@ struct BatchDims {
   int maxN = 0, maxJKe = 0, nt_max = 0, wb_cap = 0, n_reg_part = 0;
   int max_pos = 0, max_blocks = 0, maxP = 0;
   int K = 0;        // num_neighbors of the batch's slots (-1: they differ -- refused by the callers of the per-surfel kernels)
-  bool v1 = true;   // every slot of the batch has a tuple-sorted plan
-  bool vk = true;   // every slot of the batch takes the K-generic pair path (num_neighbors != 4 on the multifrontal solver)
   int gram_variants = 0;   // bit0: workgroup-merged records in use, bit1: per-run slab in use
-  bool nd = true;   // every slot of the batch has a nested-dissection plan
+  bool nd = true;   // every slot of the batch has a nested-dissection plan (false: the block-banded solver)
+  DataForm form = DataForm::none;   // the batch's data-term form; the launch arguments that follow from it:
+  const int* reuse = nullptr;   // k_data_eval / k_data_gram / k_iter_begin_nd skip the slots whose records are kept
+  bool fused_begin = false;     // the LM loop's zeroing rides on the Jacobian pass (k_begin_and_gram)
+  int* accept_reuse = nullptr;  // k_accept keeps / clears the slots' reuse flags (the form writes records)
+  int accept_eval = 0;          // k_accept: the loss pass left {r, c} in the evaluation buffer (k_data_eval)
   int max_tasks = 0;   // tasks of the persistent task-graph solver (maximum over the batch)
   // hybrid solve: every slot has the same number of levels and the same top-of-tree cut (-1: not available)
   int hybrid_cut = -2, hybrid_levels = -1, max_top_tasks = 0;
   std::vector<NDLevelSched> sched;   // per-level launch bounds over the batch
 };
-BatchDims dims_of(slm_solver* s, int first, int n) {
+// band: the block-banded solver whatever the slots' plans (slm_assemble)
+BatchDims dims_of(slm_solver* s, int first, int n, bool band = false) {
   BatchDims d;
+  bool all_v1 = true, all_vk = true;
   for (int i = first; i < first + n; ++i) {
     const FrameDev& h = s->slots[i].h;
     d.maxN = std::max(d.maxN, h.f.N);
@@ -1351,8 +1374,8 @@ BatchDims dims_of(slm_solver* s, int first, int n) {
     d.wb_cap = std::max(d.wb_cap, h.wb);
     d.max_pos = std::max(d.max_pos, h.n_pos);
     d.max_blocks = std::max(d.max_blocks, h.n_blocks);
-    d.v1 = d.v1 && h.v1_ready;
-    d.vk = d.vk && h.vk_ready;
+    all_v1 = all_v1 && h.v1_ready;
+    all_vk = all_vk && h.vk_ready;
     if (h.v1_ready) d.gram_variants |= h.v2_ready ? 1 : 2;
     d.nd = d.nd && h.nd_ready;
     d.max_tasks = std::max(d.max_tasks, h.nd_ready ? h.n_dag_tasks : 0);
@@ -1364,6 +1387,18 @@ BatchDims dims_of(slm_solver* s, int first, int n) {
     }
     d.maxP = std::max(d.maxP, h.P);
   }
+  d.nd = d.nd && !band;
+  // tuple-sorted on either solver; the pair records need the multifrontal one; per-entry atomics otherwise
+  const slm_config& c = s->cfg;
+  d.form = all_v1 ? DataForm::tuple : (d.nd && all_vk) ? DataForm::pairs : c.use_data ? DataForm::per_entry : DataForm::none;
+  const bool tuple = d.form == DataForm::tuple;
+  // (records of the Jacobian pass are reused after a rejected step on the multifrontal path, where the assembly re-reads
+  //  them; the banded path adds into the band in place)
+  if (d.nd && tuple && c.phase_test && !s->no_reuse) d.reuse = s->reuse_dev + first;
+  // (round 6) the zeroing rides on the Jacobian pass's launch when every slot takes the workgroup-merged records
+  d.fused_begin = d.nd && tuple && d.gram_variants == 1 && d.max_pos > 0 && s->fuse_begin;
+  if (tuple && c.phase_test) d.accept_reuse = s->reuse_dev + first;
+  d.accept_eval = tuple ? 1 : 0;
   if (d.nd) {
     for (int i = first; i < first + n; ++i) {
       const auto& sc = s->slots[i].nd.sched;
@@ -1453,48 +1488,58 @@ int enqueue_front_solve(slm_solver* s, const FrameDev* fr, int n, const BatchDim
   return mode;
 }
 
-// zero the fronts of slots [first, first+n) and assemble JtJ / jtl into them
-// (the data term takes the same path as enqueue_lm_iteration's: tuple-sorted for K = 4, the pair records otherwise)
-int enqueue_assemble_nd(slm_solver* s, int first, int n, const BatchDims& d, hipStream_t st) {
-  const FrameDev* fr = s->frames_dev + first;
-  if (s->cfg.use_data && !d.v1 && !d.vk)   // (nd_ready requires one of the two: unreachable today)
-    return fail(SLM_ERR_UNSUPPORTED, "slm_solve: a multifrontal slot without a multifrontal data path");
-  launch_iter_begin_nd(fr, n, st, nullptr, -2);   // zeroes the pivot columns of the fronts of all n slots in one launch
-  if (s->cfg.use_data) {
-    if (d.v1) {
-      launch_data_eval(fr, n, kLossBlocks, s->cfg.w_data, 2, st);   // {r, c} at the current beta (clobbers the loss partials)
-      launch_data_gram(fr, n, d.max_pos, s->cfg.w_data, d.gram_variants, st);
-      launch_front_assemble(fr, n, d.max_blocks, st);
-    } else {
-      launch_data_grad_pairs(fr, n, d.maxN, d.K, s->cfg.w_data, st);   // K-generic: per-pair records (zeroed, then filled)
-      launch_pair_scatter(fr, n, d.max_blocks, st);                    // records -> fronts + jtl
-    }
-  }
-  launch_reg_grad_nd(fr, n, d.maxP / 7, s->cfg.use_arap, s->cfg.w_arap, s->cfg.use_rot, s->cfg.w_rot, st);
-  if (!s->cfg.use_arap && !s->cfg.use_rot) launch_front_load_rhs(fr, n, d.maxP, st);   // (else k_reg_grad_nd did it)
-  return SLM_OK;
+// The stages of an LM step in the batch's data form and solver form; the entry points differ only in their arguments.
+// Zeroing of the normal matrix (k_iter_begin_nd / k_iter_begin): `reuse` slots keep their records, `dag_cut` what of the
+// task graph's state is reset with it (dag_cut_of; -2 nothing), `fused` leaves it to the Jacobian pass.
+void enqueue_zero(const FrameDev* fr, int n, const BatchDims& d, hipStream_t st, const int* reuse, int dag_cut, bool fused) {
+  if (!d.nd) launch_iter_begin(fr, n, st);
+  else if (!fused) launch_iter_begin_nd(fr, n, st, reuse, dag_cut);
 }
 
-void enqueue_assemble(slm_solver* s, const FrameDev* fr, int n, const BatchDims& d, hipStream_t st) {
-  launch_iter_begin(fr, n, st);
-  if (s->cfg.use_data) {
-    if (d.v1) {
-      launch_data_eval(fr, n, kLossBlocks, s->cfg.w_data, 2, st);
-      launch_data_gram(fr, n, d.max_pos, s->cfg.w_data, d.gram_variants, st);
-      launch_band_assemble(fr, n, d.max_blocks, st);
-    } else {
-      launch_data_grad(fr, n, d.maxN, d.K, s->cfg.w_data, st);
-    }
+// Jacobian pass of the data term.  Tuple-sorted: k_data_eval in `eval_mode` first (-1: none, the evaluation buffer already
+// holds {r, c} at beta), then the Grams (with the zeroing when `fused`); the K-generic forms: records or per-entry atomics.
+void enqueue_jacobian(slm_solver* s, const FrameDev* fr, int n, const BatchDims& d, hipStream_t st, int eval_mode,
+                      const int* reuse, int dag_cut, bool fused) {
+  const double w = s->cfg.w_data;
+  switch (d.form) {
+    case DataForm::tuple:
+      if (eval_mode >= 0) launch_data_eval(fr, n, kLossBlocks, w, eval_mode, st, reuse);
+      if (fused) launch_begin_and_gram(fr, n, d.max_pos, w, st, reuse, dag_cut);
+      else launch_data_gram(fr, n, d.max_pos, w, d.gram_variants, st, reuse);
+      break;
+    case DataForm::pairs: launch_data_grad_pairs(fr, n, d.maxN, d.K, w, st); break;   // per-pair records (zeroed, then filled)
+    case DataForm::per_entry: launch_data_grad(fr, n, d.maxN, d.K, w, st); break;
+    case DataForm::none: break;
   }
-  launch_reg_grad(fr, n, d.maxJKe, s->cfg.use_arap, s->cfg.w_arap, s->cfg.use_rot, s->cfg.w_rot, st);
 }
 
-void enqueue_loss(slm_solver* s, const FrameDev* fr, int n, const BatchDims& d, int use_delta,
-                  hipStream_t st) {
-  if (s->cfg.use_data) launch_data_loss(fr, n, kLossBlocks, d.K, s->cfg.w_data, use_delta, st);
-  if (d.n_reg_part > 0)
-    launch_reg_loss(fr, n, d.n_reg_part, s->cfg.use_arap, s->cfg.w_arap, s->cfg.use_rot,
-                    s->cfg.w_rot, use_delta, st);
+// Scatter of the data term's records into the solver's storage, then the regularisers.  A sharded step splits it around
+// the exchange of the pair records: before_exchange reduces the tuple-sorted Grams to pair records (the pair form wrote
+// them already), after_exchange scatters the exchanged records and adds the regularisers.
+enum class Shard { whole, before_exchange, after_exchange };
+void enqueue_scatter(slm_solver* s, const FrameDev* fr, int n, const BatchDims& d, hipStream_t st, Shard part) {
+  const slm_config& c = s->cfg;
+  const bool tuple = d.form == DataForm::tuple;
+  if (part == Shard::before_exchange) {
+    if (tuple) launch_pair_reduce(fr, n, d.max_blocks, st);
+    return;
+  }
+  if (part == Shard::after_exchange || d.form == DataForm::pairs) launch_pair_scatter(fr, n, d.max_blocks, st);
+  else if (tuple && d.nd) launch_front_assemble(fr, n, d.max_blocks, st);
+  else if (tuple) launch_band_assemble(fr, n, d.max_blocks, st);
+  if (d.nd) {
+    launch_reg_grad_nd(fr, n, d.maxP / 7, c.use_arap, c.w_arap, c.use_rot, c.w_rot, st);
+    if (!c.use_arap && !c.use_rot) launch_front_load_rhs(fr, n, d.maxP, st);   // (else k_reg_grad_nd did it)
+  } else {
+    launch_reg_grad(fr, n, d.maxJKe, c.use_arap, c.w_arap, c.use_rot, c.w_rot, st);
+  }
+}
+
+// Data loss at the trial point beta + delta (tuple-sorted: k_data_eval's loss pass, whose {r, c} feed the next Jacobian
+// pass) or, `at_beta` (slm_loss), k_data_loss at beta for every form.
+void enqueue_data_loss(slm_solver* s, const FrameDev* fr, int n, const BatchDims& d, hipStream_t st, bool at_beta) {
+  if (d.form == DataForm::tuple && !at_beta) launch_data_eval(fr, n, kLossBlocks, s->cfg.w_data, 0, st);
+  else if (d.form != DataForm::none) launch_data_loss(fr, n, kLossBlocks, d.K, s->cfg.w_data, at_beta ? 0 : 1, st);
 }
 }  // namespace
 
@@ -1532,7 +1577,7 @@ static int shard_dims(slm_solver* s, int n_frames, BatchDims& d) {
   int rc = check_slots(s, 0, n_frames);
   if (rc) return rc;
   d = dims_of(s, 0, n_frames);
-  if (!d.nd || !(d.v1 || d.vk))
+  if (!d.nd || (d.form != DataForm::tuple && d.form != DataForm::pairs))
     return fail(SLM_ERR_UNSUPPORTED, "sharded LM step: every slot needs a multifrontal data path (tuple-sorted or K-generic) and the ND solver");
   return SLM_OK;
 }
@@ -1543,17 +1588,9 @@ int slm_lm_grad_local(slm_solver* s, int32_t n_frames, void* stream) {
   if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
   const FrameDev* fr = s->frames_dev;
-  const int* reuse = (d.v1 && s->cfg.phase_test && !s->no_reuse) ? s->reuse_dev : nullptr;
-  launch_iter_begin_nd(fr, n_frames, st, reuse, -2);
-  if (s->cfg.use_data) {
-    if (d.v1) {
-      launch_data_eval(fr, n_frames, kLossBlocks, s->cfg.w_data, 1, st, reuse);   // (only slots whose buffer is not the current beta's)
-      launch_data_gram(fr, n_frames, d.max_pos, s->cfg.w_data, d.gram_variants, st, reuse);
-      launch_pair_reduce(fr, n_frames, d.max_blocks, st);
-    } else {
-      launch_data_grad_pairs(fr, n_frames, d.maxN, d.K, s->cfg.w_data, st);   // K-generic: this rank's share of the surfel list, straight into the pair records
-    }
-  }
+  enqueue_zero(fr, n_frames, d, st, d.reuse, -2, false);
+  enqueue_jacobian(s, fr, n_frames, d, st, 1, d.reuse, -2, false);   // (k_data_eval: only slots whose buffer is not the current beta's)
+  enqueue_scatter(s, fr, n_frames, d, st, Shard::before_exchange);
   HIPCHK(hipGetLastError());
   return SLM_OK;
 }
@@ -1564,10 +1601,7 @@ int slm_lm_solve(slm_solver* s, int32_t n_frames, void* stream) {
   if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
   const FrameDev* fr = s->frames_dev;
-  const slm_config& c = s->cfg;
-  if (c.use_data) launch_pair_scatter(fr, n_frames, d.max_blocks, st);
-  launch_reg_grad_nd(fr, n_frames, d.maxP / 7, c.use_arap, c.w_arap, c.use_rot, c.w_rot, st);
-  if (!c.use_arap && !c.use_rot) launch_front_load_rhs(fr, n_frames, d.maxP, st);   // (else k_reg_grad_nd did it)
+  enqueue_scatter(s, fr, n_frames, d, st, Shard::after_exchange);
   enqueue_front_solve(s, fr, n_frames, d, -1.0, st);
   HIPCHK(hipGetLastError());
   return SLM_OK;
@@ -1580,11 +1614,8 @@ int slm_lm_loss_local(slm_solver* s, int32_t n_frames, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   const FrameDev* fr = s->frames_dev;
   const slm_config& c = s->cfg;
-  if (c.use_data) {
-    launch_make_trial(fr, n_frames, d.maxJKe, st);
-    if (d.v1) launch_data_eval(fr, n_frames, kLossBlocks, c.w_data, 0, st);   // this rank's positions: loss partials + the evaluation buffer
-    else launch_data_loss(fr, n_frames, kLossBlocks, d.K, c.w_data, 1, st);   // K-generic: this rank's surfels [sf_lo, sf_hi)
-  }
+  launch_make_trial(fr, n_frames, d.maxJKe, st);
+  enqueue_data_loss(s, fr, n_frames, d, st, false);
   if (d.n_reg_part > 0)
     launch_reg_loss(fr, n_frames, d.n_reg_part, c.use_arap, c.w_arap, c.use_rot, c.w_rot, 1, st);
   HIPCHK(hipGetLastError());
@@ -1596,7 +1627,7 @@ int slm_lm_accept(slm_solver* s, int32_t n_frames, void* stream) {
   int rc = shard_dims(s, n_frames, d);
   if (rc) return rc;
   launch_accept(s->frames_dev, n_frames, s->cfg.phase_test, d.n_reg_part, std::max(s->cfg.num_iterations, 1), (hipStream_t)stream,
-                (d.v1 && s->cfg.phase_test) ? s->reuse_dev : nullptr, (s->cfg.use_data && d.v1) ? 1 : 0);   // (slm_lm_loss_local ran k_data_eval)
+                d.accept_reuse, d.accept_eval);   // (slm_lm_loss_local ran k_data_eval)
   HIPCHK(hipGetLastError());
   return SLM_OK;
 }
@@ -1670,44 +1701,17 @@ static void enqueue_lm_iteration(slm_solver* s, int first, int n, const BatchDim
     evs->push_back(e);
   };
   mark();
-  // (records of the Jacobian pass are reused after a rejected step on the multifrontal path, where the assembly
-  //  re-reads them; the banded path adds into the band in place)
-  const int* reuse = (d.nd && d.v1 && c.phase_test && !s->no_reuse) ? s->reuse_dev + first : nullptr;
-  // (round 6) the zeroing rides on the Jacobian pass's launch when every slot takes the workgroup-merged records
-  const bool fused_begin = d.nd && d.v1 && c.use_data && d.gram_variants == 1 && d.max_pos > 0 && s->fuse_begin;
-  if (d.nd) {
-    if (!fused_begin) launch_iter_begin_nd(fr, n, st, reuse, dag_cut_of(s, n, d));
-  } else {
-    launch_iter_begin(fr, n, st);
-  }
+  const int dag_cut = d.nd ? dag_cut_of(s, n, d) : -2;
+  enqueue_zero(fr, n, d, st, d.reuse, dag_cut, d.fused_begin);
   mark();
-  if (c.use_data) {
-    if (d.v1) {
-      // The Jacobian pass reads {r, c} of every position from the evaluation buffer.  Inside the loop the buffer is
-      // what the loss pass of the previous iteration left at the accepted trial point (a rejected step reuses the
-      // records and runs no Jacobian pass at all); a pass of its own is only needed at the first iteration of a run
-      // (skipped on the device for slots whose buffer is valid) and after a reject when records are not reused.
-      if (first_iteration || (c.phase_test && !reuse)) launch_data_eval(fr, n, kLossBlocks, c.w_data, 1, st, reuse);
-      if (fused_begin) launch_begin_and_gram(fr, n, d.max_pos, c.w_data, st, reuse, dag_cut_of(s, n, d));
-      else launch_data_gram(fr, n, d.max_pos, c.w_data, d.gram_variants, st, reuse);
-    } else if (d.nd && d.vk) {
-      launch_data_grad_pairs(fr, n, d.maxN, d.K, c.w_data, st);   // K-generic: per-pair records (zeroed, then filled)
-    } else {
-      launch_data_grad(fr, n, d.maxN, d.K, c.w_data, st);
-    }
-  }
+  // The Jacobian pass reads {r, c} of every position from the evaluation buffer.  Inside the loop the buffer is what the
+  // loss pass of the previous iteration left at the accepted trial point (a rejected step reuses the records and runs no
+  // Jacobian pass at all); a pass of its own is only needed at the first iteration of a run (skipped on the device for
+  // slots whose buffer is valid) and after a reject when records are not reused.
+  const int eval_mode = (first_iteration || (c.phase_test && !d.reuse)) ? 1 : -1;
+  enqueue_jacobian(s, fr, n, d, st, eval_mode, d.reuse, dag_cut, d.fused_begin);
   mark();
-  if (d.nd) {
-    if (c.use_data) {
-      if (d.v1) launch_front_assemble(fr, n, d.max_blocks, st);
-      else launch_pair_scatter(fr, n, d.max_blocks, st);          // K-generic: records -> fronts + jtl
-    }
-    launch_reg_grad_nd(fr, n, d.maxP / 7, c.use_arap, c.w_arap, c.use_rot, c.w_rot, st);
-    if (!s->cfg.use_arap && !s->cfg.use_rot) launch_front_load_rhs(fr, n, d.maxP, st);   // (else k_reg_grad_nd did it)
-  } else {
-    if (c.use_data && d.v1) launch_band_assemble(fr, n, d.max_blocks, st);
-    launch_reg_grad(fr, n, d.maxJKe, c.use_arap, c.w_arap, c.use_rot, c.w_rot, st);
-  }
+  enqueue_scatter(s, fr, n, d, st, Shard::whole);
   mark();
   // the trial point beta + delta (node_pk_try), the regularisers' loss there and the task graph's abort check: one launch
   const bool tail = c.use_data || d.n_reg_part > 0;
@@ -1716,15 +1720,11 @@ static void enqueue_lm_iteration(slm_solver* s, int first, int n, const BatchDim
   else launch_band_solve(fr, n, d.nt_max, d.wb_cap, -1.0, st);
   if (tail)   // (dag_check 2 behind an XCD-affine task-graph launch: the completion check runs whether or not the abort flag is up)
     launch_after_solve(fr, n, c.use_data ? d.maxP / 7 : 0, d.n_reg_part, c.use_arap, c.w_arap, c.use_rot, c.w_rot,
-                       (d.nd && dag_cut_of(s, n, d) >= -1) ? ((dag_mode > 0 && (dag_mode & 1)) ? 2 : 1) : 0, st);
+                       dag_cut >= -1 ? ((dag_mode > 0 && (dag_mode & 1)) ? 2 : 1) : 0, st);
   mark();
-  if (c.use_data) {
-    if (d.v1) launch_data_eval(fr, n, kLossBlocks, c.w_data, 0, st);   // the loss pass; its {r, c} feed the next Jacobian pass
-    else launch_data_loss(fr, n, kLossBlocks, d.K, c.w_data, 1, st);
-  }
+  enqueue_data_loss(s, fr, n, d, st, false);
   mark();
-  launch_accept(fr, n, c.phase_test, d.n_reg_part, std::max(c.num_iterations, 1), st,
-                (d.v1 && c.phase_test) ? s->reuse_dev + first : nullptr, (c.use_data && d.v1) ? 1 : 0);
+  launch_accept(fr, n, c.phase_test, d.n_reg_part, std::max(c.num_iterations, 1), st, d.accept_reuse, d.accept_eval);
   mark();
 }
 
@@ -1753,7 +1753,7 @@ int slm_run(slm_solver* s, int32_t n_frames, void* stream) {
   // The reuse flag of a slot says "the Gram records in HBM were computed at the slot's CURRENT beta".  k_accept keeps it
   // on every path that writes records (banded path included: a later multifrontal run may then reuse them); a run that
   // wrote none (per-entry atomics) leaves nothing to reuse.
-  if (!(d.v1 && c.phase_test) && n_frames > 0) HIPCHK(hipMemsetAsync(s->reuse_dev, 0, sizeof(int) * n_frames, st));
+  if (!d.accept_reuse) HIPCHK(hipMemsetAsync(s->reuse_dev, 0, sizeof(int) * n_frames, st));
   HIPCHK(hipGetLastError());
   return SLM_OK;
 }
@@ -1884,9 +1884,12 @@ int slm_assemble(slm_solver* s, int32_t slot, double* jtj_dense, double* jtl, vo
   if (rc) return rc;
   rc = ensure_band(s, slot, st);
   if (rc) return rc;
-  const BatchDims d = dims_of(s, slot, 1);
+  const BatchDims d = dims_of(s, slot, 1, true);
+  const FrameDev* fr = s->frames_dev + slot;
   const FrameDev& h = s->slots[slot].h;
-  enqueue_assemble(s, s->frames_dev + slot, 1, d, st);
+  enqueue_zero(fr, 1, d, st, nullptr, -2, false);
+  enqueue_jacobian(s, fr, 1, d, st, 2, nullptr, -2, false);   // (k_data_eval mode 2 clobbers the loss partials)
+  enqueue_scatter(s, fr, 1, d, st, Shard::whole);
   if (jtj_dense) launch_band_to_dense(s->frames_dev, slot, jtj_dense, st);
   if (jtl)
     HIPCHK(hipMemcpyAsync(jtl, h.rhs, sizeof(double) * h.P, hipMemcpyDeviceToDevice, st));
@@ -1902,7 +1905,10 @@ int slm_loss(slm_solver* s, int32_t slot, double* out, void* stream) {
   rc = clear_flags(s, slot, st);
   if (rc) return rc;
   const BatchDims d = dims_of(s, slot, 1);
-  enqueue_loss(s, s->frames_dev + slot, 1, d, 0, st);
+  const FrameDev* fr = s->frames_dev + slot;
+  const slm_config& c = s->cfg;
+  enqueue_data_loss(s, fr, 1, d, st, true);
+  if (d.n_reg_part > 0) launch_reg_loss(fr, 1, d.n_reg_part, c.use_arap, c.w_arap, c.use_rot, c.w_rot, 0, st);
   launch_loss_out(s->frames_dev, slot, d.n_reg_part, out, st);
   HIPCHK(hipGetLastError());
   return SLM_OK;
@@ -1916,15 +1922,13 @@ int slm_solve(slm_solver* s, int32_t slot, double u, double* delta, int32_t* sta
   rc = clear_flags(s, slot, st);
   if (rc) return rc;
   const BatchDims d = dims_of(s, slot, 1);
+  const FrameDev* fr = s->frames_dev + slot;
   const FrameDev& h = s->slots[slot].h;
-  if (d.nd) {
-    rc = enqueue_assemble_nd(s, slot, 1, d, st);
-    if (rc) return rc;
-    enqueue_front_solve(s, s->frames_dev + slot, 1, d, u, st);
-  } else {
-    enqueue_assemble(s, s->frames_dev + slot, 1, d, st);
-    launch_band_solve(s->frames_dev + slot, 1, d.nt_max, d.wb_cap, u, st);
-  }
+  enqueue_zero(fr, 1, d, st, nullptr, -2, false);
+  enqueue_jacobian(s, fr, 1, d, st, 2, nullptr, -2, false);
+  enqueue_scatter(s, fr, 1, d, st, Shard::whole);
+  if (d.nd) enqueue_front_solve(s, fr, 1, d, u, st);
+  else launch_band_solve(fr, 1, d.nt_max, d.wb_cap, u, st);
   HIPCHK(hipMemcpyAsync(delta, h.delta, sizeof(double) * h.P, hipMemcpyDeviceToDevice, st));
   if (status)
     HIPCHK(hipMemcpyAsync(status, &h.st->chol_fail, sizeof(int32_t), hipMemcpyDeviceToDevice, st));
