@@ -141,25 +141,28 @@ DataForm data_form_of(const slm_config& c, const slm_frame& f) {
   return c.solver_path != 1 ? DataForm::pairs : DataForm::per_entry;
 }
 
+// The symbolic-plan cache of a slot.  Surfels that appear / disappear change the pair list a little from frame to frame:
+// the plan covers the union of the lists seen since the node graph last changed, and a frame whose pairs are all in it only
+// needs its own pair -> destination table (a merge of two sorted lists), not a new symbolic analysis (1.7 ms at C2).
+struct PlanCache {
+  NDPlanHost nd;
+  bool valid = false;           // nd is complete and the device holds it
+  uint64_t knn_hash = 0;        // hash of (J, K_ED, node KNN) nd was built for
+  uint64_t frame_hash = 0;      // hash of the coupled-pair list + node KNN of the frame bound last ...
+  int frame_blocks = -1;        // ... and its pair count: the frame the device's destination table and tile kinds are for
+  std::vector<NDDest> frame_dest;   // destinations of that frame's pairs
+  void frame_stale() { frame_hash = 0; frame_blocks = -1; }   // the per-frame device mirrors are not to be trusted; the plan's are
+  void drop_plan() { valid = false; nd.plan_pairs.clear(); frame_stale(); }   // nothing of the plan applies any more
+};
+
 struct Slot {
   FrameDev h{};                 // host mirror of the device descriptor
   size_t cap_beta = 0, cap_vec = 0, cap_band = 0, cap_linv = 0, cap_npk = 0, cap_tpn = 0, cap_tpx = 0, cap_ev = 0;
   V1Plan plan;                  // tuple-sorted assembly buffers (grow-only)
   PairPlan pplan;               // K-generic pair path (num_neighbors != 4): pair keys, per-surfel pair indices, surfel order
-  // nested-dissection plan: host copy + device mirrors (grow-only)
-  NDPlanHost nd;
-  uint64_t nd_hash = 0;         // hash of the coupled-pair list + node KNN of the frame bound last
-  uint64_t nd_knn_hash = 0;     // hash of (J, K_ED, node KNN) the cached plan was built for
-  bool nd_valid = false;
-  // The plan is built for a SUPERSET of the frame's coupled node pairs (the union of the pair lists seen
-  // since the node graph last changed): surfels that appear / disappear change the list a little from
-  // frame to frame, and a frame whose pairs are all in the plan only needs its own pair -> destination
-  // table (a merge of two sorted lists), not a new symbolic analysis (1.7 ms at C2).
-  std::vector<uint32_t> plan_pairs;     // sorted keys the plan's block_dest is indexed by
-  std::vector<NDDest> cur_dest;         // destinations of the bound frame's pairs
-  NDDest* d_cur_dests = nullptr;
+  PlanCache cache;              // nested-dissection plan: host copy; its device mirrors below (grow-only)
+  NDDest* d_cur_dests = nullptr;   // PlanCache::frame_dest on the device
   size_t cap_cur_dests = 0;
-  int cur_n_blocks = -1;
   PinnedBuf<uint32_t> h_pairs;   // read-backs of the bind (pinned)
   PinnedBuf<int32_t> h_knn;
   PinnedBuf<float> h_pts;
@@ -174,7 +177,7 @@ struct Slot {
   int n_piv_tiles = 0, n_pure_tiles = 0;  // pivot-column tiles of the plan / of them pure fill (slm_get_plan_info)
   std::vector<uint8_t> h_tile_kind;      // host sources of the two uploads (kept: the copies are asynchronous)
   std::vector<long long> h_zero_tiles;
-  int32_t* d_ints = nullptr;    // level_start | nodes | eamap | node_front | node_pos | ... | dag_tasks | front_nin
+  int32_t* d_ints = nullptr;    // the plan's int32 arrays, one behind the other (kPlanInts)
   long long* d_dag_trace = nullptr; // diagnostics
   size_t cap_dag_trace = 0;
   int32_t* d_dag_flags = nullptr;   // persistent task-graph solver: ticket, counters, per-tile / per-column flags
@@ -450,9 +453,9 @@ int slm_debug_read(slm_solver* s, int32_t slot, int32_t what, double* host_out, 
   const double* src = nullptr;
   int64_t n = 0;
   switch (what) {
-    case 0: src = sl.ftiles; n = sl.h.nd_ready ? sl.nd.tile_doubles : 0; break;
-    case 1: src = sl.fvec; n = sl.h.nd_ready ? sl.nd.vec_doubles : 0; break;
-    case 2: src = sl.flinv; n = sl.h.nd_ready ? sl.nd.linv_doubles : 0; break;
+    case 0: src = sl.ftiles; n = sl.h.nd_ready ? sl.cache.nd.tile_doubles : 0; break;
+    case 1: src = sl.fvec; n = sl.h.nd_ready ? sl.cache.nd.vec_doubles : 0; break;
+    case 2: src = sl.flinv; n = sl.h.nd_ready ? sl.cache.nd.linv_doubles : 0; break;
     case 3: src = sl.h.delta; n = sl.h.P; break;
     case 4: src = reinterpret_cast<const double*>(sl.h.dag_trace.get()); n = sl.h.dag_trace ? 24 * (int64_t)sl.h.n_dag_tasks : 0; break;
     case 5: src = reinterpret_cast<const double*>(sl.h.dag_tasks.get()); n = sl.h.nd_ready ? sl.h.n_dag_tasks : 0; break;
@@ -674,7 +677,12 @@ inline double bind_trace_threshold() {
   }();
   return th;
 }
-inline void bt_mark() {
+// the stamps of one bind, in order (a stage that does not run leaves none): entry | data-term plan done, its size
+// read-backs included | pair list / node table on the host (read back only when the graph changed) | symbolic plan
+// settled | descriptor on its way | end
+enum BindStamp { BT_ENTRY, BT_DATA_PLAN, BT_READBACK, BT_SYMBOLIC, BT_DESCRIPTOR, BT_END };
+inline void bt_mark(BindStamp stage) {
+  if (stage == BT_ENTRY) g_bt.n = 0;
   if (bind_trace_threshold() >= 0.0 && g_bt.n < 8) g_bt.t[g_bt.n++] = bt_now();
 }
 }  // namespace
@@ -684,10 +692,7 @@ int slm_bind_frame(slm_solver* s, int32_t slot, const slm_frame* f, void* stream
   return bind_frame_impl(s, slot, f, (hipStream_t)stream, s->prep);
 }
 
-// The MODEL-side half of a bind (what depends on sf.points / sf.knn_indices / sf.knn_w / ED_nodes only: the tuple-sorted
-// copies and indices of the data term, the hashes of the coupling graph, the symbolic plan of the solver, the slot's
-// grow-only work buffers).  Leaves the slot UNBOUND; bind_target_part completes it.
-static int bind_model_part(slm_solver* s, int32_t slot, const slm_frame* f, hipStream_t st, PrepBuffers* prep) {
+static int check_model_args(const slm_solver* s, int32_t slot, const slm_frame* f) {
   if (slot < 0 || slot >= (int)s->slots.size()) return fail(SLM_ERR_INVALID, "slm_bind_frame: bad slot");
   // num_neighbors (reference options.py:49, README.md:175; super/loss.py:213-220 and super/utils.py:30-36 are K-generic):
   // 4 takes the tuple-sorted MFMA path; any other value in 1..8 the K-generic pair path on the multifrontal solver, or
@@ -700,43 +705,35 @@ static int bind_model_part(slm_solver* s, int32_t slot, const slm_frame* f, hipS
     return fail(SLM_ERR_INVALID, "slm_bind_frame: fewer nodes (J) than num_neighbors: sf_knn_idx cannot hold K distinct ids");
   if ((f->N > 0 && (!f->sf_points || !f->sf_knn_idx || !f->sf_knn_w)) || !f->ed_points || !f->ed_knn_idx)
     return fail(SLM_ERR_INVALID, "slm_bind_frame: null device pointer");
-  Slot& sl = s->slots[slot];
-  FrameDev& h = sl.h;
-  g_bt.n = 0;
-  bt_mark();                                   // [0] entry
+  return SLM_OK;
+}
 
+// The descriptor back to "nothing bound" for frame f, and the slot's grow-only work buffers at f's sizes.
+static int reset_slot(slm_solver* s, Slot& sl, const slm_frame* f, hipStream_t st) {
+  FrameDev& h = sl.h;
   const int P = 7 * f->J;
   const int nt = (P + SLM_NB - 1) / SLM_NB;
-  // the tile half-bandwidth and the band storage are only needed by the block-banded path
-  // (solver_path 1, a frame without an ND plan, slm_assemble): ensure_band() fills them in on demand
-  int wb = 0;
   sl.band_ready = false;
   h.dag_trace = nullptr;   // a trace buffer is sized for the plan it was enabled on
   h.bound = 0;             // a bind that fails half way leaves the slot unbound (slm_run refuses it)
   h.f = *f;
   h.P = P;
   h.nt = nt;
-  h.wb = wb;
-  h.n_loss_part = s->cfg.use_data ? kLossBlocks : 0;
-  size_t cap_dummy;
-  HIPCHK(grow(h.beta, sl.cap_beta, (size_t)P));
-  {
-    size_t c = sl.cap_npk;
-    HIPCHK(grow(h.node_pk, c, (size_t)2 * SLM_NPK * f->J));
-    sl.cap_npk = c;
-    h.node_pk_try = h.node_pk + (size_t)SLM_NPK * f->J;
-  }
-  {
-    size_t need = (size_t)nt * SLM_NB, c1 = sl.cap_vec, c2 = sl.cap_vec;
-    HIPCHK(grow(h.delta, c1, need));
-    HIPCHK(grow(h.rhs, c2, need));
-    sl.cap_vec = c1 < c2 ? c1 : c2;
-  }
-  h.band = sl.band;   // may be null until ensure_band()
+  // the tile half-bandwidth and the band storage are only needed by the block-banded path
+  // (solver_path 1, a frame without an ND plan, slm_assemble): ensure_band() fills them in on demand
+  h.wb = 0;
+  h.band = sl.band;
   h.linv = sl.linv;
+  h.n_loss_part = s->cfg.use_data ? kLossBlocks : 0;
+  HIPCHK(grow(h.beta, sl.cap_beta, (size_t)P));
+  HIPCHK(grow(h.node_pk, sl.cap_npk, (size_t)2 * SLM_NPK * f->J));
+  h.node_pk_try = h.node_pk + (size_t)SLM_NPK * f->J;
+  size_t cap_delta = sl.cap_vec;   // (delta and rhs share one capacity)
+  HIPCHK(grow(h.delta, cap_delta, (size_t)nt * SLM_NB));
+  HIPCHK(grow(h.rhs, sl.cap_vec, (size_t)nt * SLM_NB));
   if (!h.loss_part) {
-    cap_dummy = 0;
-    HIPCHK(grow(h.loss_part, cap_dummy, (size_t)2 * (kLossBlocks + kRegBlocksMax)));
+    size_t cap = 0;   // (fixed size: allocated once)
+    HIPCHK(grow(h.loss_part, cap, (size_t)2 * (kLossBlocks + kRegBlocksMax)));
     HIPCHK(hipMemsetAsync(h.loss_part, 0, sizeof(double) * 2 * (kLossBlocks + kRegBlocksMax), st));
   }
   if (!h.st) HIPCHK(hipMalloc((void**)&h.st, sizeof(LMState)));
@@ -750,19 +747,28 @@ static int bind_model_part(slm_solver* s, int32_t slot, const slm_frame* f, hipS
     int n = s->cfg.num_iterations > 0 ? s->cfg.num_iterations : 1;
     HIPCHK(hipMalloc((void**)&h.rec, sizeof(slm_iter_record) * n));
   }
-  // tuple-sorted data-term assembly plan (DataLoss.prepare analogue)
+  return SLM_OK;
+}
+
+// The data-term plan of the frame's form (DataLoss.prepare analogue).  form: the form that actually holds -- an empty
+// plan leaves the slot per_entry, as dims_of counts it; the two hashes of the coupling graph come from the device with
+// the plan's sizes.
+struct DataPlan {
+  DataForm form = DataForm::none;
+  uint64_t knn_hash = 0, graph_hash = 0;
+};
+static int bind_data_plan(slm_solver* s, Slot& sl, const slm_frame* f, hipStream_t st, PrepBuffers* prep, DataPlan& out) {
+  FrameDev& h = sl.h;
   h.v1_ready = 0;
   h.vk_ready = 0;
-  uint64_t dev_knn_hash = 0, dev_graph_hash = 0;   // coupling-graph hashes computed by prep_v1 on the device
-  DataForm form = data_form_of(s->cfg, *f);
-  if (form == DataForm::tuple) {
+  out.form = data_form_of(s->cfg, *f);
+  if (out.form == DataForm::tuple) {
     V1Sizes sz;
     HIPCHK(prep_v1(prep, *f, sl.plan, &sz, st));
-    if (sz.bad_knn)
-      return fail(SLM_ERR_INVALID, kBadKnn);
-    dev_knn_hash = sz.knn_hash;
-    dev_graph_hash = sz.graph_hash;
-    bt_mark();                                 // [1] tuple-sorted plan done (its size read-backs included)
+    if (sz.bad_knn) return fail(SLM_ERR_INVALID, kBadKnn);
+    out.knn_hash = sz.knn_hash;
+    out.graph_hash = sz.graph_hash;
+    bt_mark(BT_DATA_PLAN);
     if (sz.n_tuples > 0) {
       h.n_tuples = sz.n_tuples;
       h.n_pos = sz.n_pos;
@@ -792,16 +798,15 @@ static int bind_model_part(slm_solver* s, int32_t slot, const slm_frame* f, hipS
         h.v2_ready = 1;
       }
     }
-  } else if (form == DataForm::pairs) {
-    // num_neighbors != 4 (round 6): the K-generic pair path -- the coupled-pair list and every surfel's pair indices from
-    // one sort (prep_pairs), the multifrontal solver on that list, the data term through per-pair records (pairbuf)
+  } else if (out.form == DataForm::pairs) {
+    // the coupled-pair list and every surfel's pair indices from one sort (prep_pairs), the multifrontal solver on that
+    // list, the data term through per-pair records (pairbuf)
     PairSizes sz;
     HIPCHK(prep_pairs(prep, *f, sl.pplan, &sz, st));
-    if (sz.bad_knn)
-      return fail(SLM_ERR_INVALID, kBadKnn);
-    dev_knn_hash = sz.knn_hash;
-    dev_graph_hash = sz.graph_hash;
-    bt_mark();
+    if (sz.bad_knn) return fail(SLM_ERR_INVALID, kBadKnn);
+    out.knn_hash = sz.knn_hash;
+    out.graph_hash = sz.graph_hash;
+    bt_mark(BT_DATA_PLAN);
     if (sz.n_blocks > 0) {
       h.n_blocks = sz.n_blocks;
       h.blk_key = sl.pplan.blk_key;
@@ -809,258 +814,230 @@ static int bind_model_part(slm_solver* s, int32_t slot, const slm_frame* f, hipS
       h.sf_perm = sl.pplan.sf_perm;
       h.vk_ready = 1;
     }
-  } else if (form == DataForm::per_entry) {
+  } else if (out.form == DataForm::per_entry) {
     // the per-entry atomics dereference the tables too: same refusal
     // (use_data 0: ensure_band's pass over the tables checks them)
     bool bad = false;
     HIPCHK(prep_check_knn(prep, *f, &bad, st));
     if (bad) return fail(SLM_ERR_INVALID, kBadKnn);
   }
-  // an empty plan: the slot runs without one, as dims_of counts it
-  if ((form == DataForm::tuple && !h.v1_ready) || (form == DataForm::pairs && !h.vk_ready)) form = DataForm::per_entry;
-  // share of this rank when the frame is sharded over several GPUs (whole frame otherwise)
-  {
-    const int n_wg = (form == DataForm::tuple ? h.n_pos + 255 : 0) / 256;
-    h.wg_lo = (int32_t)((int64_t)n_wg * s->rank / s->world);
-    h.wg_hi = (int32_t)((int64_t)n_wg * (s->rank + 1) / s->world);
-    h.sf_lo = (int32_t)((int64_t)f->N * s->rank / s->world);
-    h.sf_hi = (int32_t)((int64_t)f->N * (s->rank + 1) / s->world);
-    h.pairbuf = nullptr;
-    if (s->shard_mode) {
-      if (form != DataForm::tuple && form != DataForm::pairs)
-        return fail(SLM_ERR_UNSUPPORTED, "slm_bind_frame: sharded frames need the multifrontal data paths "
-                                         "(data_path 0 or 2, J < 65536)");
-      HIPCHK(grow(sl.pairbuf, sl.cap_pairbuf, (size_t)h.n_blocks * SLM_WREC + SLM_VK_TAIL + 2));
-      h.pairbuf = sl.pairbuf;
-      // records (or per-run Grams) of the other ranks' workgroups stay zero for the whole frame
-      if (h.v2_ready) HIPCHK(hipMemsetAsync(h.wgslab, 0, sizeof(double) * SLM_WREC * (size_t)h.n_wblk, st));
-      else if (form == DataForm::tuple) HIPCHK(hipMemsetAsync(h.slab, 0, sizeof(double) * SLM_SLAB_STRIDE * (size_t)h.n_runs, st));
-    } else if (form == DataForm::pairs) {   // the K-generic pair path always assembles through the pair records
-      HIPCHK(grow(sl.pairbuf, sl.cap_pairbuf, (size_t)h.n_blocks * SLM_WREC + SLM_VK_TAIL + 2));
-      h.pairbuf = sl.pairbuf;
-    }
+  if ((out.form == DataForm::tuple && !h.v1_ready) || (out.form == DataForm::pairs && !h.vk_ready)) out.form = DataForm::per_entry;
+  return SLM_OK;
+}
+
+// Share of this rank when the frame is sharded over several GPUs (whole frame otherwise), and the pair-record buffer.
+static int bind_shard_share(slm_solver* s, Slot& sl, const slm_frame* f, DataForm form, hipStream_t st) {
+  FrameDev& h = sl.h;
+  const int n_wg = (form == DataForm::tuple ? h.n_pos + 255 : 0) / 256;
+  h.wg_lo = (int32_t)((int64_t)n_wg * s->rank / s->world);
+  h.wg_hi = (int32_t)((int64_t)n_wg * (s->rank + 1) / s->world);
+  h.sf_lo = (int32_t)((int64_t)f->N * s->rank / s->world);
+  h.sf_hi = (int32_t)((int64_t)f->N * (s->rank + 1) / s->world);
+  h.pairbuf = nullptr;
+  if (s->shard_mode && form != DataForm::tuple && form != DataForm::pairs)
+    return fail(SLM_ERR_UNSUPPORTED, "slm_bind_frame: sharded frames need the multifrontal data paths "
+                                     "(data_path 0 or 2, J < 65536)");
+  if (s->shard_mode || form == DataForm::pairs) {   // (the K-generic pair path always assembles through the pair records)
+    HIPCHK(grow(sl.pairbuf, sl.cap_pairbuf, (size_t)h.n_blocks * SLM_WREC + SLM_VK_TAIL + 2));
+    h.pairbuf = sl.pairbuf;
   }
-  // nested-dissection plan (symbolic analysis on the host from the coupled-pair list)
-  h.nd_ready = 0;
-  if ((form == DataForm::tuple || form == DataForm::pairs) && s->cfg.solver_path != 1) {
-    // The symbolic plan depends only on the coupling graph (node KNN table + coupled-pair list): reuse it while the
-    // graph is unchanged.  The graph's hash comes from the device with the sizes (prep_v1's one read-back): a frame
-    // whose graph is the slot's cached one reads nothing else back -- the lists only travel to the host when the
-    // hash says that they changed.
-    const uint64_t knn_hash = dev_knn_hash, hash = dev_graph_hash;
-    const bool same_graph = sl.nd_valid && sl.nd_hash == hash && sl.nd_knn_hash == knn_hash && sl.cur_n_blocks == h.n_blocks;
-    if (!same_graph) {
-      HIPCHK(sl.h_pairs.resize(h.n_blocks));
-      HIPCHK(sl.h_knn.resize((size_t)f->J * f->K_ED));
-      HIPCHK(sl.h_pts.resize((size_t)f->J * 3));
-      HIPCHK(hipMemcpyAsync(sl.h_pairs.data(), h.blk_key, sizeof(uint32_t) * h.n_blocks, hipMemcpyDeviceToHost, st));
-      HIPCHK(hipMemcpyAsync(sl.h_knn.data(), f->ed_knn_idx, sizeof(int32_t) * sl.h_knn.size(), hipMemcpyDeviceToHost, st));
-      if (f->state_f64) {
-        HIPCHK(sl.h_pts64.resize(sl.h_pts.size()));
-        HIPCHK(hipMemcpyAsync(sl.h_pts64.data(), f->ed_points, sizeof(double) * sl.h_pts64.size(), hipMemcpyDeviceToHost, st));
-      } else {
-        HIPCHK(hipMemcpyAsync(sl.h_pts.data(), f->ed_points, sizeof(float) * sl.h_pts.size(), hipMemcpyDeviceToHost, st));
-      }
-      HIPCHK(hipStreamSynchronize(st));
-      // the node positions only steer the geometric bisection of the symbolic plan: float32 is plenty
-      if (f->state_f64)
-        for (size_t i = 0; i < sl.h_pts.size(); ++i) sl.h_pts[i] = (float)sl.h_pts64[i];
-    }
-    bt_mark();                                 // [2] pair list / node table on the host (only when the graph changed)
-    // pair -> destination table of this frame from the plan's (sorted) pair list; false when a pair is new
-    // A pair the plan was not built from still has a place in it when the later-eliminated node lies in the
-    // front of the earlier one (a fill position of the dense front): no new analysis then either.
-    auto dests_from_plan = [&]() -> bool {
-      sl.cur_dest.resize(sl.h_pairs.size());
-      std::vector<size_t> fresh;   // pairs answered by nd_dest_of: remembered in the plan's list afterwards
-      size_t j = 0;
-      for (size_t i = 0; i < sl.h_pairs.size(); ++i) {
-        while (j < sl.plan_pairs.size() && sl.plan_pairs[j] < sl.h_pairs[i]) ++j;
-        if (j < sl.plan_pairs.size() && sl.plan_pairs[j] == sl.h_pairs[i]) sl.cur_dest[i] = sl.nd.block_dest[j];
-        else if (!nd_dest_of(sl.nd, f->J, sl.h_pairs[i], sl.cur_dest[i])) return false;
-        else fresh.push_back(i);
-      }
-      if (!fresh.empty()) {
-        g_plan_fill_hits += (long long)fresh.size();
-        std::vector<uint32_t> keys(sl.plan_pairs.size() + fresh.size());
-        std::vector<NDDest> dests(keys.size());
-        size_t a = 0, b = 0, o = 0;
-        while (a < sl.plan_pairs.size() || b < fresh.size()) {
-          const bool take_old = b == fresh.size() || (a < sl.plan_pairs.size() && sl.plan_pairs[a] < sl.h_pairs[fresh[b]]);
-          if (take_old) { keys[o] = sl.plan_pairs[a]; dests[o++] = sl.nd.block_dest[a++]; }
-          else { keys[o] = sl.h_pairs[fresh[b]]; dests[o++] = sl.cur_dest[fresh[b++]]; }
-        }
-        sl.plan_pairs.swap(keys);
-        sl.nd.block_dest.swap(dests);
-      }
-      return true;
-    };
-    auto upload_cur_dests = [&]() -> hipError_t {
-      hipError_t e = grow(sl.d_cur_dests, sl.cap_cur_dests, sl.cur_dest.size() + 1);
-      if (e == hipSuccess && !sl.cur_dest.empty())
-        e = hipMemcpyAsync(sl.d_cur_dests, sl.cur_dest.data(), sizeof(NDDest) * sl.cur_dest.size(), hipMemcpyHostToDevice, st);
-      h.block_dest = sl.d_cur_dests;
-      // (a failed grow / copy leaves d_cur_dests freed or half written: the slot's cached pair list must not be trusted
-      //  by a later bind of the old graph -- same_graph compares the hash AND this count)
-      sl.cur_n_blocks = e == hipSuccess ? h.n_blocks : -1;
-      if (e != hipSuccess) sl.nd_hash = 0;
-      return e;
-    };
-    // Pivot-column tiles by what reaches them (FrameDev::tile_kind, slm_common.h).  From the PLAN's destination list --
-    // every pair seen since the node graph last changed, fill-position pairs included: a superset of this frame's --,
-    // the ARAP pair blocks and the nodes' diagonal blocks (a 7 x 7 block can straddle a tile boundary: its four
-    // corners decide).  A tile that none of them reaches and that some child maps into (a pull item) is pure fill.
-    auto upload_tile_kinds = [&]() -> hipError_t {
-      const NDPlanHost& nd = sl.nd;
-      const size_t n_tiles = (size_t)(nd.tile_doubles / (SLM_NB * SLM_NB));
-      {   // (an earlier upload from these vectors may still be in flight)
-        const hipError_t e0 = hipStreamSynchronize(st);
-        if (e0 != hipSuccess) return e0;
-      }
-      std::vector<uint8_t>& kind = sl.h_tile_kind;
-      std::vector<long long>& zero = sl.h_zero_tiles;
-      kind.assign(n_tiles + 1, 0);
-      zero.clear();
-      sl.n_piv_tiles = sl.n_pure_tiles = 0;
-      std::vector<uint8_t> assembled(n_tiles + 1, 0), pulled(n_tiles + 1, 0);
-      auto nbase = [](const NDFront& fr, int pos) { return pos < fr.nv ? 7 * pos : fr.n1p + 7 * (pos - fr.nv); };
-      auto mark = [&](int front, int prow, int pcol) {
-        if (front < 0 || front >= (int)nd.fronts.size()) return;
-        const NDFront& fr = nd.fronts[front];
-        const int rb = nbase(fr, prow), cb = nbase(fr, pcol);
-        for (int x = 0; x < 7; x += 6)
-          for (int y = 0; y < 7; y += 6) {
-            int i = rb + x, j = cb + y;
-            if (i < j) std::swap(i, j);
-            const int r = i >> 6, c = j >> 6;
-            if (c < fr.npt && r < fr.nt) assembled[(size_t)fr.tile_first + (size_t)c * fr.nt - (size_t)c * (c - 1) / 2 + (size_t)(r - c)] = 1;
-          }
-      };
-      for (const NDDest& d : nd.block_dest) mark(d.front, d.prow, d.pcol);
-      for (const NDDest& d : nd.pair_dest) mark(d.front, d.prow, d.pcol);
-      for (size_t j = 0; j < nd.node_front.size(); ++j) mark(nd.node_front[j], nd.node_pos[j], nd.node_pos[j]);
-      for (size_t l = 0; l + 1 < nd.level_start.size(); ++l)
-        for (int k = nd.item_off[2 * l + 1]; k < nd.item_off[2 * l + 2]; ++k) pulled[(size_t)nd.tile_items[k].pad0] = 1;
-      for (const NDFront& fr : nd.fronts)
-        for (int c = 0; c < fr.npt; ++c)
-          for (int r = c; r < fr.nt; ++r) {
-            const size_t ix = (size_t)c * fr.nt - (size_t)c * (c - 1) / 2 + (size_t)(r - c), t = (size_t)fr.tile_first + ix;
-            kind[t] = (s->pure_fill && !assembled[t] && pulled[t]) ? 1 : 0;
-            ++sl.n_piv_tiles;
-            sl.n_pure_tiles += kind[t];
-            if (!kind[t]) zero.push_back((long long)fr.tile_off + (long long)ix * (SLM_NB * SLM_NB));
-          }
-      hipError_t e = grow(sl.d_tile_kind, sl.cap_tile_kind, n_tiles + 1);
-      if (e == hipSuccess) e = grow(sl.d_zero_tiles, sl.cap_zero_tiles, zero.size() + 1);
-      if (e == hipSuccess) e = hipMemcpyAsync(sl.d_tile_kind, kind.data(), n_tiles + 1, hipMemcpyHostToDevice, st);
-      if (e == hipSuccess && !zero.empty())
-        e = hipMemcpyAsync(sl.d_zero_tiles, zero.data(), sizeof(long long) * zero.size(), hipMemcpyHostToDevice, st);
-      h.tile_kind = sl.d_tile_kind;
-      h.zero_tiles = sl.d_zero_tiles;
-      h.n_zero_tiles = (int32_t)zero.size();
-      if (e != hipSuccess) { sl.cur_n_blocks = -1; sl.nd_hash = 0; }
-      return e;
-    };
-    if (sl.nd_valid && sl.nd_knn_hash != knn_hash) {   // another node graph: nothing of the old plan applies
-      sl.nd_valid = false;
-      sl.plan_pairs.clear();
-    }
-    std::vector<uint32_t> all_pairs;
-    if (same_graph) {
-      h.nd_ready = 1;   // device mirrors of the plan and of this pair list are still in place (pointers kept in h)
-    } else if (sl.nd_valid && dests_from_plan()) {
-      ++g_plan_reuses;
-      HIPCHK(upload_cur_dests());
-      HIPCHK(upload_tile_kinds());   // (the plan's destination list may have grown by fill-position pairs)
-      h.nd_ready = 1;
-      sl.nd_hash = hash;
-    } else if ([&] {
-                 // new pairs: analyse the union of what the plan already covers and this frame's list
-                 all_pairs.resize(sl.plan_pairs.size() + sl.h_pairs.size());
-                 all_pairs.resize(std::set_union(sl.plan_pairs.begin(), sl.plan_pairs.end(), sl.h_pairs.begin(),
-                                                 sl.h_pairs.end(), all_pairs.begin()) - all_pairs.begin());
-                 // (a solver that runs its launches as one task graph -- at most two slots, or solver_path 2 -- takes the
-                 //  larger leaves: SLM_ND_LEAF_LATENCY, slm_nd.h)
-                 return nd_build_plan(f->J, f->K_ED, sl.h_pts.data(), sl.h_knn.data(), all_pairs.data(),
-                                      (int)all_pairs.size(), sl.nd,
-                                      solve_is_task_graph(s, (int)s->slots.size(), f->J) ? SLM_ND_LEAF_LATENCY : SLM_ND_LEAF);
-               }()) {
-      sl.nd_valid = false;
-      ++g_plan_builds;
-      sl.plan_pairs.swap(all_pairs);
-      NDPlanHost& nd = sl.nd;
-      const size_t n_ints = nd.level_start.size() + nd.nodes.size() + nd.eamap.size() + 2 * (size_t)f->J +
-                            nd.in_start.size() + nd.in_edge.size() + nd.item_off.size() +
-                            nd.dag_tasks.size() + nd.dag_top_tasks.size() + nd.front_kids.size() + nd.pull_off.size() + nd.pullmap.size() + nd.prng_off.size() +
-                            nd.prng.size();
-      const size_t n_dests = nd.block_dest.size() + nd.pair_dest.size();
-      HIPCHK(grow(sl.d_fronts, sl.cap_fronts, nd.fronts.size()));
-      HIPCHK(grow(sl.d_ints, sl.cap_ints, n_ints));
-      HIPCHK(grow(sl.d_dests, sl.cap_dests, n_dests));
-      HIPCHK(grow(sl.ftiles, sl.cap_ftiles, (size_t)nd.tile_doubles));
-      HIPCHK(grow(sl.fvec, sl.cap_fvec, (size_t)nd.vec_doubles));
-      HIPCHK(grow(sl.flinv, sl.cap_flinv, (size_t)nd.linv_doubles + 1));
-      HIPCHK(grow(sl.fmail, sl.cap_fmail, (size_t)(nd.linv_doubles / (SLM_NB * SLM_NB)) * 2560 + 1));   // SLM_MAIL_DOUBLES per pivot tile column
-      HIPCHK(hipMemcpyAsync(sl.d_fronts, nd.fronts.data(), sizeof(NDFront) * nd.fronts.size(), hipMemcpyHostToDevice, st));
-      int32_t* p = sl.d_ints;
-      auto up = [&](const std::vector<int32_t>& v) -> hipError_t {
-        hipError_t e = v.empty() ? hipSuccess : hipMemcpyAsync(p, v.data(), sizeof(int32_t) * v.size(), hipMemcpyHostToDevice, st);
-        p += v.size();
-        return e;
-      };
-      h.level_start = p; HIPCHK(up(nd.level_start));
-      h.nd_nodes = p;    HIPCHK(up(nd.nodes));
-      h.nd_eamap = p;    HIPCHK(up(nd.eamap));
-      h.node_front = p;  HIPCHK(up(nd.node_front));
-      h.node_pos = p;    HIPCHK(up(nd.node_pos));
-      h.in_start = p;    HIPCHK(up(nd.in_start));
-      h.in_edge = p;     HIPCHK(up(nd.in_edge));
-      h.item_off = p;    HIPCHK(up(nd.item_off));
+  if (s->shard_mode) {
+    // records (or per-run Grams) of the other ranks' workgroups stay zero for the whole frame
+    if (h.v2_ready) HIPCHK(hipMemsetAsync(h.wgslab, 0, sizeof(double) * SLM_WREC * (size_t)h.n_wblk, st));
+    else if (form == DataForm::tuple) HIPCHK(hipMemsetAsync(h.slab, 0, sizeof(double) * SLM_SLAB_STRIDE * (size_t)h.n_runs, st));
+  }
+  return SLM_OK;
+}
+
+// What the host analysis reads: the frame's pair list, the node KNN table and the node positions (pinned read-backs).
+static int read_back_graph(Slot& sl, const slm_frame* f, hipStream_t st) {
+  const FrameDev& h = sl.h;
+  HIPCHK(sl.h_pairs.resize(h.n_blocks));
+  HIPCHK(sl.h_knn.resize((size_t)f->J * f->K_ED));
+  HIPCHK(sl.h_pts.resize((size_t)f->J * 3));
+  HIPCHK(hipMemcpyAsync(sl.h_pairs.data(), h.blk_key, sizeof(uint32_t) * h.n_blocks, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(sl.h_knn.data(), f->ed_knn_idx, sizeof(int32_t) * sl.h_knn.size(), hipMemcpyDeviceToHost, st));
+  if (f->state_f64) {
+    HIPCHK(sl.h_pts64.resize(sl.h_pts.size()));
+    HIPCHK(hipMemcpyAsync(sl.h_pts64.data(), f->ed_points, sizeof(double) * sl.h_pts64.size(), hipMemcpyDeviceToHost, st));
+  } else {
+    HIPCHK(hipMemcpyAsync(sl.h_pts.data(), f->ed_points, sizeof(float) * sl.h_pts.size(), hipMemcpyDeviceToHost, st));
+  }
+  HIPCHK(hipStreamSynchronize(st));
+  // the node positions only steer the geometric bisection of the symbolic plan: float32 is plenty
+  if (f->state_f64)
+    for (size_t i = 0; i < sl.h_pts.size(); ++i) sl.h_pts[i] = (float)sl.h_pts64[i];
+  return SLM_OK;
+}
+
+// The int32 arrays of a plan share ONE device buffer (Slot::d_ints), in this order: its size and the copies both come
+// from this table.
+struct PlanInts {
+  GP<const int32_t> FrameDev::*field;
+  std::vector<int32_t> NDPlanHost::*src;
+};
+static const PlanInts kPlanInts[] = {
+    {&FrameDev::level_start, &NDPlanHost::level_start}, {&FrameDev::nd_nodes, &NDPlanHost::nodes},
+    {&FrameDev::nd_eamap, &NDPlanHost::eamap},          {&FrameDev::node_front, &NDPlanHost::node_front},
+    {&FrameDev::node_pos, &NDPlanHost::node_pos},       {&FrameDev::in_start, &NDPlanHost::in_start},
+    {&FrameDev::in_edge, &NDPlanHost::in_edge},         {&FrameDev::item_off, &NDPlanHost::item_off},
+    {&FrameDev::dag_tasks, &NDPlanHost::dag_tasks},     {&FrameDev::dag_top_tasks, &NDPlanHost::dag_top_tasks},
+    {&FrameDev::front_kids, &NDPlanHost::front_kids},   {&FrameDev::pull_off, &NDPlanHost::pull_off},
+    {&FrameDev::pullmap, &NDPlanHost::pullmap},         {&FrameDev::prng_off, &NDPlanHost::prng_off},
+    {&FrameDev::prng, &NDPlanHost::prng},
+};
+
+// A new plan to the device: front descriptors, work items, the int32 arrays, the destinations of the plan's pairs and
+// of the ARAP pairs; the slot's factor storage at the plan's sizes.
+static int upload_plan(Slot& sl, hipStream_t st) {
+  const NDPlanHost& nd = sl.cache.nd;
+  FrameDev& h = sl.h;
+  size_t n_ints = 0;
+  for (const PlanInts& a : kPlanInts) n_ints += (nd.*a.src).size();
+  HIPCHK(grow(sl.d_fronts, sl.cap_fronts, nd.fronts.size()));
+  HIPCHK(grow(sl.d_ints, sl.cap_ints, n_ints));
+  HIPCHK(grow(sl.d_dests, sl.cap_dests, nd.block_dest.size() + nd.pair_dest.size()));
+  HIPCHK(grow(sl.ftiles, sl.cap_ftiles, (size_t)nd.tile_doubles));
+  HIPCHK(grow(sl.fvec, sl.cap_fvec, (size_t)nd.vec_doubles));
+  HIPCHK(grow(sl.flinv, sl.cap_flinv, (size_t)nd.linv_doubles + 1));
+  HIPCHK(grow(sl.fmail, sl.cap_fmail, (size_t)(nd.linv_doubles / (SLM_NB * SLM_NB)) * 2560 + 1));   // SLM_MAIL_DOUBLES per pivot tile column
+  HIPCHK(hipMemcpyAsync(sl.d_fronts, nd.fronts.data(), sizeof(NDFront) * nd.fronts.size(), hipMemcpyHostToDevice, st));
+  int32_t* p = sl.d_ints;
+  for (const PlanInts& a : kPlanInts) {
+    if (a.field == &FrameDev::dag_tasks) {   // (the work items travel here: the order of the copies on the stream is kept)
       HIPCHK(grow(sl.d_items, sl.cap_items, nd.tile_items.size() + 1));
       if (!nd.tile_items.empty())
         HIPCHK(hipMemcpyAsync(sl.d_items, nd.tile_items.data(), sizeof(NDTileItem) * nd.tile_items.size(), hipMemcpyHostToDevice, st));
-      h.tile_items = sl.d_items;
-      h.dag_tasks = p;   HIPCHK(up(nd.dag_tasks));
-      h.dag_top_tasks = p; HIPCHK(up(nd.dag_top_tasks));
-      h.n_dag_top_tasks = (int32_t)(nd.dag_top_tasks.size() / 2);
-      h.dag_cut_depth = nd.dag_cut_depth;
-      h.front_kids = p;  HIPCHK(up(nd.front_kids));
-      h.pull_off = p;    HIPCHK(up(nd.pull_off));
-      h.pullmap = p;     HIPCHK(up(nd.pullmap));
-      h.prng_off = p;    HIPCHK(up(nd.prng_off));
-      h.prng = p;        HIPCHK(up(nd.prng));
-      h.n_dag_tasks = (int32_t)(nd.dag_tasks.size() / 2);
-      h.dag_n_tiles = (int32_t)(nd.tile_doubles / (SLM_NB * SLM_NB));
-      h.dag_n_pcols = (int32_t)(nd.linv_doubles / (SLM_NB * SLM_NB));
-      h.dag_n_flags = 8 + h.dag_n_tiles + 7 * h.dag_n_pcols;
-      HIPCHK(grow(sl.d_dag_flags, sl.cap_dag_flags, (size_t)h.dag_n_flags));
-      h.dag_flags = sl.d_dag_flags;
-      if (!nd.block_dest.empty())
-        HIPCHK(hipMemcpyAsync(sl.d_dests, nd.block_dest.data(), sizeof(NDDest) * nd.block_dest.size(), hipMemcpyHostToDevice, st));
-      HIPCHK(hipMemcpyAsync(sl.d_dests + nd.block_dest.size(), nd.pair_dest.data(), sizeof(NDDest) * nd.pair_dest.size(), hipMemcpyHostToDevice, st));
-      h.pair_dest = sl.d_dests + nd.block_dest.size();
-      if (!dests_from_plan()) return fail(SLM_ERR_INVALID, "slm_bind_frame: internal error (pair missing from its own plan)");
-      HIPCHK(upload_cur_dests());
-      HIPCHK(upload_tile_kinds());
-      h.fronts = sl.d_fronts;
-      h.n_fronts = (int)nd.fronts.size();
-      h.n_levels = (int)nd.level_start.size() - 1;
-      h.ftiles = sl.ftiles;
-      h.fvec = sl.fvec;
-      h.flinv = sl.flinv;
-      h.fmail = sl.fmail;
-      h.zero_tile_doubles = nd.tile_zero_doubles;
-      h.zero_vec_doubles = nd.vec_doubles;
-      h.nd_ready = 1;
-      sl.nd_hash = hash;
-      sl.nd_knn_hash = knn_hash;
-      sl.nd_valid = true;
-    } else {
-      sl.nd_valid = false;
-      sl.plan_pairs.clear();
     }
+    const std::vector<int32_t>& v = nd.*a.src;
+    h.*a.field = p;
+    if (!v.empty()) HIPCHK(hipMemcpyAsync(p, v.data(), sizeof(int32_t) * v.size(), hipMemcpyHostToDevice, st));
+    p += v.size();
   }
-  bt_mark();                                   // [3] symbolic plan settled
+  h.tile_items = sl.d_items;
+  h.n_dag_tasks = (int32_t)(nd.dag_tasks.size() / 2);
+  h.n_dag_top_tasks = (int32_t)(nd.dag_top_tasks.size() / 2);
+  h.dag_cut_depth = nd.dag_cut_depth;
+  h.dag_n_tiles = (int32_t)(nd.tile_doubles / (SLM_NB * SLM_NB));
+  h.dag_n_pcols = (int32_t)(nd.linv_doubles / (SLM_NB * SLM_NB));
+  h.dag_n_flags = 8 + h.dag_n_tiles + 7 * h.dag_n_pcols;
+  HIPCHK(grow(sl.d_dag_flags, sl.cap_dag_flags, (size_t)h.dag_n_flags));
+  h.dag_flags = sl.d_dag_flags;
+  if (!nd.block_dest.empty())
+    HIPCHK(hipMemcpyAsync(sl.d_dests, nd.block_dest.data(), sizeof(NDDest) * nd.block_dest.size(), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(sl.d_dests + nd.block_dest.size(), nd.pair_dest.data(), sizeof(NDDest) * nd.pair_dest.size(), hipMemcpyHostToDevice, st));
+  h.pair_dest = sl.d_dests + nd.block_dest.size();
+  h.fronts = sl.d_fronts;
+  h.n_fronts = (int)nd.fronts.size();
+  h.n_levels = (int)nd.level_start.size() - 1;
+  h.ftiles = sl.ftiles;
+  h.fvec = sl.fvec;
+  h.flinv = sl.flinv;
+  h.fmail = sl.fmail;
+  h.zero_tile_doubles = nd.tile_zero_doubles;
+  h.zero_vec_doubles = nd.vec_doubles;
+  return SLM_OK;
+}
+
+// The bound frame's pair -> destination table (PlanCache::frame_dest) to the device.
+static int upload_frame_dests(Slot& sl, hipStream_t st) {
+  const std::vector<NDDest>& dest = sl.cache.frame_dest;
+  HIPCHK(grow(sl.d_cur_dests, sl.cap_cur_dests, dest.size() + 1));
+  if (!dest.empty()) HIPCHK(hipMemcpyAsync(sl.d_cur_dests, dest.data(), sizeof(NDDest) * dest.size(), hipMemcpyHostToDevice, st));
+  sl.h.block_dest = sl.d_cur_dests;
+  return SLM_OK;
+}
+
+// The kinds of the plan's pivot-column tiles (nd_tile_kinds) to the device.
+static int upload_tile_kinds(const slm_solver* s, Slot& sl, hipStream_t st) {
+  HIPCHK(hipStreamSynchronize(st));   // an earlier upload from the two host vectors may still be in flight
+  std::vector<uint8_t>& kind = sl.h_tile_kind;
+  std::vector<long long>& zero = sl.h_zero_tiles;
+  nd_tile_kinds(sl.cache.nd, s->pure_fill, kind, zero, sl.n_piv_tiles, sl.n_pure_tiles);
+  HIPCHK(grow(sl.d_tile_kind, sl.cap_tile_kind, kind.size()));
+  HIPCHK(grow(sl.d_zero_tiles, sl.cap_zero_tiles, zero.size() + 1));
+  HIPCHK(hipMemcpyAsync(sl.d_tile_kind, kind.data(), kind.size(), hipMemcpyHostToDevice, st));
+  if (!zero.empty()) HIPCHK(hipMemcpyAsync(sl.d_zero_tiles, zero.data(), sizeof(long long) * zero.size(), hipMemcpyHostToDevice, st));
+  sl.h.tile_kind = sl.d_tile_kind;
+  sl.h.zero_tiles = sl.d_zero_tiles;
+  sl.h.n_zero_tiles = (int32_t)zero.size();
+  return SLM_OK;
+}
+
+// Nested-dissection plan (symbolic analysis on the host from the coupled-pair list).  It depends only on the coupling
+// graph (node KNN table + coupled-pair list): reuse it while the graph is unchanged.  The graph's hashes come from the
+// device with the sizes of the data-term plan: a frame whose graph is the slot's cached one reads nothing else back --
+// the lists only travel to the host when the hash says that they changed.
+static int bind_symbolic_plan(slm_solver* s, Slot& sl, const slm_frame* f, const DataPlan& dp, hipStream_t st) {
+  FrameDev& h = sl.h;
+  PlanCache& pc = sl.cache;
+  if (pc.valid && pc.knn_hash != dp.knn_hash) pc.drop_plan();   // another node graph: nothing of the old plan applies
+  // same_graph: the device mirrors of the plan and of this pair list are still in place (pointers kept in h)
+  enum { same_graph, reuse_plan, rebuild } what = same_graph;
+  int rc = SLM_OK;
+  size_t fill_hits = 0;
+  if (!(pc.valid && pc.frame_hash == dp.graph_hash && pc.frame_blocks == h.n_blocks)) {
+    if ((rc = read_back_graph(sl, f, st)) != SLM_OK) return rc;
+    what = rebuild;
+  }
+  bt_mark(BT_READBACK);
+  // a frame whose pairs all have a place in the plan (fill positions included) needs no new analysis
+  if (what != same_graph && pc.valid && nd_frame_dests(pc.nd, f->J, sl.h_pairs.data(), sl.h_pairs.size(), pc.frame_dest, &fill_hits))
+    what = reuse_plan;
+  g_plan_fill_hits += (long long)fill_hits;
+  if (what == rebuild) {
+    // new pairs: analyse the union of what the plan already covers and this frame's list
+    std::vector<uint32_t> all_pairs(pc.nd.plan_pairs.size() + sl.h_pairs.size());
+    all_pairs.resize(std::set_union(pc.nd.plan_pairs.begin(), pc.nd.plan_pairs.end(), sl.h_pairs.begin(), sl.h_pairs.end(),
+                                    all_pairs.begin()) - all_pairs.begin());
+    // (a solver that runs its launches as one task graph -- at most two slots, or solver_path 2 -- takes the larger
+    //  leaves: SLM_ND_LEAF_LATENCY, slm_nd.h)
+    const int leaf = solve_is_task_graph(s, (int)s->slots.size(), f->J) ? SLM_ND_LEAF_LATENCY : SLM_ND_LEAF;
+    if (!nd_build_plan(f->J, f->K_ED, sl.h_pts.data(), sl.h_knn.data(), all_pairs.data(), (int)all_pairs.size(), pc.nd, leaf)) {
+      pc.drop_plan();   // no plan for this graph: the slot runs on the block-banded solver
+      return SLM_OK;
+    }
+    ++g_plan_builds;
+    rc = upload_plan(sl, st);
+    if (rc == SLM_OK && !nd_frame_dests(pc.nd, f->J, sl.h_pairs.data(), sl.h_pairs.size(), pc.frame_dest, &fill_hits))
+      rc = fail(SLM_ERR_INVALID, "slm_bind_frame: internal error (pair missing from its own plan)");
+  } else if (what == reuse_plan) {
+    ++g_plan_reuses;
+  }
+  if (what != same_graph) {
+    // (after a reuse too: the plan's destination list may have grown by fill-position pairs)
+    if (rc == SLM_OK) rc = upload_frame_dests(sl, st);
+    if (rc == SLM_OK) rc = upload_tile_kinds(s, sl, st);
+    if (rc != SLM_OK) {   // device mirrors freed or half written: a later bind of the same graph must not trust them
+      if (what == rebuild) pc.drop_plan();
+      else pc.frame_stale();
+      return rc;
+    }
+    pc.valid = true;
+    pc.knn_hash = dp.knn_hash;
+    pc.frame_hash = dp.graph_hash;
+    pc.frame_blocks = h.n_blocks;
+  }
+  h.nd_ready = 1;
+  return SLM_OK;
+}
+
+// The MODEL-side half of a bind (what depends on sf.points / sf.knn_indices / sf.knn_w / ED_nodes only: the tuple-sorted
+// copies and indices of the data term, the hashes of the coupling graph, the symbolic plan of the solver, the slot's
+// grow-only work buffers).  Leaves the slot UNBOUND; bind_target_part completes it.
+static int bind_model_part(slm_solver* s, int32_t slot, const slm_frame* f, hipStream_t st, PrepBuffers* prep) {
+  int rc = check_model_args(s, slot, f);
+  if (rc != SLM_OK) return rc;
+  Slot& sl = s->slots[slot];
+  bt_mark(BT_ENTRY);
+  DataPlan dp;
+  if ((rc = reset_slot(s, sl, f, st)) != SLM_OK) return rc;
+  if ((rc = bind_data_plan(s, sl, f, st, prep, dp)) != SLM_OK) return rc;
+  if ((rc = bind_shard_share(s, sl, f, dp.form, st)) != SLM_OK) return rc;
+  sl.h.nd_ready = 0;
+  if ((dp.form == DataForm::tuple || dp.form == DataForm::pairs) && s->cfg.solver_path != 1)
+    if ((rc = bind_symbolic_plan(s, sl, f, dp, st)) != SLM_OK) return rc;
+  bt_mark(BT_SYMBOLIC);
   return SLM_OK;
 }
 
@@ -1082,7 +1059,7 @@ static int bind_target_part(slm_solver* s, int32_t slot, const slm_frame* f, hip
   if (!sl.h_pin) HIPCHK(hipHostMalloc((void**)&sl.h_pin, sizeof(FrameDev), hipHostMallocDefault));
   memcpy(sl.h_pin, &h, sizeof(FrameDev));
   HIPCHK(hipMemcpyAsync(s->frames_dev + slot, sl.h_pin, sizeof(FrameDev), hipMemcpyHostToDevice, st));
-  bt_mark();                                   // [4] descriptor on its way
+  bt_mark(BT_DESCRIPTOR);
   if (!h.nd_ready) {
     std::lock_guard<std::mutex> lock(s->band_mutex);
     int rc = ensure_band(s, slot, st);
@@ -1096,7 +1073,7 @@ static int bind_target_part(slm_solver* s, int32_t slot, const slm_frame* f, hip
   launch_init_slot(s->frames_dev, slot, f->J, s->cfg, st);
   HIPCHK(hipMemsetAsync(s->reuse_dev + slot, 0, sizeof(int), st));   // a new frame: nothing to reuse
   HIPCHK(hipGetLastError());
-  bt_mark();                                   // [5] end
+  bt_mark(BT_END);
   if (bind_trace_threshold() >= 0.0 && g_bt.n >= 2 && g_bt.t[g_bt.n - 1] - g_bt.t[0] > bind_trace_threshold()) {
     char buf[256];
     int o = snprintf(buf, sizeof(buf), "[slm bind trace] slot %d start %.3f stages(ms):", slot, g_bt.t[0]);
@@ -1137,8 +1114,7 @@ static int bind_frame_impl(slm_solver* s, int32_t slot, const slm_frame* f, hipS
   }
   if (prepared) {
     if (sl.prep_rc != SLM_OK) return fail(sl.prep_rc, sl.prep_err.c_str());
-    g_bt.n = 0;
-    bt_mark();
+    bt_mark(BT_ENTRY);
   } else {
     const int rc = bind_model_part(s, slot, f, st, prep);
     if (rc != SLM_OK) return rc;
@@ -1209,22 +1185,10 @@ int slm_discard_prepared(slm_solver* s, int32_t slot) {
   return SLM_OK;
 }
 
-int slm_bind_frames(slm_solver* s, int32_t first_slot, int32_t n_frames, const slm_frame* frames, void* stream) {
-  if (!s || !frames) return fail(SLM_ERR_INVALID, "slm_bind_frames: null argument");
-  if (first_slot < 0 || n_frames < 1 || first_slot + n_frames > (int)s->slots.size())
-    return fail(SLM_ERR_INVALID, "slm_bind_frames: slot range out of bounds");
-  hipStream_t st = (hipStream_t)stream;
-  if (n_frames == 1) return bind_frame_impl(s, first_slot, frames, st, s->prep);
-  // The preparation of a frame is a chain of ~40 small launches and four size read-backs: latency, not
-  // throughput.  The frames of a batch are therefore bound CONCURRENTLY -- one host thread, stream and set of
-  // scratch buffers per frame (up to kBindWorkers at a time), forked from and joined into the caller's stream.
-  static const int kBindWorkers = [] {
-    const char* e = getenv("SLM_BIND_WORKERS");     // experiments
-    return e && atoi(e) > 0 ? atoi(e) : 8;
-  }();
-  const int W = std::min(std::min(n_frames, kBindWorkers), 63);
-  // per-worker resources: each one is pushed into its pool as soon as it exists, so a failure half way leaves
-  // nothing behind that slm_destroy does not release (the pools are reserved first: push_back cannot throw after)
+// Scratch buffers, a stream and an event per bind worker, and the fork event.  Each one is pushed into its pool as soon as
+// it exists, so a failure half way leaves nothing behind that slm_destroy does not release (the pools are reserved
+// first: push_back cannot throw after).
+static int ensure_bind_workers(slm_solver* s, int W) {
   try {
     s->bind_prep.reserve(64);
     s->bind_streams.reserve(64);
@@ -1247,45 +1211,69 @@ int slm_bind_frames(slm_solver* s, int32_t first_slot, int32_t n_frames, const s
     HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     s->bind_events.push_back(e);
   }
-  int dev = 0;
-  HIPCHK(hipGetDevice(&dev));
-  // The binds read sizes back, so they wait for the work already on `st` in any case: wait for it HERE, on one
-  // thread, rather than with W workers spinning in their first read-back for as long as the previous LM run takes
-  // (8 busy threads for tens of milliseconds per step cost the process its CPU quota on the GPU box).
-  // This is the one LONG host wait of a tracking step (the LM run of the previous step, tens of milliseconds).  Every
-  // blocking wait of this HIP runtime spins (hipStreamSynchronize, hipEventSynchronize with or without
-  // hipEventBlockingSync: one CPU at 100 %, tools/studies/wait_cpu.py), which counts where the ranks of a node share a
-  // CPU quota: the wait is therefore a poll of an event with naps while the end is far (estimated from the previous
-  // wait on this solver) and a tight poll only over the last stretch.  SLM_SPIN_WAIT=1: hipStreamSynchronize as before.
-  const double bt0 = bind_trace_threshold() >= 0.0 ? bt_now() : 0.0;
+  return SLM_OK;
+}
+
+// Host wait for the work already on `st`.  The binds read sizes back, so they wait for it in any case: wait HERE, on one
+// thread, rather than with W workers spinning in their first read-back for as long as the previous LM run takes (8 busy
+// threads for tens of milliseconds per step cost the process its CPU quota on the GPU box).
+// This is the one LONG host wait of a tracking step (the LM run of the previous step, tens of milliseconds).  Every
+// blocking wait of this HIP runtime spins (hipStreamSynchronize, hipEventSynchronize with or without
+// hipEventBlockingSync: one CPU at 100 %, tools/studies/wait_cpu.py), which counts where the ranks of a node share a
+// CPU quota: the wait is therefore a poll of an event with naps while the end is far (estimated from the previous
+// wait on this solver) and a tight poll only over the last stretch.  SLM_SPIN_WAIT=1: hipStreamSynchronize instead.
+static int drain_stream(slm_solver* s, hipStream_t st) {
   static const bool spin_wait = [] {
     const char* e = getenv("SLM_SPIN_WAIT");
     return e && atoi(e) != 0;
   }();
   if (spin_wait) {
     HIPCHK(hipStreamSynchronize(st));
-  } else {
-    if (!s->drain_event) HIPCHK(hipEventCreateWithFlags(&s->drain_event, hipEventDisableTiming));
-    HIPCHK(hipEventRecord(s->drain_event, st));
-    const auto w0 = std::chrono::steady_clock::now();
-    auto waited_ms = [&] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count(); };
-    const double est = s->drain_est_ms;
-    for (;;) {
-      const hipError_t q = hipEventQuery(s->drain_event);
-      if (q == hipSuccess) break;
-      (void)hipGetLastError();   // hipErrorNotReady is not an error here: keep it out of the sticky last-error slot
-      if (q != hipErrorNotReady) return fail(SLM_ERR_HIP, hipGetErrorString(q));
-      const double w = waited_ms();
-      if (w < 0.85 * est - 0.4) {
-        std::this_thread::sleep_for(std::chrono::microseconds(300));    // far from the expected end
-      } else if (w > est + 1.5) {
-        std::this_thread::sleep_for(std::chrono::microseconds(100));    // overdue (the step got longer): nap again
-      } else {
-        __builtin_ia32_pause();                                          // the last stretch: poll
-      }
-    }
-    s->drain_est_ms = waited_ms();
+    return SLM_OK;
   }
+  if (!s->drain_event) HIPCHK(hipEventCreateWithFlags(&s->drain_event, hipEventDisableTiming));
+  HIPCHK(hipEventRecord(s->drain_event, st));
+  const auto w0 = std::chrono::steady_clock::now();
+  auto waited_ms = [&] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count(); };
+  const double est = s->drain_est_ms;
+  for (;;) {
+    const hipError_t q = hipEventQuery(s->drain_event);
+    if (q == hipSuccess) break;
+    (void)hipGetLastError();   // hipErrorNotReady is not an error here: keep it out of the sticky last-error slot
+    if (q != hipErrorNotReady) return fail(SLM_ERR_HIP, hipGetErrorString(q));
+    const double w = waited_ms();
+    if (w < 0.85 * est - 0.4) {
+      std::this_thread::sleep_for(std::chrono::microseconds(300));    // far from the expected end
+    } else if (w > est + 1.5) {
+      std::this_thread::sleep_for(std::chrono::microseconds(100));    // overdue (the step got longer): nap again
+    } else {
+      __builtin_ia32_pause();                                          // the last stretch: poll
+    }
+  }
+  s->drain_est_ms = waited_ms();
+  return SLM_OK;
+}
+
+int slm_bind_frames(slm_solver* s, int32_t first_slot, int32_t n_frames, const slm_frame* frames, void* stream) {
+  if (!s || !frames) return fail(SLM_ERR_INVALID, "slm_bind_frames: null argument");
+  if (first_slot < 0 || n_frames < 1 || first_slot + n_frames > (int)s->slots.size())
+    return fail(SLM_ERR_INVALID, "slm_bind_frames: slot range out of bounds");
+  hipStream_t st = (hipStream_t)stream;
+  if (n_frames == 1) return bind_frame_impl(s, first_slot, frames, st, s->prep);
+  // The preparation of a frame is a chain of ~40 small launches and four size read-backs: latency, not
+  // throughput.  The frames of a batch are therefore bound CONCURRENTLY -- one host thread, stream and set of
+  // scratch buffers per frame (up to kBindWorkers at a time), forked from and joined into the caller's stream.
+  static const int kBindWorkers = [] {
+    const char* e = getenv("SLM_BIND_WORKERS");     // experiments
+    return e && atoi(e) > 0 ? atoi(e) : 8;
+  }();
+  const int W = std::min(std::min(n_frames, kBindWorkers), 63);
+  int rc = ensure_bind_workers(s, W);
+  if (rc != SLM_OK) return rc;
+  int dev = 0;
+  HIPCHK(hipGetDevice(&dev));
+  const double bt0 = bind_trace_threshold() >= 0.0 ? bt_now() : 0.0;
+  if ((rc = drain_stream(s, st)) != SLM_OK) return rc;
   const double bt1 = bind_trace_threshold() >= 0.0 ? bt_now() : 0.0;
   HIPCHK(hipEventRecord(s->bind_events[W], st));            // fork: the workers see everything enqueued on `st` so far
   // (no exception may cross the extern "C" boundary: the containers are sized before any worker starts, the pool throws
@@ -1401,7 +1389,7 @@ BatchDims dims_of(slm_solver* s, int first, int n, bool band = false) {
   d.accept_eval = tuple ? 1 : 0;
   if (d.nd) {
     for (int i = first; i < first + n; ++i) {
-      const auto& sc = s->slots[i].nd.sched;
+      const auto& sc = s->slots[i].cache.nd.sched;
       if (sc.size() > d.sched.size()) d.sched.resize(sc.size(), NDLevelSched{0, 0, 0, 0, 0, -2, 0, -2, 0, -2});
       for (size_t l = 0; l < sc.size(); ++l) {
         NDLevelSched& m = d.sched[l];
@@ -1425,7 +1413,7 @@ BatchDims dims_of(slm_solver* s, int first, int n, bool band = false) {
   if (d.nd && n > 1) {
     // slots with fewer levels than the batch maximum: their level tables must be read on the device
     for (int i = first; i < first + n; ++i)
-      for (size_t l = s->slots[i].nd.sched.size(); l < d.sched.size(); ++l)
+      for (size_t l = s->slots[i].cache.nd.sched.size(); l < d.sched.size(); ++l)
         d.sched[l].first = d.sched[l].schur_at = d.sched[l].pull_at = -1;
   }
   for (auto& m : d.sched) {
@@ -1768,12 +1756,12 @@ int slm_get_plan_info(slm_solver* s, int32_t slot, double* out_caller, int32_t c
   for (int i = 0; i < SLM_PLAN_INFO_DOUBLES; ++i) out[i] = 0.0;
   if (h.nd_ready) {
     out[0] = 0.0;
-    out[1] = (double)sl.nd.fronts.size();
-    out[2] = (double)sl.nd.level_start.size() - 1.0;
-    out[3] = sl.nd.flops;
-    out[10] = sl.nd.flops_exact;
-    out[11] = (double)sl.nd.dag_tasks.size() / 2.0;
-    out[4] = 8.0 * (double)sl.nd.tile_doubles;
+    out[1] = (double)sl.cache.nd.fronts.size();
+    out[2] = (double)sl.cache.nd.level_start.size() - 1.0;
+    out[3] = sl.cache.nd.flops;
+    out[10] = sl.cache.nd.flops_exact;
+    out[11] = (double)sl.cache.nd.dag_tasks.size() / 2.0;
+    out[4] = 8.0 * (double)sl.cache.nd.tile_doubles;
     out[12] = (double)sl.n_piv_tiles;
     out[13] = (double)sl.n_pure_tiles;
   } else {

@@ -122,7 +122,10 @@ struct NDPlanHost {
   std::vector<int32_t> item_off;
   std::vector<int32_t> in_start;      // (J+1) CSR over in_edge
   std::vector<int32_t> in_edge;       // ARAP edges e = j*K_ED + slot grouped by their TARGET node k, ascending e
-  std::vector<NDDest> block_dest;     // per data-term block (order of blk_key)
+  // The plan covers a SUPERSET of a frame's coupled node pairs: the list it was built from plus the fill-position pairs
+  // that later frames brought (nd_frame_dests).  block_dest[i] is the destination of plan_pairs[i].
+  std::vector<uint32_t> plan_pairs;   // keys a*J + b (a >= b), strictly ascending
+  std::vector<NDDest> block_dest;
   std::vector<NDDest> pair_dest;      // per (j, slot) ARAP pair, J*K_ED
   // kept for nd_dest_of(): elimination position and tree node of every ED node, front of every tree node,
   // and per node the (tree node, local position) pairs of the fronts it occurs in
@@ -159,3 +162,18 @@ bool nd_build_plan(int J, int K_ED, const float* pts, const int32_t* ed_knn, con
 // pairs the plan was NOT built from when the later-eliminated node lies in the front of the earlier one
 // (a fill position of the dense front): such a pair needs no new symbolic analysis.
 bool nd_dest_of(const NDPlanHost& plan, int J, uint32_t key, NDDest& d);
+
+// Destination table of a frame from its pair list (keys strictly ascending): dest[i] is the place of pairs[i] in the plan.
+// A pair the plan was not built from still has a place when nd_dest_of finds one; those pairs are merged into
+// plan.plan_pairs / plan.block_dest afterwards and counted in *fill_hits.  Returns false at the first pair without a
+// place: the plan is unchanged then, dest is not valid and *fill_hits is 0.
+bool nd_frame_dests(NDPlanHost& plan, int J, const uint32_t* pairs, size_t n_pairs, std::vector<NDDest>& dest, size_t* fill_hits);
+
+// Pivot-column tiles by what reaches them (FrameDev::tile_kind, slm_common.h): kind has one byte per tile number plus one,
+// 1 = PURE FILL (pure_fill only: no assembled block lands in the tile and some child maps into it), 0 = everything else;
+// zero lists the offsets (doubles, into the tile storage) of the kind-0 pivot-column tiles.  Assembled: the four corners
+// of every block_dest, pair_dest and node-diagonal block (a 7 x 7 block can straddle a tile boundary); block_dest holds
+// every pair seen since the node graph last changed, a superset of any one frame's.  n_piv / n_pure: pivot-column tiles of
+// the plan / of them pure fill.
+void nd_tile_kinds(const NDPlanHost& plan, bool pure_fill, std::vector<uint8_t>& kind, std::vector<long long>& zero, int& n_piv,
+                   int& n_pure);

@@ -672,6 +672,7 @@ bool nd_build_plan(int J, int K_ED, const float* pts, const int32_t* ed_knn, con
     d.transpose = (e == a && a != bnode) ? 1 : 0;
     return true;
   };
+  out.plan_pairs.assign(pairs, pairs + n_pairs);
   out.block_dest.resize(n_pairs);
   for (int i = 0; i < n_pairs; ++i) {
     const int a = (int)(pairs[i] / (uint32_t)J), bb = (int)(pairs[i] % (uint32_t)J);
@@ -722,4 +723,66 @@ bool nd_dest_of(const NDPlanHost& p, int J, uint32_t key, NDDest& d) {
   d.prow = prow;
   d.transpose = (e == a && a != b) ? 1 : 0;
   return true;
+}
+
+bool nd_frame_dests(NDPlanHost& p, int J, const uint32_t* pairs, size_t n_pairs, std::vector<NDDest>& dest, size_t* fill_hits) {
+  *fill_hits = 0;
+  dest.resize(n_pairs);
+  std::vector<size_t> fresh;   // pairs answered by nd_dest_of: remembered in the plan's list afterwards
+  size_t j = 0;
+  for (size_t i = 0; i < n_pairs; ++i) {
+    while (j < p.plan_pairs.size() && p.plan_pairs[j] < pairs[i]) ++j;
+    if (j < p.plan_pairs.size() && p.plan_pairs[j] == pairs[i]) dest[i] = p.block_dest[j];
+    else if (!nd_dest_of(p, J, pairs[i], dest[i])) return false;
+    else fresh.push_back(i);
+  }
+  if (fresh.empty()) return true;
+  *fill_hits = fresh.size();
+  std::vector<uint32_t> keys(p.plan_pairs.size() + fresh.size());
+  std::vector<NDDest> dests(keys.size());
+  size_t a = 0, b = 0, o = 0;
+  while (a < p.plan_pairs.size() || b < fresh.size()) {
+    const bool take_old = b == fresh.size() || (a < p.plan_pairs.size() && p.plan_pairs[a] < pairs[fresh[b]]);
+    if (take_old) { keys[o] = p.plan_pairs[a]; dests[o++] = p.block_dest[a++]; }
+    else { keys[o] = pairs[fresh[b]]; dests[o++] = dest[fresh[b++]]; }
+  }
+  p.plan_pairs.swap(keys);
+  p.block_dest.swap(dests);
+  return true;
+}
+
+void nd_tile_kinds(const NDPlanHost& p, bool pure_fill, std::vector<uint8_t>& kind, std::vector<long long>& zero, int& n_piv,
+                   int& n_pure) {
+  const size_t n_tiles = (size_t)(p.tile_doubles / 4096);
+  kind.assign(n_tiles + 1, 0);
+  zero.clear();
+  n_piv = n_pure = 0;
+  std::vector<uint8_t> assembled(n_tiles + 1, 0), pulled(n_tiles + 1, 0);
+  auto nbase = [](const NDFront& fr, int pos) { return pos < fr.nv ? 7 * pos : fr.n1p + 7 * (pos - fr.nv); };
+  auto mark = [&](int front, int prow, int pcol) {
+    if (front < 0 || front >= (int)p.fronts.size()) return;
+    const NDFront& fr = p.fronts[front];
+    const int rb = nbase(fr, prow), cb = nbase(fr, pcol);
+    for (int x = 0; x < 7; x += 6)
+      for (int y = 0; y < 7; y += 6) {
+        int i = rb + x, j = cb + y;
+        if (i < j) std::swap(i, j);
+        const int r = i >> 6, c = j >> 6;
+        if (c < fr.npt && r < fr.nt) assembled[(size_t)fr.tile_first + (size_t)c * fr.nt - (size_t)c * (c - 1) / 2 + (size_t)(r - c)] = 1;
+      }
+  };
+  for (const NDDest& d : p.block_dest) mark(d.front, d.prow, d.pcol);
+  for (const NDDest& d : p.pair_dest) mark(d.front, d.prow, d.pcol);
+  for (size_t j = 0; j < p.node_front.size(); ++j) mark(p.node_front[j], p.node_pos[j], p.node_pos[j]);
+  for (size_t l = 0; l + 1 < p.level_start.size(); ++l)
+    for (int k = p.item_off[2 * l + 1]; k < p.item_off[2 * l + 2]; ++k) pulled[(size_t)p.tile_items[k].pad0] = 1;
+  for (const NDFront& fr : p.fronts)
+    for (int c = 0; c < fr.npt; ++c)
+      for (int r = c; r < fr.nt; ++r) {
+        const size_t ix = (size_t)c * fr.nt - (size_t)c * (c - 1) / 2 + (size_t)(r - c), t = (size_t)fr.tile_first + ix;
+        kind[t] = (pure_fill && !assembled[t] && pulled[t]) ? 1 : 0;
+        ++n_piv;
+        n_pure += kind[t];
+        if (!kind[t]) zero.push_back((long long)fr.tile_off + (long long)ix * 4096);
+      }
 }

@@ -1,5 +1,6 @@
 // Host-only harness around the symbolic analysis (python-super_amd/csrc/slm_nd_host.hip): builds the plan of a coupling
 // graph handed over by tools/studies/nd_order_study.py and returns its cost figures.  Study tool, not part of the library.
+#include <algorithm>
 #include <cstdint>
 #include <cstring>
 #include <vector>
@@ -82,6 +83,114 @@ extern "C" int nd_check_orders(int J, int K_ED, const float* pts, const int32_t*
   if (a) return 1000000 + a;
   const int b = p.dag_top_tasks.empty() ? 0 : check_order(p, p.dag_top_tasks, true);
   return b ? 2000000 + b : 0;
+}
+
+// The host half of a bind's symbolic stage on one plan: a frame's destination table from its sorted pair list
+// (nd_frame_dests) and the kinds of the pivot-column tiles (nd_tile_kinds).  Returns 0, or the number of the first check
+// that fails: 1 the plan's own list, 2 a random subset, 3 lists with pairs the plan was not built from, 4 tile kinds.
+extern "C" int nd_check_frame_dests(int J, int K_ED, const float* pts, const int32_t* knn, const uint32_t* pairs, int n_pairs,
+                                    uint32_t seed) {
+  NDPlanHost p;
+  if (!nd_build_plan(J, K_ED, pts, knn, pairs, n_pairs, p)) return -1;
+  auto same = [](const NDDest& a, const NDDest& b) {
+    return a.front == b.front && a.prow == b.prow && a.pcol == b.pcol && a.transpose == b.transpose;
+  };
+  auto same_list = [&](const std::vector<NDDest>& a, const std::vector<NDDest>& b) {
+    return a.size() == b.size() && std::equal(a.begin(), a.end(), b.begin(), same);
+  };
+  auto rnd = [&seed] {
+    seed = seed * 1664525u + 1013904223u;
+    return seed >> 8;
+  };
+  const std::vector<uint32_t> own(pairs, pairs + n_pairs);
+  const std::vector<NDDest> own_dest = p.block_dest;
+  std::vector<NDDest> dest;
+  size_t hits = 99;
+  if (p.plan_pairs != own) return 1;
+  if (!nd_frame_dests(p, J, own.data(), own.size(), dest, &hits) || hits != 0 || !same_list(dest, own_dest)) return 1;
+  if (p.plan_pairs != own || !same_list(p.block_dest, own_dest)) return 1;
+
+  std::vector<uint32_t> sub;
+  for (uint32_t k : own)
+    if (rnd() & 1) sub.push_back(k);
+  if (!nd_frame_dests(p, J, sub.data(), sub.size(), dest, &hits) || hits != 0 || dest.size() != sub.size()) return 2;
+  for (size_t i = 0; i < sub.size(); ++i) {
+    NDDest d;
+    if (!nd_dest_of(p, J, sub[i], d) || !same(d, dest[i])) return 2;
+  }
+  if (p.plan_pairs != own || !same_list(p.block_dest, own_dest)) return 2;
+
+  std::vector<uint32_t> extra, placeable;   // pairs outside the plan's list / those of them with a fill position
+  for (int k = 0; k < 2 * J + 8; ++k) {
+    const uint32_t a = rnd() % (uint32_t)J, b = rnd() % (a + 1), key = a * (uint32_t)J + b;
+    if (!std::binary_search(own.begin(), own.end(), key)) extra.push_back(key);
+  }
+  std::sort(extra.begin(), extra.end());
+  extra.erase(std::unique(extra.begin(), extra.end()), extra.end());
+  for (uint32_t k : extra) {
+    NDDest d;
+    if (nd_dest_of(p, J, k, d)) placeable.push_back(k);
+  }
+  for (const std::vector<uint32_t>* ex : {&extra, &placeable}) {
+    std::vector<uint32_t> list(sub.size() + ex->size());
+    list.resize(std::set_union(sub.begin(), sub.end(), ex->begin(), ex->end(), list.begin()) - list.begin());
+    const std::vector<uint32_t> keys0 = p.plan_pairs;
+    const std::vector<NDDest> dests0 = p.block_dest;
+    size_t n_new = 0;
+    for (uint32_t k : *ex) n_new += !std::binary_search(keys0.begin(), keys0.end(), k);
+    const bool ok = nd_frame_dests(p, J, list.data(), list.size(), dest, &hits);
+    if (ok != (ex->size() == placeable.size())) return 3;
+    if (!ok) {
+      if (hits != 0 || p.plan_pairs != keys0 || !same_list(p.block_dest, dests0)) return 3;
+      continue;
+    }
+    if (hits != n_new || p.block_dest.size() != p.plan_pairs.size() || p.plan_pairs.size() != keys0.size() + n_new) return 3;
+    for (size_t i = 1; i < p.plan_pairs.size(); ++i)
+      if (p.plan_pairs[i - 1] >= p.plan_pairs[i]) return 3;
+    for (size_t i = 0; i < keys0.size(); ++i) {
+      const size_t at = std::lower_bound(p.plan_pairs.begin(), p.plan_pairs.end(), keys0[i]) - p.plan_pairs.begin();
+      if (at >= p.plan_pairs.size() || p.plan_pairs[at] != keys0[i] || !same(p.block_dest[at], dests0[i])) return 3;
+    }
+    for (size_t i = 0; i < list.size(); ++i) {
+      NDDest d;
+      if (dest.size() != list.size() || !nd_dest_of(p, J, list[i], d) || !same(d, dest[i])) return 3;
+    }
+  }
+
+  for (int pure_fill = 0; pure_fill < 2; ++pure_fill) {
+    std::vector<uint8_t> kind;
+    std::vector<long long> zero;
+    int n_piv = -1, n_pure = -1;
+    nd_tile_kinds(p, pure_fill != 0, kind, zero, n_piv, n_pure);
+    if (kind.size() != (size_t)(p.tile_doubles / 4096) + 1 || (long long)zero.size() + n_pure != n_piv) return 4;
+    long long piv_tiles = 0;
+    for (const NDFront& f : p.fronts)
+      for (int c = 0; c < f.npt; ++c) piv_tiles += f.nt - c;
+    if (n_piv != piv_tiles || (!pure_fill && n_pure != 0)) return 4;
+    std::vector<long long> z = zero;
+    std::sort(z.begin(), z.end());
+    for (size_t i = 0; i < z.size(); ++i)
+      if (z[i] < 0 || z[i] >= p.tile_doubles || z[i] % 4096 || (i && z[i] == z[i - 1])) return 4;
+    // no tile that a corner of an assembled 7 x 7 block reaches is pure fill
+    auto reached_is_pure = [&](int front, int prow, int pcol) {
+      if (front < 0) return false;
+      const NDFront& f = p.fronts[front];
+      const int rb = prow < f.nv ? 7 * prow : f.n1p + 7 * (prow - f.nv), cb = pcol < f.nv ? 7 * pcol : f.n1p + 7 * (pcol - f.nv);
+      for (int i : {rb, rb + 6})
+        for (int j : {cb, cb + 6}) {
+          const int r = std::max(i, j) / 64, c = std::min(i, j) / 64;
+          if (c < f.npt && r < f.nt && kind[(size_t)f.tile_first + (size_t)c * f.nt - (size_t)c * (c - 1) / 2 + (r - c)]) return true;
+        }
+      return false;
+    };
+    for (const NDDest& d : p.block_dest)
+      if (reached_is_pure(d.front, d.prow, d.pcol)) return 4;
+    for (const NDDest& d : p.pair_dest)
+      if (reached_is_pure(d.front, d.prow, d.pcol)) return 4;
+    for (size_t j = 0; j < p.node_front.size(); ++j)
+      if (reached_is_pure(p.node_front[j], p.node_pos[j], p.node_pos[j])) return 4;
+  }
+  return 0;
 }
 
 extern "C" int nd_stats(int J, int K_ED, const float* pts, const int32_t* knn, const uint32_t* pairs, int n_pairs,
