@@ -1,4 +1,9 @@
 // slm_prep.h -- host interface of the once-per-frame data-term preparation (slm_prep.hip).
+// Three builders behind it -- the binned preparation and the rocPRIM pipeline (prep_v1 chooses, repeats and switches), and
+// prep_pairs -- share one growth rule for groups of device arrays (grow_group over the member tables kPrepArrays,
+// kPlanArrays, kPairPlanArrays, which the *_free / prep_destroy functions walk too), the bounds of a build (v1_bounds,
+// grow_plan), the reader of the status block (read_built, finish_v1; slots: enum SC_*) and the rocPRIM scratch rule
+// (ensure_scratch).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -6,9 +11,9 @@
 
 #include "super_lm.h"
 
-struct PrepBuffers;   // scratch shared by all slots of a solver (grow-only)
+struct PrepBuffers;   // scratch shared by all slots of a solver (grow-only; one instance per bind worker)
 
-// Per-slot, grow-only device buffers that the per-iteration kernels read.
+// Per-slot, grow-only device buffers that the per-iteration kernels read.  Every array has a row in kPlanArrays (slm_prep.hip).
 struct V1Plan {
   float* s_pts = nullptr;
   int32_t* s_idx = nullptr;
@@ -33,13 +38,16 @@ struct V1Plan {
          cap_bstart = 0, cap_bentry = 0;
 };
 
-struct V1Sizes {
-  int n_tuples, n_pos, n_runs, n_blocks;
-  int n_wblk, max_wblk_per_wg;   // v2 records; v2 is usable when max_wblk_per_wg <= SLM_LB_MAX
-  // hashes of the coupling graph, computed on the device: (J, K_ED, node KNN table) and the same continued over the
-  // coupled-pair keys -- what the cached symbolic plan of a slot is compared with
+// What every plan build reports.  The hashes of the coupling graph are computed on the device: (J, K_ED, node KNN table)
+// and the same continued over the coupled-pair keys -- what the cached symbolic plan of a slot is compared with.
+struct PlanSizes {
+  int n_blocks = 0;
   uint64_t knn_hash = 0, graph_hash = 0;
   bool bad_knn = false;          // a KNN index outside [0, J) or a surfel's repeated id was seen: the frame must be refused
+};
+struct V1Sizes : PlanSizes {
+  int n_tuples = 0, n_pos = 0, n_runs = 0;
+  int n_wblk = 0, max_wblk_per_wg = 0;   // v2 records; v2 is usable when max_wblk_per_wg <= SLM_LB_MAX
 };
 
 // ---- K-generic pair plan (any opt.num_neighbors in 1..8; reference super/loss.py:213-220 is K-generic) ----------------
@@ -56,11 +64,7 @@ struct PairPlan {
   int32_t* sf_perm = nullptr;    // (N) surfel ids in neighbour-set order
   size_t cap_key = 0, cap_pidx = 0, cap_perm = 0;
 };
-struct PairSizes {
-  int n_blocks = 0;
-  uint64_t knn_hash = 0, graph_hash = 0;   // as V1Sizes
-  bool bad_knn = false;
-};
+using PairSizes = PlanSizes;
 // Stream-synchronising (one read-back).  f.K in 1..8, f.J < 65536.
 hipError_t prep_pairs(PrepBuffers*, const slm_frame& f, PairPlan& plan, PairSizes* out, hipStream_t st);
 void pairplan_free(PairPlan& plan);

@@ -15,13 +15,36 @@
 // rocPRIM is used only for these once-per-frame sorts/scans (plumbing); every kernel on
 // the per-iteration path is hand-written.
 #include <algorithm>
+#include <cstddef>
 #include <cstring>
+#include <type_traits>
 #include <rocprim/rocprim.hpp>
 
 #include "slm_common.h"
 #include "slm_prep.h"
 
 namespace {
+
+// The status block `scal` (PrepBuffers::scal on the device, scal_host its pinned mirror): what the kernels of a build
+// leave for each other and for the host's read-back.
+enum {
+  SC_NT = 0,           // tuples (cut down to the bound of a hinted build)
+  SC_PTOT,             // padded positions
+  SC_NRUNS,            // runs
+  SC_NBLOCKS,          // coupled node pairs (live unique pair keys)
+  SC_NUQ,              // rocPRIM pipeline: unique pair keys incl. a possible trailing run of the padding key
+  SC_NWUQ,             // rocPRIM pipeline: unique (workgroup, pair) keys, likewise
+  SC_NWBLK,            // live (workgroup, pair) records
+  SC_MAXWBLK,          // most records of one workgroup
+  SC_KNN_HASH,         // [8..9]   64-bit hash of (J, K_ED, node KNN table)
+  SC_GRAPH_HASH = 10,  // [10..11] the same continued over the pair keys
+  SC_NT_TRUE = 12,     // tuples before the cut
+  SC_BAD_KNN,          // a bad KNN index or row was seen
+  SC_MAXBIN,           // binned preparation: largest bin
+  SC_STATE,            // binned preparation: ST_*
+  SC_COUNT
+};
+enum { ST_OK = 0, ST_LEGACY = 1, ST_MISS = 2 };   // a bin exceeds the LDS sort: rocPRIM pipeline / a hinted plan-buffer bound did not hold
 
 __device__ __forceinline__ void sort4(int& a, int& b, int& c, int& d) {
   int t;
@@ -79,21 +102,21 @@ __global__ void __launch_bounds__(256) k_run_counts(const int* __restrict__ d_nt
 
 // A hinted preparation sizes its buffers and grids for `bound` tuples before the true count is known on the host: the
 // count every later kernel works with is cut down to the bound (a frame with more tuples is then prepared on a
-// truncated tuple list, inside its buffers, and prepared again by the host with the exact count); scal[12] keeps the
+// truncated tuple list, inside its buffers, and prepared again by the host with the exact count); scal[SC_NT_TRUE] keeps the
 // true count for that decision.
 __global__ void k_clamp_tuples(int* __restrict__ scal, int bound) {
-  const int nt = scal[0];
-  scal[12] = nt;
-  if (nt > bound) scal[0] = bound;
+  const int nt = scal[SC_NT];
+  scal[SC_NT_TRUE] = nt;
+  if (nt > bound) scal[SC_NT] = bound;
 }
 
-// scal[0] = n_tuples (already there), scal[1] = total padded positions, scal[2] = total runs
+// scal[SC_NT] = n_tuples (already there), scal[SC_PTOT] = total padded positions, scal[SC_NRUNS] = total runs
 __global__ void k_totals(int* __restrict__ scal, const int* __restrict__ pstart,
                          const int* __restrict__ pc, const int* __restrict__ rstart,
                          const int* __restrict__ nruns) {
-  const int nt = scal[0];
-  scal[1] = nt > 0 ? pstart[nt - 1] + pc[nt - 1] : 0;
-  scal[2] = nt > 0 ? rstart[nt - 1] + nruns[nt - 1] : 0;
+  const int nt = scal[SC_NT];
+  scal[SC_PTOT] = nt > 0 ? pstart[nt - 1] + pc[nt - 1] : 0;
+  scal[SC_NRUNS] = nt > 0 ? rstart[nt - 1] + nruns[nt - 1] : 0;
 }
 
 __global__ void __launch_bounds__(256) k_fill_sorted(
@@ -105,7 +128,7 @@ __global__ void __launch_bounds__(256) k_fill_sorted(
     int* __restrict__ run_chunk) {
   const int pos = blockIdx.x * blockDim.x + threadIdx.x;
   if (pos >= n_pos_bound) return;
-  const int nt = scal[0], ptot = scal[1];
+  const int nt = scal[SC_NT], ptot = scal[SC_PTOT];
   int4 idv = make_int4(-1, -1, -1, -1);
   double wv[4] = {0.0, 0.0, 0.0, 0.0};
   d3 pp = {0.0, 0.0, 0.0};
@@ -156,7 +179,7 @@ __global__ void __launch_bounds__(256) k_pairs(int n_runs_bound, const int* __re
                                                 unsigned* __restrict__ pkeys, int* __restrict__ pvals) {
   const int rr = blockIdx.x * blockDim.x + threadIdx.x;
   if (rr >= n_runs_bound) return;
-  const bool live = rr < scal[2];
+  const bool live = rr < scal[SC_NRUNS];
   int n[4] = {0, 0, 0, 0};
   if (live) {
     const int4 v = *reinterpret_cast<const int4*>(run_nodes + 4 * rr);
@@ -172,16 +195,16 @@ __global__ void __launch_bounds__(256) k_pairs(int n_runs_bound, const int* __re
     }
 }
 
-// scal[3] = n_blocks (unique live keys); blk_start[n_blocks] = end of the last live block
+// scal[SC_NBLOCKS] = n_blocks (unique live keys); blk_start[n_blocks] = end of the last live block
 __global__ void k_totals2(int* __restrict__ scal, const unsigned* __restrict__ ukeys,
                           int* __restrict__ blk_start, int n_entries) {
-  int nb = scal[4];   // unique keys incl. a possible trailing 0xFFFFFFFF run
+  int nb = scal[SC_NUQ];   // unique keys incl. a possible trailing 0xFFFFFFFF run
   if (nb > 0 && ukeys[nb - 1] == 0xFFFFFFFFu) {
     nb -= 1;          // blk_start[nb] already holds the start of the invalid run
   } else {
     blk_start[nb] = n_entries;
   }
-  scal[3] = nb;
+  scal[SC_NBLOCKS] = nb;
 }
 
 // ---- v2: (workgroup, pair) records ------------------------------------------------------
@@ -193,7 +216,7 @@ __global__ void __launch_bounds__(256) k_pairs2(int n_runs_bound, const int* __r
                                                  int* __restrict__ vals) {
   const int rr = blockIdx.x * blockDim.x + threadIdx.x;
   if (rr >= n_runs_bound) return;
-  const bool live = rr < scal[2];
+  const bool live = rr < scal[SC_NRUNS];
   int n[4] = {0, 0, 0, 0};
   unsigned long long wg = 0;
   if (live) {
@@ -219,7 +242,7 @@ __global__ void __launch_bounds__(256) k_wg_bounds(int nwb_bound, int* __restric
                                                     unsigned* __restrict__ pk, int* __restrict__ pv) {
   const int u = blockIdx.x * blockDim.x + threadIdx.x;
   if (u >= nwb_bound) return;
-  const int nu = scal[5];
+  const int nu = scal[SC_NWUQ];
   const bool live = u < nu && wkeys[u] != ~0ull;
   pk[u] = live ? (unsigned)(wkeys[u] & 0xFFFFFFFFull) : 0xFFFFFFFFu;
   pv[u] = u;
@@ -228,7 +251,7 @@ __global__ void __launch_bounds__(256) k_wg_bounds(int nwb_bound, int* __restric
   if (u == 0 || (int)(wkeys[u - 1] >> 32) != wg) wg_first[wg] = u;
   const bool last = (u + 1 >= nu) || wkeys[u + 1] == ~0ull || (int)(wkeys[u + 1] >> 32) != wg;
   if (last) wg_last[wg] = u;
-  atomicAdd(&scal[6], 1);   // live records
+  atomicAdd(&scal[SC_NWBLK], 1);   // live records
 }
 
 __global__ void __launch_bounds__(256) k_wg_max(int n_wg, const int* __restrict__ wg_first,
@@ -236,7 +259,7 @@ __global__ void __launch_bounds__(256) k_wg_max(int n_wg, const int* __restrict_
   const int g = blockIdx.x * blockDim.x + threadIdx.x;
   if (g >= n_wg) return;
   const int c = wg_last[g] - wg_first[g] + 1;
-  if (c > 0) atomicMax(&scal[7], c);
+  if (c > 0) atomicMax(&scal[SC_MAXWBLK], c);
 }
 
 // local record index of every (run, pair slot)
@@ -246,7 +269,7 @@ __global__ void __launch_bounds__(256) k_run_lidx(int nwb_bound, const int* __re
                                                    const int* __restrict__ svals, const int* __restrict__ wg_first,
                                                    uint8_t* __restrict__ run_lidx) {
   const int u = blockIdx.x * blockDim.x + threadIdx.x;
-  if (u >= nwb_bound || u >= scal[5] || wkeys[u] == ~0ull) return;
+  if (u >= nwb_bound || u >= scal[SC_NWUQ] || wkeys[u] == ~0ull) return;
   const int wg = (int)(wkeys[u] >> 32);
   const int lidx = u - wg_first[wg];
   for (int e = wstart[u]; e < wstart[u] + wcount[u]; ++e) {
@@ -266,12 +289,12 @@ __device__ __forceinline__ unsigned long long plan_mix(unsigned long long w, uns
   z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
   return z ^ (z >> 31);
 }
-// (also the range test of the node KNN table: an id outside [0, J) raises scal[13], the bad-KNN flag of the read-back that
+// (also the range test of the node KNN table: an id outside [0, J) raises scal[SC_BAD_KNN], the bad-KNN flag of the read-back that
 //  follows; nothing before it indexes with the table)
 __global__ void __launch_bounds__(256) k_plan_hash(int J, int K_ED, const int32_t* __restrict__ ed_knn,
                                                     const int32_t* __restrict__ blk_key, int* __restrict__ scal,
                                                     unsigned long long* __restrict__ out) {
-  const int n_knn = J * K_ED, n_pairs = scal[3];
+  const int n_knn = J * K_ED, n_pairs = scal[SC_NBLOCKS];
   unsigned long long h0 = 0, h1 = 0;
   bool bad = false;
   const int tid = blockIdx.x * blockDim.x + threadIdx.x, nthr = gridDim.x * blockDim.x;
@@ -281,7 +304,7 @@ __global__ void __launch_bounds__(256) k_plan_hash(int J, int K_ED, const int32_
     bad |= (unsigned)e >= (unsigned)J;
     h0 += plan_mix((unsigned)e, (unsigned long long)i);
   }
-  if (bad) scal[13] = 1;
+  if (bad) scal[SC_BAD_KNN] = 1;
   for (int i = tid; i < n_pairs; i += nthr) h1 += plan_mix((unsigned)blk_key[i], (1ull << 40) + (unsigned long long)i);
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
@@ -375,11 +398,11 @@ __global__ void __launch_bounds__(256) k_gather_keys(int N, const unsigned long 
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < N) out[i] = keys[order[i]];
 }
-__global__ void k_pair_count(int* __restrict__ scal, const unsigned* __restrict__ cnt) { scal[3] = (int)cnt[0]; }
+__global__ void k_pair_count(int* __restrict__ scal, const unsigned* __restrict__ cnt) { scal[SC_NBLOCKS] = (int)cnt[0]; }
 
 // blk2_start[n_blocks] = number of live records (end of the last live pair)
 __global__ void k_totals3(const int* __restrict__ scal, int* __restrict__ blk2_start) {
-  blk2_start[scal[3]] = scal[6];
+  blk2_start[scal[SC_NBLOCKS]] = scal[SC_NWBLK];
 }
 
 
@@ -527,8 +550,8 @@ __global__ void __launch_bounds__(1024) kb_scan_bins(int nb, int* __restrict__ c
   for (int i = threadIdx.x; i < nb; i += 1024) cnt[i] = 0;
   if (threadIdx.x == 0) {
     start[nb] = total;
-    if (s_max > scal[14]) scal[14] = s_max;
-    if (s_max > cap) scal[15] = 1;
+    if (s_max > scal[SC_MAXBIN]) scal[SC_MAXBIN] = s_max;
+    if (s_max > cap) scal[SC_STATE] = ST_LEGACY;
   }
 }
 
@@ -537,7 +560,7 @@ __global__ void __launch_bounds__(256) kb_scatter(int N, const unsigned long lon
                                                    int* __restrict__ cursor, unsigned long long* __restrict__ bkeys, int* __restrict__ bids,
                                                    const int* __restrict__ scal) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (scal[15]) return;
+  if (scal[SC_STATE]) return;
   const bool active = i < N;
   const unsigned long long k = active ? keys[i] : 0ull;
   const int a = (int)(k >> 48);
@@ -563,7 +586,7 @@ __global__ void __launch_bounds__(256) kb_sort_bins(int J, const int* __restrict
   __shared__ unsigned v[BIN_CAP];
   __shared__ int hs[BIN_CAP], hl[BIN_CAP];
   __shared__ int tmp[256];
-  if (scal[15]) return;
+  if (scal[SC_STATE]) return;
   const int b = blockIdx.x;
   const int* startA = binv + (size_t)BV_STARTA * (J + 1);
   const int base = startA[b], n = startA[b + 1] - base;
@@ -605,7 +628,7 @@ __global__ void __launch_bounds__(256) kb_sort_bins(int J, const int* __restrict
 // A5: tuples / padded positions before every bin; totals; the plan buffers must hold them
 __global__ void __launch_bounds__(1024) kb_scan_layout(int J, int* __restrict__ binv, int* __restrict__ scal, int pos_bound) {
   __shared__ int tmp[1024];
-  if (scal[15]) return;
+  if (scal[SC_STATE]) return;
   int* ntup = binv + (size_t)BV_NTUP * (J + 1);
   int* npos = binv + (size_t)BV_NPOS * (J + 1);
   int* tupoff = binv + (size_t)BV_TUPOFF * (J + 1);
@@ -615,10 +638,10 @@ __global__ void __launch_bounds__(1024) kb_scan_layout(int J, int* __restrict__ 
   const int nt = block_excl_scan<1024>(tupoff, J, tmp);
   const int ptot = block_excl_scan<1024>(posoff, J, tmp);
   if (threadIdx.x == 0) {
-    scal[0] = nt;
-    scal[12] = nt;
-    scal[1] = ptot;
-    if (pos_bound > 0 && (ptot + 63) / 64 * 64 > pos_bound) scal[15] = 2;
+    scal[SC_NT] = nt;
+    scal[SC_NT_TRUE] = nt;
+    scal[SC_PTOT] = ptot;
+    if (pos_bound > 0 && (ptot + 63) / 64 * 64 > pos_bound) scal[SC_STATE] = ST_MISS;
   }
 }
 
@@ -627,7 +650,7 @@ __global__ void __launch_bounds__(256) kb_runs(int J, int* __restrict__ binv, co
                                                 int* __restrict__ sp_rl, const int* __restrict__ scal) {
   __shared__ int nr[BIN_CAP];
   __shared__ int tmp[256];
-  if (scal[15]) return;
+  if (scal[SC_STATE]) return;
   const int b = blockIdx.x;
   const int* startA = binv + (size_t)BV_STARTA * (J + 1);
   const int base = startA[b], n = startA[b + 1] - base;
@@ -653,15 +676,15 @@ __global__ void __launch_bounds__(256) kb_runs(int J, int* __restrict__ binv, co
 // A7: runs before every bin; total; bound check
 __global__ void __launch_bounds__(1024) kb_scan_runs(int J, int* __restrict__ binv, int* __restrict__ scal, int runs_bound) {
   __shared__ int tmp[1024];
-  if (scal[15]) return;
+  if (scal[SC_STATE]) return;
   int* runs = binv + (size_t)BV_RUNS * (J + 1);
   int* runoff = binv + (size_t)BV_RUNOFF * (J + 1);
   for (int i = threadIdx.x; i < J; i += 1024) runoff[i] = runs[i];
   __syncthreads();
   const int nruns = block_excl_scan<1024>(runoff, J, tmp);
   if (threadIdx.x == 0) {
-    scal[2] = nruns;
-    if (runs_bound > 0 && nruns > runs_bound) scal[15] = 2;
+    scal[SC_NRUNS] = nruns;
+    if (runs_bound > 0 && nruns > runs_bound) scal[SC_STATE] = ST_MISS;
   }
 }
 
@@ -675,7 +698,7 @@ __global__ void __launch_bounds__(256) kb_fill(int J, const slm_frame f, const i
                                                 int* __restrict__ run_nodes, int* __restrict__ run_chunk, int* __restrict__ cntB,
                                                 int* __restrict__ wgr0x, int* __restrict__ wgr1, int RB) {
   __shared__ int pcl[BIN_CAP];
-  if (scal[15]) return;
+  if (scal[SC_STATE]) return;
   const int b = blockIdx.x;
   auto put = [&](int pos, int4 idv, const double wv[4], d3 pp, int run) {
     *reinterpret_cast<int4*>(s_idx + 4 * (size_t)pos) = idv;
@@ -693,7 +716,7 @@ __global__ void __launch_bounds__(256) kb_fill(int J, const slm_frame f, const i
     if ((pos & 3) == 0) grp_run[pos >> 2] = run;
   };
   if (b == J) {
-    const int ptot = scal[1], pend = (ptot + 63) / 64 * 64;
+    const int ptot = scal[SC_PTOT], pend = (ptot + 63) / 64 * 64;
     const double z[4] = {0.0, 0.0, 0.0, 0.0};
     for (int pos = ptot + threadIdx.x; pos < pend; pos += 256) put(pos, make_int4(-1, -1, -1, -1), z, {0.0, 0.0, 0.0}, -1);
     return;
@@ -745,7 +768,7 @@ __global__ void __launch_bounds__(256) kb_pair_scatter(int runs_bound, int J, co
                                                         const int* __restrict__ startB, int* __restrict__ cursor, unsigned* __restrict__ ekey,
                                                         int* __restrict__ eval) {
   const int rr = blockIdx.x * blockDim.x + threadIdx.x;
-  if (scal[15] || rr >= runs_bound || rr >= scal[2]) return;
+  if (scal[SC_STATE] || rr >= runs_bound || rr >= scal[SC_NRUNS]) return;
   const int4 v = *reinterpret_cast<const int4*>(run_nodes + 4 * (size_t)rr);
   const int n[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
@@ -767,7 +790,7 @@ __global__ void __launch_bounds__(256) kb_sort_pairs(int J, const int* __restric
   __shared__ unsigned v[BIN_CAP];
   __shared__ int hs[BIN_CAP];
   __shared__ int tmp[256];
-  if (scal[15]) return;
+  if (scal[SC_STATE]) return;
   const int b = blockIdx.x, base = startB[b], n = startB[b + 1] - base;
   if (n <= 0) {
     if (threadIdx.x == 0) nuq[b] = 0;
@@ -803,7 +826,7 @@ __global__ void __launch_bounds__(256) kb_wg_records(int n_wg, int J, int RB, co
   __shared__ unsigned v[1024];
   __shared__ int hs[1024], hv[1024];
   __shared__ int tmp[256];
-  if (scal[15]) return;
+  if (scal[SC_STATE]) return;
   const int wg = blockIdx.x;
   const int r1 = wgr1[wg], r0 = r1 > 0 ? RB - wgr0x[wg] : 0;
   const int n = 10 * (r1 - r0);
@@ -812,7 +835,7 @@ __global__ void __launch_bounds__(256) kb_wg_records(int n_wg, int J, int RB, co
       nrec[wg] = 0;
       // an invariant of the layout, not of the data: should it ever break, the plan would silently miss records --
       // hand the slot to the rocPRIM pipeline instead (the final read-back sees the flag)
-      if (n > 1024) const_cast<int*>(scal)[15] = 1;
+      if (n > 1024) const_cast<int*>(scal)[SC_STATE] = ST_LEGACY;
     }
     return;
   }
@@ -851,7 +874,7 @@ __global__ void __launch_bounds__(1024) kb_scan_index(int J, int n_wg, int* __re
                                                        int* __restrict__ wg_first, int* __restrict__ wg_last, int* __restrict__ scal) {
   __shared__ int tmp[1024];
   __shared__ int s_max;
-  if (scal[15]) return;
+  if (scal[SC_STATE]) return;
   int* nuq = binv + (size_t)BV_NUQ * (J + 1);
   int* uqoff = binv + (size_t)BV_UQOFF * (J + 1);
   int* startC = binv + (size_t)BV_STARTC * (J + 1);
@@ -872,9 +895,9 @@ __global__ void __launch_bounds__(1024) kb_scan_index(int J, int n_wg, int* __re
   if (threadIdx.x == 0) {
     uqoff[J] = nblocks;
     startC[J] = nrecs;
-    scal[3] = nblocks;
-    scal[6] = nwblk;
-    scal[7] = s_max;
+    scal[SC_NBLOCKS] = nblocks;
+    scal[SC_NWBLK] = nwblk;
+    scal[SC_MAXWBLK] = s_max;
   }
 }
 
@@ -882,12 +905,12 @@ __global__ void __launch_bounds__(1024) kb_scan_index(int J, int n_wg, int* __re
 __global__ void __launch_bounds__(256) kb_pair_fill(int J, const int* __restrict__ binv, const unsigned* __restrict__ ekey,
                                                      const int* __restrict__ sp_uhead, int* __restrict__ blk_key, int* __restrict__ blk_start,
                                                      const int* __restrict__ scal) {
-  if (scal[15]) return;
+  if (scal[SC_STATE]) return;
   const int b = blockIdx.x;
   const int* startB = binv + (size_t)BV_STARTB * (J + 1);
   const int* uqoff = binv + (size_t)BV_UQOFF * (J + 1);
   if (b == J) {
-    if (threadIdx.x == 0) blk_start[scal[3]] = startB[J];
+    if (threadIdx.x == 0) blk_start[scal[SC_NBLOCKS]] = startB[J];
     return;
   }
   const int base = startB[b], nu = binv[(size_t)BV_NUQ * (J + 1) + b], u0 = uqoff[b];
@@ -903,7 +926,7 @@ __global__ void __launch_bounds__(256) kb_rec_scatter(int n_wg, int J, int RB, c
                                                        const int* __restrict__ wgr1, const int* __restrict__ nrec, const int* __restrict__ wg_first,
                                                        const unsigned* __restrict__ reckey_sp, const int* __restrict__ startC,
                                                        int* __restrict__ cursor, unsigned* __restrict__ rkey, int* __restrict__ ru) {
-  if (scal[15]) return;
+  if (scal[SC_STATE]) return;
   const int wg = blockIdx.x;
   const int r1 = wgr1[wg], r0 = r1 > 0 ? RB - wgr0x[wg] : 0;
   const int nr = nrec[wg], u0 = wg_first[wg];
@@ -924,18 +947,18 @@ __global__ void __launch_bounds__(256) kb_rec_sort(int J, const int* __restrict_
   __shared__ unsigned v[BIN_CAP];
   __shared__ int hs[BIN_CAP];
   __shared__ int tmp[256];
-  if (scal[15]) return;
+  if (scal[SC_STATE]) return;
   const int b = blockIdx.x;
   const int* startC = binv + (size_t)BV_STARTC * (J + 1);
   const int* uqoff = binv + (size_t)BV_UQOFF * (J + 1);
   if (b == J) {
-    if (threadIdx.x == 0) blk2_start[scal[3]] = scal[6];
+    if (threadIdx.x == 0) blk2_start[scal[SC_NBLOCKS]] = scal[SC_NWBLK];
     return;
   }
   const int base = startC[b], n = startC[b + 1] - base;
   if (n <= 0) return;
   if (n > BIN_CAP) {                                       // (never: records of a node <= its entries, checked in phase B)
-    if (threadIdx.x == 0) const_cast<int*>(scal)[15] = 1;  // ... and if it ever happens: the rocPRIM pipeline, not a plan with holes
+    if (threadIdx.x == 0) const_cast<int*>(scal)[SC_STATE] = ST_LEGACY;  // ... and if it ever happens: the rocPRIM pipeline, not a plan with holes
     return;
   }
   for (int i = threadIdx.x; i < n; i += 256) {
@@ -958,22 +981,65 @@ __global__ void __launch_bounds__(256) kb_rec_sort(int J, const int* __restrict_
     if (v[i]) blk2_start[u0 + hs[i]] = base + i;
 }
 
-template <typename T>
-hipError_t grow_raw(T*& p, size_t& cap, size_t need) {
-  if (need <= cap) return hipSuccess;
-  if (p) {
-    hipError_t e = hipFree(p);
-    if (e != hipSuccess) return e;
-    p = nullptr;
-    cap = 0;
+#define PCHK(expr)                      \
+  do {                                  \
+    hipError_t e_ = (expr);             \
+    if (e_ != hipSuccess) return e_;    \
+  } while (0)
+
+// One grow-only device array: freed and allocated anew with 12 % + 64 elements of head-room.  (Not the `grow` of
+// slm_api.hip / slm_sem.hip: those count into slm_debug_counters and round differently.)
+hipError_t grow_raw(void** p, size_t* cap, size_t need, size_t esz) {
+  if (need <= *cap) return hipSuccess;
+  if (*p) {
+    PCHK(hipFree(*p));
+    *p = nullptr;
+    *cap = 0;
   }
   const size_t want = need + need / 8 + 64;
-  hipError_t e = hipMalloc((void**)&p, want * sizeof(T));
-  if (e == hipSuccess) cap = want;
-  return e;
+  PCHK(hipMalloc(p, want * esz));
+  *cap = want;
+  return hipSuccess;
+}
+
+// What a struct owns: one row per device array -- where its pointer and the capacity it is recorded under sit in the
+// struct, and its element size.  Arrays recorded under the same capacity are a GROUP.  Growth (grow_group) and release
+// (free_arrays) both walk the struct's table, so an array that can be grown is also freed.
+struct DevArray { size_t ptr, cap, esz; };
+#define ARR(S, name, cap) {offsetof(S, name), offsetof(S, cap), sizeof(*((S*)nullptr)->name)}
+
+// Grows the group recorded at cap_off as a unit: every member its own allocation, in table order.  While the members
+// differ the recorded capacity is 0, and a failure leaves it there: never more than what every member really has (the
+// next bind then frees and allocates the whole group again).
+template <size_t M>
+hipError_t grow_group(void* s, const DevArray (&tab)[M], size_t cap_off, size_t need) {
+  size_t& cap = *reinterpret_cast<size_t*>((char*)s + cap_off);
+  if (need <= cap) return hipSuccess;
+  const size_t old = cap;
+  size_t c = old;
+  cap = 0;
+  for (const DevArray& a : tab)
+    if (a.cap == cap_off) {
+      c = old;
+      PCHK(grow_raw(reinterpret_cast<void**>((char*)s + a.ptr), &c, need, a.esz));
+    }
+  cap = c;
+  return hipSuccess;
+}
+#define GROW(s, tab, cap, need) grow_group(s, tab, offsetof(std::remove_pointer_t<decltype(s)>, cap), need)
+
+template <size_t M>
+void free_arrays(void* s, const DevArray (&tab)[M]) {
+  for (const DevArray& a : tab)
+    if (void* q = *reinterpret_cast<void**>((char*)s + a.ptr)) (void)hipFree(q);
 }
 
 }  // namespace
+
+struct PrimScratch {   // rocPRIM temporary storage, and the three counts its size was last queried for
+  char* buf = nullptr;
+  size_t cap = 0, q[3] = {0, 0, 0};
+};
 
 struct PrepBuffers {
   // phase A
@@ -991,11 +1057,8 @@ struct PrepBuffers {
       *b2count = nullptr;
   unsigned *pk2 = nullptr, *spk2 = nullptr, *upk2 = nullptr;
   size_t cap_w = 0;
-  void* tmp = nullptr;
-  size_t cap_tmp = 0;
-  size_t q_n = 0, q_t = 0, q_e = 0;   // sizes the rocPRIM temporary-storage requirement was last queried for
-  int* scal = nullptr;        // device: nt, ptot, nruns, nblocks, nunique, ..., [8..11] the two 64-bit graph hashes, [12] unclamped nt, [13] bad surfel KNN index seen
-                              // binned preparation: [14] largest bin, [15] 1 = a bin exceeds the LDS sort (legacy path), 2 = a plan buffer bound did not hold
+  PrimScratch tmp;            // of the rocPRIM pipeline (prep_v1_legacy)
+  int* scal = nullptr;        // device: the status block, SC_COUNT ints (slots: enum SC_*)
   int* scal_host = nullptr;   // pinned mirror
   // ---- binned preparation (prep_v1_binned) ----
   int* bins = nullptr;        // one zeroed region per bind: [cntA | cntB | cntC | wg_r0 | wg_r1]
@@ -1010,11 +1073,34 @@ struct PrepBuffers {
   size_t cap_ent = 0, cap_nwg = 0;
   // ---- K-generic pair plan (prep_pairs) ----
   unsigned *gk = nullptr, *gsk = nullptr;   // N * K(K+1)/2 pair keys, unsorted / sorted (gk again: the distinct ones)
-  unsigned* gcnt = nullptr;                 // their count
-  size_t cap_g = 0, q_g = 0, q_gN = 0;      // capacity; key / surfel counts the rocPRIM scratch requirement was last queried for
-  void* gtmp = nullptr;
-  size_t cap_gtmp = 0;
+  unsigned* gcnt = nullptr;                 // their count (one unsigned, allocated at the first use)
+  size_t cap_g = 0;
+  PrimScratch gtmp;           // of prep_pairs: separate, so that a worker that alternates K = 4 and K != 4 frames does not query at every bind
 };
+
+namespace {
+#define A(name, cap) ARR(PrepBuffers, name, cap)
+constexpr DevArray kPrepArrays[] = {
+    A(keys, cap_n), A(skeys, cap_n), A(tkeys, cap_n), A(ids, cap_n), A(sids, cap_n), A(tcount, cap_n),
+    A(tstart, cap_t), A(pc, cap_t), A(pstart, cap_t), A(nruns, cap_t), A(rstart, cap_t),
+    A(pkeys, cap_e), A(spkeys, cap_e), A(ukeys, cap_e), A(pvals, cap_e), A(bcount, cap_e),
+    A(wkeys, cap_w), A(swkeys, cap_w), A(uwkeys, cap_w), A(wvals, cap_w), A(swvals, cap_w), A(wcount, cap_w), A(wstart, cap_w),
+    A(pv2, cap_w), A(spv2, cap_w), A(b2count, cap_w), A(pk2, cap_w), A(spk2, cap_w), A(upk2, cap_w),
+    A(tmp.buf, tmp.cap), A(bins, cap_bins), A(binv, cap_binv), A(nrec, cap_nwg),
+    A(sp_head, cap_sp), A(sp_pcl, cap_sp), A(sp_rl, cap_sp),
+    A(ekey, cap_ent), A(rkey, cap_ent), A(eval, cap_ent), A(ru, cap_ent), A(sp_uhead, cap_ent), A(reckey_sp, cap_ent),
+    A(gk, cap_g), A(gsk, cap_g), A(gtmp.buf, gtmp.cap)};
+#undef A
+#define A(name, cap) ARR(V1Plan, name, cap)
+constexpr DevArray kPlanArrays[] = {
+    A(s_pts, cap_pts), A(s_idx, cap_idx), A(s_w, cap_w), A(grp_run, cap_grp), A(run_nodes, cap_runs), A(run_chunk, cap_rchunk),
+    A(slab, cap_slab), A(blk_key, cap_bkey), A(blk_start, cap_bstart), A(blk_entry, cap_bentry), A(wg_first, cap_wg),
+    A(wg_last, cap_wg), A(run_lidx, cap_lidx), A(blk2_start, cap_b2start), A(blk2_entry, cap_b2entry), A(wgslab, cap_wgslab)};
+#undef A
+#define A(name, cap) ARR(PairPlan, name, cap)
+constexpr DevArray kPairPlanArrays[] = {A(blk_key, cap_key), A(sf_pidx, cap_pidx), A(sf_perm, cap_perm)};
+#undef A
+}  // namespace
 
 PrepBuffers* prep_create() {
   PrepBuffers* p = new PrepBuffers();
@@ -1028,228 +1114,206 @@ PrepBuffers* prep_create() {
 
 void prep_destroy(PrepBuffers* p) {
   if (!p) return;
-  void* ptrs[] = {p->keys, p->skeys, p->tkeys, p->ids, p->sids, p->tcount, p->tstart, p->pc, p->pstart,
-                  p->nruns, p->rstart, p->pkeys, p->spkeys, p->ukeys, p->pvals, p->bcount, p->tmp, p->scal,
-                  p->wkeys, p->swkeys, p->uwkeys, p->wvals, p->swvals, p->wcount, p->wstart, p->pv2, p->spv2,
-                  p->b2count, p->pk2, p->spk2, p->upk2, p->bins, p->binv, p->sp_head, p->sp_pcl, p->sp_rl, p->ekey, p->rkey,
-                  p->eval, p->ru, p->sp_uhead, p->nrec, p->reckey_sp, p->gk, p->gsk, p->gcnt, p->gtmp};
-  for (void* q : ptrs)
-    if (q) (void)hipFree(q);
+  free_arrays(p, kPrepArrays);
+  if (p->scal) (void)hipFree(p->scal);   // (the three fixed-size allocations)
+  if (p->gcnt) (void)hipFree(p->gcnt);
   if (p->scal_host) (void)hipHostFree(p->scal_host);
   delete p;
 }
 
-#define PCHK(expr)                      \
-  do {                                  \
-    hipError_t e_ = (expr);             \
-    if (e_ != hipSuccess) return e_;    \
-  } while (0)
+void plan_free(V1Plan& plan) {
+  free_arrays(&plan, kPlanArrays);
+  plan = V1Plan();
+}
 
-static hipError_t ensure_tmp(PrepBuffers* p, size_t bytes) {
-  size_t cap = p->cap_tmp;
-  char* q = (char*)p->tmp;
-  hipError_t e = grow_raw(q, cap, bytes);
-  p->tmp = q;
-  p->cap_tmp = cap;
-  return e;
+void pairplan_free(PairPlan& plan) {
+  free_arrays(&plan, kPairPlanArrays);
+  plan = PairPlan();
 }
 
 // rocPRIM's size queries cost tens of microseconds of host time each (device-property look-ups) and
-// slm_bind_frame is host-bound, so the requirement is queried once per buffer capacity -- for N, the
-// tuple capacity and the entry capacity, which only change when a buffer grows -- and every call then
-// gets the whole scratch buffer (rocPRIM accepts more than it needs and reports too little as an error).
-static hipError_t ensure_tmp_for(PrepBuffers* p, size_t N, size_t cap_t, size_t cap_e, hipStream_t st) {
-  if (p->q_n == N && p->q_t == cap_t && p->q_e == cap_e && p->tmp) return hipSuccess;
-  size_t need = 0, b = 0;
-  auto upd = [&](hipError_t e) {
-    need = b > need ? b : need;
-    b = 0;
-    return e;
-  };
-  hipError_t e = hipSuccess;
-  unsigned long long* k64 = nullptr;
-  unsigned* k32 = nullptr;
-  int* v = nullptr;
-  if ((e = upd(rocprim::radix_sort_pairs(nullptr, b, k64, k64, v, v, N, 0, 64, st))) != hipSuccess) return e;
-  if ((e = upd(rocprim::run_length_encode(nullptr, b, k64, N, k64, v, v, st))) != hipSuccess) return e;
-  if ((e = upd(rocprim::exclusive_scan(nullptr, b, v, v, 0, cap_t, rocprim::plus<int>(), st))) != hipSuccess) return e;
-  if ((e = upd(rocprim::radix_sort_pairs(nullptr, b, k32, k32, v, v, cap_e, 0, 32, st))) != hipSuccess) return e;
-  if ((e = upd(rocprim::run_length_encode(nullptr, b, k32, cap_e, k32, v, v, st))) != hipSuccess) return e;
-  if ((e = upd(rocprim::exclusive_scan(nullptr, b, v, v, 0, cap_e, rocprim::plus<int>(), st))) != hipSuccess) return e;
-  if ((e = upd(rocprim::radix_sort_pairs(nullptr, b, k64, k64, v, v, cap_e, 0, 64, st))) != hipSuccess) return e;
-  if ((e = upd(rocprim::run_length_encode(nullptr, b, k64, cap_e, k64, v, v, st))) != hipSuccess) return e;
-  e = ensure_tmp(p, need + need / 4 + (1u << 20));
-  if (e != hipSuccess) return e;
-  p->q_n = N;
-  p->q_t = cap_t;
-  p->q_e = cap_e;
+// slm_bind_frame is host-bound, so the requirement is queried once per buffer capacity -- for counts (a, b, c) that
+// only change when a buffer grows -- and every call then gets the whole scratch buffer (rocPRIM accepts more than it
+// needs and reports too little as an error).  query(need) sets the largest requirement in bytes.
+template <typename Query>
+static hipError_t ensure_scratch(PrepBuffers* p, PrimScratch& s, size_t a, size_t b, size_t c, size_t slack, Query query) {
+  if (s.buf && s.q[0] == a && s.q[1] == b && s.q[2] == c) return hipSuccess;
+  size_t need = 0;
+  PCHK(query(need));
+  PCHK(grow_group(p, kPrepArrays, (size_t)((char*)&s.cap - (char*)p), need + need / 4 + slack));
+  s.q[0] = a;
+  s.q[1] = b;
+  s.q[2] = c;
   return hipSuccess;
+}
+
+// The first n ints of the status block, on the host when this returns.
+static hipError_t read_scal(PrepBuffers* p, int n, hipStream_t st) {
+  PCHK(hipMemcpyAsync(p->scal_host, p->scal, n * sizeof(int), hipMemcpyDeviceToHost, st));
+  return hipStreamSynchronize(st);
 }
 
 hipError_t prep_check_knn(PrepBuffers* p, const slm_frame& f, bool* bad, hipStream_t st) {
   *bad = false;
   if (f.N <= 0) return hipSuccess;
-  PCHK(hipMemsetAsync(p->scal + 13, 0, sizeof(int), st));
+  PCHK(hipMemsetAsync(p->scal + SC_BAD_KNN, 0, sizeof(int), st));
   const long long n_ed = (long long)f.J * f.K_ED, n_thr = n_ed > f.N ? n_ed : (long long)f.N;
   hipLaunchKernelGGL(k_check_knn, dim3((unsigned)((n_thr + 255) / 256)), dim3(256), 0, st, f.N, f.K, f.J, f.sf_knn_idx, n_ed,
-                     f.ed_knn_idx, p->scal + 13);
-  PCHK(hipMemcpyAsync(p->scal_host + 13, p->scal + 13, sizeof(int), hipMemcpyDeviceToHost, st));
+                     f.ed_knn_idx, p->scal + SC_BAD_KNN);
+  PCHK(hipMemcpyAsync(p->scal_host + SC_BAD_KNN, p->scal + SC_BAD_KNN, sizeof(int), hipMemcpyDeviceToHost, st));
   PCHK(hipStreamSynchronize(st));
-  *bad = p->scal_host[13] != 0;
+  *bad = p->scal_host[SC_BAD_KNN] != 0;
   return hipSuccess;
 }
 
-void plan_free(V1Plan& plan) {
-  void* ptrs[] = {plan.s_pts, plan.s_idx, plan.s_w, plan.grp_run, plan.run_nodes, plan.slab, plan.blk_key,
-                  plan.blk_start, plan.blk_entry, plan.run_chunk, plan.wg_first, plan.wg_last, plan.run_lidx,
-                  plan.wgslab, plan.blk2_start, plan.blk2_entry};
-  for (void* q : ptrs)
-    if (q) (void)hipFree(q);
-  plan = V1Plan();
+// ---- what the two v1 builders share ----------------------------------------------------------------------------------
+// The numbers that size the buffers, grids and scans of a build.
+struct V1Bounds {
+  size_t nt = 0, pos_bound = 0, runs_bound = 0, n_entries = 0, n_wg = 0;
+};
+static V1Bounds v1_bounds_of(size_t nt, size_t pos_bound, size_t runs_bound) {
+  return {nt, pos_bound, runs_bound, 10 * runs_bound, pos_bound / 256 + 1};
+}
+// ... from a tuple count alone: every tuple pads its segment by at most 3 positions and starts at most one run more than
+// its positions fill
+static V1Bounds v1_bounds(size_t N, size_t nt) {
+  const size_t pos_bound = (N + 3 * nt + 63) / 64 * 64;
+  return v1_bounds_of(nt, pos_bound, nt + pos_bound / 64 + 1);
+}
+// The tuple count sizes the buffers and grids of a build.  A plan that has been built before carries the count of its
+// last frame: with 12 % + 64 head-room on that hint as the BOUND nothing has to be read back before the end (the kernels
+// take the count from the device and keep inside the bound; the bound sizes buffers, grids and scans) -- the one
+// read-back at the end says whether the bound held; if not (the scene changed abruptly) the preparation runs again with
+// the exact count.  A host <-> device round trip costs 0.1 ms when all is well and was seen to take 3-7 ms now and then
+// (stall_hunt.py).
+static size_t hinted_tuples(size_t N, int hint) {
+  const size_t nt = (size_t)hint + (size_t)hint / 8 + 64;
+  return nt > N ? N : nt;
 }
 
-static hipError_t prep_v1_legacy(PrepBuffers* p, const slm_frame& f, V1Plan& plan, V1Sizes* out, hipStream_t st) {
-  const size_t N = (size_t)f.N;
-  out->n_tuples = out->n_pos = out->n_runs = out->n_blocks = 0;
-  out->n_wblk = out->max_wblk_per_wg = 0;
-  if (N == 0) return hipSuccess;
-  // ---- phase A: tuples ----------------------------------------------------------
-  if (N > p->cap_n) {
-    size_t c;
-    c = p->cap_n; PCHK(grow_raw(p->keys, c, N));
-    c = p->cap_n; PCHK(grow_raw(p->skeys, c, N));
-    c = p->cap_n; PCHK(grow_raw(p->tkeys, c, N));
-    c = p->cap_n; PCHK(grow_raw(p->ids, c, N));
-    c = p->cap_n; PCHK(grow_raw(p->sids, c, N));
-    c = p->cap_n; PCHK(grow_raw(p->tcount, c, N));
-    p->cap_n = c;
-  }
-  PCHK(hipMemsetAsync(p->scal + 13, 0, sizeof(int), st));
-  hipLaunchKernelGGL(k_tuple_keys, dim3((N + 255) / 256), dim3(256), 0, st, (int)N, f.J, f.sf_knn_idx,
-                     p->keys, p->ids, p->scal + 13);
-  PCHK(ensure_tmp_for(p, N, p->cap_t ? p->cap_t : 1, p->cap_e ? p->cap_e : 1, st));
-  size_t b1 = p->cap_tmp, b2 = p->cap_tmp;
-  PCHK(rocprim::radix_sort_pairs(p->tmp, b1, p->keys, p->skeys, p->ids, p->sids, N, 0, 64, st));
-  PCHK(rocprim::run_length_encode(p->tmp, b2, p->skeys, N, p->tkeys, p->tcount, p->scal, st));
-  // The tuple count sizes the buffers and grids of everything below.  A plan that has been built before carries the
-  // count of its last frame: with 12 % + 64 head-room on that hint as the BOUND nothing has to be read back here (the
-  // kernels take the count from the device, cut down to the bound by k_clamp_tuples; the bound sizes buffers, grids and scans) -- the one read-back at the end
-  // says whether the bound held; if not (the scene changed abruptly) the preparation runs again with the exact count.
-  // A host <-> device round trip costs 0.1 ms when all is well and was seen to take 3-7 ms now and then (stall_hunt.py).
-  size_t nt;
-  const bool hinted = plan.nt_hint > 0;
-  if (hinted) {
-    nt = (size_t)plan.nt_hint + (size_t)plan.nt_hint / 8 + 64;
-    if (nt > N) nt = N;
-    hipLaunchKernelGGL(k_clamp_tuples, dim3(1), dim3(1), 0, st, p->scal, (int)nt);
-  } else {
-    PCHK(hipMemcpyAsync(p->scal_host, p->scal, sizeof(int), hipMemcpyDeviceToHost, st));
-    PCHK(hipStreamSynchronize(st));
-    nt = (size_t)p->scal_host[0];
-    if (nt == 0) return hipSuccess;
-  }
+// The buffers of a plan for bounds b: all sixteen but wgslab (finish_v1: its size is a result of the build).
+static hipError_t grow_plan(V1Plan& plan, const V1Bounds& b, bool state_f64) {
+  const size_t esz = state_f64 ? 2 : 1;   // s_pts / s_w are sized in floats; a float64 state needs twice that
+  PCHK(GROW(&plan, kPlanArrays, cap_pts, esz * 3 * b.pos_bound));
+  PCHK(GROW(&plan, kPlanArrays, cap_idx, 4 * b.pos_bound));
+  PCHK(GROW(&plan, kPlanArrays, cap_w, esz * 4 * b.pos_bound));
+  PCHK(GROW(&plan, kPlanArrays, cap_grp, b.pos_bound / 4));
+  PCHK(GROW(&plan, kPlanArrays, cap_runs, 4 * b.runs_bound));
+  PCHK(GROW(&plan, kPlanArrays, cap_rchunk, b.runs_bound));
+  PCHK(GROW(&plan, kPlanArrays, cap_slab, (size_t)SLM_SLAB_STRIDE * b.runs_bound));
+  PCHK(GROW(&plan, kPlanArrays, cap_bkey, b.n_entries));
+  PCHK(GROW(&plan, kPlanArrays, cap_bstart, b.n_entries + 1));
+  PCHK(GROW(&plan, kPlanArrays, cap_bentry, b.n_entries));
+  PCHK(GROW(&plan, kPlanArrays, cap_wg, b.n_wg));   // wg_first, wg_last
+  PCHK(GROW(&plan, kPlanArrays, cap_lidx, 10 * b.runs_bound));
+  PCHK(GROW(&plan, kPlanArrays, cap_b2start, b.n_entries + 1));
+  return GROW(&plan, kPlanArrays, cap_b2entry, b.n_entries);
+}
 
-  // ---- phase B: layout, sorted copies, inverted index ------------------------------
-  const size_t pos_bound = (N + 3 * nt + 63) / 64 * 64;
-  const size_t runs_bound = nt + pos_bound / 64 + 1;
-  const size_t n_entries = 10 * runs_bound;
-  if (nt > p->cap_t) {
-    size_t c;
-    c = p->cap_t; PCHK(grow_raw(p->tstart, c, nt));
-    c = p->cap_t; PCHK(grow_raw(p->pc, c, nt));
-    c = p->cap_t; PCHK(grow_raw(p->pstart, c, nt));
-    c = p->cap_t; PCHK(grow_raw(p->nruns, c, nt));
-    c = p->cap_t; PCHK(grow_raw(p->rstart, c, nt));
-    p->cap_t = c;
-  }
-  if (n_entries > p->cap_e) {
-    size_t c;
-    c = p->cap_e; PCHK(grow_raw(p->pkeys, c, n_entries));
-    c = p->cap_e; PCHK(grow_raw(p->spkeys, c, n_entries));
-    c = p->cap_e; PCHK(grow_raw(p->ukeys, c, n_entries));
-    c = p->cap_e; PCHK(grow_raw(p->pvals, c, n_entries));
-    c = p->cap_e; PCHK(grow_raw(p->bcount, c, n_entries));
-    p->cap_e = c;
-  }
-  // s_pts / s_w are sized in floats; a float64 state needs twice that
-  const size_t esz = f.state_f64 ? 2 : 1;
-  PCHK(grow_raw(plan.s_pts, plan.cap_pts, esz * 3 * pos_bound));
-  PCHK(grow_raw(plan.s_idx, plan.cap_idx, 4 * pos_bound));
-  PCHK(grow_raw(plan.s_w, plan.cap_w, esz * 4 * pos_bound));
-  PCHK(grow_raw(plan.grp_run, plan.cap_grp, pos_bound / 4));
-  PCHK(grow_raw(plan.run_nodes, plan.cap_runs, 4 * runs_bound));
-  PCHK(grow_raw(plan.run_chunk, plan.cap_rchunk, runs_bound));
-  PCHK(grow_raw(plan.slab, plan.cap_slab, (size_t)SLM_SLAB_STRIDE * runs_bound));
-  PCHK(grow_raw(plan.blk_key, plan.cap_bkey, n_entries));
-  PCHK(grow_raw(plan.blk_start, plan.cap_bstart, n_entries + 1));
-  PCHK(grow_raw(plan.blk_entry, plan.cap_bentry, n_entries));
+// What a build ended in.  retry: the hinted bound did not hold, once more without the hint; legacy: a bin does not fit the
+// LDS sort, the slot goes to the rocPRIM pipeline.
+enum class Built { done, refused, retry, legacy };
 
+// The one reader of the status block that a build has copied back (sh; state: its SC_STATE, or what stands for it).
+static Built read_built(const int* sh, int state, PlanSizes* out) {
+  out->bad_knn = sh[SC_BAD_KNN] != 0;
+  if (out->bad_knn) return Built::refused;   // the caller refuses the frame
+  if (state == ST_LEGACY) return Built::legacy;
+  if (state == ST_MISS) return Built::retry;
+  out->n_blocks = sh[SC_NBLOCKS];
+  memcpy(&out->knn_hash, sh + SC_KNN_HASH, 8);
+  memcpy(&out->graph_hash, sh + SC_GRAPH_HASH, 8);
+  return Built::done;
+}
+
+// The end of a v1 build: the outcome and, when done, the sizes, the hint for the next build and wgslab.  Every other
+// outcome clears the hint: the next preparation reads its sizes back.
+static hipError_t finish_v1(PrepBuffers* p, V1Plan& plan, int state, V1Sizes* out, Built* r) {
+  const int* sh = p->scal_host;
+  *r = read_built(sh, state, out);
+  plan.nt_hint = *r == Built::done ? sh[SC_NT] : 0;
+  if (*r != Built::done) return hipSuccess;
+  out->n_tuples = sh[SC_NT];
+  out->n_pos = (sh[SC_PTOT] + 63) / 64 * 64;
+  out->n_runs = sh[SC_NRUNS];
+  out->n_wblk = sh[SC_NWBLK];
+  out->max_wblk_per_wg = sh[SC_MAXWBLK];
+  PCHK(GROW(&plan, kPlanArrays, cap_wgslab, (size_t)SLM_WREC * (out->n_wblk + 1)));
+  return hipGetLastError();
+}
+
+// ---- the rocPRIM pipeline ----------------------------------------------------------------------------------------------
+static hipError_t legacy_scratch(PrepBuffers* p, size_t N, hipStream_t st) {
+  const size_t cap_t = p->cap_t ? p->cap_t : 1, cap_e = p->cap_e ? p->cap_e : 1;
+  return ensure_scratch(p, p->tmp, N, cap_t, cap_e, 1u << 20, [&](size_t& need) {
+    size_t b[8] = {};
+    unsigned long long* k64 = nullptr;
+    unsigned* k32 = nullptr;
+    int* v = nullptr;
+    PCHK(rocprim::radix_sort_pairs(nullptr, b[0], k64, k64, v, v, N, 0, 64, st));
+    PCHK(rocprim::run_length_encode(nullptr, b[1], k64, N, k64, v, v, st));
+    PCHK(rocprim::exclusive_scan(nullptr, b[2], v, v, 0, cap_t, rocprim::plus<int>(), st));
+    PCHK(rocprim::radix_sort_pairs(nullptr, b[3], k32, k32, v, v, cap_e, 0, 32, st));
+    PCHK(rocprim::run_length_encode(nullptr, b[4], k32, cap_e, k32, v, v, st));
+    PCHK(rocprim::exclusive_scan(nullptr, b[5], v, v, 0, cap_e, rocprim::plus<int>(), st));
+    PCHK(rocprim::radix_sort_pairs(nullptr, b[6], k64, k64, v, v, cap_e, 0, 64, st));
+    PCHK(rocprim::run_length_encode(nullptr, b[7], k64, cap_e, k64, v, v, st));
+    need = *std::max_element(b, b + 8);
+    return hipSuccess;
+  });
+}
+
+// Only the bits a pair key can have are sorted: every 8 bits less is one launch less in a chain of ~90 small launches.
+// A live pair key is < J*J <= 2^pbits - 1, the padding key 0xFFFFFFFF has all of those bits set and still sorts last.
+static unsigned pair_key_bits(int J) {
+  unsigned pbits = 1;
+  while (pbits < 32 && (1ull << pbits) <= (unsigned long long)J * (unsigned long long)J) ++pbits;
+  return pbits;
+}
+
+// phase B: layout, sorted copies, inverted index
+static hipError_t legacy_layout(PrepBuffers* p, const slm_frame& f, V1Plan& plan, const V1Bounds& b, hipStream_t st) {
+  const size_t nt = b.nt, n_entries = b.n_entries;
   const dim3 gt((nt + 255) / 256), blk(256);
   hipLaunchKernelGGL(k_padded_counts, gt, blk, 0, st, p->scal, p->tcount, p->pc);
-  PCHK(ensure_tmp_for(p, N, p->cap_t, p->cap_e, st));
-  size_t bs = p->cap_tmp;
-  PCHK(rocprim::exclusive_scan(p->tmp, bs, p->tcount, p->tstart, 0, nt, rocprim::plus<int>(), st));
-  PCHK(rocprim::exclusive_scan(p->tmp, bs, p->pc, p->pstart, 0, nt, rocprim::plus<int>(), st));
+  PCHK(legacy_scratch(p, (size_t)f.N, st));
+  size_t bs = p->tmp.cap;
+  PCHK(rocprim::exclusive_scan(p->tmp.buf, bs, p->tcount, p->tstart, 0, nt, rocprim::plus<int>(), st));
+  PCHK(rocprim::exclusive_scan(p->tmp.buf, bs, p->pc, p->pstart, 0, nt, rocprim::plus<int>(), st));
   hipLaunchKernelGGL(k_run_counts, gt, blk, 0, st, p->scal, p->pstart, p->pc, p->nruns);
-  PCHK(rocprim::exclusive_scan(p->tmp, bs, p->nruns, p->rstart, 0, nt, rocprim::plus<int>(), st));
+  PCHK(rocprim::exclusive_scan(p->tmp.buf, bs, p->nruns, p->rstart, 0, nt, rocprim::plus<int>(), st));
   hipLaunchKernelGGL(k_totals, dim3(1), dim3(1), 0, st, p->scal, p->pstart, p->pc, p->rstart, p->nruns);
-  hipLaunchKernelGGL(k_fill_sorted, dim3((pos_bound + 255) / 256), blk, 0, st, (int)pos_bound, p->scal, f,
+  hipLaunchKernelGGL(k_fill_sorted, dim3((b.pos_bound + 255) / 256), blk, 0, st, (int)b.pos_bound, p->scal, f,
                      p->tkeys, p->tcount, p->tstart, p->pstart, p->rstart, p->sids, plan.s_pts,
                      plan.s_idx, plan.s_w, plan.grp_run, plan.run_nodes, plan.run_chunk);
-  hipLaunchKernelGGL(k_pairs, dim3((runs_bound + 255) / 256), blk, 0, st, (int)runs_bound, p->scal, f.J,
+  hipLaunchKernelGGL(k_pairs, dim3((b.runs_bound + 255) / 256), blk, 0, st, (int)b.runs_bound, p->scal, f.J,
                      plan.run_nodes, p->pkeys, p->pvals);
-  size_t b3 = p->cap_tmp, b4 = p->cap_tmp, b5 = p->cap_tmp;
-  // (only the bits a key can have are sorted: every 8 bits less is one launch less in a chain of ~90 small launches.
-  //  A live pair key is < J*J <= 2^pbits - 1, the padding key 0xFFFFFFFF has all of those bits set and still sorts last.)
-  unsigned pbits = 1;
-  while (pbits < 32 && (1ull << pbits) <= (unsigned long long)f.J * (unsigned long long)f.J) ++pbits;
-  PCHK(rocprim::radix_sort_pairs(p->tmp, b3, p->pkeys, p->spkeys, p->pvals, plan.blk_entry, n_entries, 0,
-                                 pbits, st));
-  PCHK(rocprim::run_length_encode(p->tmp, b4, p->spkeys, n_entries, p->ukeys, p->bcount, p->scal + 4, st));
+  size_t b3 = p->tmp.cap, b4 = p->tmp.cap, b5 = p->tmp.cap;
+  PCHK(rocprim::radix_sort_pairs(p->tmp.buf, b3, p->pkeys, p->spkeys, p->pvals, plan.blk_entry, n_entries, 0,
+                                 pair_key_bits(f.J), st));
+  PCHK(rocprim::run_length_encode(p->tmp.buf, b4, p->spkeys, n_entries, p->ukeys, p->bcount, p->scal + SC_NUQ, st));
   // scan / copy over the full bound: entries past the unique count are never read
-  PCHK(rocprim::exclusive_scan(p->tmp, b5, p->bcount, plan.blk_start, 0, n_entries, rocprim::plus<int>(), st));
+  PCHK(rocprim::exclusive_scan(p->tmp.buf, b5, p->bcount, plan.blk_start, 0, n_entries, rocprim::plus<int>(), st));
   PCHK(hipMemcpyAsync(plan.blk_key, p->ukeys, sizeof(unsigned) * n_entries, hipMemcpyDeviceToDevice, st));
   hipLaunchKernelGGL(k_totals2, dim3(1), dim3(1), 0, st, p->scal, p->ukeys, plan.blk_start, (int)n_entries);
-  // ---- phase C: (workgroup, pair) records for the LDS-merged Gram path -------------------
-  const size_t n_wg = pos_bound / 256 + 1;
-  if (n_entries > p->cap_w) {
-    size_t c;
-    c = p->cap_w; PCHK(grow_raw(p->wkeys, c, n_entries));
-    c = p->cap_w; PCHK(grow_raw(p->swkeys, c, n_entries));
-    c = p->cap_w; PCHK(grow_raw(p->uwkeys, c, n_entries));
-    c = p->cap_w; PCHK(grow_raw(p->wvals, c, n_entries));
-    c = p->cap_w; PCHK(grow_raw(p->swvals, c, n_entries));
-    c = p->cap_w; PCHK(grow_raw(p->wcount, c, n_entries));
-    c = p->cap_w; PCHK(grow_raw(p->wstart, c, n_entries));
-    c = p->cap_w; PCHK(grow_raw(p->pv2, c, n_entries));
-    c = p->cap_w; PCHK(grow_raw(p->spv2, c, n_entries));
-    c = p->cap_w; PCHK(grow_raw(p->b2count, c, n_entries));
-    c = p->cap_w; PCHK(grow_raw(p->pk2, c, n_entries));
-    c = p->cap_w; PCHK(grow_raw(p->spk2, c, n_entries));
-    c = p->cap_w; PCHK(grow_raw(p->upk2, c, n_entries));
-    p->cap_w = c;
-  }
-  {
-    size_t c1 = plan.cap_wg, c2 = plan.cap_wg;
-    PCHK(grow_raw(plan.wg_first, c1, n_wg));
-    PCHK(grow_raw(plan.wg_last, c2, n_wg));
-    plan.cap_wg = c1 < c2 ? c1 : c2;
-  }
-  PCHK(grow_raw(plan.run_lidx, plan.cap_lidx, 10 * runs_bound));
-  PCHK(grow_raw(plan.blk2_start, plan.cap_b2start, n_entries + 1));
-  PCHK(grow_raw(plan.blk2_entry, plan.cap_b2entry, n_entries));
-  PCHK(hipMemsetAsync(p->scal + 5, 0, 3 * sizeof(int), st));
+  return hipSuccess;
+}
+
+// phase C: (workgroup, pair) records for the LDS-merged Gram path
+static hipError_t legacy_records(PrepBuffers* p, const slm_frame& f, V1Plan& plan, const V1Bounds& b, hipStream_t st) {
+  const size_t n_entries = b.n_entries, n_wg = b.n_wg;
+  const dim3 blk(256), ge((n_entries + 255) / 256);
+  PCHK(hipMemsetAsync(p->scal + SC_NWUQ, 0, 3 * sizeof(int), st));   // SC_NWUQ, SC_NWBLK, SC_MAXWBLK
   PCHK(hipMemsetAsync(plan.wg_first, 0, n_wg * sizeof(int), st));
   PCHK(hipMemsetAsync(plan.wg_last, 0xFF, n_wg * sizeof(int), st));   // -1
-  hipLaunchKernelGGL(k_pairs2, dim3((runs_bound + 255) / 256), blk, 0, st, (int)runs_bound, p->scal, f.J,
+  hipLaunchKernelGGL(k_pairs2, dim3((b.runs_bound + 255) / 256), blk, 0, st, (int)b.runs_bound, p->scal, f.J,
                      plan.run_nodes, plan.run_chunk, p->wkeys, p->wvals);
-  size_t c1 = p->cap_tmp, c2 = p->cap_tmp, c3 = p->cap_tmp, c4 = p->cap_tmp, c5 = p->cap_tmp;
+  size_t c1 = p->tmp.cap, c2 = p->tmp.cap, c3 = p->tmp.cap, c4 = p->tmp.cap, c5 = p->tmp.cap;
   unsigned wbits = 1;   // a live key's workgroup is < n_wg <= 2^wbits - 1; the padding key ~0 sorts last
   while (wbits < 32 && (1ull << wbits) <= (unsigned long long)n_wg) ++wbits;
-  PCHK(rocprim::radix_sort_pairs(p->tmp, c1, p->wkeys, p->swkeys, p->wvals, p->swvals, n_entries, 0, 32 + wbits, st));
-  PCHK(rocprim::run_length_encode(p->tmp, c2, p->swkeys, n_entries, p->uwkeys, p->wcount, p->scal + 5, st));
-  PCHK(rocprim::exclusive_scan(p->tmp, c3, p->wcount, p->wstart, 0, n_entries, rocprim::plus<int>(), st));
-  const dim3 ge((n_entries + 255) / 256);
+  PCHK(rocprim::radix_sort_pairs(p->tmp.buf, c1, p->wkeys, p->swkeys, p->wvals, p->swvals, n_entries, 0, 32 + wbits, st));
+  PCHK(rocprim::run_length_encode(p->tmp.buf, c2, p->swkeys, n_entries, p->uwkeys, p->wcount, p->scal + SC_NWUQ, st));
+  PCHK(rocprim::exclusive_scan(p->tmp.buf, c3, p->wcount, p->wstart, 0, n_entries, rocprim::plus<int>(), st));
   hipLaunchKernelGGL(k_wg_bounds, ge, blk, 0, st, (int)n_entries, p->scal, p->uwkeys, plan.wg_first, plan.wg_last,
                      p->pk2, p->pv2);
   hipLaunchKernelGGL(k_wg_max, dim3((n_wg + 255) / 256), blk, 0, st, (int)n_wg, plan.wg_first, plan.wg_last,
@@ -1257,70 +1321,67 @@ static hipError_t prep_v1_legacy(PrepBuffers* p, const slm_frame& f, V1Plan& pla
   hipLaunchKernelGGL(k_run_lidx, ge, blk, 0, st, (int)n_entries, p->scal, p->uwkeys, p->wstart, p->wcount,
                      p->swvals, plan.wg_first, plan.run_lidx);
   // pair -> records: same pair order as blk_key (both are the ascending unique pair keys)
-  PCHK(rocprim::radix_sort_pairs(p->tmp, c4, p->pk2, p->spk2, p->pv2, plan.blk2_entry, n_entries, 0, pbits, st));
-  PCHK(rocprim::run_length_encode(p->tmp, c5, p->spk2, n_entries, p->upk2, p->b2count, p->scal + 4, st));
-  PCHK(rocprim::exclusive_scan(p->tmp, c3, p->b2count, plan.blk2_start, 0, n_entries, rocprim::plus<int>(), st));
+  PCHK(rocprim::radix_sort_pairs(p->tmp.buf, c4, p->pk2, p->spk2, p->pv2, plan.blk2_entry, n_entries, 0, pair_key_bits(f.J), st));
+  PCHK(rocprim::run_length_encode(p->tmp.buf, c5, p->spk2, n_entries, p->upk2, p->b2count, p->scal + SC_NUQ, st));
+  PCHK(rocprim::exclusive_scan(p->tmp.buf, c3, p->b2count, plan.blk2_start, 0, n_entries, rocprim::plus<int>(), st));
   hipLaunchKernelGGL(k_totals3, dim3(1), dim3(1), 0, st, p->scal, plan.blk2_start);
-  // hash of the coupling graph (node KNN table + pair keys): rides along with the sizes in the one read-back
-  PCHK(hipMemsetAsync(p->scal + 8, 0, 4 * sizeof(int), st));
-  hipLaunchKernelGGL(k_plan_hash, dim3(16), blk, 0, st, f.J, f.K_ED, f.ed_knn_idx, plan.blk_key, p->scal,
-                     reinterpret_cast<unsigned long long*>(p->scal + 8));
+  return hipSuccess;
+}
 
-  PCHK(hipMemcpyAsync(p->scal_host, p->scal, 14 * sizeof(int), hipMemcpyDeviceToHost, st));
-  PCHK(hipStreamSynchronize(st));
-  out->bad_knn = p->scal_host[13] != 0;
-  if (out->bad_knn) {   // the caller refuses the frame; the next preparation starts without a hint
-    plan.nt_hint = 0;
-    return hipSuccess;
+// The rocPRIM pipeline: the path for a bin over BIN_CAP (and SLM_PREP_LEGACY=1), and what the binned preparation is
+// tested against.  Hinted: one read-back at the end; else one more for the tuple count.
+static hipError_t prep_v1_legacy(PrepBuffers* p, const slm_frame& f, V1Plan& plan, V1Sizes* out, Built* r, hipStream_t st) {
+  const size_t N = (size_t)f.N;
+  const bool hinted = plan.nt_hint > 0;
+  *r = Built::done;
+  // ---- phase A: tuples ----------------------------------------------------------
+  PCHK(GROW(p, kPrepArrays, cap_n, N));
+  PCHK(hipMemsetAsync(p->scal + SC_BAD_KNN, 0, sizeof(int), st));
+  hipLaunchKernelGGL(k_tuple_keys, dim3((N + 255) / 256), dim3(256), 0, st, (int)N, f.J, f.sf_knn_idx,
+                     p->keys, p->ids, p->scal + SC_BAD_KNN);
+  PCHK(legacy_scratch(p, N, st));
+  size_t b1 = p->tmp.cap, b2 = p->tmp.cap;
+  PCHK(rocprim::radix_sort_pairs(p->tmp.buf, b1, p->keys, p->skeys, p->ids, p->sids, N, 0, 64, st));
+  PCHK(rocprim::run_length_encode(p->tmp.buf, b2, p->skeys, N, p->tkeys, p->tcount, p->scal + SC_NT, st));
+  V1Bounds b;
+  if (hinted) {   // the kernels below take the count from the device, cut down to the bound by k_clamp_tuples
+    b = v1_bounds(N, hinted_tuples(N, plan.nt_hint));
+    hipLaunchKernelGGL(k_clamp_tuples, dim3(1), dim3(1), 0, st, p->scal, (int)b.nt);
+  } else {
+    PCHK(read_scal(p, 1, st));
+    b = v1_bounds(N, (size_t)p->scal_host[SC_NT]);
+    if (b.nt == 0) return hipSuccess;
   }
-  if (hinted && (size_t)p->scal_host[12] > nt) {   // the hinted bound did not hold: once more with the exact count
-    plan.nt_hint = 0;
-    return prep_v1_legacy(p, f, plan, out, st);
-  }
-  plan.nt_hint = p->scal_host[0];
-  memcpy(&out->knn_hash, p->scal_host + 8, 8);
-  memcpy(&out->graph_hash, p->scal_host + 10, 8);
-  out->n_tuples = p->scal_host[0];
-  out->n_pos = (p->scal_host[1] + 63) / 64 * 64;
-  out->n_runs = p->scal_host[2];
-  out->n_blocks = p->scal_host[3];
-  out->n_wblk = p->scal_host[6];
-  out->max_wblk_per_wg = p->scal_host[7];
-  PCHK(grow_raw(plan.wgslab, plan.cap_wgslab, (size_t)SLM_WREC * (out->n_wblk + 1)));
-  return hipGetLastError();
+  PCHK(GROW(p, kPrepArrays, cap_t, b.nt));
+  PCHK(GROW(p, kPrepArrays, cap_e, b.n_entries));
+  PCHK(grow_plan(plan, b, f.state_f64));
+  PCHK(legacy_layout(p, f, plan, b, st));
+  PCHK(GROW(p, kPrepArrays, cap_w, b.n_entries));
+  PCHK(legacy_records(p, f, plan, b, st));
+  // hash of the coupling graph (node KNN table + pair keys): rides along with the sizes in the one read-back
+  PCHK(hipMemsetAsync(p->scal + SC_KNN_HASH, 0, 4 * sizeof(int), st));   // both hashes
+  hipLaunchKernelGGL(k_plan_hash, dim3(16), dim3(256), 0, st, f.J, f.K_ED, f.ed_knn_idx, plan.blk_key, p->scal,
+                     reinterpret_cast<unsigned long long*>(p->scal + SC_KNN_HASH));
+  PCHK(read_scal(p, SC_BAD_KNN + 1, st));
+  // (this pipeline keeps no SC_STATE: the bound held if the count k_clamp_tuples saw was inside it)
+  const bool miss = hinted && (size_t)p->scal_host[SC_NT_TRUE] > b.nt;
+  return finish_v1(p, plan, miss ? ST_MISS : ST_OK, out, r);
 }
 
 // The binned preparation (kernels above).  Same outputs as prep_v1_legacy, array for array.  Hinted (the plan carries the
 // tuple count of its last frame): one read-back at the end; first frame of a plan: one more after the layout pass.
-static hipError_t prep_v1_binned(PrepBuffers* p, const slm_frame& f, V1Plan& plan, V1Sizes* out, hipStream_t st, bool* use_legacy) {
+static hipError_t prep_v1_binned(PrepBuffers* p, const slm_frame& f, V1Plan& plan, V1Sizes* out, Built* r, hipStream_t st) {
   const size_t N = (size_t)f.N;
   const int J = f.J;
-  *use_legacy = false;
-  out->n_tuples = out->n_pos = out->n_runs = out->n_blocks = 0;
-  out->n_wblk = out->max_wblk_per_wg = 0;
-  if (N == 0) return hipSuccess;
-  if (N > p->cap_n) {
-    size_t c;
-    c = p->cap_n; PCHK(grow_raw(p->keys, c, N));
-    c = p->cap_n; PCHK(grow_raw(p->skeys, c, N));
-    c = p->cap_n; PCHK(grow_raw(p->tkeys, c, N));
-    c = p->cap_n; PCHK(grow_raw(p->ids, c, N));
-    c = p->cap_n; PCHK(grow_raw(p->sids, c, N));
-    c = p->cap_n; PCHK(grow_raw(p->tcount, c, N));
-    p->cap_n = c;
-  }
-  if (N > p->cap_sp) {
-    size_t c;
-    c = p->cap_sp; PCHK(grow_raw(p->sp_head, c, N));
-    c = p->cap_sp; PCHK(grow_raw(p->sp_pcl, c, N));
-    c = p->cap_sp; PCHK(grow_raw(p->sp_rl, c, N));
-    p->cap_sp = c;
-  }
+  const int* sh = p->scal_host;
+  *r = Built::done;
+  PCHK(GROW(p, kPrepArrays, cap_n, N));
+  PCHK(GROW(p, kPrepArrays, cap_sp, N));
   const size_t nb1 = (size_t)J + 1;
   const size_t n_wg_max = (4 * N + 63) / 256 + 2;          // positions <= N + 3 * tuples <= 4 N
-  PCHK(grow_raw(p->bins, p->cap_bins, 3 * nb1 + 2 * n_wg_max));
-  PCHK(grow_raw(p->binv, p->cap_binv, (size_t)BV_COUNT * nb1));
-  PCHK(grow_raw(p->nrec, p->cap_nwg, n_wg_max));
+  PCHK(GROW(p, kPrepArrays, cap_bins, 3 * nb1 + 2 * n_wg_max));
+  PCHK(GROW(p, kPrepArrays, cap_binv, (size_t)BV_COUNT * nb1));
+  PCHK(GROW(p, kPrepArrays, cap_nwg, n_wg_max));
   int* cntA = p->bins;
   int* cntB = cntA + nb1;
   int* cntC = cntB + nb1;
@@ -1329,67 +1390,30 @@ static hipError_t prep_v1_binned(PrepBuffers* p, const slm_frame& f, V1Plan& pla
   int* bv = p->binv;
   auto BV = [&](int which) { return bv + (size_t)which * nb1; };
   PCHK(hipMemsetAsync(p->bins, 0, sizeof(int) * (3 * nb1 + 2 * n_wg_max), st));
-  PCHK(hipMemsetAsync(p->scal, 0, sizeof(int) * 16, st));
+  PCHK(hipMemsetAsync(p->scal, 0, sizeof(int) * SC_COUNT, st));
   const dim3 blk(256);
-  hipLaunchKernelGGL(kb_keys, dim3((N + 255) / 256), blk, 0, st, (int)N, J, f.sf_knn_idx, p->keys, cntA, p->scal + 13);
+  hipLaunchKernelGGL(kb_keys, dim3((N + 255) / 256), blk, 0, st, (int)N, J, f.sf_knn_idx, p->keys, cntA, p->scal + SC_BAD_KNN);
   hipLaunchKernelGGL(kb_scan_bins, dim3(1), dim3(1024), 0, st, J, cntA, BV(BV_STARTA), p->scal, BIN_CAP);
   hipLaunchKernelGGL(kb_scatter, dim3((N + 255) / 256), blk, 0, st, (int)N, p->keys, BV(BV_STARTA), cntA, p->skeys, p->sids, p->scal);
   hipLaunchKernelGGL(kb_sort_bins, dim3(J), blk, 0, st, J, bv, p->skeys, p->sids, p->sp_head, p->sp_pcl, BV(BV_NTUP), BV(BV_NPOS), p->scal);
 
+  // hinted: the layout kernels check the bounds and raise ST_MISS; else they get 0 (no bound) and the exact sizes are read back
   const bool hinted = plan.nt_hint > 0;
-  size_t nt = 0, pos_bound = 0, runs_bound = 0;
-  if (hinted) {
-    nt = (size_t)plan.nt_hint + (size_t)plan.nt_hint / 8 + 64;
-    if (nt > N) nt = N;
-    pos_bound = (N + 3 * nt + 63) / 64 * 64;
-    runs_bound = nt + pos_bound / 64 + 1;
-  }
-  hipLaunchKernelGGL(kb_scan_layout, dim3(1), dim3(1024), 0, st, J, bv, p->scal, (int)pos_bound);
+  V1Bounds b;
+  if (hinted) b = v1_bounds(N, hinted_tuples(N, plan.nt_hint));
+  hipLaunchKernelGGL(kb_scan_layout, dim3(1), dim3(1024), 0, st, J, bv, p->scal, (int)b.pos_bound);
   hipLaunchKernelGGL(kb_runs, dim3(J), blk, 0, st, J, bv, p->sp_head, p->sp_pcl, p->sp_rl, p->scal);
-  hipLaunchKernelGGL(kb_scan_runs, dim3(1), dim3(1024), 0, st, J, bv, p->scal, (int)runs_bound);
+  hipLaunchKernelGGL(kb_scan_runs, dim3(1), dim3(1024), 0, st, J, bv, p->scal, (int)b.runs_bound);
   if (!hinted) {
-    PCHK(hipMemcpyAsync(p->scal_host, p->scal, 16 * sizeof(int), hipMemcpyDeviceToHost, st));
-    PCHK(hipStreamSynchronize(st));
-    if (p->scal_host[15] == 1) { *use_legacy = true; return hipSuccess; }
-    if (p->scal_host[13]) { out->bad_knn = true; plan.nt_hint = 0; return hipSuccess; }
-    nt = (size_t)p->scal_host[0];
-    if (nt == 0) return hipSuccess;
-    pos_bound = ((size_t)p->scal_host[1] + 63) / 64 * 64;
-    runs_bound = (size_t)p->scal_host[2];
+    PCHK(read_scal(p, SC_COUNT, st));
+    if (sh[SC_STATE] == ST_LEGACY) { *r = Built::legacy; return hipSuccess; }
+    if (sh[SC_BAD_KNN]) { out->bad_knn = true; plan.nt_hint = 0; *r = Built::refused; return hipSuccess; }
+    if (sh[SC_NT] == 0) return hipSuccess;
+    b = v1_bounds_of((size_t)sh[SC_NT], ((size_t)sh[SC_PTOT] + 63) / 64 * 64, (size_t)sh[SC_NRUNS]);   // exact, not derived from the count
   }
-  const size_t n_entries = 10 * runs_bound;
-  const size_t n_wg = pos_bound / 256 + 1;
-  // ---- plan buffers (the layout of prep_v1_legacy) ----
-  const size_t esz = f.state_f64 ? 2 : 1;
-  PCHK(grow_raw(plan.s_pts, plan.cap_pts, esz * 3 * pos_bound));
-  PCHK(grow_raw(plan.s_idx, plan.cap_idx, 4 * pos_bound));
-  PCHK(grow_raw(plan.s_w, plan.cap_w, esz * 4 * pos_bound));
-  PCHK(grow_raw(plan.grp_run, plan.cap_grp, pos_bound / 4));
-  PCHK(grow_raw(plan.run_nodes, plan.cap_runs, 4 * runs_bound));
-  PCHK(grow_raw(plan.run_chunk, plan.cap_rchunk, runs_bound));
-  PCHK(grow_raw(plan.slab, plan.cap_slab, (size_t)SLM_SLAB_STRIDE * runs_bound));
-  PCHK(grow_raw(plan.blk_key, plan.cap_bkey, n_entries));
-  PCHK(grow_raw(plan.blk_start, plan.cap_bstart, n_entries + 1));
-  PCHK(grow_raw(plan.blk_entry, plan.cap_bentry, n_entries));
-  {
-    size_t c1 = plan.cap_wg, c2 = plan.cap_wg;
-    PCHK(grow_raw(plan.wg_first, c1, n_wg));
-    PCHK(grow_raw(plan.wg_last, c2, n_wg));
-    plan.cap_wg = c1 < c2 ? c1 : c2;
-  }
-  PCHK(grow_raw(plan.run_lidx, plan.cap_lidx, 10 * runs_bound));
-  PCHK(grow_raw(plan.blk2_start, plan.cap_b2start, n_entries + 1));
-  PCHK(grow_raw(plan.blk2_entry, plan.cap_b2entry, n_entries));
-  if (n_entries > p->cap_ent) {
-    size_t c;
-    c = p->cap_ent; PCHK(grow_raw(p->ekey, c, n_entries));
-    c = p->cap_ent; PCHK(grow_raw(p->rkey, c, n_entries));
-    c = p->cap_ent; PCHK(grow_raw(p->eval, c, n_entries));
-    c = p->cap_ent; PCHK(grow_raw(p->ru, c, n_entries));
-    c = p->cap_ent; PCHK(grow_raw(p->sp_uhead, c, n_entries));
-    c = p->cap_ent; PCHK(grow_raw(p->reckey_sp, c, n_entries));
-    p->cap_ent = c;
-  }
+  PCHK(grow_plan(plan, b, f.state_f64));
+  PCHK(GROW(p, kPrepArrays, cap_ent, b.n_entries));
+  const size_t runs_bound = b.runs_bound, n_wg = b.n_wg;
   const int RB = (int)runs_bound + 1;
   hipLaunchKernelGGL(kb_fill, dim3(J + 1), blk, 0, st, J, f, bv, p->skeys, p->sids, p->sp_head, p->sp_pcl, p->sp_rl, p->scal, plan.s_pts,
                      plan.s_idx, plan.s_w, plan.grp_run, plan.run_nodes, plan.run_chunk, cntB, wgr0x, wgr1, RB);
@@ -1406,57 +1430,36 @@ static hipError_t prep_v1_binned(PrepBuffers* p, const slm_frame& f, V1Plan& pla
   hipLaunchKernelGGL(kb_rec_sort, dim3(J + 1), blk, 0, st, J, bv, p->rkey, p->ru, plan.blk2_start, plan.blk2_entry, p->scal);
   // hash of the coupling graph (node KNN table + pair keys): rides along with the sizes in the one read-back
   hipLaunchKernelGGL(k_plan_hash, dim3(16), blk, 0, st, f.J, f.K_ED, f.ed_knn_idx, plan.blk_key, p->scal,
-                     reinterpret_cast<unsigned long long*>(p->scal + 8));
-  PCHK(hipMemcpyAsync(p->scal_host, p->scal, 16 * sizeof(int), hipMemcpyDeviceToHost, st));
-  PCHK(hipStreamSynchronize(st));
-  out->bad_knn = p->scal_host[13] != 0;
-  if (out->bad_knn) {
-    plan.nt_hint = 0;
-    return hipSuccess;
-  }
-  if (p->scal_host[15] == 1) { *use_legacy = true; return hipSuccess; }
-  if (p->scal_host[15] == 2) {            // a hinted bound did not hold: once more, sizes read back
-    plan.nt_hint = 0;
-    return prep_v1_binned(p, f, plan, out, st, use_legacy);
-  }
-  plan.nt_hint = p->scal_host[0];
-  memcpy(&out->knn_hash, p->scal_host + 8, 8);
-  memcpy(&out->graph_hash, p->scal_host + 10, 8);
-  out->n_tuples = p->scal_host[0];
-  out->n_pos = (p->scal_host[1] + 63) / 64 * 64;
-  out->n_runs = p->scal_host[2];
-  out->n_blocks = p->scal_host[3];
-  out->n_wblk = p->scal_host[6];
-  out->max_wblk_per_wg = p->scal_host[7];
-  PCHK(grow_raw(plan.wgslab, plan.cap_wgslab, (size_t)SLM_WREC * (out->n_wblk + 1)));
-  return hipGetLastError();
+                     reinterpret_cast<unsigned long long*>(p->scal + SC_KNN_HASH));
+  PCHK(read_scal(p, SC_COUNT, st));
+  return finish_v1(p, plan, sh[SC_STATE], out, r);
 }
 
-// Binned preparation unless the slot's plan has met a bin that does not fit the LDS sort (sticky) or SLM_PREP_LEGACY=1.
+// The only place that repeats a build or switches pipelines: binned unless the slot's plan has met a bin that does not
+// fit the LDS sort (sticky) or SLM_PREP_LEGACY=1; on `retry` once more, unhinted (finish_v1 has cleared the hint, and an
+// unhinted build has no bound to miss); on `legacy` the plan is marked and the rocPRIM pipeline runs.
 hipError_t prep_v1(PrepBuffers* p, const slm_frame& f, V1Plan& plan, V1Sizes* out, hipStream_t st) {
   static const bool force_legacy = [] {
     const char* e = getenv("SLM_PREP_LEGACY");
     return e && atoi(e) != 0;
   }();
+  *out = V1Sizes();
+  if (f.N == 0) return hipSuccess;
+  Built r = Built::legacy;
   if (!force_legacy && !plan.legacy) {
-    bool use_legacy = false;
-    const hipError_t e = prep_v1_binned(p, f, plan, out, st, &use_legacy);
-    if (e != hipSuccess || !use_legacy) return e;
+    PCHK(prep_v1_binned(p, f, plan, out, &r, st));
+    if (r == Built::retry) PCHK(prep_v1_binned(p, f, plan, out, &r, st));
+    if (r != Built::legacy) return hipSuccess;
     plan.legacy = true;
     plan.nt_hint = 0;
   }
-  return prep_v1_legacy(p, f, plan, out, st);
+  PCHK(prep_v1_legacy(p, f, plan, out, &r, st));
+  if (r == Built::retry) PCHK(prep_v1_legacy(p, f, plan, out, &r, st));
+  return hipSuccess;
 }
-
 
 // ---- K-generic pair plan ---------------------------------------------------------------------------------------------
-void pairplan_free(PairPlan& plan) {
-  if (plan.blk_key) (void)hipFree(plan.blk_key);
-  if (plan.sf_pidx) (void)hipFree(plan.sf_pidx);
-  if (plan.sf_perm) (void)hipFree(plan.sf_perm);
-  plan = PairPlan();
-}
-
+// (no default: prep_pairs, the only user, returns early for K outside 1..8)
 #define SLM_PREP_K_DISPATCH(K, CALL)                                   \
   switch (K) {                                                         \
     case 1: { constexpr int KK = 1; CALL; break; }                     \
@@ -1467,84 +1470,55 @@ void pairplan_free(PairPlan& plan) {
     case 6: { constexpr int KK = 6; CALL; break; }                     \
     case 7: { constexpr int KK = 7; CALL; break; }                     \
     case 8: { constexpr int KK = 8; CALL; break; }                     \
-    default: break;                                                    \
   }
 
 hipError_t prep_pairs(PrepBuffers* p, const slm_frame& f, PairPlan& plan, PairSizes* out, hipStream_t st) {
   *out = PairSizes();
   if (f.N <= 0 || f.K < 1 || f.K > 8 || f.J >= 65536) return hipSuccess;
-  const size_t NP = (size_t)f.K * (f.K + 1) / 2, n = (size_t)f.N * NP;
-  if (n > p->cap_g) {
-    size_t c;
-    c = p->cap_g; PCHK(grow_raw(p->gk, c, n));
-    c = p->cap_g; PCHK(grow_raw(p->gsk, c, n));
-    p->cap_g = c;
-  }
+  const size_t N = (size_t)f.N, NP = (size_t)f.K * (f.K + 1) / 2, n = N * NP;
+  PCHK(GROW(p, kPrepArrays, cap_g, n));
   if (!p->gcnt) PCHK(hipMalloc((void**)&p->gcnt, sizeof(unsigned)));
   // key bits: a*J + b < J*J
   int bits = 1;
   while (bits < 32 && (1ull << bits) < (unsigned long long)f.J * (unsigned long long)f.J) ++bits;
-  const size_t N = (size_t)f.N;
-  if (N > p->cap_n) {   // (the phase-A buffers of the tuple-sorted preparation: order keys / surfel ids, unsorted and sorted)
-    size_t c;
-    c = p->cap_n; PCHK(grow_raw(p->keys, c, N));
-    c = p->cap_n; PCHK(grow_raw(p->skeys, c, N));
-    c = p->cap_n; PCHK(grow_raw(p->tkeys, c, N));
-    c = p->cap_n; PCHK(grow_raw(p->ids, c, N));
-    c = p->cap_n; PCHK(grow_raw(p->sids, c, N));
-    c = p->cap_n; PCHK(grow_raw(p->tcount, c, N));
-    p->cap_n = c;
-  }
-  if (p->q_g != n || p->q_gN != N || !p->gtmp) {
-    size_t b1 = 0, b2 = 0, b3 = 0;
-    PCHK(rocprim::radix_sort_keys(nullptr, b1, p->gk, p->gsk, n, 0, 32, st));
-    PCHK(rocprim::unique(nullptr, b2, p->gsk, p->gk, p->gcnt, n, rocprim::equal_to<unsigned>(), st));
-    PCHK(rocprim::radix_sort_pairs(nullptr, b3, p->keys, p->skeys, p->ids, p->sids, N, 0, 64, st));
-    b1 = b1 > b3 ? b1 : b3;
-    size_t need = (b1 > b2 ? b1 : b2), cap = p->cap_gtmp;
-    need += need / 4 + (1u << 16);
-    char* q = (char*)p->gtmp;
-    PCHK(grow_raw(q, cap, need));
-    p->gtmp = q;
-    p->cap_gtmp = cap;
-    p->q_g = n;
-    p->q_gN = N;
-  }
-  PCHK(hipMemsetAsync(p->scal, 0, 16 * sizeof(int), st));
+  PCHK(GROW(p, kPrepArrays, cap_n, N));   // (the phase-A buffers of the tuple-sorted preparation: order keys / surfel ids, unsorted and sorted)
+  PCHK(ensure_scratch(p, p->gtmp, n, N, 0, 1u << 16, [&](size_t& need) {
+    size_t b[3] = {};
+    PCHK(rocprim::radix_sort_keys(nullptr, b[0], p->gk, p->gsk, n, 0, 32, st));
+    PCHK(rocprim::unique(nullptr, b[1], p->gsk, p->gk, p->gcnt, n, rocprim::equal_to<unsigned>(), st));
+    PCHK(rocprim::radix_sort_pairs(nullptr, b[2], p->keys, p->skeys, p->ids, p->sids, N, 0, 64, st));
+    need = *std::max_element(b, b + 3);
+    return hipSuccess;
+  }));
+  PCHK(hipMemsetAsync(p->scal, 0, SC_COUNT * sizeof(int), st));
   const dim3 blk(256);
   SLM_PREP_K_DISPATCH(f.K, hipLaunchKernelGGL(k_pair_keys<KK>, dim3((unsigned)((f.N + 255) / 256)), blk, 0, st, f.N, f.J, f.sf_knn_idx,
-                                              p->gk, p->scal + 13));
-  size_t b1 = p->cap_gtmp, b2 = p->cap_gtmp;
-  PCHK(rocprim::radix_sort_keys(p->gtmp, b1, p->gk, p->gsk, n, 0, bits, st));
-  PCHK(rocprim::unique(p->gtmp, b2, p->gsk, p->gk, p->gcnt, n, rocprim::equal_to<unsigned>(), st));
+                                              p->gk, p->scal + SC_BAD_KNN));
+  size_t b1 = p->gtmp.cap, b2 = p->gtmp.cap;
+  PCHK(rocprim::radix_sort_keys(p->gtmp.buf, b1, p->gk, p->gsk, n, 0, bits, st));
+  PCHK(rocprim::unique(p->gtmp.buf, b2, p->gsk, p->gk, p->gcnt, n, rocprim::equal_to<unsigned>(), st));
   hipLaunchKernelGGL(k_pair_count, dim3(1), dim3(1), 0, st, p->scal, p->gcnt);
   // the hashes the cached symbolic plan is compared with (same function as the tuple-sorted preparation's)
   hipLaunchKernelGGL(k_plan_hash, dim3(16), blk, 0, st, f.J, f.K_ED, f.ed_knn_idx, reinterpret_cast<const int32_t*>(p->gk), p->scal,
-                     reinterpret_cast<unsigned long long*>(p->scal + 8));
-  PCHK(hipMemcpyAsync(p->scal_host, p->scal, 16 * sizeof(int), hipMemcpyDeviceToHost, st));
-  PCHK(hipStreamSynchronize(st));
-  out->bad_knn = p->scal_host[13] != 0;
-  if (out->bad_knn) return hipSuccess;
-  out->n_blocks = p->scal_host[3];
-  memcpy(&out->knn_hash, p->scal_host + 8, 8);
-  memcpy(&out->graph_hash, p->scal_host + 10, 8);
-  if (out->n_blocks <= 0) return hipSuccess;
-  PCHK(grow_raw(plan.blk_key, plan.cap_key, (size_t)out->n_blocks));
-  PCHK(grow_raw(plan.sf_pidx, plan.cap_pidx, n));
-  PCHK(grow_raw(plan.sf_perm, plan.cap_perm, N));
+                     reinterpret_cast<unsigned long long*>(p->scal + SC_KNN_HASH));
+  PCHK(read_scal(p, SC_COUNT, st));
+  if (read_built(p->scal_host, ST_OK, out) != Built::done || out->n_blocks <= 0) return hipSuccess;
+  PCHK(GROW(&plan, kPairPlanArrays, cap_key, (size_t)out->n_blocks));
+  PCHK(GROW(&plan, kPairPlanArrays, cap_pidx, n));
+  PCHK(GROW(&plan, kPairPlanArrays, cap_perm, N));
   PCHK(hipMemcpyAsync(plan.blk_key, p->gk, sizeof(unsigned) * (size_t)out->n_blocks, hipMemcpyDeviceToDevice, st));
   SLM_PREP_K_DISPATCH(f.K, hipLaunchKernelGGL(k_pair_index<KK>, dim3((unsigned)((N + 255) / 256)), blk, 0, st, f.N, f.J, out->n_blocks,
                                               f.sf_knn_idx, reinterpret_cast<const unsigned*>(plan.blk_key), plan.sf_pidx,
                                               p->keys, p->tkeys, p->ids));
-  size_t b3 = p->cap_gtmp;
+  size_t b3 = p->gtmp.cap;
   if (f.K <= 4) {
-    PCHK(rocprim::radix_sort_pairs(p->gtmp, b3, p->keys, p->skeys, p->ids, plan.sf_perm, N, 0, 64, st));
+    PCHK(rocprim::radix_sort_pairs(p->gtmp.buf, b3, p->keys, p->skeys, p->ids, plan.sf_perm, N, 0, 64, st));
   } else {
     // lexicographic order of the full canonical tuple: stable sorts, least significant key (ids 4..7) first
-    PCHK(rocprim::radix_sort_pairs(p->gtmp, b3, p->tkeys, p->skeys, p->ids, p->sids, N, 0, 64, st));
+    PCHK(rocprim::radix_sort_pairs(p->gtmp.buf, b3, p->tkeys, p->skeys, p->ids, p->sids, N, 0, 64, st));
     hipLaunchKernelGGL(k_gather_keys, dim3((unsigned)((N + 255) / 256)), blk, 0, st, f.N, p->keys, p->sids, p->tkeys);
-    b3 = p->cap_gtmp;
-    PCHK(rocprim::radix_sort_pairs(p->gtmp, b3, p->tkeys, p->skeys, p->sids, plan.sf_perm, N, 0, 64, st));
+    b3 = p->gtmp.cap;
+    PCHK(rocprim::radix_sort_pairs(p->gtmp.buf, b3, p->tkeys, p->skeys, p->sids, plan.sf_perm, N, 0, 64, st));
   }
   return hipGetLastError();
 }

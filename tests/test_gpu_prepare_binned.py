@@ -25,6 +25,15 @@ from super_amd.engine import DeviceFrame, Engine
 dev = torch.device("cuda", 0)
 cases = json.loads(sys.argv[2])
 out = {}
+def read_plan(eng):
+    digest = {}
+    for what in range(13):
+        n = C.c_int64(0)
+        _lib.check(eng.lib.slm_debug_read_plan(eng.h, 0, what, None, 0, C.byref(n), eng.stream), "size")
+        buf = (C.c_char * max(n.value, 1))()
+        _lib.check(eng.lib.slm_debug_read_plan(eng.h, 0, what, buf, n.value, C.byref(n), eng.stream), "read")
+        digest[str(what)] = [n.value, hashlib.sha256(bytes(buf[:n.value])).hexdigest()]
+    return digest
 for name, kw in cases.items():
     sc = synth.make_scene(**kw)
     for f64 in (False, True):
@@ -33,19 +42,24 @@ for name, kw in cases.items():
         eng.bind(0, fr)
         eng.bind(0, fr)                      # the second bind takes the hinted path
         info = eng.plan_info(0)
-        digest = {}
-        for what in range(13):
-            n = C.c_int64(0)
-            _lib.check(eng.lib.slm_debug_read_plan(eng.h, 0, what, None, 0, C.byref(n), eng.stream), "size")
-            buf = (C.c_char * max(n.value, 1))()
-            _lib.check(eng.lib.slm_debug_read_plan(eng.h, 0, what, buf, n.value, C.byref(n), eng.stream), "read")
-            digest[str(what)] = [n.value, hashlib.sha256(bytes(buf[:n.value])).hexdigest()]
+        digest = read_plan(eng)
         eng.run(1)
         beta = eng.beta(0).cpu().numpy()
         out[f"{name}/{'f64' if f64 else 'f32'}"] = {"info": {k: v for k, v in info.items() if k != "solver"}, "plan": digest,
                                                     "beta_sha": hashlib.sha256(beta.tobytes()).hexdigest(),
                                                     "loss": [r["loss"] for r in eng.records(0)]}
         eng.close()
+# the hint that does not hold: a scene with more than 9/8 of the tuples of the slot's last frame, plus 64 -- the hinted
+# build is thrown away and the plan built again from the exact sizes
+for f64 in (False, True):
+    eng = Engine(dev, data_path=0, num_iterations=3)
+    eng.bind(0, DeviceFrame.from_scene(synth.make_scene(**cases["tiny"]), dev, state_f64=f64))
+    t0 = int(eng.plan_info(0)["tuples"])
+    eng.bind(0, DeviceFrame.from_scene(synth.make_scene(**cases["small"]), dev, state_f64=f64))
+    info = eng.plan_info(0)
+    assert info["tuples"] > t0 + t0 // 8 + 64, (t0, info["tuples"])
+    out[f"small-after-tiny/{'f64' if f64 else 'f32'}"] = {"info": {k: v for k, v in info.items() if k != "solver"}, "plan": read_plan(eng)}
+    eng.close()
 print("RESULT " + json.dumps(out))
 '''
 
@@ -75,6 +89,10 @@ def test_binned_preparation_gives_the_rocprim_plan_array_for_array():
         for what, (n_bytes, sha) in new[key]["plan"].items():
             assert [n_bytes, sha] == old[key]["plan"][what], (key, "plan array", what, n_bytes, old[key]["plan"][what][0])
         assert new[key]["info"]["tuples"] > 0 and new[key]["info"]["merged_records"] > 0
+    for prec in ("f32", "f64"):   # ... and the plan after a hint that did not hold is the plan of a fresh slot
+        for res in (new, old):
+            assert res["small-after-tiny/" + prec]["plan"] == res["small/" + prec]["plan"], prec
+            assert res["small-after-tiny/" + prec]["info"] == res["small/" + prec]["info"], prec
 
 
 def test_a_bin_that_does_not_fit_falls_back_to_the_rocprim_pipeline():
