@@ -48,6 +48,39 @@ def hit_sets(points, K, H, W, rad, view_scale=1.0, n_track=rm.N_TRACK):
     return pix[keep], ids[keep], rank[keep]
 
 
+def hit_sets_fast(points, K, H, W, rad, view_scale=1.0, n_track=rm.N_TRACK, max_candidates=8_000_000):
+    """``hit_sets`` without the Python loop over the surfels, for scenes of the driver's size: the candidate pixels of
+    a run of surfels (``max_candidates`` at most) are enumerated at once (row-major inside each surfel's range, as the loop does) and pass through
+    the same ``rm._range`` / ``rm.rho`` expressions, so every rho is the same float64.  ``hit_sets`` stays the
+    definition; test_render_loss_cases.py holds this form identical to it, array by array."""
+    P = np.asarray(points, np.float64).astype(np.float32).astype(np.float64)
+    w, h, f, ccx, ccy = rm.camera(K, H, W, view_scale)
+    live = np.nonzero((P[:, 2] >= rm.Z_NEAR) & (P[:, 2] <= rm.Z_FAR))[0] if len(P) else np.zeros(0, np.int64)
+    X0, X1 = rm._range(P[live, 0], P[live, 2], rad, f, ccx, w, 0.5)
+    Y0, Y1 = rm._range(P[live, 1], P[live, 2], rad, f, ccy, h, 0.5)
+    NX, NY = np.maximum(X1 - X0 + 1, 0), np.maximum(Y1 - Y0 + 1, 0)
+    chunk = np.cumsum(NX * NY) // max_candidates          # surfels whose candidates fit one pass together
+    pix_l, id_l = [np.zeros(0, np.int64)], [np.zeros(0, np.int64)]
+    for c in np.unique(chunk):
+        s = chunk == c
+        ids, x0, y0, nx, cnt = live[s], X0[s], Y0[s], NX[s], (NX * NY)[s]
+        sid = np.repeat(np.arange(len(ids)), cnt)
+        k = np.arange(cnt.sum()) - np.repeat(np.cumsum(cnt) - cnt, cnt)
+        ii, jj = y0[sid] + k // nx[sid], x0[sid] + k % nx[sid]
+        hit = rm.rho(P[ids[sid]], ii, jj, f, ccx, ccy) < rad
+        pix_l.append(ii[hit] * w + jj[hit])
+        id_l.append(ids[sid[hit]])
+    pix, ids = np.concatenate(pix_l), np.concatenate(id_l)
+    if not len(pix):
+        return pix, pix.copy(), pix.copy()
+    o = np.lexsort((ids, P[ids, 2], pix))
+    pix, ids = pix[o], ids[o]
+    first = np.r_[0, np.nonzero(np.diff(pix))[0] + 1]
+    rank = np.arange(len(pix)) - np.repeat(first, np.diff(np.r_[first, len(pix)]))
+    keep = rank < n_track
+    return pix[keep], ids[keep], rank[keep]
+
+
 def blend(points, colors, hits, K, H, W, rad, view_scale=1.0, bg=(0.0, 0.0, 0.0), round32=True):
     """The (h,w,3) float64 image as a torch function of ``points`` (N,3) for the fixed ``hits`` of ``hit_sets``:
     w_k = (1 - rho_k/rad) exp((zt_k - zt_max)/gamma), colour = (sum w_k c_k + w_bg bg) / (sum w_k + w_bg).

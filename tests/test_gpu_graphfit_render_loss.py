@@ -70,9 +70,10 @@ def _gpu_frame(sc, stable, cols, tgt):
     return sf, inputs, new_data, SimpleNamespace(optical_flow=optical_flow, calls=calls)
 
 
-def _render_loss(sc, stable, cols, tgt, P, weight):
+def _render_loss(sc, stable, cols, tgt, P, weight, rad=RAD, hit_sets=rgm.hit_sets):
     import torch
-    img = rgm.render(P, cols[stable], sc.K, sc.H, sc.W, RAD)
+    hits = hit_sets(P.detach().numpy(), sc.K, sc.H, sc.W, rad)
+    img = rgm.blend(P, cols[stable], hits, sc.K, sc.H, sc.W, rad)        # rgm.render, with the hit sets' form chosen
     img32 = img + (img.detach().float().double() - img.detach())
     loss, kept, _, _ = rgm.ssim_loss(img32, torch.from_numpy(tgt).double(), weight)
     return loss, kept, img.detach()
