@@ -13,78 +13,16 @@
 #include <cstring>
 
 #include "slm_common.h"
+#include "slm_host.h"
+#include "slm_launch.h"
 #include "slm_prep.h"
 
-// launchers defined next to their kernels
-void launch_data_grad(const FrameDev*, int, int, int, double, hipStream_t);
-void launch_data_grad_pairs(const FrameDev*, int, int, int, double, hipStream_t);
-void launch_data_loss(const FrameDev*, int, int, int, double, int, hipStream_t);
-void launch_data_resid(const FrameDev*, int, int, int, double, double*, uint8_t*, int32_t*, hipStream_t);
-void launch_data_gram(const FrameDev*, int, int, double, int, hipStream_t, const int* reuse = nullptr);
-void launch_begin_and_gram(const FrameDev*, int, int, double, hipStream_t, const int* reuse, int dag_cut);
-void launch_data_eval(const FrameDev*, int, int, double, int mode, hipStream_t, const int* reuse = nullptr);
-void launch_band_assemble(const FrameDev*, int, int, hipStream_t);
-void launch_reg_grad(const FrameDev*, int, int, int, double, int, double, hipStream_t);
-void launch_front_assemble(const FrameDev*, int, int, hipStream_t);
-void launch_pair_reduce(const FrameDev*, int, int, hipStream_t);
-void launch_pair_scatter(const FrameDev*, int, int, hipStream_t);
-void launch_reg_grad_nd(const FrameDev*, int, int, int, double, int, double, hipStream_t);
-void launch_front_load_rhs(const FrameDev*, int, int, hipStream_t);
-void launch_iter_begin_nd(const FrameDev*, int, hipStream_t, const int* reuse, int dag_cut);
-void launch_front_solve(const FrameDev*, int, const NDLevelSched*, int, double, hipStream_t);
-int launch_front_solve_dag(const FrameDev*, int, int, double, hipStream_t, int cut, bool reset, bool check);
-int dag_device_setup(int dev, int* xcd8_out);
-int dag_last_mode();
-void launch_after_solve(const FrameDev*, int, int, int, int, double, int, double, int, hipStream_t);
-hipError_t set_dag_timeout_ticks(long long);
-void launch_dag_abort_check(const FrameDev*, int, hipStream_t);
-void launch_front_levels(const FrameDev*, int, const NDLevelSched*, int, int, int, double, hipStream_t);
-void launch_reg_loss(const FrameDev*, int, int, int, double, int, double, int, hipStream_t);
-void launch_bandwidth(const slm_frame&, int*, hipStream_t);
-void launch_band_solve(const FrameDev*, int, int, int, double, hipStream_t);
-void launch_band_to_dense(const FrameDev*, int, double*, hipStream_t);
-void launch_dense_to_band(const FrameDev*, const double*, const double*, hipStream_t);
-void launch_init_slot(const FrameDev*, int, int, const slm_config&, hipStream_t);
-void launch_iter_begin(const FrameDev*, int, hipStream_t);
-void launch_pack_nodes(const FrameDev*, int, int, hipStream_t);
-void launch_make_trial(const FrameDev*, int, int, hipStream_t);
-void launch_pack_target(int, const float*, const float*, float4*, hipStream_t);
-void launch_pack_target_px(int, const int*, const uint8_t*, const float*, const float*, float4*, hipStream_t);
-void launch_accept(const FrameDev*, int, int, int, int, hipStream_t, int* reuse = nullptr, int eval_pass = 0);
-void launch_loss_out(const FrameDev*, int, int, double*, hipStream_t);
-void launch_zero_reg_part(const FrameDev*, int, int, hipStream_t);
-void launch_update(int, int, int, float*, float*, const int*, const float*, float*, float*, const double*,
-                   hipStream_t);
-void launch_update64(int, int, int, double*, double*, const int*, const double*, double*, double*, const double*,
-                     hipStream_t);
-void launch_knn(int, int, int, int, const float*, const float*, int*, float*, hipStream_t);
-void launch_knn64(int, int, int, int, const double*, const double*, const int*, const int*, int*, double*, int*,
-                  hipStream_t);
-void launch_knn_weights64(int, int, int, const int*, const double*, const double*, int, const double*, const double*,
-                          double*, uint8_t*, hipStream_t);
-void launch_knn_weights(int, int, int, const int*, const float*, const float*, float*, uint8_t*,
-                        hipStream_t);
-
-static thread_local std::string g_err;
-
-#define HIPCHK(expr)                                                                      \
-  do {                                                                                    \
-    hipError_t e_ = (expr);                                                               \
-    if (e_ != hipSuccess) {                                                               \
-      g_err = std::string(#expr) + ": " + hipGetErrorString(e_);                          \
-      return SLM_ERR_HIP;                                                                 \
-    }                                                                                     \
-  } while (0)
-
-static int fail(int code, const char* msg) {
-  g_err = msg;
-  return code;
-}
+static thread_local std::string g_err;   // what slm_last_error() returns
 // what the reference could never have been given (its KNN ids come from a top-k: distinct and inside [0, J))
 static const char* const kBadKnn =
     "slm_bind_frame: a KNN index (sf_knn_idx or ed_knn_idx) lies outside [0, J) or a surfel's row of sf_knn_idx repeats an id";
 
-// other translation units (slm_gf.hip) report through the same slm_last_error()
+// every translation unit reports through it (slm_host.h: fail, HIPCHK)
 void slm_set_error_text(const char* msg) { g_err = msg; }
 
 namespace {
@@ -370,20 +308,14 @@ bool solve_is_task_graph(const slm_solver* s, int n, int J);   // (below: which 
 // diagnostics (slm_debug_counters): device reallocations and symbolic analyses since the library was loaded
 static std::atomic<long long> g_reallocs{0}, g_realloc_bytes{0}, g_plan_builds{0}, g_plan_reuses{0}, g_plan_fill_hits{0};   // (binds may run on worker threads)
 
+// The solver's form of slm_host.h's grow: 12 % of head-room, and every growth counts into slm_debug_counters.
 template <typename T>
 static hipError_t grow(T*& p, size_t& cap, size_t need) {
   if (need <= cap) return hipSuccess;
+  const size_t want = need + need / 8;
   ++g_reallocs;
-  g_realloc_bytes += (long long)((need + need / 8) * sizeof(T));
-  if (p) {
-    hipError_t e = hipFree(p);
-    if (e != hipSuccess) return e;
-    p = nullptr;
-  }
-  size_t want = need + need / 8;
-  hipError_t e = hipMalloc((void**)&p, want * sizeof(T));
-  if (e == hipSuccess) cap = want;
-  return e;
+  g_realloc_bytes += (long long)(want * sizeof(T));
+  return grow(p, cap, need, want);
 }
 template <typename T>
 static hipError_t grow(GP<T>& p, size_t& cap, size_t need) {   // (a descriptor field, slm_common.h GP)
@@ -394,7 +326,6 @@ static hipError_t grow(GP<T>& p, size_t& cap, size_t need) {   // (a descriptor 
 }
 
 static int check_slots(slm_solver* s, int first, int n);
-static int check_slots_fwd(slm_solver* s, int first, int n) { return check_slots(s, first, n); }
 
 extern "C" {
 
@@ -419,7 +350,7 @@ int slm_debug_dag_timeout(int64_t ticks) {
 }
 
 int slm_debug_dag_abort(slm_solver* s, int32_t n_frames, void* stream) {
-  int rc = check_slots_fwd(s, 0, n_frames);
+  int rc = check_slots(s, 0, n_frames);
   if (rc) return rc;
   for (int i = 0; i < n_frames; ++i)
     if (!s->slots[i].h.nd_ready) return fail(SLM_ERR_UNSUPPORTED, "slm_debug_dag_abort: every slot needs a nested-dissection plan");
@@ -471,7 +402,7 @@ int slm_debug_read(slm_solver* s, int32_t slot, int32_t what, double* host_out, 
 
 int slm_debug_read_plan(slm_solver* s, int32_t slot, int32_t what, void* host_out, int64_t max_bytes, int64_t* n_bytes, void* stream) {
   if (!s || slot < 0 || slot >= (int)s->slots.size() || !n_bytes) return fail(SLM_ERR_INVALID, "slm_debug_read_plan: bad argument");
-  int rc = check_slots_fwd(s, slot, 1);
+  int rc = check_slots(s, slot, 1);
   if (rc) return rc;
   const Slot& sl = s->slots[slot];
   const FrameDev& h = sl.h;

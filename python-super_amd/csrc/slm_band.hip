@@ -14,6 +14,7 @@
 // Back substitution k_backsub(c), c = nt-1..0: x_c = L_cc^-T y_c, y_(c-d) -= L(c,c-d)^T x_c.
 // A non-positive pivot sets st->chol_fail (reference: RuntimeError -> "Solver failed").
 #include "slm_tile.h"
+#include "slm_launch.h"
 
 // ---------------------------------------------------------------------------------
 // Tile half-bandwidth from the KNN tables: max over coupled node pairs (a >= b) of

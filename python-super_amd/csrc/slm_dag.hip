@@ -49,6 +49,7 @@
 
 #include "slm_tile.h"
 #include "slm_lane.h"
+#include "slm_launch.h"
 
 namespace {
 

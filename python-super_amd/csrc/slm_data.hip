@@ -4,6 +4,8 @@
 //   k_data_loss   : sum r^2 at beta (+ delta), fresh match set     (loss.py:222-255,290)
 //   k_data_resid  : per-surfel r / match / taps for parity tests
 #include "slm_data.h"
+#include "slm_host.h"
+#include "slm_launch.h"
 
 // grid = (ceil(maxN/256), n_frames); KK = opt.num_neighbors of every slot of the launch (a slot with another K is skipped:
 // the launcher only sees the batch's common value)
@@ -223,20 +225,7 @@ __global__ void __launch_bounds__(256) k_zero_pairbuf(const FrameDev* __restrict
 }
 
 // ---- host launchers (called from slm_api.hip) ------------------------------------
-// K = the batch's num_neighbors (1..SLM_KMAX): one instantiation per value
-#define SLM_K_DISPATCH(K, CALL)                                        \
-  switch (K) {                                                         \
-    case 1: { constexpr int KK = 1; CALL; break; }                     \
-    case 2: { constexpr int KK = 2; CALL; break; }                     \
-    case 3: { constexpr int KK = 3; CALL; break; }                     \
-    case 4: { constexpr int KK = 4; CALL; break; }                     \
-    case 5: { constexpr int KK = 5; CALL; break; }                     \
-    case 6: { constexpr int KK = 6; CALL; break; }                     \
-    case 7: { constexpr int KK = 7; CALL; break; }                     \
-    case 8: { constexpr int KK = 8; CALL; break; }                     \
-    default: break;                                                    \
-  }
-
+// K = the batch's num_neighbors (1..SLM_KMAX): one instantiation per value (SLM_K_DISPATCH, slm_host.h)
 void launch_data_grad(const FrameDev* frames_dev, int n_frames, int maxN, int K, double lam, hipStream_t st) {
   if (maxN <= 0) return;
   dim3 grid((maxN + 255) / 256, n_frames);

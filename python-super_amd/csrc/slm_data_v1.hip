@@ -22,6 +22,7 @@
 
 #include "slm_data.h"
 #include "slm_begin.h"
+#include "slm_launch.h"
 
 #define ROW_STRIDE 17   // doubles per surfel half-row in LDS (odd: conflict-free 64-bit writes)
 

@@ -15,11 +15,8 @@
 #include <cstring>
 #include <rocprim/rocprim.hpp>
 
-#include <string>
-
+#include "slm_host.h"
 #include "slm_sem.h"
-
-void slm_set_error_text(const char* msg);   // slm_api.hip
 
 struct slm_depth {
   int H = 0, W = 0;
@@ -36,20 +33,6 @@ struct slm_depth {
 };
 
 namespace {
-
-#define DCHK(expr)                                                        \
-  do {                                                                    \
-    hipError_t e_ = (expr);                                               \
-    if (e_ != hipSuccess) {                                               \
-      slm_set_error_text((std::string(#expr) + ": " + hipGetErrorString(e_)).c_str()); \
-      return SLM_ERR_HIP;                                                 \
-    }                                                                     \
-  } while (0)
-
-int dfail(int code, const char* msg) {
-  slm_set_error_text(msg);
-  return code;
-}
 
 // superv1 base map: ~valid_mask | (seg in del classes)
 __global__ void __launch_bounds__(256) k_dp_base(slm_depth_config c, slm_depth_inputs in, uint8_t* __restrict__ m) {
@@ -370,36 +353,28 @@ __global__ void __launch_bounds__(256) k_dp_dist2edge(slm_depth_config c, int T,
   out[t] = best;
 }
 
-template <typename T>
-hipError_t dgrow(T*& p, size_t n) {
-  if (p) return hipSuccess;
-  return hipMalloc((void**)&p, n * sizeof(T));
-}
+// the device arrays of a context; the one size of slm_depth_create: [0] pixels, [1] 1
+#define A(name, mult, unit) DEV_MEMBER(slm_depth, name, mult, unit)
+constexpr DevMember kDepthArrays[] = {A(m0, 1, 0), A(m1, 1, 0), A(pcd, 3, 0), A(nrm, 3, 0), A(flag, 1, 0), A(idx, 1, 0),
+                                      A(total, 2, 1), A(warp, 3, 0), A(ssim, 1, 0), DEV_GROWN(slm_depth, tmp)};
+#undef A
 
 }  // namespace
 
 extern "C" {
 
 int slm_depth_create(int32_t H, int32_t W, slm_depth** out) {
-  if (!out || H < 8 || W < 8) return dfail(SLM_ERR_INVALID, "slm_depth_create: bad argument");
-  if (slm_device_count() < 1) return dfail(SLM_ERR_NO_DEVICE, "slm_depth_create: no HIP device visible");
+  if (!out || H < 8 || W < 8) return fail(SLM_ERR_INVALID, "slm_depth_create: bad argument");
+  if (slm_device_count() < 1) return fail(SLM_ERR_NO_DEVICE, "slm_depth_create: no HIP device visible");
   slm_depth* d = new slm_depth();
   d->H = H;
   d->W = W;
   const size_t n = (size_t)H * W;
-  hipError_t e = dgrow(d->m0, n);
-  if (e == hipSuccess) e = dgrow(d->m1, n);
-  if (e == hipSuccess) e = dgrow(d->pcd, 3 * n);
-  if (e == hipSuccess) e = dgrow(d->nrm, 3 * n);
-  if (e == hipSuccess) e = dgrow(d->flag, n);
-  if (e == hipSuccess) e = dgrow(d->idx, n);
-  if (e == hipSuccess) e = dgrow(d->total, 2);
-  if (e == hipSuccess) e = dgrow(d->warp, 3 * n);
-  if (e == hipSuccess) e = dgrow(d->ssim, n);
+  const size_t units[] = {n, 1};
+  const hipError_t e = alloc_members(d, kDepthArrays, units);
   if (e != hipSuccess) {
-    slm_set_error_text((std::string("slm_depth_create: ") + hipGetErrorString(e)).c_str());
     slm_depth_destroy(d);
-    return SLM_ERR_HIP;
+    return fail(SLM_ERR_HIP, std::string("slm_depth_create: ") + hipGetErrorString(e));
   }
   *out = d;
   return SLM_OK;
@@ -407,9 +382,7 @@ int slm_depth_create(int32_t H, int32_t W, slm_depth** out) {
 
 int slm_depth_destroy(slm_depth* d) {
   if (!d) return SLM_OK;
-  void* ptrs[] = {d->m0, d->m1, d->pcd, d->nrm, d->flag, d->idx, d->total, d->tmp, d->warp, d->ssim};
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
+  free_members(d, kDepthArrays);
   sem_free(d->sem);
   delete d;
   return SLM_OK;
@@ -417,13 +390,13 @@ int slm_depth_destroy(slm_depth* d) {
 
 int slm_depth_preprocess(slm_depth* d, const slm_depth_config* cfg, const slm_depth_inputs* in,
                          const slm_depth_outputs* out, int32_t* n_valid_host, void* stream) {
-  if (!d || !cfg || !in || !out) return dfail(SLM_ERR_INVALID, "slm_depth_preprocess: null argument");
-  if (cfg->H != d->H || cfg->W != d->W) return dfail(SLM_ERR_INVALID, "slm_depth_preprocess: image size differs from slm_depth_create");
-  if (!in->depth || !in->color) return dfail(SLM_ERR_INVALID, "slm_depth_preprocess: null device pointer");
+  if (!d || !cfg || !in || !out) return fail(SLM_ERR_INVALID, "slm_depth_preprocess: null argument");
+  if (cfg->H != d->H || cfg->W != d->W) return fail(SLM_ERR_INVALID, "slm_depth_preprocess: image size differs from slm_depth_create");
+  if (!in->depth || !in->color) return fail(SLM_ERR_INVALID, "slm_depth_preprocess: null device pointer");
   if (cfg->n_del_classes < 0 || cfg->n_del_classes > 3 || (cfg->n_del_classes > 0 && !in->seg))
-    return dfail(SLM_ERR_INVALID, "slm_depth_preprocess: del_seg_classes needs the segmentation image");
+    return fail(SLM_ERR_INVALID, "slm_depth_preprocess: del_seg_classes needs the segmentation image");
   if (in->seg && (cfg->num_classes < 1 || cfg->num_classes > SLM_MAX_CLASSES))
-    return dfail(SLM_ERR_UNSUPPORTED, "slm_depth_preprocess: num_classes must be 1..4");
+    return fail(SLM_ERR_UNSUPPORTED, "slm_depth_preprocess: num_classes must be 1..4");
   hipStream_t st = (hipStream_t)stream;
   const int H = d->H, W = d->W, HW = H * W;
   const dim3 grid((HW + 255) / 256), blk(256);
@@ -433,7 +406,7 @@ int slm_depth_preprocess(slm_depth* d, const slm_depth_config* cfg, const slm_de
     hipLaunchKernelGGL(k_dp_warp, grid, blk, 0, st, *cfg, *in, d->warp);
     hipLaunchKernelGGL(k_dp_ssim, grid, blk, 0, st, H, W, d->warp, in->color, d->ssim);
     ssim = d->ssim;
-    if (out->disp_conf) DCHK(hipMemcpyAsync(out->disp_conf, d->ssim, sizeof(float) * (size_t)HW, hipMemcpyDeviceToDevice, st));
+    if (out->disp_conf) HIPCHK(hipMemcpyAsync(out->disp_conf, d->ssim, sizeof(float) * (size_t)HW, hipMemcpyDeviceToDevice, st));
   }
   // 1. invalid map
   int have_base = 0;
@@ -454,25 +427,18 @@ int slm_depth_preprocess(slm_depth* d, const slm_depth_config* cfg, const slm_de
     }
   }
   hipLaunchKernelGGL(k_dp_points, grid, blk, 0, st, *cfg, *in, m, have_base, d->pcd);
-  if (out->inval) DCHK(hipMemcpyAsync(out->inval, m, (size_t)HW, hipMemcpyDeviceToDevice, st));
+  if (out->inval) HIPCHK(hipMemcpyAsync(out->inval, m, (size_t)HW, hipMemcpyDeviceToDevice, st));
   // 2. normals + valid flags
   hipLaunchKernelGGL(k_dp_normals, grid, blk, 0, st, H, W, cfg->normal_model, d->pcd, in->color, d->nrm, d->flag);
   // 3. index_map = exclusive scan of the flags; total = last index + last flag
-  size_t bytes = 0;
-  DCHK(rocprim::exclusive_scan(nullptr, bytes, d->flag, d->idx, 0, (size_t)HW, rocprim::plus<int32_t>(), st));
-  if (bytes > d->cap_tmp) {
-    if (d->tmp) DCHK(hipFree(d->tmp));
-    d->tmp = nullptr;
-    d->cap_tmp = 0;
-    DCHK(hipMalloc(&d->tmp, bytes));
-    d->cap_tmp = bytes;
-  }
-  DCHK(rocprim::exclusive_scan(d->tmp, bytes, d->flag, d->idx, 0, (size_t)HW, rocprim::plus<int32_t>(), st));
+  HIPCHK(with_scratch(d->tmp, d->cap_tmp, [&](void* tmp, size_t& bytes) {
+    return rocprim::exclusive_scan(tmp, bytes, d->flag, d->idx, 0, (size_t)HW, rocprim::plus<int32_t>(), st);
+  }));
   hipLaunchKernelGGL(k_dp_gather, grid, blk, 0, st, *cfg, *in, *out, ssim, d->pcd, d->nrm, d->flag, d->idx);
   int32_t last[2];
-  DCHK(hipMemcpyAsync(&last[0], d->idx + HW - 1, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  DCHK(hipMemcpyAsync(&last[1], d->flag + HW - 1, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  DCHK(hipStreamSynchronize(st));
+  HIPCHK(hipMemcpyAsync(&last[0], d->idx + HW - 1, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(&last[1], d->flag + HW - 1, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
   const int T = last[0] + last[1];
   if (n_valid_host) *n_valid_host = T;
   // 4. distance to the class boundaries
@@ -481,11 +447,11 @@ int slm_depth_preprocess(slm_depth* d, const slm_depth_config* cfg, const slm_de
     sem.num_classes = cfg->num_classes;
     sem.img_seg = in->seg;
     int32_t off[SLM_MAX_CLASSES + 1];
-    DCHK(sem_extract_edges(d->sem, sem, H, W, off, st));
+    HIPCHK(sem_extract_edges(d->sem, sem, H, W, off, st));
     hipLaunchKernelGGL(k_dp_dist2edge, dim3((T + 255) / 256), blk, 0, st, *cfg, T, out->points, out->seg,
                        d->sem.edge_xy, off[0], off[1], off[2], off[3], off[4], out->dist2edge);
   }
-  DCHK(hipGetLastError());
+  HIPCHK(hipGetLastError());
   return SLM_OK;
 }
 

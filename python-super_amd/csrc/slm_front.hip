@@ -15,6 +15,7 @@
 
 #include "slm_tile.h"
 #include "slm_begin.h"
+#include "slm_launch.h"
 
 __device__ __forceinline__ int nd_base(const NDFront& f, int p) {
   return p < f.nv ? 7 * p : f.n1p + 7 * (p - f.nv);

@@ -19,11 +19,8 @@
 #include <cstring>
 #include <rocprim/rocprim.hpp>
 
-#include <string>
-
 #include "slm_common.h"
-
-void slm_set_error_text(const char* msg);   // slm_api.hip
+#include "slm_host.h"
 
 #define FU_LAYERS 16
 
@@ -53,20 +50,6 @@ struct slm_fuse {
 };
 
 namespace {
-
-#define FCHK(expr)                                                        \
-  do {                                                                    \
-    hipError_t e_ = (expr);                                               \
-    if (e_ != hipSuccess) {                                               \
-      slm_set_error_text((std::string(#expr) + ": " + hipGetErrorString(e_)).c_str()); \
-      return SLM_ERR_HIP;                                                 \
-    }                                                                     \
-  } while (0)
-
-int ffail(int code, const char* msg) {
-  slm_set_error_text(msg);
-  return code;
-}
 
 __device__ __forceinline__ void fu_project(const slm_fuse_config& c, const double* p, double& u_, double& v_) {
   const double Z = p[2] + 1e-8;
@@ -626,38 +609,21 @@ __global__ void __launch_bounds__(256) k_fu_compact(slm_surfel_model m, slm_fuse
   }
 }
 
-#define FU_K_DISPATCH(K, ...)                                          \
-  switch (K) {                                                         \
-    case 1: { constexpr int KK = 1; __VA_ARGS__; break; }              \
-    case 2: { constexpr int KK = 2; __VA_ARGS__; break; }              \
-    case 3: { constexpr int KK = 3; __VA_ARGS__; break; }              \
-    case 4: { constexpr int KK = 4; __VA_ARGS__; break; }              \
-    case 5: { constexpr int KK = 5; __VA_ARGS__; break; }              \
-    case 6: { constexpr int KK = 6; __VA_ARGS__; break; }              \
-    case 7: { constexpr int KK = 7; __VA_ARGS__; break; }              \
-    case 8: { constexpr int KK = 8; __VA_ARGS__; break; }              \
-    default: break;                                                    \
-  }
 static inline size_t fu_Kh(const slm_surfel_model& m) { return (size_t)(m.K > 0 ? m.K : 4); }
 
-template <typename T>
-hipError_t falloc(T*& p, size_t n) {
-  return hipMalloc((void**)&p, n * sizeof(T));
-}
+// the device arrays of a context; sizes of slm_fuse_create: [0] surfel capacity, [1] pixels, [2] the larger of the two, [3] 1
+#define A(name, mult, unit) DEV_MEMBER(slm_fuse, name, mult, unit)
+constexpr DevMember kFuseArrays[] = {
+    A(keys, 1, 0), A(skeys, 1, 0), A(ids, 1, 0), A(sids, 1, 0), A(layers, FU_LAYERS, 1), A(flag, 1, 2), A(pos, 1, 2),
+    A(cand_idx, FU_KMAX, 1), A(cand_w, FU_KMAX, 1), A(dead, 1, 0), A(counters, 4, 3),
+    A(s_d3, 6, 0), A(s_d1, 1, 0), A(s_d4, FU_KMAX, 0), A(s_f3, 3, 0), A(s_f1, 2, 0), A(s_f2, 2, 0), A(s_i4, FU_KMAX, 0),
+    A(s_seg, 1, 0), A(s_sc, SLM_MAX_CLASSES, 0), A(s_d2e, 1, 0), DEV_GROWN(slm_fuse, boxes), DEV_GROWN(slm_fuse, tmp)};
+#undef A
 
 hipError_t scan_flags(slm_fuse* f, int n, hipStream_t st) {
-  size_t bytes = 0;
-  hipError_t e = rocprim::exclusive_scan(nullptr, bytes, f->flag, f->pos, 0, (size_t)n, rocprim::plus<int32_t>(), st);
-  if (e != hipSuccess) return e;
-  if (bytes > f->cap_tmp) {
-    if (f->tmp) (void)hipFree(f->tmp);
-    f->tmp = nullptr;
-    f->cap_tmp = 0;
-    e = hipMalloc(&f->tmp, bytes);
-    if (e != hipSuccess) return e;
-    f->cap_tmp = bytes;
-  }
-  return rocprim::exclusive_scan(f->tmp, bytes, f->flag, f->pos, 0, (size_t)n, rocprim::plus<int32_t>(), st);
+  return with_scratch(f->tmp, f->cap_tmp, [&](void* tmp, size_t& bytes) {
+    return rocprim::exclusive_scan(tmp, bytes, f->flag, f->pos, 0, (size_t)n, rocprim::plus<int32_t>(), st);
+  });
 }
 
 __global__ void k_fu_total(const int32_t* __restrict__ pos, const int32_t* __restrict__ flag, int n, int32_t* __restrict__ counters) {
@@ -680,39 +646,19 @@ hipError_t count_flags(slm_fuse* f, int n, hipStream_t st, int* out, int* aux = 
 extern "C" {
 
 int slm_fuse_create(int32_t H, int32_t W, int32_t max_surfels, slm_fuse** out) {
-  if (!out || H < 8 || W < 8 || max_surfels < 1) return ffail(SLM_ERR_INVALID, "slm_fuse_create: bad argument");
-  if (slm_device_count() < 1) return ffail(SLM_ERR_NO_DEVICE, "slm_fuse_create: no HIP device visible");
+  if (!out || H < 8 || W < 8 || max_surfels < 1) return fail(SLM_ERR_INVALID, "slm_fuse_create: bad argument");
+  if (slm_device_count() < 1) return fail(SLM_ERR_NO_DEVICE, "slm_fuse_create: no HIP device visible");
   slm_fuse* f = new slm_fuse();
   f->H = H;
   f->W = W;
   f->cap = max_surfels;
   const size_t HW = (size_t)H * W, cap = (size_t)max_surfels, nmax = HW > cap ? HW : cap;
-  hipError_t e = falloc(f->keys, cap);
-  if (e == hipSuccess) e = falloc(f->skeys, cap);
-  if (e == hipSuccess) e = falloc(f->ids, cap);
-  if (e == hipSuccess) e = falloc(f->sids, cap);
-  if (e == hipSuccess) e = falloc(f->layers, FU_LAYERS * HW);
-  if (e == hipSuccess) e = falloc(f->flag, nmax);
-  if (e == hipSuccess) e = falloc(f->pos, nmax);
-  if (e == hipSuccess) e = falloc(f->cand_idx, FU_KMAX * HW);
-  if (e == hipSuccess) e = falloc(f->cand_w, FU_KMAX * HW);
-  if (e == hipSuccess) e = falloc(f->dead, cap);
-  if (e == hipSuccess) e = falloc(f->counters, 4);
+  const size_t units[] = {cap, HW, nmax, 1};
+  hipError_t e = alloc_members(f, kFuseArrays, units);
   if (e == hipSuccess) e = hipHostMalloc((void**)&f->h_counters, sizeof(int32_t) * 4, hipHostMallocDefault);
-  if (e == hipSuccess) e = falloc(f->s_d3, 6 * cap);
-  if (e == hipSuccess) e = falloc(f->s_d1, cap);
-  if (e == hipSuccess) e = falloc(f->s_d4, FU_KMAX * cap);
-  if (e == hipSuccess) e = falloc(f->s_f3, 3 * cap);
-  if (e == hipSuccess) e = falloc(f->s_f1, 2 * cap);
-  if (e == hipSuccess) e = falloc(f->s_f2, 2 * cap);
-  if (e == hipSuccess) e = falloc(f->s_i4, FU_KMAX * cap);
-  if (e == hipSuccess) e = falloc(f->s_seg, cap);
-  if (e == hipSuccess) e = falloc(f->s_sc, SLM_MAX_CLASSES * cap);
-  if (e == hipSuccess) e = falloc(f->s_d2e, cap);
   if (e != hipSuccess) {
-    slm_set_error_text((std::string("slm_fuse_create: ") + hipGetErrorString(e)).c_str());
     slm_fuse_destroy(f);
-    return SLM_ERR_HIP;
+    return fail(SLM_ERR_HIP, std::string("slm_fuse_create: ") + hipGetErrorString(e));
   }
   *out = f;
   return SLM_OK;
@@ -720,40 +666,36 @@ int slm_fuse_create(int32_t H, int32_t W, int32_t max_surfels, slm_fuse** out) {
 
 int slm_fuse_destroy(slm_fuse* f) {
   if (!f) return SLM_OK;
-  void* ptrs[] = {f->keys, f->skeys, f->ids, f->sids, f->layers, f->flag, f->pos, f->cand_idx, f->cand_w, f->dead,
-                  f->counters, f->boxes, f->tmp, f->s_d3, f->s_d1, f->s_d4, f->s_f3, f->s_f1, f->s_f2, f->s_i4, f->s_seg, f->s_sc,
-                  f->s_d2e};
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
+  free_members(f, kFuseArrays);
   if (f->h_counters) (void)hipHostFree(f->h_counters);
   delete f;
   return SLM_OK;
 }
 
 int slm_fuse_bind_semantic(slm_fuse* f, const slm_fuse_semantic* sem) {
-  if (!f) return ffail(SLM_ERR_INVALID, "slm_fuse_bind_semantic: null handle");
+  if (!f) return fail(SLM_ERR_INVALID, "slm_fuse_bind_semantic: null handle");
   if (!sem) {
     f->sem = slm_fuse_semantic{};
     return SLM_OK;
   }
   if (sem->num_classes < 1 || sem->num_classes > SLM_MAX_CLASSES)
-    return ffail(SLM_ERR_UNSUPPORTED, "slm_fuse_bind_semantic: num_classes must be in 1..4");
+    return fail(SLM_ERR_UNSUPPORTED, "slm_fuse_bind_semantic: num_classes must be in 1..4");
   if (!sem->seg || !sem->seg_conf || !sem->dist2edge)
-    return ffail(SLM_ERR_INVALID, "slm_fuse_bind_semantic: seg / seg_conf / dist2edge must be given");
+    return fail(SLM_ERR_INVALID, "slm_fuse_bind_semantic: seg / seg_conf / dist2edge must be given");
   if ((sem->soft_weights && !sem->ed_seg_conf) || (sem->hard_seg && !sem->ed_seg))
-    return ffail(SLM_ERR_INVALID, "slm_fuse_bind_semantic: the ED nodes' seg_conf (soft weights) / seg (hard_seg) is missing");
+    return fail(SLM_ERR_INVALID, "slm_fuse_bind_semantic: the ED nodes' seg_conf (soft weights) / seg (hard_seg) is missing");
   f->sem = *sem;
   return SLM_OK;
 }
 
 static int fuse_check(slm_fuse* f, const slm_fuse_config* c, const slm_surfel_model* m) {
-  if (!f || !c || !m) return ffail(SLM_ERR_INVALID, "slm_fuse: null argument");
-  if (c->H != f->H || c->W != f->W) return ffail(SLM_ERR_INVALID, "slm_fuse: image size differs from slm_fuse_create");
-  if (m->n < 0 || m->cap > f->cap || m->n > m->cap) return ffail(SLM_ERR_INVALID, "slm_fuse: model rows exceed the capacity");
+  if (!f || !c || !m) return fail(SLM_ERR_INVALID, "slm_fuse: null argument");
+  if (c->H != f->H || c->W != f->W) return fail(SLM_ERR_INVALID, "slm_fuse: image size differs from slm_fuse_create");
+  if (m->n < 0 || m->cap > f->cap || m->n > m->cap) return fail(SLM_ERR_INVALID, "slm_fuse: model rows exceed the capacity");
   if (!m->points || !m->norms || !m->colors || !m->radii || !m->confs || !m->time_stamp || !m->is_stable ||
       !m->knn_idx || !m->knn_w || !m->projdata || !m->ed_points || !m->ed_radii || m->J < (int)fu_Kh(*m))
-    return ffail(SLM_ERR_INVALID, "slm_fuse: null device pointer (or fewer than num_neighbors ED nodes)");
-  if (m->K < 0 || m->K > FU_KMAX) return ffail(SLM_ERR_UNSUPPORTED, "slm_fuse: num_neighbors must be in 1..8 (0 = 4)");
+    return fail(SLM_ERR_INVALID, "slm_fuse: null device pointer (or fewer than num_neighbors ED nodes)");
+  if (m->K < 0 || m->K > FU_KMAX) return fail(SLM_ERR_UNSUPPORTED, "slm_fuse: num_neighbors must be in 1..8 (0 = 4)");
   return SLM_OK;
 }
 
@@ -763,37 +705,30 @@ int slm_fuse_input_data(slm_fuse* f, const slm_fuse_config* cfg, slm_surfel_mode
   if (rc) return rc;
   if (!frame || !frame->valid || !frame->index_map ||
       (frame->T > 0 && (!frame->points || !frame->norms || !frame->colors || !frame->radii || !frame->confs)))
-    return ffail(SLM_ERR_INVALID, "slm_fuse_input_data: null frame pointer");
+    return fail(SLM_ERR_INVALID, "slm_fuse_input_data: null frame pointer");
   const slm_fuse_semantic sm = f->sem;
   if (sm.num_classes > 0 && frame->T > 0 && (!sm.new_seg || !sm.new_seg_conf || !sm.new_dist2edge))
-    return ffail(SLM_ERR_INVALID, "slm_fuse_input_data: the frame's seg / seg_conf / dist2edge are not bound");
+    return fail(SLM_ERR_INVALID, "slm_fuse_input_data: the frame's seg / seg_conf / dist2edge are not bound");
   hipStream_t st = (hipStream_t)stream;
   const slm_fuse_config c = *cfg;
   slm_surfel_model m = *model;
   const int HW = c.H * c.W, n = m.n;
   const dim3 blk(256), gp((HW + 255) / 256), gs((n + 255) / 256);
   // 1. per-pixel confidence-ordered layers
-  if (m.merged_into && n > 0) FCHK(hipMemsetAsync(m.merged_into, 0xFF, sizeof(int32_t) * (size_t)n, st));
-  FCHK(hipMemsetAsync(f->layers, 0xFF, sizeof(int32_t) * FU_LAYERS * (size_t)HW, st));
-  FCHK(hipMemsetAsync(f->dead, 0, (size_t)f->cap, st));
-  FCHK(hipMemsetAsync(f->counters, 0, sizeof(int32_t) * 4, st));
+  if (m.merged_into && n > 0) HIPCHK(hipMemsetAsync(m.merged_into, 0xFF, sizeof(int32_t) * (size_t)n, st));
+  HIPCHK(hipMemsetAsync(f->layers, 0xFF, sizeof(int32_t) * FU_LAYERS * (size_t)HW, st));
+  HIPCHK(hipMemsetAsync(f->dead, 0, (size_t)f->cap, st));
+  HIPCHK(hipMemsetAsync(f->counters, 0, sizeof(int32_t) * 4, st));
   // (the number of layer maps in use stays on the device, counters[0]: no read-back between the stages)
   if (n > 0) {
     hipLaunchKernelGGL(k_fu_keys, gs, blk, 0, st, c, m, f->keys, f->ids);
-    size_t bytes = 0;
     // keys are (pixel << 32) | ~confidence, or ~0 for surfels that do not project: the significant bits are the 32
     // confidence bits and the bits of H*W (one more so that the all-ones key still sorts last)
     unsigned end_bit = 33;
     while (end_bit < 64 && (1ull << (end_bit - 32)) <= (unsigned long long)HW) ++end_bit;
-    FCHK(rocprim::radix_sort_pairs(nullptr, bytes, f->keys, f->skeys, f->ids, f->sids, (size_t)n, 0, end_bit, st));
-    if (bytes > f->cap_tmp) {
-      if (f->tmp) FCHK(hipFree(f->tmp));
-      f->tmp = nullptr;
-      f->cap_tmp = 0;
-      FCHK(hipMalloc(&f->tmp, bytes));
-      f->cap_tmp = bytes;
-    }
-    FCHK(rocprim::radix_sort_pairs(f->tmp, bytes, f->keys, f->skeys, f->ids, f->sids, (size_t)n, 0, end_bit, st));
+    HIPCHK(with_scratch(f->tmp, f->cap_tmp, [&](void* tmp, size_t& bytes) {
+      return rocprim::radix_sort_pairs(tmp, bytes, f->keys, f->skeys, f->ids, f->sids, (size_t)n, 0, end_bit, st);
+    }));
     hipLaunchKernelGGL(k_fu_layers, gs, blk, 0, st, n, HW, f->skeys, f->sids, f->layers, f->dead, f->counters);
   }
   // 2. the frame's points into the layers; flag = candidate new surfel
@@ -805,33 +740,27 @@ int slm_fuse_input_data(slm_fuse* f, const slm_fuse_config* cfg, slm_surfel_mode
   }
   // 4. skinning weights at the fused positions
   const int K = (int)fu_Kh(m);
-  if (n > 0) FU_K_DISPATCH(K, hipLaunchKernelGGL(k_fu_weights<KK>, gs, blk, 0, st, m, sm));
+  if (n > 0) SLM_K_DISPATCH(K, hipLaunchKernelGGL(k_fu_weights<KK>, gs, blk, 0, st, m, sm));
   // 5. unmatched points with a nearby node become new surfels, in row-major pixel (= sfdata) order
   int n_new = 0;
   if (c.add_new && c.merge_new && n > 0) {   // (no surfel projects anywhere -> every flag is 0, nothing is added)
     const int n_runs = (m.J + FU_RUN - 1) / FU_RUN;
-    if ((size_t)n_runs > f->cap_boxes) {
-      if (f->boxes) FCHK(hipFree(f->boxes));
-      f->boxes = nullptr;
-      f->cap_boxes = 0;
-      FCHK(hipMalloc((void**)&f->boxes, sizeof(double) * 6 * (size_t)n_runs));
-      f->cap_boxes = (size_t)n_runs;
-    }
+    HIPCHK(grow(f->boxes, f->cap_boxes, 6 * (size_t)n_runs, 6 * (size_t)n_runs));
     hipLaunchKernelGGL(k_fu_node_boxes, dim3(n_runs), dim3(64), 0, st, m.J, m.ed_points, f->boxes);
-    FU_K_DISPATCH(K, hipLaunchKernelGGL(k_fu_candidates<KK>, gp, blk, 0, st, c, m, sm, *frame, f->flag, f->cand_idx, f->cand_w,
+    SLM_K_DISPATCH(K, hipLaunchKernelGGL(k_fu_candidates<KK>, gp, blk, 0, st, c, m, sm, *frame, f->flag, f->cand_idx, f->cand_w,
                                         f->counters, f->boxes));
-    FCHK(scan_flags(f, HW, st));
+    HIPCHK(scan_flags(f, HW, st));
     int n_short = 0;
-    FCHK(count_flags(f, HW, st, &n_new, &n_short));
+    HIPCHK(count_flags(f, HW, st, &n_new, &n_short));
     if (n_short > 0)
-      return ffail(SLM_ERR_INVALID, "slm_fuse_input_data: hard_seg needs at least num_neighbors ED nodes of every class that has new points");
-    if (n + n_new > m.cap) return ffail(SLM_ERR_INVALID, "slm_fuse_input_data: model capacity too small for the new surfels");
+      return fail(SLM_ERR_INVALID, "slm_fuse_input_data: hard_seg needs at least num_neighbors ED nodes of every class that has new points");
+    if (n + n_new > m.cap) return fail(SLM_ERR_INVALID, "slm_fuse_input_data: model capacity too small for the new surfels");
     if (n_new > 0)
       hipLaunchKernelGGL(k_fu_append, gp, blk, 0, st, c, m, sm, *frame, f->flag, f->pos, f->cand_idx, f->cand_w);
   }
   m.n = n + n_new;
   if (m.n > 0) hipLaunchKernelGGL(k_fu_proj, dim3((m.n + 255) / 256), blk, 0, st, c, m, m.n);
-  FCHK(hipGetLastError());
+  HIPCHK(hipGetLastError());
   model->n = m.n;
   return SLM_OK;
 }
@@ -840,7 +769,7 @@ int slm_fuse_swap_stable(slm_fuse* f, const slm_fuse_config* cfg, slm_surfel_mod
                          const int32_t* keep_ids, int32_t n_keep, int32_t* new_index, void* stream) {
   int rc = fuse_check(f, cfg, model);
   if (rc) return rc;
-  if (n_keep < 0 || (n_keep > 0 && !keep_ids)) return ffail(SLM_ERR_INVALID, "slm_fuse_swap_stable: bad keep_ids");
+  if (n_keep < 0 || (n_keep > 0 && !keep_ids)) return fail(SLM_ERR_INVALID, "slm_fuse_swap_stable: bad keep_ids");
   if (!cfg->remove_unstable || model->n == 0) return SLM_OK;
   hipStream_t st = (hipStream_t)stream;
   slm_surfel_model m = *model;
@@ -849,31 +778,31 @@ int slm_fuse_swap_stable(slm_fuse* f, const slm_fuse_config* cfg, slm_surfel_mod
   hipLaunchKernelGGL(k_fu_keep, gs, blk, 0, st, *cfg, m, time, f->flag);
   if (n_keep > 0)
     hipLaunchKernelGGL(k_fu_force_keep, dim3((n_keep + 63) / 64), dim3(64), 0, st, n, n_keep, keep_ids, f->flag);
-  FCHK(scan_flags(f, n, st));
+  HIPCHK(scan_flags(f, n, st));
   if (new_index) hipLaunchKernelGGL(k_fu_new_index, gs, blk, 0, st, n, f->flag, f->pos, new_index);
   slm_fuse scratch = *f;
   hipLaunchKernelGGL(k_fu_compact, gs, blk, 0, st, m, scratch, f->flag, f->pos);   // before the read-back: runs under it
   int kept = 0;
-  FCHK(count_flags(f, n, st, &kept));
+  HIPCHK(count_flags(f, n, st, &kept));
   const size_t k = (size_t)kept, cap = (size_t)m.cap;
   if (kept > 0) {
-    FCHK(hipMemcpyAsync(m.points, f->s_d3, sizeof(double) * 3 * k, hipMemcpyDeviceToDevice, st));
-    FCHK(hipMemcpyAsync(m.norms, f->s_d3 + 3 * cap, sizeof(double) * 3 * k, hipMemcpyDeviceToDevice, st));
-    FCHK(hipMemcpyAsync(m.colors, f->s_f3, sizeof(float) * 3 * k, hipMemcpyDeviceToDevice, st));
-    FCHK(hipMemcpyAsync(m.radii, f->s_d1, sizeof(double) * k, hipMemcpyDeviceToDevice, st));
-    FCHK(hipMemcpyAsync(m.confs, f->s_f1, sizeof(float) * k, hipMemcpyDeviceToDevice, st));
-    FCHK(hipMemcpyAsync(m.time_stamp, f->s_f1 + cap, sizeof(float) * k, hipMemcpyDeviceToDevice, st));
-    FCHK(hipMemcpyAsync(m.knn_idx, f->s_i4, sizeof(int32_t) * fu_Kh(m) * k, hipMemcpyDeviceToDevice, st));
-    FCHK(hipMemcpyAsync(m.knn_w, f->s_d4, sizeof(double) * fu_Kh(m) * k, hipMemcpyDeviceToDevice, st));
-    FCHK(hipMemcpyAsync(m.projdata, f->s_f2, sizeof(float) * 2 * k, hipMemcpyDeviceToDevice, st));
-    FCHK(hipMemsetAsync(m.is_stable, 1, k, st));
+    HIPCHK(hipMemcpyAsync(m.points, f->s_d3, sizeof(double) * 3 * k, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(m.norms, f->s_d3 + 3 * cap, sizeof(double) * 3 * k, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(m.colors, f->s_f3, sizeof(float) * 3 * k, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(m.radii, f->s_d1, sizeof(double) * k, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(m.confs, f->s_f1, sizeof(float) * k, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(m.time_stamp, f->s_f1 + cap, sizeof(float) * k, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(m.knn_idx, f->s_i4, sizeof(int32_t) * fu_Kh(m) * k, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(m.knn_w, f->s_d4, sizeof(double) * fu_Kh(m) * k, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(m.projdata, f->s_f2, sizeof(float) * 2 * k, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemsetAsync(m.is_stable, 1, k, st));
     if (f->sem.num_classes > 0) {
-      FCHK(hipMemcpyAsync(f->sem.seg, f->s_seg, sizeof(int32_t) * k, hipMemcpyDeviceToDevice, st));
-      FCHK(hipMemcpyAsync(f->sem.seg_conf, f->s_sc, sizeof(double) * f->sem.num_classes * k, hipMemcpyDeviceToDevice, st));
-      FCHK(hipMemcpyAsync(f->sem.dist2edge, f->s_d2e, sizeof(double) * k, hipMemcpyDeviceToDevice, st));
+      HIPCHK(hipMemcpyAsync(f->sem.seg, f->s_seg, sizeof(int32_t) * k, hipMemcpyDeviceToDevice, st));
+      HIPCHK(hipMemcpyAsync(f->sem.seg_conf, f->s_sc, sizeof(double) * f->sem.num_classes * k, hipMemcpyDeviceToDevice, st));
+      HIPCHK(hipMemcpyAsync(f->sem.dist2edge, f->s_d2e, sizeof(double) * k, hipMemcpyDeviceToDevice, st));
     }
   }
-  FCHK(hipGetLastError());
+  HIPCHK(hipGetLastError());
   model->n = kept;
   return SLM_OK;
 }

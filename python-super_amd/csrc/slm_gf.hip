@@ -14,6 +14,7 @@
 #include <string>
 #include <vector>
 
+#include "slm_host.h"
 #include "slm_sem.h"
 #include "slm_lane.h"
 
@@ -723,27 +724,11 @@ __global__ void __launch_bounds__(256) k_gf_update_nodes(int J, RT* __restrict__
 }
 
 // ---------------------------------------------------------------------------------------
-void slm_set_error_text(const char* msg);   // slm_api.hip
-
-// one instantiation of the per-surfel kernels per opt.num_neighbors (1..8)
-#define GF_K_DISPATCH(K, ...)                                          \
-  switch (K) {                                                         \
-    case 1: { constexpr int KK = 1; __VA_ARGS__; break; }                     \
-    case 2: { constexpr int KK = 2; __VA_ARGS__; break; }                     \
-    case 3: { constexpr int KK = 3; __VA_ARGS__; break; }                     \
-    case 4: { constexpr int KK = 4; __VA_ARGS__; break; }                     \
-    case 5: { constexpr int KK = 5; __VA_ARGS__; break; }                     \
-    case 6: { constexpr int KK = 6; __VA_ARGS__; break; }                     \
-    case 7: { constexpr int KK = 7; __VA_ARGS__; break; }                     \
-    case 8: { constexpr int KK = 8; __VA_ARGS__; break; }                     \
-    default: break;                                                    \
-  }
-
 struct slm_gf {
   int batch_K = SLM_K;       // num_neighbors of the slots of the launch being enqueued (gf_dims: they must agree)
   slm_gf_config cfg{};
   std::vector<GfSlot> host;
-  std::vector<size_t> cap;
+  std::vector<size_t> cap;   // per slot: doubles of its one allocation (GfSlot::dv)
   std::vector<SemScratch> sem;
   GfSlot* dev = nullptr;
   int* knn_bad = nullptr;    // device flag of slm_gf_bind_frame's table check
@@ -751,20 +736,6 @@ struct slm_gf {
   const double** pgrad = nullptr;             // (max_frames) device: slm_gf_bind_point_grad's buffer per slot, or null
   std::vector<const double*> pgrad_host;      // the same on the host: selects the EXTRA launch
 };
-
-#define GFCHK(expr)                                                       \
-  do {                                                                    \
-    hipError_t e_ = (expr);                                               \
-    if (e_ != hipSuccess) {                                               \
-      slm_set_error_text((std::string(#expr) + ": " + hipGetErrorString(e_)).c_str()); \
-      return SLM_ERR_HIP;                                                 \
-    }                                                                     \
-  } while (0)
-
-static int gf_fail(int code, const char* msg) {
-  slm_set_error_text(msg);
-  return code;
-}
 
 // pass 1: zero the gradient / terms, then the morphing term's per-surfel pass (sum, count)
 static void gf_enqueue_morph(slm_gf* g, GfSlot* slots, int n, int maxN, hipStream_t st) {
@@ -791,11 +762,11 @@ static void gf_enqueue_losses(slm_gf* g, GfSlot* slots, int n, int maxN, int max
     // the node terms ride on this launch as its tail blocks
     const bool extra = c.seg_mode || c.use_bn_morph || c.corr_mode || c.pp_max > 0.0 || pg;
     if (extra) {
-      GF_K_DISPATCH(g->batch_K, hipLaunchKernelGGL((k_gf_data<KK, true>), dim3(nd + nr, n), dim3(256), 0, st, slots, use_pp, c.w_data,
+      SLM_K_DISPATCH(g->batch_K, hipLaunchKernelGGL((k_gf_data<KK, true>), dim3(nd + nr, n), dim3(256), 0, st, slots, use_pp, c.w_data,
                                                    c.seg_mode, c.seg_mode ? 0.0 : c.pp_max, c.use_bn_morph ? (morph_in_partials ? 2 : 1) : 0, c.w_bn_morph, c.corr_mode, c.w_corr,
                                                    nd, ra, pg ? g->pgrad + first : nullptr));
     } else {
-      GF_K_DISPATCH(g->batch_K, hipLaunchKernelGGL((k_gf_data<KK, false>), dim3(nd + nr, n), dim3(256), 0, st, slots, use_pp, c.w_data,
+      SLM_K_DISPATCH(g->batch_K, hipLaunchKernelGGL((k_gf_data<KK, false>), dim3(nd + nr, n), dim3(256), 0, st, slots, use_pp, c.w_data,
                                                    0, 0.0, 0, 0.0, 0, 0.0, nd, ra, nullptr));
     }
   } else if (reg) {
@@ -813,16 +784,16 @@ template <typename RT>
 static int apply_update_gf_t(int32_t N, int32_t J, int32_t K, RT* sf_points, RT* sf_norms,
                              const int32_t* sf_knn_idx, const RT* sf_knn_w, RT* ed_points, RT* ed_norms,
                              const double* deform, void* stream) {
-  if (K < 1 || K > 8) return gf_fail(SLM_ERR_UNSUPPORTED, "slm_apply_update_gf: num_neighbors must be in 1..8");
+  if (K < 1 || K > 8) return fail(SLM_ERR_UNSUPPORTED, "slm_apply_update_gf: num_neighbors must be in 1..8");
   if (N < 0 || J < 1 || !ed_points || !ed_norms || !deform ||
       (N > 0 && (!sf_points || !sf_norms || !sf_knn_idx || !sf_knn_w)))
-    return gf_fail(SLM_ERR_INVALID, "slm_apply_update_gf: bad argument");
+    return fail(SLM_ERR_INVALID, "slm_apply_update_gf: bad argument");
   hipStream_t st = (hipStream_t)stream;
   if (N > 0)
-    GF_K_DISPATCH(K, hipLaunchKernelGGL((k_gf_update_surfels<RT, KK>), dim3((N + 255) / 256), dim3(256), 0, st, N, J, sf_points, sf_norms,
+    SLM_K_DISPATCH(K, hipLaunchKernelGGL((k_gf_update_surfels<RT, KK>), dim3((N + 255) / 256), dim3(256), 0, st, N, J, sf_points, sf_norms,
                                         sf_knn_idx, sf_knn_w, (const RT*)ed_points, deform));
   hipLaunchKernelGGL(k_gf_update_nodes<RT>, dim3((J + 255) / 256), dim3(256), 0, st, J, ed_points, ed_norms, deform);
-  GFCHK(hipGetLastError());
+  HIPCHK(hipGetLastError());
   return SLM_OK;
 }
 
@@ -831,8 +802,8 @@ extern "C" {
 int slm_gf_create(const slm_gf_config* cfg, slm_gf** out) {
   if (!cfg || !out || cfg->max_frames < 1 || cfg->num_iterations < 0 || (cfg->optimizer != 0 && cfg->optimizer != 1) ||
       cfg->seg_mode < 0 || cfg->seg_mode > 2 || cfg->corr_mode < 0 || cfg->corr_mode > 2)
-    return gf_fail(SLM_ERR_INVALID, "slm_gf_create: bad argument");
-  if (slm_device_count() < 1) return gf_fail(SLM_ERR_NO_DEVICE, "slm_gf_create: no HIP device visible");
+    return fail(SLM_ERR_INVALID, "slm_gf_create: bad argument");
+  if (slm_device_count() < 1) return fail(SLM_ERR_NO_DEVICE, "slm_gf_create: no HIP device visible");
   slm_gf* g = new slm_gf();
   g->cfg = *cfg;
   g->host.assign(cfg->max_frames, GfSlot{});
@@ -845,12 +816,8 @@ int slm_gf_create(const slm_gf_config* cfg, slm_gf** out) {
   if (e == hipSuccess) e = hipMalloc((void**)&g->pgrad, sizeof(const double*) * cfg->max_frames);
   if (e == hipSuccess) e = hipMemset(g->pgrad, 0, sizeof(const double*) * cfg->max_frames);
   if (e != hipSuccess) {
-    slm_set_error_text((std::string("slm_gf_create: ") + hipGetErrorString(e)).c_str());
-    if (g->dev) (void)hipFree(g->dev);
-    if (g->knn_bad) (void)hipFree(g->knn_bad);
-    if (g->pgrad) (void)hipFree(g->pgrad);
-    delete g;
-    return SLM_ERR_HIP;
+    slm_gf_destroy(g);
+    return fail(SLM_ERR_HIP, std::string("slm_gf_create: ") + hipGetErrorString(e));
   }
   *out = g;
   return SLM_OK;
@@ -870,27 +837,23 @@ int slm_gf_destroy(slm_gf* g) {
 }
 
 int slm_gf_bind_frame(slm_gf* g, int32_t slot, const slm_gf_frame* fr, void* stream) {
-  if (!g || !fr) return gf_fail(SLM_ERR_INVALID, "slm_gf_bind_frame: null argument");
-  if (slot < 0 || slot >= (int)g->host.size()) return gf_fail(SLM_ERR_INVALID, "slm_gf_bind_frame: bad slot");
+  if (!g || !fr) return fail(SLM_ERR_INVALID, "slm_gf_bind_frame: null argument");
+  if (slot < 0 || slot >= (int)g->host.size()) return fail(SLM_ERR_INVALID, "slm_gf_bind_frame: bad slot");
   const slm_frame& f = fr->base;
-  if (f.K < 1 || f.K > 8) return gf_fail(SLM_ERR_UNSUPPORTED, "slm_gf_bind_frame: num_neighbors must be in 1..8");
+  if (f.K < 1 || f.K > 8) return fail(SLM_ERR_UNSUPPORTED, "slm_gf_bind_frame: num_neighbors must be in 1..8");
   if (f.K_ED < 1 || f.K_ED > SLM_MAX_KED || f.N < 0 || f.J < 1 || f.H < 4 || f.W < 4)
-    return gf_fail(SLM_ERR_INVALID, "slm_gf_bind_frame: bad sizes");
+    return fail(SLM_ERR_INVALID, "slm_gf_bind_frame: bad sizes");
   if (!f.sf_points || !f.sf_knn_idx || !f.sf_knn_w || !f.ed_points || !f.ed_knn_idx || !f.tgt_points ||
       !f.tgt_norms || !f.index_map || (g->cfg.use_arap && !fr->ed_knn_w) ||
       (g->cfg.use_face && (!fr->ed_triangles || !fr->ed_triangle_areas)))
-    return gf_fail(SLM_ERR_INVALID, "slm_gf_bind_frame: null device pointer");
+    return fail(SLM_ERR_INVALID, "slm_gf_bind_frame: null device pointer");
   if (f.N > 0 && f.J < f.K)   // (the reference's top-k of K among J nodes raises)
-    return gf_fail(SLM_ERR_INVALID, "slm_gf_bind_frame: fewer nodes (J) than num_neighbors: sf_knn_idx cannot hold K distinct ids");
+    return fail(SLM_ERR_INVALID, "slm_gf_bind_frame: fewer nodes (J) than num_neighbors: sf_knn_idx cannot hold K distinct ids");
   hipStream_t st = (hipStream_t)stream;
   GfSlot& s = g->host[slot];
   const size_t n = (size_t)(f.J + 1) * 7;
-  if (n > g->cap[slot]) {
-    if (s.dv) GFCHK(hipFree(s.dv));
-    s.dv = nullptr;
-    GFCHK(hipMalloc((void**)&s.dv, sizeof(double) * (4 * n + SLM_GF_NTERMS + GF_PART_DOUBLES)));   // ... | terms | spread block partials
-    g->cap[slot] = n;
-  }
+  const size_t n_dv = 4 * n + SLM_GF_NTERMS + GF_PART_DOUBLES;   // ... | terms | spread block partials
+  HIPCHK(grow(s.dv, g->cap[slot], n_dv, n_dv));
   s.grad = s.dv + n;
   s.m1 = s.dv + 2 * n;
   s.m2 = s.dv + 3 * n;
@@ -901,7 +864,7 @@ int slm_gf_bind_frame(slm_gf* g, int32_t slot, const slm_gf_frame* fr, void* str
   s.sem_bound = 0;   // semantic inputs, the flow and a point gradient belong to the frame: bind them again
   s.flow = nullptr;
   g->pgrad_host[slot] = nullptr;
-  GFCHK(hipMemcpyAsync(g->pgrad + slot, &g->pgrad_host[slot], sizeof(const double*), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(g->pgrad + slot, &g->pgrad_host[slot], sizeof(const double*), hipMemcpyHostToDevice, st));
   s.shard_lo = (int32_t)((int64_t)f.N * g->rank / g->world);
   s.shard_hi = (int32_t)((int64_t)f.N * (g->rank + 1) / g->world);
   // The KNN tables as the reference's top-k makes them: distinct ids in [0, J) (k_gf_data's row pass gives every id of a
@@ -909,110 +872,110 @@ int slm_gf_bind_frame(slm_gf* g, int32_t slot, const slm_gf_frame* fr, void* str
   int bad_host = 0;
   {
     const int n_ed = f.J * f.K_ED, n_thr = n_ed > f.N ? n_ed : f.N;
-    GFCHK(hipMemsetAsync(g->knn_bad, 0, sizeof(int), st));
+    HIPCHK(hipMemsetAsync(g->knn_bad, 0, sizeof(int), st));
     hipLaunchKernelGGL(k_gf_check_knn, dim3((unsigned)((n_thr + 255) / 256)), dim3(256), 0, st, f.N, f.K, f.J, f.sf_knn_idx, n_ed,
                        f.ed_knn_idx, g->knn_bad);
-    GFCHK(hipMemcpyAsync(&bad_host, g->knn_bad, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&bad_host, g->knn_bad, sizeof(int), hipMemcpyDeviceToHost, st));
   }
-  GFCHK(hipMemcpyAsync(g->dev + slot, &s, sizeof(GfSlot), hipMemcpyHostToDevice, st));
-  GFCHK(hipStreamSynchronize(st));
+  HIPCHK(hipMemcpyAsync(g->dev + slot, &s, sizeof(GfSlot), hipMemcpyHostToDevice, st));
+  HIPCHK(hipStreamSynchronize(st));
   if (bad_host) {   // refused: the slot stays unbound, on the device too
     s.bound = 0;
-    GFCHK(hipMemcpyAsync(g->dev + slot, &s, sizeof(GfSlot), hipMemcpyHostToDevice, st));
-    GFCHK(hipStreamSynchronize(st));
-    return gf_fail(SLM_ERR_INVALID, "slm_gf_bind_frame: a KNN index (sf_knn_idx or ed_knn_idx) lies outside [0, J) or a "
+    HIPCHK(hipMemcpyAsync(g->dev + slot, &s, sizeof(GfSlot), hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return fail(SLM_ERR_INVALID, "slm_gf_bind_frame: a KNN index (sf_knn_idx or ed_knn_idx) lies outside [0, J) or a "
                                     "surfel's row of sf_knn_idx repeats an id");
   }
   hipLaunchKernelGGL(k_gf_init, dim3((n + 255) / 256), dim3(256), 0, st, g->dev, slot);
-  GFCHK(hipGetLastError());
+  HIPCHK(hipGetLastError());
   return SLM_OK;
 }
 
 int slm_gf_bind_semantic(slm_gf* g, int32_t slot, const slm_gf_semantic* sem, int32_t* edge_counts_host,
                          void* stream) {
-  if (!g || !sem) return gf_fail(SLM_ERR_INVALID, "slm_gf_bind_semantic: null argument");
-  if (slot < 0 || slot >= (int)g->host.size()) return gf_fail(SLM_ERR_INVALID, "slm_gf_bind_semantic: bad slot");
+  if (!g || !sem) return fail(SLM_ERR_INVALID, "slm_gf_bind_semantic: null argument");
+  if (slot < 0 || slot >= (int)g->host.size()) return fail(SLM_ERR_INVALID, "slm_gf_bind_semantic: bad slot");
   GfSlot& s = g->host[slot];
-  if (!s.bound) return gf_fail(SLM_ERR_UNBOUND, "slm_gf_bind_semantic: slm_gf_bind_frame first");
+  if (!s.bound) return fail(SLM_ERR_UNBOUND, "slm_gf_bind_semantic: slm_gf_bind_frame first");
   if (sem->num_classes < 1 || sem->num_classes > SLM_MAX_CLASSES)
-    return gf_fail(SLM_ERR_UNSUPPORTED, "slm_gf_bind_semantic: num_classes must be 1..4");
+    return fail(SLM_ERR_UNSUPPORTED, "slm_gf_bind_semantic: num_classes must be 1..4");
   const slm_frame& f = s.f.base;
   const bool need_pp = g->cfg.seg_mode != 0, need_morph = g->cfg.use_bn_morph != 0;
   if ((f.N > 0 && !sem->sf_seg) || (need_pp && ((f.N > 0 && !sem->sf_seg_conf) || (f.T > 0 && !sem->tgt_seg_conf))) ||
       (need_morph && (!sem->img_seg_conf || !sem->img_seg)))
-    return gf_fail(SLM_ERR_INVALID, "slm_gf_bind_semantic: null device pointer");
+    return fail(SLM_ERR_INVALID, "slm_gf_bind_semantic: null device pointer");
   hipStream_t st = (hipStream_t)stream;
   SemScratch& sc = g->sem[slot];
   s.sem = *sem;
   for (int c = 0; c <= SLM_MAX_CLASSES; ++c) s.edge_off[c] = 0;
   if (need_morph) {
-    GFCHK(sem_extract_edges(sc, *sem, f.H, f.W, s.edge_off, st));
-    GFCHK(sem_ensure_morph(sc, f.N));
+    HIPCHK(sem_extract_edges(sc, *sem, f.H, f.W, s.edge_off, st));
+    HIPCHK(sem_ensure_morph(sc, f.N));
   }
   s.edge_xy = sc.edge_xy;
   s.morph_g = sc.morph_g;
   s.sem_bound = 1;
   if (edge_counts_host)
     for (int c = 0; c < sem->num_classes; ++c) edge_counts_host[c] = s.edge_off[c + 1] - s.edge_off[c];
-  GFCHK(hipMemcpyAsync(g->dev + slot, &s, sizeof(GfSlot), hipMemcpyHostToDevice, st));
-  GFCHK(hipStreamSynchronize(st));
+  HIPCHK(hipMemcpyAsync(g->dev + slot, &s, sizeof(GfSlot), hipMemcpyHostToDevice, st));
+  HIPCHK(hipStreamSynchronize(st));
   return SLM_OK;
 }
 
 int slm_gf_bind_flow(slm_gf* g, int32_t slot, const float* flow, void* stream) {
-  if (!g || !flow) return gf_fail(SLM_ERR_INVALID, "slm_gf_bind_flow: null argument");
-  if (slot < 0 || slot >= (int)g->host.size()) return gf_fail(SLM_ERR_INVALID, "slm_gf_bind_flow: bad slot");
+  if (!g || !flow) return fail(SLM_ERR_INVALID, "slm_gf_bind_flow: null argument");
+  if (slot < 0 || slot >= (int)g->host.size()) return fail(SLM_ERR_INVALID, "slm_gf_bind_flow: bad slot");
   GfSlot& s = g->host[slot];
-  if (!s.bound) return gf_fail(SLM_ERR_UNBOUND, "slm_gf_bind_flow: slm_gf_bind_frame first");
+  if (!s.bound) return fail(SLM_ERR_UNBOUND, "slm_gf_bind_flow: slm_gf_bind_frame first");
   hipStream_t st = (hipStream_t)stream;
   s.flow = flow;
   // the pointer alone: the device copy of the slot also holds the optimiser's step count, which the host copy does not
   // follow (sf_corr_match_renderimg binds a new flow between the iterations of one frame)
-  GFCHK(hipMemcpyAsync(&g->dev[slot].flow, &s.flow, sizeof(s.flow), hipMemcpyHostToDevice, st));
-  GFCHK(hipStreamSynchronize(st));
+  HIPCHK(hipMemcpyAsync(&g->dev[slot].flow, &s.flow, sizeof(s.flow), hipMemcpyHostToDevice, st));
+  HIPCHK(hipStreamSynchronize(st));
   return SLM_OK;
 }
 
 int slm_gf_bind_point_grad(slm_gf* g, int32_t slot, const double* grad, void* stream) {
-  if (!g) return gf_fail(SLM_ERR_INVALID, "slm_gf_bind_point_grad: null argument");
-  if (slot < 0 || slot >= (int)g->host.size()) return gf_fail(SLM_ERR_INVALID, "slm_gf_bind_point_grad: bad slot");
-  if (!g->host[slot].bound) return gf_fail(SLM_ERR_UNBOUND, "slm_gf_bind_point_grad: slm_gf_bind_frame first");
+  if (!g) return fail(SLM_ERR_INVALID, "slm_gf_bind_point_grad: null argument");
+  if (slot < 0 || slot >= (int)g->host.size()) return fail(SLM_ERR_INVALID, "slm_gf_bind_point_grad: bad slot");
+  if (!g->host[slot].bound) return fail(SLM_ERR_UNBOUND, "slm_gf_bind_point_grad: slm_gf_bind_frame first");
   hipStream_t st = (hipStream_t)stream;
   g->pgrad_host[slot] = grad;
-  GFCHK(hipMemcpyAsync(g->pgrad + slot, &g->pgrad_host[slot], sizeof(const double*), hipMemcpyHostToDevice, st));
-  GFCHK(hipStreamSynchronize(st));
+  HIPCHK(hipMemcpyAsync(g->pgrad + slot, &g->pgrad_host[slot], sizeof(const double*), hipMemcpyHostToDevice, st));
+  HIPCHK(hipStreamSynchronize(st));
   return SLM_OK;
 }
 
 int slm_gf_get_edge_points(slm_gf* g, int32_t slot, int32_t class_id, float* xy_out, int32_t max_points,
                            void* stream) {
   if (!g || slot < 0 || slot >= (int)g->host.size() || !xy_out)
-    return gf_fail(SLM_ERR_INVALID, "slm_gf_get_edge_points: bad argument");
+    return fail(SLM_ERR_INVALID, "slm_gf_get_edge_points: bad argument");
   const GfSlot& s = g->host[slot];
-  if (!s.bound || !s.sem_bound) return gf_fail(SLM_ERR_UNBOUND, "slm_gf_get_edge_points: no semantic inputs bound");
+  if (!s.bound || !s.sem_bound) return fail(SLM_ERR_UNBOUND, "slm_gf_get_edge_points: no semantic inputs bound");
   if (class_id < 0 || class_id >= s.sem.num_classes)
-    return gf_fail(SLM_ERR_INVALID, "slm_gf_get_edge_points: bad class");
+    return fail(SLM_ERR_INVALID, "slm_gf_get_edge_points: bad class");
   const int n = s.edge_off[class_id + 1] - s.edge_off[class_id];
-  if (n > max_points) return gf_fail(SLM_ERR_INVALID, "slm_gf_get_edge_points: output too small");
+  if (n > max_points) return fail(SLM_ERR_INVALID, "slm_gf_get_edge_points: output too small");
   if (n > 0)
-    GFCHK(hipMemcpyAsync(xy_out, s.edge_xy + s.edge_off[class_id], sizeof(float2) * n, hipMemcpyDeviceToDevice,
+    HIPCHK(hipMemcpyAsync(xy_out, s.edge_xy + s.edge_off[class_id], sizeof(float2) * n, hipMemcpyDeviceToDevice,
                          (hipStream_t)stream));
   return SLM_OK;
 }
 
 static int gf_dims(slm_gf* g, int first, int n, int* maxN, int* maxReg, int* maxP) {
   if (!g || first < 0 || n < 1 || first + n > (int)g->host.size())
-    return gf_fail(SLM_ERR_INVALID, "slm_gf: slot range out of bounds");
+    return fail(SLM_ERR_INVALID, "slm_gf: slot range out of bounds");
   *maxN = *maxReg = *maxP = 0;
   for (int i = first; i < first + n; ++i) {
     const GfSlot& s = g->host[i];
-    if (!s.bound) return gf_fail(SLM_ERR_UNBOUND, "slm_gf: slot used before slm_gf_bind_frame");
+    if (!s.bound) return fail(SLM_ERR_UNBOUND, "slm_gf: slot used before slm_gf_bind_frame");
     if ((g->cfg.seg_mode || g->cfg.use_bn_morph) && !s.sem_bound)
-      return gf_fail(SLM_ERR_UNBOUND, "slm_gf: semantic terms enabled but slm_gf_bind_semantic was not called");
+      return fail(SLM_ERR_UNBOUND, "slm_gf: semantic terms enabled but slm_gf_bind_semantic was not called");
     if (g->cfg.corr_mode && !s.flow)
-      return gf_fail(SLM_ERR_UNBOUND, "slm_gf: corr_mode set but slm_gf_bind_flow was not called");
+      return fail(SLM_ERR_UNBOUND, "slm_gf: corr_mode set but slm_gf_bind_flow was not called");
     if (s.f.base.K != g->host[first].f.base.K)
-      return gf_fail(SLM_ERR_UNSUPPORTED, "slm_gf: the frames of one batch must have the same num_neighbors");
+      return fail(SLM_ERR_UNSUPPORTED, "slm_gf: the frames of one batch must have the same num_neighbors");
     *maxN = std::max(*maxN, s.f.base.N);
     int reg = std::max(s.f.base.J * s.f.base.K_ED, s.f.base.J + 1);
     if (g->cfg.use_face) reg = std::max(reg, s.f.n_triangles);
@@ -1024,12 +987,12 @@ static int gf_dims(slm_gf* g, int first, int n, int* maxN, int* maxReg, int* max
 }
 
 int slm_gf_set_shard(slm_gf* g, int32_t rank, int32_t world) {
-  if (!g || world < 1 || rank < 0 || rank >= world) return gf_fail(SLM_ERR_INVALID, "slm_gf_set_shard: bad rank/world");
+  if (!g || world < 1 || rank < 0 || rank >= world) return fail(SLM_ERR_INVALID, "slm_gf_set_shard: bad rank/world");
   g->rank = rank;
   g->world = world;
   for (GfSlot& s : g->host) s.bound = 0;   // shard bounds are fixed at bind time
   hipError_t e = hipMemset(g->dev, 0, sizeof(GfSlot) * g->host.size());
-  if (e != hipSuccess) return gf_fail(SLM_ERR_HIP, hipGetErrorString(e));
+  if (e != hipSuccess) return fail(SLM_ERR_HIP, hipGetErrorString(e));
   return SLM_OK;
 }
 
@@ -1038,7 +1001,7 @@ int slm_gf_eval_morph(slm_gf* g, int32_t n_frames, void* stream) {
   int rc = gf_dims(g, 0, n_frames, &maxN, &maxReg, &maxP);
   if (rc) return rc;
   gf_enqueue_morph(g, g->dev, n_frames, maxN, (hipStream_t)stream);
-  GFCHK(hipGetLastError());
+  HIPCHK(hipGetLastError());
   return SLM_OK;
 }
 
@@ -1047,7 +1010,7 @@ int slm_gf_eval_losses(slm_gf* g, int32_t n_frames, void* stream) {
   int rc = gf_dims(g, 0, n_frames, &maxN, &maxReg, &maxP);
   if (rc) return rc;
   gf_enqueue_losses(g, g->dev, n_frames, maxN, maxReg, (hipStream_t)stream);
-  GFCHK(hipGetLastError());
+  HIPCHK(hipGetLastError());
   return SLM_OK;
 }
 
@@ -1059,7 +1022,7 @@ int slm_gf_step(slm_gf* g, int32_t n_frames, void* stream) {
   hipLaunchKernelGGL(k_gf_step, dim3((maxP + 255) / 256, n_frames), dim3(256), 0, st, g->dev, g->cfg.optimizer,
                      g->cfg.lr, 1, g->cfg.use_bn_morph, g->cfg.w_bn_morph, 0, 0);
   hipLaunchKernelGGL(k_gf_advance, dim3(n_frames), dim3(64), 0, st, g->dev, 1);
-  GFCHK(hipGetLastError());
+  HIPCHK(hipGetLastError());
   return SLM_OK;
 }
 
@@ -1067,11 +1030,11 @@ int slm_gf_get_partial(slm_gf* g, int32_t slot, double* out, void* stream) {
   int maxN, maxReg, maxP;
   int rc = gf_dims(g, slot, 1, &maxN, &maxReg, &maxP);
   if (rc) return rc;
-  if (!out) return gf_fail(SLM_ERR_INVALID, "slm_gf_get_partial: null output");
+  if (!out) return fail(SLM_ERR_INVALID, "slm_gf_get_partial: null output");
   const GfSlot& s = g->host[slot];
   hipStream_t st = (hipStream_t)stream;
-  GFCHK(hipMemcpyAsync(out, s.grad, sizeof(double) * maxP, hipMemcpyDeviceToDevice, st));
-  GFCHK(hipMemcpyAsync(out + maxP, s.terms, sizeof(double) * SLM_GF_NTERMS, hipMemcpyDeviceToDevice, st));
+  HIPCHK(hipMemcpyAsync(out, s.grad, sizeof(double) * maxP, hipMemcpyDeviceToDevice, st));
+  HIPCHK(hipMemcpyAsync(out + maxP, s.terms, sizeof(double) * SLM_GF_NTERMS, hipMemcpyDeviceToDevice, st));
   return SLM_OK;
 }
 
@@ -1079,11 +1042,11 @@ int slm_gf_set_partial(slm_gf* g, int32_t slot, const double* in, void* stream) 
   int maxN, maxReg, maxP;
   int rc = gf_dims(g, slot, 1, &maxN, &maxReg, &maxP);
   if (rc) return rc;
-  if (!in) return gf_fail(SLM_ERR_INVALID, "slm_gf_set_partial: null input");
+  if (!in) return fail(SLM_ERR_INVALID, "slm_gf_set_partial: null input");
   const GfSlot& s = g->host[slot];
   hipStream_t st = (hipStream_t)stream;
-  GFCHK(hipMemcpyAsync(s.grad, in, sizeof(double) * maxP, hipMemcpyDeviceToDevice, st));
-  GFCHK(hipMemcpyAsync(s.terms, in + maxP, sizeof(double) * SLM_GF_NTERMS, hipMemcpyDeviceToDevice, st));
+  HIPCHK(hipMemcpyAsync(s.grad, in, sizeof(double) * maxP, hipMemcpyDeviceToDevice, st));
+  HIPCHK(hipMemcpyAsync(s.terms, in + maxP, sizeof(double) * SLM_GF_NTERMS, hipMemcpyDeviceToDevice, st));
   return SLM_OK;
 }
 
@@ -1092,7 +1055,7 @@ int slm_gf_run(slm_gf* g, int32_t n_frames, void* stream) {
   int rc = gf_dims(g, 0, n_frames, &maxN, &maxReg, &maxP);
   if (rc) return rc;
   if (g->world > 1)
-    return gf_fail(SLM_ERR_UNSUPPORTED,
+    return fail(SLM_ERR_UNSUPPORTED,
                    "slm_gf_run: surfels are sharded; drive slm_gf_eval_morph / eval_losses / step with an "
                    "all-reduce of slm_gf_get_partial between them");
   hipStream_t st = (hipStream_t)stream;
@@ -1112,7 +1075,7 @@ int slm_gf_run(slm_gf* g, int32_t n_frames, void* stream) {
                        g->cfg.optimizer, g->cfg.lr, 1, g->cfg.use_bn_morph, g->cfg.w_bn_morph, fold, it);
   }
   if (n_it > 0) hipLaunchKernelGGL(k_gf_advance, dim3(n_frames), dim3(64), 0, st, g->dev, n_it);
-  GFCHK(hipGetLastError());
+  HIPCHK(hipGetLastError());
   return SLM_OK;
 }
 
@@ -1120,8 +1083,8 @@ int slm_gf_get_deform(slm_gf* g, int32_t slot, double* out, void* stream) {
   int maxN, maxReg, maxP;
   int rc = gf_dims(g, slot, 1, &maxN, &maxReg, &maxP);
   if (rc) return rc;
-  if (!out) return gf_fail(SLM_ERR_INVALID, "slm_gf_get_deform: null output");
-  GFCHK(hipMemcpyAsync(out, g->host[slot].dv, sizeof(double) * maxP, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  if (!out) return fail(SLM_ERR_INVALID, "slm_gf_get_deform: null output");
+  HIPCHK(hipMemcpyAsync(out, g->host[slot].dv, sizeof(double) * maxP, hipMemcpyDeviceToDevice, (hipStream_t)stream));
   return SLM_OK;
 }
 
@@ -1129,16 +1092,16 @@ int slm_gf_loss_grad(slm_gf* g, int32_t slot, const double* dv, double* terms, d
   int maxN, maxReg, maxP;
   int rc = gf_dims(g, slot, 1, &maxN, &maxReg, &maxP);
   if (rc) return rc;
-  if (!dv) return gf_fail(SLM_ERR_INVALID, "slm_gf_loss_grad: null dv");
+  if (!dv) return fail(SLM_ERR_INVALID, "slm_gf_loss_grad: null dv");
   hipStream_t st = (hipStream_t)stream;
   const GfSlot& s = g->host[slot];
-  GFCHK(hipMemcpyAsync(s.dv, dv, sizeof(double) * maxP, hipMemcpyDeviceToDevice, st));
+  HIPCHK(hipMemcpyAsync(s.dv, dv, sizeof(double) * maxP, hipMemcpyDeviceToDevice, st));
   gf_enqueue_eval(g, g->dev + slot, 1, maxN, maxReg, st);
   hipLaunchKernelGGL(k_gf_step, dim3((maxP + 255) / 256, 1), dim3(256), 0, st, g->dev + slot, g->cfg.optimizer,
                      g->cfg.lr, 0, g->cfg.use_bn_morph, g->cfg.w_bn_morph, 0, 0);
-  if (terms) GFCHK(hipMemcpyAsync(terms, s.terms, sizeof(double) * SLM_GF_NTERMS, hipMemcpyDeviceToDevice, st));
-  if (grad) GFCHK(hipMemcpyAsync(grad, s.grad, sizeof(double) * maxP, hipMemcpyDeviceToDevice, st));
-  GFCHK(hipGetLastError());
+  if (terms) HIPCHK(hipMemcpyAsync(terms, s.terms, sizeof(double) * SLM_GF_NTERMS, hipMemcpyDeviceToDevice, st));
+  if (grad) HIPCHK(hipMemcpyAsync(grad, s.grad, sizeof(double) * maxP, hipMemcpyDeviceToDevice, st));
+  HIPCHK(hipGetLastError());
   return SLM_OK;
 }
 
@@ -1157,8 +1120,8 @@ int slm_apply_update_gf_f64(int32_t N, int32_t J, int32_t K, double* sf_points, 
 }  // extern "C"
 
 int gf_render_slot(slm_gf* g, int32_t slot, GfSlot** dev, int32_t* n_surfels) {
-  if (!g || slot < 0 || slot >= (int)g->host.size()) return gf_fail(SLM_ERR_INVALID, "slm_gf_render: bad slot");
-  if (!g->host[slot].bound) return gf_fail(SLM_ERR_UNBOUND, "slm_gf_render: slm_gf_bind_frame first");
+  if (!g || slot < 0 || slot >= (int)g->host.size()) return fail(SLM_ERR_INVALID, "slm_gf_render: bad slot");
+  if (!g->host[slot].bound) return fail(SLM_ERR_UNBOUND, "slm_gf_render: slm_gf_bind_frame first");
   *dev = g->dev + slot;
   *n_surfels = g->host[slot].f.base.N;
   return SLM_OK;

@@ -13,24 +13,10 @@
 #include <cstring>
 #include <rocprim/rocprim.hpp>
 
-#include <string>
-
 #include "slm_common.h"
-
-void slm_set_error_text(const char* msg);   // slm_api.hip
+#include "slm_host.h"
 
 namespace {
-
-#define GCHK(expr)                                                        \
-  do {                                                                    \
-    hipError_t e_ = (expr);                                               \
-    if (e_ != hipSuccess) {                                               \
-      slm_set_error_text((std::string(#expr) + ": " + hipGetErrorString(e_)).c_str()); \
-      for (void* p_ : owned)                                              \
-        if (p_) (void)hipFree(p_);                                        \
-      return SLM_ERR_HIP;                                                 \
-    }                                                                     \
-  } while (0)
 
 struct Grid {
   int H, W, step, gw, gh;   // gw x gh grid points: u = 0, step, ... < W-1; v likewise < H-1
@@ -208,46 +194,35 @@ __global__ void __launch_bounds__(256) k_gr_fix_nan(int J, double* __restrict__ 
 
 }  // namespace
 
-static int graph_init_impl(int32_t H, int32_t W, int32_t step, const uint8_t* valid, const int32_t* index_map,
-                           const double* points, const double* norms, const slm_graph_outputs* out, GrSem sm,
-                           int32_t* counts_host, void* stream) {
-  if (H < 2 || W < 2 || step < 1 || !valid || !index_map || !points || !norms || !out || !out->points || !out->norms ||
-      !out->radii || !out->edge_index || !out->edges_lens || !out->triangles || !out->triangles_areas) {
-    slm_set_error_text("slm_graph_init: bad argument");
-    return SLM_ERR_INVALID;
-  }
-  Grid g{H, W, step, (W - 1 + step - 1) / step, (H - 1 + step - 1) / step};
+// the stages of a graph construction on grid g; what it allocates is the caller's to free (owned), however it returns
+static int graph_build(const Grid& g, const uint8_t* valid, const int32_t* index_map, const double* points,
+                       const double* norms, const slm_graph_outputs* out, GrSem sm, int32_t* counts_host, hipStream_t st,
+                       void* (&owned)[8]) {
   const int cells = g.gw * g.gh;
-  if (cells < 1 || out->cap_nodes < cells) {
-    slm_set_error_text("slm_graph_init: cap_nodes is smaller than the anchor grid");
-    return SLM_ERR_INVALID;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  void* owned[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   int32_t *flag = nullptr, *pos = nullptr, *node_of = nullptr, *cell_of = nullptr, *eflag = nullptr, *epos = nullptr;
   double* acc = nullptr;
   void* tmp = nullptr;
   const size_t nmax = 4 * (size_t)cells;
-  GCHK(hipMalloc((void**)&flag, sizeof(int32_t) * 6 * (size_t)cells)); owned[0] = flag;
-  GCHK(hipMalloc((void**)&pos, sizeof(int32_t) * 6 * (size_t)cells)); owned[1] = pos;
-  GCHK(hipMalloc((void**)&node_of, sizeof(int32_t) * (size_t)cells)); owned[2] = node_of;
-  GCHK(hipMalloc((void**)&cell_of, sizeof(int32_t) * (size_t)cells)); owned[3] = cell_of;
-  GCHK(hipMalloc((void**)&eflag, sizeof(int32_t) * 6 * (size_t)cells)); owned[4] = eflag;
-  GCHK(hipMalloc((void**)&epos, sizeof(int32_t) * 6 * (size_t)cells)); owned[5] = epos;
-  GCHK(hipMalloc((void**)&acc, sizeof(double) * 2)); owned[6] = acc;
+  HIPCHK(hipMalloc((void**)&flag, sizeof(int32_t) * 6 * (size_t)cells)); owned[0] = flag;
+  HIPCHK(hipMalloc((void**)&pos, sizeof(int32_t) * 6 * (size_t)cells)); owned[1] = pos;
+  HIPCHK(hipMalloc((void**)&node_of, sizeof(int32_t) * (size_t)cells)); owned[2] = node_of;
+  HIPCHK(hipMalloc((void**)&cell_of, sizeof(int32_t) * (size_t)cells)); owned[3] = cell_of;
+  HIPCHK(hipMalloc((void**)&eflag, sizeof(int32_t) * 6 * (size_t)cells)); owned[4] = eflag;
+  HIPCHK(hipMalloc((void**)&epos, sizeof(int32_t) * 6 * (size_t)cells)); owned[5] = epos;
+  HIPCHK(hipMalloc((void**)&acc, sizeof(double) * 2)); owned[6] = acc;
   size_t bytes = 0;
-  GCHK(rocprim::exclusive_scan(nullptr, bytes, flag, pos, 0, nmax, rocprim::plus<int32_t>(), st));
-  GCHK(hipMalloc(&tmp, bytes)); owned[7] = tmp;
+  HIPCHK(rocprim::exclusive_scan(nullptr, bytes, flag, pos, 0, nmax, rocprim::plus<int32_t>(), st));
+  HIPCHK(hipMalloc(&tmp, bytes)); owned[7] = tmp;
   const dim3 blk(256), gc((cells + 255) / 256);
   // anchors -> node numbers
   hipLaunchKernelGGL(k_gr_anchor, gc, blk, 0, st, g, valid, flag);
   size_t b1 = bytes;
-  GCHK(rocprim::exclusive_scan(tmp, b1, flag, pos, 0, (size_t)cells, rocprim::plus<int32_t>(), st));
+  HIPCHK(rocprim::exclusive_scan(tmp, b1, flag, pos, 0, (size_t)cells, rocprim::plus<int32_t>(), st));
   hipLaunchKernelGGL(k_gr_nodes, gc, blk, 0, st, g, flag, pos, index_map, points, norms, node_of, *out, sm);
   int32_t last[2];
-  GCHK(hipMemcpyAsync(&last[0], pos + cells - 1, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  GCHK(hipMemcpyAsync(&last[1], flag + cells - 1, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  GCHK(hipStreamSynchronize(st));
+  HIPCHK(hipMemcpyAsync(&last[0], pos + cells - 1, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(&last[1], flag + cells - 1, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
   const int J = last[0] + last[1];
   int E = 0, F = 0;
   if (J > 0) {
@@ -257,32 +232,46 @@ static int graph_init_impl(int32_t H, int32_t W, int32_t step, const uint8_t* va
     int32_t* tpos = epos + 4 * (size_t)cells;
     hipLaunchKernelGGL(k_gr_cell_flags, gj, blk, 0, st, g, node_of, J, cell_of, eflag, tflag, sm);
     b1 = bytes;
-    GCHK(rocprim::exclusive_scan(tmp, b1, eflag, epos, 0, 4 * (size_t)J, rocprim::plus<int32_t>(), st));
+    HIPCHK(rocprim::exclusive_scan(tmp, b1, eflag, epos, 0, 4 * (size_t)J, rocprim::plus<int32_t>(), st));
     b1 = bytes;
-    GCHK(rocprim::exclusive_scan(tmp, b1, tflag, tpos, 0, 2 * (size_t)J, rocprim::plus<int32_t>(), st));
+    HIPCHK(rocprim::exclusive_scan(tmp, b1, tflag, tpos, 0, 2 * (size_t)J, rocprim::plus<int32_t>(), st));
     hipLaunchKernelGGL(k_gr_cells, gj, blk, 0, st, g, node_of, J, cell_of, eflag, epos, tflag, tpos, *out);
-    GCHK(hipMemsetAsync(acc, 0, sizeof(double) * 2, st));
+    HIPCHK(hipMemsetAsync(acc, 0, sizeof(double) * 2, st));
     hipLaunchKernelGGL(k_gr_radii, gj, blk, 0, st, g, node_of, J, cell_of, eflag, epos, *out, acc,
                        reinterpret_cast<int32_t*>(acc + 1));
     hipLaunchKernelGGL(k_gr_fix_nan, gj, blk, 0, st, J, out->radii, acc, reinterpret_cast<const int32_t*>(acc + 1));
     int32_t le[4];
-    GCHK(hipMemcpyAsync(&le[0], epos + 4 * (size_t)J - 1, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    GCHK(hipMemcpyAsync(&le[1], eflag + 4 * (size_t)J - 1, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    GCHK(hipMemcpyAsync(&le[2], tpos + 2 * (size_t)J - 1, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    GCHK(hipMemcpyAsync(&le[3], tflag + 2 * (size_t)J - 1, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    GCHK(hipStreamSynchronize(st));
+    HIPCHK(hipMemcpyAsync(&le[0], epos + 4 * (size_t)J - 1, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&le[1], eflag + 4 * (size_t)J - 1, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&le[2], tpos + 2 * (size_t)J - 1, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&le[3], tflag + 2 * (size_t)J - 1, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
     E = le[0] + le[1];
     F = le[2] + le[3];
   }
-  GCHK(hipGetLastError());
+  HIPCHK(hipGetLastError());
   if (counts_host) {
     counts_host[0] = J;
     counts_host[1] = E;
     counts_host[2] = F;
   }
+  return SLM_OK;
+}
+
+static int graph_init_impl(int32_t H, int32_t W, int32_t step, const uint8_t* valid, const int32_t* index_map,
+                           const double* points, const double* norms, const slm_graph_outputs* out, GrSem sm,
+                           int32_t* counts_host, void* stream) {
+  if (H < 2 || W < 2 || step < 1 || !valid || !index_map || !points || !norms || !out || !out->points || !out->norms ||
+      !out->radii || !out->edge_index || !out->edges_lens || !out->triangles || !out->triangles_areas)
+    return fail(SLM_ERR_INVALID, "slm_graph_init: bad argument");
+  const Grid g{H, W, step, (W - 1 + step - 1) / step, (H - 1 + step - 1) / step};
+  if (g.gw * g.gh < 1 || out->cap_nodes < g.gw * g.gh)
+    return fail(SLM_ERR_INVALID, "slm_graph_init: cap_nodes is smaller than the anchor grid");
+  void* owned[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  const int rc = graph_build(g, valid, index_map, points, norms, out, sm, counts_host, (hipStream_t)stream, owned);
   for (void* p : owned)
     if (p) (void)hipFree(p);
-  return SLM_OK;
+  return rc;
 }
 
 extern "C" int slm_graph_init(int32_t H, int32_t W, int32_t step, const uint8_t* valid, const int32_t* index_map,
@@ -296,10 +285,8 @@ extern "C" int slm_graph_init_semantic(int32_t H, int32_t W, int32_t step, const
                                        const double* points, const double* norms, int32_t num_classes,
                                        const double* seg_conf, int32_t prune_class_edges, const slm_graph_outputs* out,
                                        int32_t* node_seg, double* node_seg_conf, int32_t* counts_host, void* stream) {
-  if (num_classes < 1 || num_classes > SLM_MAX_CLASSES || !seg_conf || !node_seg || !node_seg_conf) {
-    slm_set_error_text("slm_graph_init_semantic: bad argument (1..4 classes, seg_conf and both node outputs)");
-    return SLM_ERR_INVALID;
-  }
+  if (num_classes < 1 || num_classes > SLM_MAX_CLASSES || !seg_conf || !node_seg || !node_seg_conf)
+    return fail(SLM_ERR_INVALID, "slm_graph_init_semantic: bad argument (1..4 classes, seg_conf and both node outputs)");
   return graph_init_impl(H, W, step, valid, index_map, points, norms, out,
                          GrSem{num_classes, prune_class_edges ? 1 : 0, seg_conf, node_seg, node_seg_conf}, counts_host,
                          stream);

@@ -1,0 +1,66 @@
+// slm_launch.h -- the launch functions of the LM solver's kernels, declared once, with their default arguments:
+// slm_api.hip calls them; the file that holds the kernels defines them and includes this too, so its definitions are
+// compiled against these declarations (a drifted return type or a repeated default argument does not compile; a
+// drifted parameter list is still only caught when the library is loaded).
+#pragma once
+#include "slm_common.h"
+
+// slm_data.hip
+void launch_data_grad(const FrameDev*, int, int, int, double, hipStream_t);
+void launch_data_grad_pairs(const FrameDev*, int, int, int, double, hipStream_t);
+void launch_data_loss(const FrameDev*, int, int, int, double, int, hipStream_t);
+void launch_data_resid(const FrameDev*, int, int, int, double, double*, uint8_t*, int32_t*, hipStream_t);
+
+// slm_data_v1.hip
+void launch_data_gram(const FrameDev*, int, int, double, int, hipStream_t, const int* reuse = nullptr);
+void launch_begin_and_gram(const FrameDev*, int, int, double, hipStream_t, const int* reuse, int dag_cut);
+void launch_data_eval(const FrameDev*, int, int, double, int mode, hipStream_t, const int* reuse = nullptr);
+void launch_band_assemble(const FrameDev*, int, int, hipStream_t);
+
+// slm_front.hip
+void launch_front_assemble(const FrameDev*, int, int, hipStream_t);
+void launch_pair_reduce(const FrameDev*, int, int, hipStream_t);
+void launch_pair_scatter(const FrameDev*, int, int, hipStream_t);
+void launch_reg_grad_nd(const FrameDev*, int, int, int, double, int, double, hipStream_t);
+void launch_front_load_rhs(const FrameDev*, int, int, hipStream_t);
+void launch_iter_begin_nd(const FrameDev*, int, hipStream_t, const int* reuse, int dag_cut);
+void launch_front_solve(const FrameDev*, int, const NDLevelSched*, int, double, hipStream_t);
+void launch_front_levels(const FrameDev*, int, const NDLevelSched*, int, int, int, double, hipStream_t);
+
+// slm_dag.hip
+int launch_front_solve_dag(const FrameDev*, int, int, double, hipStream_t, int cut, bool reset, bool check);
+int dag_device_setup(int dev, int* xcd8_out);
+int dag_last_mode();
+hipError_t set_dag_timeout_ticks(long long);
+void launch_dag_abort_check(const FrameDev*, int, hipStream_t);
+
+// slm_band.hip
+void launch_bandwidth(const slm_frame&, int*, hipStream_t);
+void launch_band_solve(const FrameDev*, int, int, int, double, hipStream_t);
+void launch_band_to_dense(const FrameDev*, int, double*, hipStream_t);
+void launch_dense_to_band(const FrameDev*, const double*, const double*, hipStream_t);
+
+// slm_reg.hip
+void launch_reg_grad(const FrameDev*, int, int, int, double, int, double, hipStream_t);
+void launch_after_solve(const FrameDev*, int, int, int, int, double, int, double, int, hipStream_t);
+void launch_reg_loss(const FrameDev*, int, int, int, double, int, double, int, hipStream_t);
+
+// slm_misc.hip
+void launch_init_slot(const FrameDev*, int, int, const slm_config&, hipStream_t);
+void launch_iter_begin(const FrameDev*, int, hipStream_t);
+void launch_pack_nodes(const FrameDev*, int, int, hipStream_t);
+void launch_make_trial(const FrameDev*, int, int, hipStream_t);
+void launch_pack_target(int, const float*, const float*, float4*, hipStream_t);
+void launch_pack_target_px(int, const int*, const uint8_t*, const float*, const float*, float4*, hipStream_t);
+void launch_accept(const FrameDev*, int, int, int, int, hipStream_t, int* reuse = nullptr, int eval_pass = 0);
+void launch_loss_out(const FrameDev*, int, int, double*, hipStream_t);
+void launch_zero_reg_part(const FrameDev*, int, int, hipStream_t);
+void launch_update(int, int, int, float*, float*, const int*, const float*, float*, float*, const double*, hipStream_t);
+void launch_update64(int, int, int, double*, double*, const int*, const double*, double*, double*, const double*,
+                     hipStream_t);
+void launch_knn(int, int, int, int, const float*, const float*, int*, float*, hipStream_t);
+void launch_knn64(int, int, int, int, const double*, const double*, const int*, const int*, int*, double*, int*,
+                  hipStream_t);
+void launch_knn_weights64(int, int, int, const int*, const double*, const double*, int, const double*, const double*,
+                          double*, uint8_t*, hipStream_t);
+void launch_knn_weights(int, int, int, const int*, const float*, const float*, float*, uint8_t*, hipStream_t);

@@ -1,6 +1,7 @@
 // slm_misc.hip -- LM loop state kernels (accept/reject on the device), Surfels.update,
 // and the KNN feeder.
 #include "slm_common.h"
+#include "slm_launch.h"
 
 // ---------------------------------------------------------------------------------
 // beta <- identity, state <- initial (reference super/LM.py:81-91)

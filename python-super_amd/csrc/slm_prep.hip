@@ -21,6 +21,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "slm_common.h"
+#include "slm_host.h"
 #include "slm_prep.h"
 
 namespace {
@@ -981,34 +982,14 @@ __global__ void __launch_bounds__(256) kb_rec_sort(int J, const int* __restrict_
     if (v[i]) blk2_start[u0 + hs[i]] = base + i;
 }
 
-#define PCHK(expr)                      \
-  do {                                  \
-    hipError_t e_ = (expr);             \
-    if (e_ != hipSuccess) return e_;    \
-  } while (0)
-
-// One grow-only device array: freed and allocated anew with 12 % + 64 elements of head-room.  (Not the `grow` of
-// slm_api.hip / slm_sem.hip: those count into slm_debug_counters and round differently.)
-hipError_t grow_raw(void** p, size_t* cap, size_t need, size_t esz) {
-  if (need <= *cap) return hipSuccess;
-  if (*p) {
-    PCHK(hipFree(*p));
-    *p = nullptr;
-    *cap = 0;
-  }
-  const size_t want = need + need / 8 + 64;
-  PCHK(hipMalloc(p, want * esz));
-  *cap = want;
-  return hipSuccess;
-}
-
 // What a struct owns: one row per device array -- where its pointer and the capacity it is recorded under sit in the
 // struct, and its element size.  Arrays recorded under the same capacity are a GROUP.  Growth (grow_group) and release
 // (free_arrays) both walk the struct's table, so an array that can be grown is also freed.
 struct DevArray { size_t ptr, cap, esz; };
 #define ARR(S, name, cap) {offsetof(S, name), offsetof(S, cap), sizeof(*((S*)nullptr)->name)}
 
-// Grows the group recorded at cap_off as a unit: every member its own allocation, in table order.  While the members
+// Grows the group recorded at cap_off as a unit: every member its own allocation (slm_host.h grow, with 12 % + 64
+// elements of head-room; nothing here counts into slm_debug_counters), in table order.  While the members
 // differ the recorded capacity is 0, and a failure leaves it there: never more than what every member really has (the
 // next bind then frees and allocates the whole group again).
 template <size_t M>
@@ -1021,7 +1002,7 @@ hipError_t grow_group(void* s, const DevArray (&tab)[M], size_t cap_off, size_t 
   for (const DevArray& a : tab)
     if (a.cap == cap_off) {
       c = old;
-      PCHK(grow_raw(reinterpret_cast<void**>((char*)s + a.ptr), &c, need, a.esz));
+      HIPRET(grow(*reinterpret_cast<void**>((char*)s + a.ptr), c, need, need + need / 8 + 64, a.esz));
     }
   cap = c;
   return hipSuccess;
@@ -1139,8 +1120,8 @@ template <typename Query>
 static hipError_t ensure_scratch(PrepBuffers* p, PrimScratch& s, size_t a, size_t b, size_t c, size_t slack, Query query) {
   if (s.buf && s.q[0] == a && s.q[1] == b && s.q[2] == c) return hipSuccess;
   size_t need = 0;
-  PCHK(query(need));
-  PCHK(grow_group(p, kPrepArrays, (size_t)((char*)&s.cap - (char*)p), need + need / 4 + slack));
+  HIPRET(query(need));
+  HIPRET(grow_group(p, kPrepArrays, (size_t)((char*)&s.cap - (char*)p), need + need / 4 + slack));
   s.q[0] = a;
   s.q[1] = b;
   s.q[2] = c;
@@ -1149,19 +1130,19 @@ static hipError_t ensure_scratch(PrepBuffers* p, PrimScratch& s, size_t a, size_
 
 // The first n ints of the status block, on the host when this returns.
 static hipError_t read_scal(PrepBuffers* p, int n, hipStream_t st) {
-  PCHK(hipMemcpyAsync(p->scal_host, p->scal, n * sizeof(int), hipMemcpyDeviceToHost, st));
+  HIPRET(hipMemcpyAsync(p->scal_host, p->scal, n * sizeof(int), hipMemcpyDeviceToHost, st));
   return hipStreamSynchronize(st);
 }
 
 hipError_t prep_check_knn(PrepBuffers* p, const slm_frame& f, bool* bad, hipStream_t st) {
   *bad = false;
   if (f.N <= 0) return hipSuccess;
-  PCHK(hipMemsetAsync(p->scal + SC_BAD_KNN, 0, sizeof(int), st));
+  HIPRET(hipMemsetAsync(p->scal + SC_BAD_KNN, 0, sizeof(int), st));
   const long long n_ed = (long long)f.J * f.K_ED, n_thr = n_ed > f.N ? n_ed : (long long)f.N;
   hipLaunchKernelGGL(k_check_knn, dim3((unsigned)((n_thr + 255) / 256)), dim3(256), 0, st, f.N, f.K, f.J, f.sf_knn_idx, n_ed,
                      f.ed_knn_idx, p->scal + SC_BAD_KNN);
-  PCHK(hipMemcpyAsync(p->scal_host + SC_BAD_KNN, p->scal + SC_BAD_KNN, sizeof(int), hipMemcpyDeviceToHost, st));
-  PCHK(hipStreamSynchronize(st));
+  HIPRET(hipMemcpyAsync(p->scal_host + SC_BAD_KNN, p->scal + SC_BAD_KNN, sizeof(int), hipMemcpyDeviceToHost, st));
+  HIPRET(hipStreamSynchronize(st));
   *bad = p->scal_host[SC_BAD_KNN] != 0;
   return hipSuccess;
 }
@@ -1194,19 +1175,19 @@ static size_t hinted_tuples(size_t N, int hint) {
 // The buffers of a plan for bounds b: all sixteen but wgslab (finish_v1: its size is a result of the build).
 static hipError_t grow_plan(V1Plan& plan, const V1Bounds& b, bool state_f64) {
   const size_t esz = state_f64 ? 2 : 1;   // s_pts / s_w are sized in floats; a float64 state needs twice that
-  PCHK(GROW(&plan, kPlanArrays, cap_pts, esz * 3 * b.pos_bound));
-  PCHK(GROW(&plan, kPlanArrays, cap_idx, 4 * b.pos_bound));
-  PCHK(GROW(&plan, kPlanArrays, cap_w, esz * 4 * b.pos_bound));
-  PCHK(GROW(&plan, kPlanArrays, cap_grp, b.pos_bound / 4));
-  PCHK(GROW(&plan, kPlanArrays, cap_runs, 4 * b.runs_bound));
-  PCHK(GROW(&plan, kPlanArrays, cap_rchunk, b.runs_bound));
-  PCHK(GROW(&plan, kPlanArrays, cap_slab, (size_t)SLM_SLAB_STRIDE * b.runs_bound));
-  PCHK(GROW(&plan, kPlanArrays, cap_bkey, b.n_entries));
-  PCHK(GROW(&plan, kPlanArrays, cap_bstart, b.n_entries + 1));
-  PCHK(GROW(&plan, kPlanArrays, cap_bentry, b.n_entries));
-  PCHK(GROW(&plan, kPlanArrays, cap_wg, b.n_wg));   // wg_first, wg_last
-  PCHK(GROW(&plan, kPlanArrays, cap_lidx, 10 * b.runs_bound));
-  PCHK(GROW(&plan, kPlanArrays, cap_b2start, b.n_entries + 1));
+  HIPRET(GROW(&plan, kPlanArrays, cap_pts, esz * 3 * b.pos_bound));
+  HIPRET(GROW(&plan, kPlanArrays, cap_idx, 4 * b.pos_bound));
+  HIPRET(GROW(&plan, kPlanArrays, cap_w, esz * 4 * b.pos_bound));
+  HIPRET(GROW(&plan, kPlanArrays, cap_grp, b.pos_bound / 4));
+  HIPRET(GROW(&plan, kPlanArrays, cap_runs, 4 * b.runs_bound));
+  HIPRET(GROW(&plan, kPlanArrays, cap_rchunk, b.runs_bound));
+  HIPRET(GROW(&plan, kPlanArrays, cap_slab, (size_t)SLM_SLAB_STRIDE * b.runs_bound));
+  HIPRET(GROW(&plan, kPlanArrays, cap_bkey, b.n_entries));
+  HIPRET(GROW(&plan, kPlanArrays, cap_bstart, b.n_entries + 1));
+  HIPRET(GROW(&plan, kPlanArrays, cap_bentry, b.n_entries));
+  HIPRET(GROW(&plan, kPlanArrays, cap_wg, b.n_wg));   // wg_first, wg_last
+  HIPRET(GROW(&plan, kPlanArrays, cap_lidx, 10 * b.runs_bound));
+  HIPRET(GROW(&plan, kPlanArrays, cap_b2start, b.n_entries + 1));
   return GROW(&plan, kPlanArrays, cap_b2entry, b.n_entries);
 }
 
@@ -1238,7 +1219,7 @@ static hipError_t finish_v1(PrepBuffers* p, V1Plan& plan, int state, V1Sizes* ou
   out->n_runs = sh[SC_NRUNS];
   out->n_wblk = sh[SC_NWBLK];
   out->max_wblk_per_wg = sh[SC_MAXWBLK];
-  PCHK(GROW(&plan, kPlanArrays, cap_wgslab, (size_t)SLM_WREC * (out->n_wblk + 1)));
+  HIPRET(GROW(&plan, kPlanArrays, cap_wgslab, (size_t)SLM_WREC * (out->n_wblk + 1)));
   return hipGetLastError();
 }
 
@@ -1250,14 +1231,14 @@ static hipError_t legacy_scratch(PrepBuffers* p, size_t N, hipStream_t st) {
     unsigned long long* k64 = nullptr;
     unsigned* k32 = nullptr;
     int* v = nullptr;
-    PCHK(rocprim::radix_sort_pairs(nullptr, b[0], k64, k64, v, v, N, 0, 64, st));
-    PCHK(rocprim::run_length_encode(nullptr, b[1], k64, N, k64, v, v, st));
-    PCHK(rocprim::exclusive_scan(nullptr, b[2], v, v, 0, cap_t, rocprim::plus<int>(), st));
-    PCHK(rocprim::radix_sort_pairs(nullptr, b[3], k32, k32, v, v, cap_e, 0, 32, st));
-    PCHK(rocprim::run_length_encode(nullptr, b[4], k32, cap_e, k32, v, v, st));
-    PCHK(rocprim::exclusive_scan(nullptr, b[5], v, v, 0, cap_e, rocprim::plus<int>(), st));
-    PCHK(rocprim::radix_sort_pairs(nullptr, b[6], k64, k64, v, v, cap_e, 0, 64, st));
-    PCHK(rocprim::run_length_encode(nullptr, b[7], k64, cap_e, k64, v, v, st));
+    HIPRET(rocprim::radix_sort_pairs(nullptr, b[0], k64, k64, v, v, N, 0, 64, st));
+    HIPRET(rocprim::run_length_encode(nullptr, b[1], k64, N, k64, v, v, st));
+    HIPRET(rocprim::exclusive_scan(nullptr, b[2], v, v, 0, cap_t, rocprim::plus<int>(), st));
+    HIPRET(rocprim::radix_sort_pairs(nullptr, b[3], k32, k32, v, v, cap_e, 0, 32, st));
+    HIPRET(rocprim::run_length_encode(nullptr, b[4], k32, cap_e, k32, v, v, st));
+    HIPRET(rocprim::exclusive_scan(nullptr, b[5], v, v, 0, cap_e, rocprim::plus<int>(), st));
+    HIPRET(rocprim::radix_sort_pairs(nullptr, b[6], k64, k64, v, v, cap_e, 0, 64, st));
+    HIPRET(rocprim::run_length_encode(nullptr, b[7], k64, cap_e, k64, v, v, st));
     need = *std::max_element(b, b + 8);
     return hipSuccess;
   });
@@ -1276,12 +1257,12 @@ static hipError_t legacy_layout(PrepBuffers* p, const slm_frame& f, V1Plan& plan
   const size_t nt = b.nt, n_entries = b.n_entries;
   const dim3 gt((nt + 255) / 256), blk(256);
   hipLaunchKernelGGL(k_padded_counts, gt, blk, 0, st, p->scal, p->tcount, p->pc);
-  PCHK(legacy_scratch(p, (size_t)f.N, st));
+  HIPRET(legacy_scratch(p, (size_t)f.N, st));
   size_t bs = p->tmp.cap;
-  PCHK(rocprim::exclusive_scan(p->tmp.buf, bs, p->tcount, p->tstart, 0, nt, rocprim::plus<int>(), st));
-  PCHK(rocprim::exclusive_scan(p->tmp.buf, bs, p->pc, p->pstart, 0, nt, rocprim::plus<int>(), st));
+  HIPRET(rocprim::exclusive_scan(p->tmp.buf, bs, p->tcount, p->tstart, 0, nt, rocprim::plus<int>(), st));
+  HIPRET(rocprim::exclusive_scan(p->tmp.buf, bs, p->pc, p->pstart, 0, nt, rocprim::plus<int>(), st));
   hipLaunchKernelGGL(k_run_counts, gt, blk, 0, st, p->scal, p->pstart, p->pc, p->nruns);
-  PCHK(rocprim::exclusive_scan(p->tmp.buf, bs, p->nruns, p->rstart, 0, nt, rocprim::plus<int>(), st));
+  HIPRET(rocprim::exclusive_scan(p->tmp.buf, bs, p->nruns, p->rstart, 0, nt, rocprim::plus<int>(), st));
   hipLaunchKernelGGL(k_totals, dim3(1), dim3(1), 0, st, p->scal, p->pstart, p->pc, p->rstart, p->nruns);
   hipLaunchKernelGGL(k_fill_sorted, dim3((b.pos_bound + 255) / 256), blk, 0, st, (int)b.pos_bound, p->scal, f,
                      p->tkeys, p->tcount, p->tstart, p->pstart, p->rstart, p->sids, plan.s_pts,
@@ -1289,12 +1270,12 @@ static hipError_t legacy_layout(PrepBuffers* p, const slm_frame& f, V1Plan& plan
   hipLaunchKernelGGL(k_pairs, dim3((b.runs_bound + 255) / 256), blk, 0, st, (int)b.runs_bound, p->scal, f.J,
                      plan.run_nodes, p->pkeys, p->pvals);
   size_t b3 = p->tmp.cap, b4 = p->tmp.cap, b5 = p->tmp.cap;
-  PCHK(rocprim::radix_sort_pairs(p->tmp.buf, b3, p->pkeys, p->spkeys, p->pvals, plan.blk_entry, n_entries, 0,
+  HIPRET(rocprim::radix_sort_pairs(p->tmp.buf, b3, p->pkeys, p->spkeys, p->pvals, plan.blk_entry, n_entries, 0,
                                  pair_key_bits(f.J), st));
-  PCHK(rocprim::run_length_encode(p->tmp.buf, b4, p->spkeys, n_entries, p->ukeys, p->bcount, p->scal + SC_NUQ, st));
+  HIPRET(rocprim::run_length_encode(p->tmp.buf, b4, p->spkeys, n_entries, p->ukeys, p->bcount, p->scal + SC_NUQ, st));
   // scan / copy over the full bound: entries past the unique count are never read
-  PCHK(rocprim::exclusive_scan(p->tmp.buf, b5, p->bcount, plan.blk_start, 0, n_entries, rocprim::plus<int>(), st));
-  PCHK(hipMemcpyAsync(plan.blk_key, p->ukeys, sizeof(unsigned) * n_entries, hipMemcpyDeviceToDevice, st));
+  HIPRET(rocprim::exclusive_scan(p->tmp.buf, b5, p->bcount, plan.blk_start, 0, n_entries, rocprim::plus<int>(), st));
+  HIPRET(hipMemcpyAsync(plan.blk_key, p->ukeys, sizeof(unsigned) * n_entries, hipMemcpyDeviceToDevice, st));
   hipLaunchKernelGGL(k_totals2, dim3(1), dim3(1), 0, st, p->scal, p->ukeys, plan.blk_start, (int)n_entries);
   return hipSuccess;
 }
@@ -1303,17 +1284,17 @@ static hipError_t legacy_layout(PrepBuffers* p, const slm_frame& f, V1Plan& plan
 static hipError_t legacy_records(PrepBuffers* p, const slm_frame& f, V1Plan& plan, const V1Bounds& b, hipStream_t st) {
   const size_t n_entries = b.n_entries, n_wg = b.n_wg;
   const dim3 blk(256), ge((n_entries + 255) / 256);
-  PCHK(hipMemsetAsync(p->scal + SC_NWUQ, 0, 3 * sizeof(int), st));   // SC_NWUQ, SC_NWBLK, SC_MAXWBLK
-  PCHK(hipMemsetAsync(plan.wg_first, 0, n_wg * sizeof(int), st));
-  PCHK(hipMemsetAsync(plan.wg_last, 0xFF, n_wg * sizeof(int), st));   // -1
+  HIPRET(hipMemsetAsync(p->scal + SC_NWUQ, 0, 3 * sizeof(int), st));   // SC_NWUQ, SC_NWBLK, SC_MAXWBLK
+  HIPRET(hipMemsetAsync(plan.wg_first, 0, n_wg * sizeof(int), st));
+  HIPRET(hipMemsetAsync(plan.wg_last, 0xFF, n_wg * sizeof(int), st));   // -1
   hipLaunchKernelGGL(k_pairs2, dim3((b.runs_bound + 255) / 256), blk, 0, st, (int)b.runs_bound, p->scal, f.J,
                      plan.run_nodes, plan.run_chunk, p->wkeys, p->wvals);
   size_t c1 = p->tmp.cap, c2 = p->tmp.cap, c3 = p->tmp.cap, c4 = p->tmp.cap, c5 = p->tmp.cap;
   unsigned wbits = 1;   // a live key's workgroup is < n_wg <= 2^wbits - 1; the padding key ~0 sorts last
   while (wbits < 32 && (1ull << wbits) <= (unsigned long long)n_wg) ++wbits;
-  PCHK(rocprim::radix_sort_pairs(p->tmp.buf, c1, p->wkeys, p->swkeys, p->wvals, p->swvals, n_entries, 0, 32 + wbits, st));
-  PCHK(rocprim::run_length_encode(p->tmp.buf, c2, p->swkeys, n_entries, p->uwkeys, p->wcount, p->scal + SC_NWUQ, st));
-  PCHK(rocprim::exclusive_scan(p->tmp.buf, c3, p->wcount, p->wstart, 0, n_entries, rocprim::plus<int>(), st));
+  HIPRET(rocprim::radix_sort_pairs(p->tmp.buf, c1, p->wkeys, p->swkeys, p->wvals, p->swvals, n_entries, 0, 32 + wbits, st));
+  HIPRET(rocprim::run_length_encode(p->tmp.buf, c2, p->swkeys, n_entries, p->uwkeys, p->wcount, p->scal + SC_NWUQ, st));
+  HIPRET(rocprim::exclusive_scan(p->tmp.buf, c3, p->wcount, p->wstart, 0, n_entries, rocprim::plus<int>(), st));
   hipLaunchKernelGGL(k_wg_bounds, ge, blk, 0, st, (int)n_entries, p->scal, p->uwkeys, plan.wg_first, plan.wg_last,
                      p->pk2, p->pv2);
   hipLaunchKernelGGL(k_wg_max, dim3((n_wg + 255) / 256), blk, 0, st, (int)n_wg, plan.wg_first, plan.wg_last,
@@ -1321,9 +1302,9 @@ static hipError_t legacy_records(PrepBuffers* p, const slm_frame& f, V1Plan& pla
   hipLaunchKernelGGL(k_run_lidx, ge, blk, 0, st, (int)n_entries, p->scal, p->uwkeys, p->wstart, p->wcount,
                      p->swvals, plan.wg_first, plan.run_lidx);
   // pair -> records: same pair order as blk_key (both are the ascending unique pair keys)
-  PCHK(rocprim::radix_sort_pairs(p->tmp.buf, c4, p->pk2, p->spk2, p->pv2, plan.blk2_entry, n_entries, 0, pair_key_bits(f.J), st));
-  PCHK(rocprim::run_length_encode(p->tmp.buf, c5, p->spk2, n_entries, p->upk2, p->b2count, p->scal + SC_NUQ, st));
-  PCHK(rocprim::exclusive_scan(p->tmp.buf, c3, p->b2count, plan.blk2_start, 0, n_entries, rocprim::plus<int>(), st));
+  HIPRET(rocprim::radix_sort_pairs(p->tmp.buf, c4, p->pk2, p->spk2, p->pv2, plan.blk2_entry, n_entries, 0, pair_key_bits(f.J), st));
+  HIPRET(rocprim::run_length_encode(p->tmp.buf, c5, p->spk2, n_entries, p->upk2, p->b2count, p->scal + SC_NUQ, st));
+  HIPRET(rocprim::exclusive_scan(p->tmp.buf, c3, p->b2count, plan.blk2_start, 0, n_entries, rocprim::plus<int>(), st));
   hipLaunchKernelGGL(k_totals3, dim3(1), dim3(1), 0, st, p->scal, plan.blk2_start);
   return hipSuccess;
 }
@@ -1335,34 +1316,34 @@ static hipError_t prep_v1_legacy(PrepBuffers* p, const slm_frame& f, V1Plan& pla
   const bool hinted = plan.nt_hint > 0;
   *r = Built::done;
   // ---- phase A: tuples ----------------------------------------------------------
-  PCHK(GROW(p, kPrepArrays, cap_n, N));
-  PCHK(hipMemsetAsync(p->scal + SC_BAD_KNN, 0, sizeof(int), st));
+  HIPRET(GROW(p, kPrepArrays, cap_n, N));
+  HIPRET(hipMemsetAsync(p->scal + SC_BAD_KNN, 0, sizeof(int), st));
   hipLaunchKernelGGL(k_tuple_keys, dim3((N + 255) / 256), dim3(256), 0, st, (int)N, f.J, f.sf_knn_idx,
                      p->keys, p->ids, p->scal + SC_BAD_KNN);
-  PCHK(legacy_scratch(p, N, st));
+  HIPRET(legacy_scratch(p, N, st));
   size_t b1 = p->tmp.cap, b2 = p->tmp.cap;
-  PCHK(rocprim::radix_sort_pairs(p->tmp.buf, b1, p->keys, p->skeys, p->ids, p->sids, N, 0, 64, st));
-  PCHK(rocprim::run_length_encode(p->tmp.buf, b2, p->skeys, N, p->tkeys, p->tcount, p->scal + SC_NT, st));
+  HIPRET(rocprim::radix_sort_pairs(p->tmp.buf, b1, p->keys, p->skeys, p->ids, p->sids, N, 0, 64, st));
+  HIPRET(rocprim::run_length_encode(p->tmp.buf, b2, p->skeys, N, p->tkeys, p->tcount, p->scal + SC_NT, st));
   V1Bounds b;
   if (hinted) {   // the kernels below take the count from the device, cut down to the bound by k_clamp_tuples
     b = v1_bounds(N, hinted_tuples(N, plan.nt_hint));
     hipLaunchKernelGGL(k_clamp_tuples, dim3(1), dim3(1), 0, st, p->scal, (int)b.nt);
   } else {
-    PCHK(read_scal(p, 1, st));
+    HIPRET(read_scal(p, 1, st));
     b = v1_bounds(N, (size_t)p->scal_host[SC_NT]);
     if (b.nt == 0) return hipSuccess;
   }
-  PCHK(GROW(p, kPrepArrays, cap_t, b.nt));
-  PCHK(GROW(p, kPrepArrays, cap_e, b.n_entries));
-  PCHK(grow_plan(plan, b, f.state_f64));
-  PCHK(legacy_layout(p, f, plan, b, st));
-  PCHK(GROW(p, kPrepArrays, cap_w, b.n_entries));
-  PCHK(legacy_records(p, f, plan, b, st));
+  HIPRET(GROW(p, kPrepArrays, cap_t, b.nt));
+  HIPRET(GROW(p, kPrepArrays, cap_e, b.n_entries));
+  HIPRET(grow_plan(plan, b, f.state_f64));
+  HIPRET(legacy_layout(p, f, plan, b, st));
+  HIPRET(GROW(p, kPrepArrays, cap_w, b.n_entries));
+  HIPRET(legacy_records(p, f, plan, b, st));
   // hash of the coupling graph (node KNN table + pair keys): rides along with the sizes in the one read-back
-  PCHK(hipMemsetAsync(p->scal + SC_KNN_HASH, 0, 4 * sizeof(int), st));   // both hashes
+  HIPRET(hipMemsetAsync(p->scal + SC_KNN_HASH, 0, 4 * sizeof(int), st));   // both hashes
   hipLaunchKernelGGL(k_plan_hash, dim3(16), dim3(256), 0, st, f.J, f.K_ED, f.ed_knn_idx, plan.blk_key, p->scal,
                      reinterpret_cast<unsigned long long*>(p->scal + SC_KNN_HASH));
-  PCHK(read_scal(p, SC_BAD_KNN + 1, st));
+  HIPRET(read_scal(p, SC_BAD_KNN + 1, st));
   // (this pipeline keeps no SC_STATE: the bound held if the count k_clamp_tuples saw was inside it)
   const bool miss = hinted && (size_t)p->scal_host[SC_NT_TRUE] > b.nt;
   return finish_v1(p, plan, miss ? ST_MISS : ST_OK, out, r);
@@ -1375,13 +1356,13 @@ static hipError_t prep_v1_binned(PrepBuffers* p, const slm_frame& f, V1Plan& pla
   const int J = f.J;
   const int* sh = p->scal_host;
   *r = Built::done;
-  PCHK(GROW(p, kPrepArrays, cap_n, N));
-  PCHK(GROW(p, kPrepArrays, cap_sp, N));
+  HIPRET(GROW(p, kPrepArrays, cap_n, N));
+  HIPRET(GROW(p, kPrepArrays, cap_sp, N));
   const size_t nb1 = (size_t)J + 1;
   const size_t n_wg_max = (4 * N + 63) / 256 + 2;          // positions <= N + 3 * tuples <= 4 N
-  PCHK(GROW(p, kPrepArrays, cap_bins, 3 * nb1 + 2 * n_wg_max));
-  PCHK(GROW(p, kPrepArrays, cap_binv, (size_t)BV_COUNT * nb1));
-  PCHK(GROW(p, kPrepArrays, cap_nwg, n_wg_max));
+  HIPRET(GROW(p, kPrepArrays, cap_bins, 3 * nb1 + 2 * n_wg_max));
+  HIPRET(GROW(p, kPrepArrays, cap_binv, (size_t)BV_COUNT * nb1));
+  HIPRET(GROW(p, kPrepArrays, cap_nwg, n_wg_max));
   int* cntA = p->bins;
   int* cntB = cntA + nb1;
   int* cntC = cntB + nb1;
@@ -1389,8 +1370,8 @@ static hipError_t prep_v1_binned(PrepBuffers* p, const slm_frame& f, V1Plan& pla
   int* wgr1 = wgr0x + n_wg_max;
   int* bv = p->binv;
   auto BV = [&](int which) { return bv + (size_t)which * nb1; };
-  PCHK(hipMemsetAsync(p->bins, 0, sizeof(int) * (3 * nb1 + 2 * n_wg_max), st));
-  PCHK(hipMemsetAsync(p->scal, 0, sizeof(int) * SC_COUNT, st));
+  HIPRET(hipMemsetAsync(p->bins, 0, sizeof(int) * (3 * nb1 + 2 * n_wg_max), st));
+  HIPRET(hipMemsetAsync(p->scal, 0, sizeof(int) * SC_COUNT, st));
   const dim3 blk(256);
   hipLaunchKernelGGL(kb_keys, dim3((N + 255) / 256), blk, 0, st, (int)N, J, f.sf_knn_idx, p->keys, cntA, p->scal + SC_BAD_KNN);
   hipLaunchKernelGGL(kb_scan_bins, dim3(1), dim3(1024), 0, st, J, cntA, BV(BV_STARTA), p->scal, BIN_CAP);
@@ -1405,14 +1386,14 @@ static hipError_t prep_v1_binned(PrepBuffers* p, const slm_frame& f, V1Plan& pla
   hipLaunchKernelGGL(kb_runs, dim3(J), blk, 0, st, J, bv, p->sp_head, p->sp_pcl, p->sp_rl, p->scal);
   hipLaunchKernelGGL(kb_scan_runs, dim3(1), dim3(1024), 0, st, J, bv, p->scal, (int)b.runs_bound);
   if (!hinted) {
-    PCHK(read_scal(p, SC_COUNT, st));
+    HIPRET(read_scal(p, SC_COUNT, st));
     if (sh[SC_STATE] == ST_LEGACY) { *r = Built::legacy; return hipSuccess; }
     if (sh[SC_BAD_KNN]) { out->bad_knn = true; plan.nt_hint = 0; *r = Built::refused; return hipSuccess; }
     if (sh[SC_NT] == 0) return hipSuccess;
     b = v1_bounds_of((size_t)sh[SC_NT], ((size_t)sh[SC_PTOT] + 63) / 64 * 64, (size_t)sh[SC_NRUNS]);   // exact, not derived from the count
   }
-  PCHK(grow_plan(plan, b, f.state_f64));
-  PCHK(GROW(p, kPrepArrays, cap_ent, b.n_entries));
+  HIPRET(grow_plan(plan, b, f.state_f64));
+  HIPRET(GROW(p, kPrepArrays, cap_ent, b.n_entries));
   const size_t runs_bound = b.runs_bound, n_wg = b.n_wg;
   const int RB = (int)runs_bound + 1;
   hipLaunchKernelGGL(kb_fill, dim3(J + 1), blk, 0, st, J, f, bv, p->skeys, p->sids, p->sp_head, p->sp_pcl, p->sp_rl, p->scal, plan.s_pts,
@@ -1431,7 +1412,7 @@ static hipError_t prep_v1_binned(PrepBuffers* p, const slm_frame& f, V1Plan& pla
   // hash of the coupling graph (node KNN table + pair keys): rides along with the sizes in the one read-back
   hipLaunchKernelGGL(k_plan_hash, dim3(16), blk, 0, st, f.J, f.K_ED, f.ed_knn_idx, plan.blk_key, p->scal,
                      reinterpret_cast<unsigned long long*>(p->scal + SC_KNN_HASH));
-  PCHK(read_scal(p, SC_COUNT, st));
+  HIPRET(read_scal(p, SC_COUNT, st));
   return finish_v1(p, plan, sh[SC_STATE], out, r);
 }
 
@@ -1447,78 +1428,66 @@ hipError_t prep_v1(PrepBuffers* p, const slm_frame& f, V1Plan& plan, V1Sizes* ou
   if (f.N == 0) return hipSuccess;
   Built r = Built::legacy;
   if (!force_legacy && !plan.legacy) {
-    PCHK(prep_v1_binned(p, f, plan, out, &r, st));
-    if (r == Built::retry) PCHK(prep_v1_binned(p, f, plan, out, &r, st));
+    HIPRET(prep_v1_binned(p, f, plan, out, &r, st));
+    if (r == Built::retry) HIPRET(prep_v1_binned(p, f, plan, out, &r, st));
     if (r != Built::legacy) return hipSuccess;
     plan.legacy = true;
     plan.nt_hint = 0;
   }
-  PCHK(prep_v1_legacy(p, f, plan, out, &r, st));
-  if (r == Built::retry) PCHK(prep_v1_legacy(p, f, plan, out, &r, st));
+  HIPRET(prep_v1_legacy(p, f, plan, out, &r, st));
+  if (r == Built::retry) HIPRET(prep_v1_legacy(p, f, plan, out, &r, st));
   return hipSuccess;
 }
 
 // ---- K-generic pair plan ---------------------------------------------------------------------------------------------
-// (no default: prep_pairs, the only user, returns early for K outside 1..8)
-#define SLM_PREP_K_DISPATCH(K, CALL)                                   \
-  switch (K) {                                                         \
-    case 1: { constexpr int KK = 1; CALL; break; }                     \
-    case 2: { constexpr int KK = 2; CALL; break; }                     \
-    case 3: { constexpr int KK = 3; CALL; break; }                     \
-    case 4: { constexpr int KK = 4; CALL; break; }                     \
-    case 5: { constexpr int KK = 5; CALL; break; }                     \
-    case 6: { constexpr int KK = 6; CALL; break; }                     \
-    case 7: { constexpr int KK = 7; CALL; break; }                     \
-    case 8: { constexpr int KK = 8; CALL; break; }                     \
-  }
-
+// (SLM_K_DISPATCH's default is dead code here: prep_pairs, the only user, returns early for K outside 1..8)
 hipError_t prep_pairs(PrepBuffers* p, const slm_frame& f, PairPlan& plan, PairSizes* out, hipStream_t st) {
   *out = PairSizes();
   if (f.N <= 0 || f.K < 1 || f.K > 8 || f.J >= 65536) return hipSuccess;
   const size_t N = (size_t)f.N, NP = (size_t)f.K * (f.K + 1) / 2, n = N * NP;
-  PCHK(GROW(p, kPrepArrays, cap_g, n));
-  if (!p->gcnt) PCHK(hipMalloc((void**)&p->gcnt, sizeof(unsigned)));
+  HIPRET(GROW(p, kPrepArrays, cap_g, n));
+  if (!p->gcnt) HIPRET(hipMalloc((void**)&p->gcnt, sizeof(unsigned)));
   // key bits: a*J + b < J*J
   int bits = 1;
   while (bits < 32 && (1ull << bits) < (unsigned long long)f.J * (unsigned long long)f.J) ++bits;
-  PCHK(GROW(p, kPrepArrays, cap_n, N));   // (the phase-A buffers of the tuple-sorted preparation: order keys / surfel ids, unsorted and sorted)
-  PCHK(ensure_scratch(p, p->gtmp, n, N, 0, 1u << 16, [&](size_t& need) {
+  HIPRET(GROW(p, kPrepArrays, cap_n, N));   // (the phase-A buffers of the tuple-sorted preparation: order keys / surfel ids, unsorted and sorted)
+  HIPRET(ensure_scratch(p, p->gtmp, n, N, 0, 1u << 16, [&](size_t& need) {
     size_t b[3] = {};
-    PCHK(rocprim::radix_sort_keys(nullptr, b[0], p->gk, p->gsk, n, 0, 32, st));
-    PCHK(rocprim::unique(nullptr, b[1], p->gsk, p->gk, p->gcnt, n, rocprim::equal_to<unsigned>(), st));
-    PCHK(rocprim::radix_sort_pairs(nullptr, b[2], p->keys, p->skeys, p->ids, p->sids, N, 0, 64, st));
+    HIPRET(rocprim::radix_sort_keys(nullptr, b[0], p->gk, p->gsk, n, 0, 32, st));
+    HIPRET(rocprim::unique(nullptr, b[1], p->gsk, p->gk, p->gcnt, n, rocprim::equal_to<unsigned>(), st));
+    HIPRET(rocprim::radix_sort_pairs(nullptr, b[2], p->keys, p->skeys, p->ids, p->sids, N, 0, 64, st));
     need = *std::max_element(b, b + 3);
     return hipSuccess;
   }));
-  PCHK(hipMemsetAsync(p->scal, 0, SC_COUNT * sizeof(int), st));
+  HIPRET(hipMemsetAsync(p->scal, 0, SC_COUNT * sizeof(int), st));
   const dim3 blk(256);
-  SLM_PREP_K_DISPATCH(f.K, hipLaunchKernelGGL(k_pair_keys<KK>, dim3((unsigned)((f.N + 255) / 256)), blk, 0, st, f.N, f.J, f.sf_knn_idx,
+  SLM_K_DISPATCH(f.K, hipLaunchKernelGGL(k_pair_keys<KK>, dim3((unsigned)((f.N + 255) / 256)), blk, 0, st, f.N, f.J, f.sf_knn_idx,
                                               p->gk, p->scal + SC_BAD_KNN));
   size_t b1 = p->gtmp.cap, b2 = p->gtmp.cap;
-  PCHK(rocprim::radix_sort_keys(p->gtmp.buf, b1, p->gk, p->gsk, n, 0, bits, st));
-  PCHK(rocprim::unique(p->gtmp.buf, b2, p->gsk, p->gk, p->gcnt, n, rocprim::equal_to<unsigned>(), st));
+  HIPRET(rocprim::radix_sort_keys(p->gtmp.buf, b1, p->gk, p->gsk, n, 0, bits, st));
+  HIPRET(rocprim::unique(p->gtmp.buf, b2, p->gsk, p->gk, p->gcnt, n, rocprim::equal_to<unsigned>(), st));
   hipLaunchKernelGGL(k_pair_count, dim3(1), dim3(1), 0, st, p->scal, p->gcnt);
   // the hashes the cached symbolic plan is compared with (same function as the tuple-sorted preparation's)
   hipLaunchKernelGGL(k_plan_hash, dim3(16), blk, 0, st, f.J, f.K_ED, f.ed_knn_idx, reinterpret_cast<const int32_t*>(p->gk), p->scal,
                      reinterpret_cast<unsigned long long*>(p->scal + SC_KNN_HASH));
-  PCHK(read_scal(p, SC_COUNT, st));
+  HIPRET(read_scal(p, SC_COUNT, st));
   if (read_built(p->scal_host, ST_OK, out) != Built::done || out->n_blocks <= 0) return hipSuccess;
-  PCHK(GROW(&plan, kPairPlanArrays, cap_key, (size_t)out->n_blocks));
-  PCHK(GROW(&plan, kPairPlanArrays, cap_pidx, n));
-  PCHK(GROW(&plan, kPairPlanArrays, cap_perm, N));
-  PCHK(hipMemcpyAsync(plan.blk_key, p->gk, sizeof(unsigned) * (size_t)out->n_blocks, hipMemcpyDeviceToDevice, st));
-  SLM_PREP_K_DISPATCH(f.K, hipLaunchKernelGGL(k_pair_index<KK>, dim3((unsigned)((N + 255) / 256)), blk, 0, st, f.N, f.J, out->n_blocks,
+  HIPRET(GROW(&plan, kPairPlanArrays, cap_key, (size_t)out->n_blocks));
+  HIPRET(GROW(&plan, kPairPlanArrays, cap_pidx, n));
+  HIPRET(GROW(&plan, kPairPlanArrays, cap_perm, N));
+  HIPRET(hipMemcpyAsync(plan.blk_key, p->gk, sizeof(unsigned) * (size_t)out->n_blocks, hipMemcpyDeviceToDevice, st));
+  SLM_K_DISPATCH(f.K, hipLaunchKernelGGL(k_pair_index<KK>, dim3((unsigned)((N + 255) / 256)), blk, 0, st, f.N, f.J, out->n_blocks,
                                               f.sf_knn_idx, reinterpret_cast<const unsigned*>(plan.blk_key), plan.sf_pidx,
                                               p->keys, p->tkeys, p->ids));
   size_t b3 = p->gtmp.cap;
   if (f.K <= 4) {
-    PCHK(rocprim::radix_sort_pairs(p->gtmp.buf, b3, p->keys, p->skeys, p->ids, plan.sf_perm, N, 0, 64, st));
+    HIPRET(rocprim::radix_sort_pairs(p->gtmp.buf, b3, p->keys, p->skeys, p->ids, plan.sf_perm, N, 0, 64, st));
   } else {
     // lexicographic order of the full canonical tuple: stable sorts, least significant key (ids 4..7) first
-    PCHK(rocprim::radix_sort_pairs(p->gtmp.buf, b3, p->tkeys, p->skeys, p->ids, p->sids, N, 0, 64, st));
+    HIPRET(rocprim::radix_sort_pairs(p->gtmp.buf, b3, p->tkeys, p->skeys, p->ids, p->sids, N, 0, 64, st));
     hipLaunchKernelGGL(k_gather_keys, dim3((unsigned)((N + 255) / 256)), blk, 0, st, f.N, p->keys, p->sids, p->tkeys);
     b3 = p->gtmp.cap;
-    PCHK(rocprim::radix_sort_pairs(p->gtmp.buf, b3, p->tkeys, p->skeys, p->sids, plan.sf_perm, N, 0, 64, st));
+    HIPRET(rocprim::radix_sort_pairs(p->gtmp.buf, b3, p->tkeys, p->skeys, p->sids, plan.sf_perm, N, 0, 64, st));
   }
   return hipGetLastError();
 }

@@ -6,6 +6,7 @@
 // Rot (reference super/loss.py:480-499): r_j = lam (1 - |q_j|^2) evaluated in FLOAT32,
 //   cols 7j+0..3 <- -2 lam q_j; its JtJ / jtl products are float32 too.
 #include "slm_common.h"
+#include "slm_launch.h"
 
 __device__ __forceinline__ void load_beta(const double* beta, const double* delta, int j,
                                           double bb[7]) {

@@ -25,15 +25,12 @@
 #include <climits>
 #include <cmath>
 #include <cstring>
-#include <string>
-
 #include "slm_gf.h"
+#include "slm_host.h"
 
 #define RN_TILE 16            // tile edge in pixels: one lane per pixel, 256 lanes per workgroup
 #define RN_SORT_CAP 4096      // keys a workgroup sorts in LDS at once (32 KB)
 #define RN_CHUNK 256          // list entries staged in LDS per step of the walk
-
-void slm_set_error_text(const char* msg);   // slm_api.hip
 
 struct slm_render {
   int H = 0, W = 0, cap = 0;
@@ -43,8 +40,8 @@ struct slm_render {
   unsigned long long* off = nullptr;     // (tiles + 1) exclusive scan of cnt
   unsigned long long* cur = nullptr;     // (tiles) scatter cursors
   unsigned long long* keys = nullptr;    // (cap_keys) tile lists
-  unsigned long long* tmp = nullptr;     // (cap_keys) merge scratch of the overflow path
-  size_t cap_keys = 0;
+  unsigned long long* tmp = nullptr;     // (cap_tmp, as many) merge scratch of the overflow path
+  size_t cap_keys = 0, cap_tmp = 0;
   unsigned long long* h_total = nullptr; // pinned host copy of off[tiles]
   // ---- state of the last forward, read by slm_render_backward ----
   float4* col = nullptr;                 // (cap) colours of the points, w unused
@@ -515,19 +512,12 @@ __global__ void __launch_bounds__(256) k_rn_bwd_point_ex(int N, int tiles_x, con
     for (int q = 0; q < 3; ++q) out_c[3 * (size_t)i + q] = g[S - 3 + q];
 }
 
-int rfail(int code, const char* msg) {
-  slm_set_error_text(msg);
-  return code;
-}
-
-#define RNCHK(expr)                                                                   \
-  do {                                                                                \
-    hipError_t e_ = (expr);                                                           \
-    if (e_ != hipSuccess) {                                                           \
-      slm_set_error_text((std::string(#expr) + ": " + hipGetErrorString(e_)).c_str()); \
-      return SLM_ERR_HIP;                                                             \
-    }                                                                                 \
-  } while (0)
+// the device arrays of a context; sizes of slm_render_create: [0] points + 1, [1] tiles, [2] tiles + 1, [3] pixels
+#define A(name, mult, unit) DEV_MEMBER(slm_render, name, mult, unit)
+constexpr DevMember kRenderArrays[] = {A(pos, 1, 0), A(box, 1, 0), A(cnt, 1, 1), A(off, 1, 2), A(cur, 1, 1), A(col, 1, 0),
+                                       A(pix, 1, 3), DEV_GROWN(slm_render, keys), DEV_GROWN(slm_render, tmp),
+                                       DEV_GROWN(slm_render, slab)};
+#undef A
 
 int rn_tiles_x(int w) { return (w + RN_TILE - 1) / RN_TILE; }
 
@@ -563,22 +553,22 @@ int render_common(slm_render* r, const slm_render_params* p, int N, int src, con
                   const float* colors, int cstride, float* image, int32_t* front_id, int32_t* hit_count, void* stream,
                   const char* who) {
   std::string w(who);
-  if (!r || !p || !image) return rfail(SLM_ERR_INVALID, (w + ": null argument").c_str());
+  if (!r || !p || !image) return fail(SLM_ERR_INVALID, w + ": null argument");
   if (p->width < 1 || p->height < 1 || p->width > r->W || p->height > r->H)
-    return rfail(SLM_ERR_INVALID, (w + ": image size outside the context's H x W").c_str());
-  if (p->n_track < 1 || p->n_track > SLM_RENDER_MAX_TRACK) return rfail(SLM_ERR_INVALID, (w + ": n_track must be 1..64").c_str());
+    return fail(SLM_ERR_INVALID, w + ": image size outside the context's H x W");
+  if (p->n_track < 1 || p->n_track > SLM_RENDER_MAX_TRACK) return fail(SLM_ERR_INVALID, w + ": n_track must be 1..64");
   if (!(p->focal > 0.0) || !(p->radius > 0.0) || !(p->gamma > 0.0) || !(p->z_near > 0.0) || !(p->z_far > p->z_near) ||
       !std::isfinite(p->focal) || !std::isfinite(p->ccx) || !std::isfinite(p->ccy) || !std::isfinite(p->z_far) ||
       !std::isfinite(p->radius) || !std::isfinite(p->bg_eps))
-    return rfail(SLM_ERR_INVALID, (w + ": bad camera or blend parameters").c_str());
-  if (N < 0 || N > r->cap) return rfail(SLM_ERR_INVALID, (w + ": more points than the context holds").c_str());
+    return fail(SLM_ERR_INVALID, w + ": bad camera or blend parameters");
+  if (N < 0 || N > r->cap) return fail(SLM_ERR_INVALID, w + ": more points than the context holds");
   if (N > 0 && ((src != RN_SRC_GF && !pts) || !colors || cstride < 3))
-    return rfail(SLM_ERR_INVALID, (w + ": null points / colours or color_stride < 3").c_str());
+    return fail(SLM_ERR_INVALID, w + ": null points / colours or color_stride < 3");
   r->has_fwd = 0;
   hipStream_t st = (hipStream_t)stream;
   const RnCam cam = rn_cam(p);
   const int tiles_y = (p->height + RN_TILE - 1) / RN_TILE, tiles = cam.tiles_x * tiles_y;
-  RNCHK(hipMemsetAsync(r->cnt, 0, sizeof(unsigned int) * tiles, st));
+  HIPCHK(hipMemsetAsync(r->cnt, 0, sizeof(unsigned int) * tiles, st));
   const dim3 gp((N + 255) / 256);
   if (N > 0) {
     if (src == RN_SRC_F32)
@@ -589,26 +579,19 @@ int render_common(slm_render* r, const slm_render_params* p, int N, int src, con
       hipLaunchKernelGGL(k_rn_project<RN_SRC_GF>, gp, dim3(256), 0, st, N, pts, gslot, cam, r->pos, r->box, r->cnt, colors, cstride, r->col);
   }
   hipLaunchKernelGGL(k_rn_scan, dim3(1), dim3(1024), 0, st, tiles, r->cnt, r->off, r->cur);
-  RNCHK(hipGetLastError());
-  RNCHK(hipMemcpyAsync(r->h_total, r->off + tiles, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-  RNCHK(hipStreamSynchronize(st));
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(r->h_total, r->off + tiles, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
   const unsigned long long total = *r->h_total;
-  if (total > (1ull << 31)) return rfail(SLM_ERR_UNSUPPORTED, (w + ": more than 2^31 tile entries").c_str());
-  if (total > r->cap_keys) {
-    if (r->keys) RNCHK(hipFree(r->keys));
-    if (r->tmp) RNCHK(hipFree(r->tmp));
-    r->keys = r->tmp = nullptr;
-    r->cap_keys = 0;
-    const size_t c = (size_t)total + total / 4 + 1024;
-    RNCHK(hipMalloc((void**)&r->keys, sizeof(unsigned long long) * c));
-    RNCHK(hipMalloc((void**)&r->tmp, sizeof(unsigned long long) * c));
-    r->cap_keys = c;
-  }
+  if (total > (1ull << 31)) return fail(SLM_ERR_UNSUPPORTED, w + ": more than 2^31 tile entries");
+  const size_t want = (size_t)total + total / 4 + 1024;   // (head-room of the tile lists; the slab's follows it)
+  HIPCHK(grow(r->keys, r->cap_keys, total, want));
+  HIPCHK(grow(r->tmp, r->cap_tmp, total, want));
   if (total > 0)
     hipLaunchKernelGGL(k_rn_scatter, gp, dim3(256), 0, st, N, cam.tiles_x, r->pos, r->box, r->cur, r->keys);
   hipLaunchKernelGGL(k_rn_tile, dim3(cam.tiles_x, tiles_y), dim3(256), 0, st, cam, r->off, r->keys, r->tmp, r->pos, r->box,
                      colors, cstride, image, front_id, hit_count, r->pix);
-  RNCHK(hipGetLastError());
+  HIPCHK(hipGetLastError());
   r->last = *p;
   r->n_last = N;
   r->total_last = total;
@@ -625,14 +608,7 @@ int rn_backward(slm_render* r, const slm_render_params* p, const double* grad_im
   const int mode = (grad_points ? RN_BWD_POINTS : 0) | (grad_colors ? RN_BWD_COLORS : 0);
   const size_t S = mode == (RN_BWD_POINTS | RN_BWD_COLORS) ? 6 : 3;
   const unsigned long long total = r->total_last;
-  if (S * total > r->cap_slab) {
-    if (r->slab) RNCHK(hipFree(r->slab));
-    r->slab = nullptr;
-    r->cap_slab = 0;
-    const size_t c = S * ((size_t)total + total / 4 + 1024);
-    RNCHK(hipMalloc((void**)&r->slab, sizeof(double) * c));
-    r->cap_slab = c;
-  }
+  HIPCHK(grow(r->slab, r->cap_slab, S * total, S * ((size_t)total + total / 4 + 1024)));
   const dim3 gt(cam.tiles_x, tiles_y), gp((N + 255) / 256), b(256);
   if (mode == RN_BWD_POINTS) {
     if (total > 0)
@@ -652,7 +628,7 @@ int rn_backward(slm_render* r, const slm_render_params* p, const double* grad_im
     hipLaunchKernelGGL(k_rn_bwd_point_ex<RN_BWD_POINTS | RN_BWD_COLORS>, gp, b, 0, st, N, cam.tiles_x, r->off, r->keys,
                        r->pos, r->box, r->slab, grad_points, grad_colors);
   }
-  RNCHK(hipGetLastError());
+  HIPCHK(hipGetLastError());
   return SLM_OK;
 }
 
@@ -661,25 +637,19 @@ int rn_backward(slm_render* r, const slm_render_params* p, const double* grad_im
 extern "C" {
 
 int slm_render_create(int32_t H, int32_t W, int32_t max_points, slm_render** out) {
-  if (!out || H < 1 || W < 1 || max_points < 0) return rfail(SLM_ERR_INVALID, "slm_render_create: bad argument");
-  if (slm_device_count() < 1) return rfail(SLM_ERR_NO_DEVICE, "slm_render_create: no HIP device visible");
+  if (!out || H < 1 || W < 1 || max_points < 0) return fail(SLM_ERR_INVALID, "slm_render_create: bad argument");
+  if (slm_device_count() < 1) return fail(SLM_ERR_NO_DEVICE, "slm_render_create: no HIP device visible");
   slm_render* r = new slm_render();
   r->H = H;
   r->W = W;
   r->cap = max_points;
   const size_t cap = (size_t)max_points + 1, tiles = (size_t)rn_tiles_x(W) * ((H + RN_TILE - 1) / RN_TILE);
-  hipError_t e = hipMalloc((void**)&r->pos, sizeof(float4) * cap);
-  if (e == hipSuccess) e = hipMalloc((void**)&r->box, sizeof(int4) * cap);
-  if (e == hipSuccess) e = hipMalloc((void**)&r->cnt, sizeof(unsigned int) * tiles);
-  if (e == hipSuccess) e = hipMalloc((void**)&r->off, sizeof(unsigned long long) * (tiles + 1));
-  if (e == hipSuccess) e = hipMalloc((void**)&r->cur, sizeof(unsigned long long) * tiles);
+  const size_t units[] = {cap, tiles, tiles + 1, (size_t)H * W};
+  hipError_t e = alloc_members(r, kRenderArrays, units);
   if (e == hipSuccess) e = hipHostMalloc((void**)&r->h_total, sizeof(unsigned long long), hipHostMallocDefault);
-  if (e == hipSuccess) e = hipMalloc((void**)&r->col, sizeof(float4) * cap);
-  if (e == hipSuccess) e = hipMalloc((void**)&r->pix, sizeof(RnPix) * (size_t)H * W);
   if (e != hipSuccess) {
-    slm_set_error_text((std::string("slm_render_create: ") + hipGetErrorString(e)).c_str());
     slm_render_destroy(r);
-    return SLM_ERR_HIP;
+    return fail(SLM_ERR_HIP, std::string("slm_render_create: ") + hipGetErrorString(e));
   }
   *out = r;
   return SLM_OK;
@@ -687,9 +657,7 @@ int slm_render_create(int32_t H, int32_t W, int32_t max_points, slm_render** out
 
 int slm_render_destroy(slm_render* r) {
   if (!r) return SLM_OK;
-  void* ptrs[] = {r->pos, r->box, r->cnt, r->off, r->cur, r->keys, r->tmp, r->col, r->pix, r->slab};
-  for (void* q : ptrs)
-    if (q) (void)hipFree(q);
+  free_members(r, kRenderArrays);
   if (r->h_total) (void)hipHostFree(r->h_total);
   delete r;
   return SLM_OK;
@@ -697,7 +665,7 @@ int slm_render_destroy(slm_render* r) {
 
 int slm_render_points(slm_render* r, const slm_render_params* p, int32_t N, const void* points, const float* colors,
                       int32_t color_stride, float* image, int32_t* front_id, int32_t* hit_count, void* stream) {
-  if (!p) return rfail(SLM_ERR_INVALID, "slm_render_points: null argument");
+  if (!p) return fail(SLM_ERR_INVALID, "slm_render_points: null argument");
   return render_common(r, p, N, p->points_f64 ? RN_SRC_F64 : RN_SRC_F32, points, nullptr, colors, color_stride, image,
                        front_id, hit_count, stream, "slm_render_points");
 }
@@ -714,24 +682,24 @@ int slm_gf_render(slm_gf* g, int32_t slot, slm_render* r, const slm_render_param
 
 int slm_render_backward(slm_render* r, const slm_render_params* p, const double* grad_image, double* grad_points,
                         void* stream) {
-  if (!r || !p || !grad_image) return rfail(SLM_ERR_INVALID, "slm_render_backward: null argument");
-  if (!r->has_fwd) return rfail(SLM_ERR_INVALID, "slm_render_backward: no completed forward on this context");
+  if (!r || !p || !grad_image) return fail(SLM_ERR_INVALID, "slm_render_backward: null argument");
+  if (!r->has_fwd) return fail(SLM_ERR_INVALID, "slm_render_backward: no completed forward on this context");
   if (!rn_same_params(*p, r->last))
-    return rfail(SLM_ERR_INVALID, "slm_render_backward: parameters differ from those of the last forward");
+    return fail(SLM_ERR_INVALID, "slm_render_backward: parameters differ from those of the last forward");
   const int N = r->n_last;
   if (N == 0) return SLM_OK;
-  if (!grad_points) return rfail(SLM_ERR_INVALID, "slm_render_backward: null grad_points");
+  if (!grad_points) return fail(SLM_ERR_INVALID, "slm_render_backward: null grad_points");
   return rn_backward(r, p, grad_image, grad_points, nullptr, (hipStream_t)stream);
 }
 
 int slm_render_backward_ex(slm_render* r, const slm_render_params* p, const double* grad_image, double* grad_points,
                            double* grad_colors, void* stream) {
-  if (!r || !p || !grad_image) return rfail(SLM_ERR_INVALID, "slm_render_backward_ex: null argument");
-  if (!r->has_fwd) return rfail(SLM_ERR_INVALID, "slm_render_backward_ex: no completed forward on this context");
+  if (!r || !p || !grad_image) return fail(SLM_ERR_INVALID, "slm_render_backward_ex: null argument");
+  if (!r->has_fwd) return fail(SLM_ERR_INVALID, "slm_render_backward_ex: no completed forward on this context");
   if (!rn_same_params(*p, r->last))
-    return rfail(SLM_ERR_INVALID, "slm_render_backward_ex: parameters differ from those of the last forward");
+    return fail(SLM_ERR_INVALID, "slm_render_backward_ex: parameters differ from those of the last forward");
   if (r->n_last == 0) return SLM_OK;
-  if (!grad_points && !grad_colors) return rfail(SLM_ERR_INVALID, "slm_render_backward_ex: null grad_points and grad_colors");
+  if (!grad_points && !grad_colors) return fail(SLM_ERR_INVALID, "slm_render_backward_ex: null grad_points and grad_colors");
   return rn_backward(r, p, grad_image, grad_points, grad_colors, (hipStream_t)stream);
 }
 

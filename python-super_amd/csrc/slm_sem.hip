@@ -11,6 +11,7 @@
 #include <cstring>
 #include <rocprim/rocprim.hpp>
 
+#include "slm_host.h"
 #include "slm_sem.h"
 
 namespace {
@@ -42,63 +43,36 @@ __global__ void __launch_bounds__(256) k_edge_pack(int n, int HW, int W, const i
   xy[e] = make_float2((float)(pix % W), (float)(pix / W));
 }
 
-template <typename T>
-hipError_t grow(T*& p, size_t& cap, size_t need) {
-  if (need <= cap) return hipSuccess;
-  if (p) {
-    hipError_t e = hipFree(p);
-    if (e != hipSuccess) return e;
-    p = nullptr;
-    cap = 0;
-  }
-  hipError_t e = hipMalloc((void**)&p, need * sizeof(T));
-  if (e == hipSuccess) cap = need;
-  return e;
-}
-
 }  // namespace
-
-#define SCHK(expr)                   \
-  do {                               \
-    hipError_t e_ = (expr);          \
-    if (e_ != hipSuccess) return e_; \
-  } while (0)
 
 hipError_t sem_extract_edges(SemScratch& sc, const slm_gf_semantic& sem, int H, int W, int32_t* edge_off,
                              hipStream_t st) {
   const int C = sem.num_classes;
   const size_t HW = (size_t)H * W, n = HW * C;
-  SCHK(grow(sc.flags, sc.cap_flags, n));
-  if (!sc.counts) SCHK(hipMalloc((void**)&sc.counts, sizeof(int32_t) * (SLM_MAX_CLASSES + 1)));
-  SCHK(hipMemsetAsync(sc.counts, 0, sizeof(int32_t) * (SLM_MAX_CLASSES + 1), st));
+  HIPRET(grow(sc.flags, sc.cap_flags, n, n));
+  if (!sc.counts) HIPRET(hipMalloc((void**)&sc.counts, sizeof(int32_t) * (SLM_MAX_CLASSES + 1)));
+  HIPRET(hipMemsetAsync(sc.counts, 0, sizeof(int32_t) * (SLM_MAX_CLASSES + 1), st));
   hipLaunchKernelGGL(k_edge_flags, dim3((HW + 255) / 256), dim3(256), 0, st, H, W, C, sem.img_seg, sc.flags,
                      sc.counts);
   int32_t h[SLM_MAX_CLASSES + 1];
-  SCHK(hipMemcpyAsync(h, sc.counts, sizeof(h), hipMemcpyDeviceToHost, st));
-  SCHK(hipStreamSynchronize(st));
+  HIPRET(hipMemcpyAsync(h, sc.counts, sizeof(h), hipMemcpyDeviceToHost, st));
+  HIPRET(hipStreamSynchronize(st));
   edge_off[0] = 0;
   for (int c = 0; c < SLM_MAX_CLASSES; ++c) edge_off[c + 1] = edge_off[c] + (c < C ? h[c] : 0);
   const int total = edge_off[C];
-  SCHK(grow(sc.sel, sc.cap_sel, (size_t)total + 1));
-  SCHK(grow(sc.edge_xy, sc.cap_edge, (size_t)total + 1));
+  HIPRET(grow(sc.sel, sc.cap_sel, (size_t)total + 1, (size_t)total + 1));
+  HIPRET(grow(sc.edge_xy, sc.cap_edge, (size_t)total + 1, (size_t)total + 1));
   if (total == 0) return hipSuccess;
-  size_t bytes = 0;
   rocprim::counting_iterator<int32_t> first(0);
-  SCHK(rocprim::select(nullptr, bytes, first, sc.flags, sc.sel, sc.counts + SLM_MAX_CLASSES, n, st));
-  if (bytes > sc.cap_tmp) {
-    if (sc.tmp) SCHK(hipFree(sc.tmp));
-    sc.tmp = nullptr;
-    sc.cap_tmp = 0;
-    SCHK(hipMalloc(&sc.tmp, bytes));
-    sc.cap_tmp = bytes;
-  }
-  SCHK(rocprim::select(sc.tmp, bytes, first, sc.flags, sc.sel, sc.counts + SLM_MAX_CLASSES, n, st));
+  HIPRET(with_scratch(sc.tmp, sc.cap_tmp, [&](void* tmp, size_t& bytes) {
+    return rocprim::select(tmp, bytes, first, sc.flags, sc.sel, sc.counts + SLM_MAX_CLASSES, n, st);
+  }));
   hipLaunchKernelGGL(k_edge_pack, dim3((total + 255) / 256), dim3(256), 0, st, total, (int)HW, W, sc.sel,
                      sc.edge_xy);
   return hipGetLastError();
 }
 
-hipError_t sem_ensure_morph(SemScratch& sc, int N) { return grow(sc.morph_g, sc.cap_morph, (size_t)N + 1); }
+hipError_t sem_ensure_morph(SemScratch& sc, int N) { return grow(sc.morph_g, sc.cap_morph, (size_t)N + 1, (size_t)N + 1); }
 
 void sem_free(SemScratch& sc) {
   void* ptrs[] = {sc.flags, sc.sel, sc.counts, sc.tmp, sc.edge_xy, sc.morph_g};

@@ -11,15 +11,12 @@
 //               |p - q| <= 5 per axis, each weighted by how often q lies in p's reflected window (1..3 per axis)
 //   k_ssim_sum  one workgroup: the tile partials in a fixed order -> loss_out
 // No float atomics: the loss and the gradient are bitwise reproducible.
-#include <string>
-
 #include "slm_gf.h"
+#include "slm_host.h"
 
 #define SS_T 16                  // tile edge
 #define SS_R 5                   // window radius (kernel 11)
 #define SS_E (SS_T + 2 * SS_R)   // tile edge with the halo
-
-void slm_set_error_text(const char* msg);   // slm_api.hip
 
 namespace {
 
@@ -178,17 +175,12 @@ __global__ void __launch_bounds__(256) k_ssim_sum(int nb, const double* __restri
   }
 }
 
-int sfail(int code, const char* msg) {
-  slm_set_error_text(msg);
-  return code;
-}
-
 }  // namespace
 
 extern "C" int slm_render_ssim_loss(int32_t h, int32_t w, const float* image_hwc, const float* target_chw, double weight,
                                     double* loss_out, double* grad_image, void* stream) {
-  if (!image_hwc || !target_chw || !loss_out) return sfail(SLM_ERR_INVALID, "slm_render_ssim_loss: null argument");
-  if (h < SS_R + 1 || w < SS_R + 1) return sfail(SLM_ERR_INVALID, "slm_render_ssim_loss: h and w must be >= 6");
+  if (!image_hwc || !target_chw || !loss_out) return fail(SLM_ERR_INVALID, "slm_render_ssim_loss: null argument");
+  if (h < SS_R + 1 || w < SS_R + 1) return fail(SLM_ERR_INVALID, "slm_render_ssim_loss: h and w must be >= 6");
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid((w + SS_T - 1) / SS_T, (h + SS_T - 1) / SS_T);
   const int nb = (int)(grid.x * grid.y);
@@ -196,7 +188,7 @@ extern "C" int slm_render_ssim_loss(int32_t h, int32_t w, const float* image_hwc
   double* scratch = nullptr;
   hipError_t e = hipMallocAsync((void**)&scratch, sizeof(double) * (n_part + n_g), st);
   if (e != hipSuccess)
-    return sfail(SLM_ERR_HIP, (std::string("slm_render_ssim_loss: hipMallocAsync: ") + hipGetErrorString(e)).c_str());
+    return fail(SLM_ERR_HIP, std::string("slm_render_ssim_loss: hipMallocAsync: ") + hipGetErrorString(e));
   double* part = scratch;
   double* G = grad_image ? scratch + n_part : nullptr;
   hipLaunchKernelGGL(k_ssim_fwd, grid, dim3(256), 0, st, h, w, image_hwc, target_chw, weight, G, part);
@@ -206,6 +198,6 @@ extern "C" int slm_render_ssim_loss(int32_t h, int32_t w, const float* image_hwc
   const hipError_t f = hipFreeAsync(scratch, st);
   if (e == hipSuccess) e = f;
   if (e != hipSuccess)
-    return sfail(SLM_ERR_HIP, (std::string("slm_render_ssim_loss: ") + hipGetErrorString(e)).c_str());
+    return fail(SLM_ERR_HIP, std::string("slm_render_ssim_loss: ") + hipGetErrorString(e));
   return SLM_OK;
 }
