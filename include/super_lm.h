@@ -690,6 +690,40 @@ int slm_render_backward_ex(slm_render* r, const slm_render_params* p, const doub
  * runs float32).  h, w >= 6.  Allocates its scratch stream-ordered; does not synchronise. */
 int slm_render_ssim_loss(int32_t h, int32_t w, const float* image_hwc, const float* target_chw, double weight,
                          double* loss_out, double* grad_image, void* stream);
+
+/* Per-point radii (Pulsar's vert_rad is a float32 (N,) tensor; the surfel model carries one radius per surfel)
+ *   slm_render_points_radii    <- Pulsar's vert_rad as the caller's (N,) tensor
+ *   slm_gf_render_radii        <- the same for the deformed stable surfels of a GraphFit slot
+ *   slm_render_backward_radii  <- dL/dP, dL/dc and dL/dr of such a render
+ * The blend above with r_k, the float32 `radii[k]` widened to double, in place of `radius`: sphere k is hit when
+ * rho_k < r_k, its silhouette box is that of r_k (a sphere with Z^2 - r_k^2 <= 0 is a candidate of every pixel), and
+ *   w_k = (1 - rho_k/r_k) exp((zt_k - zt_max)/gamma).
+ * A row whose radius is not finite or not > 0 is culled like a centre outside [z_near, z_far]: it is hit nowhere, front_id
+ * never names it and its gradient rows are 0.  The order of the hits, the n_track cut, the tie rule, the background term and
+ * the float64 arithmetic are unchanged; with all radii equal to one float32 value v the results are bitwise those of the
+ * one-radius entries at radius = (double)v.  p->radius must still be valid (> 0, finite) and must still match at the
+ * backward, but the geometry does not read it.  The context keeps the radii with the centres, so a later backward does not
+ * read `radii` again.  Other arguments, the synchronisation and the reproducibility are those of slm_render_points /
+ * slm_gf_render.  radii: (N) float32 device; for slm_gf_render_radii indexed by surfel row like the colours (rows of
+ * unstable surfels are not read). */
+int slm_render_points_radii(slm_render* r, const slm_render_params* p, int32_t N, const void* points, const float* radii,
+                            const float* colors, int32_t color_stride, float* image, int32_t* front_id,
+                            int32_t* hit_count, void* stream);
+int slm_gf_render_radii(slm_gf* g, int32_t slot, slm_render* r, const slm_render_params* p, const float* radii,
+                        const float* colors, int32_t color_stride, float* image, int32_t* front_id, int32_t* hit_count,
+                        void* stream);
+/* slm_render_backward_ex with the radius gradient as well.  After a per-point forward, with s_k = g.(c_k - C)/W,
+ *   dL/dP_k and dL/dc_k as above with r_k in place of `radius`,
+ *   dL/dr_k = sum over the pixels k takes part in of  s_k e_k rho_k / r_k^2      (dw_k/dr_k = e_k rho_k / r_k^2)
+ * at the forward's hit sets (discrete).  The gradient passes the float32 radius unchanged.  grad_radii: (N) float64 device,
+ * 0 on culled and unstable rows.  Any of the three outputs may be NULL, not all three; each output is bitwise the same
+ * whichever others are requested, and grad_points / grad_colors equal those of slm_render_backward /
+ * slm_render_backward_ex, which after a per-point forward use the stored radii too.  After a forward with one radius it
+ * serves grad_points and grad_colors like slm_render_backward_ex and refuses a non-NULL grad_radii with SLM_ERR_INVALID
+ * ("slm_render_backward_radii: grad_radii after a forward with one radius").  The same two passes (one more slab double
+ * per tile-list entry), the same refusals otherwise.  Bitwise reproducible (no float atomics); does not synchronise. */
+int slm_render_backward_radii(slm_render* r, const slm_render_params* p, const double* grad_image, double* grad_points,
+                              double* grad_colors, double* grad_radii, void* stream);
 /* After slm_gf_bind_frame: binds dL/dP (N,3) float64 device, by surfel row, of an outside term (the render loss:
  * slm_render_backward of an slm_gf_render).  Every later evaluation of the slot -- slm_gf_eval_losses, slm_gf_loss_grad,
  * each iteration of slm_gf_run -- adds it to each stable surfel's dL/dP before the chain rule to the node rows and the

@@ -193,4 +193,4 @@ __device__ __forceinline__ d3 gf_skin_pos(const GfSlotDev& s, int i) {
 
 // slm_gf_render (slm_render.hip): the device descriptor of bound slot `slot` (its current deform_verts) and its
 // surfel count; SLM_OK or an error status with the text set.
-int gf_render_slot(slm_gf* g, int32_t slot, GfSlot** dev, int32_t* n_surfels);
+int gf_render_slot(slm_gf* g, int32_t slot, GfSlot** dev, int32_t* n_surfels, const char* who = "slm_gf_render");

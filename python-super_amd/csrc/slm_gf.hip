@@ -1119,9 +1119,9 @@ int slm_apply_update_gf_f64(int32_t N, int32_t J, int32_t K, double* sf_points, 
 
 }  // extern "C"
 
-int gf_render_slot(slm_gf* g, int32_t slot, GfSlot** dev, int32_t* n_surfels) {
-  if (!g || slot < 0 || slot >= (int)g->host.size()) return fail(SLM_ERR_INVALID, "slm_gf_render: bad slot");
-  if (!g->host[slot].bound) return fail(SLM_ERR_UNBOUND, "slm_gf_render: slm_gf_bind_frame first");
+int gf_render_slot(slm_gf* g, int32_t slot, GfSlot** dev, int32_t* n_surfels, const char* who) {
+  if (!g || slot < 0 || slot >= (int)g->host.size()) return fail(SLM_ERR_INVALID, std::string(who) + ": bad slot");
+  if (!g->host[slot].bound) return fail(SLM_ERR_UNBOUND, std::string(who) + ": slm_gf_bind_frame first");
   *dev = g->dev + slot;
   *n_surfels = g->host[slot].f.base.N;
   return SLM_OK;

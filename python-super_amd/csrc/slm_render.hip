@@ -22,6 +22,12 @@
 //   k_rn_bwd_point  per point: the slab entries of its tiles, found by binary search of its key, summed in tile order
 // slm_render_backward_ex adds the colour gradient in the same two passes (k_rn_bwd_entry<MODE>, k_rn_bwd_point_ex<MODE>):
 // the slab holds 6 doubles per entry with both gradients, 3 with one.
+//
+// Per-point radii (slm_render_points_radii, slm_gf_render_radii): the instantiations with PR = true read the radius of a
+// point from pos[].w, where k_rn_project<SRC, true> leaves the caller's float32 value (so a later backward does not
+// depend on the caller's buffer); a radius that is not finite or not > 0 culls its row.  The instantiations with
+// PR = false read the one double radius of the parameters and are the code they were before.  The radius gradient
+// (slm_render_backward_radii) is the MODE bit RN_BWD_RADII: one more double per slab entry, behind the others.
 #include <climits>
 #include <cmath>
 #include <cstring>
@@ -34,7 +40,7 @@
 
 struct slm_render {
   int H = 0, W = 0, cap = 0;
-  float4* pos = nullptr;                 // (cap) float32 centre, w unused
+  float4* pos = nullptr;                 // (cap) float32 centre; w: the point's radius after a per-point forward, else 0
   int4* box = nullptr;                   // (cap) inclusive pixel box x0, x1, y0, y1 (x0 > x1: culled)
   unsigned int* cnt = nullptr;           // (tiles) entries per tile
   unsigned long long* off = nullptr;     // (tiles + 1) exclusive scan of cnt
@@ -52,6 +58,7 @@ struct slm_render {
   int n_last = 0;                        // its point count
   unsigned long long total_last = 0;     // its tile-list entries
   int has_fwd = 0;                       // 1 after a forward that completed; cleared when one starts
+  int per_point_last = 0;                // 1 when that forward had per-point radii (pos[].w)
 };
 
 // the per-pixel record of a forward: float64 blend of the taken hits, and `cut`, the list position of the n_track-th hit
@@ -101,11 +108,12 @@ __device__ __forceinline__ double rn_rho(double X, double Y, double Z, double dx
   return sqrt(cx * cx + cy * cy + cz * cz) * inv_dn;
 }
 
-template <int SRC>
+template <int SRC, bool PR>
 __global__ void __launch_bounds__(256) k_rn_project(int N, const void* __restrict__ pts, GfSlot* __restrict__ gslot, RnCam cam,
                                                     float4* __restrict__ pos, int4* __restrict__ box,
                                                     unsigned int* __restrict__ cnt, const float* __restrict__ colors,
-                                                    int cstride, float4* __restrict__ col) {
+                                                    int cstride, float4* __restrict__ col,
+                                                    const float* __restrict__ radii) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= N) return;
   float X, Y, Z;
@@ -130,18 +138,27 @@ __global__ void __launch_bounds__(256) k_rn_project(int N, const void* __restric
     const float* c = colors + (size_t)i * cstride;
     col[i] = make_float4(c[0], c[1], c[2], 0.f);
   }
+  float rw = 0.f;
+  double r = cam.r;
+  if constexpr (PR) {   // the point's own radius, by row (rows of unstable surfels are not read); NaN, inf, <= 0: culled
+    if (live) {
+      rw = radii[i];
+      r = (double)rw;
+      live = rw > 0.f && rw < INFINITY;
+    }
+  }
   int4 b = make_int4(1, 0, 1, 0);   // empty
   if (live && (double)Z >= cam.zn && (double)Z <= cam.zf) {
     int x0, x1, y0, y1;
-    rn_range((double)X, (double)Z, cam.r, cam.f, cam.ccx, cam.w, x0, x1);
-    rn_range((double)Y, (double)Z, cam.r, cam.f, cam.ccy, cam.h, y0, y1);
+    rn_range((double)X, (double)Z, r, cam.f, cam.ccx, cam.w, x0, x1);
+    rn_range((double)Y, (double)Z, r, cam.f, cam.ccy, cam.h, y0, y1);
     if (x0 <= x1 && y0 <= y1) {
       b = make_int4(x0, x1, y0, y1);
       for (int ty = y0 / RN_TILE; ty <= y1 / RN_TILE; ++ty)
         for (int tx = x0 / RN_TILE; tx <= x1 / RN_TILE; ++tx) atomicAdd(cnt + ty * cam.tiles_x + tx, 1u);
     }
   }
-  pos[i] = make_float4(X, Y, Z, 0.f);
+  pos[i] = make_float4(X, Y, Z, rw);
   box[i] = b;
 }
 
@@ -215,6 +232,7 @@ __device__ __forceinline__ void rn_sort_lds(unsigned long long* s, const unsigne
   rn_bitonic(s, n2);
 }
 
+template <bool PR>
 __global__ void __launch_bounds__(256) k_rn_tile(RnCam cam, const unsigned long long* __restrict__ off,
                                                  unsigned long long* __restrict__ keys, unsigned long long* __restrict__ tmp,
                                                  const float4* __restrict__ pos, const int4* __restrict__ box,
@@ -292,14 +310,15 @@ __global__ void __launch_bounds__(256) k_rn_tile(RnCam cam, const unsigned long 
         const float4 p = spos[e];
         const double X = p.x, Y = p.y, Z = p.z;
         const double rho = rn_rho(X, Y, Z, dx, dy, inv_dn);
-        if (!(rho < cam.r)) continue;
+        const double r = PR ? (double)p.w : cam.r;
+        if (!(rho < r)) continue;
         const double zt = (cam.zf - Z) / zspan;
         const int id = sid[e];
         if (nh == 0) {
           zt_max = zt;
           first = id;
         }
-        const double wk = (1.0 - rho / cam.r) * exp((zt - zt_max) / cam.gamma);
+        const double wk = (1.0 - rho / r) * exp((zt - zt_max) / cam.gamma);
         const float* c = colors + (size_t)id * cstride;
         sw += wk;
         s0 += wk * (double)c[0];
@@ -339,22 +358,25 @@ __global__ void __launch_bounds__(256) k_rn_tile(RnCam cam, const unsigned long 
 
 // What a backward computes: the point gradient, the colour gradient, or both (template parameter of the backward kernels).
 // The slab holds 3 doubles per tile-list entry and output: the point partials first.
-enum { RN_BWD_POINTS = 1, RN_BWD_COLORS = 2 };
+enum { RN_BWD_POINTS = 1, RN_BWD_COLORS = 2, RN_BWD_RADII = 4 };
 
 // Backward, pass 1 (see the top of the file): one workgroup per tile.  Lane t stages pixel t of the tile -- its ray and the
 // coefficients a = g / W, b = g.C / W of s_k = g.(c_k - C) / W, or cut = -1 when the pixel has no hit or g = 0 -- then every
 // lane takes list entries e = t, t + 256, ... and sums, in row-major order over the pixels of the entry's box inside the tile
 // that it reaches (position <= cut, rho < r: the forward's decisions), s_k ( -(e_k / r) drho/dP - w_k / (gamma zspan) z )
-// (RN_BWD_POINTS) and a w_k = g w_k / W (RN_BWD_COLORS).
-template <int MODE>
+// (RN_BWD_POINTS), a w_k = g w_k / W (RN_BWD_COLORS) and s_k e_k rho / r^2 (RN_BWD_RADII, per-point radii only).  With PR the
+// radius r is the point's (pos[].w), else the parameters'.
+template <int MODE, bool PR>
 __global__ void __launch_bounds__(256) k_rn_bwd_entry(RnCam cam, const unsigned long long* __restrict__ off,
                                                       const unsigned long long* __restrict__ keys, const float4* __restrict__ pos,
                                                       const int4* __restrict__ box, const float4* __restrict__ col,
                                                       const RnPix* __restrict__ pix, const double* __restrict__ gimg,
                                                       double* __restrict__ slab) {
-  constexpr bool GP = (MODE & RN_BWD_POINTS) != 0, GC = (MODE & RN_BWD_COLORS) != 0;
-  constexpr int S = (GP ? 3 : 0) + (GC ? 3 : 0);
-  __shared__ double sdx[256], sdy[256], sinv[256], szt[256], sa0[256], sa1[256], sa2[256], sb[GP ? 256 : 1];
+  constexpr bool GP = (MODE & RN_BWD_POINTS) != 0, GC = (MODE & RN_BWD_COLORS) != 0, GR = (MODE & RN_BWD_RADII) != 0;
+  constexpr bool GS = GP || GR;   // s_k is needed: the colour copy and b
+  constexpr int S = (GP ? 3 : 0) + (GC ? 3 : 0) + (GR ? 1 : 0);
+  static_assert(PR || !GR, "the radius gradient belongs to a per-point forward");
+  __shared__ double sdx[256], sdy[256], sinv[256], szt[256], sa0[256], sa1[256], sa2[256], sb[GS ? 256 : 1];
   __shared__ int scut[256];
   const int tile = blockIdx.y * cam.tiles_x + blockIdx.x;
   const unsigned long long base = off[tile];
@@ -373,7 +395,7 @@ __global__ void __launch_bounds__(256) k_rn_bwd_entry(RnCam cam, const unsigned 
         sa0[t] = g0 / rec.W;
         sa1[t] = g1 / rec.W;
         sa2[t] = g2 / rec.W;
-        if constexpr (GP) sb[t] = (g0 * rec.c0 + g1 * rec.c1 + g2 * rec.c2) / rec.W;
+        if constexpr (GS) sb[t] = (g0 * rec.c0 + g1 * rec.c1 + g2 * rec.c2) / rec.W;
         szt[t] = rec.zt_max;
         double dx, dy, inv_dn;
         rn_ray(cam, i, j, dx, dy, inv_dn);
@@ -391,10 +413,11 @@ __global__ void __launch_bounds__(256) k_rn_bwd_entry(RnCam cam, const unsigned 
     const int4 b = box[id];
     const float4 p = pos[id];
     float4 c = make_float4(0.f, 0.f, 0.f, 0.f);
-    if constexpr (GP) c = col[id];
+    if constexpr (GS) c = col[id];
     const double X = p.x, Y = p.y, Z = p.z;
     const double zt = (cam.zf - Z) / zspan;
-    double gx = 0.0, gy = 0.0, gz = 0.0, q0 = 0.0, q1 = 0.0, q2 = 0.0;
+    const double r = PR ? (double)p.w : cam.r;
+    double gx = 0.0, gy = 0.0, gz = 0.0, q0 = 0.0, q1 = 0.0, q2 = 0.0, gr = 0.0;
     const int i0 = max(b.z, ty0), i1 = min(b.w, ty0 + RN_TILE - 1), j0 = max(b.x, tx0), j1 = min(b.y, tx0 + RN_TILE - 1);
     for (int i = i0; i <= i1; ++i)
       for (int j = j0; j <= j1; ++j) {
@@ -402,15 +425,17 @@ __global__ void __launch_bounds__(256) k_rn_bwd_entry(RnCam cam, const unsigned 
         if (e > scut[t]) continue;
         const double dx = sdx[t], dy = sdy[t], inv_dn = sinv[t];
         const double rho = rn_rho(X, Y, Z, dx, dy, inv_dn);
-        if (!(rho < cam.r)) continue;
-        const double ek = exp((zt - szt[t]) / cam.gamma), wk = (1.0 - rho / cam.r) * ek;
+        if (!(rho < r)) continue;
+        const double ek = exp((zt - szt[t]) / cam.gamma), wk = (1.0 - rho / r) * ek;
+        double sk = 0.0;
+        if constexpr (GS) sk = sa0[t] * (double)c.x + sa1[t] * (double)c.y + sa2[t] * (double)c.z - sb[t];
+        if constexpr (GR) gr += sk * ek * rho / (r * r);
         if constexpr (GP) {
-          const double sk = sa0[t] * (double)c.x + sa1[t] * (double)c.y + sa2[t] * (double)c.z - sb[t];
           if (rho > 0.0) {
             // drho/dP = (P - (P.d^) d^) / rho, d^ = d / |d|
             const double hx = dx * inv_dn, hy = dy * inv_dn, hz = inv_dn;
             const double pd = X * hx + Y * hy + Z * hz;
-            const double q = -sk * ek / (cam.r * rho);
+            const double q = -sk * ek / (r * rho);
             gx += q * (X - pd * hx);
             gy += q * (Y - pd * hy);
             gz += q * (Z - pd * hz);
@@ -430,10 +455,11 @@ __global__ void __launch_bounds__(256) k_rn_bwd_entry(RnCam cam, const unsigned 
       o[2] = gz;
     }
     if constexpr (GC) {
-      o[S - 3] = q0;
-      o[S - 2] = q1;
-      o[S - 1] = q2;
+      o[(GP ? 3 : 0)] = q0;
+      o[(GP ? 3 : 0) + 1] = q1;
+      o[(GP ? 3 : 0) + 2] = q2;
     }
+    if constexpr (GR) o[S - 1] = gr;
   }
 }
 
@@ -494,22 +520,31 @@ __global__ void __launch_bounds__(256) k_rn_bwd_point(int N, int tiles_x, const 
   out[3 * (size_t)i + 2] = gz;
 }
 
-// Backward, pass 2 of slm_render_backward_ex with colours (MODE has RN_BWD_COLORS): per point, dL/dc and, with
-// RN_BWD_POINTS, dL/dP; either output may be NULL.
+// Backward, pass 2 of every MODE but RN_BWD_POINTS alone: per point, the sums of the slab's S doubles -- dL/dP (3,
+// RN_BWD_POINTS), dL/dc (3, RN_BWD_COLORS), dL/dr (1, RN_BWD_RADII), in that order; an output that is NULL is not written.
 template <int MODE>
 __global__ void __launch_bounds__(256) k_rn_bwd_point_ex(int N, int tiles_x, const unsigned long long* __restrict__ off,
                                                          const unsigned long long* __restrict__ keys, const float4* __restrict__ pos,
                                                          const int4* __restrict__ box, const double* __restrict__ slab,
-                                                         double* __restrict__ out_p, double* __restrict__ out_c) {
-  constexpr int S = (MODE & RN_BWD_POINTS) ? 6 : 3;
+                                                         double* __restrict__ out_p, double* __restrict__ out_c,
+                                                         double* __restrict__ out_r) {
+  constexpr int OC = (MODE & RN_BWD_POINTS) ? 3 : 0;
+  constexpr int S = OC + ((MODE & RN_BWD_COLORS) ? 3 : 0) + ((MODE & RN_BWD_RADII) ? 1 : 0);
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= N) return;
   double g[S];
   rn_bwd_gather<S>(i, tiles_x, off, keys, pos, box, slab, g);
-  if (out_p)
-    for (int q = 0; q < 3; ++q) out_p[3 * (size_t)i + q] = g[q];
-  if (out_c)
-    for (int q = 0; q < 3; ++q) out_c[3 * (size_t)i + q] = g[S - 3 + q];
+  if constexpr ((MODE & RN_BWD_POINTS) != 0) {
+    if (out_p)
+      for (int q = 0; q < 3; ++q) out_p[3 * (size_t)i + q] = g[q];
+  }
+  if constexpr ((MODE & RN_BWD_COLORS) != 0) {
+    if (out_c)
+      for (int q = 0; q < 3; ++q) out_c[3 * (size_t)i + q] = g[OC + q];
+  }
+  if constexpr ((MODE & RN_BWD_RADII) != 0) {
+    if (out_r) out_r[i] = g[S - 1];
+  }
 }
 
 // the device arrays of a context; sizes of slm_render_create: [0] points + 1, [1] tiles, [2] tiles + 1, [3] pixels
@@ -549,9 +584,22 @@ bool rn_same_params(const slm_render_params& a, const slm_render_params& b) {
          a.bg[2] == b.bg[2];
 }
 
+// the projection of one source, with the parameters' radius or (per_point) the points' own
+template <int SRC>
+void rn_project(dim3 grid, hipStream_t st, int N, const void* pts, GfSlot* gslot, const RnCam& cam, slm_render* r,
+                const float* colors, int cstride, const float* radii, bool per_point) {
+  if (per_point)
+    hipLaunchKernelGGL((k_rn_project<SRC, true>), grid, dim3(256), 0, st, N, pts, gslot, cam, r->pos, r->box, r->cnt, colors,
+                       cstride, r->col, radii);
+  else
+    hipLaunchKernelGGL((k_rn_project<SRC, false>), grid, dim3(256), 0, st, N, pts, gslot, cam, r->pos, r->box, r->cnt, colors,
+                       cstride, r->col, radii);
+}
+
+// per_point: radii (N) float32 device holds one radius per point (by surfel row for RN_SRC_GF); else p->radius serves all
 int render_common(slm_render* r, const slm_render_params* p, int N, int src, const void* pts, GfSlot* gslot,
-                  const float* colors, int cstride, float* image, int32_t* front_id, int32_t* hit_count, void* stream,
-                  const char* who) {
+                  bool per_point, const float* radii, const float* colors, int cstride, float* image, int32_t* front_id,
+                  int32_t* hit_count, void* stream, const char* who) {
   std::string w(who);
   if (!r || !p || !image) return fail(SLM_ERR_INVALID, w + ": null argument");
   if (p->width < 1 || p->height < 1 || p->width > r->W || p->height > r->H)
@@ -572,11 +620,11 @@ int render_common(slm_render* r, const slm_render_params* p, int N, int src, con
   const dim3 gp((N + 255) / 256);
   if (N > 0) {
     if (src == RN_SRC_F32)
-      hipLaunchKernelGGL(k_rn_project<RN_SRC_F32>, gp, dim3(256), 0, st, N, pts, gslot, cam, r->pos, r->box, r->cnt, colors, cstride, r->col);
+      rn_project<RN_SRC_F32>(gp, st, N, pts, gslot, cam, r, colors, cstride, radii, per_point);
     else if (src == RN_SRC_F64)
-      hipLaunchKernelGGL(k_rn_project<RN_SRC_F64>, gp, dim3(256), 0, st, N, pts, gslot, cam, r->pos, r->box, r->cnt, colors, cstride, r->col);
+      rn_project<RN_SRC_F64>(gp, st, N, pts, gslot, cam, r, colors, cstride, radii, per_point);
     else
-      hipLaunchKernelGGL(k_rn_project<RN_SRC_GF>, gp, dim3(256), 0, st, N, pts, gslot, cam, r->pos, r->box, r->cnt, colors, cstride, r->col);
+      rn_project<RN_SRC_GF>(gp, st, N, pts, gslot, cam, r, colors, cstride, radii, per_point);
   }
   hipLaunchKernelGGL(k_rn_scan, dim3(1), dim3(1024), 0, st, tiles, r->cnt, r->off, r->cur);
   HIPCHK(hipGetLastError());
@@ -589,44 +637,67 @@ int render_common(slm_render* r, const slm_render_params* p, int N, int src, con
   HIPCHK(grow(r->tmp, r->cap_tmp, total, want));
   if (total > 0)
     hipLaunchKernelGGL(k_rn_scatter, gp, dim3(256), 0, st, N, cam.tiles_x, r->pos, r->box, r->cur, r->keys);
-  hipLaunchKernelGGL(k_rn_tile, dim3(cam.tiles_x, tiles_y), dim3(256), 0, st, cam, r->off, r->keys, r->tmp, r->pos, r->box,
-                     colors, cstride, image, front_id, hit_count, r->pix);
+  if (per_point)
+    hipLaunchKernelGGL(k_rn_tile<true>, dim3(cam.tiles_x, tiles_y), dim3(256), 0, st, cam, r->off, r->keys, r->tmp, r->pos,
+                       r->box, colors, cstride, image, front_id, hit_count, r->pix);
+  else
+    hipLaunchKernelGGL(k_rn_tile<false>, dim3(cam.tiles_x, tiles_y), dim3(256), 0, st, cam, r->off, r->keys, r->tmp, r->pos,
+                       r->box, colors, cstride, image, front_id, hit_count, r->pix);
   HIPCHK(hipGetLastError());
   r->last = *p;
+  r->per_point_last = per_point;
   r->n_last = N;
   r->total_last = total;
   r->has_fwd = 1;
   return SLM_OK;
 }
 
-// the two backward launches of the last forward on r (checked by the caller; N > 0), S = 3 or 6 slab doubles per entry
-int rn_backward(slm_render* r, const slm_render_params* p, const double* grad_image, double* grad_points,
-                double* grad_colors, hipStream_t st) {
+// the two backward launches of one MODE for a forward with (PR) or without per-point radii
+template <int MODE, bool PR>
+void rn_bwd_launch(slm_render* r, const RnCam& cam, int tiles_y, const double* grad_image, double* grad_points,
+                   double* grad_colors, double* grad_radii, hipStream_t st) {
   const int N = r->n_last;
+  const dim3 gt(cam.tiles_x, tiles_y), gp((N + 255) / 256), b(256);
+  if (r->total_last > 0)
+    hipLaunchKernelGGL((k_rn_bwd_entry<MODE, PR>), gt, b, 0, st, cam, r->off, r->keys, r->pos, r->box, r->col, r->pix,
+                       grad_image, r->slab);
+  if constexpr (MODE == RN_BWD_POINTS)
+    hipLaunchKernelGGL(k_rn_bwd_point, gp, b, 0, st, N, cam.tiles_x, r->off, r->keys, r->pos, r->box, r->slab, grad_points);
+  else
+    hipLaunchKernelGGL(k_rn_bwd_point_ex<MODE>, gp, b, 0, st, N, cam.tiles_x, r->off, r->keys, r->pos, r->box, r->slab,
+                       grad_points, grad_colors, grad_radii);
+}
+
+// one MODE for the forward that r holds.  A MODE with RN_BWD_RADII exists only with PR (the caller has refused grad_radii after
+// a one-radius forward); this is a template so that the branch not taken for such a MODE is discarded, not instantiated.
+template <int MODE>
+void rn_bwd_mode(slm_render* r, const RnCam& cam, int tiles_y, const double* grad_image, double* grad_points,
+                 double* grad_colors, double* grad_radii, hipStream_t st) {
+  if (r->per_point_last)
+    rn_bwd_launch<MODE, true>(r, cam, tiles_y, grad_image, grad_points, grad_colors, grad_radii, st);
+  else if constexpr ((MODE & RN_BWD_RADII) == 0)
+    rn_bwd_launch<MODE, false>(r, cam, tiles_y, grad_image, grad_points, grad_colors, grad_radii, st);
+}
+
+// the backward of the last forward on r (checked by the caller; N > 0, one output at least; grad_radii only after a
+// per-point forward): 3 slab doubles per tile-list entry for the points, 3 for the colours, 1 for the radii
+int rn_backward(slm_render* r, const slm_render_params* p, const double* grad_image, double* grad_points,
+                double* grad_colors, double* grad_radii, hipStream_t st) {
   const RnCam cam = rn_cam(p);
   const int tiles_y = (p->height + RN_TILE - 1) / RN_TILE;
-  const int mode = (grad_points ? RN_BWD_POINTS : 0) | (grad_colors ? RN_BWD_COLORS : 0);
-  const size_t S = mode == (RN_BWD_POINTS | RN_BWD_COLORS) ? 6 : 3;
+  const int mode = (grad_points ? RN_BWD_POINTS : 0) | (grad_colors ? RN_BWD_COLORS : 0) | (grad_radii ? RN_BWD_RADII : 0);
+  const size_t S = (grad_points ? 3 : 0) + (grad_colors ? 3 : 0) + (grad_radii ? 1 : 0);
   const unsigned long long total = r->total_last;
   HIPCHK(grow(r->slab, r->cap_slab, S * total, S * ((size_t)total + total / 4 + 1024)));
-  const dim3 gt(cam.tiles_x, tiles_y), gp((N + 255) / 256), b(256);
-  if (mode == RN_BWD_POINTS) {
-    if (total > 0)
-      hipLaunchKernelGGL(k_rn_bwd_entry<RN_BWD_POINTS>, gt, b, 0, st, cam, r->off, r->keys, r->pos, r->box, r->col, r->pix,
-                         grad_image, r->slab);
-    hipLaunchKernelGGL(k_rn_bwd_point, gp, b, 0, st, N, cam.tiles_x, r->off, r->keys, r->pos, r->box, r->slab, grad_points);
-  } else if (mode == RN_BWD_COLORS) {
-    if (total > 0)
-      hipLaunchKernelGGL(k_rn_bwd_entry<RN_BWD_COLORS>, gt, b, 0, st, cam, r->off, r->keys, r->pos, r->box, r->col, r->pix,
-                         grad_image, r->slab);
-    hipLaunchKernelGGL(k_rn_bwd_point_ex<RN_BWD_COLORS>, gp, b, 0, st, N, cam.tiles_x, r->off, r->keys, r->pos, r->box,
-                       r->slab, grad_points, grad_colors);
-  } else {
-    if (total > 0)
-      hipLaunchKernelGGL(k_rn_bwd_entry<RN_BWD_POINTS | RN_BWD_COLORS>, gt, b, 0, st, cam, r->off, r->keys, r->pos, r->box,
-                         r->col, r->pix, grad_image, r->slab);
-    hipLaunchKernelGGL(k_rn_bwd_point_ex<RN_BWD_POINTS | RN_BWD_COLORS>, gp, b, 0, st, N, cam.tiles_x, r->off, r->keys,
-                       r->pos, r->box, r->slab, grad_points, grad_colors);
+  switch (mode) {
+    case 1: rn_bwd_mode<1>(r, cam, tiles_y, grad_image, grad_points, grad_colors, grad_radii, st); break;
+    case 2: rn_bwd_mode<2>(r, cam, tiles_y, grad_image, grad_points, grad_colors, grad_radii, st); break;
+    case 3: rn_bwd_mode<3>(r, cam, tiles_y, grad_image, grad_points, grad_colors, grad_radii, st); break;
+    case 4: rn_bwd_mode<4>(r, cam, tiles_y, grad_image, grad_points, grad_colors, grad_radii, st); break;
+    case 5: rn_bwd_mode<5>(r, cam, tiles_y, grad_image, grad_points, grad_colors, grad_radii, st); break;
+    case 6: rn_bwd_mode<6>(r, cam, tiles_y, grad_image, grad_points, grad_colors, grad_radii, st); break;
+    case 7: rn_bwd_mode<7>(r, cam, tiles_y, grad_image, grad_points, grad_colors, grad_radii, st); break;
+    default: break;
   }
   HIPCHK(hipGetLastError());
   return SLM_OK;
@@ -666,8 +737,17 @@ int slm_render_destroy(slm_render* r) {
 int slm_render_points(slm_render* r, const slm_render_params* p, int32_t N, const void* points, const float* colors,
                       int32_t color_stride, float* image, int32_t* front_id, int32_t* hit_count, void* stream) {
   if (!p) return fail(SLM_ERR_INVALID, "slm_render_points: null argument");
-  return render_common(r, p, N, p->points_f64 ? RN_SRC_F64 : RN_SRC_F32, points, nullptr, colors, color_stride, image,
-                       front_id, hit_count, stream, "slm_render_points");
+  return render_common(r, p, N, p->points_f64 ? RN_SRC_F64 : RN_SRC_F32, points, nullptr, false, nullptr, colors,
+                       color_stride, image, front_id, hit_count, stream, "slm_render_points");
+}
+
+int slm_render_points_radii(slm_render* r, const slm_render_params* p, int32_t N, const void* points, const float* radii,
+                            const float* colors, int32_t color_stride, float* image, int32_t* front_id,
+                            int32_t* hit_count, void* stream) {
+  if (!r || !p || !image) return fail(SLM_ERR_INVALID, "slm_render_points_radii: null argument");
+  if (N > 0 && !radii) return fail(SLM_ERR_INVALID, "slm_render_points_radii: null radii");
+  return render_common(r, p, N, p->points_f64 ? RN_SRC_F64 : RN_SRC_F32, points, nullptr, true, radii, colors, color_stride,
+                       image, front_id, hit_count, stream, "slm_render_points_radii");
 }
 
 int slm_gf_render(slm_gf* g, int32_t slot, slm_render* r, const slm_render_params* p, const float* colors,
@@ -676,8 +756,21 @@ int slm_gf_render(slm_gf* g, int32_t slot, slm_render* r, const slm_render_param
   int32_t n = 0;
   const int rc = gf_render_slot(g, slot, &dev, &n);
   if (rc != SLM_OK) return rc;
-  return render_common(r, p, n, RN_SRC_GF, nullptr, dev, colors, color_stride, image, front_id, hit_count, stream,
-                       "slm_gf_render");
+  return render_common(r, p, n, RN_SRC_GF, nullptr, dev, false, nullptr, colors, color_stride, image, front_id, hit_count,
+                       stream, "slm_gf_render");
+}
+
+int slm_gf_render_radii(slm_gf* g, int32_t slot, slm_render* r, const slm_render_params* p, const float* radii,
+                        const float* colors, int32_t color_stride, float* image, int32_t* front_id, int32_t* hit_count,
+                        void* stream) {
+  if (!g || !r || !p || !image) return fail(SLM_ERR_INVALID, "slm_gf_render_radii: null argument");
+  if (!radii) return fail(SLM_ERR_INVALID, "slm_gf_render_radii: null radii");
+  GfSlot* dev = nullptr;
+  int32_t n = 0;
+  const int rc = gf_render_slot(g, slot, &dev, &n, "slm_gf_render_radii");
+  if (rc != SLM_OK) return rc;
+  return render_common(r, p, n, RN_SRC_GF, nullptr, dev, true, radii, colors, color_stride, image, front_id, hit_count,
+                       stream, "slm_gf_render_radii");
 }
 
 int slm_render_backward(slm_render* r, const slm_render_params* p, const double* grad_image, double* grad_points,
@@ -689,7 +782,7 @@ int slm_render_backward(slm_render* r, const slm_render_params* p, const double*
   const int N = r->n_last;
   if (N == 0) return SLM_OK;
   if (!grad_points) return fail(SLM_ERR_INVALID, "slm_render_backward: null grad_points");
-  return rn_backward(r, p, grad_image, grad_points, nullptr, (hipStream_t)stream);
+  return rn_backward(r, p, grad_image, grad_points, nullptr, nullptr, (hipStream_t)stream);
 }
 
 int slm_render_backward_ex(slm_render* r, const slm_render_params* p, const double* grad_image, double* grad_points,
@@ -700,7 +793,21 @@ int slm_render_backward_ex(slm_render* r, const slm_render_params* p, const doub
     return fail(SLM_ERR_INVALID, "slm_render_backward_ex: parameters differ from those of the last forward");
   if (r->n_last == 0) return SLM_OK;
   if (!grad_points && !grad_colors) return fail(SLM_ERR_INVALID, "slm_render_backward_ex: null grad_points and grad_colors");
-  return rn_backward(r, p, grad_image, grad_points, grad_colors, (hipStream_t)stream);
+  return rn_backward(r, p, grad_image, grad_points, grad_colors, nullptr, (hipStream_t)stream);
+}
+
+int slm_render_backward_radii(slm_render* r, const slm_render_params* p, const double* grad_image, double* grad_points,
+                              double* grad_colors, double* grad_radii, void* stream) {
+  if (!r || !p || !grad_image) return fail(SLM_ERR_INVALID, "slm_render_backward_radii: null argument");
+  if (!r->has_fwd) return fail(SLM_ERR_INVALID, "slm_render_backward_radii: no completed forward on this context");
+  if (!rn_same_params(*p, r->last))
+    return fail(SLM_ERR_INVALID, "slm_render_backward_radii: parameters differ from those of the last forward");
+  if (grad_radii && !r->per_point_last)
+    return fail(SLM_ERR_INVALID, "slm_render_backward_radii: grad_radii after a forward with one radius");
+  if (r->n_last == 0) return SLM_OK;
+  if (!grad_points && !grad_colors && !grad_radii)
+    return fail(SLM_ERR_INVALID, "slm_render_backward_radii: null grad_points, grad_colors and grad_radii");
+  return rn_backward(r, p, grad_image, grad_points, grad_colors, grad_radii, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -38,6 +38,7 @@ EXPORTS = [
     "slm_abi_version", "slm_abi_check", "slm_debug_dag_timeout", "slm_debug_dag_abort", "slm_prepare_model", "slm_discard_prepared", "slm_debug_read_plan",
     "slm_render_create", "slm_render_destroy", "slm_render_points", "slm_gf_render",
     "slm_render_backward", "slm_render_ssim_loss", "slm_gf_bind_point_grad", "slm_render_backward_ex",
+    "slm_render_points_radii", "slm_gf_render_radii", "slm_render_backward_radii",
 ]
 
 
@@ -252,6 +253,9 @@ def load():
         "slm_gf_render": [vp, i32, vp, C.POINTER(SlmRenderParams), vp, i32, vp, vp, vp, vp],
         "slm_render_backward": [vp, C.POINTER(SlmRenderParams), vp, vp, vp],
         "slm_render_backward_ex": [vp, C.POINTER(SlmRenderParams), vp, vp, vp, vp],
+        "slm_render_points_radii": [vp, C.POINTER(SlmRenderParams), i32, vp, vp, vp, i32, vp, vp, vp, vp],
+        "slm_gf_render_radii": [vp, i32, vp, C.POINTER(SlmRenderParams), vp, vp, i32, vp, vp, vp, vp],
+        "slm_render_backward_radii": [vp, C.POINTER(SlmRenderParams), vp, vp, vp, vp, vp],
         "slm_render_ssim_loss": [i32, i32, vp, vp, dbl, vp, vp, vp],
         "slm_gf_bind_point_grad": [vp, i32, vp, vp],
         "slm_gf_get_deform": [vp, i32, vp, vp],

@@ -29,6 +29,10 @@ raises for the flag.  Every iteration renders the deformed stable surfels (slm_g
 ``sf_corr_match_renderimg`` that one render also feeds the flow network -- scores the SSIM-11 loss against
 ``inputs[("color",0)]`` with its image gradient (slm_render_ssim_loss), back-propagates it to the surfels
 (slm_render_backward), binds that (slm_gf_bind_point_grad) and takes one evaluation and step.
+
+``opt.renderer_surfel_radii`` (absent or False: nothing changes) renders every surfel with its own radius,
+``src.radii * opt.renderer_radii_scale`` (default 1.0) as float32 by surfel row (slm_gf_render_radii), in place of the one
+``opt.renderer_rad``: the same render feeds the render loss and ``sf_corr_match_renderimg``.  The radii are not optimised.
 """
 from __future__ import annotations
 
@@ -77,6 +81,11 @@ class GraphFit:
             if shard_surfels or world is not None:
                 raise NotImplementedError("super_amd.GraphFit: opt.sf_corr_match_renderimg on surfel-sharded frames")
         self._render_ctx = None
+        # opt-in: the renders of this class give every surfel its own radius, src.radii * renderer_radii_scale
+        # (slm_gf_render_radii), instead of opt.renderer_rad; the radii are not optimised (no radius gradient is asked for)
+        self.surfel_radii = bool(getattr(opt, "renderer_surfel_radii", False))
+        self.radii_scale = float(getattr(opt, "renderer_radii_scale", 1.0))
+        self._render_radii = None
         self.valid_margin = 1
         self.optim = opt.optimizer
         self.Niter = opt.num_optimize_iterations
@@ -213,6 +222,11 @@ class GraphFit:
                 raise ValueError(f"flow must be (1,2,{bf.c.H},{bf.c.W}), got {tuple(fl.shape)}")
             keep.append(fl)
             _lib.check(self.lib.slm_gf_bind_flow(self.h, slot, _dev_ptr(fl), _stream_ptr(dev)), "slm_gf_bind_flow")
+        if self.surfel_radii and slot == 0:      # float32 by surfel row, like Pulsar's vert_rad
+            self._render_radii = (src.radii.detach() * self.radii_scale).to(device=dev, dtype=torch.float32).contiguous()
+            if tuple(self._render_radii.shape) != (bf.c.N,):
+                raise ValueError(f"src.radii must be ({bf.c.N},), got {tuple(src.radii.shape)}")
+            keep.append(self._render_radii)
         self._keep[slot] = keep
         return bf
 
@@ -305,7 +319,9 @@ class GraphFit:
         return self._render_deformed_hwc(inputs, colors)[0].permute(2, 0, 1).unsqueeze(0)
 
     def _render_deformed_hwc(self, inputs, colors):
-        """``render_deformed`` as the (h,w,3) float32 image, with the render parameters."""
+        """``render_deformed`` as the (h,w,3) float32 image, with the render parameters.  With
+        ``opt.renderer_surfel_radii`` every surfel has its own radius (bound by ``_bind``); ``opt.renderer_rad`` then
+        only has to be valid."""
         from .renderer import DEFAULT_RAD, RenderContext, render_params
         bf = self._keep[0][0]
         H, W = bf.c.H, bf.c.W
@@ -317,8 +333,13 @@ class GraphFit:
         img = torch.empty((p.height, p.width, 3), dtype=torch.float32, device=bf.device)
         ctx.last_n = 0
         ctx.serial += 1
-        _lib.check(self.lib.slm_gf_render(self.h, 0, ctx.h, C.byref(p), _dev_ptr(colors), int(colors.stride(0)),
-                                          _dev_ptr(img), None, None, _stream_ptr(bf.device)), "slm_gf_render")
+        if self.surfel_radii:
+            _lib.check(self.lib.slm_gf_render_radii(self.h, 0, ctx.h, C.byref(p), _dev_ptr(self._render_radii),
+                                                    _dev_ptr(colors), int(colors.stride(0)), _dev_ptr(img), None, None,
+                                                    _stream_ptr(bf.device)), "slm_gf_render_radii")
+        else:
+            _lib.check(self.lib.slm_gf_render(self.h, 0, ctx.h, C.byref(p), _dev_ptr(colors), int(colors.stride(0)),
+                                              _dev_ptr(img), None, None, _stream_ptr(bf.device)), "slm_gf_render")
         ctx.last_n = bf.c.N
         return img, p
 

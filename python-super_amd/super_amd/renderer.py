@@ -13,6 +13,12 @@ the points and the colours, the exact derivative of THIS blend (``slm_render_bac
 (unpinned, hence opt-in).  The context keeps only its last forward; the backward of an earlier render re-renders its
 saved inputs first (renders are bitwise reproducible, so the hit sets are the same).
 
+Per-point radii: Pulsar's ``vert_rad`` is a float32 (N,) tensor, which the reference fills with one constant.  Here a
+``rad`` of shape (N,) gives every point its own radius (``slm_render_points_radii``; a radius that is not finite or not
+> 0 culls its point), and with ``differentiable=True`` an (N,) ``rad`` that requires grad gets dL/drad
+(``slm_render_backward_radii``).  ``opt.renderer_surfel_radii`` makes ``render_`` / ``render_img`` and GraphFit render the
+surfels with their own radii, ``sf.radii * opt.renderer_radii_scale``.
+
 The render loss of GraphFit (``opt.render_loss``, deform_mesh.py:113-123) has two native pieces here:
 ``render_backward`` -- dL/dpoints of the last render on a context, the exact derivative of THIS blend (Pulsar's own
 backward is not pinned) -- and ``ssim_render_loss`` -- monodepth2's SSIM-11 loss with the reference's mask,
@@ -112,6 +118,14 @@ def _colors_arg(colors, n, device):
     return c, int(c.stride(0))
 
 
+def _radii_arg(radii, n, device):
+    """(N,) float32 contiguous radii on ``device`` (Pulsar's vert_rad is float32)"""
+    r = radii.detach()
+    if r.dim() != 1 or r.shape[0] != n:
+        raise ValueError(f"radii must be (N,) with N = {n}, got {tuple(r.shape)}")
+    return r.to(device=device, dtype=torch.float32).contiguous()
+
+
 def _check_no_grad(*ts):
     for t in ts:
         if torch.is_tensor(t) and t.requires_grad:
@@ -119,14 +133,15 @@ def _check_no_grad(*ts):
                                "gradient is render_backward); pass tensors that do not require grad")
 
 
-def render_points(ctx, params, points, colors, with_info=False):
+def render_points(ctx, params, points, colors, with_info=False, radii=None):
     """Render (N,3) ``points`` (float32 or float64) with (N,3) ``colors``: (h,w,3) float32 on the device, and with
-    ``with_info`` also the (h,w) int32 front-most row (-1: nothing hit) and hit count (<= n_track)."""
-    _check_no_grad(points, colors)
-    return _render(ctx, params, points, colors, with_info)
+    ``with_info`` also the (h,w) int32 front-most row (-1: nothing hit) and hit count (<= n_track).  ``radii`` (N,), read
+    as float32: one radius per point instead of ``params.radius`` (``slm_render_points_radii``)."""
+    _check_no_grad(points, colors, radii)
+    return _render(ctx, params, points, colors, with_info, radii)
 
 
-def _render(ctx, params, points, colors, with_info=False):
+def _render(ctx, params, points, colors, with_info=False, radii=None):
     dev = points.device
     n = int(points.shape[0])
     if points.dim() != 2 or points.shape[1] != 3:
@@ -137,6 +152,7 @@ def _render(ctx, params, points, colors, with_info=False):
     pts = pts.contiguous()
     params.points_f64 = int(pts.dtype == torch.float64)
     col, stride = _colors_arg(colors, n, dev)
+    rad = None if radii is None else _radii_arg(radii, n, dev)
     ctx.reserve(n)
     img = torch.empty((params.height, params.width, 3), dtype=torch.float32, device=dev)
     fid = cnt = None
@@ -146,8 +162,13 @@ def _render(ctx, params, points, colors, with_info=False):
     ptr = lambda t: _dev_ptr(t) if t is not None and t.numel() else None
     ctx.last_n = 0
     ctx.serial += 1
-    _lib.check(ctx.lib.slm_render_points(ctx.h, C.byref(params), n, ptr(pts), ptr(col), stride, _dev_ptr(img),
-                                         ptr(fid), ptr(cnt), _stream_ptr(dev)), "slm_render_points")
+    if rad is None:
+        _lib.check(ctx.lib.slm_render_points(ctx.h, C.byref(params), n, ptr(pts), ptr(col), stride, _dev_ptr(img),
+                                             ptr(fid), ptr(cnt), _stream_ptr(dev)), "slm_render_points")
+    else:
+        _lib.check(ctx.lib.slm_render_points_radii(ctx.h, C.byref(params), n, ptr(pts), ptr(rad), ptr(col), stride,
+                                                   _dev_ptr(img), ptr(fid), ptr(cnt), _stream_ptr(dev)),
+                   "slm_render_points_radii")
     ctx.last_n = n
     return (img, fid, cnt) if with_info else img
 
@@ -168,12 +189,9 @@ def render_backward(ctx, params, grad_image):
     return out
 
 
-def render_backward_ex(ctx, params, grad_image, points=True, colors=True):
-    """``render_backward`` with the colour gradient: (dL/dpoints or None, dL/dcolors or None), each (N,3) float64, for
-    the last render on ``ctx`` (include/super_lm.h ``slm_render_backward_ex``: dL/dc_k = sum over the pixels k takes
-    part in of g w_k / W; the gradient passes the float32 cast of the colours).  Rows as ``render_backward``."""
-    if not (points or colors):
-        raise ValueError("render_backward_ex: request the points' gradient, the colours' or both")
+def _render_backward_all(ctx, params, grad_image, points, colors, radii):
+    """(dL/dpoints (N,3) or None, dL/dcolors (N,3) or None, dL/dradii (N,) or None), float64, of the last render on
+    ``ctx``: always three entries.  ``radii`` needs a last render with per-point radii."""
     g = torch.as_tensor(grad_image).detach()
     dev = g.device
     if tuple(g.shape) != (params.height, params.width, 3):
@@ -181,10 +199,28 @@ def render_backward_ex(ctx, params, grad_image, points=True, colors=True):
     g = g.to(dtype=torch.float64).contiguous()
     gp = torch.empty((ctx.last_n, 3), dtype=torch.float64, device=dev) if points else None
     gc = torch.empty((ctx.last_n, 3), dtype=torch.float64, device=dev) if colors else None
+    gr = torch.empty((ctx.last_n,), dtype=torch.float64, device=dev) if radii else None
     ptr = lambda t: _dev_ptr(t) if t is not None and t.numel() else None
-    _lib.check(ctx.lib.slm_render_backward_ex(ctx.h, C.byref(params), _dev_ptr(g), ptr(gp), ptr(gc), _stream_ptr(dev)),
-               "slm_render_backward_ex")
-    return gp, gc
+    if radii:
+        _lib.check(ctx.lib.slm_render_backward_radii(ctx.h, C.byref(params), _dev_ptr(g), ptr(gp), ptr(gc), ptr(gr),
+                                                     _stream_ptr(dev)), "slm_render_backward_radii")
+    else:
+        _lib.check(ctx.lib.slm_render_backward_ex(ctx.h, C.byref(params), _dev_ptr(g), ptr(gp), ptr(gc),
+                                                  _stream_ptr(dev)), "slm_render_backward_ex")
+    return gp, gc, gr
+
+
+def render_backward_ex(ctx, params, grad_image, points=True, colors=True, radii=False):
+    """``render_backward`` with the colour gradient: (dL/dpoints or None, dL/dcolors or None), each (N,3) float64, for
+    the last render on ``ctx`` (include/super_lm.h ``slm_render_backward_ex``: dL/dc_k = sum over the pixels k takes
+    part in of g w_k / W; the gradient passes the float32 cast of the colours).  Rows as ``render_backward``.
+    Called with ``radii=True`` (the last render had per-point radii) the result is a triple: dL/dradii (N,) float64
+    follows (``slm_render_backward_radii``: sum of g.(c_k - C)/W e_k rho_k / r_k^2), 0 on culled and unstable rows.
+    The length of the result follows the caller's own ``radii`` argument, never the data."""
+    if not (points or colors or radii):
+        raise ValueError("render_backward_ex: request the points' gradient, the colours' or both")
+    out = _render_backward_all(ctx, params, grad_image, points, colors, radii)
+    return out if radii else out[:2]
 
 
 class _Render(torch.autograd.Function):
@@ -194,41 +230,49 @@ class _Render(torch.autograd.Function):
     ``reserve`` recreated -- the backward re-renders the saved inputs into it first."""
 
     @staticmethod
-    def forward(fctx, rctx, params, points, colors):
-        img = _render(rctx, params, points, colors)
+    def forward(fctx, rctx, params, points, colors, radii):
+        img = _render(rctx, params, points, colors, radii=radii)
         fctx.rctx, fctx.params, fctx.serial = rctx, SlmRenderParams.from_buffer_copy(params), rctx.serial
-        fctx.save_for_backward(points, colors)
+        fctx.per_point = radii is not None
+        fctx.save_for_backward(points, colors, *(() if radii is None else (radii,)))
         return img
 
     @staticmethod
     @once_differentiable
     def backward(fctx, grad_image):
-        points, colors = fctx.saved_tensors
+        points, colors = fctx.saved_tensors[:2]
+        radii = fctx.saved_tensors[2] if fctx.per_point else None
         want_p, want_c = fctx.needs_input_grad[2], fctx.needs_input_grad[3]
-        if not (want_p or want_c):
-            return None, None, None, None
+        want_r = fctx.per_point and fctx.needs_input_grad[4]
+        if not (want_p or want_c or want_r):
+            return None, None, None, None, None
         rctx, params = fctx.rctx, fctx.params
         if rctx.serial != fctx.serial:
-            _render(rctx, params, points, colors)
+            _render(rctx, params, points, colors, radii=radii)
             fctx.serial = rctx.serial
-        gp, gc = render_backward_ex(rctx, params, grad_image, want_p, want_c)
+        gp, gc, gr = _render_backward_all(rctx, params, grad_image, want_p, want_c, want_r)
         if gp is not None:
             gp = gp.to(device=points.device, dtype=points.dtype)
         if gc is not None:
             full = torch.zeros(colors.shape, dtype=colors.dtype, device=colors.device)
             full[:, :3] = gc
             gc = full
-        return None, None, gp, gc
+        if gr is not None:
+            gr = gr.to(device=radii.device, dtype=radii.dtype)
+        return None, None, gp, gc, gr
 
 
-def render_differentiable(ctx, params, points, colors):
+def render_differentiable(ctx, params, points, colors, radii=None):
     """``render_points`` as a node of the autograd graph: (h,w,3) float32 image; gradients to ``points`` (N,3) float32
-    or float64 and to ``colors`` (N,>=3) of any float dtype (columns beyond 3 get 0), each in its input's dtype and
+    or float64, to ``colors`` (N,>=3) of any float dtype (columns beyond 3 get 0) and, when given, to the per-point
+    ``radii`` (N,) of any float dtype (the render reads them as float32), each in its input's dtype and
     shape and only where ``needs_input_grad`` asks.  The gradient is ``render_backward_ex``'s, for the grad_image cast
     to float64; computed on the current stream.  ``ctx`` may be shared with other renders (see ``_Render``)."""
     if points.dim() != 2 or points.shape[1] != 3:
         raise ValueError(f"points must be (N,3), got {tuple(points.shape)}")
-    return _Render.apply(ctx, params, points, colors)
+    if radii is not None and (radii.dim() != 1 or radii.shape[0] != points.shape[0]):
+        raise ValueError(f"radii must be (N,) with N = {points.shape[0]}, got {tuple(radii.shape)}")
+    return _Render.apply(ctx, params, points, colors, radii)
 
 
 def _ssim_args(img_hwc, target_chw):
@@ -268,14 +312,27 @@ def ssim_render_loss(img_hwc, target_chw, weight, with_grad=True):
     return loss, int(kept), grad
 
 
+def _split_rad(rad, n):
+    """``rad`` of ``Pulsar.render`` -> (the one radius, None) for a number or a one-element tensor, (DEFAULT_RAD, the
+    (N,) tensor) for per-point radii (``params.radius`` must be valid but the per-point render does not read it)."""
+    if not torch.is_tensor(rad) or rad.numel() == 1:
+        return rad, None
+    if rad.dim() == 1 and rad.shape[0] == n:
+        return DEFAULT_RAD, rad
+    raise ValueError(f"rad must be a number, a one-element tensor or of shape (N,) = ({n},), got {tuple(rad.shape)}")
+
+
 class Pulsar:
     """``Pulsar(opt)`` as in the reference: ``forward(inputs, data, colors=None, view_scale=1.0, rad=0.01,
     bg_col=...)`` returns the (h,w,3) float32 image on the device, channels last (callers permute it).
 
-    ``Pulsar(opt, differentiable=True)``: with grad enabled and points or colours that require grad, the image is in
-    the autograd graph (``render_differentiable``); other inputs take the plain forward.  ``bg_col`` and ``rad`` are
-    constants: a tensor of either that requires grad is refused.  Plain ``Pulsar(opt)`` refuses inputs that require
-    grad (its gradient is this blend's, not Pulsar's own backward, which is unpinned)."""
+    ``rad`` is a number or a one-element tensor (one radius for every point, as the reference calls it) or a tensor of
+    shape (N,): one radius per point, Pulsar's ``vert_rad`` (read as float32); any other shape raises ValueError.
+
+    ``Pulsar(opt, differentiable=True)``: with grad enabled and points, colours or an (N,) ``rad`` that require grad,
+    the image is in the autograd graph (``render_differentiable``); other inputs take the plain forward.  ``bg_col``
+    and a one-element ``rad`` are constants: a tensor of either that requires grad is refused.  Plain ``Pulsar(opt)``
+    refuses inputs that require grad (its gradient is this blend's, not Pulsar's own backward, which is unpinned)."""
 
     def __init__(self, opt, differentiable=False) -> None:
         self.height = opt.height
@@ -300,21 +357,23 @@ class Pulsar:
         if colors is None:
             colors = data.colors
         points = data.points
+        rad, radii = _split_rad(rad, int(points.shape[0]))
         if self.differentiable and torch.is_grad_enabled():
             for name, t in (("bg_col", bg_col), ("rad", rad)):
                 if torch.is_tensor(t) and t.requires_grad:
                     raise RuntimeError(f"super_amd.renderer.Pulsar: {name} is a constant of the render (no gradient); "
                                        f"pass a {name} that does not require grad")
-            if any(torch.is_tensor(t) and t.requires_grad for t in (points, colors)):
+            if any(torch.is_tensor(t) and t.requires_grad for t in (points, colors, radii)):
                 if with_info:
                     raise ValueError("super_amd.renderer.Pulsar: with_info is not available for a render in the graph")
                 params = render_params(inputs["K"], self.height, self.width, view_scale, rad, bg_col)
-                return render_differentiable(self.context(view_scale), params, points, colors)
+                return render_differentiable(self.context(view_scale), params, points, colors, radii)
         if self.differentiable:        # not in the graph: the plain forward of the detached inputs
             points, colors = points.detach(), colors.detach()
+            radii = None if radii is None else radii.detach()
         with torch.no_grad():
             params = render_params(inputs["K"], self.height, self.width, view_scale, rad, bg_col)
-            return render_points(self.context(view_scale), params, points, colors, with_info)
+            return render_points(self.context(view_scale), params, points, colors, with_info, radii)
 
     def forward(self, inputs, data, colors=None, view_scale=1.0, rad=0.01, bg_col=torch.tensor([0.0, 0.0, 0.0])):
         return self.render(inputs, data, colors, view_scale, rad, bg_col)
@@ -368,8 +427,12 @@ def _renderer_of(sf):
 
 def render_(sf, inputs):
     """(reference ``Surfels.render_``, nodes.py:630-645) sets ``sf.renderImg`` (colours) and
-    ``sf.renderImg_conf_heat`` (``magma`` of the confidences), both (1,3,H,W), from the stable surfels."""
+    ``sf.renderImg_conf_heat`` (``magma`` of the confidences), both (1,3,H,W), from the stable surfels.  With
+    ``opt.renderer_surfel_radii`` the radii are ``sf.radii[sf.isStable] * opt.renderer_radii_scale`` (default 1.0)
+    instead of ``opt.renderer_rad``."""
     rad = getattr(sf.opt, "renderer_rad", DEFAULT_RAD)
+    if getattr(sf.opt, "renderer_surfel_radii", False):      # opt-in: every surfel with its own radius
+        rad = sf.radii[sf.isStable].detach() * float(getattr(sf.opt, "renderer_radii_scale", 1.0))
     r = _renderer_of(sf)
     pts = sf.points[sf.isStable]
     cols = sf.colors[sf.isStable]

@@ -7,6 +7,12 @@ through torch (Pulsar(opt, differentiable=True), gradients to the points and the
 (10 SGD iterations) with opt.render_loss (native_render_loss=True).
 
     python tools/time_render.py [--reps 30] [--out gpu_out.json]
+    python tools/time_render.py --radii [--reps 30] [--out gpu_out.json]
+
+``--radii`` times the per-point render instead (slm_render_points_radii): the same 300 k surfels at 480x640 with the
+radii of the reference's formula, Z / (sqrt(2) f clamp(|n_z|, 0.26, 1)); beside the two one-radius forwards it reports
+the per-point forward, forward + SSIM loss + backward (the point gradient; with the radius gradient as well), the loss +
+backward alone, and the fractions of pixels hit and kept.
 
 HIP events around each call after warm-up; median and maximum over --reps runs.  A render synchronises once
 inside (the tile-list total is read back), so a timed call includes that round trip.  Kernel times: run it under
@@ -39,11 +45,72 @@ def _time(fn, reps, warm=3):
     return {"median_us": float(np.median(ts)), "max_us": float(np.max(ts)), "reps": reps}
 
 
+def radii_mode(a):
+    from types import SimpleNamespace
+
+    from super_amd import synth
+    from super_amd.renderer import (DEFAULT_RAD, Pulsar, render_backward, render_backward_ex, render_params,
+                                    ssim_render_loss_device)
+    res = {}
+    sc = synth.make_scene(N=300_000, J=512, H=480, W=640, seed=5, src_border=2)
+    pts = torch.from_numpy(sc.sf_points).cuda()
+    cols = torch.from_numpy(np.random.default_rng(2).uniform(size=(sc.N, 3)).astype(np.float32)).cuda()
+    nz = np.clip(np.abs(sc.sf_norms[:, 2].astype(np.float64)), 0.26, 1.0)
+    radii = torch.from_numpy((sc.sf_points[:, 2].astype(np.float64) / (np.sqrt(2.0) * sc.K[0, 0] * nz)).astype(np.float32)).cuda()
+    inputs = {"K": torch.from_numpy(sc.K).float()[None].cuda()}
+    r = Pulsar(SimpleNamespace(height=sc.H, width=sc.W))
+    data = SimpleNamespace(points=pts, colors=cols)
+    gen = torch.Generator("cuda").manual_seed(3)
+    for name, rad in (("render_rad2e-4", 2e-4), ("render_rad2e-3", 2e-3), ("render_radii", radii)):
+        res[name] = _time(lambda: r(inputs, data, rad=rad), a.reps)
+        img, _, cnt = r.render(inputs, data, rad=rad, with_info=True)
+        tgt = (img.permute(2, 0, 1) + 0.01 * torch.randn(3, sc.H, sc.W, device="cuda", generator=gen)).contiguous()
+        out, _ = ssim_render_loss_device(img, tgt, 1e-4, with_grad=False)
+        res[name]["pixels_hit"] = float((cnt > 0).float().mean())
+        res[name]["pixels_kept"] = float(out[1]) / (sc.H * sc.W)
+        res[name]["hits_per_pixel_mean"] = float(cnt.float().mean())
+        res[name]["hits_per_pixel_max"] = int(cnt.max())
+        ctx = r.context()
+        p = render_params(inputs["K"], sc.H, sc.W, 1.0, DEFAULT_RAD if torch.is_tensor(rad) else rad)
+        key = name[len("render_"):]
+
+        def loss_bwd():
+            _, g = ssim_render_loss_device(loss_bwd.img, tgt, 1e-4)
+            return render_backward(ctx, p, g)
+
+        def fwd_loss_bwd():
+            loss_bwd.img = r(inputs, data, rad=rad)
+            return loss_bwd()
+
+        fwd_loss_bwd()
+        res["render_fwd_ssim_bwd_" + key] = _time(fwd_loss_bwd, a.reps)
+        fwd_loss_bwd()
+        res["render_ssim_bwd_" + key] = _time(loss_bwd, a.reps)
+        if torch.is_tensor(rad):
+            def loss_bwd_all():
+                _, g = ssim_render_loss_device(loss_bwd.img, tgt, 1e-4)
+                return render_backward_ex(ctx, p, g, radii=True)
+
+            fwd_loss_bwd()
+            res["render_ssim_bwd_points_colors_radii_" + key] = _time(loss_bwd_all, a.reps)
+    res["render_points"] = sc.N
+    res["radii_px"] = [float((radii * sc.K[0, 0] / pts[:, 2]).min()), float((radii * sc.K[0, 0] / pts[:, 2]).max())]
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--radii", action="store_true", help="time the per-point render (see the module's docstring)")
     a = ap.parse_args()
+    if a.radii:
+        res = radii_mode(a)
+        print(json.dumps(res, indent=1))
+        if a.out:
+            with open(a.out, "w") as f:
+                json.dump(res, f, indent=1)
+        return
     from types import SimpleNamespace
 
     from helpers import torch_frame
