@@ -724,6 +724,41 @@ int slm_gf_render_radii(slm_gf* g, int32_t slot, slm_render* r, const slm_render
  * per tile-list entry), the same refusals otherwise.  Bitwise reproducible (no float atomics); does not synchronise. */
 int slm_render_backward_radii(slm_render* r, const slm_render_params* p, const double* grad_image, double* grad_points,
                               double* grad_colors, double* grad_radii, void* stream);
+/* N-channel features (Pulsar's n_channels: a feature vector per point -- class probabilities, a confidence, a depth
+ * column, colour plus any of these -- blended in one geometry pass)
+ *   slm_render_points_channels    <- Renderer(..., n_channels=C)
+ *   slm_render_backward_channels  <- dL/dP, dL/dfeatures and dL/dr of such a render
+ * The blend above with channel c of `features` in place of a colour channel, 1 <= C <= SLM_RENDER_MAX_CHANNELS:
+ *   out_c = (sum_k w_k f_kc + w_bg bg_c) / (sum_k w_k + w_bg),   bg_c where nothing is hit.
+ * The geometry, the culling (a bad per-point radius included), the hit test, the order of the hits with its tie rule, the
+ * n_track cut, w_k, w_bg, front_id and hit_count are those of slm_render_points (radii == NULL: p->radius for every point)
+ * or slm_render_points_radii (radii (N) float32 device).  Every channel is summed on its own, in float64, by one lane in
+ * list order, with the operations of the three-channel entries: channel c is bitwise what slm_render_points /
+ * slm_render_points_radii write for the same column of numbers and the same background value, and with C == 3 and
+ * bg == p->bg the whole image is theirs.  features (N,C) device float32, row i at features + i * feature_stride
+ * (feature_stride >= C); bg: C floats on the HOST (p->bg is not read); image (height,width,C) device float32.  The context
+ * keeps a copy of the features, so a later backward does not read `features` again; the buffers that are C wide are
+ * allocated by the first such call on a context.  One synchronisation of `stream`, as for slm_render_points.
+ * SLM_ERR_INVALID, before any device call, for C outside 1..8, feature_stride < C, or a null bg, image or (N > 0) features. */
+#define SLM_RENDER_MAX_CHANNELS 8
+int slm_render_points_channels(slm_render* r, const slm_render_params* p, int32_t N, const void* points,
+                               const float* radii /* NULL: p->radius for every point */, int32_t C, const float* features,
+                               int32_t feature_stride /* >= C */, const float* bg /* host, C floats; p->bg is not read */,
+                               float* image /* (height,width,C) */, int32_t* front_id, int32_t* hit_count, void* stream);
+/* The backward of the last forward on `r`, which must be a completed slm_render_points_channels with the same C and the same
+ * p (field by field, bg excepted).  With F the float64 channels of a pixel, g = dL/dF and s_k = sum_c g_c (f_kc - F_c) / W,
+ *   dL/dP_k and dL/dr_k as for slm_render_backward_radii with that s_k,
+ *   dL/df_kc = sum over the pixels k takes part in of  g_c w_k / W
+ * at the forward's hit sets.  grad_image (height,width,C) float64 device; grad_points (N,3), grad_features (N,C), grad_radii
+ * (N) float64 device, 0 on culled rows.  Any of the three may be NULL, not all three; each is bitwise the same whichever
+ * others are requested.  grad_radii after a forward with radii == NULL is refused ("slm_render_backward_channels: grad_radii
+ * after a forward with one radius").  After a channels forward slm_render_backward, _ex and _radii refuse (the per-pixel
+ * record is laid out differently, also at C == 3), and this entry refuses after a three-channel forward.  The same two
+ * store-and-sum passes: a slab entry holds 3 + C + 1 doubles when everything is requested.  Bitwise reproducible (no float
+ * atomics); does not synchronise.  There is no GraphFit twin: nothing in GraphFit consumes more than three channels. */
+int slm_render_backward_channels(slm_render* r, const slm_render_params* p, int32_t C,
+                                 const double* grad_image /* (height,width,C) */, double* grad_points /* (N,3) */,
+                                 double* grad_features /* (N,C) */, double* grad_radii /* (N) */, void* stream);
 /* After slm_gf_bind_frame: binds dL/dP (N,3) float64 device, by surfel row, of an outside term (the render loss:
  * slm_render_backward of an slm_gf_render).  Every later evaluation of the slot -- slm_gf_eval_losses, slm_gf_loss_grad,
  * each iteration of slm_gf_run -- adds it to each stable surfel's dL/dP before the chain rule to the node rows and the

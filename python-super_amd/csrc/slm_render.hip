@@ -59,6 +59,11 @@ struct slm_render {
   unsigned long long total_last = 0;     // its tile-list entries
   int has_fwd = 0;                       // 1 after a forward that completed; cleared when one starts
   int per_point_last = 0;                // 1 when that forward had per-point radii (pos[].w)
+  // ---- only after slm_render_points_channels (grown on its first call; a context without one never allocates them) ----
+  float* feat = nullptr;                 // (cap_feat floats) the points' features, rows padded with 0 to 4 or 8 floats
+  double* pixf = nullptr;                // (cap_pixf doubles) per pixel the C float64 blended channels; pix holds zt_max, W, cut
+  size_t cap_feat = 0, cap_pixf = 0;
+  int ch_last = 0;                       // the channel count of that forward when it was a channels one, else 0
 };
 
 // the per-pixel record of a forward: float64 blend of the taken hits, and `cut`, the list position of the n_track-th hit
@@ -232,21 +237,10 @@ __device__ __forceinline__ void rn_sort_lds(unsigned long long* s, const unsigne
   rn_bitonic(s, n2);
 }
 
-template <bool PR>
-__global__ void __launch_bounds__(256) k_rn_tile(RnCam cam, const unsigned long long* __restrict__ off,
-                                                 unsigned long long* __restrict__ keys, unsigned long long* __restrict__ tmp,
-                                                 const float4* __restrict__ pos, const int4* __restrict__ box,
-                                                 const float* __restrict__ colors, int cstride, float* __restrict__ image,
-                                                 int* __restrict__ front_id, int* __restrict__ hit_count, RnPix* __restrict__ pix) {
-  __shared__ unsigned long long skey[RN_SORT_CAP];
-  __shared__ float4 spos[RN_CHUNK];
-  __shared__ int4 sbox[RN_CHUNK];
-  __shared__ int sid[RN_CHUNK];
-  const int tile = blockIdx.y * cam.tiles_x + blockIdx.x;
-  const unsigned long long base = off[tile];
-  const int n = (int)(off[tile + 1] - base);
-  unsigned long long* list = keys + base;
-  const unsigned long long* gl = list;   // the sorted list when it does not fit in LDS
+// sort the n keys of a tile's list front to back, all 256 lanes; the sorted list ends in `list` on every path and, when
+// n <= RN_SORT_CAP, in skey as well.  `scratch` (n keys) serves the merges of a longer list.
+__device__ __forceinline__ void rn_tile_sort(unsigned long long* skey, unsigned long long* list, unsigned long long* scratch,
+                                             int n) {
   if (n > 0 && n <= RN_SORT_CAP) {
     rn_sort_lds(skey, list, n);
     for (int e = threadIdx.x; e < n; e += 256) list[e] = skey[e];   // the backward finds its keys in the sorted list
@@ -259,7 +253,7 @@ __global__ void __launch_bounds__(256) k_rn_tile(RnCam cam, const unsigned long 
       for (int e = threadIdx.x; e < m; e += 256) list[c + e] = skey[e];
       __syncthreads();
     }
-    unsigned long long *src = list, *dst = tmp + base;
+    unsigned long long *src = list, *dst = scratch;
     for (int wdt = RN_SORT_CAP; wdt < n; wdt <<= 1) {
       for (int e = threadIdx.x; e < n; e += 256) {
         const int run = e / wdt, lo = run * wdt, pb = (run & ~1) * wdt;
@@ -282,6 +276,24 @@ __global__ void __launch_bounds__(256) k_rn_tile(RnCam cam, const unsigned long 
       __syncthreads();
     }
   }
+}
+
+template <bool PR>
+__global__ void __launch_bounds__(256) k_rn_tile(RnCam cam, const unsigned long long* __restrict__ off,
+                                                 unsigned long long* __restrict__ keys, unsigned long long* __restrict__ tmp,
+                                                 const float4* __restrict__ pos, const int4* __restrict__ box,
+                                                 const float* __restrict__ colors, int cstride, float* __restrict__ image,
+                                                 int* __restrict__ front_id, int* __restrict__ hit_count, RnPix* __restrict__ pix) {
+  __shared__ unsigned long long skey[RN_SORT_CAP];
+  __shared__ float4 spos[RN_CHUNK];
+  __shared__ int4 sbox[RN_CHUNK];
+  __shared__ int sid[RN_CHUNK];
+  const int tile = blockIdx.y * cam.tiles_x + blockIdx.x;
+  const unsigned long long base = off[tile];
+  const int n = (int)(off[tile + 1] - base);
+  unsigned long long* list = keys + base;
+  const unsigned long long* gl = list;   // the sorted list when it does not fit in LDS
+  rn_tile_sort(skey, list, tmp + base, n);
   const bool in_lds = n <= RN_SORT_CAP;
 
   const int j = blockIdx.x * RN_TILE + (threadIdx.x & (RN_TILE - 1));
@@ -352,6 +364,127 @@ __global__ void __launch_bounds__(256) k_rn_tile(RnCam cam, const unsigned long 
   image[3 * px] = o0;
   image[3 * px + 1] = o1;
   image[3 * px + 2] = o2;
+  if (front_id) front_id[px] = first;
+  if (hit_count) hit_count[px] = nh;
+}
+
+// ---- N-channel features (slm_render_points_channels) ----------------------------------------------------------------------
+// The context's copy of the features has rows of CP floats, CP = 4 for C <= 4 and 8 otherwise, the columns past C zero: the
+// walk and the backward read a row as one or two float4 and the padded sums cost a few FMAs on zeros.  k_rn_project then
+// reads that copy as its `colors` (stride CP), so the one-radius and per-point projections serve unchanged.
+struct RnBg { float v[SLM_RENDER_MAX_CHANNELS]; };
+
+__global__ void __launch_bounds__(256) k_rn_feat(int N, int C, int CP, const float* __restrict__ features, int stride,
+                                                 float* __restrict__ feat) {
+  const size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= (size_t)N * CP) return;
+  const size_t i = q / CP;
+  const int c = (int)(q - i * CP);
+  feat[q] = c < C ? features[i * stride + c] : 0.f;
+}
+
+// k_rn_tile with CP accumulators (a compile-time bound, padded: see above) of which the first C are written.  Every channel's
+// sum is the FMA chain that k_rn_tile's s0 / s1 / s2 compile to, written out, so a channel is bitwise what the three-channel
+// kernel gives for the same column.  The record of a pixel: zt_max, W and cut in pix (its colour fields 0), the C float64
+// channels in pixf.
+template <bool PR, int CP>
+__global__ void __launch_bounds__(256) k_rn_tile_ch(RnCam cam, RnBg bg, int C, const unsigned long long* __restrict__ off,
+                                                    unsigned long long* __restrict__ keys, unsigned long long* __restrict__ tmp,
+                                                    const float4* __restrict__ pos, const int4* __restrict__ box,
+                                                    const float* __restrict__ feat, float* __restrict__ image,
+                                                    int* __restrict__ front_id, int* __restrict__ hit_count,
+                                                    RnPix* __restrict__ pix, double* __restrict__ pixf) {
+  __shared__ unsigned long long skey[RN_SORT_CAP];
+  __shared__ float4 spos[RN_CHUNK];
+  __shared__ int4 sbox[RN_CHUNK];
+  __shared__ int sid[RN_CHUNK];
+  const int tile = blockIdx.y * cam.tiles_x + blockIdx.x;
+  const unsigned long long base = off[tile];
+  const int n = (int)(off[tile + 1] - base);
+  unsigned long long* list = keys + base;
+  const unsigned long long* gl = list;
+  rn_tile_sort(skey, list, tmp + base, n);
+  const bool in_lds = n <= RN_SORT_CAP;
+
+  const int j = blockIdx.x * RN_TILE + (threadIdx.x & (RN_TILE - 1));
+  const int i = blockIdx.y * RN_TILE + (threadIdx.x / RN_TILE);
+  const bool inside = i < cam.h && j < cam.w;
+  double dx, dy, inv_dn;
+  rn_ray(cam, i, j, dx, dy, inv_dn);
+  const double zspan = cam.zf - cam.zn;
+  int nh = 0, first = -1, cut = INT_MAX;
+  double zt_max = 0.0, sw = 0.0, s[CP];
+#pragma unroll
+  for (int c = 0; c < CP; ++c) s[c] = 0.0;
+  bool active = inside;
+  for (int c0 = 0; c0 < n; c0 += RN_CHUNK) {
+    const int m = min(RN_CHUNK, n - c0);
+    if (threadIdx.x < m) {
+      const unsigned long long k = in_lds ? skey[c0 + threadIdx.x] : gl[c0 + threadIdx.x];
+      const int id = (int)(unsigned int)k;
+      sid[threadIdx.x] = id;
+      spos[threadIdx.x] = pos[id];
+      sbox[threadIdx.x] = box[id];
+    }
+    __syncthreads();
+    if (active) {
+      for (int e = 0; e < m; ++e) {
+        const int4 b = sbox[e];
+        if (j < b.x || j > b.y || i < b.z || i > b.w) continue;
+        const float4 p = spos[e];
+        const double X = p.x, Y = p.y, Z = p.z;
+        const double rho = rn_rho(X, Y, Z, dx, dy, inv_dn);
+        const double r = PR ? (double)p.w : cam.r;
+        if (!(rho < r)) continue;
+        const double zt = (cam.zf - Z) / zspan;
+        const int id = sid[e];
+        if (nh == 0) {
+          zt_max = zt;
+          first = id;
+        }
+        const double wk = (1.0 - rho / r) * exp((zt - zt_max) / cam.gamma);
+        const float4* f = reinterpret_cast<const float4*>(feat + (size_t)id * CP);
+        sw += wk;
+#pragma unroll
+        for (int q = 0; q < CP / 4; ++q) {
+          const float4 v = f[q];
+          s[4 * q] = fma(wk, (double)v.x, s[4 * q]);
+          s[4 * q + 1] = fma(wk, (double)v.y, s[4 * q + 1]);
+          s[4 * q + 2] = fma(wk, (double)v.z, s[4 * q + 2]);
+          s[4 * q + 3] = fma(wk, (double)v.w, s[4 * q + 3]);
+        }
+        if (++nh == cam.n_track) {
+          cut = c0 + e;
+          active = false;
+          break;
+        }
+      }
+    }
+    if (!__syncthreads_or(active && c0 + RN_CHUNK < n)) break;
+  }
+  if (!inside) return;
+  const size_t px = (size_t)i * cam.w + j;
+  RnPix rec = {0.0, 0.0, 0.0, 0.0, 0.0, cut, 0};
+  double den = 1.0, wbg = 0.0;
+  if (nh > 0) {
+    wbg = exp((cam.eps - zt_max) / cam.gamma);
+    den = sw + wbg;
+    rec.zt_max = zt_max;
+    rec.W = den;
+  }
+  pix[px] = rec;
+#pragma unroll
+  for (int c = 0; c < CP; ++c)
+    if (c < C) {
+      float o = bg.v[c];
+      double F = 0.0;
+      if (nh > 0) {
+        F = fma(wbg, (double)bg.v[c], s[c]) / den;
+        o = (float)F;
+      }
+      pixf[px * C + c] = F;
+      image[px * C + c] = o;
+    }
   if (front_id) front_id[px] = first;
   if (hit_count) hit_count[px] = nh;
 }
@@ -547,11 +680,189 @@ __global__ void __launch_bounds__(256) k_rn_bwd_point_ex(int N, int tiles_x, con
   }
 }
 
+// The two backward passes of a channels forward (slm_render_backward_channels).  The channel count is a run-time bound of
+// loops unrolled to SLM_RENDER_MAX_CHANNELS, and what is wanted (RN_BWD_POINTS | RN_BWD_COLORS, here the features, |
+// RN_BWD_RADII) a run-time uniform too: one instantiation per PR instead of MODE x PR x C.  A slab entry holds, packed in this
+// order, 3 doubles for the point (if wanted), C for the features, 1 for the radius.  Every output is summed in its own
+// registers by the same instructions whatever else is wanted, so it does not depend on the others.
+//   pixel coefficients in LDS: a_c = g_c / W (C x 256 doubles), b = sum_c g_c F_c / W;  s_k = sum_c a_c f_kc - b
+template <bool PR>
+__global__ void __launch_bounds__(256) k_rn_bwd_entry_ch(RnCam cam, int C, int CP, int want,
+                                                         const unsigned long long* __restrict__ off,
+                                                         const unsigned long long* __restrict__ keys,
+                                                         const float4* __restrict__ pos, const int4* __restrict__ box,
+                                                         const float* __restrict__ feat, const RnPix* __restrict__ pix,
+                                                         const double* __restrict__ pixf, const double* __restrict__ gimg,
+                                                         double* __restrict__ slab) {
+  constexpr int MC = SLM_RENDER_MAX_CHANNELS;
+  __shared__ double sdx[256], sdy[256], sinv[256], szt[256], sb[256], sa[MC][256];
+  __shared__ int scut[256];
+  const bool GP = (want & RN_BWD_POINTS) != 0, GC = (want & RN_BWD_COLORS) != 0, GR = PR && (want & RN_BWD_RADII) != 0;
+  const bool GS = GP || GR;
+  const int S = (GP ? 3 : 0) + (GC ? C : 0) + (GR ? 1 : 0), of = GP ? 3 : 0;
+  const int tile = blockIdx.y * cam.tiles_x + blockIdx.x;
+  const unsigned long long base = off[tile];
+  const int n = (int)(off[tile + 1] - base);
+  if (n == 0) return;
+  const int tx0 = blockIdx.x * RN_TILE, ty0 = blockIdx.y * RN_TILE;
+  {
+    const int t = threadIdx.x, j = tx0 + (t & (RN_TILE - 1)), i = ty0 + t / RN_TILE;
+    int cut = -1;
+    if (i < cam.h && j < cam.w) {
+      const size_t px = (size_t)i * cam.w + j;
+      const RnPix rec = pix[px];
+      double g[MC];
+      bool any = false;
+#pragma unroll
+      for (int c = 0; c < MC; ++c) {
+        g[c] = c < C ? gimg[px * C + c] : 0.0;
+        any = any || g[c] != 0.0;
+      }
+      if (rec.W > 0.0 && any) {
+        cut = rec.cut;
+        double b = 0.0;
+#pragma unroll
+        for (int c = 0; c < MC; ++c)
+          if (c < C) {
+            sa[c][t] = g[c] / rec.W;
+            b = fma(g[c], pixf[px * C + c], b);
+          }
+        sb[t] = b / rec.W;
+        szt[t] = rec.zt_max;
+        double dx, dy, inv_dn;
+        rn_ray(cam, i, j, dx, dy, inv_dn);
+        sdx[t] = dx;
+        sdy[t] = dy;
+        sinv[t] = inv_dn;
+      }
+    }
+    scut[t] = cut;
+  }
+  __syncthreads();
+  const double zspan = cam.zf - cam.zn, kz = 1.0 / (cam.gamma * zspan);
+  for (int e = threadIdx.x; e < n; e += 256) {
+    const int id = (int)(unsigned int)keys[base + e];
+    const int4 b = box[id];
+    const float4 p = pos[id];
+    float f[MC];
+    {
+      const float4* fr = reinterpret_cast<const float4*>(feat + (size_t)id * CP);
+      const float4 v0 = fr[0], v1 = CP > 4 ? fr[1] : make_float4(0.f, 0.f, 0.f, 0.f);
+      f[0] = v0.x; f[1] = v0.y; f[2] = v0.z; f[3] = v0.w;
+      f[4] = v1.x; f[5] = v1.y; f[6] = v1.z; f[7] = v1.w;
+    }
+    const double X = p.x, Y = p.y, Z = p.z;
+    const double zt = (cam.zf - Z) / zspan;
+    const double r = PR ? (double)p.w : cam.r;
+    double gx = 0.0, gy = 0.0, gz = 0.0, gr = 0.0, q[MC];
+#pragma unroll
+    for (int c = 0; c < MC; ++c) q[c] = 0.0;
+    const int i0 = max(b.z, ty0), i1 = min(b.w, ty0 + RN_TILE - 1), j0 = max(b.x, tx0), j1 = min(b.y, tx0 + RN_TILE - 1);
+    for (int i = i0; i <= i1; ++i)
+      for (int j = j0; j <= j1; ++j) {
+        const int t = (i - ty0) * RN_TILE + (j - tx0);
+        if (e > scut[t]) continue;
+        const double dx = sdx[t], dy = sdy[t], inv_dn = sinv[t];
+        const double rho = rn_rho(X, Y, Z, dx, dy, inv_dn);
+        if (!(rho < r)) continue;
+        const double ek = exp((zt - szt[t]) / cam.gamma), wk = (1.0 - rho / r) * ek;
+        double sk = 0.0;
+        if (GS) {
+#pragma unroll
+          for (int c = 0; c < MC; ++c)
+            if (c < C) sk = fma(sa[c][t], (double)f[c], sk);
+          sk -= sb[t];
+        }
+        if constexpr (PR) {
+          if (GR) gr += sk * ek * rho / (r * r);
+        }
+        if (GP) {
+          if (rho > 0.0) {
+            const double hx = dx * inv_dn, hy = dy * inv_dn, hz = inv_dn;
+            const double pd = X * hx + Y * hy + Z * hz;
+            const double qq = -sk * ek / (r * rho);
+            gx += qq * (X - pd * hx);
+            gy += qq * (Y - pd * hy);
+            gz += qq * (Z - pd * hz);
+          }
+          gz -= sk * wk * kz;
+        }
+        if (GC) {
+#pragma unroll
+          for (int c = 0; c < MC; ++c)
+            if (c < C) q[c] = fma(sa[c][t], wk, q[c]);
+        }
+      }
+    double* o = slab + (size_t)S * (base + e);
+    if (GP) {
+      o[0] = gx;
+      o[1] = gy;
+      o[2] = gz;
+    }
+    if (GC) {
+#pragma unroll
+      for (int c = 0; c < MC; ++c)
+        if (c < C) o[of + c] = q[c];
+    }
+    if (GR) o[S - 1] = gr;
+  }
+}
+
+// pass 2: per point the sums of its slab entries, in the scatter's tile order (rn_bwd_gather with the run-time layout above)
+__global__ void __launch_bounds__(256) k_rn_bwd_point_ch(int N, int tiles_x, int C, const unsigned long long* __restrict__ off,
+                                                         const unsigned long long* __restrict__ keys,
+                                                         const float4* __restrict__ pos, const int4* __restrict__ box,
+                                                         const double* __restrict__ slab, double* __restrict__ out_p,
+                                                         double* __restrict__ out_f, double* __restrict__ out_r) {
+  constexpr int MC = SLM_RENDER_MAX_CHANNELS;
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= N) return;
+  const int of = out_p ? 3 : 0, S = of + (out_f ? C : 0) + (out_r ? 1 : 0);
+  double ap[3] = {0.0, 0.0, 0.0}, ar = 0.0, af[MC];
+#pragma unroll
+  for (int c = 0; c < MC; ++c) af[c] = 0.0;
+  const int4 b = box[i];
+  if (b.x <= b.y) {
+    const unsigned long long key = ((unsigned long long)__float_as_uint(pos[i].z) << 32) | (unsigned int)i;
+    for (int ty = b.z / RN_TILE; ty <= b.w / RN_TILE; ++ty)
+      for (int tx = b.x / RN_TILE; tx <= b.y / RN_TILE; ++tx) {
+        const int t = ty * tiles_x + tx;
+        unsigned long long lo = off[t], hi = off[t + 1];
+        while (lo < hi) {
+          const unsigned long long mid = (lo + hi) >> 1;
+          if (keys[mid] < key) lo = mid + 1; else hi = mid;
+        }
+        if (lo < off[t + 1] && keys[lo] == key) {
+          const double* e = slab + (size_t)S * lo;
+          if (out_p) {
+            ap[0] += e[0];
+            ap[1] += e[1];
+            ap[2] += e[2];
+          }
+          if (out_f) {
+#pragma unroll
+            for (int c = 0; c < MC; ++c)
+              if (c < C) af[c] += e[of + c];
+          }
+          if (out_r) ar += e[S - 1];
+        }
+      }
+  }
+  if (out_p)
+    for (int q = 0; q < 3; ++q) out_p[3 * (size_t)i + q] = ap[q];
+  if (out_f) {
+#pragma unroll
+    for (int c = 0; c < MC; ++c)
+      if (c < C) out_f[(size_t)C * i + c] = af[c];
+  }
+  if (out_r) out_r[i] = ar;
+}
+
 // the device arrays of a context; sizes of slm_render_create: [0] points + 1, [1] tiles, [2] tiles + 1, [3] pixels
 #define A(name, mult, unit) DEV_MEMBER(slm_render, name, mult, unit)
 constexpr DevMember kRenderArrays[] = {A(pos, 1, 0), A(box, 1, 0), A(cnt, 1, 1), A(off, 1, 2), A(cur, 1, 1), A(col, 1, 0),
                                        A(pix, 1, 3), DEV_GROWN(slm_render, keys), DEV_GROWN(slm_render, tmp),
-                                       DEV_GROWN(slm_render, slab)};
+                                       DEV_GROWN(slm_render, slab), DEV_GROWN(slm_render, feat), DEV_GROWN(slm_render, pixf)};
 #undef A
 
 int rn_tiles_x(int w) { return (w + RN_TILE - 1) / RN_TILE; }
@@ -576,12 +887,15 @@ RnCam rn_cam(const slm_render_params* p) {
   return cam;
 }
 
-// the parameters a backward must repeat: those of its forward, field by field (pad excluded)
-bool rn_same_params(const slm_render_params& a, const slm_render_params& b) {
+// the parameters a backward must repeat: those of its forward, field by field (pad excluded); a channels forward does
+// not read bg, so its backward does not compare it
+bool rn_same_geometry(const slm_render_params& a, const slm_render_params& b) {
   return a.width == b.width && a.height == b.height && a.n_track == b.n_track && a.points_f64 == b.points_f64 &&
          a.focal == b.focal && a.ccx == b.ccx && a.ccy == b.ccy && a.radius == b.radius && a.z_near == b.z_near &&
-         a.z_far == b.z_far && a.gamma == b.gamma && a.bg_eps == b.bg_eps && a.bg[0] == b.bg[0] && a.bg[1] == b.bg[1] &&
-         a.bg[2] == b.bg[2];
+         a.z_far == b.z_far && a.gamma == b.gamma && a.bg_eps == b.bg_eps;
+}
+bool rn_same_params(const slm_render_params& a, const slm_render_params& b) {
+  return rn_same_geometry(a, b) && a.bg[0] == b.bg[0] && a.bg[1] == b.bg[1] && a.bg[2] == b.bg[2];
 }
 
 // the projection of one source, with the parameters' radius or (per_point) the points' own
@@ -596,10 +910,27 @@ void rn_project(dim3 grid, hipStream_t st, int N, const void* pts, GfSlot* gslot
                        cstride, r->col, radii);
 }
 
-// per_point: radii (N) float32 device holds one radius per point (by surfel row for RN_SRC_GF); else p->radius serves all
+// the tile walk of a channels forward: CP = 4 or 8 accumulators, with the parameters' radius or the points' own
+template <int CP>
+void rn_tile_ch(dim3 grid, hipStream_t st, const RnCam& cam, const RnBg& bg, int C, slm_render* r, bool per_point, float* image,
+                int32_t* front_id, int32_t* hit_count) {
+  if (per_point)
+    hipLaunchKernelGGL((k_rn_tile_ch<true, CP>), grid, dim3(256), 0, st, cam, bg, C, r->off, r->keys, r->tmp, r->pos, r->box,
+                       r->feat, image, front_id, hit_count, r->pix, r->pixf);
+  else
+    hipLaunchKernelGGL((k_rn_tile_ch<false, CP>), grid, dim3(256), 0, st, cam, bg, C, r->off, r->keys, r->tmp, r->pos, r->box,
+                       r->feat, image, front_id, hit_count, r->pix, r->pixf);
+}
+
+// the padded row width of the context's feature copy
+int rn_padded(int C) { return C <= 4 ? 4 : 8; }
+
+// per_point: radii (N) float32 device holds one radius per point (by surfel row for RN_SRC_GF); else p->radius serves all.
+// ch = 0: the three colour channels and p->bg.  ch = 1..8 (slm_render_points_channels, which has checked them): `colors`
+// holds ch features per row and bg_host ch floats.
 int render_common(slm_render* r, const slm_render_params* p, int N, int src, const void* pts, GfSlot* gslot,
                   bool per_point, const float* radii, const float* colors, int cstride, float* image, int32_t* front_id,
-                  int32_t* hit_count, void* stream, const char* who) {
+                  int32_t* hit_count, void* stream, const char* who, int ch = 0, const float* bg_host = nullptr) {
   std::string w(who);
   if (!r || !p || !image) return fail(SLM_ERR_INVALID, w + ": null argument");
   if (p->width < 1 || p->height < 1 || p->width > r->W || p->height > r->H)
@@ -610,12 +941,28 @@ int render_common(slm_render* r, const slm_render_params* p, int N, int src, con
       !std::isfinite(p->radius) || !std::isfinite(p->bg_eps))
     return fail(SLM_ERR_INVALID, w + ": bad camera or blend parameters");
   if (N < 0 || N > r->cap) return fail(SLM_ERR_INVALID, w + ": more points than the context holds");
-  if (N > 0 && ((src != RN_SRC_GF && !pts) || !colors || cstride < 3))
+  if (ch && N > 0 && !pts) return fail(SLM_ERR_INVALID, w + ": null points");
+  if (!ch && N > 0 && ((src != RN_SRC_GF && !pts) || !colors || cstride < 3))
     return fail(SLM_ERR_INVALID, w + ": null points / colours or color_stride < 3");
   r->has_fwd = 0;
   hipStream_t st = (hipStream_t)stream;
   const RnCam cam = rn_cam(p);
   const int tiles_y = (p->height + RN_TILE - 1) / RN_TILE, tiles = cam.tiles_x * tiles_y;
+  const int CP = rn_padded(ch);
+  RnBg bg{};
+  if (ch) {   // the wider buffers, first needed here: the feature copy at its widest, the pixel record at this width
+    const size_t rows = (size_t)r->cap + 1, pixels = (size_t)r->H * r->W;
+    HIPCHK(grow(r->feat, r->cap_feat, rows * CP, rows * SLM_RENDER_MAX_CHANNELS));
+    HIPCHK(grow(r->pixf, r->cap_pixf, pixels * ch, pixels * ch));
+    for (int c = 0; c < ch; ++c) bg.v[c] = bg_host[c];
+    if (N > 0) {
+      const size_t cells = (size_t)N * CP;
+      hipLaunchKernelGGL(k_rn_feat, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, N, ch, CP, colors, cstride,
+                         r->feat);
+      colors = r->feat;   // k_rn_project copies its first three columns into col, which nothing reads after this forward
+      cstride = CP;
+    }
+  }
   HIPCHK(hipMemsetAsync(r->cnt, 0, sizeof(unsigned int) * tiles, st));
   const dim3 gp((N + 255) / 256);
   if (N > 0) {
@@ -637,7 +984,11 @@ int render_common(slm_render* r, const slm_render_params* p, int N, int src, con
   HIPCHK(grow(r->tmp, r->cap_tmp, total, want));
   if (total > 0)
     hipLaunchKernelGGL(k_rn_scatter, gp, dim3(256), 0, st, N, cam.tiles_x, r->pos, r->box, r->cur, r->keys);
-  if (per_point)
+  if (ch && CP == 4)
+    rn_tile_ch<4>(dim3(cam.tiles_x, tiles_y), st, cam, bg, ch, r, per_point, image, front_id, hit_count);
+  else if (ch)
+    rn_tile_ch<8>(dim3(cam.tiles_x, tiles_y), st, cam, bg, ch, r, per_point, image, front_id, hit_count);
+  else if (per_point)
     hipLaunchKernelGGL(k_rn_tile<true>, dim3(cam.tiles_x, tiles_y), dim3(256), 0, st, cam, r->off, r->keys, r->tmp, r->pos,
                        r->box, colors, cstride, image, front_id, hit_count, r->pix);
   else
@@ -646,6 +997,7 @@ int render_common(slm_render* r, const slm_render_params* p, int N, int src, con
   HIPCHK(hipGetLastError());
   r->last = *p;
   r->per_point_last = per_point;
+  r->ch_last = ch;
   r->n_last = N;
   r->total_last = total;
   r->has_fwd = 1;
@@ -777,6 +1129,7 @@ int slm_render_backward(slm_render* r, const slm_render_params* p, const double*
                         void* stream) {
   if (!r || !p || !grad_image) return fail(SLM_ERR_INVALID, "slm_render_backward: null argument");
   if (!r->has_fwd) return fail(SLM_ERR_INVALID, "slm_render_backward: no completed forward on this context");
+  if (r->ch_last) return fail(SLM_ERR_INVALID, "slm_render_backward: the last forward had N-channel features: use slm_render_backward_channels");
   if (!rn_same_params(*p, r->last))
     return fail(SLM_ERR_INVALID, "slm_render_backward: parameters differ from those of the last forward");
   const int N = r->n_last;
@@ -789,6 +1142,7 @@ int slm_render_backward_ex(slm_render* r, const slm_render_params* p, const doub
                            double* grad_colors, void* stream) {
   if (!r || !p || !grad_image) return fail(SLM_ERR_INVALID, "slm_render_backward_ex: null argument");
   if (!r->has_fwd) return fail(SLM_ERR_INVALID, "slm_render_backward_ex: no completed forward on this context");
+  if (r->ch_last) return fail(SLM_ERR_INVALID, "slm_render_backward_ex: the last forward had N-channel features: use slm_render_backward_channels");
   if (!rn_same_params(*p, r->last))
     return fail(SLM_ERR_INVALID, "slm_render_backward_ex: parameters differ from those of the last forward");
   if (r->n_last == 0) return SLM_OK;
@@ -800,6 +1154,7 @@ int slm_render_backward_radii(slm_render* r, const slm_render_params* p, const d
                               double* grad_colors, double* grad_radii, void* stream) {
   if (!r || !p || !grad_image) return fail(SLM_ERR_INVALID, "slm_render_backward_radii: null argument");
   if (!r->has_fwd) return fail(SLM_ERR_INVALID, "slm_render_backward_radii: no completed forward on this context");
+  if (r->ch_last) return fail(SLM_ERR_INVALID, "slm_render_backward_radii: the last forward had N-channel features: use slm_render_backward_channels");
   if (!rn_same_params(*p, r->last))
     return fail(SLM_ERR_INVALID, "slm_render_backward_radii: parameters differ from those of the last forward");
   if (grad_radii && !r->per_point_last)
@@ -808,6 +1163,57 @@ int slm_render_backward_radii(slm_render* r, const slm_render_params* p, const d
   if (!grad_points && !grad_colors && !grad_radii)
     return fail(SLM_ERR_INVALID, "slm_render_backward_radii: null grad_points, grad_colors and grad_radii");
   return rn_backward(r, p, grad_image, grad_points, grad_colors, grad_radii, (hipStream_t)stream);
+}
+
+int slm_render_points_channels(slm_render* r, const slm_render_params* p, int32_t N, const void* points, const float* radii,
+                               int32_t C, const float* features, int32_t feature_stride, const float* bg, float* image,
+                               int32_t* front_id, int32_t* hit_count, void* stream) {
+  if (!r || !p || !image || !bg) return fail(SLM_ERR_INVALID, "slm_render_points_channels: null argument");
+  if (C < 1 || C > SLM_RENDER_MAX_CHANNELS) return fail(SLM_ERR_INVALID, "slm_render_points_channels: channels must be 1..8");
+  if (feature_stride < C) return fail(SLM_ERR_INVALID, "slm_render_points_channels: feature_stride < channels");
+  if (N > 0 && !features) return fail(SLM_ERR_INVALID, "slm_render_points_channels: null features");
+  return render_common(r, p, N, p->points_f64 ? RN_SRC_F64 : RN_SRC_F32, points, nullptr, radii != nullptr, radii, features,
+                       feature_stride, image, front_id, hit_count, stream, "slm_render_points_channels", C, bg);
+}
+
+int slm_render_backward_channels(slm_render* r, const slm_render_params* p, int32_t C, const double* grad_image,
+                                 double* grad_points, double* grad_features, double* grad_radii, void* stream) {
+  if (!r || !p || !grad_image) return fail(SLM_ERR_INVALID, "slm_render_backward_channels: null argument");
+  if (C < 1 || C > SLM_RENDER_MAX_CHANNELS)
+    return fail(SLM_ERR_INVALID, "slm_render_backward_channels: channels must be 1..8");
+  if (!r->has_fwd) return fail(SLM_ERR_INVALID, "slm_render_backward_channels: no completed forward on this context");
+  if (!r->ch_last)
+    return fail(SLM_ERR_INVALID, "slm_render_backward_channels: the last forward was not slm_render_points_channels");
+  if (r->ch_last != C)
+    return fail(SLM_ERR_INVALID, "slm_render_backward_channels: channels differ from those of the last forward");
+  if (!rn_same_geometry(*p, r->last))
+    return fail(SLM_ERR_INVALID, "slm_render_backward_channels: parameters differ from those of the last forward");
+  if (grad_radii && !r->per_point_last)
+    return fail(SLM_ERR_INVALID, "slm_render_backward_channels: grad_radii after a forward with one radius");
+  const int N = r->n_last;
+  if (N == 0) return SLM_OK;
+  if (!grad_points && !grad_features && !grad_radii)
+    return fail(SLM_ERR_INVALID, "slm_render_backward_channels: null grad_points, grad_features and grad_radii");
+  hipStream_t st = (hipStream_t)stream;
+  const RnCam cam = rn_cam(p);
+  const int tiles_y = (p->height + RN_TILE - 1) / RN_TILE;
+  const int want = (grad_points ? RN_BWD_POINTS : 0) | (grad_features ? RN_BWD_COLORS : 0) | (grad_radii ? RN_BWD_RADII : 0);
+  const size_t S = (grad_points ? 3 : 0) + (grad_features ? C : 0) + (grad_radii ? 1 : 0);
+  const unsigned long long total = r->total_last;
+  HIPCHK(grow(r->slab, r->cap_slab, S * total, S * ((size_t)total + total / 4 + 1024)));
+  const dim3 gt(cam.tiles_x, tiles_y), gp((N + 255) / 256), b(256);
+  if (total > 0) {
+    if (r->per_point_last)
+      hipLaunchKernelGGL(k_rn_bwd_entry_ch<true>, gt, b, 0, st, cam, C, rn_padded(C), want, r->off, r->keys, r->pos, r->box,
+                         r->feat, r->pix, r->pixf, grad_image, r->slab);
+    else
+      hipLaunchKernelGGL(k_rn_bwd_entry_ch<false>, gt, b, 0, st, cam, C, rn_padded(C), want, r->off, r->keys, r->pos, r->box,
+                         r->feat, r->pix, r->pixf, grad_image, r->slab);
+  }
+  hipLaunchKernelGGL(k_rn_bwd_point_ch, gp, b, 0, st, N, cam.tiles_x, C, r->off, r->keys, r->pos, r->box, r->slab, grad_points,
+                     grad_features, grad_radii);
+  HIPCHK(hipGetLastError());
+  return SLM_OK;
 }
 
 }  // extern "C"

@@ -39,6 +39,7 @@ EXPORTS = [
     "slm_render_create", "slm_render_destroy", "slm_render_points", "slm_gf_render",
     "slm_render_backward", "slm_render_ssim_loss", "slm_gf_bind_point_grad", "slm_render_backward_ex",
     "slm_render_points_radii", "slm_gf_render_radii", "slm_render_backward_radii",
+    "slm_render_points_channels", "slm_render_backward_channels",
 ]
 
 
@@ -141,6 +142,7 @@ class SlmGraphOutputs(C.Structure):
 
 
 SLM_RENDER_MAX_TRACK = 64   # include/super_lm.h
+SLM_RENDER_MAX_CHANNELS = 8
 
 
 class SlmRenderParams(C.Structure):
@@ -256,6 +258,9 @@ def load():
         "slm_render_points_radii": [vp, C.POINTER(SlmRenderParams), i32, vp, vp, vp, i32, vp, vp, vp, vp],
         "slm_gf_render_radii": [vp, i32, vp, C.POINTER(SlmRenderParams), vp, vp, i32, vp, vp, vp, vp],
         "slm_render_backward_radii": [vp, C.POINTER(SlmRenderParams), vp, vp, vp, vp, vp],
+        "slm_render_points_channels": [vp, C.POINTER(SlmRenderParams), i32, vp, vp, i32, vp, i32, vp, vp, vp,
+                                       vp, vp],
+        "slm_render_backward_channels": [vp, C.POINTER(SlmRenderParams), i32, vp, vp, vp, vp, vp],
         "slm_render_ssim_loss": [i32, i32, vp, vp, dbl, vp, vp, vp],
         "slm_gf_bind_point_grad": [vp, i32, vp, vp],
         "slm_gf_get_deform": [vp, i32, vp, vp],

@@ -19,6 +19,12 @@ Per-point radii: Pulsar's ``vert_rad`` is a float32 (N,) tensor, which the refer
 (``slm_render_backward_radii``).  ``opt.renderer_surfel_radii`` makes ``render_`` / ``render_img`` and GraphFit render the
 surfels with their own radii, ``sf.radii * opt.renderer_radii_scale``.
 
+N-channel features: ``render_channels`` renders an (N,C) feature tensor, 1 <= C <= 8, into an (h,w,C) image in one
+geometry pass (``slm_render_points_channels``: every channel is bitwise what a three-channel render gives for the same
+column); ``render_backward_channels`` and ``render_channels_differentiable`` give dL/dpoints, dL/dfeatures and dL/dradii,
+and ``Pulsar.render_channels`` dispatches between the plain forward and the node like ``Pulsar.render``.
+``opt.renderer_one_pass`` makes ``render_`` blend the colours and the confidence heat in one six-channel render.
+
 The render loss of GraphFit (``opt.render_loss``, deform_mesh.py:113-123) has two native pieces here:
 ``render_backward`` -- dL/dpoints of the last render on a context, the exact derivative of THIS blend (Pulsar's own
 backward is not pinned) -- and ``ssim_render_loss`` -- monodepth2's SSIM-11 loss with the reference's mask,
@@ -173,6 +179,85 @@ def _render(ctx, params, points, colors, with_info=False, radii=None):
     return (img, fid, cnt) if with_info else img
 
 
+def _features_arg(features, n, device):
+    """(N,C) float32 features with unit column stride on ``device``, 1 <= C <= 8, and their row stride in floats"""
+    f = features.detach()
+    if f.dim() != 2 or f.shape[0] != n or not 1 <= f.shape[1] <= _lib.SLM_RENDER_MAX_CHANNELS:
+        raise ValueError(f"features must be (N,C) with N = {n} and 1 <= C <= {_lib.SLM_RENDER_MAX_CHANNELS}, "
+                         f"got {tuple(f.shape)}")
+    if f.dtype != torch.float32 or f.device != device or f.stride(1) != 1 or f.stride(0) < f.shape[1]:
+        f = f.to(device=device, dtype=torch.float32).contiguous()
+    return f, max(int(f.stride(0)), int(f.shape[1]))     # (an empty tensor's row stride may be anything)
+
+
+def _bg_arg(bg, c):
+    """the C background values as a host float array (zeros by default)"""
+    b = torch.zeros(c) if bg is None else torch.as_tensor(bg).detach().float().cpu().reshape(-1)
+    if b.numel() != c:
+        raise ValueError(f"bg must have C = {c} values, got {b.numel()}")
+    return (C.c_float * c)(*b.tolist())
+
+
+def render_channels(ctx, params, points, features, bg=None, with_info=False, radii=None):
+    """Render (N,3) ``points`` with (N,C) ``features``, 1 <= C <= 8: (h,w,C) float32 on the device, every channel the
+    blend of ``render_points`` for its column (``slm_render_points_channels``), in one geometry pass.  ``bg``: C
+    background values (default zeros; ``params.bg`` is not read).  ``with_info`` and ``radii`` as ``render_points``.
+    Forward only: inputs that require grad are refused."""
+    _check_no_grad(points, features, radii)
+    return _render_channels(ctx, params, points, features, bg, with_info, radii)
+
+
+def _render_channels(ctx, params, points, features, bg=None, with_info=False, radii=None):
+    dev = points.device
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError(f"points must be (N,3), got {tuple(points.shape)}")
+    n = int(points.shape[0])
+    pts = points.detach()
+    if pts.dtype != torch.float64:
+        pts = pts.float()
+    pts = pts.contiguous()
+    params.points_f64 = int(pts.dtype == torch.float64)
+    feat, stride = _features_arg(features, n, dev)
+    c = int(feat.shape[1])
+    bgv = _bg_arg(bg, c)
+    rad = None if radii is None else _radii_arg(radii, n, dev)
+    ctx.reserve(n)
+    img = torch.empty((params.height, params.width, c), dtype=torch.float32, device=dev)
+    fid = cnt = None
+    if with_info:
+        fid = torch.empty((params.height, params.width), dtype=torch.int32, device=dev)
+        cnt = torch.empty_like(fid)
+    ptr = lambda t: _dev_ptr(t) if t is not None and t.numel() else None
+    ctx.last_n = 0
+    ctx.serial += 1
+    _lib.check(ctx.lib.slm_render_points_channels(ctx.h, C.byref(params), n, ptr(pts), ptr(rad), c, ptr(feat), stride, bgv, _dev_ptr(img), ptr(fid), ptr(cnt),
+                                                  _stream_ptr(dev)), "slm_render_points_channels")
+    ctx.last_n = n
+    return (img, fid, cnt) if with_info else img
+
+
+def render_backward_channels(ctx, params, grad_image, points=True, features=True, radii=False):
+    """(dL/dpoints (N,3) or None, dL/dfeatures (N,C) or None, dL/dradii (N,) or None), float64, of the last render on
+    ``ctx``, which must be a ``render_channels`` with ``params`` (``slm_render_backward_channels``); C is
+    ``grad_image``'s last dimension.  ``radii`` needs a render with per-point radii."""
+    if not (points or features or radii):
+        raise ValueError("render_backward_channels: request the points' gradient, the features' or the radii's")
+    g = torch.as_tensor(grad_image).detach()
+    dev = g.device
+    if g.dim() != 3 or tuple(g.shape[:2]) != (params.height, params.width):
+        raise ValueError(f"grad_image must be ({params.height},{params.width},C), got {tuple(g.shape)}")
+    c = int(g.shape[2])
+    g = g.to(dtype=torch.float64).contiguous()
+    n = ctx.last_n
+    gp = torch.empty((n, 3), dtype=torch.float64, device=dev) if points else None
+    gf = torch.empty((n, c), dtype=torch.float64, device=dev) if features else None
+    gr = torch.empty((n,), dtype=torch.float64, device=dev) if radii else None
+    ptr = lambda t: _dev_ptr(t) if t is not None and t.numel() else None
+    _lib.check(ctx.lib.slm_render_backward_channels(ctx.h, C.byref(params), c, _dev_ptr(g), ptr(gp), ptr(gf), ptr(gr),
+                                                    _stream_ptr(dev)), "slm_render_backward_channels")
+    return gp, gf, gr
+
+
 def render_backward(ctx, params, grad_image):
     """dL/dpoints (N,3) float64 of the last render on ``ctx`` (``render_points`` or GraphFit's ``slm_gf_render``:
     then by surfel row, 0 on unstable rows) for ``grad_image`` = dL/dimage (h,w,3).  ``params`` must be the render's.
@@ -275,6 +360,58 @@ def render_differentiable(ctx, params, points, colors, radii=None):
     return _Render.apply(ctx, params, points, colors, radii)
 
 
+class _RenderChannels(torch.autograd.Function):
+    """``_Render`` for N-channel features: the same saved inputs and the same serial / recompute rule."""
+
+    @staticmethod
+    def forward(fctx, rctx, params, points, features, bg, radii):
+        img = _render_channels(rctx, params, points, features, bg, radii=radii)
+        fctx.rctx, fctx.params, fctx.serial = rctx, SlmRenderParams.from_buffer_copy(params), rctx.serial
+        fctx.per_point, fctx.bg = radii is not None, bg
+        fctx.save_for_backward(points, features, *(() if radii is None else (radii,)))
+        return img
+
+    @staticmethod
+    @once_differentiable
+    def backward(fctx, grad_image):
+        points, features = fctx.saved_tensors[:2]
+        radii = fctx.saved_tensors[2] if fctx.per_point else None
+        want_p, want_f = fctx.needs_input_grad[2], fctx.needs_input_grad[3]
+        want_r = fctx.per_point and fctx.needs_input_grad[5]
+        if not (want_p or want_f or want_r):
+            return None, None, None, None, None, None
+        rctx, params = fctx.rctx, fctx.params
+        if rctx.serial != fctx.serial:
+            _render_channels(rctx, params, points, features, fctx.bg, radii=radii)
+            fctx.serial = rctx.serial
+        gp, gf, gr = render_backward_channels(rctx, params, grad_image, want_p, want_f, want_r)
+        if gp is not None:
+            gp = gp.to(device=points.device, dtype=points.dtype)
+        if gf is not None:
+            gf = gf.to(device=features.device, dtype=features.dtype)
+        if gr is not None:
+            gr = gr.to(device=radii.device, dtype=radii.dtype)
+        return None, None, gp, gf, None, gr
+
+
+def render_channels_differentiable(ctx, params, points, features, bg=None, radii=None):
+    """``render_channels`` as a node of the autograd graph: (h,w,C) float32 image; gradients to ``points`` (N,3), to
+    ``features`` (N,C) and, when given, to the per-point ``radii`` (N,), each in its input's dtype and only where
+    ``needs_input_grad`` asks (``render_backward_channels`` for the grad_image cast to float64).  ``bg`` is a constant.
+    ``ctx`` may be shared with other renders (see ``_Render``)."""
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError(f"points must be (N,3), got {tuple(points.shape)}")
+    n = int(points.shape[0])
+    if features.dim() != 2 or features.shape[0] != n or not 1 <= features.shape[1] <= _lib.SLM_RENDER_MAX_CHANNELS:
+        raise ValueError(f"features must be (N,C) with N = {n} and 1 <= C <= {_lib.SLM_RENDER_MAX_CHANNELS}, "
+                         f"got {tuple(features.shape)}")
+    if radii is not None and (radii.dim() != 1 or radii.shape[0] != n):
+        raise ValueError(f"radii must be (N,) with N = {n}, got {tuple(radii.shape)}")
+    if torch.is_tensor(bg):
+        bg = bg.detach().float().cpu()
+    return _RenderChannels.apply(ctx, params, points, features, bg, radii)
+
+
 def _ssim_args(img_hwc, target_chw):
     img = img_hwc.detach()
     if img.dim() != 3 or img.shape[2] != 3:
@@ -375,6 +512,28 @@ class Pulsar:
             params = render_params(inputs["K"], self.height, self.width, view_scale, rad, bg_col)
             return render_points(self.context(view_scale), params, points, colors, with_info, radii)
 
+    def render_channels(self, inputs, data, features, view_scale=1.0, rad=0.01, bg=None, with_info=False):
+        """``render`` for (N,C) ``features``, 1 <= C <= 8: the (h,w,C) float32 image of ``data.points``, every channel
+        blended like a colour channel, in one geometry pass.  ``rad`` as for ``render``; ``bg``: C values, default
+        zeros.  In the graph (``render_channels_differentiable``) under the conditions of ``render``."""
+        points = data.points
+        rad, radii = _split_rad(rad, int(points.shape[0]))
+        params = render_params(inputs["K"], self.height, self.width, view_scale, rad)
+        if self.differentiable and torch.is_grad_enabled():
+            for name, t in (("bg", bg), ("rad", rad)):
+                if torch.is_tensor(t) and t.requires_grad:
+                    raise RuntimeError(f"super_amd.renderer.Pulsar: {name} is a constant of the render (no gradient); "
+                                       f"pass a {name} that does not require grad")
+            if any(torch.is_tensor(t) and t.requires_grad for t in (points, features, radii)):
+                if with_info:
+                    raise ValueError("super_amd.renderer.Pulsar: with_info is not available for a render in the graph")
+                return render_channels_differentiable(self.context(view_scale), params, points, features, bg, radii)
+        if self.differentiable:        # not in the graph: the plain forward of the detached inputs
+            points, features = points.detach(), features.detach()
+            radii = None if radii is None else radii.detach()
+        with torch.no_grad():
+            return render_channels(self.context(view_scale), params, points, features, bg, with_info, radii)
+
     def forward(self, inputs, data, colors=None, view_scale=1.0, rad=0.01, bg_col=torch.tensor([0.0, 0.0, 0.0])):
         return self.render(inputs, data, colors, view_scale, rad, bg_col)
 
@@ -429,7 +588,9 @@ def render_(sf, inputs):
     """(reference ``Surfels.render_``, nodes.py:630-645) sets ``sf.renderImg`` (colours) and
     ``sf.renderImg_conf_heat`` (``magma`` of the confidences), both (1,3,H,W), from the stable surfels.  With
     ``opt.renderer_surfel_radii`` the radii are ``sf.radii[sf.isStable] * opt.renderer_radii_scale`` (default 1.0)
-    instead of ``opt.renderer_rad``."""
+    instead of ``opt.renderer_rad``.  With ``opt.renderer_one_pass`` both images come from one six-channel render of
+    ``cat(colors, heat)`` (bitwise the two renders'; the context then holds a channels forward, which a later
+    ``render_backward`` on it refuses)."""
     rad = getattr(sf.opt, "renderer_rad", DEFAULT_RAD)
     if getattr(sf.opt, "renderer_surfel_radii", False):      # opt-in: every surfel with its own radius
         rad = sf.radii[sf.isStable].detach() * float(getattr(sf.opt, "renderer_radii_scale", 1.0))
@@ -439,6 +600,11 @@ def render_(sf, inputs):
     heat = conf2color(sf.confs)[sf.isStable]
     data = type("Data", (), {})()
     data.points, data.colors = pts, cols
+    if getattr(sf.opt, "renderer_one_pass", False):          # opt-in: one geometry pass for both images
+        both = r.render_channels(inputs, data, torch.cat([cols.float(), heat.float()], 1), rad=rad)
+        sf.renderImg = both[..., :3].contiguous().permute(2, 0, 1).unsqueeze(0)          # the layout of the two renders
+        sf.renderImg_conf_heat = both[..., 3:].contiguous().permute(2, 0, 1).unsqueeze(0)
+        return
     sf.renderImg = r(inputs, data, colors=data.colors, rad=rad).permute(2, 0, 1).unsqueeze(0)
     sf.renderImg_conf_heat = r(inputs, data, colors=heat, rad=rad).permute(2, 0, 1).unsqueeze(0)
 

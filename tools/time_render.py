@@ -8,11 +8,17 @@ through torch (Pulsar(opt, differentiable=True), gradients to the points and the
 
     python tools/time_render.py [--reps 30] [--out gpu_out.json]
     python tools/time_render.py --radii [--reps 30] [--out gpu_out.json]
+    python tools/time_render.py --channels 6 [--radii] [--reps 30] [--out gpu_out.json]
 
 ``--radii`` times the per-point render instead (slm_render_points_radii): the same 300 k surfels at 480x640 with the
 radii of the reference's formula, Z / (sqrt(2) f clamp(|n_z|, 0.26, 1)); beside the two one-radius forwards it reports
 the per-point forward, forward + SSIM loss + backward (the point gradient; with the radius gradient as well), the loss +
 backward alone, and the fractions of pixels hit and kept.
+
+``--channels C`` times the N-channel render (slm_render_points_channels) on the same scene at 2e-4, at 2e-3 and, with
+``--radii``, with the formula's radii: the C-channel forward, the same columns as ceil(C/3) three-channel renders (what
+the C channels cost before), and the channels backward (points and features; with the radii as well under ``--radii``) for a
+random dL/dimage, after one forward.
 
 HIP events around each call after warm-up; median and maximum over --reps runs.  A render synchronises once
 inside (the tile-list total is read back), so a timed call includes that round trip.  Kernel times: run it under
@@ -98,14 +104,54 @@ def radii_mode(a):
     return res
 
 
+def channels_mode(a):
+    from super_amd import synth
+    from super_amd.renderer import (DEFAULT_RAD, RenderContext, render_backward_channels, render_channels, render_params,
+                                    render_points)
+    nch, res = a.channels, {}
+    sc = synth.make_scene(N=300_000, J=512, H=480, W=640, seed=5, src_border=2)
+    pts = torch.from_numpy(sc.sf_points).cuda()
+    feat = torch.from_numpy(np.random.default_rng(2).uniform(size=(sc.N, nch)).astype(np.float32)).cuda()
+    groups = []                                    # the same columns, three at a time, padded with zeros
+    for c0 in range(0, nch, 3):
+        cols = torch.zeros((sc.N, 3), dtype=torch.float32, device="cuda")
+        cols[:, :min(3, nch - c0)] = feat[:, c0:c0 + 3]
+        groups.append(cols)
+    K = torch.from_numpy(sc.K).float()[None]
+    cases = [("rad2e-4", 2e-4, None), ("rad2e-3", 2e-3, None)]
+    if a.radii:
+        nz = np.clip(np.abs(sc.sf_norms[:, 2].astype(np.float64)), 0.26, 1.0)
+        radii = (sc.sf_points[:, 2].astype(np.float64) / (np.sqrt(2.0) * sc.K[0, 0] * nz)).astype(np.float32)
+        cases.append(("radii", DEFAULT_RAD, torch.from_numpy(radii).cuda()))
+    ctx = RenderContext(sc.H, sc.W, sc.N)
+    g = torch.randn((sc.H, sc.W, nch), dtype=torch.float64, device="cuda", generator=torch.Generator("cuda").manual_seed(3))
+    for key, rad, radii in cases:
+        p = render_params(K, sc.H, sc.W, 1.0, rad)
+        res[f"channels{nch}_fwd_{key}"] = _time(lambda: render_channels(ctx, p, pts, feat, radii=radii), a.reps)
+        res[f"three_channel_x{len(groups)}_fwd_{key}"] = _time(
+            lambda: [render_points(ctx, p, pts, cols, radii=radii) for cols in groups], a.reps)
+        res[f"three_channel_x1_fwd_{key}"] = _time(lambda: render_points(ctx, p, pts, groups[0], radii=radii), a.reps)
+        _, _, cnt = render_channels(ctx, p, pts, feat, with_info=True, radii=radii)
+        res[f"channels{nch}_fwd_{key}"]["pixels_hit"] = float((cnt > 0).float().mean())
+        res[f"channels{nch}_fwd_{key}"]["hits_per_pixel_mean"] = float(cnt.float().mean())
+        res[f"channels{nch}_bwd_points_features_{key}"] = _time(lambda: render_backward_channels(ctx, p, g), a.reps)
+        if radii is not None:
+            res[f"channels{nch}_bwd_points_features_radii_{key}"] = _time(
+                lambda: render_backward_channels(ctx, p, g, radii=True), a.reps)
+    res["render_points"] = sc.N
+    res["channels"] = nch
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--out", default=None)
     ap.add_argument("--radii", action="store_true", help="time the per-point render (see the module's docstring)")
+    ap.add_argument("--channels", type=int, default=0, help="time the N-channel render with this many channels (1..8)")
     a = ap.parse_args()
-    if a.radii:
-        res = radii_mode(a)
+    if a.channels or a.radii:
+        res = channels_mode(a) if a.channels else radii_mode(a)
         print(json.dumps(res, indent=1))
         if a.out:
             with open(a.out, "w") as f:
