@@ -1,33 +1,39 @@
-// slm_render.hip -- forward surfel renderer: Pulsar's blend (Lassner & Zollhoefer, CVPR 2021) at the parameters of
-// the reference's call (renderer/renderer.py:23-78).  The image it computes is specified in include/super_lm.h and
-// DESIGN.md section "Renderer"; tests/render_model.py restates it on the CPU.
+// slm_render.hip -- the surfel renderer: Pulsar's blend (Lassner & Zollhoefer, CVPR 2021) at the parameters of the
+// reference's call (renderer/renderer.py:23-78), forward and backward.  The image it computes is specified in
+// include/super_lm.h and DESIGN.md section "Renderer"; tests/render_model.py restates it on the CPU.
 //
-// Four launches and one 8-byte read-back per render:
+// Forward (render_common, behind the five forward entry points): four launches and one 8-byte read-back.
 //   k_rn_project  per point: float32 position, cull, pixel box of the sphere's silhouette, count per 16x16 tile
 //   k_rn_scan     one workgroup: exclusive scan of the tile counts -> list offsets and scatter cursors
 //   (host)        the list total sizes the key buffers
-//   k_rn_scatter  per point: key (float bits of Z << 32 | row) into the list of every tile its box touches
-//   k_rn_tile     one workgroup per tile: sort the tile's keys front to back (bitonic in LDS; a list longer than
+//   k_rn_scatter  per point: its key (rn_key: float bits of Z << 32 | row) into the list of every tile its box touches
+//   k_rn_tile     one workgroup per tile, rn_walk: sort the tile's keys front to back (bitonic in LDS; a list longer than
 //                 RN_SORT_CAP is sorted in LDS chunk by chunk and merged in global memory), then every lane walks its
 //                 pixel's list front to back in LDS chunks, keeps the first n_track hits and blends in float64.
 // The keys are unique (one per point and tile), so the sorted order -- and with it every float64 sum, taken by one
 // lane in list order -- does not depend on the order the atomic cursors handed out slots: renders are bitwise
 // reproducible.  The only atomics are integer ones (tile counts, cursors).
 //
-// Every forward leaves on the context what slm_render_backward needs: the float32 centres and pixel boxes, a copy of the
-// colours, the sorted tile lists (written back to `keys` on both sort paths) and per pixel the float64 blend (zt_max, W,
-// C) with the list position of its n_track-th hit.  The backward is two launches, store-and-sum, no float atomics:
-//   k_rn_bwd_entry  one workgroup per tile: the tile's pixel coefficients g/W, g.C/W in LDS, then per list entry the
-//                   contributions of the pixels of its box inside the tile, summed in row-major pixel order -> `slab`
-//   k_rn_bwd_point  per point: the slab entries of its tiles, found by binary search of its key, summed in tile order
-// slm_render_backward_ex adds the colour gradient in the same two passes (k_rn_bwd_entry<MODE>, k_rn_bwd_point_ex<MODE>):
-// the slab holds 6 doubles per entry with both gradients, 3 with one.
+// Every forward leaves on the context what a backward needs: the float32 centres and pixel boxes, a copy of the points'
+// values, the sorted tile lists (written back to `keys` on both sort paths) and per pixel the float64 blend (zt_max, W, C)
+// with the list position of its n_track-th hit.  Backward (rn_backward, behind the four backward entry points): two
+// launches, store-and-sum, no float atomics.
+//   k_rn_bwd_entry  one workgroup per tile, rn_bwd_tile: the tile's pixel coefficients g/W, g.C/W in LDS, then per list entry
+//                   the contributions of the pixels of its box inside the tile, summed in row-major pixel order -> `slab`
+//   k_rn_bwd_point  per point, rn_point_entries: the slab entries of its tiles, each found by binary search of its key
+//                   (rn_find), summed in tile order
+// What is asked for -- the point gradient, the value gradient, the radius gradient -- decides the doubles per slab entry.
 //
-// Per-point radii (slm_render_points_radii, slm_gf_render_radii): the instantiations with PR = true read the radius of a
-// point from pos[].w, where k_rn_project<SRC, true> leaves the caller's float32 value (so a later backward does not
-// depend on the caller's buffer); a radius that is not finite or not > 0 culls its row.  The instantiations with
-// PR = false read the one double radius of the parameters and are the code they were before.  The radius gradient
-// (slm_render_backward_radii) is the MODE bit RN_BWD_RADII: one more double per slab entry, behind the others.
+// Two things vary, and each kernel family has one instantiation per combination:
+//   PR        per-point radii (slm_render_points_radii, slm_gf_render_radii, a channels forward with radii): the radius of a
+//             point is pos[].w, where k_rn_project<SRC, true> leaves the caller's float32 value (so a later backward does not
+//             depend on the caller's buffer); a radius that is not finite or not > 0 culls its row.  Without PR every point
+//             has the one double radius of the parameters.  Only a PR forward has a radius gradient.
+//   channels  three colours read in place from the caller's rows (k_rn_tile, k_rn_bwd_entry<MODE>, k_rn_bwd_point_ex<MODE>:
+//             what is asked for is the compile-time MODE), or C = 1..8 features copied into padded rows on the context
+//             (k_rn_tile_ch<CP>, k_rn_bwd_entry_ch, k_rn_bwd_point_ch: C and what is asked for are run-time uniforms).  The
+//             two share rn_walk and rn_bwd_tile and differ in how a hit's values are accumulated, in s_k and the value
+//             gradient, and in the pixel record (RnPix alone, or RnPix + pixf).
 #include <climits>
 #include <cmath>
 #include <cstring>
@@ -197,6 +203,24 @@ __global__ void __launch_bounds__(1024) k_rn_scan(int n, const unsigned int* __r
   if (t == 0) off[n] = carry;
 }
 
+// the key of point i in the list of every tile it touches: ascending keys are front to back (Z > 0), ties by row
+__device__ __forceinline__ unsigned long long rn_key(const float4* __restrict__ pos, int i) {
+  return ((unsigned long long)__float_as_uint(pos[i].z) << 32) | (unsigned int)i;
+}
+
+#define RN_ABSENT (~0ull)
+
+// the position of `key` in tile t's sorted list (keys are unique), or RN_ABSENT
+__device__ __forceinline__ unsigned long long rn_find(const unsigned long long* __restrict__ off,
+                                                      const unsigned long long* __restrict__ keys, int t, unsigned long long key) {
+  unsigned long long lo = off[t], hi = off[t + 1];
+  while (lo < hi) {
+    const unsigned long long mid = (lo + hi) >> 1;
+    if (keys[mid] < key) lo = mid + 1; else hi = mid;
+  }
+  return lo < off[t + 1] && keys[lo] == key ? lo : RN_ABSENT;
+}
+
 __global__ void __launch_bounds__(256) k_rn_scatter(int N, int tiles_x, const float4* __restrict__ pos,
                                                     const int4* __restrict__ box, unsigned long long* __restrict__ cur,
                                                     unsigned long long* __restrict__ keys) {
@@ -204,7 +228,7 @@ __global__ void __launch_bounds__(256) k_rn_scatter(int N, int tiles_x, const fl
   if (i >= N) return;
   const int4 b = box[i];
   if (b.x > b.y) return;
-  const unsigned long long key = ((unsigned long long)__float_as_uint(pos[i].z) << 32) | (unsigned int)i;   // Z > 0
+  const unsigned long long key = rn_key(pos, i);
   for (int ty = b.z / RN_TILE; ty <= b.w / RN_TILE; ++ty)
     for (int tx = b.x / RN_TILE; tx <= b.y / RN_TILE; ++tx) {
       const unsigned long long at = atomicAdd(cur + ty * tiles_x + tx, 1ull);
@@ -278,12 +302,25 @@ __device__ __forceinline__ void rn_tile_sort(unsigned long long* skey, unsigned 
   }
 }
 
-template <bool PR>
-__global__ void __launch_bounds__(256) k_rn_tile(RnCam cam, const unsigned long long* __restrict__ off,
-                                                 unsigned long long* __restrict__ keys, unsigned long long* __restrict__ tmp,
-                                                 const float4* __restrict__ pos, const int4* __restrict__ box,
-                                                 const float* __restrict__ colors, int cstride, float* __restrict__ image,
-                                                 int* __restrict__ front_id, int* __restrict__ hit_count, RnPix* __restrict__ pix) {
+// What the walk of a tile leaves in every lane: its pixel and whether that lies in the image, the hits it took (<= n_track),
+// the front-most row (-1: none), the list position of the n_track-th hit (INT_MAX: fewer), the depth term of the first hit
+// and the sum of the weights.
+struct RnWalk {
+  int i, j, nh, first, cut;
+  bool inside;
+  double zt_max, sw;
+};
+
+// The forward of one tile, all 256 lanes of its workgroup: sort the tile's list front to back (it stays in `keys` for the
+// backward), then every lane walks its pixel's ray down the list, staged in LDS RN_CHUNK entries at a time, and takes the
+// first n_track entries whose box holds the pixel and whose sphere the ray enters (rho < r; r the point's own with PR, else
+// the parameters'), each with the weight w_k = (1 - rho / r) exp((zt - zt_max) / gamma).  hit(row, w_k) accumulates the
+// point's values: the one step of the walk in which the three-channel and the N-channel kernels differ.  The workgroup
+// leaves the list when no lane is active any more.
+template <bool PR, typename Hit>
+__device__ __forceinline__ RnWalk rn_walk(const RnCam& cam, const unsigned long long* __restrict__ off,
+                                          unsigned long long* __restrict__ keys, unsigned long long* __restrict__ tmp,
+                                          const float4* __restrict__ pos, const int4* __restrict__ box, Hit hit) {
   __shared__ unsigned long long skey[RN_SORT_CAP];
   __shared__ float4 spos[RN_CHUNK];
   __shared__ int4 sbox[RN_CHUNK];
@@ -298,13 +335,11 @@ __global__ void __launch_bounds__(256) k_rn_tile(RnCam cam, const unsigned long 
 
   const int j = blockIdx.x * RN_TILE + (threadIdx.x & (RN_TILE - 1));
   const int i = blockIdx.y * RN_TILE + (threadIdx.x / RN_TILE);
-  const bool inside = i < cam.h && j < cam.w;
+  RnWalk w = {i, j, 0, -1, INT_MAX, i < cam.h && j < cam.w, 0.0, 0.0};
   double dx, dy, inv_dn;
   rn_ray(cam, i, j, dx, dy, inv_dn);
   const double zspan = cam.zf - cam.zn;
-  int nh = 0, first = -1, cut = INT_MAX;
-  double zt_max = 0.0, sw = 0.0, s0 = 0.0, s1 = 0.0, s2 = 0.0;
-  bool active = inside;
+  bool active = w.inside;
   for (int c0 = 0; c0 < n; c0 += RN_CHUNK) {
     const int m = min(RN_CHUNK, n - c0);
     if (threadIdx.x < m) {
@@ -326,18 +361,15 @@ __global__ void __launch_bounds__(256) k_rn_tile(RnCam cam, const unsigned long 
         if (!(rho < r)) continue;
         const double zt = (cam.zf - Z) / zspan;
         const int id = sid[e];
-        if (nh == 0) {
-          zt_max = zt;
-          first = id;
+        if (w.nh == 0) {
+          w.zt_max = zt;
+          w.first = id;
         }
-        const double wk = (1.0 - rho / r) * exp((zt - zt_max) / cam.gamma);
-        const float* c = colors + (size_t)id * cstride;
-        sw += wk;
-        s0 += wk * (double)c[0];
-        s1 += wk * (double)c[1];
-        s2 += wk * (double)c[2];
-        if (++nh == cam.n_track) {
-          cut = c0 + e;
+        const double wk = (1.0 - rho / r) * exp((zt - w.zt_max) / cam.gamma);
+        w.sw += wk;
+        hit(id, wk);
+        if (++w.nh == cam.n_track) {
+          w.cut = c0 + e;
           active = false;
           break;
         }
@@ -345,13 +377,30 @@ __global__ void __launch_bounds__(256) k_rn_tile(RnCam cam, const unsigned long 
     }
     if (!__syncthreads_or(active && c0 + RN_CHUNK < n)) break;
   }
-  if (!inside) return;
-  const size_t px = (size_t)i * cam.w + j;
+  return w;
+}
+
+// the three-channel forward: three float64 sums of w_k c_k over the caller's colours; the pixel's record goes to pix
+template <bool PR>
+__global__ void __launch_bounds__(256) k_rn_tile(RnCam cam, const unsigned long long* __restrict__ off,
+                                                 unsigned long long* __restrict__ keys, unsigned long long* __restrict__ tmp,
+                                                 const float4* __restrict__ pos, const int4* __restrict__ box,
+                                                 const float* __restrict__ colors, int cstride, float* __restrict__ image,
+                                                 int* __restrict__ front_id, int* __restrict__ hit_count, RnPix* __restrict__ pix) {
+  double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+  const RnWalk w = rn_walk<PR>(cam, off, keys, tmp, pos, box, [&](int id, double wk) {
+    const float* c = colors + (size_t)id * cstride;
+    s0 += wk * (double)c[0];
+    s1 += wk * (double)c[1];
+    s2 += wk * (double)c[2];
+  });
+  if (!w.inside) return;
+  const size_t px = (size_t)w.i * cam.w + w.j;
   float o0 = cam.bg0, o1 = cam.bg1, o2 = cam.bg2;
-  RnPix rec = {0.0, 0.0, 0.0, 0.0, 0.0, cut, 0};
-  if (nh > 0) {
-    const double wbg = exp((cam.eps - zt_max) / cam.gamma), den = sw + wbg;
-    rec.zt_max = zt_max;
+  RnPix rec = {0.0, 0.0, 0.0, 0.0, 0.0, w.cut, 0};
+  if (w.nh > 0) {
+    const double wbg = exp((cam.eps - w.zt_max) / cam.gamma), den = w.sw + wbg;
+    rec.zt_max = w.zt_max;
     rec.W = den;
     rec.c0 = (s0 + wbg * (double)cam.bg0) / den;
     rec.c1 = (s1 + wbg * (double)cam.bg1) / den;
@@ -364,8 +413,8 @@ __global__ void __launch_bounds__(256) k_rn_tile(RnCam cam, const unsigned long 
   image[3 * px] = o0;
   image[3 * px + 1] = o1;
   image[3 * px + 2] = o2;
-  if (front_id) front_id[px] = first;
-  if (hit_count) hit_count[px] = nh;
+  if (front_id) front_id[px] = w.first;
+  if (hit_count) hit_count[px] = w.nh;
 }
 
 // ---- N-channel features (slm_render_points_channels) ----------------------------------------------------------------------
@@ -383,10 +432,10 @@ __global__ void __launch_bounds__(256) k_rn_feat(int N, int C, int CP, const flo
   feat[q] = c < C ? features[i * stride + c] : 0.f;
 }
 
-// k_rn_tile with CP accumulators (a compile-time bound, padded: see above) of which the first C are written.  Every channel's
-// sum is the FMA chain that k_rn_tile's s0 / s1 / s2 compile to, written out, so a channel is bitwise what the three-channel
-// kernel gives for the same column.  The record of a pixel: zt_max, W and cut in pix (its colour fields 0), the C float64
-// channels in pixf.
+// The N-channel forward: CP accumulators (a compile-time bound, padded: see above) of which the first C are written.  Every
+// channel's sum is the FMA chain that k_rn_tile's s0 / s1 / s2 compile to, written out, so a channel is bitwise what the
+// three-channel kernel gives for the same column.  The record of a pixel: zt_max, W and cut in pix (its colour fields 0), the
+// C float64 channels in pixf.
 template <bool PR, int CP>
 __global__ void __launch_bounds__(256) k_rn_tile_ch(RnCam cam, RnBg bg, int C, const unsigned long long* __restrict__ off,
                                                     unsigned long long* __restrict__ keys, unsigned long long* __restrict__ tmp,
@@ -394,82 +443,28 @@ __global__ void __launch_bounds__(256) k_rn_tile_ch(RnCam cam, RnBg bg, int C, c
                                                     const float* __restrict__ feat, float* __restrict__ image,
                                                     int* __restrict__ front_id, int* __restrict__ hit_count,
                                                     RnPix* __restrict__ pix, double* __restrict__ pixf) {
-  __shared__ unsigned long long skey[RN_SORT_CAP];
-  __shared__ float4 spos[RN_CHUNK];
-  __shared__ int4 sbox[RN_CHUNK];
-  __shared__ int sid[RN_CHUNK];
-  const int tile = blockIdx.y * cam.tiles_x + blockIdx.x;
-  const unsigned long long base = off[tile];
-  const int n = (int)(off[tile + 1] - base);
-  unsigned long long* list = keys + base;
-  const unsigned long long* gl = list;
-  rn_tile_sort(skey, list, tmp + base, n);
-  const bool in_lds = n <= RN_SORT_CAP;
-
-  const int j = blockIdx.x * RN_TILE + (threadIdx.x & (RN_TILE - 1));
-  const int i = blockIdx.y * RN_TILE + (threadIdx.x / RN_TILE);
-  const bool inside = i < cam.h && j < cam.w;
-  double dx, dy, inv_dn;
-  rn_ray(cam, i, j, dx, dy, inv_dn);
-  const double zspan = cam.zf - cam.zn;
-  int nh = 0, first = -1, cut = INT_MAX;
-  double zt_max = 0.0, sw = 0.0, s[CP];
+  double s[CP];
 #pragma unroll
   for (int c = 0; c < CP; ++c) s[c] = 0.0;
-  bool active = inside;
-  for (int c0 = 0; c0 < n; c0 += RN_CHUNK) {
-    const int m = min(RN_CHUNK, n - c0);
-    if (threadIdx.x < m) {
-      const unsigned long long k = in_lds ? skey[c0 + threadIdx.x] : gl[c0 + threadIdx.x];
-      const int id = (int)(unsigned int)k;
-      sid[threadIdx.x] = id;
-      spos[threadIdx.x] = pos[id];
-      sbox[threadIdx.x] = box[id];
-    }
-    __syncthreads();
-    if (active) {
-      for (int e = 0; e < m; ++e) {
-        const int4 b = sbox[e];
-        if (j < b.x || j > b.y || i < b.z || i > b.w) continue;
-        const float4 p = spos[e];
-        const double X = p.x, Y = p.y, Z = p.z;
-        const double rho = rn_rho(X, Y, Z, dx, dy, inv_dn);
-        const double r = PR ? (double)p.w : cam.r;
-        if (!(rho < r)) continue;
-        const double zt = (cam.zf - Z) / zspan;
-        const int id = sid[e];
-        if (nh == 0) {
-          zt_max = zt;
-          first = id;
-        }
-        const double wk = (1.0 - rho / r) * exp((zt - zt_max) / cam.gamma);
-        const float4* f = reinterpret_cast<const float4*>(feat + (size_t)id * CP);
-        sw += wk;
+  const RnWalk w = rn_walk<PR>(cam, off, keys, tmp, pos, box, [&](int id, double wk) {
+    const float4* f = reinterpret_cast<const float4*>(feat + (size_t)id * CP);
 #pragma unroll
-        for (int q = 0; q < CP / 4; ++q) {
-          const float4 v = f[q];
-          s[4 * q] = fma(wk, (double)v.x, s[4 * q]);
-          s[4 * q + 1] = fma(wk, (double)v.y, s[4 * q + 1]);
-          s[4 * q + 2] = fma(wk, (double)v.z, s[4 * q + 2]);
-          s[4 * q + 3] = fma(wk, (double)v.w, s[4 * q + 3]);
-        }
-        if (++nh == cam.n_track) {
-          cut = c0 + e;
-          active = false;
-          break;
-        }
-      }
+    for (int q = 0; q < CP / 4; ++q) {
+      const float4 v = f[q];
+      s[4 * q] = fma(wk, (double)v.x, s[4 * q]);
+      s[4 * q + 1] = fma(wk, (double)v.y, s[4 * q + 1]);
+      s[4 * q + 2] = fma(wk, (double)v.z, s[4 * q + 2]);
+      s[4 * q + 3] = fma(wk, (double)v.w, s[4 * q + 3]);
     }
-    if (!__syncthreads_or(active && c0 + RN_CHUNK < n)) break;
-  }
-  if (!inside) return;
-  const size_t px = (size_t)i * cam.w + j;
-  RnPix rec = {0.0, 0.0, 0.0, 0.0, 0.0, cut, 0};
+  });
+  if (!w.inside) return;
+  const size_t px = (size_t)w.i * cam.w + w.j;
+  RnPix rec = {0.0, 0.0, 0.0, 0.0, 0.0, w.cut, 0};
   double den = 1.0, wbg = 0.0;
-  if (nh > 0) {
-    wbg = exp((cam.eps - zt_max) / cam.gamma);
-    den = sw + wbg;
-    rec.zt_max = zt_max;
+  if (w.nh > 0) {
+    wbg = exp((cam.eps - w.zt_max) / cam.gamma);
+    den = w.sw + wbg;
+    rec.zt_max = w.zt_max;
     rec.W = den;
   }
   pix[px] = rec;
@@ -478,38 +473,35 @@ __global__ void __launch_bounds__(256) k_rn_tile_ch(RnCam cam, RnBg bg, int C, c
     if (c < C) {
       float o = bg.v[c];
       double F = 0.0;
-      if (nh > 0) {
+      if (w.nh > 0) {
         F = fma(wbg, (double)bg.v[c], s[c]) / den;
         o = (float)F;
       }
       pixf[px * C + c] = F;
       image[px * C + c] = o;
     }
-  if (front_id) front_id[px] = first;
-  if (hit_count) hit_count[px] = nh;
+  if (front_id) front_id[px] = w.first;
+  if (hit_count) hit_count[px] = w.nh;
 }
 
-// What a backward computes: the point gradient, the colour gradient, or both (template parameter of the backward kernels).
-// The slab holds 3 doubles per tile-list entry and output: the point partials first.
-enum { RN_BWD_POINTS = 1, RN_BWD_COLORS = 2, RN_BWD_RADII = 4 };
-
-// Backward, pass 1 (see the top of the file): one workgroup per tile.  Lane t stages pixel t of the tile -- its ray and the
-// coefficients a = g / W, b = g.C / W of s_k = g.(c_k - C) / W, or cut = -1 when the pixel has no hit or g = 0 -- then every
-// lane takes list entries e = t, t + 256, ... and sums, in row-major order over the pixels of the entry's box inside the tile
-// that it reaches (position <= cut, rho < r: the forward's decisions), s_k ( -(e_k / r) drho/dP - w_k / (gamma zspan) z )
-// (RN_BWD_POINTS), a w_k = g w_k / W (RN_BWD_COLORS) and s_k e_k rho / r^2 (RN_BWD_RADII, per-point radii only).  With PR the
-// radius r is the point's (pos[].w), else the parameters'.
-template <int MODE, bool PR>
-__global__ void __launch_bounds__(256) k_rn_bwd_entry(RnCam cam, const unsigned long long* __restrict__ off,
-                                                      const unsigned long long* __restrict__ keys, const float4* __restrict__ pos,
-                                                      const int4* __restrict__ box, const float4* __restrict__ col,
-                                                      const RnPix* __restrict__ pix, const double* __restrict__ gimg,
-                                                      double* __restrict__ slab) {
-  constexpr bool GP = (MODE & RN_BWD_POINTS) != 0, GC = (MODE & RN_BWD_COLORS) != 0, GR = (MODE & RN_BWD_RADII) != 0;
-  constexpr bool GS = GP || GR;   // s_k is needed: the colour copy and b
-  constexpr int S = (GP ? 3 : 0) + (GC ? 3 : 0) + (GR ? 1 : 0);
-  static_assert(PR || !GR, "the radius gradient belongs to a per-point forward");
-  __shared__ double sdx[256], sdy[256], sinv[256], szt[256], sa0[256], sa1[256], sa2[256], sb[GS ? 256 : 1];
+// Backward, pass 1 (see the top of the file), all 256 lanes of a tile's workgroup.  Lane t stages pixel t of the tile -- its
+// ray, zt_max and cut, or cut = -1 when val.stage() says that the pixel has no hit or g = 0 -- then every lane takes list
+// entries e = t, t + 256, ... and sums, in row-major order over the pixels of the entry's box inside the tile that it reaches
+// (position <= cut, rho < r: the forward's decisions), with e_k = exp((zt - zt_max) / gamma) and w_k = (1 - rho / r) e_k:
+//   GP  s_k ( -(e_k / r) drho/dP - w_k / (gamma zspan) z ),   GR  s_k e_k rho / r^2   (per-point radii only),
+// into the first three and the last of the entry's S slab doubles.  With PR the radius r is the point's (pos[].w), else the
+// parameters'.  The values of the points -- three colours or C features -- are Val's:
+//   stage(t, px, rec)  read g at pixel px; false when W = 0 or g = 0, else a = g / W and b = g.C / W of pixel t into LDS
+//   entry(id)          read the values of point id, clear its value gradient
+//   sk(t)              s_k = a.c_k - b at pixel t (asked only with GP or GR)
+//   add(t, w_k)        value gradient += a w_k
+//   store(o)           the value gradient into the slab, behind the point's
+template <bool PR, typename Val>
+__device__ __forceinline__ void rn_bwd_tile(const RnCam& cam, const unsigned long long* __restrict__ off,
+                                            const unsigned long long* __restrict__ keys, const float4* __restrict__ pos,
+                                            const int4* __restrict__ box, const RnPix* __restrict__ pix,
+                                            double* __restrict__ slab, const int S, const bool GP, const bool GR, Val val) {
+  __shared__ double sdx[256], sdy[256], sinv[256], szt[256];
   __shared__ int scut[256];
   const int tile = blockIdx.y * cam.tiles_x + blockIdx.x;
   const unsigned long long base = off[tile];
@@ -522,13 +514,8 @@ __global__ void __launch_bounds__(256) k_rn_bwd_entry(RnCam cam, const unsigned 
     if (i < cam.h && j < cam.w) {
       const size_t px = (size_t)i * cam.w + j;
       const RnPix rec = pix[px];
-      const double g0 = gimg[3 * px], g1 = gimg[3 * px + 1], g2 = gimg[3 * px + 2];
-      if (rec.W > 0.0 && (g0 != 0.0 || g1 != 0.0 || g2 != 0.0)) {
+      if (val.stage(t, px, rec)) {
         cut = rec.cut;
-        sa0[t] = g0 / rec.W;
-        sa1[t] = g1 / rec.W;
-        sa2[t] = g2 / rec.W;
-        if constexpr (GS) sb[t] = (g0 * rec.c0 + g1 * rec.c1 + g2 * rec.c2) / rec.W;
         szt[t] = rec.zt_max;
         double dx, dy, inv_dn;
         rn_ray(cam, i, j, dx, dy, inv_dn);
@@ -545,12 +532,11 @@ __global__ void __launch_bounds__(256) k_rn_bwd_entry(RnCam cam, const unsigned 
     const int id = (int)(unsigned int)keys[base + e];
     const int4 b = box[id];
     const float4 p = pos[id];
-    float4 c = make_float4(0.f, 0.f, 0.f, 0.f);
-    if constexpr (GS) c = col[id];
+    val.entry(id);
     const double X = p.x, Y = p.y, Z = p.z;
     const double zt = (cam.zf - Z) / zspan;
     const double r = PR ? (double)p.w : cam.r;
-    double gx = 0.0, gy = 0.0, gz = 0.0, q0 = 0.0, q1 = 0.0, q2 = 0.0, gr = 0.0;
+    double gx = 0.0, gy = 0.0, gz = 0.0, gr = 0.0;
     const int i0 = max(b.z, ty0), i1 = min(b.w, ty0 + RN_TILE - 1), j0 = max(b.x, tx0), j1 = min(b.y, tx0 + RN_TILE - 1);
     for (int i = i0; i <= i1; ++i)
       for (int j = j0; j <= j1; ++j) {
@@ -561,9 +547,9 @@ __global__ void __launch_bounds__(256) k_rn_bwd_entry(RnCam cam, const unsigned 
         if (!(rho < r)) continue;
         const double ek = exp((zt - szt[t]) / cam.gamma), wk = (1.0 - rho / r) * ek;
         double sk = 0.0;
-        if constexpr (GS) sk = sa0[t] * (double)c.x + sa1[t] * (double)c.y + sa2[t] * (double)c.z - sb[t];
-        if constexpr (GR) gr += sk * ek * rho / (r * r);
-        if constexpr (GP) {
+        if (GP || GR) sk = val.sk(t);
+        if (GR) gr += sk * ek * rho / (r * r);
+        if (GP) {
           if (rho > 0.0) {
             // drho/dP = (P - (P.d^) d^) / rho, d^ = d / |d|
             const double hx = dx * inv_dn, hy = dy * inv_dn, hz = inv_dn;
@@ -575,86 +561,168 @@ __global__ void __launch_bounds__(256) k_rn_bwd_entry(RnCam cam, const unsigned 
           }
           gz -= sk * wk * kz;
         }
-        if constexpr (GC) {
-          q0 += sa0[t] * wk;
-          q1 += sa1[t] * wk;
-          q2 += sa2[t] * wk;
-        }
+        val.add(t, wk);
       }
-    double* o = slab + S * (base + e);
-    if constexpr (GP) {
+    double* o = slab + (size_t)S * (base + e);
+    if (GP) {
       o[0] = gx;
       o[1] = gy;
       o[2] = gz;
     }
-    if constexpr (GC) {
-      o[(GP ? 3 : 0)] = q0;
-      o[(GP ? 3 : 0) + 1] = q1;
-      o[(GP ? 3 : 0) + 2] = q2;
-    }
-    if constexpr (GR) o[S - 1] = gr;
+    val.store(o + (GP ? 3 : 0));
+    if (GR) o[S - 1] = gr;
   }
 }
 
-// Backward, pass 2, for one point: the S-double slab entries of the tiles its box touches (the scatter's order), each found
-// by binary search of the point's key -- unique in its tile's sorted list -- summed into acc.  Culled points (and unstable
-// surfels) get 0.
-template <int S>
-__device__ __forceinline__ void rn_bwd_gather(int i, int tiles_x, const unsigned long long* __restrict__ off,
-                                              const unsigned long long* __restrict__ keys, const float4* __restrict__ pos,
-                                              const int4* __restrict__ box, const double* __restrict__ slab, double (&acc)[S]) {
-  for (int q = 0; q < S; ++q) acc[q] = 0.0;
-  const int4 b = box[i];
-  if (b.x <= b.y) {
-    const unsigned long long key = ((unsigned long long)__float_as_uint(pos[i].z) << 32) | (unsigned int)i;
-    for (int ty = b.z / RN_TILE; ty <= b.w / RN_TILE; ++ty)
-      for (int tx = b.x / RN_TILE; tx <= b.y / RN_TILE; ++tx) {
-        const int t = ty * tiles_x + tx;
-        unsigned long long lo = off[t], hi = off[t + 1];
-        while (lo < hi) {
-          const unsigned long long mid = (lo + hi) >> 1;
-          if (keys[mid] < key) lo = mid + 1; else hi = mid;
-        }
-        if (lo < off[t + 1] && keys[lo] == key)
-          for (int q = 0; q < S; ++q) acc[q] += slab[S * lo + q];
-      }
-  }
-}
+// What a backward computes: the point gradient, the colour (value) gradient, the radius gradient, or any union of them.  A
+// slab entry holds, packed in this order, 3 doubles for the point, 3 (C with channels) for the values, 1 for the radius.
+enum { RN_BWD_POINTS = 1, RN_BWD_COLORS = 2, RN_BWD_RADII = 4 };
 
-// Backward, pass 2 of slm_render_backward (RN_BWD_POINTS): per point, dL/dP -- rn_bwd_gather<3> written out (this
-// form keeps its registers).
-__global__ void __launch_bounds__(256) k_rn_bwd_point(int N, int tiles_x, const unsigned long long* __restrict__ off,
+// pass 1 after a three-channel forward: MODE is a template parameter, so every union of outputs has its own registers and LDS
+// (no b, and no read of the colours, for the colour gradient alone).  RN_BWD_RADII needs PR.
+template <int MODE, bool PR>
+__global__ void __launch_bounds__(256) k_rn_bwd_entry(RnCam cam, const unsigned long long* __restrict__ off,
                                                       const unsigned long long* __restrict__ keys, const float4* __restrict__ pos,
-                                                      const int4* __restrict__ box, const double* __restrict__ slab,
-                                                      double* __restrict__ out) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= N) return;
-  const int4 b = box[i];
-  double gx = 0.0, gy = 0.0, gz = 0.0;
-  if (b.x <= b.y) {
-    const unsigned long long key = ((unsigned long long)__float_as_uint(pos[i].z) << 32) | (unsigned int)i;
-    for (int ty = b.z / RN_TILE; ty <= b.w / RN_TILE; ++ty)
-      for (int tx = b.x / RN_TILE; tx <= b.y / RN_TILE; ++tx) {
-        const int t = ty * tiles_x + tx;
-        unsigned long long lo = off[t], hi = off[t + 1];
-        while (lo < hi) {
-          const unsigned long long mid = (lo + hi) >> 1;
-          if (keys[mid] < key) lo = mid + 1; else hi = mid;
-        }
-        if (lo < off[t + 1] && keys[lo] == key) {
-          gx += slab[3 * lo];
-          gy += slab[3 * lo + 1];
-          gz += slab[3 * lo + 2];
-        }
+                                                      const int4* __restrict__ box, const float4* __restrict__ col,
+                                                      const RnPix* __restrict__ pix, const double* __restrict__ gimg,
+                                                      double* __restrict__ slab) {
+  constexpr bool GP = (MODE & RN_BWD_POINTS) != 0, GC = (MODE & RN_BWD_COLORS) != 0, GR = (MODE & RN_BWD_RADII) != 0;
+  constexpr bool GS = GP || GR;   // s_k is needed: the colour copy and b
+  constexpr int S = (GP ? 3 : 0) + (GC ? 3 : 0) + (GR ? 1 : 0);
+  static_assert(PR || !GR, "the radius gradient belongs to a per-point forward");
+  __shared__ double sa0[256], sa1[256], sa2[256], sb[GS ? 256 : 1];
+  struct Val {
+    const float4* __restrict__ col;
+    const double* __restrict__ gimg;
+    float4 c;
+    double q0, q1, q2;
+    __device__ bool stage(int t, size_t px, const RnPix& rec) {
+      const double g0 = gimg[3 * px], g1 = gimg[3 * px + 1], g2 = gimg[3 * px + 2];
+      if (!(rec.W > 0.0 && (g0 != 0.0 || g1 != 0.0 || g2 != 0.0))) return false;
+      sa0[t] = g0 / rec.W;
+      sa1[t] = g1 / rec.W;
+      sa2[t] = g2 / rec.W;
+      if constexpr (GS) sb[t] = (g0 * rec.c0 + g1 * rec.c1 + g2 * rec.c2) / rec.W;
+      return true;
+    }
+    __device__ void entry(int id) {
+      c = make_float4(0.f, 0.f, 0.f, 0.f);
+      if constexpr (GS) c = col[id];
+      q0 = q1 = q2 = 0.0;
+    }
+    __device__ double sk(int t) const { return sa0[t] * (double)c.x + sa1[t] * (double)c.y + sa2[t] * (double)c.z - sb[t]; }
+    __device__ void add(int t, double wk) {
+      if constexpr (GC) {
+        q0 += sa0[t] * wk;
+        q1 += sa1[t] * wk;
+        q2 += sa2[t] * wk;
       }
-  }
-  out[3 * (size_t)i] = gx;
-  out[3 * (size_t)i + 1] = gy;
-  out[3 * (size_t)i + 2] = gz;
+    }
+    __device__ void store(double* o) const {
+      if constexpr (GC) {
+        o[0] = q0;
+        o[1] = q1;
+        o[2] = q2;
+      }
+    }
+  };
+  rn_bwd_tile<PR>(cam, off, keys, pos, box, pix, slab, S, GP, GR, Val{col, gimg});
 }
 
-// Backward, pass 2 of every MODE but RN_BWD_POINTS alone: per point, the sums of the slab's S doubles -- dL/dP (3,
-// RN_BWD_POINTS), dL/dc (3, RN_BWD_COLORS), dL/dr (1, RN_BWD_RADII), in that order; an output that is NULL is not written.
+// pass 1 after a channels forward.  The channel count is a run-time bound of loops unrolled to SLM_RENDER_MAX_CHANNELS, and
+// what is wanted (RN_BWD_COLORS: here the features) a run-time uniform too: one instantiation per PR instead of MODE x PR x C.
+// Every output is summed in its own registers by the same instructions whatever else is wanted, so it does not depend on the
+// others.  In LDS a_c = g_c / W (C x 256 doubles) and b = sum_c g_c F_c / W;  s_k = sum_c a_c f_kc - b.
+template <bool PR>
+__global__ void __launch_bounds__(256) k_rn_bwd_entry_ch(RnCam cam, int C, int CP, int want,
+                                                         const unsigned long long* __restrict__ off,
+                                                         const unsigned long long* __restrict__ keys,
+                                                         const float4* __restrict__ pos, const int4* __restrict__ box,
+                                                         const float* __restrict__ feat, const RnPix* __restrict__ pix,
+                                                         const double* __restrict__ pixf, const double* __restrict__ gimg,
+                                                         double* __restrict__ slab) {
+  constexpr int MC = SLM_RENDER_MAX_CHANNELS;
+  __shared__ double sb[256], sa[MC][256];
+  const bool GP = (want & RN_BWD_POINTS) != 0, GC = (want & RN_BWD_COLORS) != 0, GR = PR && (want & RN_BWD_RADII) != 0;
+  const int S = (GP ? 3 : 0) + (GC ? C : 0) + (GR ? 1 : 0);
+  struct Val {
+    int C, CP;
+    bool GC;
+    const float* __restrict__ feat;
+    const double* __restrict__ pixf;
+    const double* __restrict__ gimg;
+    float f[MC];
+    double q[MC];
+    __device__ bool stage(int t, size_t px, const RnPix& rec) {
+      double g[MC];
+      bool any = false;
+#pragma unroll
+      for (int c = 0; c < MC; ++c) {
+        g[c] = c < C ? gimg[px * C + c] : 0.0;
+        any = any || g[c] != 0.0;
+      }
+      if (!(rec.W > 0.0 && any)) return false;
+      double b = 0.0;
+#pragma unroll
+      for (int c = 0; c < MC; ++c)
+        if (c < C) {
+          sa[c][t] = g[c] / rec.W;
+          b = fma(g[c], pixf[px * C + c], b);
+        }
+      sb[t] = b / rec.W;
+      return true;
+    }
+    __device__ void entry(int id) {
+      const float4* fr = reinterpret_cast<const float4*>(feat + (size_t)id * CP);
+      const float4 v0 = fr[0], v1 = CP > 4 ? fr[1] : make_float4(0.f, 0.f, 0.f, 0.f);
+      f[0] = v0.x; f[1] = v0.y; f[2] = v0.z; f[3] = v0.w;
+      f[4] = v1.x; f[5] = v1.y; f[6] = v1.z; f[7] = v1.w;
+#pragma unroll
+      for (int c = 0; c < MC; ++c) q[c] = 0.0;
+    }
+    __device__ double sk(int t) const {
+      double s = 0.0;
+#pragma unroll
+      for (int c = 0; c < MC; ++c)
+        if (c < C) s = fma(sa[c][t], (double)f[c], s);
+      return s - sb[t];
+    }
+    __device__ void add(int t, double wk) {
+      if (GC) {
+#pragma unroll
+        for (int c = 0; c < MC; ++c)
+          if (c < C) q[c] = fma(sa[c][t], wk, q[c]);
+      }
+    }
+    __device__ void store(double* o) const {
+      if (GC) {
+#pragma unroll
+        for (int c = 0; c < MC; ++c)
+          if (c < C) o[c] = q[c];
+      }
+    }
+  };
+  rn_bwd_tile<PR>(cam, off, keys, pos, box, pix, slab, S, GP, GR, Val{C, CP, GC, feat, pixf, gimg});
+}
+
+// Backward, pass 2: f(at) for the position `at` of point i's entry in the sorted list of every tile its box touches, in the
+// scatter's tile order.  Nothing for a culled point (or an unstable surfel).
+template <typename F>
+__device__ __forceinline__ void rn_point_entries(int i, int tiles_x, const unsigned long long* __restrict__ off,
+                                                 const unsigned long long* __restrict__ keys, const float4* __restrict__ pos,
+                                                 const int4* __restrict__ box, F f) {
+  const int4 b = box[i];
+  if (b.x > b.y) return;
+  const unsigned long long key = rn_key(pos, i);
+  for (int ty = b.z / RN_TILE; ty <= b.w / RN_TILE; ++ty)
+    for (int tx = b.x / RN_TILE; tx <= b.y / RN_TILE; ++tx) {
+      const unsigned long long at = rn_find(off, keys, ty * tiles_x + tx, key);
+      if (at != RN_ABSENT) f(at);
+    }
+}
+
+// pass 2 after a three-channel forward: per point, the sums of its slab entries' S doubles -- dL/dP (3, RN_BWD_POINTS),
+// dL/dc (3, RN_BWD_COLORS), dL/dr (1, RN_BWD_RADII), in that order; an output that is NULL is not written.
 template <int MODE>
 __global__ void __launch_bounds__(256) k_rn_bwd_point_ex(int N, int tiles_x, const unsigned long long* __restrict__ off,
                                                          const unsigned long long* __restrict__ keys, const float4* __restrict__ pos,
@@ -666,7 +734,10 @@ __global__ void __launch_bounds__(256) k_rn_bwd_point_ex(int N, int tiles_x, con
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= N) return;
   double g[S];
-  rn_bwd_gather<S>(i, tiles_x, off, keys, pos, box, slab, g);
+  for (int q = 0; q < S; ++q) g[q] = 0.0;
+  rn_point_entries(i, tiles_x, off, keys, pos, box, [&](unsigned long long at) {
+    for (int q = 0; q < S; ++q) g[q] += slab[S * at + q];
+  });
   if constexpr ((MODE & RN_BWD_POINTS) != 0) {
     if (out_p)
       for (int q = 0; q < 3; ++q) out_p[3 * (size_t)i + q] = g[q];
@@ -680,135 +751,27 @@ __global__ void __launch_bounds__(256) k_rn_bwd_point_ex(int N, int tiles_x, con
   }
 }
 
-// The two backward passes of a channels forward (slm_render_backward_channels).  The channel count is a run-time bound of
-// loops unrolled to SLM_RENDER_MAX_CHANNELS, and what is wanted (RN_BWD_POINTS | RN_BWD_COLORS, here the features, |
-// RN_BWD_RADII) a run-time uniform too: one instantiation per PR instead of MODE x PR x C.  A slab entry holds, packed in this
-// order, 3 doubles for the point (if wanted), C for the features, 1 for the radius.  Every output is summed in its own
-// registers by the same instructions whatever else is wanted, so it does not depend on the others.
-//   pixel coefficients in LDS: a_c = g_c / W (C x 256 doubles), b = sum_c g_c F_c / W;  s_k = sum_c a_c f_kc - b
-template <bool PR>
-__global__ void __launch_bounds__(256) k_rn_bwd_entry_ch(RnCam cam, int C, int CP, int want,
-                                                         const unsigned long long* __restrict__ off,
-                                                         const unsigned long long* __restrict__ keys,
-                                                         const float4* __restrict__ pos, const int4* __restrict__ box,
-                                                         const float* __restrict__ feat, const RnPix* __restrict__ pix,
-                                                         const double* __restrict__ pixf, const double* __restrict__ gimg,
-                                                         double* __restrict__ slab) {
-  constexpr int MC = SLM_RENDER_MAX_CHANNELS;
-  __shared__ double sdx[256], sdy[256], sinv[256], szt[256], sb[256], sa[MC][256];
-  __shared__ int scut[256];
-  const bool GP = (want & RN_BWD_POINTS) != 0, GC = (want & RN_BWD_COLORS) != 0, GR = PR && (want & RN_BWD_RADII) != 0;
-  const bool GS = GP || GR;
-  const int S = (GP ? 3 : 0) + (GC ? C : 0) + (GR ? 1 : 0), of = GP ? 3 : 0;
-  const int tile = blockIdx.y * cam.tiles_x + blockIdx.x;
-  const unsigned long long base = off[tile];
-  const int n = (int)(off[tile + 1] - base);
-  if (n == 0) return;
-  const int tx0 = blockIdx.x * RN_TILE, ty0 = blockIdx.y * RN_TILE;
-  {
-    const int t = threadIdx.x, j = tx0 + (t & (RN_TILE - 1)), i = ty0 + t / RN_TILE;
-    int cut = -1;
-    if (i < cam.h && j < cam.w) {
-      const size_t px = (size_t)i * cam.w + j;
-      const RnPix rec = pix[px];
-      double g[MC];
-      bool any = false;
-#pragma unroll
-      for (int c = 0; c < MC; ++c) {
-        g[c] = c < C ? gimg[px * C + c] : 0.0;
-        any = any || g[c] != 0.0;
-      }
-      if (rec.W > 0.0 && any) {
-        cut = rec.cut;
-        double b = 0.0;
-#pragma unroll
-        for (int c = 0; c < MC; ++c)
-          if (c < C) {
-            sa[c][t] = g[c] / rec.W;
-            b = fma(g[c], pixf[px * C + c], b);
-          }
-        sb[t] = b / rec.W;
-        szt[t] = rec.zt_max;
-        double dx, dy, inv_dn;
-        rn_ray(cam, i, j, dx, dy, inv_dn);
-        sdx[t] = dx;
-        sdy[t] = dy;
-        sinv[t] = inv_dn;
-      }
-    }
-    scut[t] = cut;
-  }
-  __syncthreads();
-  const double zspan = cam.zf - cam.zn, kz = 1.0 / (cam.gamma * zspan);
-  for (int e = threadIdx.x; e < n; e += 256) {
-    const int id = (int)(unsigned int)keys[base + e];
-    const int4 b = box[id];
-    const float4 p = pos[id];
-    float f[MC];
-    {
-      const float4* fr = reinterpret_cast<const float4*>(feat + (size_t)id * CP);
-      const float4 v0 = fr[0], v1 = CP > 4 ? fr[1] : make_float4(0.f, 0.f, 0.f, 0.f);
-      f[0] = v0.x; f[1] = v0.y; f[2] = v0.z; f[3] = v0.w;
-      f[4] = v1.x; f[5] = v1.y; f[6] = v1.z; f[7] = v1.w;
-    }
-    const double X = p.x, Y = p.y, Z = p.z;
-    const double zt = (cam.zf - Z) / zspan;
-    const double r = PR ? (double)p.w : cam.r;
-    double gx = 0.0, gy = 0.0, gz = 0.0, gr = 0.0, q[MC];
-#pragma unroll
-    for (int c = 0; c < MC; ++c) q[c] = 0.0;
-    const int i0 = max(b.z, ty0), i1 = min(b.w, ty0 + RN_TILE - 1), j0 = max(b.x, tx0), j1 = min(b.y, tx0 + RN_TILE - 1);
-    for (int i = i0; i <= i1; ++i)
-      for (int j = j0; j <= j1; ++j) {
-        const int t = (i - ty0) * RN_TILE + (j - tx0);
-        if (e > scut[t]) continue;
-        const double dx = sdx[t], dy = sdy[t], inv_dn = sinv[t];
-        const double rho = rn_rho(X, Y, Z, dx, dy, inv_dn);
-        if (!(rho < r)) continue;
-        const double ek = exp((zt - szt[t]) / cam.gamma), wk = (1.0 - rho / r) * ek;
-        double sk = 0.0;
-        if (GS) {
-#pragma unroll
-          for (int c = 0; c < MC; ++c)
-            if (c < C) sk = fma(sa[c][t], (double)f[c], sk);
-          sk -= sb[t];
-        }
-        if constexpr (PR) {
-          if (GR) gr += sk * ek * rho / (r * r);
-        }
-        if (GP) {
-          if (rho > 0.0) {
-            const double hx = dx * inv_dn, hy = dy * inv_dn, hz = inv_dn;
-            const double pd = X * hx + Y * hy + Z * hz;
-            const double qq = -sk * ek / (r * rho);
-            gx += qq * (X - pd * hx);
-            gy += qq * (Y - pd * hy);
-            gz += qq * (Z - pd * hz);
-          }
-          gz -= sk * wk * kz;
-        }
-        if (GC) {
-#pragma unroll
-          for (int c = 0; c < MC; ++c)
-            if (c < C) q[c] = fma(sa[c][t], wk, q[c]);
-        }
-      }
-    double* o = slab + (size_t)S * (base + e);
-    if (GP) {
-      o[0] = gx;
-      o[1] = gy;
-      o[2] = gz;
-    }
-    if (GC) {
-#pragma unroll
-      for (int c = 0; c < MC; ++c)
-        if (c < C) o[of + c] = q[c];
-    }
-    if (GR) o[S - 1] = gr;
-  }
+// pass 2 for the point gradient alone (slm_render_backward, every GraphFit render-loss step): k_rn_bwd_point_ex<RN_BWD_POINTS>
+// without the two unused outputs.  Kept beside it because that instantiation, on the same search, has the same 26 VGPRs and no
+// scratch but 152 instructions against the 142 here (it clears its sums as six 32-bit moves per site and tests out_p).
+__global__ void __launch_bounds__(256) k_rn_bwd_point(int N, int tiles_x, const unsigned long long* __restrict__ off,
+                                                      const unsigned long long* __restrict__ keys, const float4* __restrict__ pos,
+                                                      const int4* __restrict__ box, const double* __restrict__ slab,
+                                                      double* __restrict__ out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= N) return;
+  double gx = 0.0, gy = 0.0, gz = 0.0;
+  rn_point_entries(i, tiles_x, off, keys, pos, box, [&](unsigned long long at) {
+    gx += slab[3 * at];
+    gy += slab[3 * at + 1];
+    gz += slab[3 * at + 2];
+  });
+  out[3 * (size_t)i] = gx;
+  out[3 * (size_t)i + 1] = gy;
+  out[3 * (size_t)i + 2] = gz;
 }
 
-// pass 2: per point the sums of its slab entries, in the scatter's tile order (rn_bwd_gather with the run-time layout above)
+// pass 2 after a channels forward: the same sums with the run-time slab layout of k_rn_bwd_entry_ch
 __global__ void __launch_bounds__(256) k_rn_bwd_point_ch(int N, int tiles_x, int C, const unsigned long long* __restrict__ off,
                                                          const unsigned long long* __restrict__ keys,
                                                          const float4* __restrict__ pos, const int4* __restrict__ box,
@@ -821,33 +784,20 @@ __global__ void __launch_bounds__(256) k_rn_bwd_point_ch(int N, int tiles_x, int
   double ap[3] = {0.0, 0.0, 0.0}, ar = 0.0, af[MC];
 #pragma unroll
   for (int c = 0; c < MC; ++c) af[c] = 0.0;
-  const int4 b = box[i];
-  if (b.x <= b.y) {
-    const unsigned long long key = ((unsigned long long)__float_as_uint(pos[i].z) << 32) | (unsigned int)i;
-    for (int ty = b.z / RN_TILE; ty <= b.w / RN_TILE; ++ty)
-      for (int tx = b.x / RN_TILE; tx <= b.y / RN_TILE; ++tx) {
-        const int t = ty * tiles_x + tx;
-        unsigned long long lo = off[t], hi = off[t + 1];
-        while (lo < hi) {
-          const unsigned long long mid = (lo + hi) >> 1;
-          if (keys[mid] < key) lo = mid + 1; else hi = mid;
-        }
-        if (lo < off[t + 1] && keys[lo] == key) {
-          const double* e = slab + (size_t)S * lo;
-          if (out_p) {
-            ap[0] += e[0];
-            ap[1] += e[1];
-            ap[2] += e[2];
-          }
-          if (out_f) {
+  rn_point_entries(i, tiles_x, off, keys, pos, box, [&](unsigned long long at) {
+    const double* e = slab + (size_t)S * at;
+    if (out_p) {
+      ap[0] += e[0];
+      ap[1] += e[1];
+      ap[2] += e[2];
+    }
+    if (out_f) {
 #pragma unroll
-            for (int c = 0; c < MC; ++c)
-              if (c < C) af[c] += e[of + c];
-          }
-          if (out_r) ar += e[S - 1];
-        }
-      }
-  }
+      for (int c = 0; c < MC; ++c)
+        if (c < C) af[c] += e[of + c];
+    }
+    if (out_r) ar += e[S - 1];
+  });
   if (out_p)
     for (int q = 0; q < 3; ++q) out_p[3 * (size_t)i + q] = ap[q];
   if (out_f) {
@@ -898,41 +848,50 @@ bool rn_same_params(const slm_render_params& a, const slm_render_params& b) {
   return rn_same_geometry(a, b) && a.bg[0] == b.bg[0] && a.bg[1] == b.bg[1] && a.bg[2] == b.bg[2];
 }
 
-// the projection of one source, with the parameters' radius or (per_point) the points' own
-template <int SRC>
-void rn_project(dim3 grid, hipStream_t st, int N, const void* pts, GfSlot* gslot, const RnCam& cam, slm_render* r,
-                const float* colors, int cstride, const float* radii, bool per_point) {
-  if (per_point)
-    hipLaunchKernelGGL((k_rn_project<SRC, true>), grid, dim3(256), 0, st, N, pts, gslot, cam, r->pos, r->box, r->cnt, colors,
-                       cstride, r->col, radii);
-  else
-    hipLaunchKernelGGL((k_rn_project<SRC, false>), grid, dim3(256), 0, st, N, pts, gslot, cam, r->pos, r->box, r->cnt, colors,
-                       cstride, r->col, radii);
-}
-
-// the tile walk of a channels forward: CP = 4 or 8 accumulators, with the parameters' radius or the points' own
-template <int CP>
-void rn_tile_ch(dim3 grid, hipStream_t st, const RnCam& cam, const RnBg& bg, int C, slm_render* r, bool per_point, float* image,
-                int32_t* front_id, int32_t* hit_count) {
-  if (per_point)
-    hipLaunchKernelGGL((k_rn_tile_ch<true, CP>), grid, dim3(256), 0, st, cam, bg, C, r->off, r->keys, r->tmp, r->pos, r->box,
-                       r->feat, image, front_id, hit_count, r->pix, r->pixf);
-  else
-    hipLaunchKernelGGL((k_rn_tile_ch<false, CP>), grid, dim3(256), 0, st, cam, bg, C, r->off, r->keys, r->tmp, r->pos, r->box,
-                       r->feat, image, front_id, hit_count, r->pix, r->pixf);
-}
-
 // the padded row width of the context's feature copy
 int rn_padded(int C) { return C <= 4 ? 4 : 8; }
 
-// per_point: radii (N) float32 device holds one radius per point (by surfel row for RN_SRC_GF); else p->radius serves all.
-// ch = 0: the three colour channels and p->bg.  ch = 1..8 (slm_render_points_channels, which has checked them): `colors`
-// holds ch features per row and bg_host ch floats.
-int render_common(slm_render* r, const slm_render_params* p, int N, int src, const void* pts, GfSlot* gslot,
-                  bool per_point, const float* radii, const float* colors, int cstride, float* image, int32_t* front_id,
-                  int32_t* hit_count, void* stream, const char* who, int ch = 0, const float* bg_host = nullptr) {
-  std::string w(who);
-  if (!r || !p || !image) return fail(SLM_ERR_INVALID, w + ": null argument");
+// Every instantiation of a kernel family, indexed by the run-time choices it was compiled for, so that each family is launched
+// from one place.  A MODE with RN_BWD_RADII exists only with PR (the entry points refuse grad_radii after a one-radius
+// forward): those slots of the PR = false row stay null and are never instantiated.
+constexpr decltype(&k_rn_project<0, false>) kProject[3][2] = {   // [SRC][PR]
+    {k_rn_project<RN_SRC_F32, false>, k_rn_project<RN_SRC_F32, true>},
+    {k_rn_project<RN_SRC_F64, false>, k_rn_project<RN_SRC_F64, true>},
+    {k_rn_project<RN_SRC_GF, false>, k_rn_project<RN_SRC_GF, true>}};
+constexpr decltype(&k_rn_tile<false>) kTile[2] = {k_rn_tile<false>, k_rn_tile<true>};   // [PR]
+constexpr decltype(&k_rn_tile_ch<false, 4>) kTileCh[2][2] = {                            // [CP == 8][PR]
+    {k_rn_tile_ch<false, 4>, k_rn_tile_ch<true, 4>}, {k_rn_tile_ch<false, 8>, k_rn_tile_ch<true, 8>}};
+constexpr decltype(&k_rn_bwd_entry<1, false>) kBwdEntry[2][8] = {                        // [PR][MODE]
+    {nullptr, k_rn_bwd_entry<1, false>, k_rn_bwd_entry<2, false>, k_rn_bwd_entry<3, false>},
+    {nullptr, k_rn_bwd_entry<1, true>, k_rn_bwd_entry<2, true>, k_rn_bwd_entry<3, true>, k_rn_bwd_entry<4, true>,
+     k_rn_bwd_entry<5, true>, k_rn_bwd_entry<6, true>, k_rn_bwd_entry<7, true>}};
+constexpr decltype(&k_rn_bwd_point_ex<2>) kBwdPoint[8] = {                               // [MODE]; 1 is k_rn_bwd_point
+    nullptr, nullptr, k_rn_bwd_point_ex<2>, k_rn_bwd_point_ex<3>, k_rn_bwd_point_ex<4>,
+    k_rn_bwd_point_ex<5>, k_rn_bwd_point_ex<6>, k_rn_bwd_point_ex<7>};
+constexpr decltype(&k_rn_bwd_entry_ch<false>) kBwdEntryCh[2] = {k_rn_bwd_entry_ch<false>, k_rn_bwd_entry_ch<true>};   // [PR]
+
+// one forward, as its entry point describes it
+struct RnForward {
+  const char* who;       // the entry point's name, for its refusals
+  int src;               // RN_SRC_F32 / F64: N rows of `pts`;  RN_SRC_GF: the N surfels of `gslot`
+  const void* pts;
+  GfSlot* gslot;
+  int N;
+  bool per_point;        // radii (N) float32 device holds one radius per point (by surfel row for RN_SRC_GF); else p->radius
+  const float* radii;
+  const float* values;   // the colours (ch = 0) or the features, rows of `stride` floats
+  int stride;
+  int ch;                // 0: the three colour channels and p->bg;  1..8: that many channels and the host floats `bg`
+  const float* bg;
+  float* image;
+  int32_t *front_id, *hit_count;
+  void* stream;
+};
+
+int render_common(slm_render* r, const slm_render_params* p, const RnForward& f) {
+  const std::string w(f.who);
+  const int N = f.N, ch = f.ch;
+  if (!r || !p || !f.image) return fail(SLM_ERR_INVALID, w + ": null argument");
   if (p->width < 1 || p->height < 1 || p->width > r->W || p->height > r->H)
     return fail(SLM_ERR_INVALID, w + ": image size outside the context's H x W");
   if (p->n_track < 1 || p->n_track > SLM_RENDER_MAX_TRACK) return fail(SLM_ERR_INVALID, w + ": n_track must be 1..64");
@@ -941,20 +900,22 @@ int render_common(slm_render* r, const slm_render_params* p, int N, int src, con
       !std::isfinite(p->radius) || !std::isfinite(p->bg_eps))
     return fail(SLM_ERR_INVALID, w + ": bad camera or blend parameters");
   if (N < 0 || N > r->cap) return fail(SLM_ERR_INVALID, w + ": more points than the context holds");
-  if (ch && N > 0 && !pts) return fail(SLM_ERR_INVALID, w + ": null points");
-  if (!ch && N > 0 && ((src != RN_SRC_GF && !pts) || !colors || cstride < 3))
+  if (ch && N > 0 && !f.pts) return fail(SLM_ERR_INVALID, w + ": null points");
+  if (!ch && N > 0 && ((f.src != RN_SRC_GF && !f.pts) || !f.values || f.stride < 3))
     return fail(SLM_ERR_INVALID, w + ": null points / colours or color_stride < 3");
   r->has_fwd = 0;
-  hipStream_t st = (hipStream_t)stream;
+  hipStream_t st = (hipStream_t)f.stream;
   const RnCam cam = rn_cam(p);
   const int tiles_y = (p->height + RN_TILE - 1) / RN_TILE, tiles = cam.tiles_x * tiles_y;
   const int CP = rn_padded(ch);
+  const float* colors = f.values;
+  int cstride = f.stride;
   RnBg bg{};
   if (ch) {   // the wider buffers, first needed here: the feature copy at its widest, the pixel record at this width
     const size_t rows = (size_t)r->cap + 1, pixels = (size_t)r->H * r->W;
     HIPCHK(grow(r->feat, r->cap_feat, rows * CP, rows * SLM_RENDER_MAX_CHANNELS));
     HIPCHK(grow(r->pixf, r->cap_pixf, pixels * ch, pixels * ch));
-    for (int c = 0; c < ch; ++c) bg.v[c] = bg_host[c];
+    for (int c = 0; c < ch; ++c) bg.v[c] = f.bg[c];
     if (N > 0) {
       const size_t cells = (size_t)N * CP;
       hipLaunchKernelGGL(k_rn_feat, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, N, ch, CP, colors, cstride,
@@ -964,15 +925,10 @@ int render_common(slm_render* r, const slm_render_params* p, int N, int src, con
     }
   }
   HIPCHK(hipMemsetAsync(r->cnt, 0, sizeof(unsigned int) * tiles, st));
-  const dim3 gp((N + 255) / 256);
-  if (N > 0) {
-    if (src == RN_SRC_F32)
-      rn_project<RN_SRC_F32>(gp, st, N, pts, gslot, cam, r, colors, cstride, radii, per_point);
-    else if (src == RN_SRC_F64)
-      rn_project<RN_SRC_F64>(gp, st, N, pts, gslot, cam, r, colors, cstride, radii, per_point);
-    else
-      rn_project<RN_SRC_GF>(gp, st, N, pts, gslot, cam, r, colors, cstride, radii, per_point);
-  }
+  const dim3 gp((N + 255) / 256), gt(cam.tiles_x, tiles_y);
+  if (N > 0)
+    hipLaunchKernelGGL(kProject[f.src][f.per_point], gp, dim3(256), 0, st, N, f.pts, f.gslot, cam, r->pos, r->box, r->cnt,
+                       colors, cstride, r->col, f.radii);
   hipLaunchKernelGGL(k_rn_scan, dim3(1), dim3(1024), 0, st, tiles, r->cnt, r->off, r->cur);
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(r->h_total, r->off + tiles, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
@@ -984,19 +940,15 @@ int render_common(slm_render* r, const slm_render_params* p, int N, int src, con
   HIPCHK(grow(r->tmp, r->cap_tmp, total, want));
   if (total > 0)
     hipLaunchKernelGGL(k_rn_scatter, gp, dim3(256), 0, st, N, cam.tiles_x, r->pos, r->box, r->cur, r->keys);
-  if (ch && CP == 4)
-    rn_tile_ch<4>(dim3(cam.tiles_x, tiles_y), st, cam, bg, ch, r, per_point, image, front_id, hit_count);
-  else if (ch)
-    rn_tile_ch<8>(dim3(cam.tiles_x, tiles_y), st, cam, bg, ch, r, per_point, image, front_id, hit_count);
-  else if (per_point)
-    hipLaunchKernelGGL(k_rn_tile<true>, dim3(cam.tiles_x, tiles_y), dim3(256), 0, st, cam, r->off, r->keys, r->tmp, r->pos,
-                       r->box, colors, cstride, image, front_id, hit_count, r->pix);
+  if (ch)
+    hipLaunchKernelGGL(kTileCh[CP == 8][f.per_point], gt, dim3(256), 0, st, cam, bg, ch, r->off, r->keys, r->tmp, r->pos,
+                       r->box, r->feat, f.image, f.front_id, f.hit_count, r->pix, r->pixf);
   else
-    hipLaunchKernelGGL(k_rn_tile<false>, dim3(cam.tiles_x, tiles_y), dim3(256), 0, st, cam, r->off, r->keys, r->tmp, r->pos,
-                       r->box, colors, cstride, image, front_id, hit_count, r->pix);
+    hipLaunchKernelGGL(kTile[f.per_point], gt, dim3(256), 0, st, cam, r->off, r->keys, r->tmp, r->pos, r->box, colors,
+                       cstride, f.image, f.front_id, f.hit_count, r->pix);
   HIPCHK(hipGetLastError());
   r->last = *p;
-  r->per_point_last = per_point;
+  r->per_point_last = f.per_point;
   r->ch_last = ch;
   r->n_last = N;
   r->total_last = total;
@@ -1004,52 +956,53 @@ int render_common(slm_render* r, const slm_render_params* p, int N, int src, con
   return SLM_OK;
 }
 
-// the two backward launches of one MODE for a forward with (PR) or without per-point radii
-template <int MODE, bool PR>
-void rn_bwd_launch(slm_render* r, const RnCam& cam, int tiles_y, const double* grad_image, double* grad_points,
-                   double* grad_colors, double* grad_radii, hipStream_t st) {
-  const int N = r->n_last;
-  const dim3 gt(cam.tiles_x, tiles_y), gp((N + 255) / 256), b(256);
-  if (r->total_last > 0)
-    hipLaunchKernelGGL((k_rn_bwd_entry<MODE, PR>), gt, b, 0, st, cam, r->off, r->keys, r->pos, r->box, r->col, r->pix,
-                       grad_image, r->slab);
-  if constexpr (MODE == RN_BWD_POINTS)
-    hipLaunchKernelGGL(k_rn_bwd_point, gp, b, 0, st, N, cam.tiles_x, r->off, r->keys, r->pos, r->box, r->slab, grad_points);
-  else
-    hipLaunchKernelGGL(k_rn_bwd_point_ex<MODE>, gp, b, 0, st, N, cam.tiles_x, r->off, r->keys, r->pos, r->box, r->slab,
-                       grad_points, grad_colors, grad_radii);
+// The refusals that every backward entry point `who` shares, in their order.  C = 0: the entry follows a three-channel
+// forward, else a channels forward of C channels (which does not read bg, so bg is not compared).  grad_radii: null where the
+// entry has none.
+int rn_bwd_check(const char* who, int C, bool channels, const slm_render* r, const slm_render_params* p,
+                 const double* grad_image, const double* grad_radii) {
+  const std::string w(who);
+  if (!r || !p || !grad_image) return fail(SLM_ERR_INVALID, w + ": null argument");
+  if (channels && (C < 1 || C > SLM_RENDER_MAX_CHANNELS)) return fail(SLM_ERR_INVALID, w + ": channels must be 1..8");
+  if (!r->has_fwd) return fail(SLM_ERR_INVALID, w + ": no completed forward on this context");
+  if (!channels && r->ch_last)
+    return fail(SLM_ERR_INVALID, w + ": the last forward had N-channel features: use slm_render_backward_channels");
+  if (channels && !r->ch_last) return fail(SLM_ERR_INVALID, w + ": the last forward was not slm_render_points_channels");
+  if (channels && r->ch_last != C) return fail(SLM_ERR_INVALID, w + ": channels differ from those of the last forward");
+  if (!(channels ? rn_same_geometry(*p, r->last) : rn_same_params(*p, r->last)))
+    return fail(SLM_ERR_INVALID, w + ": parameters differ from those of the last forward");
+  if (grad_radii && !r->per_point_last) return fail(SLM_ERR_INVALID, w + ": grad_radii after a forward with one radius");
+  return SLM_OK;
 }
 
-// one MODE for the forward that r holds.  A MODE with RN_BWD_RADII exists only with PR (the caller has refused grad_radii after
-// a one-radius forward); this is a template so that the branch not taken for such a MODE is discarded, not instantiated.
-template <int MODE>
-void rn_bwd_mode(slm_render* r, const RnCam& cam, int tiles_y, const double* grad_image, double* grad_points,
-                 double* grad_colors, double* grad_radii, hipStream_t st) {
-  if (r->per_point_last)
-    rn_bwd_launch<MODE, true>(r, cam, tiles_y, grad_image, grad_points, grad_colors, grad_radii, st);
-  else if constexpr ((MODE & RN_BWD_RADII) == 0)
-    rn_bwd_launch<MODE, false>(r, cam, tiles_y, grad_image, grad_points, grad_colors, grad_radii, st);
-}
-
-// the backward of the last forward on r (checked by the caller; N > 0, one output at least; grad_radii only after a
-// per-point forward): 3 slab doubles per tile-list entry for the points, 3 for the colours, 1 for the radii
-int rn_backward(slm_render* r, const slm_render_params* p, const double* grad_image, double* grad_points,
-                double* grad_colors, double* grad_radii, hipStream_t st) {
+// The backward of the last forward on r (checked by the caller; N > 0, one output at least; grad_radii only after a per-point
+// forward), C = 0 after a three-channel forward.  The slab holds per tile-list entry 3 doubles for the points, 3 (or C) for
+// the values and 1 for the radii, those that are wanted, with the head-room of the tile lists.
+int rn_backward(slm_render* r, const slm_render_params* p, int C, const double* grad_image, double* grad_points,
+                double* grad_values, double* grad_radii, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
   const RnCam cam = rn_cam(p);
-  const int tiles_y = (p->height + RN_TILE - 1) / RN_TILE;
-  const int mode = (grad_points ? RN_BWD_POINTS : 0) | (grad_colors ? RN_BWD_COLORS : 0) | (grad_radii ? RN_BWD_RADII : 0);
-  const size_t S = (grad_points ? 3 : 0) + (grad_colors ? 3 : 0) + (grad_radii ? 1 : 0);
+  const int N = r->n_last, pr = r->per_point_last;
+  const int want = (grad_points ? RN_BWD_POINTS : 0) | (grad_values ? RN_BWD_COLORS : 0) | (grad_radii ? RN_BWD_RADII : 0);
+  const size_t S = (grad_points ? 3 : 0) + (grad_values ? (C ? C : 3) : 0) + (grad_radii ? 1 : 0);
   const unsigned long long total = r->total_last;
   HIPCHK(grow(r->slab, r->cap_slab, S * total, S * ((size_t)total + total / 4 + 1024)));
-  switch (mode) {
-    case 1: rn_bwd_mode<1>(r, cam, tiles_y, grad_image, grad_points, grad_colors, grad_radii, st); break;
-    case 2: rn_bwd_mode<2>(r, cam, tiles_y, grad_image, grad_points, grad_colors, grad_radii, st); break;
-    case 3: rn_bwd_mode<3>(r, cam, tiles_y, grad_image, grad_points, grad_colors, grad_radii, st); break;
-    case 4: rn_bwd_mode<4>(r, cam, tiles_y, grad_image, grad_points, grad_colors, grad_radii, st); break;
-    case 5: rn_bwd_mode<5>(r, cam, tiles_y, grad_image, grad_points, grad_colors, grad_radii, st); break;
-    case 6: rn_bwd_mode<6>(r, cam, tiles_y, grad_image, grad_points, grad_colors, grad_radii, st); break;
-    case 7: rn_bwd_mode<7>(r, cam, tiles_y, grad_image, grad_points, grad_colors, grad_radii, st); break;
-    default: break;
+  const dim3 gt(cam.tiles_x, (p->height + RN_TILE - 1) / RN_TILE), gp((N + 255) / 256), b(256);
+  if (C) {
+    if (total > 0)
+      hipLaunchKernelGGL(kBwdEntryCh[pr], gt, b, 0, st, cam, C, rn_padded(C), want, r->off, r->keys, r->pos, r->box, r->feat,
+                         r->pix, r->pixf, grad_image, r->slab);
+    hipLaunchKernelGGL(k_rn_bwd_point_ch, gp, b, 0, st, N, cam.tiles_x, C, r->off, r->keys, r->pos, r->box, r->slab,
+                       grad_points, grad_values, grad_radii);
+  } else {
+    if (total > 0)
+      hipLaunchKernelGGL(kBwdEntry[pr][want], gt, b, 0, st, cam, r->off, r->keys, r->pos, r->box, r->col, r->pix, grad_image,
+                         r->slab);
+    if (want == RN_BWD_POINTS)
+      hipLaunchKernelGGL(k_rn_bwd_point, gp, b, 0, st, N, cam.tiles_x, r->off, r->keys, r->pos, r->box, r->slab, grad_points);
+    else
+      hipLaunchKernelGGL(kBwdPoint[want], gp, b, 0, st, N, cam.tiles_x, r->off, r->keys, r->pos, r->box, r->slab, grad_points,
+                         grad_values, grad_radii);
   }
   HIPCHK(hipGetLastError());
   return SLM_OK;
@@ -1089,8 +1042,8 @@ int slm_render_destroy(slm_render* r) {
 int slm_render_points(slm_render* r, const slm_render_params* p, int32_t N, const void* points, const float* colors,
                       int32_t color_stride, float* image, int32_t* front_id, int32_t* hit_count, void* stream) {
   if (!p) return fail(SLM_ERR_INVALID, "slm_render_points: null argument");
-  return render_common(r, p, N, p->points_f64 ? RN_SRC_F64 : RN_SRC_F32, points, nullptr, false, nullptr, colors,
-                       color_stride, image, front_id, hit_count, stream, "slm_render_points");
+  return render_common(r, p, {"slm_render_points", p->points_f64 ? RN_SRC_F64 : RN_SRC_F32, points, nullptr, N, false, nullptr,
+                              colors, color_stride, 0, nullptr, image, front_id, hit_count, stream});
 }
 
 int slm_render_points_radii(slm_render* r, const slm_render_params* p, int32_t N, const void* points, const float* radii,
@@ -1098,8 +1051,8 @@ int slm_render_points_radii(slm_render* r, const slm_render_params* p, int32_t N
                             int32_t* hit_count, void* stream) {
   if (!r || !p || !image) return fail(SLM_ERR_INVALID, "slm_render_points_radii: null argument");
   if (N > 0 && !radii) return fail(SLM_ERR_INVALID, "slm_render_points_radii: null radii");
-  return render_common(r, p, N, p->points_f64 ? RN_SRC_F64 : RN_SRC_F32, points, nullptr, true, radii, colors, color_stride,
-                       image, front_id, hit_count, stream, "slm_render_points_radii");
+  return render_common(r, p, {"slm_render_points_radii", p->points_f64 ? RN_SRC_F64 : RN_SRC_F32, points, nullptr, N, true,
+                              radii, colors, color_stride, 0, nullptr, image, front_id, hit_count, stream});
 }
 
 int slm_gf_render(slm_gf* g, int32_t slot, slm_render* r, const slm_render_params* p, const float* colors,
@@ -1108,8 +1061,8 @@ int slm_gf_render(slm_gf* g, int32_t slot, slm_render* r, const slm_render_param
   int32_t n = 0;
   const int rc = gf_render_slot(g, slot, &dev, &n);
   if (rc != SLM_OK) return rc;
-  return render_common(r, p, n, RN_SRC_GF, nullptr, dev, false, nullptr, colors, color_stride, image, front_id, hit_count,
-                       stream, "slm_gf_render");
+  return render_common(r, p, {"slm_gf_render", RN_SRC_GF, nullptr, dev, n, false, nullptr, colors, color_stride, 0, nullptr,
+                              image, front_id, hit_count, stream});
 }
 
 int slm_gf_render_radii(slm_gf* g, int32_t slot, slm_render* r, const slm_render_params* p, const float* radii,
@@ -1121,48 +1074,8 @@ int slm_gf_render_radii(slm_gf* g, int32_t slot, slm_render* r, const slm_render
   int32_t n = 0;
   const int rc = gf_render_slot(g, slot, &dev, &n, "slm_gf_render_radii");
   if (rc != SLM_OK) return rc;
-  return render_common(r, p, n, RN_SRC_GF, nullptr, dev, true, radii, colors, color_stride, image, front_id, hit_count,
-                       stream, "slm_gf_render_radii");
-}
-
-int slm_render_backward(slm_render* r, const slm_render_params* p, const double* grad_image, double* grad_points,
-                        void* stream) {
-  if (!r || !p || !grad_image) return fail(SLM_ERR_INVALID, "slm_render_backward: null argument");
-  if (!r->has_fwd) return fail(SLM_ERR_INVALID, "slm_render_backward: no completed forward on this context");
-  if (r->ch_last) return fail(SLM_ERR_INVALID, "slm_render_backward: the last forward had N-channel features: use slm_render_backward_channels");
-  if (!rn_same_params(*p, r->last))
-    return fail(SLM_ERR_INVALID, "slm_render_backward: parameters differ from those of the last forward");
-  const int N = r->n_last;
-  if (N == 0) return SLM_OK;
-  if (!grad_points) return fail(SLM_ERR_INVALID, "slm_render_backward: null grad_points");
-  return rn_backward(r, p, grad_image, grad_points, nullptr, nullptr, (hipStream_t)stream);
-}
-
-int slm_render_backward_ex(slm_render* r, const slm_render_params* p, const double* grad_image, double* grad_points,
-                           double* grad_colors, void* stream) {
-  if (!r || !p || !grad_image) return fail(SLM_ERR_INVALID, "slm_render_backward_ex: null argument");
-  if (!r->has_fwd) return fail(SLM_ERR_INVALID, "slm_render_backward_ex: no completed forward on this context");
-  if (r->ch_last) return fail(SLM_ERR_INVALID, "slm_render_backward_ex: the last forward had N-channel features: use slm_render_backward_channels");
-  if (!rn_same_params(*p, r->last))
-    return fail(SLM_ERR_INVALID, "slm_render_backward_ex: parameters differ from those of the last forward");
-  if (r->n_last == 0) return SLM_OK;
-  if (!grad_points && !grad_colors) return fail(SLM_ERR_INVALID, "slm_render_backward_ex: null grad_points and grad_colors");
-  return rn_backward(r, p, grad_image, grad_points, grad_colors, nullptr, (hipStream_t)stream);
-}
-
-int slm_render_backward_radii(slm_render* r, const slm_render_params* p, const double* grad_image, double* grad_points,
-                              double* grad_colors, double* grad_radii, void* stream) {
-  if (!r || !p || !grad_image) return fail(SLM_ERR_INVALID, "slm_render_backward_radii: null argument");
-  if (!r->has_fwd) return fail(SLM_ERR_INVALID, "slm_render_backward_radii: no completed forward on this context");
-  if (r->ch_last) return fail(SLM_ERR_INVALID, "slm_render_backward_radii: the last forward had N-channel features: use slm_render_backward_channels");
-  if (!rn_same_params(*p, r->last))
-    return fail(SLM_ERR_INVALID, "slm_render_backward_radii: parameters differ from those of the last forward");
-  if (grad_radii && !r->per_point_last)
-    return fail(SLM_ERR_INVALID, "slm_render_backward_radii: grad_radii after a forward with one radius");
-  if (r->n_last == 0) return SLM_OK;
-  if (!grad_points && !grad_colors && !grad_radii)
-    return fail(SLM_ERR_INVALID, "slm_render_backward_radii: null grad_points, grad_colors and grad_radii");
-  return rn_backward(r, p, grad_image, grad_points, grad_colors, grad_radii, (hipStream_t)stream);
+  return render_common(r, p, {"slm_gf_render_radii", RN_SRC_GF, nullptr, dev, n, true, radii, colors, color_stride, 0, nullptr,
+                              image, front_id, hit_count, stream});
 }
 
 int slm_render_points_channels(slm_render* r, const slm_render_params* p, int32_t N, const void* points, const float* radii,
@@ -1172,48 +1085,42 @@ int slm_render_points_channels(slm_render* r, const slm_render_params* p, int32_
   if (C < 1 || C > SLM_RENDER_MAX_CHANNELS) return fail(SLM_ERR_INVALID, "slm_render_points_channels: channels must be 1..8");
   if (feature_stride < C) return fail(SLM_ERR_INVALID, "slm_render_points_channels: feature_stride < channels");
   if (N > 0 && !features) return fail(SLM_ERR_INVALID, "slm_render_points_channels: null features");
-  return render_common(r, p, N, p->points_f64 ? RN_SRC_F64 : RN_SRC_F32, points, nullptr, radii != nullptr, radii, features,
-                       feature_stride, image, front_id, hit_count, stream, "slm_render_points_channels", C, bg);
+  return render_common(r, p, {"slm_render_points_channels", p->points_f64 ? RN_SRC_F64 : RN_SRC_F32, points, nullptr, N,
+                              radii != nullptr, radii, features, feature_stride, C, bg, image, front_id, hit_count, stream});
+}
+
+int slm_render_backward(slm_render* r, const slm_render_params* p, const double* grad_image, double* grad_points,
+                        void* stream) {
+  if (const int rc = rn_bwd_check("slm_render_backward", 0, false, r, p, grad_image, nullptr)) return rc;
+  if (r->n_last == 0) return SLM_OK;
+  if (!grad_points) return fail(SLM_ERR_INVALID, "slm_render_backward: null grad_points");
+  return rn_backward(r, p, 0, grad_image, grad_points, nullptr, nullptr, stream);
+}
+
+int slm_render_backward_ex(slm_render* r, const slm_render_params* p, const double* grad_image, double* grad_points,
+                           double* grad_colors, void* stream) {
+  if (const int rc = rn_bwd_check("slm_render_backward_ex", 0, false, r, p, grad_image, nullptr)) return rc;
+  if (r->n_last == 0) return SLM_OK;
+  if (!grad_points && !grad_colors) return fail(SLM_ERR_INVALID, "slm_render_backward_ex: null grad_points and grad_colors");
+  return rn_backward(r, p, 0, grad_image, grad_points, grad_colors, nullptr, stream);
+}
+
+int slm_render_backward_radii(slm_render* r, const slm_render_params* p, const double* grad_image, double* grad_points,
+                              double* grad_colors, double* grad_radii, void* stream) {
+  if (const int rc = rn_bwd_check("slm_render_backward_radii", 0, false, r, p, grad_image, grad_radii)) return rc;
+  if (r->n_last == 0) return SLM_OK;
+  if (!grad_points && !grad_colors && !grad_radii)
+    return fail(SLM_ERR_INVALID, "slm_render_backward_radii: null grad_points, grad_colors and grad_radii");
+  return rn_backward(r, p, 0, grad_image, grad_points, grad_colors, grad_radii, stream);
 }
 
 int slm_render_backward_channels(slm_render* r, const slm_render_params* p, int32_t C, const double* grad_image,
                                  double* grad_points, double* grad_features, double* grad_radii, void* stream) {
-  if (!r || !p || !grad_image) return fail(SLM_ERR_INVALID, "slm_render_backward_channels: null argument");
-  if (C < 1 || C > SLM_RENDER_MAX_CHANNELS)
-    return fail(SLM_ERR_INVALID, "slm_render_backward_channels: channels must be 1..8");
-  if (!r->has_fwd) return fail(SLM_ERR_INVALID, "slm_render_backward_channels: no completed forward on this context");
-  if (!r->ch_last)
-    return fail(SLM_ERR_INVALID, "slm_render_backward_channels: the last forward was not slm_render_points_channels");
-  if (r->ch_last != C)
-    return fail(SLM_ERR_INVALID, "slm_render_backward_channels: channels differ from those of the last forward");
-  if (!rn_same_geometry(*p, r->last))
-    return fail(SLM_ERR_INVALID, "slm_render_backward_channels: parameters differ from those of the last forward");
-  if (grad_radii && !r->per_point_last)
-    return fail(SLM_ERR_INVALID, "slm_render_backward_channels: grad_radii after a forward with one radius");
-  const int N = r->n_last;
-  if (N == 0) return SLM_OK;
+  if (const int rc = rn_bwd_check("slm_render_backward_channels", C, true, r, p, grad_image, grad_radii)) return rc;
+  if (r->n_last == 0) return SLM_OK;
   if (!grad_points && !grad_features && !grad_radii)
     return fail(SLM_ERR_INVALID, "slm_render_backward_channels: null grad_points, grad_features and grad_radii");
-  hipStream_t st = (hipStream_t)stream;
-  const RnCam cam = rn_cam(p);
-  const int tiles_y = (p->height + RN_TILE - 1) / RN_TILE;
-  const int want = (grad_points ? RN_BWD_POINTS : 0) | (grad_features ? RN_BWD_COLORS : 0) | (grad_radii ? RN_BWD_RADII : 0);
-  const size_t S = (grad_points ? 3 : 0) + (grad_features ? C : 0) + (grad_radii ? 1 : 0);
-  const unsigned long long total = r->total_last;
-  HIPCHK(grow(r->slab, r->cap_slab, S * total, S * ((size_t)total + total / 4 + 1024)));
-  const dim3 gt(cam.tiles_x, tiles_y), gp((N + 255) / 256), b(256);
-  if (total > 0) {
-    if (r->per_point_last)
-      hipLaunchKernelGGL(k_rn_bwd_entry_ch<true>, gt, b, 0, st, cam, C, rn_padded(C), want, r->off, r->keys, r->pos, r->box,
-                         r->feat, r->pix, r->pixf, grad_image, r->slab);
-    else
-      hipLaunchKernelGGL(k_rn_bwd_entry_ch<false>, gt, b, 0, st, cam, C, rn_padded(C), want, r->off, r->keys, r->pos, r->box,
-                         r->feat, r->pix, r->pixf, grad_image, r->slab);
-  }
-  hipLaunchKernelGGL(k_rn_bwd_point_ch, gp, b, 0, st, N, cam.tiles_x, C, r->off, r->keys, r->pos, r->box, r->slab, grad_points,
-                     grad_features, grad_radii);
-  HIPCHK(hipGetLastError());
-  return SLM_OK;
+  return rn_backward(r, p, C, grad_image, grad_points, grad_features, grad_radii, stream);
 }
 
 }  // extern "C"

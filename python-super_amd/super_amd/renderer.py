@@ -139,44 +139,9 @@ def _check_no_grad(*ts):
                                "gradient is render_backward); pass tensors that do not require grad")
 
 
-def render_points(ctx, params, points, colors, with_info=False, radii=None):
-    """Render (N,3) ``points`` (float32 or float64) with (N,3) ``colors``: (h,w,3) float32 on the device, and with
-    ``with_info`` also the (h,w) int32 front-most row (-1: nothing hit) and hit count (<= n_track).  ``radii`` (N,), read
-    as float32: one radius per point instead of ``params.radius`` (``slm_render_points_radii``)."""
-    _check_no_grad(points, colors, radii)
-    return _render(ctx, params, points, colors, with_info, radii)
-
-
-def _render(ctx, params, points, colors, with_info=False, radii=None):
-    dev = points.device
-    n = int(points.shape[0])
-    if points.dim() != 2 or points.shape[1] != 3:
-        raise ValueError(f"points must be (N,3), got {tuple(points.shape)}")
-    pts = points.detach()
-    if pts.dtype != torch.float64:
-        pts = pts.float()
-    pts = pts.contiguous()
-    params.points_f64 = int(pts.dtype == torch.float64)
-    col, stride = _colors_arg(colors, n, dev)
-    rad = None if radii is None else _radii_arg(radii, n, dev)
-    ctx.reserve(n)
-    img = torch.empty((params.height, params.width, 3), dtype=torch.float32, device=dev)
-    fid = cnt = None
-    if with_info:
-        fid = torch.empty((params.height, params.width), dtype=torch.int32, device=dev)
-        cnt = torch.empty_like(fid)
-    ptr = lambda t: _dev_ptr(t) if t is not None and t.numel() else None
-    ctx.last_n = 0
-    ctx.serial += 1
-    if rad is None:
-        _lib.check(ctx.lib.slm_render_points(ctx.h, C.byref(params), n, ptr(pts), ptr(col), stride, _dev_ptr(img),
-                                             ptr(fid), ptr(cnt), _stream_ptr(dev)), "slm_render_points")
-    else:
-        _lib.check(ctx.lib.slm_render_points_radii(ctx.h, C.byref(params), n, ptr(pts), ptr(rad), ptr(col), stride,
-                                                   _dev_ptr(img), ptr(fid), ptr(cnt), _stream_ptr(dev)),
-                   "slm_render_points_radii")
-    ctx.last_n = n
-    return (img, fid, cnt) if with_info else img
+def _ptr(t):
+    """the device pointer of a tensor; None for None and for an empty tensor"""
+    return _dev_ptr(t) if t is not None and t.numel() else None
 
 
 def _features_arg(features, n, device):
@@ -198,16 +163,10 @@ def _bg_arg(bg, c):
     return (C.c_float * c)(*b.tolist())
 
 
-def render_channels(ctx, params, points, features, bg=None, with_info=False, radii=None):
-    """Render (N,3) ``points`` with (N,C) ``features``, 1 <= C <= 8: (h,w,C) float32 on the device, every channel the
-    blend of ``render_points`` for its column (``slm_render_points_channels``), in one geometry pass.  ``bg``: C
-    background values (default zeros; ``params.bg`` is not read).  ``with_info`` and ``radii`` as ``render_points``.
-    Forward only: inputs that require grad are refused."""
-    _check_no_grad(points, features, radii)
-    return _render_channels(ctx, params, points, features, bg, with_info, radii)
-
-
-def _render_channels(ctx, params, points, features, bg=None, with_info=False, radii=None):
+def _forward(ctx, params, points, values, with_info=False, radii=None, bg=None, channels=False):
+    """One render on ``ctx``, no check for grad: ``values`` are (N,>=3) colours (``slm_render_points``, with ``radii``
+    ``slm_render_points_radii``) or, with ``channels``, (N,C) features with the background ``bg``
+    (``slm_render_points_channels``).  Bumps ``ctx.serial``; ``ctx.last_n`` is N once the render has completed."""
     dev = points.device
     if points.dim() != 2 or points.shape[1] != 3:
         raise ValueError(f"points must be (N,3), got {tuple(points.shape)}")
@@ -217,9 +176,9 @@ def _render_channels(ctx, params, points, features, bg=None, with_info=False, ra
         pts = pts.float()
     pts = pts.contiguous()
     params.points_f64 = int(pts.dtype == torch.float64)
-    feat, stride = _features_arg(features, n, dev)
-    c = int(feat.shape[1])
-    bgv = _bg_arg(bg, c)
+    val, stride = (_features_arg if channels else _colors_arg)(values, n, dev)
+    c = int(val.shape[1]) if channels else 3
+    bgv = _bg_arg(bg, c) if channels else None
     rad = None if radii is None else _radii_arg(radii, n, dev)
     ctx.reserve(n)
     img = torch.empty((params.height, params.width, c), dtype=torch.float32, device=dev)
@@ -227,13 +186,59 @@ def _render_channels(ctx, params, points, features, bg=None, with_info=False, ra
     if with_info:
         fid = torch.empty((params.height, params.width), dtype=torch.int32, device=dev)
         cnt = torch.empty_like(fid)
-    ptr = lambda t: _dev_ptr(t) if t is not None and t.numel() else None
     ctx.last_n = 0
     ctx.serial += 1
-    _lib.check(ctx.lib.slm_render_points_channels(ctx.h, C.byref(params), n, ptr(pts), ptr(rad), c, ptr(feat), stride, bgv, _dev_ptr(img), ptr(fid), ptr(cnt),
-                                                  _stream_ptr(dev)), "slm_render_points_channels")
+    head, tail = (ctx.h, C.byref(params), n, _ptr(pts)), (_dev_ptr(img), _ptr(fid), _ptr(cnt), _stream_ptr(dev))
+    if channels:
+        _lib.check(ctx.lib.slm_render_points_channels(*head, _ptr(rad), c, _ptr(val), stride, bgv, *tail),
+                   "slm_render_points_channels")
+    elif rad is None:
+        _lib.check(ctx.lib.slm_render_points(*head, _ptr(val), stride, *tail), "slm_render_points")
+    else:
+        _lib.check(ctx.lib.slm_render_points_radii(*head, _ptr(rad), _ptr(val), stride, *tail), "slm_render_points_radii")
     ctx.last_n = n
     return (img, fid, cnt) if with_info else img
+
+
+def _backward(ctx, params, grad_image, points, values, radii, entry=None):
+    """(dL/dpoints (N,3), dL/dvalues (N,3) or (N,C), dL/dradii (N,)) of the last render on ``ctx``, float64, None where
+    not asked: always three entries.  ``entry``: the C entry point; by default ``slm_render_backward_radii`` when the
+    radii's gradient is asked and ``slm_render_backward_ex`` otherwise."""
+    entry = entry or ("slm_render_backward_radii" if radii else "slm_render_backward_ex")
+    channels = entry == "slm_render_backward_channels"
+    g = torch.as_tensor(grad_image).detach()
+    dev = g.device
+    if channels and (g.dim() != 3 or tuple(g.shape[:2]) != (params.height, params.width)):
+        raise ValueError(f"grad_image must be ({params.height},{params.width},C), got {tuple(g.shape)}")
+    if not channels and tuple(g.shape) != (params.height, params.width, 3):
+        raise ValueError(f"grad_image must be ({params.height},{params.width},3), got {tuple(g.shape)}")
+    c = int(g.shape[2])
+    g = g.to(dtype=torch.float64).contiguous()
+    n = ctx.last_n
+    gp = torch.empty((n, 3), dtype=torch.float64, device=dev) if points else None
+    gv = torch.empty((n, c), dtype=torch.float64, device=dev) if values else None
+    gr = torch.empty((n,), dtype=torch.float64, device=dev) if radii else None
+    outs = {"slm_render_backward": (gp,), "slm_render_backward_ex": (gp, gv)}.get(entry, (gp, gv, gr))
+    _lib.check(getattr(ctx.lib, entry)(ctx.h, C.byref(params), *((c,) if channels else ()), _dev_ptr(g), *map(_ptr, outs),
+                                       _stream_ptr(dev)), entry)
+    return gp, gv, gr
+
+
+def render_points(ctx, params, points, colors, with_info=False, radii=None):
+    """Render (N,3) ``points`` (float32 or float64) with (N,3) ``colors``: (h,w,3) float32 on the device, and with
+    ``with_info`` also the (h,w) int32 front-most row (-1: nothing hit) and hit count (<= n_track).  ``radii`` (N,), read
+    as float32: one radius per point instead of ``params.radius`` (``slm_render_points_radii``)."""
+    _check_no_grad(points, colors, radii)
+    return _forward(ctx, params, points, colors, with_info, radii)
+
+
+def render_channels(ctx, params, points, features, bg=None, with_info=False, radii=None):
+    """Render (N,3) ``points`` with (N,C) ``features``, 1 <= C <= 8: (h,w,C) float32 on the device, every channel the
+    blend of ``render_points`` for its column (``slm_render_points_channels``), in one geometry pass.  ``bg``: C
+    background values (default zeros; ``params.bg`` is not read).  ``with_info`` and ``radii`` as ``render_points``.
+    Forward only: inputs that require grad are refused."""
+    _check_no_grad(points, features, radii)
+    return _forward(ctx, params, points, features, with_info, radii, bg, channels=True)
 
 
 def render_backward_channels(ctx, params, grad_image, points=True, features=True, radii=False):
@@ -242,20 +247,7 @@ def render_backward_channels(ctx, params, grad_image, points=True, features=True
     ``grad_image``'s last dimension.  ``radii`` needs a render with per-point radii."""
     if not (points or features or radii):
         raise ValueError("render_backward_channels: request the points' gradient, the features' or the radii's")
-    g = torch.as_tensor(grad_image).detach()
-    dev = g.device
-    if g.dim() != 3 or tuple(g.shape[:2]) != (params.height, params.width):
-        raise ValueError(f"grad_image must be ({params.height},{params.width},C), got {tuple(g.shape)}")
-    c = int(g.shape[2])
-    g = g.to(dtype=torch.float64).contiguous()
-    n = ctx.last_n
-    gp = torch.empty((n, 3), dtype=torch.float64, device=dev) if points else None
-    gf = torch.empty((n, c), dtype=torch.float64, device=dev) if features else None
-    gr = torch.empty((n,), dtype=torch.float64, device=dev) if radii else None
-    ptr = lambda t: _dev_ptr(t) if t is not None and t.numel() else None
-    _lib.check(ctx.lib.slm_render_backward_channels(ctx.h, C.byref(params), c, _dev_ptr(g), ptr(gp), ptr(gf), ptr(gr),
-                                                    _stream_ptr(dev)), "slm_render_backward_channels")
-    return gp, gf, gr
+    return _backward(ctx, params, grad_image, points, features, radii, "slm_render_backward_channels")
 
 
 def render_backward(ctx, params, grad_image):
@@ -263,36 +255,7 @@ def render_backward(ctx, params, grad_image):
     then by surfel row, 0 on unstable rows) for ``grad_image`` = dL/dimage (h,w,3).  ``params`` must be the render's.
     The exact derivative of the blend (include/super_lm.h ``slm_render_backward``): hit sets and the n_track cut are
     the forward's, positions the float32-rounded ones; not Pulsar's own backward (unpinned)."""
-    g = torch.as_tensor(grad_image).detach()
-    dev = g.device
-    if tuple(g.shape) != (params.height, params.width, 3):
-        raise ValueError(f"grad_image must be ({params.height},{params.width},3), got {tuple(g.shape)}")
-    g = g.to(dtype=torch.float64).contiguous()
-    out = torch.empty((ctx.last_n, 3), dtype=torch.float64, device=dev)
-    _lib.check(ctx.lib.slm_render_backward(ctx.h, C.byref(params), _dev_ptr(g), _dev_ptr(out) if out.numel() else None,
-                                           _stream_ptr(dev)), "slm_render_backward")
-    return out
-
-
-def _render_backward_all(ctx, params, grad_image, points, colors, radii):
-    """(dL/dpoints (N,3) or None, dL/dcolors (N,3) or None, dL/dradii (N,) or None), float64, of the last render on
-    ``ctx``: always three entries.  ``radii`` needs a last render with per-point radii."""
-    g = torch.as_tensor(grad_image).detach()
-    dev = g.device
-    if tuple(g.shape) != (params.height, params.width, 3):
-        raise ValueError(f"grad_image must be ({params.height},{params.width},3), got {tuple(g.shape)}")
-    g = g.to(dtype=torch.float64).contiguous()
-    gp = torch.empty((ctx.last_n, 3), dtype=torch.float64, device=dev) if points else None
-    gc = torch.empty((ctx.last_n, 3), dtype=torch.float64, device=dev) if colors else None
-    gr = torch.empty((ctx.last_n,), dtype=torch.float64, device=dev) if radii else None
-    ptr = lambda t: _dev_ptr(t) if t is not None and t.numel() else None
-    if radii:
-        _lib.check(ctx.lib.slm_render_backward_radii(ctx.h, C.byref(params), _dev_ptr(g), ptr(gp), ptr(gc), ptr(gr),
-                                                     _stream_ptr(dev)), "slm_render_backward_radii")
-    else:
-        _lib.check(ctx.lib.slm_render_backward_ex(ctx.h, C.byref(params), _dev_ptr(g), ptr(gp), ptr(gc),
-                                                  _stream_ptr(dev)), "slm_render_backward_ex")
-    return gp, gc, gr
+    return _backward(ctx, params, grad_image, True, False, False, "slm_render_backward")[0]
 
 
 def render_backward_ex(ctx, params, grad_image, points=True, colors=True, radii=False):
@@ -304,47 +267,49 @@ def render_backward_ex(ctx, params, grad_image, points=True, colors=True, radii=
     The length of the result follows the caller's own ``radii`` argument, never the data."""
     if not (points or colors or radii):
         raise ValueError("render_backward_ex: request the points' gradient, the colours' or both")
-    out = _render_backward_all(ctx, params, grad_image, points, colors, radii)
+    out = _backward(ctx, params, grad_image, points, colors, radii)
     return out if radii else out[:2]
 
 
 class _Render(torch.autograd.Function):
-    """The render as an autograd node.  It keeps its inputs (``save_for_backward``: autograd's version check catches an
-    in-place change after the forward), a copy of its parameters, its context object and the context's serial after
-    its forward.  If another render has run on that context since -- any render, on the same handle or on one
-    ``reserve`` recreated -- the backward re-renders the saved inputs into it first."""
+    """The render as an autograd node, of colours or (``channels``) of features.  It keeps its inputs
+    (``save_for_backward``: autograd's version check catches an in-place change after the forward), a copy of its
+    parameters, its context object and the context's serial after its forward.  If another render has run on that
+    context since -- any render, on the same handle or on one ``reserve`` recreated -- the backward re-renders the saved
+    inputs into it first."""
 
     @staticmethod
-    def forward(fctx, rctx, params, points, colors, radii):
-        img = _render(rctx, params, points, colors, radii=radii)
+    def forward(fctx, rctx, params, points, values, radii, bg, channels):
+        img = _forward(rctx, params, points, values, radii=radii, bg=bg, channels=channels)
         fctx.rctx, fctx.params, fctx.serial = rctx, SlmRenderParams.from_buffer_copy(params), rctx.serial
-        fctx.per_point = radii is not None
-        fctx.save_for_backward(points, colors, *(() if radii is None else (radii,)))
+        fctx.per_point, fctx.bg, fctx.channels = radii is not None, bg, channels
+        fctx.save_for_backward(points, values, *(() if radii is None else (radii,)))
         return img
 
     @staticmethod
     @once_differentiable
     def backward(fctx, grad_image):
-        points, colors = fctx.saved_tensors[:2]
+        points, values = fctx.saved_tensors[:2]
         radii = fctx.saved_tensors[2] if fctx.per_point else None
-        want_p, want_c = fctx.needs_input_grad[2], fctx.needs_input_grad[3]
+        want_p, want_v = fctx.needs_input_grad[2], fctx.needs_input_grad[3]
         want_r = fctx.per_point and fctx.needs_input_grad[4]
-        if not (want_p or want_c or want_r):
-            return None, None, None, None, None
+        if not (want_p or want_v or want_r):
+            return (None,) * 7
         rctx, params = fctx.rctx, fctx.params
         if rctx.serial != fctx.serial:
-            _render(rctx, params, points, colors, radii=radii)
+            _forward(rctx, params, points, values, radii=radii, bg=fctx.bg, channels=fctx.channels)
             fctx.serial = rctx.serial
-        gp, gc, gr = _render_backward_all(rctx, params, grad_image, want_p, want_c, want_r)
+        gp, gv, gr = _backward(rctx, params, grad_image, want_p, want_v, want_r,
+                               "slm_render_backward_channels" if fctx.channels else None)
         if gp is not None:
             gp = gp.to(device=points.device, dtype=points.dtype)
-        if gc is not None:
-            full = torch.zeros(colors.shape, dtype=colors.dtype, device=colors.device)
-            full[:, :3] = gc
-            gc = full
+        if gv is not None:          # colours may have more than three columns: those beyond get 0
+            full = torch.zeros(values.shape, dtype=values.dtype, device=values.device)
+            full[:, :gv.shape[1]] = gv
+            gv = full
         if gr is not None:
             gr = gr.to(device=radii.device, dtype=radii.dtype)
-        return None, None, gp, gc, gr
+        return None, None, gp, gv, gr, None, None
 
 
 def render_differentiable(ctx, params, points, colors, radii=None):
@@ -357,41 +322,7 @@ def render_differentiable(ctx, params, points, colors, radii=None):
         raise ValueError(f"points must be (N,3), got {tuple(points.shape)}")
     if radii is not None and (radii.dim() != 1 or radii.shape[0] != points.shape[0]):
         raise ValueError(f"radii must be (N,) with N = {points.shape[0]}, got {tuple(radii.shape)}")
-    return _Render.apply(ctx, params, points, colors, radii)
-
-
-class _RenderChannels(torch.autograd.Function):
-    """``_Render`` for N-channel features: the same saved inputs and the same serial / recompute rule."""
-
-    @staticmethod
-    def forward(fctx, rctx, params, points, features, bg, radii):
-        img = _render_channels(rctx, params, points, features, bg, radii=radii)
-        fctx.rctx, fctx.params, fctx.serial = rctx, SlmRenderParams.from_buffer_copy(params), rctx.serial
-        fctx.per_point, fctx.bg = radii is not None, bg
-        fctx.save_for_backward(points, features, *(() if radii is None else (radii,)))
-        return img
-
-    @staticmethod
-    @once_differentiable
-    def backward(fctx, grad_image):
-        points, features = fctx.saved_tensors[:2]
-        radii = fctx.saved_tensors[2] if fctx.per_point else None
-        want_p, want_f = fctx.needs_input_grad[2], fctx.needs_input_grad[3]
-        want_r = fctx.per_point and fctx.needs_input_grad[5]
-        if not (want_p or want_f or want_r):
-            return None, None, None, None, None, None
-        rctx, params = fctx.rctx, fctx.params
-        if rctx.serial != fctx.serial:
-            _render_channels(rctx, params, points, features, fctx.bg, radii=radii)
-            fctx.serial = rctx.serial
-        gp, gf, gr = render_backward_channels(rctx, params, grad_image, want_p, want_f, want_r)
-        if gp is not None:
-            gp = gp.to(device=points.device, dtype=points.dtype)
-        if gf is not None:
-            gf = gf.to(device=features.device, dtype=features.dtype)
-        if gr is not None:
-            gr = gr.to(device=radii.device, dtype=radii.dtype)
-        return None, None, gp, gf, None, gr
+    return _Render.apply(ctx, params, points, colors, radii, None, False)
 
 
 def render_channels_differentiable(ctx, params, points, features, bg=None, radii=None):
@@ -409,7 +340,7 @@ def render_channels_differentiable(ctx, params, points, features, bg=None, radii
         raise ValueError(f"radii must be (N,) with N = {n}, got {tuple(radii.shape)}")
     if torch.is_tensor(bg):
         bg = bg.detach().float().cpu()
-    return _RenderChannels.apply(ctx, params, points, features, bg, radii)
+    return _Render.apply(ctx, params, points, features, radii, bg, True)
 
 
 def _ssim_args(img_hwc, target_chw):
@@ -489,50 +420,41 @@ class Pulsar:
             self._ctx = RenderContext(H, W)
         return self._ctx
 
+    def _render(self, inputs, points, values, view_scale, rad, bg, with_info, channels):
+        """colours or features, in the graph or plain (see the class)"""
+        rad, radii = _split_rad(rad, int(points.shape[0]))
+        params = lambda: render_params(inputs["K"], self.height, self.width, view_scale, rad,
+                                       *(() if channels else (bg,)))
+        if self.differentiable and torch.is_grad_enabled():
+            for name, t in (("bg" if channels else "bg_col", bg), ("rad", rad)):
+                if torch.is_tensor(t) and t.requires_grad:
+                    raise RuntimeError(f"super_amd.renderer.Pulsar: {name} is a constant of the render (no gradient); "
+                                       f"pass a {name} that does not require grad")
+            if any(torch.is_tensor(t) and t.requires_grad for t in (points, values, radii)):
+                if with_info:
+                    raise ValueError("super_amd.renderer.Pulsar: with_info is not available for a render in the graph")
+                if channels:
+                    return render_channels_differentiable(self.context(view_scale), params(), points, values, bg, radii)
+                return render_differentiable(self.context(view_scale), params(), points, values, radii)
+        if self.differentiable:        # not in the graph: the plain forward of the detached inputs
+            points, values = points.detach(), values.detach()
+            radii = None if radii is None else radii.detach()
+        with torch.no_grad():
+            if channels:
+                return render_channels(self.context(view_scale), params(), points, values, bg, with_info, radii)
+            return render_points(self.context(view_scale), params(), points, values, with_info, radii)
+
     def render(self, inputs, data, colors=None, view_scale=1.0, rad=0.01, bg_col=torch.tensor([0.0, 0.0, 0.0]),
                with_info=False):
         if colors is None:
             colors = data.colors
-        points = data.points
-        rad, radii = _split_rad(rad, int(points.shape[0]))
-        if self.differentiable and torch.is_grad_enabled():
-            for name, t in (("bg_col", bg_col), ("rad", rad)):
-                if torch.is_tensor(t) and t.requires_grad:
-                    raise RuntimeError(f"super_amd.renderer.Pulsar: {name} is a constant of the render (no gradient); "
-                                       f"pass a {name} that does not require grad")
-            if any(torch.is_tensor(t) and t.requires_grad for t in (points, colors, radii)):
-                if with_info:
-                    raise ValueError("super_amd.renderer.Pulsar: with_info is not available for a render in the graph")
-                params = render_params(inputs["K"], self.height, self.width, view_scale, rad, bg_col)
-                return render_differentiable(self.context(view_scale), params, points, colors, radii)
-        if self.differentiable:        # not in the graph: the plain forward of the detached inputs
-            points, colors = points.detach(), colors.detach()
-            radii = None if radii is None else radii.detach()
-        with torch.no_grad():
-            params = render_params(inputs["K"], self.height, self.width, view_scale, rad, bg_col)
-            return render_points(self.context(view_scale), params, points, colors, with_info, radii)
+        return self._render(inputs, data.points, colors, view_scale, rad, bg_col, with_info, False)
 
     def render_channels(self, inputs, data, features, view_scale=1.0, rad=0.01, bg=None, with_info=False):
         """``render`` for (N,C) ``features``, 1 <= C <= 8: the (h,w,C) float32 image of ``data.points``, every channel
         blended like a colour channel, in one geometry pass.  ``rad`` as for ``render``; ``bg``: C values, default
         zeros.  In the graph (``render_channels_differentiable``) under the conditions of ``render``."""
-        points = data.points
-        rad, radii = _split_rad(rad, int(points.shape[0]))
-        params = render_params(inputs["K"], self.height, self.width, view_scale, rad)
-        if self.differentiable and torch.is_grad_enabled():
-            for name, t in (("bg", bg), ("rad", rad)):
-                if torch.is_tensor(t) and t.requires_grad:
-                    raise RuntimeError(f"super_amd.renderer.Pulsar: {name} is a constant of the render (no gradient); "
-                                       f"pass a {name} that does not require grad")
-            if any(torch.is_tensor(t) and t.requires_grad for t in (points, features, radii)):
-                if with_info:
-                    raise ValueError("super_amd.renderer.Pulsar: with_info is not available for a render in the graph")
-                return render_channels_differentiable(self.context(view_scale), params, points, features, bg, radii)
-        if self.differentiable:        # not in the graph: the plain forward of the detached inputs
-            points, features = points.detach(), features.detach()
-            radii = None if radii is None else radii.detach()
-        with torch.no_grad():
-            return render_channels(self.context(view_scale), params, points, features, bg, with_info, radii)
+        return self._render(inputs, data.points, features, view_scale, rad, bg, with_info, True)
 
     def forward(self, inputs, data, colors=None, view_scale=1.0, rad=0.01, bg_col=torch.tensor([0.0, 0.0, 0.0])):
         return self.render(inputs, data, colors, view_scale, rad, bg_col)
