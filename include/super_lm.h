@@ -767,6 +767,37 @@ int slm_render_backward_channels(slm_render* r, const slm_render_params* p, int3
  * is read, not copied.  Synchronises `stream`. */
 int slm_gf_bind_point_grad(slm_gf* g, int32_t slot, const double* grad_device, void* stream);
 
+/* The render loss as a term of the run: after slm_gf_bind_frame, binds to the slot the render of its deformed stable surfels
+ * on `r` (slm_gf_render; radii != NULL: slm_gf_render_radii, (N) float32 device by surfel row), the SSIM loss of that render
+ * against target_chw with `weight` (slm_render_ssim_loss) and its point gradient (slm_render_backward).  Every later
+ * evaluation of the slot -- slm_gf_eval_losses, slm_gf_loss_grad, each iteration of slm_gf_run for every slot of the batch
+ * that has the term -- enqueues the three in front of its losses and adds the gradient like a bound point gradient.  Those
+ * calls stay enqueue-only: no synchronisation, read-back or allocation.
+ *   The tile lists cannot be sized from a read-back then, so their capacity is fixed here: one render of the slot's current
+ * state through slm_gf_render's path (one synchronisation) gives the total T0, the context's lists and slab are grown for
+ * L = T0 + T0 / 4 + 1024 entries, and L is the entry limit of every render of the term.  A device-side guard compares each
+ * render's total with L.  Within L the image, the per-pixel records and the point gradient are bitwise those of slm_gf_render
+ * + slm_render_backward on the same state.  Over L the render is EMPTY -- no tile-list entry is written or read, the image is
+ * the background, the point gradient 0 -- and the context's status record counts it: read slm_gf_render_loss_status after the
+ * run and bind again with a larger entry_limit.  entry_limit > 0 sets L to exactly that value (the buffers hold at least the
+ * sizing render's head-room as well, so a limit below the need only empties renders).
+ *   The slot owns the image, its gradient, the point gradient and the loss; colors (rows of color_stride >= 3 floats, by
+ * surfel row), radii and target_chw ((3,height,width) float32 device) are read, not copied, and `r` must outlive the binding.
+ * r == NULL clears the term; slm_gf_bind_frame clears it too.  Refused: a slot with a point gradient bound
+ * (slm_gf_bind_point_grad, which in turn refuses a slot with the term), a context bound to another slot of `g`, sharded
+ * surfels, height or width < 6, and whatever slm_gf_render refuses.  Afterwards slm_render_backward* on `r` refuse until the
+ * next forward through an existing entry point.  Synchronises `stream`. */
+int slm_gf_bind_render_loss(slm_gf* g, int32_t slot, slm_render* r, const slm_render_params* p,
+                            const float* radii /* NULL: p->radius */, const float* colors, int32_t color_stride,
+                            const float* target_chw, double weight, int64_t entry_limit /* 0: from a sizing render */,
+                            void* stream);
+/* out_host: {weighted loss, kept pixel count} of the term's last evaluation (0, 0 before the first), the renders over the
+ * entry limit and the largest tile-list total since the bind (the sizing render included).  Synchronises `stream`. */
+int slm_gf_render_loss_status(slm_gf* g, int32_t slot, double out_host[4], void* stream);
+/* Copies the render (height,width,3) float32 and the point gradient (N,3) float64 of the term's last evaluation to device
+ * buffers (either may be NULL); after the bind and before an evaluation: the sizing render and zeros.  Does not synchronise. */
+int slm_gf_render_loss_read(slm_gf* g, int32_t slot, float* image_device, double* grad_points_device, void* stream);
+
 /* ===================================================================================
  * "Next" row f3: ED-graph construction at frame 0
  *   slm_graph_init  <- init_graph + DirectDeformGraph (grid_mesh)   super/graph_encoder.py:11-67,128-195

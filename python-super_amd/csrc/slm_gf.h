@@ -194,3 +194,38 @@ __device__ __forceinline__ d3 gf_skin_pos(const GfSlotDev& s, int i) {
 // slm_gf_render (slm_render.hip): the device descriptor of bound slot `slot` (its current deform_verts) and its
 // surfel count; SLM_OK or an error status with the text set.
 int gf_render_slot(slm_gf* g, int32_t slot, GfSlot** dev, int32_t* n_surfels, const char* who = "slm_gf_render");
+
+// ---- the render loss as a term of the run (slm_gf_bind_render_loss, slm_gf.hip) ----------------------------------------------
+// What a slot with the term holds: the caller's context, inputs and parameters, the entry limit of the tile lists fixed at the
+// bind, and the buffers the slot owns (grow-only, kept across binds).  ctx == null: no term.
+struct GfRenderTerm {
+  slm_render* ctx = nullptr;
+  slm_render_params p{};
+  const float* radii = nullptr;    // (N) float32 by surfel row, or null: p.radius
+  const float* colors = nullptr;
+  int cstride = 0;
+  const float* target = nullptr;   // (3,h,w) float32
+  double weight = 0.0;
+  unsigned long long limit = 0;
+  float* image = nullptr;          // (h,w,3) the render of the last evaluation
+  double* gimg = nullptr;          // (h,w,3) dL/dimage
+  double* pgrad = nullptr;         // (N,3) dL/dP by surfel row: what k_gf_data<K, true> reads
+  double* loss = nullptr;          // [weighted loss, kept pixels] of the last evaluation
+  double* scratch = nullptr;       // k_ssim_*'s
+  size_t cap_image = 0, cap_gimg = 0, cap_pgrad = 0, cap_loss = 0, cap_scratch = 0;
+};
+
+// slm_render.hip: the guarded, enqueue-only renderer behind the term (see there)
+int rn_gf_check(const char* who, const slm_render* r, const slm_render_params* p, int N, const float* colors, int cstride);
+int rn_gf_size(const char* who, slm_render* r, const slm_render_params* p, GfSlot* gslot, int N, const float* radii,
+               const float* colors, int cstride, float* image, int64_t entry_limit, unsigned long long* limit_out,
+               void* stream);
+void rn_gf_forward(slm_render* r, const slm_render_params* p, GfSlot* gslot, int N, const float* radii, const float* colors,
+                   int cstride, float* image, unsigned long long limit, hipStream_t st);
+void rn_gf_backward(slm_render* r, const slm_render_params* p, int N, bool per_point, const double* grad_image,
+                    double* grad_points, hipStream_t st);
+hipError_t rn_gf_status(const slm_render* r, unsigned long long out_host[2], hipStream_t st);
+// slm_ssim.hip: slm_render_ssim_loss's launches on the caller's scratch
+size_t ssim_scratch_doubles(int h, int w, bool with_grad);
+void ssim_enqueue(int h, int w, const float* image_hwc, const float* target_chw, double weight, double* loss_out,
+                  double* grad_image, double* scratch, hipStream_t st);

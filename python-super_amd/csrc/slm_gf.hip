@@ -11,6 +11,7 @@
 //   face         w_f sum_tri (area(V) - area0)^2,  area = 1/2 sqrt(|e1 x e2|^2 + 1e-13)
 // Gradient of the global row is divided by J before the step (deform_mesh.py:326).
 // Local rows: summed per workgroup in an LDS table, then one f64 atomic per entry and touched node; the global row is reduced per block first.
+#include <cmath>
 #include <string>
 #include <vector>
 
@@ -735,7 +736,32 @@ struct slm_gf {
   int rank = 0, world = 1;   // surfel sharding of every slot (slm_gf_set_shard)
   const double** pgrad = nullptr;             // (max_frames) device: slm_gf_bind_point_grad's buffer per slot, or null
   std::vector<const double*> pgrad_host;      // the same on the host: selects the EXTRA launch
+  std::vector<GfRenderTerm> rterm;            // per slot: the render loss of slm_gf_bind_render_loss (its pgrad is the slot's)
 };
+
+// The render loss of the slots [first, first + n) that have it, in front of an evaluation: the guarded forward of the slot's
+// current deform_verts, the SSIM loss with its image gradient, the guarded backward into the buffer k_gf_data<K, true> reads.
+// Launches only: the buffers and the lists' entry limit were fixed by slm_gf_bind_render_loss.
+static void gf_enqueue_render(slm_gf* g, int first, int n, hipStream_t st) {
+  for (int k = first; k < first + n; ++k) {
+    const GfRenderTerm& t = g->rterm[k];
+    if (!t.ctx) continue;
+    const int N = g->host[k].f.base.N;
+    rn_gf_forward(t.ctx, &t.p, g->dev + k, N, t.radii, t.colors, t.cstride, t.image, t.limit, st);
+    ssim_enqueue(t.p.height, t.p.width, t.image, t.target, t.weight, t.loss, t.gimg, t.scratch, st);
+    if (N > 0) rn_gf_backward(t.ctx, &t.p, N, t.radii != nullptr, t.gimg, t.pgrad, st);
+  }
+}
+
+// takes the term off the slot (the buffers stay for the next bind); the slot's point gradient goes with it
+static int gf_clear_render(slm_gf* g, int slot, hipStream_t st) {
+  if (!g->rterm[slot].ctx) return SLM_OK;
+  g->rterm[slot].ctx = nullptr;
+  g->pgrad_host[slot] = nullptr;
+  HIPCHK(hipMemcpyAsync(g->pgrad + slot, &g->pgrad_host[slot], sizeof(const double*), hipMemcpyHostToDevice, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return SLM_OK;
+}
 
 // pass 1: zero the gradient / terms, then the morphing term's per-surfel pass (sum, count)
 static void gf_enqueue_morph(slm_gf* g, GfSlot* slots, int n, int maxN, hipStream_t st) {
@@ -810,6 +836,7 @@ int slm_gf_create(const slm_gf_config* cfg, slm_gf** out) {
   g->cap.assign(cfg->max_frames, 0);
   g->sem.assign(cfg->max_frames, SemScratch());
   g->pgrad_host.assign(cfg->max_frames, nullptr);
+  g->rterm.assign(cfg->max_frames, GfRenderTerm{});
   hipError_t e = hipMalloc((void**)&g->dev, sizeof(GfSlot) * cfg->max_frames);
   if (e == hipSuccess) e = hipMemset(g->dev, 0, sizeof(GfSlot) * cfg->max_frames);
   if (e == hipSuccess) e = hipMalloc((void**)&g->knn_bad, sizeof(int));
@@ -829,6 +856,9 @@ int slm_gf_destroy(slm_gf* g) {
     if (s.dv) (void)hipFree(s.dv);   // dv | grad | m1 | m2 | terms are one allocation
   }
   for (SemScratch& sc : g->sem) sem_free(sc);
+  for (GfRenderTerm& t : g->rterm)
+    for (void* q : {(void*)t.image, (void*)t.gimg, (void*)t.pgrad, (void*)t.loss, (void*)t.scratch})
+      if (q) (void)hipFree(q);
   if (g->dev) (void)hipFree(g->dev);
   if (g->knn_bad) (void)hipFree(g->knn_bad);
   if (g->pgrad) (void)hipFree(g->pgrad);
@@ -861,8 +891,9 @@ int slm_gf_bind_frame(slm_gf* g, int32_t slot, const slm_gf_frame* fr, void* str
   s.f = *fr;
   s.bound = 1;
   s.step = 0;
-  s.sem_bound = 0;   // semantic inputs, the flow and a point gradient belong to the frame: bind them again
+  s.sem_bound = 0;   // semantic inputs, the flow, a point gradient and the render loss belong to the frame: bind them again
   s.flow = nullptr;
+  g->rterm[slot].ctx = nullptr;
   g->pgrad_host[slot] = nullptr;
   HIPCHK(hipMemcpyAsync(g->pgrad + slot, &g->pgrad_host[slot], sizeof(const double*), hipMemcpyHostToDevice, st));
   s.shard_lo = (int32_t)((int64_t)f.N * g->rank / g->world);
@@ -940,10 +971,104 @@ int slm_gf_bind_point_grad(slm_gf* g, int32_t slot, const double* grad, void* st
   if (!g) return fail(SLM_ERR_INVALID, "slm_gf_bind_point_grad: null argument");
   if (slot < 0 || slot >= (int)g->host.size()) return fail(SLM_ERR_INVALID, "slm_gf_bind_point_grad: bad slot");
   if (!g->host[slot].bound) return fail(SLM_ERR_UNBOUND, "slm_gf_bind_point_grad: slm_gf_bind_frame first");
+  if (g->rterm[slot].ctx)
+    return fail(SLM_ERR_INVALID, "slm_gf_bind_point_grad: the render loss is bound to the slot (slm_gf_bind_render_loss), "
+                                    "which owns its point gradient: clear it first");
   hipStream_t st = (hipStream_t)stream;
   g->pgrad_host[slot] = grad;
   HIPCHK(hipMemcpyAsync(g->pgrad + slot, &g->pgrad_host[slot], sizeof(const double*), hipMemcpyHostToDevice, st));
   HIPCHK(hipStreamSynchronize(st));
+  return SLM_OK;
+}
+
+int slm_gf_bind_render_loss(slm_gf* g, int32_t slot, slm_render* r, const slm_render_params* p, const float* radii,
+                            const float* colors, int32_t color_stride, const float* target_chw, double weight,
+                            int64_t entry_limit, void* stream) {
+  const char* who = "slm_gf_bind_render_loss";
+  if (!g) return fail(SLM_ERR_INVALID, "slm_gf_bind_render_loss: null argument");
+  if (slot < 0 || slot >= (int)g->host.size()) return fail(SLM_ERR_INVALID, "slm_gf_bind_render_loss: bad slot");
+  hipStream_t st = (hipStream_t)stream;
+  if (!r) return gf_clear_render(g, slot, st);
+  if (!p || !target_chw) return fail(SLM_ERR_INVALID, "slm_gf_bind_render_loss: null argument");
+  if (!g->host[slot].bound) return fail(SLM_ERR_UNBOUND, "slm_gf_bind_render_loss: slm_gf_bind_frame first");
+  if (g->world > 1)
+    return fail(SLM_ERR_UNSUPPORTED, "slm_gf_bind_render_loss: surfels are sharded; the render loss needs every surfel of "
+                                        "the frame on one device");
+  GfRenderTerm& t = g->rterm[slot];
+  if (!t.ctx && g->pgrad_host[slot])
+    return fail(SLM_ERR_INVALID, "slm_gf_bind_render_loss: a point gradient is bound to the slot (slm_gf_bind_point_grad): "
+                                    "clear it first");
+  for (int k = 0; k < (int)g->rterm.size(); ++k)
+    if (k != slot && g->rterm[k].ctx == r)
+      return fail(SLM_ERR_INVALID, "slm_gf_bind_render_loss: the context is bound to another slot; one context serves one "
+                                      "slot");
+  if (!std::isfinite(weight)) return fail(SLM_ERR_INVALID, "slm_gf_bind_render_loss: weight must be finite");
+  if (entry_limit < 0 || entry_limit > ((int64_t)1 << 31))
+    return fail(SLM_ERR_INVALID, "slm_gf_bind_render_loss: entry_limit must be 0 (from a sizing render) or 1..2^31");
+  const int N = g->host[slot].f.base.N;
+  if (const int rc = rn_gf_check(who, r, p, N, colors, color_stride)) return rc;
+  if (p->height < 6 || p->width < 6)
+    return fail(SLM_ERR_INVALID, "slm_gf_bind_render_loss: height and width must be >= 6 (the SSIM window)");
+  if (const int rc = gf_clear_render(g, slot, st)) return rc;   // (a failure below leaves the slot without the term)
+  const size_t px3 = 3 * (size_t)p->height * p->width, n3 = 3 * (size_t)N + 3;
+  const size_t n_scr = ssim_scratch_doubles(p->height, p->width, true);
+  HIPCHK(grow(t.image, t.cap_image, px3, px3));
+  HIPCHK(grow(t.gimg, t.cap_gimg, px3, px3));
+  HIPCHK(grow(t.pgrad, t.cap_pgrad, n3, n3));
+  HIPCHK(grow(t.loss, t.cap_loss, 2, 2));
+  HIPCHK(grow(t.scratch, t.cap_scratch, n_scr, n_scr));
+  unsigned long long limit = 0;
+  if (const int rc = rn_gf_size(who, r, p, g->dev + slot, N, radii, colors, color_stride, t.image, entry_limit, &limit, stream))
+    return rc;
+  HIPCHK(hipMemsetAsync(t.loss, 0, 2 * sizeof(double), st));
+  HIPCHK(hipMemsetAsync(t.pgrad, 0, n3 * sizeof(double), st));
+  t.p = *p;
+  t.radii = radii;
+  t.colors = colors;
+  t.cstride = color_stride;
+  t.target = target_chw;
+  t.weight = weight;
+  t.limit = limit;
+  g->pgrad_host[slot] = t.pgrad;
+  HIPCHK(hipMemcpyAsync(g->pgrad + slot, &g->pgrad_host[slot], sizeof(const double*), hipMemcpyHostToDevice, st));
+  HIPCHK(hipStreamSynchronize(st));
+  t.ctx = r;
+  return SLM_OK;
+}
+
+static int gf_render_term(slm_gf* g, int32_t slot, const char* who, const GfRenderTerm** t) {
+  const std::string w(who);
+  if (!g) return fail(SLM_ERR_INVALID, w + ": null argument");
+  if (slot < 0 || slot >= (int)g->host.size()) return fail(SLM_ERR_INVALID, w + ": bad slot");
+  if (!g->rterm[slot].ctx) return fail(SLM_ERR_UNBOUND, w + ": slm_gf_bind_render_loss first");
+  *t = &g->rterm[slot];
+  return SLM_OK;
+}
+
+int slm_gf_render_loss_status(slm_gf* g, int32_t slot, double out_host[4], void* stream) {
+  const GfRenderTerm* t = nullptr;
+  if (const int rc = gf_render_term(g, slot, "slm_gf_render_loss_status", &t)) return rc;
+  if (!out_host) return fail(SLM_ERR_INVALID, "slm_gf_render_loss_status: null argument");
+  hipStream_t st = (hipStream_t)stream;
+  double loss[2] = {0.0, 0.0};
+  unsigned long long stat[2] = {0, 0};
+  HIPCHK(hipMemcpyAsync(loss, t->loss, sizeof(loss), hipMemcpyDeviceToHost, st));
+  HIPCHK(rn_gf_status(t->ctx, stat, st));
+  HIPCHK(hipStreamSynchronize(st));
+  out_host[0] = loss[0];
+  out_host[1] = loss[1];
+  out_host[2] = (double)stat[0];
+  out_host[3] = (double)stat[1];
+  return SLM_OK;
+}
+
+int slm_gf_render_loss_read(slm_gf* g, int32_t slot, float* image, double* grad_points, void* stream) {
+  const GfRenderTerm* t = nullptr;
+  if (const int rc = gf_render_term(g, slot, "slm_gf_render_loss_read", &t)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const size_t px3 = 3 * (size_t)t->p.height * t->p.width, n3 = 3 * (size_t)g->host[slot].f.base.N;
+  if (image) HIPCHK(hipMemcpyAsync(image, t->image, sizeof(float) * px3, hipMemcpyDeviceToDevice, st));
+  if (grad_points && n3) HIPCHK(hipMemcpyAsync(grad_points, t->pgrad, sizeof(double) * n3, hipMemcpyDeviceToDevice, st));
   return SLM_OK;
 }
 
@@ -991,6 +1116,10 @@ int slm_gf_set_shard(slm_gf* g, int32_t rank, int32_t world) {
   g->rank = rank;
   g->world = world;
   for (GfSlot& s : g->host) s.bound = 0;   // shard bounds are fixed at bind time
+  for (size_t k = 0; k < g->rterm.size(); ++k) {
+    g->rterm[k].ctx = nullptr;
+    g->pgrad_host[k] = nullptr;
+  }
   hipError_t e = hipMemset(g->dev, 0, sizeof(GfSlot) * g->host.size());
   if (e != hipSuccess) return fail(SLM_ERR_HIP, hipGetErrorString(e));
   return SLM_OK;
@@ -1009,6 +1138,7 @@ int slm_gf_eval_losses(slm_gf* g, int32_t n_frames, void* stream) {
   int maxN, maxReg, maxP;
   int rc = gf_dims(g, 0, n_frames, &maxN, &maxReg, &maxP);
   if (rc) return rc;
+  gf_enqueue_render(g, 0, n_frames, (hipStream_t)stream);
   gf_enqueue_losses(g, g->dev, n_frames, maxN, maxReg, (hipStream_t)stream);
   HIPCHK(hipGetLastError());
   return SLM_OK;
@@ -1069,6 +1199,7 @@ int slm_gf_run(slm_gf* g, int32_t n_frames, void* stream) {
   for (int it = 0; it < n_it; ++it) {
     if (it == 0) hipLaunchKernelGGL(k_gf_zero, dim3(32, n_frames), dim3(256), 0, st, g->dev);
     if (morph) launch_gf_morph(g->dev, n_frames, maxN, st);
+    gf_enqueue_render(g, 0, n_frames, st);   // (nothing without slm_gf_bind_render_loss)
     gf_enqueue_losses(g, g->dev, n_frames, maxN, maxReg, st, false, morph);   // (the step folds)
     const int fold = (it + 1 < n_it ? 7 : 3) | (morph ? 8 : 0);
     hipLaunchKernelGGL(k_gf_step, dim3((maxP + 255) / 256, n_frames), dim3(256), 0, st, g->dev,
@@ -1096,6 +1227,7 @@ int slm_gf_loss_grad(slm_gf* g, int32_t slot, const double* dv, double* terms, d
   hipStream_t st = (hipStream_t)stream;
   const GfSlot& s = g->host[slot];
   HIPCHK(hipMemcpyAsync(s.dv, dv, sizeof(double) * maxP, hipMemcpyDeviceToDevice, st));
+  gf_enqueue_render(g, slot, 1, st);
   gf_enqueue_eval(g, g->dev + slot, 1, maxN, maxReg, st);
   hipLaunchKernelGGL(k_gf_step, dim3((maxP + 255) / 256, 1), dim3(256), 0, st, g->dev + slot, g->cfg.optimizer,
                      g->cfg.lr, 0, g->cfg.use_bn_morph, g->cfg.w_bn_morph, 0, 0);

@@ -55,6 +55,8 @@ struct slm_render {
   unsigned long long* tmp = nullptr;     // (cap_tmp, as many) merge scratch of the overflow path
   size_t cap_keys = 0, cap_tmp = 0;
   unsigned long long* h_total = nullptr; // pinned host copy of off[tiles]
+  unsigned long long* stat = nullptr;    // (3) status of the guarded forwards (rn_gf_forward): renders over their entry
+                                         // limit, the largest list total, the last total -- since rn_gf_size cleared it
   // ---- state of the last forward, read by slm_render_backward ----
   float4* col = nullptr;                 // (cap) colours of the points, w unused
   struct RnPix* pix = nullptr;           // (H * W) per-pixel blend record
@@ -174,8 +176,12 @@ __global__ void __launch_bounds__(256) k_rn_project(int N, const void* __restric
 }
 
 // exclusive scan of n tile counts, one workgroup of 1024 lanes, 1024 counts per round
+// The guarded form (stat != null: the enqueue-only forward, which cannot size the lists from the total) compares the total
+// with `limit`, the entries the lists hold: over it every list is left empty (off and cur all 0), so that nothing behind this
+// kernel indexes keys, tmp or the slab at all, and stat counts the render; stat also keeps the last and the largest total.
 __global__ void __launch_bounds__(1024) k_rn_scan(int n, const unsigned int* __restrict__ cnt,
-                                                  unsigned long long* __restrict__ off, unsigned long long* __restrict__ cur) {
+                                                  unsigned long long* __restrict__ off, unsigned long long* __restrict__ cur,
+                                                  unsigned long long limit, unsigned long long* __restrict__ stat) {
   __shared__ unsigned long long s[1024];
   __shared__ unsigned long long carry;
   const int t = threadIdx.x;
@@ -200,7 +206,21 @@ __global__ void __launch_bounds__(1024) k_rn_scan(int n, const unsigned int* __r
     if (t == 1023) carry += s[1023];
     __syncthreads();
   }
-  if (t == 0) off[n] = carry;
+  const unsigned long long total = carry;
+  const bool over = stat && total > limit;
+  if (over) {   // (element e was written above by this same lane)
+    for (int e = t; e <= n; e += 1024) {
+      off[e] = 0;
+      if (e < n) cur[e] = 0;
+    }
+  } else if (t == 0) {
+    off[n] = total;
+  }
+  if (stat && t == 0) {
+    if (over) stat[0] += 1;
+    if (total > stat[1]) stat[1] = total;
+    stat[2] = total;
+  }
 }
 
 // the key of point i in the list of every tile it touches: ascending keys are front to back (Z > 0), ties by row
@@ -221,11 +241,14 @@ __device__ __forceinline__ unsigned long long rn_find(const unsigned long long* 
   return lo < off[t + 1] && keys[lo] == key ? lo : RN_ABSENT;
 }
 
+// total != null (the guarded forward): nothing is written when the render's total, left there by k_rn_scan, is over `limit`
 __global__ void __launch_bounds__(256) k_rn_scatter(int N, int tiles_x, const float4* __restrict__ pos,
                                                     const int4* __restrict__ box, unsigned long long* __restrict__ cur,
-                                                    unsigned long long* __restrict__ keys) {
+                                                    unsigned long long* __restrict__ keys,
+                                                    const unsigned long long* __restrict__ total, unsigned long long limit) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= N) return;
+  if (total && *total > limit) return;
   const int4 b = box[i];
   if (b.x > b.y) return;
   const unsigned long long key = rn_key(pos, i);
@@ -808,10 +831,10 @@ __global__ void __launch_bounds__(256) k_rn_bwd_point_ch(int N, int tiles_x, int
   if (out_r) out_r[i] = ar;
 }
 
-// the device arrays of a context; sizes of slm_render_create: [0] points + 1, [1] tiles, [2] tiles + 1, [3] pixels
+// the device arrays of a context; sizes of slm_render_create: [0] points + 1, [1] tiles, [2] tiles + 1, [3] pixels, [4] 1
 #define A(name, mult, unit) DEV_MEMBER(slm_render, name, mult, unit)
 constexpr DevMember kRenderArrays[] = {A(pos, 1, 0), A(box, 1, 0), A(cnt, 1, 1), A(off, 1, 2), A(cur, 1, 1), A(col, 1, 0),
-                                       A(pix, 1, 3), DEV_GROWN(slm_render, keys), DEV_GROWN(slm_render, tmp),
+                                       A(pix, 1, 3), A(stat, 3, 4), DEV_GROWN(slm_render, keys), DEV_GROWN(slm_render, tmp),
                                        DEV_GROWN(slm_render, slab), DEV_GROWN(slm_render, feat), DEV_GROWN(slm_render, pixf)};
 #undef A
 
@@ -888,10 +911,8 @@ struct RnForward {
   void* stream;
 };
 
-int render_common(slm_render* r, const slm_render_params* p, const RnForward& f) {
-  const std::string w(f.who);
-  const int N = f.N, ch = f.ch;
-  if (!r || !p || !f.image) return fail(SLM_ERR_INVALID, w + ": null argument");
+// the refusals of a forward on the parameters and the point count, in their order (r and p not null)
+int rn_check_params(const std::string& w, const slm_render* r, const slm_render_params* p, int N) {
   if (p->width < 1 || p->height < 1 || p->width > r->W || p->height > r->H)
     return fail(SLM_ERR_INVALID, w + ": image size outside the context's H x W");
   if (p->n_track < 1 || p->n_track > SLM_RENDER_MAX_TRACK) return fail(SLM_ERR_INVALID, w + ": n_track must be 1..64");
@@ -900,6 +921,14 @@ int render_common(slm_render* r, const slm_render_params* p, const RnForward& f)
       !std::isfinite(p->radius) || !std::isfinite(p->bg_eps))
     return fail(SLM_ERR_INVALID, w + ": bad camera or blend parameters");
   if (N < 0 || N > r->cap) return fail(SLM_ERR_INVALID, w + ": more points than the context holds");
+  return SLM_OK;
+}
+
+int render_common(slm_render* r, const slm_render_params* p, const RnForward& f) {
+  const std::string w(f.who);
+  const int N = f.N, ch = f.ch;
+  if (!r || !p || !f.image) return fail(SLM_ERR_INVALID, w + ": null argument");
+  if (const int rc = rn_check_params(w, r, p, N)) return rc;
   if (ch && N > 0 && !f.pts) return fail(SLM_ERR_INVALID, w + ": null points");
   if (!ch && N > 0 && ((f.src != RN_SRC_GF && !f.pts) || !f.values || f.stride < 3))
     return fail(SLM_ERR_INVALID, w + ": null points / colours or color_stride < 3");
@@ -929,7 +958,7 @@ int render_common(slm_render* r, const slm_render_params* p, const RnForward& f)
   if (N > 0)
     hipLaunchKernelGGL(kProject[f.src][f.per_point], gp, dim3(256), 0, st, N, f.pts, f.gslot, cam, r->pos, r->box, r->cnt,
                        colors, cstride, r->col, f.radii);
-  hipLaunchKernelGGL(k_rn_scan, dim3(1), dim3(1024), 0, st, tiles, r->cnt, r->off, r->cur);
+  hipLaunchKernelGGL(k_rn_scan, dim3(1), dim3(1024), 0, st, tiles, r->cnt, r->off, r->cur, 0ull, nullptr);
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(r->h_total, r->off + tiles, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
@@ -939,7 +968,7 @@ int render_common(slm_render* r, const slm_render_params* p, const RnForward& f)
   HIPCHK(grow(r->keys, r->cap_keys, total, want));
   HIPCHK(grow(r->tmp, r->cap_tmp, total, want));
   if (total > 0)
-    hipLaunchKernelGGL(k_rn_scatter, gp, dim3(256), 0, st, N, cam.tiles_x, r->pos, r->box, r->cur, r->keys);
+    hipLaunchKernelGGL(k_rn_scatter, gp, dim3(256), 0, st, N, cam.tiles_x, r->pos, r->box, r->cur, r->keys, nullptr, 0ull);
   if (ch)
     hipLaunchKernelGGL(kTileCh[CP == 8][f.per_point], gt, dim3(256), 0, st, cam, bg, ch, r->off, r->keys, r->tmp, r->pos,
                        r->box, r->feat, f.image, f.front_id, f.hit_count, r->pix, r->pixf);
@@ -1010,6 +1039,74 @@ int rn_backward(slm_render* r, const slm_render_params* p, int C, const double* 
 
 }  // namespace
 
+// ---- the render loss inside slm_gf_run (slm_gf.hip; declared in slm_gf.h) ---------------------------------------------------
+// rn_gf_size at the bind, then per evaluation rn_gf_forward and rn_gf_backward, which only enqueue: the lists' capacity is the
+// entry limit fixed here, and k_rn_scan's guard keeps every render inside it.
+
+int rn_gf_check(const char* who, const slm_render* r, const slm_render_params* p, int N, const float* colors, int cstride) {
+  const std::string w(who);
+  if (const int rc = rn_check_params(w, r, p, N)) return rc;
+  if (N > 0 && (!colors || cstride < 3)) return fail(SLM_ERR_INVALID, w + ": null points / colours or color_stride < 3");
+  return SLM_OK;
+}
+
+// One render of the slot's current state through render_common (one synchronisation) sizes the lists and the slab (3 doubles
+// per entry) with the usual head-room; entry_limit > 0 replaces the logical limit, and the buffers hold at least that too.
+// Clears the status record and enters the sizing render's total as the largest seen.
+int rn_gf_size(const char* who, slm_render* r, const slm_render_params* p, GfSlot* gslot, int N, const float* radii,
+               const float* colors, int cstride, float* image, int64_t entry_limit, unsigned long long* limit_out,
+               void* stream) {
+  const int rc = render_common(r, p, {who, RN_SRC_GF, nullptr, gslot, N, radii != nullptr, radii, colors, cstride, 0, nullptr,
+                                      image, nullptr, nullptr, stream});
+  if (rc != SLM_OK) return rc;
+  const unsigned long long total = r->total_last;
+  const size_t sized = (size_t)total + total / 4 + 1024;
+  const size_t limit = entry_limit > 0 ? (size_t)entry_limit : sized, want = limit > sized ? limit : sized;
+  HIPCHK(grow(r->keys, r->cap_keys, want, want));
+  HIPCHK(grow(r->tmp, r->cap_tmp, want, want));
+  HIPCHK(grow(r->slab, r->cap_slab, 3 * want, 3 * want));
+  const unsigned long long stat[3] = {0, total, total};
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(hipMemcpyAsync(r->stat, stat, sizeof(stat), hipMemcpyHostToDevice, st));
+  HIPCHK(hipStreamSynchronize(st));
+  r->has_fwd = 0;   // the guarded forwards leave no host-side record: a backward entry point refuses until the next forward
+  *limit_out = limit;
+  return SLM_OK;
+}
+
+// render_common's launches for the surfels of `gslot`, three colour channels, with the guard in place of the read-back
+void rn_gf_forward(slm_render* r, const slm_render_params* p, GfSlot* gslot, int N, const float* radii, const float* colors,
+                   int cstride, float* image, unsigned long long limit, hipStream_t st) {
+  const RnCam cam = rn_cam(p);
+  const int tiles_y = (p->height + RN_TILE - 1) / RN_TILE, tiles = cam.tiles_x * tiles_y, pr = radii != nullptr;
+  r->has_fwd = 0;
+  (void)hipMemsetAsync(r->cnt, 0, sizeof(unsigned int) * tiles, st);
+  const dim3 gp((N + 255) / 256), gt(cam.tiles_x, tiles_y);
+  if (N > 0)
+    hipLaunchKernelGGL(kProject[RN_SRC_GF][pr], gp, dim3(256), 0, st, N, nullptr, gslot, cam, r->pos, r->box, r->cnt, colors,
+                       cstride, r->col, radii);
+  hipLaunchKernelGGL(k_rn_scan, dim3(1), dim3(1024), 0, st, tiles, r->cnt, r->off, r->cur, limit, r->stat);
+  if (N > 0)
+    hipLaunchKernelGGL(k_rn_scatter, gp, dim3(256), 0, st, N, cam.tiles_x, r->pos, r->box, r->cur, r->keys, r->stat + 2, limit);
+  hipLaunchKernelGGL(kTile[pr], gt, dim3(256), 0, st, cam, r->off, r->keys, r->tmp, r->pos, r->box, colors, cstride, image,
+                     nullptr, nullptr, r->pix);
+}
+
+// rn_backward's launches for the point gradient of the last rn_gf_forward (N > 0)
+void rn_gf_backward(slm_render* r, const slm_render_params* p, int N, bool per_point, const double* grad_image,
+                    double* grad_points, hipStream_t st) {
+  const RnCam cam = rn_cam(p);
+  const dim3 gt(cam.tiles_x, (p->height + RN_TILE - 1) / RN_TILE), gp((N + 255) / 256), b(256);
+  hipLaunchKernelGGL(kBwdEntry[per_point][RN_BWD_POINTS], gt, b, 0, st, cam, r->off, r->keys, r->pos, r->box, r->col, r->pix,
+                     grad_image, r->slab);
+  hipLaunchKernelGGL(k_rn_bwd_point, gp, b, 0, st, N, cam.tiles_x, r->off, r->keys, r->pos, r->box, r->slab, grad_points);
+}
+
+// {renders over their limit, largest total} since rn_gf_size, copied to the host on `st` (the caller synchronises)
+hipError_t rn_gf_status(const slm_render* r, unsigned long long out_host[2], hipStream_t st) {
+  return hipMemcpyAsync(out_host, r->stat, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st);
+}
+
 extern "C" {
 
 int slm_render_create(int32_t H, int32_t W, int32_t max_points, slm_render** out) {
@@ -1020,7 +1117,7 @@ int slm_render_create(int32_t H, int32_t W, int32_t max_points, slm_render** out
   r->W = W;
   r->cap = max_points;
   const size_t cap = (size_t)max_points + 1, tiles = (size_t)rn_tiles_x(W) * ((H + RN_TILE - 1) / RN_TILE);
-  const size_t units[] = {cap, tiles, tiles + 1, (size_t)H * W};
+  const size_t units[] = {cap, tiles, tiles + 1, (size_t)H * W, 1};
   hipError_t e = alloc_members(r, kRenderArrays, units);
   if (e == hipSuccess) e = hipHostMalloc((void**)&r->h_total, sizeof(unsigned long long), hipHostMallocDefault);
   if (e != hipSuccess) {

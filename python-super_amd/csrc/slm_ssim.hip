@@ -177,23 +177,34 @@ __global__ void __launch_bounds__(256) k_ssim_sum(int nb, const double* __restri
 
 }  // namespace
 
+// the doubles of scratch one evaluation needs: the tile partials and, with the gradient, the three maps of k_ssim_fwd
+size_t ssim_scratch_doubles(int h, int w, bool with_grad) {
+  const size_t nb = (size_t)((w + SS_T - 1) / SS_T) * ((h + SS_T - 1) / SS_T);
+  return 2 * nb + (with_grad ? 9 * (size_t)h * w : 0);
+}
+
+// the launches of one evaluation on the caller's scratch (h, w >= 6; grad_image may be null)
+void ssim_enqueue(int h, int w, const float* image_hwc, const float* target_chw, double weight, double* loss_out,
+                  double* grad_image, double* scratch, hipStream_t st) {
+  const dim3 grid((w + SS_T - 1) / SS_T, (h + SS_T - 1) / SS_T);
+  const int nb = (int)(grid.x * grid.y);
+  double* part = scratch;
+  double* G = grad_image ? scratch + 2 * (size_t)nb : nullptr;
+  hipLaunchKernelGGL(k_ssim_fwd, grid, dim3(256), 0, st, h, w, image_hwc, target_chw, weight, G, part);
+  hipLaunchKernelGGL(k_ssim_sum, dim3(1), dim3(256), 0, st, nb, part, weight, loss_out);
+  if (grad_image) hipLaunchKernelGGL(k_ssim_bwd, grid, dim3(256), 0, st, h, w, image_hwc, target_chw, G, grad_image);
+}
+
 extern "C" int slm_render_ssim_loss(int32_t h, int32_t w, const float* image_hwc, const float* target_chw, double weight,
                                     double* loss_out, double* grad_image, void* stream) {
   if (!image_hwc || !target_chw || !loss_out) return fail(SLM_ERR_INVALID, "slm_render_ssim_loss: null argument");
   if (h < SS_R + 1 || w < SS_R + 1) return fail(SLM_ERR_INVALID, "slm_render_ssim_loss: h and w must be >= 6");
   hipStream_t st = (hipStream_t)stream;
-  const dim3 grid((w + SS_T - 1) / SS_T, (h + SS_T - 1) / SS_T);
-  const int nb = (int)(grid.x * grid.y);
-  const size_t n_part = 2 * (size_t)nb, n_g = grad_image ? 9 * (size_t)h * w : 0;
   double* scratch = nullptr;
-  hipError_t e = hipMallocAsync((void**)&scratch, sizeof(double) * (n_part + n_g), st);
+  hipError_t e = hipMallocAsync((void**)&scratch, sizeof(double) * ssim_scratch_doubles(h, w, grad_image != nullptr), st);
   if (e != hipSuccess)
     return fail(SLM_ERR_HIP, std::string("slm_render_ssim_loss: hipMallocAsync: ") + hipGetErrorString(e));
-  double* part = scratch;
-  double* G = grad_image ? scratch + n_part : nullptr;
-  hipLaunchKernelGGL(k_ssim_fwd, grid, dim3(256), 0, st, h, w, image_hwc, target_chw, weight, G, part);
-  hipLaunchKernelGGL(k_ssim_sum, dim3(1), dim3(256), 0, st, nb, part, weight, loss_out);
-  if (grad_image) hipLaunchKernelGGL(k_ssim_bwd, grid, dim3(256), 0, st, h, w, image_hwc, target_chw, G, grad_image);
+  ssim_enqueue(h, w, image_hwc, target_chw, weight, loss_out, grad_image, scratch, st);
   e = hipGetLastError();
   const hipError_t f = hipFreeAsync(scratch, st);
   if (e == hipSuccess) e = f;

@@ -40,6 +40,7 @@ EXPORTS = [
     "slm_render_backward", "slm_render_ssim_loss", "slm_gf_bind_point_grad", "slm_render_backward_ex",
     "slm_render_points_radii", "slm_gf_render_radii", "slm_render_backward_radii",
     "slm_render_points_channels", "slm_render_backward_channels",
+    "slm_gf_bind_render_loss", "slm_gf_render_loss_status", "slm_gf_render_loss_read",
 ]
 
 
@@ -263,6 +264,9 @@ def load():
         "slm_render_backward_channels": [vp, C.POINTER(SlmRenderParams), i32, vp, vp, vp, vp, vp],
         "slm_render_ssim_loss": [i32, i32, vp, vp, dbl, vp, vp, vp],
         "slm_gf_bind_point_grad": [vp, i32, vp, vp],
+        "slm_gf_bind_render_loss": [vp, i32, vp, C.POINTER(SlmRenderParams), vp, vp, i32, vp, dbl, C.c_int64, vp],
+        "slm_gf_render_loss_status": [vp, i32, C.POINTER(C.c_double), vp],
+        "slm_gf_render_loss_read": [vp, i32, vp, vp, vp],
         "slm_gf_get_deform": [vp, i32, vp, vp],
         "slm_gf_loss_grad": [vp, i32, vp, vp, vp, vp],
         "slm_apply_update_gf": [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp],

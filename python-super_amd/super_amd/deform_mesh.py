@@ -30,6 +30,15 @@ raises for the flag.  Every iteration renders the deformed stable surfels (slm_g
 ``inputs[("color",0)]`` with its image gradient (slm_render_ssim_loss), back-propagates it to the surfels
 (slm_render_backward), binds that (slm_gf_bind_point_grad) and takes one evaluation and step.
 
+``GraphFit(opt, native_render_loss=True, render_in_run=True)`` makes the render loss a term of the run instead: the
+frame and the term are bound (slm_gf_bind_render_loss: one sizing render fixes the tile lists' entry limit) and ONE
+``slm_gf_run`` enqueues every iteration's render, SSIM loss, backward, evaluation and step with no host round trip.  A render
+whose tile lists would not fit the limit is empty and counted on the device; ``forward`` reads that status after the run and,
+if any render overflowed, binds again with a limit of 1.25 x the largest total + 1024 and repeats the run (the bind resets the
+state, so a repeat is a clean repeat; two repeats at most).  ``forward_frames`` runs up to ``max_frames`` frames in one
+``slm_gf_run``, with or without the term, one ``RenderContext`` per slot.  ``sf_corr_match_renderimg`` needs the image on the
+host side every iteration and is refused with ``render_in_run``.
+
 ``opt.renderer_surfel_radii`` (absent or False: nothing changes) renders every surfel with its own radius,
 ``src.radii * opt.renderer_radii_scale`` (default 1.0) as float32 by surfel row (slm_gf_render_radii), in place of the one
 ``opt.renderer_rad``: the same render feeds the render loss and ``sf_corr_match_renderimg``.  The radii are not optimised.
@@ -53,7 +62,7 @@ class GraphFit:
     rank takes the same step (BASELINE configs[4])."""
 
     def __init__(self, opt, max_frames=1, shard_surfels=False, rank=None, world=None, all_reduce=None,
-                 native_render_loss=False):
+                 native_render_loss=False, render_in_run=False):
         self.opt = opt
         self.lib = _lib.load()
         if not torch.cuda.is_available():
@@ -80,7 +89,16 @@ class GraphFit:
                                           f"only 'pulsar' is implemented (got {getattr(opt, 'renderer', None)!r})")
             if shard_surfels or world is not None:
                 raise NotImplementedError("super_amd.GraphFit: opt.sf_corr_match_renderimg on surfel-sharded frames")
+        self.render_in_run = bool(render_in_run)
+        if self.render_in_run and self.match_render:
+            raise NotImplementedError("super_amd.GraphFit: render_in_run with opt.sf_corr_match_renderimg: the flow network "
+                                      "needs the render on the host side every iteration; use the stepwise form")
         self._render_ctx = None
+        self._slot_ctx = [None] * max_frames       # render_in_run: one RenderContext per slot
+        self._slot_radii = [None] * max_frames
+        self._entry_limit_once = 0                 # tests: the entry limit of the next in-run bind of every slot, once
+        self.last_render_status = None             # render_in_run: per frame (loss, kept, overflowed renders, largest total)
+        self.render_repeats = 0                    # render_in_run: repeats the last forward needed
         # opt-in: the renders of this class give every surfel its own radius, src.radii * renderer_radii_scale
         # (slm_gf_render_radii), instead of opt.renderer_rad; the radii are not optimised (no radius gradient is asked for)
         self.surfel_radii = bool(getattr(opt, "renderer_surfel_radii", False))
@@ -222,11 +240,14 @@ class GraphFit:
                 raise ValueError(f"flow must be (1,2,{bf.c.H},{bf.c.W}), got {tuple(fl.shape)}")
             keep.append(fl)
             _lib.check(self.lib.slm_gf_bind_flow(self.h, slot, _dev_ptr(fl), _stream_ptr(dev)), "slm_gf_bind_flow")
-        if self.surfel_radii and slot == 0:      # float32 by surfel row, like Pulsar's vert_rad
-            self._render_radii = (src.radii.detach() * self.radii_scale).to(device=dev, dtype=torch.float32).contiguous()
-            if tuple(self._render_radii.shape) != (bf.c.N,):
+        if self.surfel_radii:      # float32 by surfel row, like Pulsar's vert_rad
+            radii = (src.radii.detach() * self.radii_scale).to(device=dev, dtype=torch.float32).contiguous()
+            if tuple(radii.shape) != (bf.c.N,):
                 raise ValueError(f"src.radii must be ({bf.c.N},), got {tuple(src.radii.shape)}")
-            keep.append(self._render_radii)
+            keep.append(radii)
+            self._slot_radii[slot] = radii
+            if slot == 0:
+                self._render_radii = radii
         self._keep[slot] = keep
         return bf
 
@@ -234,6 +255,8 @@ class GraphFit:
         """(reference ``deform_mesh.py:232-247``) returns deform_verts (J+1,7) float64."""
         if getattr(self.opt, "deform_udpate_method", "super_edg") != "super_edg":
             raise NotImplementedError("only deform_udpate_method == 'super_edg'")
+        if self.render_loss and self.render_in_run:
+            return self.forward_frames([(inputs, src, trg)], models)[0]
         if self.render_loss:
             return self._forward_render_loss(inputs, src, trg, models)
         if self.match_render:
@@ -256,6 +279,94 @@ class GraphFit:
         return out
 
     __call__ = forward
+
+    def _bind_render_term(self, slot, inputs, src, entry_limit=0):
+        """Binds the render loss to ``slot`` as a term of the run (slm_gf_bind_render_loss), after ``_bind`` of the same
+        frame: the slot's own ``RenderContext``, ``src.colors``, the radii of ``opt.renderer_surfel_radii`` and
+        ``inputs[("color",0)]`` as the target.  ``entry_limit`` 0: from the sizing render."""
+        from .renderer import DEFAULT_RAD, RenderContext, render_params
+        bf = self._keep[slot][0]
+        H, W, dev = bf.c.H, bf.c.W, bf.device
+        ctx = self._slot_ctx[slot]
+        if ctx is None or ctx.H < H or ctx.W < W:
+            ctx = self._slot_ctx[slot] = RenderContext(H, W)
+        ctx.reserve(bf.c.N)          # (the frame's bind took the term, and with it the old context, off the slot)
+        ctx.last_n = 0
+        ctx.serial += 1
+        p = render_params(inputs["K"], H, W, 1.0, getattr(self.opt, "renderer_rad", DEFAULT_RAD))
+        colors = src.colors.detach().to(device=dev, dtype=torch.float32).contiguous()
+        tgt = inputs[("color", 0)].detach()
+        tgt = tgt.reshape(tgt.shape[-3:]) if tgt.dim() == 4 else tgt
+        if tuple(tgt.shape) != (3, p.height, p.width):
+            raise ValueError(f'inputs[("color",0)] must be (3,{p.height},{p.width}) or (1,3,{p.height},{p.width}), '
+                             f"got {tuple(tgt.shape)}")
+        tgt = tgt.to(device=dev, dtype=torch.float32).contiguous()
+        radii = self._slot_radii[slot] if self.surfel_radii else None
+        self._keep[slot] += [colors, tgt]
+        _lib.check(self.lib.slm_gf_bind_render_loss(
+            self.h, slot, ctx.h, C.byref(p), _dev_ptr(radii) if radii is not None else None, _dev_ptr(colors),
+            int(colors.stride(0)), _dev_ptr(tgt), self.render_loss_weight, int(entry_limit), _stream_ptr(dev)),
+            "slm_gf_bind_render_loss")
+        return p
+
+    def render_loss_status(self, slot=0):
+        """(weighted loss, kept pixels) of the slot's last in-run evaluation, the renders over the entry limit and the
+        largest tile-list total since its bind (slm_gf_render_loss_status; synchronises)."""
+        out = (C.c_double * 4)()
+        _lib.check(self.lib.slm_gf_render_loss_status(self.h, slot, out, self._st()), "slm_gf_render_loss_status")
+        return float(out[0]), int(out[1]), int(out[2]), int(out[3])
+
+    def forward_frames(self, frames, models=None, render_frames=None):
+        """Up to ``max_frames`` frames, a list of ``(inputs, src, trg)``, in ONE ``slm_gf_run``: the list of their
+        deform_verts (J+1,7) float64.  All frames need the same ``num_neighbors``.  With ``opt.render_loss`` (needs
+        ``render_in_run=True``) every frame has the term, or those whose entry of ``render_frames`` (a list of bools) is
+        true; ``self.last_render_status`` then holds per frame (loss, kept, overflowed renders, largest total) or None.
+        If a render overflowed its tile lists' entry limit, the frames are bound again -- that frame with a limit of 1.25 x
+        its largest total + 1024 -- and the run is repeated, twice at most."""
+        if getattr(self.opt, "deform_udpate_method", "super_edg") != "super_edg":
+            raise NotImplementedError("only deform_udpate_method == 'super_edg'")
+        n = len(frames)
+        if n < 1 or n > self.max_frames:
+            raise ValueError(f"forward_frames: {n} frames, max_frames is {self.max_frames}")
+        if self.sharded:
+            raise NotImplementedError("super_amd.GraphFit: forward_frames on surfel-sharded frames")
+        if self.match_render:
+            raise NotImplementedError("super_amd.GraphFit: forward_frames with opt.sf_corr_match_renderimg")
+        if self.render_loss and not self.render_in_run:
+            raise NotImplementedError("super_amd.GraphFit: forward_frames with opt.render_loss needs render_in_run=True")
+        term = [self.render_loss] * n if render_frames is None else [bool(t) and self.render_loss for t in render_frames]
+        if len(term) != n:
+            raise ValueError("forward_frames: render_frames must have one entry per frame")
+        limits = [self._entry_limit_once] * n
+        self._entry_limit_once = 0
+        self.render_repeats = 0
+        while True:
+            for k, (inputs, src, trg) in enumerate(frames):
+                self._bind(k, inputs, src, trg, models)
+                if term[k]:
+                    self._bind_render_term(k, inputs, src, limits[k])
+            _lib.check(self.lib.slm_gf_run(self.h, n, self._st()), "slm_gf_run")
+            status = [self.render_loss_status(k) if term[k] else None for k in range(n)]
+            over = [k for k in range(n) if status[k] is not None and status[k][2] > 0]
+            if not over:
+                break
+            if self.render_repeats == 2:
+                raise _lib.SuperLMError(
+                    "super_amd.GraphFit: renders still overflow their tile lists after two repeats (frames "
+                    f"{over}, largest totals {[status[k][3] for k in over]}, limits {[limits[k] for k in over]})")
+            for k in over:
+                limits[k] = status[k][3] + status[k][3] // 4 + 1024
+            self.render_repeats += 1
+        self.last_render_status = status
+        if status[0] is not None:
+            self.last_render_kept = status[0][1]
+        outs = []
+        for k in range(n):
+            bf = self._keep[k][0]
+            out = torch.empty((bf.J + 1, 7), dtype=torch.float64, device=bf.device)
+            _lib.check(self.lib.slm_gf_get_deform(self.h, k, _dev_ptr(out), self._st()), "slm_gf_get_deform")
+            outs.append(out)
+        return outs
 
     def _forward_match_render(self, inputs, src, trg, models):
         """deform_mesh.py:286-330 with sf_corr_match_renderimg: per iteration render -> flow -> bind -> step."""

@@ -20,6 +20,12 @@ backward alone, and the fractions of pixels hit and kept.
 the C channels cost before), and the channels backward (points and features; with the radii as well under ``--radii``) for a
 random dL/dimage, after one forward.
 
+``--in-run`` times one GraphFit frame at C2 (200 k surfels, 2 000 nodes, 10 SGD iterations) four ways, interleaved in one
+process, at renderer_rad 2e-4, at 2e-3 and with the formula's per-surfel radii: without the render loss (``plain``), with it
+stepwise (``native_render_loss=True``), with it inside the run (``render_in_run=True``), and ``--frames B`` (default 8) such
+frames in one ``slm_gf_run`` (``forward_frames``; reported per frame).  Every timed call is the whole ``forward``, binds
+included.  ``--no-in-run-forms`` leaves the two in-run forms out (a library without them: SLM_LIB names another build).
+
 HIP events around each call after warm-up; median and maximum over --reps runs.  A render synchronises once
 inside (the tile-list total is read back), so a timed call includes that round trip.  Kernel times: run it under
 ``rocprofv3 --kernel-trace --stats -- python tools/time_render.py``."""
@@ -49,6 +55,72 @@ def _time(fn, reps, warm=3):
         b.synchronize()
         ts.append(a.elapsed_time(b) * 1e3)
     return {"median_us": float(np.median(ts)), "max_us": float(np.max(ts)), "reps": reps}
+
+
+def _time_interleaved(fns, reps, warm=2):
+    """{name: fn} -> {name: median / min / max in us}: the calls take turns, rep by rep, in one process"""
+    for _ in range(warm):
+        for fn in fns.values():
+            fn()
+    torch.cuda.synchronize()
+    ts = {k: [] for k in fns}
+    for _ in range(reps):
+        for k, fn in fns.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            ts[k].append(a.elapsed_time(b) * 1e3)
+    return {k: {"median_us": float(np.median(v)), "min_us": float(np.min(v)), "max_us": float(np.max(v)), "reps": reps}
+            for k, v in ts.items()}
+
+
+def in_run_mode(a):
+    from helpers import torch_frame
+    from oracle import graphfit_oracle as gfo
+    from super_amd import synth
+    from super_amd.deform_mesh import GraphFit
+    B, res = a.frames, {}
+    gsc = synth.make_scene(seed=0, **synth.WORKLOADS["C2"])
+    sf, ginputs, new_data = torch_frame(gsc)
+    sf.colors = torch.rand(gsc.N, 3, device="cuda", generator=torch.Generator("cuda").manual_seed(1))
+    sf.rgb = torch.zeros(1, 3, gsc.H, gsc.W, device="cuda")
+    nz = np.clip(np.abs(gsc.sf_norms[:, 2].astype(np.float64)), 0.26, 1.0)
+    sf.radii = torch.from_numpy(gsc.sf_points[:, 2].astype(np.float64) / (np.sqrt(2.0) * gsc.K[0, 0] * nz)).cuda()
+    ginputs = dict(ginputs)
+    ginputs[("color", 0)] = torch.zeros(1, 3, gsc.H, gsc.W, device="cuda")
+
+    def opt_of(rad, radii, loss):
+        o = gfo.default_opt(renderer="pulsar", renderer_rad=rad, render_loss=loss, render_loss_weight=1e-4)
+        o.deform_udpate_method = "super_edg"
+        o.renderer_surfel_radii = radii
+        return o
+
+    for key, rad, radii in (("rad2e-4", 2e-4, False), ("rad2e-3", 2e-3, False), ("radii", 2e-4, True)):
+        step = GraphFit(opt_of(rad, radii, True), native_render_loss=True)
+        step._bind(0, ginputs, sf, new_data)              # the colour frame: the render at identity, brightened
+        inp = dict(ginputs)
+        inp[("color", 0)] = (step.render_deformed(inp, sf.colors.float().contiguous()) + 0.01).contiguous()
+        plain = GraphFit(opt_of(rad, radii, False))
+        fns = {"plain": lambda: plain(inp, sf, new_data, None), "stepwise": lambda: step(inp, sf, new_data, None)}
+        if not a.no_in_run_forms:
+            one = GraphFit(opt_of(rad, radii, True), native_render_loss=True, render_in_run=True)
+            many = GraphFit(opt_of(rad, radii, True), max_frames=B, native_render_loss=True, render_in_run=True)
+            plain_many = GraphFit(opt_of(rad, radii, False), max_frames=B)
+            fns["in_run"] = lambda: one(inp, sf, new_data, None)
+            fns[f"in_run_b{B}"] = lambda: many.forward_frames([(inp, sf, new_data)] * B)
+            fns[f"plain_b{B}"] = lambda: plain_many.forward_frames([(inp, sf, new_data)] * B)
+        t = _time_interleaved(fns, a.reps)
+        for k, v in t.items():
+            if k.endswith(f"_b{B}"):
+                v["per_frame_median_us"] = v["median_us"] / B
+            res[f"graphfit_{k}_{key}"] = v
+        if not a.no_in_run_forms:
+            res[f"graphfit_in_run_{key}"]["status"] = one.last_render_status[0]
+            res[f"graphfit_in_run_{key}"]["repeats"] = one.render_repeats
+    res["graphfit_surfels"], res["frames"] = gsc.N, B
+    return res
 
 
 def radii_mode(a):
@@ -149,9 +221,12 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--radii", action="store_true", help="time the per-point render (see the module's docstring)")
     ap.add_argument("--channels", type=int, default=0, help="time the N-channel render with this many channels (1..8)")
+    ap.add_argument("--in-run", action="store_true", help="time the GraphFit render-loss frame stepwise and inside the run")
+    ap.add_argument("--frames", type=int, default=8, help="--in-run: frames per slm_gf_run of the batched form")
+    ap.add_argument("--no-in-run-forms", action="store_true", help="--in-run: only the plain and the stepwise frame")
     a = ap.parse_args()
-    if a.channels or a.radii:
-        res = channels_mode(a) if a.channels else radii_mode(a)
+    if a.in_run or a.channels or a.radii:
+        res = in_run_mode(a) if a.in_run else (channels_mode(a) if a.channels else radii_mode(a))
         print(json.dumps(res, indent=1))
         if a.out:
             with open(a.out, "w") as f:
