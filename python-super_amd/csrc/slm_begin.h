@@ -1,6 +1,6 @@
 // slm_begin.h -- start of an LM iteration on the multifrontal path: zero the assembled pivot-column tiles of the fronts, the
 // front vectors, rhs and the counters; reset the task graph's flags and mailboxes.  A device function (round 6) so that it
-// can run as k_iter_begin_nd (slm_front.hip) or as the tail blocks of the Jacobian pass's launch (k_data_gram, slm_data_v1.hip:
+// can run as k_iter_begin_nd (slm_front.hip) or as the tail blocks of the Jacobian pass's launch (k_data_gram, slm_data_k4.hip:
 // the two touch disjoint memory -- records vs fronts -- and the zeroing's store stream hides under the Gram pass's arithmetic).
 #pragma once
 #include "slm_tile.h"

@@ -49,7 +49,7 @@ struct LMState {
   int32_t chol_fail;     // set by the factorisation of the current iteration
   int32_t m_grad_local;  // surfel-sharded frames: this rank's own share of m_grad (k_pair_scatter puts the all-reduced count into
                          // m_grad; a Jacobian pass reused after a rejected step sends the share again, not the global count)
-  // ---- evaluation buffer of the tuple-sorted data path (k_data_eval, slm_data_v1.hip) ----
+  // ---- evaluation buffer of the tuple-sorted data path (k_data_eval, slm_data_k4.hip) ----
   int32_t eval_valid;    // 1: fd.ev_rc holds the evaluation (r, c per position) at the slot's CURRENT beta
   int32_t m_eval;        // matched surfels (of this rank's share) of the evaluation in fd.ev_rc
   unsigned long long eval_acc;   // k_data_eval: blocks done << 32 | sum of their matched counts, ONE relaxed atomic per block
@@ -83,7 +83,7 @@ struct FrameDev {
   // is one of the four taps -- needs no load of its own; the two taps of an image row are adjacent in memory.
   GP<float4> tgt_px;
   GP<unsigned long long> dbg;  // diagnostic builds only (-DSLM_STAMPS): in-kernel s_memtime stamps
-  // ---- tuple-sorted data-term assembly (slm_prep.hip / slm_data_v1.hip) ----
+  // ---- tuple-sorted data-term assembly (slm_prep.hip / slm_data_k4.hip) ----
   int32_t v1_ready;      // 1 when the structures below are valid for this frame
   int32_t n_tuples;      // distinct canonical KNN 4-tuples
   int32_t n_pos;         // padded surfel positions (multiple of 64)

@@ -50,7 +50,7 @@ __device__ __forceinline__ void rows_from_c(const d3 p, const int id[4], const d
 // 4 target rows); the loads of each stage are issued together, and callers that can fetch the
 // surfel stream entries early pass them in (eval_surfel_core).
 // MODE 0: residual only (loss pass); 1: residual + the 28 row entries; 2: residual + c (the evaluation pass that feeds
-// the tuple-sorted Jacobian pass, slm_data_v1.hip)
+// the tuple-sorted Jacobian pass, slm_data_k4.hip)
 // PX: the target taps come from the per-pixel table (FrameDev::tgt_px): one 32-byte gather per tap, the validity of the
 // rounded pixel from the tap that IS that pixel; out.taps is not filled (the evaluation pass of the LM loop does not
 // need the row numbers).  Same values, same sums: the match set and the residuals are those of the row-table form.

@@ -1,4 +1,4 @@
-// slm_data_v1.hip -- tuple-sorted data-term Jacobian pass (JtJ / jtl of the point-to-plane
+// slm_data_k4.hip -- tuple-sorted data-term Jacobian pass (JtJ / jtl of the point-to-plane
 // term, reference super/loss.py:222-288 + 200-205), no per-entry atomics on the matrix:
 //
 //   k_data_eval     the TARGET-side half of the per-surfel work, one thread per tuple-sorted position: skin ->

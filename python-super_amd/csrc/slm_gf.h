@@ -1,16 +1,30 @@
 // slm_gf.h -- state shared by the GraphFit kernels (slm_gf.hip) and the Semantic-SuPer
-// kernels (slm_sem.hip).
+// kernels (slm_sem.hip): the spread block partials and their one fold, the slot descriptor, the skinning sum.
 #pragma once
 #include "slm_data.h"
 
 // Block partials of the per-slot scalars (the global row's gradient, the loss terms, the counts) go to GF_NCOPY spread copies
-// behind `terms` -- copy (blockIdx.x % GF_NCOPY), entry a: terms[SLM_GF_NTERMS + 16 copy + a] -- and k_gf_fold sums the copies
-// in a fixed order into grad[7J..] / terms[].  One global f64 atomic per block and scalar onto ONE address serialises in the
-// L2: 782 blocks x ~0.1 us = the whole 82 us of k_gf_data at C2 (round 6); spread over 64 addresses it is 12 per address.
-//   a = 0..6 global row (k_gf_data, k_gf_reg) | 7, 8 point-plane loss, kept | 9, 10 correspondence loss, kept |
-//   11, 12, 13 face, arap, rot | 14, 15 morphing sum, kept
+// behind `terms` -- copy (blockIdx.x % GF_NCOPY), entry a: gf_part(s, copy)[a] -- and k_gf_fold / k_gf_step sum the copies in a
+// fixed order (gf_part_fold) into grad[7J..] / terms[].  One global f64 atomic per block and scalar onto ONE address serialises
+// in the L2: 782 blocks x ~0.1 us = the whole 82 us of k_gf_data at C2 (round 6); spread over 64 addresses it is 12 per address.
 #define GF_NCOPY 64
-#define GF_PART_DOUBLES (16 * GF_NCOPY)
+enum GfPart {
+  GFP_GLOBAL = 0,                        // 0..6 the global row's gradient (k_gf_data, k_gf_reg)
+  GFP_PP_LOSS = 7, GFP_PP_KEPT = 8,      // point-plane loss, residuals kept (k_gf_data)
+  GFP_CORR_LOSS = 9, GFP_CORR_KEPT = 10, // flow-correspondence loss, residuals kept (k_gf_data)
+  GFP_FACE = 11, GFP_ARAP = 12, GFP_ROT = 13,   // the node terms (gf_reg_body)
+  GFP_MORPH_SUM = 14, GFP_MORPH_KEPT = 15,      // morphing sum, kept (k_gf_morph)
+  GF_NPART = 16
+};
+#define GF_PART_DOUBLES (GF_NPART * GF_NCOPY)
+// which of the partials a launch folds: k_gf_fold's `which`
+enum GfFoldWhich { GF_FOLD_DATA = 1,     // the entries of k_gf_data / k_gf_reg (0..13)
+                   GF_FOLD_MORPH = 2 };  // those of k_gf_morph (14, 15)
+// k_gf_step's `fold` (see there)
+enum GfStepFold { GF_STEP_FOLD = 1,      // it sums the partials of k_gf_data / k_gf_reg itself (no k_gf_fold launch)
+                  GF_STEP_OWN = 2,       // it owns them: clears what it summed and ASSIGNS the loss terms
+                  GF_STEP_REZERO = 4,    // it leaves the gradient zeroed for the next iteration
+                  GF_STEP_MORPH = 8 };   // it also owns the morphing term's partials
 
 struct GfSlot {
   slm_gf_frame f;
@@ -83,57 +97,50 @@ __device__ __forceinline__ d3 quat_apply_t(double w, d3 v, d3 c) {
   return quat_apply(w, {-v.x, -v.y, -v.z}, c);
 }
 
-// deformed surfel i: T(p) = sum_k w_k [R(q_k)(p-g_k) + b_k + g_k], P = R(q_g) T + b_g
-// (deform_source, super/deform_mesh.py:198-221; K-generic like the reference: KK = opt.num_neighbors, 1..8)
-template <int KK>
-struct GfSkinT {
-  int id[KK];
-  double w[KK], qw[KK];
-  d3 qv[KK], dk[KK], T, P;
-  double gw;
-  d3 gv;
-};
-typedef GfSkinT<SLM_K> GfSkin;
-
-template <int KK>
-__device__ __forceinline__ void gf_skin(const GfSlotDev& s, int i, GfSkinT<KK>& k) {
-  const FrameIn& f = s.f.base;
-  const d3 p = ld_state3(f.sf_points, (size_t)i, f.state_f64);
-  if constexpr (KK == SLM_K) {
-    const int4 ids = *reinterpret_cast<const int4*>(f.sf_knn_idx + 4 * (size_t)i);
-    k.id[0] = ids.x; k.id[1] = ids.y; k.id[2] = ids.z; k.id[3] = ids.w;
-    ld_state4(f.sf_knn_w, (size_t)i, f.state_f64, k.w);
-  } else {
-#pragma unroll
-    for (int a = 0; a < KK; ++a) {
-      k.id[a] = f.sf_knn_idx[(size_t)KK * i + a];
-      k.w[a] = ld_state1(f.sf_knn_w, (size_t)KK * i + a, f.state_f64);
-    }
+// entry a of the partials -> the index in terms[] it is summed into (-1: the global row, grad[7J + a])
+__device__ __forceinline__ int gf_part_term(int a) {
+  constexpr int map[GF_NPART] = {-1, -1, -1, -1, -1, -1, -1, 3, 4, 8, 9, 0, 1, 2, 5, 6};
+  return map[a];
+}
+// the spread copy of the partials a block adds to
+__device__ __forceinline__ double* gf_part(GfSlotDev& s, int copy) { return s.terms.get() + SLM_GF_NTERMS + GF_NPART * copy; }
+// sum of the GF_NCOPY copies of entry a, in copy order; clear: the caller owns the partials and leaves them zeroed
+__device__ __forceinline__ double gf_part_fold(GfSlotDev& s, int a, bool clear) {
+  double* part = gf_part(s, 0);
+  double t = 0.0;
+  for (int c = 0; c < GF_NCOPY; ++c) {
+    t += part[GF_NPART * c + a];
+    if (clear) part[GF_NPART * c + a] = 0.0;
   }
-  k.T = {0, 0, 0};
-#pragma unroll
-  for (int a = 0; a < KK; ++a) {
-    const double* b = s.dv + 7 * k.id[a];
-    const d3 g = ld_state3(f.ed_points, (size_t)k.id[a], f.state_f64);
-    k.qw[a] = b[0];
-    k.qv[a] = {b[1], b[2], b[3]};
-    k.dk[a] = p - g;
-    d3 t = quat_apply(k.qw[a], k.qv[a], k.dk[a]);
-    t = {t.x + b[4] + g.x, t.y + b[5] + g.y, t.z + b[6] + g.z};
-    k.T = {k.T.x + k.w[a] * t.x, k.T.y + k.w[a] * t.y, k.T.z + k.w[a] * t.z};
-  }
-  const double* bgl = s.dv + 7 * f.J;
-  k.gw = bgl[0];
-  k.gv = {bgl[1], bgl[2], bgl[3]};
-  k.P = quat_apply(k.gw, k.gv, k.T);
-  k.P = {k.P.x + bgl[4], k.P.y + bgl[5], k.P.z + bgl[6]};
+  return t;
 }
 
-// The same without the per-neighbour state: ids, weights, p, T, P and the global row only.  k_gf_data keeps THIS across its
-// sampling phase (26 + 3 K registers instead of 30 + 17 K) and re-reads the nodes -- cache hits -- when it back-propagates:
-// with GfSkinT held live the kernel needed more than 256 VGPRs and ran at ONE wave per SIMD (round 6).
+// deformed surfel i: T(p) = sum_k w_k [R(q_k)(p-g_k) + b_k + g_k], P = R(q_g) T + b_g
+// (deform_source, super/deform_mesh.py:198-221; K-generic like the reference: KK = opt.num_neighbors, 1..8)
+// The sum is written once: gf_skin_add is one neighbour's term, gf_skin_global the global row; gf_skin<KK> (K at compile
+// time) and gf_skin_pos (K at run time) walk the neighbours in list order through them.
+__device__ __forceinline__ void gf_skin_add(const GfSlotDev& s, const d3 p, const int id, const double w, d3& T) {
+  const FrameIn& f = s.f.base;
+  const double* b = s.dv + 7 * id;
+  const d3 g = ld_state3(f.ed_points, (size_t)id, f.state_f64);
+  d3 t = quat_apply(b[0], {b[1], b[2], b[3]}, p - g);
+  t = {t.x + b[4] + g.x, t.y + b[5] + g.y, t.z + b[6] + g.z};
+  T = {T.x + w * t.x, T.y + w * t.y, T.z + w * t.z};
+}
+__device__ __forceinline__ d3 gf_skin_global(const GfSlotDev& s, const d3 T, double& gw, d3& gv) {
+  const double* bgl = s.dv + 7 * s.f.base.J;
+  gw = bgl[0];
+  gv = {bgl[1], bgl[2], bgl[3]};
+  const d3 P = quat_apply(gw, gv, T);
+  return {P.x + bgl[4], P.y + bgl[5], P.z + bgl[6]};
+}
+
+// What a surfel's evaluation keeps: ids, weights, p, T, P and the global row -- no per-neighbour state.  k_gf_data holds THIS
+// across its sampling phase (26 + 3 K registers) and re-reads the nodes -- cache hits -- when it back-propagates: with the
+// rotations and offsets of every neighbour held live (30 + 17 K) the kernel needed more than 256 VGPRs and ran at ONE wave
+// per SIMD (round 6).
 template <int KK>
-struct GfSkinLight {
+struct GfSkin {
   int id[KK];
   double w[KK];
   d3 p, T, P;
@@ -141,7 +148,7 @@ struct GfSkinLight {
   d3 gv;
 };
 template <int KK>
-__device__ __forceinline__ void gf_skin_light(const GfSlotDev& s, int i, GfSkinLight<KK>& k) {
+__device__ __forceinline__ void gf_skin(const GfSlotDev& s, int i, GfSkin<KK>& k) {
   const FrameIn& f = s.f.base;
   k.p = ld_state3(f.sf_points, (size_t)i, f.state_f64);
   if constexpr (KK == SLM_K) {
@@ -157,38 +164,21 @@ __device__ __forceinline__ void gf_skin_light(const GfSlotDev& s, int i, GfSkinL
   }
   k.T = {0, 0, 0};
 #pragma unroll
-  for (int a = 0; a < KK; ++a) {
-    const double* b = s.dv + 7 * k.id[a];
-    const d3 g = ld_state3(f.ed_points, (size_t)k.id[a], f.state_f64);
-    d3 t = quat_apply(b[0], {b[1], b[2], b[3]}, k.p - g);
-    t = {t.x + b[4] + g.x, t.y + b[5] + g.y, t.z + b[6] + g.z};
-    k.T = {k.T.x + k.w[a] * t.x, k.T.y + k.w[a] * t.y, k.T.z + k.w[a] * t.z};
-  }
-  const double* bgl = s.dv + 7 * f.J;
-  k.gw = bgl[0];
-  k.gv = {bgl[1], bgl[2], bgl[3]};
-  k.P = quat_apply(k.gw, k.gv, k.T);
-  k.P = {k.P.x + bgl[4], k.P.y + bgl[5], k.P.z + bgl[6]};
+  for (int a = 0; a < KK; ++a) gf_skin_add(s, k.p, k.id[a], k.w[a], k.T);
+  k.P = gf_skin_global(s, k.T, k.gw, k.gv);
 }
 
-// the deformed position alone, K at run time (the morphing term's pass: it needs P only) -- the same sums in the same order
+// the deformed position alone, K at run time (k_gf_morph at K != 4: it needs P only)
 __device__ __forceinline__ d3 gf_skin_pos(const GfSlotDev& s, int i) {
   const FrameIn& f = s.f.base;
   const int K = f.K;
   const d3 p = ld_state3(f.sf_points, (size_t)i, f.state_f64);
   d3 T = {0, 0, 0};
-  for (int a = 0; a < K; ++a) {
-    const int id = f.sf_knn_idx[(size_t)K * i + a];
-    const double w = ld_state1(f.sf_knn_w, (size_t)K * i + a, f.state_f64);
-    const double* b = s.dv + 7 * id;
-    const d3 g = ld_state3(f.ed_points, (size_t)id, f.state_f64);
-    d3 t = quat_apply(b[0], {b[1], b[2], b[3]}, p - g);
-    t = {t.x + b[4] + g.x, t.y + b[5] + g.y, t.z + b[6] + g.z};
-    T = {T.x + w * t.x, T.y + w * t.y, T.z + w * t.z};
-  }
-  const double* bgl = s.dv + 7 * f.J;
-  d3 P = quat_apply(bgl[0], {bgl[1], bgl[2], bgl[3]}, T);
-  return {P.x + bgl[4], P.y + bgl[5], P.z + bgl[6]};
+  for (int a = 0; a < K; ++a)
+    gf_skin_add(s, p, f.sf_knn_idx[(size_t)K * i + a], ld_state1(f.sf_knn_w, (size_t)K * i + a, f.state_f64), T);
+  double gw;
+  d3 gv;
+  return gf_skin_global(s, T, gw, gv);
 }
 
 // slm_gf_render (slm_render.hip): the device descriptor of bound slot `slot` (its current deform_verts) and its

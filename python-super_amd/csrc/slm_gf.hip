@@ -11,6 +11,12 @@
 //   face         w_f sum_tri (area(V) - area0)^2,  area = 1/2 sqrt(|e1 x e2|^2 + 1e-13)
 // Gradient of the global row is divided by J before the step (deform_mesh.py:326).
 // Local rows: summed per workgroup in an LDS table, then one f64 atomic per entry and touched node; the global row is reduced per block first.
+//
+// Layout of this file: k_gf_zero / k_gf_fold; the samplers (gf_sample, gf_flow_sample); the stages of k_gf_data, each a
+// function with its inputs and outputs in its signature (gf_project, gf_sem_weight, gf_point_plane, gf_corr, gf_row_pass,
+// gf_table_flush, gf_block_partials) and the kernel that runs them; the node terms (gf_reg_body); k_gf_step; bind / update
+// kernels.  Host: gf_slot (every entry point's argument checks), gf_dims, gf_publish_pgrad, gf_upload_slot, gf_launch_step,
+// gf_enqueue_morph / gf_enqueue_eval (the one evaluation sequence), then the entry points.
 #include <cmath>
 #include <string>
 #include <vector>
@@ -30,28 +36,17 @@ __global__ void __launch_bounds__(256) k_gf_zero(GfSlot* __restrict__ slots) {
 }
 
 // the spread block partials (slm_gf.h) -> grad[7J + 0..6] and terms[], copies summed in a fixed order, then cleared.
-// which: bit0 = the entries of k_gf_data / k_gf_reg (0..13), bit1 = those of k_gf_morph (14, 15).  grid = (1, n_frames), 64 threads
+// which: GfFoldWhich bits.  grid = (1, n_frames), 64 threads
 __global__ void __launch_bounds__(64) k_gf_fold(GfSlot* __restrict__ slots, int which) {
   GfSlotDev& s = gf_dev(slots)[blockIdx.y];
   if (!s.bound) return;
   const int a = threadIdx.x;
-  if (a >= 16) return;
-  const bool mine = a < 14 ? (which & 1) != 0 : (which & 2) != 0;
-  if (!mine) return;
-  double* part = s.terms.get() + SLM_GF_NTERMS;
-  double t = 0.0;
-  for (int c = 0; c < GF_NCOPY; ++c) {
-    t += part[16 * c + a];
-    part[16 * c + a] = 0.0;
-  }
+  if (a >= GF_NPART) return;
+  if (!(which & (a < GFP_MORPH_SUM ? GF_FOLD_DATA : GF_FOLD_MORPH))) return;
+  const double t = gf_part_fold(s, a, true);
   if (t == 0.0) return;
-  const int J = s.f.base.J;
-  if (a < 7) s.grad[7 * J + a] += t;
-  else {
-    // 7, 8 -> terms[3], [4]; 9, 10 -> [8], [9]; 11, 12, 13 -> [0], [1], [2]; 14, 15 -> [5], [6]
-    const int map[9] = {3, 4, 8, 9, 0, 1, 2, 5, 6};
-    s.terms[map[a - 7]] += t;
-  }
+  if (a < GFP_PP_LOSS) s.grad[7 * s.f.base.J + a] += t;
+  else s.terms[gf_part_term(a)] += t;
 }
 
 // 4-tap gather of the target maps at the float pixel (u_, v_) (bilinear_sample, loss.py:9-80, zero fill):
@@ -135,36 +130,278 @@ struct GfRegArgs {
 };
 __device__ __forceinline__ void gf_reg_body(GfSlotDev& s, const int bx, const GfRegArgs ra, double* sm);
 
-// grid = (ceil(maxN/256) [+ the regulariser's blocks], n_frames)
-// n_data_blocks: blocks [0, n_data_blocks) of a slot evaluate surfels; the blocks behind them, if any, run the node terms
-// (gf_reg_body: independent work that only meets this kernel's in the gradient's atomics -- slm_gf_run's loop saves a launch)
-// seg_mode: 0 none, 1 hard, 2 soft semantic weight on the squared residual (loss.py:379-399);
-// pp_max > 0 (and no seg_mode): squared residuals >= pp_max are dropped (loss.py:369-370);
-// use_morph: adds the back-propagation of the morphing term prepared by k_gf_morph (2: the kept count is still in the spread partials).
-// pgrad_ (EXTRA only): per slot of the launch a bound (N,3) dL/dP or null, added where morph_g is.
-// KK = opt.num_neighbors of the launch's slots (deform_source is K-generic, super/deform_mesh.py:198-221)
+// What a k_gf_data launch is given, built once on the host (gf_enqueue_eval).  The EXTRA = false instantiation reads
+// use_pp, lam, n_data_blocks and ra only.
+struct GfDataArgs {
+  int use_pp;          // the point-plane term is on
+  int seg_mode;        // 0 none, 1 hard, 2 soft semantic weight on the squared residual (loss.py:379-399)
+  int use_morph;       // adds the back-propagation of the morphing term prepared by k_gf_morph (2: the kept count is still
+                       // in the spread partials)
+  int corr_mode;       // 0 none, 1 'point-point', 2 'point-plane' flow-correspondence term
+  int n_data_blocks;   // blocks [0, n_data_blocks) of a slot evaluate surfels; the blocks behind them, if any, run the node
+                       // terms (gf_reg_body: independent work that only meets this kernel's in the gradient's atomics --
+                       // slm_gf_run's loop saves a launch)
+  int pad;
+  double lam;          // weight of the point-plane term
+  double pp_max;       // > 0 (and no seg_mode): squared residuals >= pp_max are dropped (loss.py:369-370)
+  double w_morph, lam_c;
+  GfRegArgs ra;
+  const double* const* pgrad;   // per slot of the launch a bound (N,3) dL/dP or null, added where morph_g is; or null
+};
+
+// ---- the stages of k_gf_data, in the order the kernel runs them --------------------------------------------------------------
+// the projection of P and the rows of its Jacobian: (u, v) = (fx X / Ze + cx, fy Y / Ze + cy), Ze = Z + 1e-8 -- the forward
+// divides by Z + 1e-8, and so does its derivative
+struct GfProj {
+  double u, v;
+  d3 Pi0, Pi1;   // du/dP, dv/dP
+};
+__device__ __forceinline__ GfProj gf_project(const FrameIn& f, const d3 P) {
+  const double fx = (double)f.fx, fy = (double)f.fy, cx = (double)f.cx, cy = (double)f.cy;
+  const double Ze = P.z + 1e-8;
+  GfProj pr;
+  pr.Pi0 = {fx / Ze, 0.0, -fx * P.x / (Ze * Ze)};
+  pr.Pi1 = {0.0, fy / Ze, -fy * P.y / (Ze * Ze)};
+  pr.u = P.x * fx / Ze + cx;
+  pr.v = P.y * fy / Ze + cy;
+  return pr;
+}
+
+// G (n + s0 A + s1 B): dL/dP of a residual along n whose sample position moves with P by A = du/dP, B = dv/dP
+__device__ __forceinline__ d3 gf_resid_grad(const double G, const d3 n, const double s0, const double s1, const d3 A, const d3 B) {
+  return {G * (n.x + s0 * A.x + s1 * B.x), G * (n.y + s0 * A.y + s1 * B.y), G * (n.z + s0 * A.z + s1 * B.z)};
+}
+
+// the semantic weight of surfel i's squared residual: conf = the target's class scores at the sample (C of them).
+// seg_mode 1: 1 where the surfel's class is the sample's, else 0; 2: exp(-0.1 JSD) of the two distributions.
+__device__ __forceinline__ double gf_sem_weight(const GfSlotDev& s, const int i, const int seg_mode, const int C, const double* conf) {
+  // sampled trg.seg_conf is softmaxed again (loss.py:357); weights are detached
+  double mx = conf[0];
+  int am = 0;
+  for (int c = 1; c < C; ++c)
+    if (conf[c] > mx) {
+      mx = conf[c];
+      am = c;
+    }
+  if (seg_mode == 1) return (s.sem.sf_seg[i] == am) ? 1.0 : 0.0;
+  double q[SLM_MAX_CLASSES], den = 0.0;
+  for (int c = 0; c < C; ++c) {
+    q[c] = exp(conf[c] - mx);
+    den += q[c];
+  }
+  // JSD(P, Q) = (KL(P|M) + KL(Q|M)) / 2, KL(P|Q) = sum P log(P / (Q + eps) + eps)  (utils.py:244-254)
+  const double eps = 1e-13;
+  double k1 = 0.0, k2 = 0.0;
+  for (int c = 0; c < C; ++c) {
+    const double pc = (double)s.sem.sf_seg_conf[(size_t)i * C + c], qc = q[c] / den;
+    const double m = 0.5 * (pc + qc);
+    k1 += pc * log(pc / (m + eps) + eps);
+    k2 += qc * log(qc / (m + eps) + eps);
+  }
+  return exp(-0.1 * (0.5 * (k1 + k2)));
+}
+
+// the point-plane term of surfel i at P: true when its residual is kept, then loss = lam wgt r^2 and gP = its dL/dP
+__device__ __forceinline__ bool gf_point_plane(const GfSlotDev& s, const int i, const d3 P, const GfProj& pr, const int seg_mode,
+                                               const double pp_max, const double lam, double& loss, d3& gP) {
+  const FrameIn& f = s.f.base;
+  const double ur = rint(pr.u), vr = rint(pr.v);
+  // valid_margin = 1 (loss.py:306-309)
+  if (!(vr >= 1.0 && vr < (double)(f.H - 2) && ur >= 1.0 && ur < (double)(f.W - 2))) return false;
+  GfSample q;
+  if (!gf_sample(f, pr.u, pr.v, q)) return false;
+  const d3 o = q.o, n = q.n, dou = q.dou, dov = q.dov, dnu = q.dnu, dnv = q.dnv;
+  double conf[SLM_MAX_CLASSES] = {0, 0, 0, 0};
+  const int C = (seg_mode && s.sem_bound) ? s.sem.num_classes : 0;
+  for (int t = 0; t < 4; ++t)
+    for (int c = 0; c < C; ++c) conf[c] += (double)s.sem.tgt_seg_conf[(size_t)q.rows[t] * C + c] * q.wv[t];
+  const d3 e = P - o;
+  const double r = dot(n, e);
+  double wgt = 1.0;
+  if (C > 0) wgt = gf_sem_weight(s, i, seg_mode, C, conf);
+  else if (pp_max > 0.0 && !((r * r) < pp_max)) return false;
+  loss = lam * wgt * r * r;
+  // c = dr/dP
+  const double s0 = dot(e, dnu) - dot(n, dou), s1 = dot(e, dnv) - dot(n, dov);
+  gP = gf_resid_grad(2.0 * lam * wgt * r, n, s0, s1, pr.Pi0, pr.Pi1);
+  return true;
+}
+
+// flow-correspondence term (opt.sf_corr, deform_mesh.py:100-109 -> loss.py:293-345 with flow): the UNROUNDED projection is moved
+// by the flow sampled at it, validity is margin 1 on the moved float coordinates.  True when kept: lossc set, gP += its dL/dP
+__device__ __forceinline__ bool gf_corr(const GfSlotDev& s, const d3 P, const GfProj& pr, const int corr_mode, const double lam_c,
+                                        double& lossc, d3& gP) {
+  const FrameIn& f = s.f.base;
+  const int H = f.H, W = f.W;
+  double fl[2], D[4];
+  gf_flow_sample(s.flow, H, W, pr.u, pr.v, fl, D);
+  const double uc = pr.u + fl[0], vc = pr.v + fl[1];
+  if (!(vc >= 1.0 && vc < (double)(H - 2) && uc >= 1.0 && uc < (double)(W - 2))) return false;
+  GfSample q;
+  if (!gf_sample(f, uc, vc, q)) return false;
+  // d(u', v')/dP = (I + dflow/d(u,v)) Pi
+  const d3 Pi0 = pr.Pi0, Pi1 = pr.Pi1;
+  const d3 Au = {(1.0 + D[0]) * Pi0.x + D[1] * Pi1.x, (1.0 + D[0]) * Pi0.y + D[1] * Pi1.y,
+                 (1.0 + D[0]) * Pi0.z + D[1] * Pi1.z};
+  const d3 Av = {D[2] * Pi0.x + (1.0 + D[3]) * Pi1.x, D[2] * Pi0.y + (1.0 + D[3]) * Pi1.y,
+                 D[2] * Pi0.z + (1.0 + D[3]) * Pi1.z};
+  const d3 e = P - q.o;
+  d3 g;
+  if (corr_mode == 1) {          // 'point-point': |P - o|^2
+    lossc = lam_c * dot(e, e);
+    g = gf_resid_grad(2.0 * lam_c, e, -dot(e, q.dou), -dot(e, q.dov), Au, Av);
+  } else {                       // 'point-plane': (n.(P - o))^2
+    const double r = dot(q.n, e);
+    lossc = lam_c * r * r;
+    g = gf_resid_grad(2.0 * lam_c * r, q.n, dot(e, q.dnu) - dot(q.n, q.dou), dot(e, q.dnv) - dot(q.n, q.dov), Au, Av);
+  }
+  gP = {gP.x + g.x, gP.y + g.y, gP.z + g.z};
+  return true;
+}
+
 #define GF_TAB 128   // LDS gradient table: slots per workgroup (power of two)
+// The local rows.  The 256 surfels of a workgroup are neighbours on the image and share a few dozen ED nodes: their
+// gradient rows are summed in an LDS table keyed by node (tkey / tval, ds_add_f64) and flushed with one global
+// atomic per entry and touched node (gf_table_flush) -- about 20x fewer memory-side f64 atomics than one per surfel
+// and entry.  A slot taken by another node (direct-mapped, node & 127) falls back to global atomics.
+// The WAVE turns round (round 6).  One LDS atomic per surfel, neighbour and entry -- 28 per surfel,
+// most of them onto the few addresses the wave's surfels share -- serialised inside every instruction (k_gf_data was 8x
+// slower per surfel than the LM path's evaluation pass).  Now the gradient rows of 16 surfels at a time go to LDS in
+// canonical slot order (s_gval / s_gid, per wave) and lane e < 7 KK owns ENTRY (slot e / 7, component e % 7): it walks the
+// surfels, accumulates in a register while the slot's node stays the same and adds to the workgroup's table when it changes
+// -- one conflict-free add per run of surfels with a common node instead of one conflicting add per surfel.
+// in: the surfel's skinning state k and cl = dL/dT(p) where has_grad
+template <int KK>
+__device__ __forceinline__ void gf_row_pass(GfSlotDev& s, const GfSkin<KK>& k, const d3 cl, const bool has_grad, int* tkey,
+                                            double* tval, double (*s_gval)[16][7 * KK], int (*s_gid)[16][KK]) {
+  const int l = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const unsigned long long am = __ballot(has_grad);
+  // WG entry-lane groups of 7 KK lanes share a round's 16 surfels (K = 4: lanes 0..27 walk surfels 0..7, lanes 28..55
+  // surfels 8..15): half the steps per round for one more flush per lane and round
+  constexpr int WG = (7 * KK <= 16) ? 4 : ((7 * KK <= 32) ? 2 : 1), WS = 16 / WG;
+  const int grp = l / (7 * KK), el = l - 7 * KK * grp;   // group, entry inside the group
+  const int slot = el / 7;
+  double acc = 0.0;
+  int prev = -1;
+  auto flush = [&]() {
+    if (prev < 0) return;
+    const int ts = prev & (GF_TAB - 1);
+    const int old = atomicCAS(&tkey[ts], -1, prev);
+    if (old == -1 || old == prev) unsafeAtomicAdd(&tval[7 * ts + (el - 7 * slot)], acc);
+    else atomic_add_f64(s.grad + 7 * prev + (el - 7 * slot), acc);
+  };
+  // K <= 4: every lane forms the quaternion parts of its K rows NOW, all 64 lanes at once (the node rows / positions are
+  // read again -- cache hits -- and held: 8 K registers); only the staging goes 16 surfels at a time.  (Formed inside the
+  // rounds by the 16 lanes of the round, the same instructions issued four times: 40 of the launch's 200 us at 8 C2 frames.)
+  constexpr bool EAGER = KK <= 4;
+  double jqa[EAGER ? KK : 1][4];
+  if (EAGER && has_grad) {
+    const FrameIn& f = s.f.base;
+#pragma unroll
+    for (int a = 0; a < (EAGER ? KK : 0); ++a) {
+      const double* b = s.dv + 7 * k.id[a];
+      const d3 g = ld_state3(f.ed_points, (size_t)k.id[a], f.state_f64);
+      quat_jac_row(b[0], {b[1], b[2], b[3]}, k.p - g, cl, jqa[a]);
+    }
+  }
+  if (!am) return;
+#pragma unroll 1
+  for (int sb = 0; sb < 4; ++sb) {
+    const unsigned mask16 = (unsigned)((am >> (16 * sb)) & 0xFFFFull);
+    if (mask16 == 0u) continue;                       // (uniform)
+    if ((l >> 4) == sb && has_grad) {
+      // this sub-batch's surfels form their rows now and write them straight to LDS (nothing per neighbour was held
+      // across the sampling phase: the node rows / positions are read again -- cache hits)
+      const FrameIn& f = s.f.base;
+#pragma unroll
+      for (int a = 0; a < KK; ++a) {
+        double jq[4];
+        if constexpr (EAGER) {
+#pragma unroll
+          for (int c = 0; c < 4; ++c) jq[c] = jqa[a][c];
+        } else {
+          const double* b = s.dv + 7 * k.id[a];
+          const d3 g = ld_state3(f.ed_points, (size_t)k.id[a], f.state_f64);
+          quat_jac_row(b[0], {b[1], b[2], b[3]}, k.p - g, cl, jq);
+        }
+        const double wk = k.w[a];
+        // canonical slot of neighbour a: its rank among the surfel's node ids (two surfels with the same neighbour SET
+        // have the same node in every slot, whatever the distance order of their KNN lists; the ids are distinct:
+        // slm_gf_bind_frame refuses a row that repeats one)
+        int rank = 0;
+#pragma unroll
+        for (int b2 = 0; b2 < KK; ++b2) rank += (k.id[b2] < k.id[a]) ? 1 : 0;
+        s_gid[w][l & 15][rank] = k.id[a];
+        double* dst = &s_gval[w][l & 15][7 * rank];
+        dst[0] = wk * jq[0]; dst[1] = wk * jq[1]; dst[2] = wk * jq[2]; dst[3] = wk * jq[3];
+        dst[4] = wk * cl.x;  dst[5] = wk * cl.y;  dst[6] = wk * cl.z;
+      }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    if (grp < WG) {
+      for (unsigned mm = mask16 & (((1u << WS) - 1u) << (WS * grp)); mm; mm &= mm - 1) {
+        const int si = __builtin_ctz(mm);
+        const int id = s_gid[w][si][slot];
+        const double v = s_gval[w][si][el];
+        if (id != prev) {
+          flush();
+          prev = id;
+          acc = v;
+        } else {
+          acc += v;
+        }
+      }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  }
+  if (grp < WG) flush();
+}
+
+// the workgroup's table -> the gradient: one global atomic per entry and touched node (behind a barrier)
+__device__ __forceinline__ void gf_table_flush(GfSlotDev& s, const int* tkey, const double* tval) {
+  for (int t = threadIdx.x; t < GF_TAB * 7; t += blockDim.x) {
+    const int node = tkey[t / 7];
+    const double v = tval[t];
+    if (node >= 0 && v != 0.0) atomic_add_f64(s.grad + 7 * node + t % 7, v);
+  }
+}
+
+// the block's sums of the first n_entries partial entries (vals: this thread's, by GfPart) -> its spread copy: one butterfly
+// over the 16 values of a thread per wave (col_reduce16, slm_lane.h: lane 4 a holds the wave's sum of value a), the four waves'
+// sums through LDS, then one atomic each (9 block_sums with two barriers each before: 19 of the launch's 215 us at 8 C2
+// frames, tools/diag/gf_ablate_time.py)
+__device__ __forceinline__ void gf_block_partials(GfSlotDev& s, double vals[GF_NPART], double* s_part, const int n_entries) {
+  const double r = col_reduce16(vals);
+  const int l = threadIdx.x & 63;
+  if ((l & 3) == 0) s_part[(threadIdx.x >> 6) * 16 + (l >> 2)] = r;
+  __syncthreads();
+  const int a = threadIdx.x;
+  if (a < n_entries) {
+    const double t = s_part[a] + s_part[16 + a] + s_part[32 + a] + s_part[48 + a];
+    if (t != 0.0) atomic_add_f64(gf_part(s, blockIdx.x % GF_NCOPY) + a, t);
+  }
+}
+
+// grid = (ceil(maxN/256) [+ the regulariser's blocks], n_frames)
+// KK = opt.num_neighbors of the launch's slots (deform_source is K-generic, super/deform_mesh.py:198-221)
 // EXTRA = false: the plain point-plane term only (no segmentation weight, clip, morphing or correspondence term) -- the
 // instantiation the default options run: those code paths, and the registers they hold, are compiled out (round 6: the
 // kernel ran at ONE wave per SIMD with everything in one body).
 template <int KK, bool EXTRA>
-__global__ void __launch_bounds__(256, (EXTRA || KK > 4) ? 3 : 4) k_gf_data(GfSlot* __restrict__ slots, int use_pp, double lam, int seg_mode_,
-                                                     double pp_max_, int use_morph_, double w_morph, int corr_mode_,
-                                                     double lam_c, int n_data_blocks, GfRegArgs ra,
-                                                     const double* const* __restrict__ pgrad_) {
-  const int seg_mode = EXTRA ? seg_mode_ : 0, use_morph = EXTRA ? use_morph_ : 0, corr_mode = EXTRA ? corr_mode_ : 0;
-  const double pp_max = EXTRA ? pp_max_ : 0.0;
+__global__ void __launch_bounds__(256, (EXTRA || KK > 4) ? 3 : 4) k_gf_data(GfSlot* __restrict__ slots, const GfDataArgs A) {
+  const int seg_mode = EXTRA ? A.seg_mode : 0, use_morph = EXTRA ? A.use_morph : 0, corr_mode = EXTRA ? A.corr_mode : 0;
+  const double pp_max = EXTRA ? A.pp_max : 0.0;
   __shared__ double sm[16];
-  if ((int)blockIdx.x >= n_data_blocks) {
+  if ((int)blockIdx.x >= A.n_data_blocks) {
     GfSlotDev& sr = gf_dev(slots)[blockIdx.y];
-    if (sr.bound) gf_reg_body(sr, blockIdx.x - n_data_blocks, ra, sm);
+    if (sr.bound) gf_reg_body(sr, blockIdx.x - A.n_data_blocks, A.ra, sm);
     return;
   }
-  // The 256 surfels of a workgroup are neighbours on the image and share a few dozen ED nodes: their
-  // gradient rows are summed in an LDS table keyed by node (ds_add_f64) and flushed with one global
-  // atomic per entry and touched node -- about 20x fewer memory-side f64 atomics than one per surfel
-  // and entry.  A slot taken by another node (direct-mapped, node & 127) falls back to global atomics.
-  __shared__ int tkey[GF_TAB];
+  __shared__ int tkey[GF_TAB];               // gf_row_pass's table: node per slot, 7 sums per slot
   __shared__ double tval[GF_TAB * 7];
   __shared__ double s_gval[4][16][7 * KK];   // gradient rows of 16 surfels of each wave, canonical slot order
   __shared__ int s_gid[4][16][KK];
@@ -175,138 +412,48 @@ __global__ void __launch_bounds__(256, (EXTRA || KK > 4) ? 3 : 4) k_gf_data(GfSl
   for (int t = threadIdx.x; t < GF_TAB; t += blockDim.x) tkey[t] = -1;
   for (int t = threadIdx.x; t < GF_TAB * 7; t += blockDim.x) tval[t] = 0.0;
   if (use_morph == 2 && threadIdx.x < 64) {
-    const double v = wave_sum((double)s.terms[SLM_GF_NTERMS + 16 * threadIdx.x + 15]);
+    const double v = wave_sum((double)gf_part(s, threadIdx.x)[GFP_MORPH_KEPT]);
     if (threadIdx.x == 0) s_kept = v;
   }
   __syncthreads();
   const FrameIn& f = s.f.base;
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  const int J = f.J;
   double gq[4] = {0, 0, 0, 0}, gb[3] = {0, 0, 0}, loss = 0.0, cnt = 0.0, lossc = 0.0, cntc = 0.0;
   bool has_grad = false;
   d3 cl = {0, 0, 0};          // dL/dT(p) of this surfel (the global rotation undone): what its neighbours' rows are formed from
-  GfSkinLight<KK> k;
+  GfSkin<KK> k;
 #pragma unroll
   for (int a = 0; a < KK; ++a) k.id[a] = 0;
   if (i >= s.shard_lo && i < s.shard_hi && (!s.f.sf_stable || s.f.sf_stable[i])) {
-    gf_skin_light<KK>(s, i, k);
+    gf_skin<KK>(s, i, k);
     const d3 P = k.P;
-    const double fx = (double)f.fx, fy = (double)f.fy, cx = (double)f.cx, cy = (double)f.cy;
-    const double Ze = P.z + 1e-8;
-    // the forward divides by Z + 1e-8, and so does its derivative
-    const d3 Pi0 = {fx / Ze, 0.0, -fx * P.x / (Ze * Ze)};
-    const d3 Pi1 = {0.0, fy / Ze, -fy * P.y / (Ze * Ze)};
+    const GfProj pr = gf_project(f, P);
     d3 gP = {0, 0, 0};   // dL/dP of this surfel
     bool any = false;
-    const double u_ = P.x * fx / Ze + cx, v_ = P.y * fy / Ze + cy;
-    const double ur = rint(u_), vr = rint(v_);
-    const int H = f.H, W = f.W;
-    // valid_margin = 1 (loss.py:306-309)
-    if (use_pp && vr >= 1.0 && vr < (double)(H - 2) && ur >= 1.0 && ur < (double)(W - 2)) {
-      GfSample q;
-      if (gf_sample(f, u_, v_, q)) {
-        const d3 o = q.o, n = q.n, dou = q.dou, dov = q.dov, dnu = q.dnu, dnv = q.dnv;
-        double conf[SLM_MAX_CLASSES] = {0, 0, 0, 0};
-        const int C = (seg_mode && s.sem_bound) ? s.sem.num_classes : 0;
-        for (int t = 0; t < 4; ++t)
-          for (int c = 0; c < C; ++c) conf[c] += (double)s.sem.tgt_seg_conf[(size_t)q.rows[t] * C + c] * q.wv[t];
-        const d3 e = P - o;
-        const double r = dot(n, e);
-        double wgt = 1.0;
-        bool keep = true;
-        if (C > 0) {
-          // sampled trg.seg_conf is softmaxed again (loss.py:357); weights are detached
-          double mx = conf[0];
-          int am = 0;
-          for (int c = 1; c < C; ++c)
-            if (conf[c] > mx) {
-              mx = conf[c];
-              am = c;
-            }
-          if (seg_mode == 1) {
-            wgt = (s.sem.sf_seg[i] == am) ? 1.0 : 0.0;
-          } else {
-            double q[SLM_MAX_CLASSES], den = 0.0;
-            for (int c = 0; c < C; ++c) {
-              q[c] = exp(conf[c] - mx);
-              den += q[c];
-            }
-            // JSD(P, Q) = (KL(P|M) + KL(Q|M)) / 2, KL(P|Q) = sum P log(P / (Q + eps) + eps)  (utils.py:244-254)
-            const double eps = 1e-13;
-            double k1 = 0.0, k2 = 0.0;
-            for (int c = 0; c < C; ++c) {
-              const double pc = (double)s.sem.sf_seg_conf[(size_t)i * C + c], qc = q[c] / den;
-              const double m = 0.5 * (pc + qc);
-              k1 += pc * log(pc / (m + eps) + eps);
-              k2 += qc * log(qc / (m + eps) + eps);
-            }
-            wgt = exp(-0.1 * (0.5 * (k1 + k2)));
-          }
-        } else if (pp_max > 0.0) {
-          keep = (r * r) < pp_max;
-        }
-        if (keep) {
-          loss = lam * wgt * r * r;
-          cnt = 1.0;
-          // c = dr/dP
-          const double s0 = dot(e, dnu) - dot(n, dou), s1 = dot(e, dnv) - dot(n, dov);
-          const double G = 2.0 * lam * wgt * r;
-          gP = {G * (n.x + s0 * Pi0.x + s1 * Pi1.x), G * (n.y + s0 * Pi0.y + s1 * Pi1.y),
-                G * (n.z + s0 * Pi0.z + s1 * Pi1.z)};
-          any = true;
-        }
-      }
+    if (A.use_pp && gf_point_plane(s, i, P, pr, seg_mode, pp_max, A.lam, loss, gP)) {
+      cnt = 1.0;
+      any = true;
     }
-    if (corr_mode && s.flow) {
-      // flow-correspondence term (opt.sf_corr, deform_mesh.py:100-109 -> loss.py:293-345 with flow): the UNROUNDED
-      // projection is moved by the flow sampled at it, validity is margin 1 on the moved float coordinates
-      double fl[2], D[4];
-      gf_flow_sample(s.flow, H, W, u_, v_, fl, D);
-      const double uc = u_ + fl[0], vc = v_ + fl[1];
-      if (vc >= 1.0 && vc < (double)(H - 2) && uc >= 1.0 && uc < (double)(W - 2)) {
-        GfSample q;
-        if (gf_sample(f, uc, vc, q)) {
-          // d(u', v')/dP = (I + dflow/d(u,v)) Pi
-          const d3 Au = {(1.0 + D[0]) * Pi0.x + D[1] * Pi1.x, (1.0 + D[0]) * Pi0.y + D[1] * Pi1.y,
-                         (1.0 + D[0]) * Pi0.z + D[1] * Pi1.z};
-          const d3 Av = {D[2] * Pi0.x + (1.0 + D[3]) * Pi1.x, D[2] * Pi0.y + (1.0 + D[3]) * Pi1.y,
-                         D[2] * Pi0.z + (1.0 + D[3]) * Pi1.z};
-          const d3 e = P - q.o;
-          if (corr_mode == 1) {          // 'point-point': |P - o|^2
-            lossc = lam_c * dot(e, e);
-            const double s0 = -dot(e, q.dou), s1 = -dot(e, q.dov);
-            const double G = 2.0 * lam_c;
-            gP = {gP.x + G * (e.x + s0 * Au.x + s1 * Av.x), gP.y + G * (e.y + s0 * Au.y + s1 * Av.y),
-                  gP.z + G * (e.z + s0 * Au.z + s1 * Av.z)};
-          } else {                       // 'point-plane': (n.(P - o))^2
-            const double r = dot(q.n, e);
-            lossc = lam_c * r * r;
-            const double s0 = dot(e, q.dnu) - dot(q.n, q.dou), s1 = dot(e, q.dnv) - dot(q.n, q.dov);
-            const double G = 2.0 * lam_c * r;
-            gP = {gP.x + G * (q.n.x + s0 * Au.x + s1 * Av.x), gP.y + G * (q.n.y + s0 * Au.y + s1 * Av.y),
-                  gP.z + G * (q.n.z + s0 * Au.z + s1 * Av.z)};
-          }
-          cntc = 1.0;
-          any = true;
-        }
-      }
+    if (corr_mode && s.flow && gf_corr(s, P, pr, corr_mode, A.lam_c, lossc, gP)) {
+      cntc = 1.0;
+      any = true;
     }
     if (use_morph && s.sem_bound) {
       // mean over the kept surfels (count from k_gf_morph, earlier in the stream: folded into terms[6] by k_gf_fold, or --
-      // use_morph == 2, slm_gf_run's loop -- still in the 64 spread copies of entry 15: summed once per block, s_kept; a count,
-      // exact in any order)
+      // use_morph == 2, slm_gf_run's loop -- still in the 64 spread copies of its entry: summed once per block, s_kept; a
+      // count, exact in any order)
       const double2 mg = s.morph_g[i];
       const double kept = use_morph == 2 ? s_kept : (double)s.terms[6];
       if (kept > 0.0 && (mg.x != 0.0 || mg.y != 0.0)) {
-        const double sc = w_morph / kept;
-        gP = {gP.x + sc * (mg.x * Pi0.x + mg.y * Pi1.x), gP.y + sc * (mg.x * Pi0.y + mg.y * Pi1.y),
-              gP.z + sc * (mg.x * Pi0.z + mg.y * Pi1.z)};
+        const double sc = A.w_morph / kept;
+        gP = {gP.x + sc * (mg.x * pr.Pi0.x + mg.y * pr.Pi1.x), gP.y + sc * (mg.x * pr.Pi0.y + mg.y * pr.Pi1.y),
+              gP.z + sc * (mg.x * pr.Pi0.z + mg.y * pr.Pi1.z)};
         any = true;
       }
     }
-    if (EXTRA && pgrad_) {
+    if (EXTRA && A.pgrad) {
       // an outside term's dL/dP by surfel row (slm_gf_bind_point_grad: the render loss through slm_render_backward)
-      const double* pg = pgrad_[blockIdx.y];
+      const double* pg = A.pgrad[blockIdx.y];
       if (pg) {
         const double ax = pg[3 * (size_t)i], ay = pg[3 * (size_t)i + 1], az = pg[3 * (size_t)i + 2];
         if (ax != 0.0 || ay != 0.0 || az != 0.0) {
@@ -327,122 +474,11 @@ __global__ void __launch_bounds__(256, (EXTRA || KK > 4) ? 3 : 4) k_gf_data(GfSl
       has_grad = true;
     }
   }
-  // ---- the local rows: the WAVE turns round (round 6).  One LDS atomic per surfel, neighbour and entry -- 28 per surfel,
-  // most of them onto the few addresses the wave's surfels share -- serialised inside every instruction (k_gf_data was 8x
-  // slower per surfel than the LM path's evaluation pass).  Now the gradient rows of 16 surfels at a time go to LDS in
-  // canonical slot order and lane e < 7 KK owns ENTRY (slot e / 7, component e % 7): it walks the surfels, accumulates in
-  // a register while the slot's node stays the same and adds to the workgroup's table when it changes -- one conflict-free
-  // add per run of surfels with a common node instead of one conflicting add per surfel.
-  {
-    const int l = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const unsigned long long am = __ballot(has_grad);
-    // WG entry-lane groups of 7 KK lanes share a round's 16 surfels (K = 4: lanes 0..27 walk surfels 0..7, lanes 28..55
-    // surfels 8..15): half the steps per round for one more flush per lane and round
-    constexpr int WG = (7 * KK <= 16) ? 4 : ((7 * KK <= 32) ? 2 : 1), WS = 16 / WG;
-    const int grp = l / (7 * KK), el = l - 7 * KK * grp;   // group, entry inside the group
-    const int slot = el / 7;
-    double acc = 0.0;
-    int prev = -1;
-    auto flush = [&]() {
-      if (prev < 0) return;
-      const int ts = prev & (GF_TAB - 1);
-      const int old = atomicCAS(&tkey[ts], -1, prev);
-      if (old == -1 || old == prev) unsafeAtomicAdd(&tval[7 * ts + (el - 7 * slot)], acc);
-      else atomic_add_f64(s.grad + 7 * prev + (el - 7 * slot), acc);
-    };
-    // K <= 4: every lane forms the quaternion parts of its K rows NOW, all 64 lanes at once (the node rows / positions are
-    // read again -- cache hits -- and held: 8 K registers); only the staging goes 16 surfels at a time.  (Formed inside the
-    // rounds by the 16 lanes of the round, the same instructions issued four times: 40 of the launch's 200 us at 8 C2 frames.)
-    constexpr bool EAGER = KK <= 4;
-    double jqa[EAGER ? KK : 1][4];
-    if (EAGER && has_grad) {
-      const FrameIn& f = s.f.base;
-#pragma unroll
-      for (int a = 0; a < (EAGER ? KK : 0); ++a) {
-        const double* b = s.dv + 7 * k.id[a];
-        const d3 g = ld_state3(f.ed_points, (size_t)k.id[a], f.state_f64);
-        quat_jac_row(b[0], {b[1], b[2], b[3]}, k.p - g, cl, jqa[a]);
-      }
-    }
-    if (am) {
-#pragma unroll 1
-      for (int sb = 0; sb < 4; ++sb) {
-        const unsigned mask16 = (unsigned)((am >> (16 * sb)) & 0xFFFFull);
-        if (mask16 == 0u) continue;                       // (uniform)
-        if ((l >> 4) == sb && has_grad) {
-          // this sub-batch's surfels form their rows now and write them straight to LDS (nothing per neighbour was held
-          // across the sampling phase: the node rows / positions are read again -- cache hits)
-          const FrameIn& f = s.f.base;
-#pragma unroll
-          for (int a = 0; a < KK; ++a) {
-            double jq[4];
-            if constexpr (EAGER) {
-#pragma unroll
-              for (int c = 0; c < 4; ++c) jq[c] = jqa[a][c];
-            } else {
-              const double* b = s.dv + 7 * k.id[a];
-              const d3 g = ld_state3(f.ed_points, (size_t)k.id[a], f.state_f64);
-              quat_jac_row(b[0], {b[1], b[2], b[3]}, k.p - g, cl, jq);
-            }
-            const double wk = k.w[a];
-            // canonical slot of neighbour a: its rank among the surfel's node ids (two surfels with the same neighbour SET
-            // have the same node in every slot, whatever the distance order of their KNN lists; the ids are distinct:
-            // slm_gf_bind_frame refuses a row that repeats one)
-            int rank = 0;
-#pragma unroll
-            for (int b2 = 0; b2 < KK; ++b2) rank += (k.id[b2] < k.id[a]) ? 1 : 0;
-            s_gid[w][l & 15][rank] = k.id[a];
-            double* dst = &s_gval[w][l & 15][7 * rank];
-            dst[0] = wk * jq[0]; dst[1] = wk * jq[1]; dst[2] = wk * jq[2]; dst[3] = wk * jq[3];
-            dst[4] = wk * cl.x;  dst[5] = wk * cl.y;  dst[6] = wk * cl.z;
-          }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        if (grp < WG) {
-          for (unsigned mm = mask16 & (((1u << WS) - 1u) << (WS * grp)); mm; mm &= mm - 1) {
-            const int si = __builtin_ctz(mm);
-            const int id = s_gid[w][si][slot];
-            const double v = s_gval[w][si][el];
-            if (id != prev) {
-              flush();
-              prev = id;
-              acc = v;
-            } else {
-              acc += v;
-            }
-          }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-      }
-      if (grp < WG) flush();
-    }
-  }
+  gf_row_pass<KK>(s, k, cl, has_grad, tkey, tval, s_gval, s_gid);
   __syncthreads();
-  for (int t = threadIdx.x; t < GF_TAB * 7; t += blockDim.x) {
-    const int node = tkey[t / 7];
-    const double v = tval[t];
-    if (node >= 0 && v != 0.0) atomic_add_f64(s.grad + 7 * node + t % 7, v);
-  }
-  // global row, loss and count: one butterfly over the 16 values of a thread per wave (col_reduce16, slm_lane.h: lane 4 a holds
-  // the wave's sum of value a), the four waves' sums through LDS, then one atomic each (9 block_sums with two barriers each
-  // before: 19 of the launch's 215 us at 8 C2 frames, tools/diag/gf_ablate_time.py)
-  {
-    double vals[16] = {gq[0], gq[1], gq[2], gq[3], gb[0], gb[1], gb[2], loss, cnt, lossc, cntc, 0.0, 0.0, 0.0, 0.0, 0.0};
-    const double r = col_reduce16(vals);
-    const int l = threadIdx.x & 63;
-    if ((l & 3) == 0) s_part[(threadIdx.x >> 6) * 16 + (l >> 2)] = r;
-    __syncthreads();
-    const int a = threadIdx.x;
-    if (a < (corr_mode ? 11 : 9)) {
-      const double t = s_part[a] + s_part[16 + a] + s_part[32 + a] + s_part[48 + a];
-      // (spread block partials, slm_gf.h: entries 0..6 global row, 7 / 8 point-plane loss / kept, 9 / 10 correspondence loss / kept)
-      if (t != 0.0) atomic_add_f64(s.terms.get() + SLM_GF_NTERMS + 16 * (blockIdx.x % GF_NCOPY) + a, t);
-    }
-  }
+  gf_table_flush(s, tkey, tval);
+  double vals[GF_NPART] = {gq[0], gq[1], gq[2], gq[3], gb[0], gb[1], gb[2], loss, cnt, lossc, cntc, 0.0, 0.0, 0.0, 0.0, 0.0};
+  gf_block_partials(s, vals, s_part, corr_mode ? GFP_CORR_KEPT + 1 : GFP_PP_KEPT + 1);
 }
 
 // ARAP: one thread per (node, slot); Rot: one thread per row (J+1); face: one per triangle.
@@ -539,9 +575,8 @@ __device__ __forceinline__ void gf_reg_body(GfSlotDev& s, const int bx, const Gf
 #pragma unroll
   for (int a = 0; a < 10; ++a) {
     const double tt = block_sum(vals[a], sm);
-    // (spread block partials: 0..6 global row, 11 / 12 / 13 face / arap / rot)
-    if (threadIdx.x == 0 && tt != 0.0)
-      atomic_add_f64(s.terms.get() + SLM_GF_NTERMS + 16 * (bx % GF_NCOPY) + (a < 7 ? a : a + 4), tt);
+    // (spread block partials: the global row, then face / arap / rot)
+    if (threadIdx.x == 0 && tt != 0.0) atomic_add_f64(gf_part(s, bx % GF_NCOPY) + (a < 7 ? GFP_GLOBAL + a : GFP_FACE + a - 7), tt);
   }
 }
 __global__ void __launch_bounds__(256) k_gf_reg(GfSlot* __restrict__ slots, GfRegArgs ra) {
@@ -553,13 +588,13 @@ __global__ void __launch_bounds__(256) k_gf_reg(GfSlot* __restrict__ slots, GfRe
 
 // grad[J] /= J, then torch.optim.SGD(momentum=0.9) or torch.optim.Adam step (float64).
 // Also turns the morphing term's sum into the reference's weighted mean (NaN over an empty set).
-// fold: bit 0 -- this launch also sums the spread block partials of k_gf_data / k_gf_reg (what k_gf_fold(which = 1) does as a
-// launch of its own: slm_gf_run's loop saves that launch; the thread of a global-row entry sums its own 64 copies, threads
-// 0..6 the loss terms');  bit 1 -- the launch OWNS the partials: it clears what it summed and ASSIGNS the loss terms (nothing
-// else wrote them since the last k_gf_zero);  bit 2 -- it leaves the gradient zeroed for the next iteration (bits 1 + 2:
-// slm_gf_run's loop needs no k_gf_zero between two iterations);  bit 3 -- the launch also owns the morphing term's partials
-// (entries 14 / 15: k_gf_fold(which = 2) as a launch of its own otherwise): it assigns terms[5] / [6] from them, clears them and,
-// with bit 2, resets the candidates flag terms[7] for the next iteration's k_gf_morph.
+// fold (GfStepFold bits): GF_STEP_FOLD -- this launch also sums the spread block partials of k_gf_data / k_gf_reg (what
+// k_gf_fold(GF_FOLD_DATA) does as a launch of its own: slm_gf_run's loop saves that launch; the thread of a global-row entry
+// sums its own 64 copies, threads 0..6 the loss terms');  GF_STEP_OWN -- the launch OWNS the partials: it clears what it summed
+// and ASSIGNS the loss terms (nothing else wrote them since the last k_gf_zero);  GF_STEP_REZERO -- it leaves the gradient zeroed
+// for the next iteration (OWN + REZERO: slm_gf_run's loop needs no k_gf_zero between two iterations);  GF_STEP_MORPH -- the
+// launch also owns the morphing term's partials (k_gf_fold(GF_FOLD_MORPH) as a launch of its own otherwise): it assigns
+// terms[5] / [6] from them, clears them and, with REZERO, resets the candidates flag terms[7] for the next iteration's k_gf_morph.
 // step_off: optimiser steps of this run that s.step does not count yet (k_gf_advance adds them at the end of the run)
 __global__ void __launch_bounds__(256) k_gf_step(GfSlot* __restrict__ slots, int optimizer, double lr,
                                                   int apply, int use_morph, double w_morph, int fold, int step_off) {
@@ -569,50 +604,31 @@ __global__ void __launch_bounds__(256) k_gf_step(GfSlot* __restrict__ slots, int
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   if (e == 0 && use_morph) {
     double li = s.terms[5], kept = s.terms[6];
-    if (fold & 8) {
-      double* part = s.terms.get() + SLM_GF_NTERMS;
-      li = 0.0;
-      kept = 0.0;
-      for (int c = 0; c < GF_NCOPY; ++c) {
-        li += part[16 * c + 14];
-        kept += part[16 * c + 15];
-        part[16 * c + 14] = 0.0;
-        part[16 * c + 15] = 0.0;
-      }
+    if (fold & GF_STEP_MORPH) {
+      li = gf_part_fold(s, GFP_MORPH_SUM, true);
+      kept = gf_part_fold(s, GFP_MORPH_KEPT, true);
       s.terms[6] = kept;
     }
     s.terms[5] = s.terms[7] != 0.0 ? (kept > 0.0 ? w_morph * li / kept : nan("")) : 0.0;
-    if ((fold & 12) == 12) s.terms[7] = 0.0;
+    if ((fold & (GF_STEP_REZERO | GF_STEP_MORPH)) == (GF_STEP_REZERO | GF_STEP_MORPH)) s.terms[7] = 0.0;
   }
   if (e >= n) return;
   double g = s.grad[e];
-  const bool own = (fold & 2) != 0;
-  if (fold & 1) {
-    double* part = s.terms.get() + SLM_GF_NTERMS;
-    if (e < 7) {   // entries 7..13 of the partials: point-plane loss / kept, correspondence loss / kept, face, arap, rot
-      const int map[7] = {3, 4, 8, 9, 0, 1, 2};
-      double t = 0.0;
-      for (int c = 0; c < GF_NCOPY; ++c) {
-        t += part[16 * c + 7 + e];
-        if (own) part[16 * c + 7 + e] = 0.0;
-      }
-      if (own) s.terms[map[e]] = t;
-      else if (t != 0.0) s.terms[map[e]] += t;
+  if (fold & GF_STEP_FOLD) {
+    const bool own = (fold & GF_STEP_OWN) != 0;
+    if (e < GFP_MORPH_SUM - GFP_PP_LOSS) {   // thread e: the loss term of entry GFP_PP_LOSS + e (point-plane .. rot)
+      const int a = GFP_PP_LOSS + e;
+      const double t = gf_part_fold(s, a, own);
+      if (own) s.terms[gf_part_term(a)] = t;
+      else if (t != 0.0) s.terms[gf_part_term(a)] += t;
     }
-    if (e >= 7 * J) {
-      double t = 0.0;
-      for (int c = 0; c < GF_NCOPY; ++c) {
-        t += part[16 * c + (e - 7 * J)];
-        if (own) part[16 * c + (e - 7 * J)] = 0.0;
-      }
-      g += t;
-    }
+    if (e >= 7 * J) g += gf_part_fold(s, GFP_GLOBAL + e - 7 * J, own);
   }
   if (e >= 7 * J) {
     g /= (double)J;
     s.grad[e] = g;
   }
-  if (fold & 4) s.grad[e] = 0.0;
+  if (fold & GF_STEP_REZERO) s.grad[e] = 0.0;
   if (!apply) return;
   const int t = s.step + 1 + step_off;
   if (optimizer == 0) {
@@ -739,6 +755,74 @@ struct slm_gf {
   std::vector<GfRenderTerm> rterm;            // per slot: the render loss of slm_gf_bind_render_loss (its pgrad is the slot's)
 };
 
+// ---- what every entry point goes through ---------------------------------------------------------------------------------------
+// The slots [first, first + n) of an entry point `who`: g, the other required arguments (args_ok) and the range checked, and --
+// need_bound -- that slot `first` holds a frame; *out = the host copy of slot `first`.  The texts are each family's own.
+struct GfSlotTexts {
+  const char *null_arg, *range, *unbound;
+};
+static const GfSlotTexts GF_TEXTS_BIND = {"null argument", "bad slot", "slm_gf_bind_frame first"};
+static const GfSlotTexts GF_TEXTS_RENDER = {"bad slot", "bad slot", "slm_gf_bind_frame first"};
+static const GfSlotTexts GF_TEXTS_EDGE = {"bad argument", "bad argument", nullptr};
+static const GfSlotTexts GF_TEXTS_RANGE = {"slot range out of bounds", "slot range out of bounds", "slot used before slm_gf_bind_frame"};
+static int gf_slot(const char* who, const GfSlotTexts& tx, slm_gf* g, bool args_ok, int first, int n, bool need_bound, GfSlot** out) {
+  auto refuse = [who](int code, const char* text) { return fail(code, std::string(who) + ": " + text); };   // (no string unless refused)
+  if (!g || !args_ok) return refuse(SLM_ERR_INVALID, tx.null_arg);
+  if (first < 0 || n < 1 || first + n > (int)g->host.size()) return refuse(SLM_ERR_INVALID, tx.range);
+  if (need_bound && !g->host[first].bound) return refuse(SLM_ERR_UNBOUND, tx.unbound);
+  if (out) *out = &g->host[first];
+  return SLM_OK;
+}
+
+// the launch sizes over the slots [first, first + n) of an evaluation entry point, every slot checked for what the
+// configuration needs bound; sets g->batch_K
+struct GfDims {
+  int maxN = 0, maxReg = 0, maxP = 0;
+};
+static int gf_dims(slm_gf* g, int first, int n, GfDims* d) {
+  if (const int rc = gf_slot("slm_gf", GF_TEXTS_RANGE, g, true, first, n, false, nullptr)) return rc;
+  *d = GfDims{};
+  for (int i = first; i < first + n; ++i) {
+    GfSlot* sp = nullptr;
+    if (const int rc = gf_slot("slm_gf", GF_TEXTS_RANGE, g, true, i, 1, true, &sp)) return rc;
+    const GfSlot& s = *sp;
+    if ((g->cfg.seg_mode || g->cfg.use_bn_morph) && !s.sem_bound)
+      return fail(SLM_ERR_UNBOUND, "slm_gf: semantic terms enabled but slm_gf_bind_semantic was not called");
+    if (g->cfg.corr_mode && !s.flow)
+      return fail(SLM_ERR_UNBOUND, "slm_gf: corr_mode set but slm_gf_bind_flow was not called");
+    if (s.f.base.K != g->host[first].f.base.K)
+      return fail(SLM_ERR_UNSUPPORTED, "slm_gf: the frames of one batch must have the same num_neighbors");
+    d->maxN = std::max(d->maxN, s.f.base.N);
+    int reg = std::max(s.f.base.J * s.f.base.K_ED, s.f.base.J + 1);
+    if (g->cfg.use_face) reg = std::max(reg, s.f.n_triangles);
+    d->maxReg = std::max(d->maxReg, reg);
+    d->maxP = std::max(d->maxP, (s.f.base.J + 1) * 7);
+  }
+  g->batch_K = g->host[first].f.base.K;
+  return SLM_OK;
+}
+
+// the slot's point gradient (what k_gf_data<K, true> adds), on the host and in the device table; wait: behind the copy
+static int gf_publish_pgrad(slm_gf* g, int slot, const double* pgrad, hipStream_t st, bool wait = true) {
+  g->pgrad_host[slot] = pgrad;
+  HIPCHK(hipMemcpyAsync(g->pgrad + slot, &g->pgrad_host[slot], sizeof(const double*), hipMemcpyHostToDevice, st));
+  if (wait) HIPCHK(hipStreamSynchronize(st));
+  return SLM_OK;
+}
+
+// the host copy of the slot's descriptor -> the device, waited for
+static int gf_upload_slot(slm_gf* g, int slot, hipStream_t st) {
+  HIPCHK(hipMemcpyAsync(g->dev + slot, &g->host[slot], sizeof(GfSlot), hipMemcpyHostToDevice, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return SLM_OK;
+}
+
+// k_gf_step over the slots [first, first + n): fold = GfStepFold bits, step_off as the kernel's
+static void gf_launch_step(slm_gf* g, int first, int n, const GfDims& d, int apply, int fold, int step_off, hipStream_t st) {
+  hipLaunchKernelGGL(k_gf_step, dim3((d.maxP + 255) / 256, n), dim3(256), 0, st, g->dev + first, g->cfg.optimizer, g->cfg.lr, apply,
+                     g->cfg.use_bn_morph, g->cfg.w_bn_morph, fold, step_off);
+}
+
 // The render loss of the slots [first, first + n) that have it, in front of an evaluation: the guarded forward of the slot's
 // current deform_verts, the SSIM loss with its image gradient, the guarded backward into the buffer k_gf_data<K, true> reads.
 // Launches only: the buffers and the lists' entry limit were fixed by slm_gf_bind_render_loss.
@@ -757,53 +841,67 @@ static void gf_enqueue_render(slm_gf* g, int first, int n, hipStream_t st) {
 static int gf_clear_render(slm_gf* g, int slot, hipStream_t st) {
   if (!g->rterm[slot].ctx) return SLM_OK;
   g->rterm[slot].ctx = nullptr;
-  g->pgrad_host[slot] = nullptr;
-  HIPCHK(hipMemcpyAsync(g->pgrad + slot, &g->pgrad_host[slot], sizeof(const double*), hipMemcpyHostToDevice, st));
-  HIPCHK(hipStreamSynchronize(st));
-  return SLM_OK;
+  return gf_publish_pgrad(g, slot, nullptr, st);
 }
 
-// pass 1: zero the gradient / terms, then the morphing term's per-surfel pass (sum, count)
-static void gf_enqueue_morph(slm_gf* g, GfSlot* slots, int n, int maxN, hipStream_t st) {
-  hipLaunchKernelGGL(k_gf_zero, dim3(32, n), dim3(256), 0, st, slots);
-  if (g->cfg.use_bn_morph) {
-    launch_gf_morph(slots, n, maxN, st);
-    hipLaunchKernelGGL(k_gf_fold, dim3(1, n), dim3(64), 0, st, slots, 2);   // terms[5], [6]: what the back-propagation divides by
-  }
+// What an evaluation consists of (gf_enqueue_morph, gf_enqueue_eval)
+enum GfEval {
+  GF_EVAL_ZERO = 1,     // k_gf_zero in front of pass 1
+  GF_EVAL_PASS1 = 2,    // gf_enqueue_eval: pass 1 (gf_enqueue_morph) in front of pass 2
+  GF_EVAL_IN_RUN = 4    // an iteration of slm_gf_run's loop: no k_gf_fold launches (k_gf_data reads the morphing term's kept count
+                        // from the partials, the caller's k_gf_step folds) and the render terms sit behind pass 1, not in front
+};
+
+// pass 1 of an evaluation: [zero the gradient / terms], then the morphing term's per-surfel pass (sum, count) into the spread
+// partials; stepwise, k_gf_fold puts them into terms[5], [6], what the back-propagation divides by
+static void gf_enqueue_morph(slm_gf* g, int first, int n, const GfDims& d, hipStream_t st, int what) {
+  GfSlot* slots = g->dev + first;
+  if (what & GF_EVAL_ZERO) hipLaunchKernelGGL(k_gf_zero, dim3(32, n), dim3(256), 0, st, slots);
+  if (!g->cfg.use_bn_morph) return;
+  launch_gf_morph(slots, n, d.maxN, st);
+  if (!(what & GF_EVAL_IN_RUN)) hipLaunchKernelGGL(k_gf_fold, dim3(1, n), dim3(64), 0, st, slots, (int)GF_FOLD_MORPH);
 }
 
-// pass 2: point-plane (+ morphing back-propagation, needs the GLOBAL kept count in terms[6]) and
-// the node terms (on rank 0 only when the surfels are sharded: the caller sums the partials)
-static void gf_enqueue_losses(slm_gf* g, GfSlot* slots, int n, int maxN, int maxReg, hipStream_t st, bool fold = true, bool morph_in_partials = false) {
+// One evaluation of the slots [first, first + n), launches only; what = GfEval bits.  Pass 2 is point-plane (+ morphing
+// back-propagation, which needs the GLOBAL kept count) and the node terms (on rank 0 only when the surfels are sharded: the
+// caller sums the partials), the node terms as the tail blocks of k_gf_data.
+//   stepwise:        the render terms, [pass 1 with its fold], pass 2, k_gf_fold -- gradient and terms are complete behind it
+//   GF_EVAL_IN_RUN:  [pass 1 without the fold], the render terms, pass 2; no fold
+static void gf_enqueue_eval(slm_gf* g, int first, int n, const GfDims& d, hipStream_t st, int what) {
   const slm_gf_config& c = g->cfg;
-  const int use_pp = (c.use_data || c.seg_mode) ? 1 : 0;   // either flag enables the term (deform_mesh.py:81)
-  const bool data = (use_pp || c.use_bn_morph || c.corr_mode) && maxN > 0;
-  const bool reg = g->rank == 0 && (c.use_arap || c.use_rot || c.use_face) && maxReg > 0;
-  const GfRegArgs ra = {c.use_arap, c.use_rot, c.use_face, 0, c.w_arap, c.w_rot, c.w_face};
-  const int nd = (maxN + 255) / 256, nr = reg ? (maxReg + 255) / 256 : 0;
-  const int first = (int)(slots - g->dev);   // (slots of the launch: first .. first + n - 1)
+  GfSlot* slots = g->dev + first;
+  const bool in_run = (what & GF_EVAL_IN_RUN) != 0;
+  if (!in_run) gf_enqueue_render(g, first, n, st);   // (nothing without slm_gf_bind_render_loss)
+  if (what & GF_EVAL_PASS1) gf_enqueue_morph(g, first, n, d, st, what);
+  if (in_run) gf_enqueue_render(g, first, n, st);
+  GfDataArgs A{};
+  A.use_pp = (c.use_data || c.seg_mode) ? 1 : 0;   // either flag enables the term (deform_mesh.py:81)
+  const bool data = (A.use_pp || c.use_bn_morph || c.corr_mode) && d.maxN > 0;
+  const bool reg = g->rank == 0 && (c.use_arap || c.use_rot || c.use_face) && d.maxReg > 0;
+  const int nr = reg ? (d.maxReg + 255) / 256 : 0;
+  A.n_data_blocks = (d.maxN + 255) / 256;
+  A.lam = c.w_data;
+  A.ra = {c.use_arap, c.use_rot, c.use_face, 0, c.w_arap, c.w_rot, c.w_face};
   bool pg = false;
   for (int k = first; k < first + n; ++k) pg = pg || g->pgrad_host[k] != nullptr;
-  if (data || (pg && maxN > 0)) {
-    // the node terms ride on this launch as its tail blocks
-    const bool extra = c.seg_mode || c.use_bn_morph || c.corr_mode || c.pp_max > 0.0 || pg;
-    if (extra) {
-      SLM_K_DISPATCH(g->batch_K, hipLaunchKernelGGL((k_gf_data<KK, true>), dim3(nd + nr, n), dim3(256), 0, st, slots, use_pp, c.w_data,
-                                                   c.seg_mode, c.seg_mode ? 0.0 : c.pp_max, c.use_bn_morph ? (morph_in_partials ? 2 : 1) : 0, c.w_bn_morph, c.corr_mode, c.w_corr,
-                                                   nd, ra, pg ? g->pgrad + first : nullptr));
+  if (data || (pg && d.maxN > 0)) {
+    const dim3 grid(A.n_data_blocks + nr, n);
+    if (c.seg_mode || c.use_bn_morph || c.corr_mode || c.pp_max > 0.0 || pg) {
+      A.seg_mode = c.seg_mode;
+      A.pp_max = c.seg_mode ? 0.0 : c.pp_max;
+      A.use_morph = c.use_bn_morph ? (in_run ? 2 : 1) : 0;
+      A.w_morph = c.w_bn_morph;
+      A.corr_mode = c.corr_mode;
+      A.lam_c = c.w_corr;
+      A.pgrad = pg ? g->pgrad + first : nullptr;
+      SLM_K_DISPATCH(g->batch_K, hipLaunchKernelGGL((k_gf_data<KK, true>), grid, dim3(256), 0, st, slots, A));
     } else {
-      SLM_K_DISPATCH(g->batch_K, hipLaunchKernelGGL((k_gf_data<KK, false>), dim3(nd + nr, n), dim3(256), 0, st, slots, use_pp, c.w_data,
-                                                   0, 0.0, 0, 0.0, 0, 0.0, nd, ra, nullptr));
+      SLM_K_DISPATCH(g->batch_K, hipLaunchKernelGGL((k_gf_data<KK, false>), grid, dim3(256), 0, st, slots, A));
     }
   } else if (reg) {
-    hipLaunchKernelGGL(k_gf_reg, dim3(nr, n), dim3(256), 0, st, slots, ra);
+    hipLaunchKernelGGL(k_gf_reg, dim3(nr, n), dim3(256), 0, st, slots, A.ra);
   }
-  if (fold) hipLaunchKernelGGL(k_gf_fold, dim3(1, n), dim3(64), 0, st, slots, 1);   // (else the caller's k_gf_step folds)
-}
-
-static void gf_enqueue_eval(slm_gf* g, GfSlot* slots, int n, int maxN, int maxReg, hipStream_t st, bool fold = true) {
-  gf_enqueue_morph(g, slots, n, maxN, st);
-  gf_enqueue_losses(g, slots, n, maxN, maxReg, st, fold);
+  if (!in_run) hipLaunchKernelGGL(k_gf_fold, dim3(1, n), dim3(64), 0, st, slots, (int)GF_FOLD_DATA);
 }
 
 template <typename RT>
@@ -867,8 +965,8 @@ int slm_gf_destroy(slm_gf* g) {
 }
 
 int slm_gf_bind_frame(slm_gf* g, int32_t slot, const slm_gf_frame* fr, void* stream) {
-  if (!g || !fr) return fail(SLM_ERR_INVALID, "slm_gf_bind_frame: null argument");
-  if (slot < 0 || slot >= (int)g->host.size()) return fail(SLM_ERR_INVALID, "slm_gf_bind_frame: bad slot");
+  GfSlot* sp = nullptr;
+  if (const int rc = gf_slot("slm_gf_bind_frame", GF_TEXTS_BIND, g, fr != nullptr, slot, 1, false, &sp)) return rc;
   const slm_frame& f = fr->base;
   if (f.K < 1 || f.K > 8) return fail(SLM_ERR_UNSUPPORTED, "slm_gf_bind_frame: num_neighbors must be in 1..8");
   if (f.K_ED < 1 || f.K_ED > SLM_MAX_KED || f.N < 0 || f.J < 1 || f.H < 4 || f.W < 4)
@@ -880,7 +978,7 @@ int slm_gf_bind_frame(slm_gf* g, int32_t slot, const slm_gf_frame* fr, void* str
   if (f.N > 0 && f.J < f.K)   // (the reference's top-k of K among J nodes raises)
     return fail(SLM_ERR_INVALID, "slm_gf_bind_frame: fewer nodes (J) than num_neighbors: sf_knn_idx cannot hold K distinct ids");
   hipStream_t st = (hipStream_t)stream;
-  GfSlot& s = g->host[slot];
+  GfSlot& s = *sp;
   const size_t n = (size_t)(f.J + 1) * 7;
   const size_t n_dv = 4 * n + SLM_GF_NTERMS + GF_PART_DOUBLES;   // ... | terms | spread block partials
   HIPCHK(grow(s.dv, g->cap[slot], n_dv, n_dv));
@@ -894,8 +992,7 @@ int slm_gf_bind_frame(slm_gf* g, int32_t slot, const slm_gf_frame* fr, void* str
   s.sem_bound = 0;   // semantic inputs, the flow, a point gradient and the render loss belong to the frame: bind them again
   s.flow = nullptr;
   g->rterm[slot].ctx = nullptr;
-  g->pgrad_host[slot] = nullptr;
-  HIPCHK(hipMemcpyAsync(g->pgrad + slot, &g->pgrad_host[slot], sizeof(const double*), hipMemcpyHostToDevice, st));
+  if (const int rc = gf_publish_pgrad(g, slot, nullptr, st, false)) return rc;   // (waited for with the descriptor, below)
   s.shard_lo = (int32_t)((int64_t)f.N * g->rank / g->world);
   s.shard_hi = (int32_t)((int64_t)f.N * (g->rank + 1) / g->world);
   // The KNN tables as the reference's top-k makes them: distinct ids in [0, J) (k_gf_data's row pass gives every id of a
@@ -908,12 +1005,10 @@ int slm_gf_bind_frame(slm_gf* g, int32_t slot, const slm_gf_frame* fr, void* str
                        f.ed_knn_idx, g->knn_bad);
     HIPCHK(hipMemcpyAsync(&bad_host, g->knn_bad, sizeof(int), hipMemcpyDeviceToHost, st));
   }
-  HIPCHK(hipMemcpyAsync(g->dev + slot, &s, sizeof(GfSlot), hipMemcpyHostToDevice, st));
-  HIPCHK(hipStreamSynchronize(st));
+  if (const int rc = gf_upload_slot(g, slot, st)) return rc;
   if (bad_host) {   // refused: the slot stays unbound, on the device too
     s.bound = 0;
-    HIPCHK(hipMemcpyAsync(g->dev + slot, &s, sizeof(GfSlot), hipMemcpyHostToDevice, st));
-    HIPCHK(hipStreamSynchronize(st));
+    if (const int rc = gf_upload_slot(g, slot, st)) return rc;
     return fail(SLM_ERR_INVALID, "slm_gf_bind_frame: a KNN index (sf_knn_idx or ed_knn_idx) lies outside [0, J) or a "
                                     "surfel's row of sf_knn_idx repeats an id");
   }
@@ -924,10 +1019,9 @@ int slm_gf_bind_frame(slm_gf* g, int32_t slot, const slm_gf_frame* fr, void* str
 
 int slm_gf_bind_semantic(slm_gf* g, int32_t slot, const slm_gf_semantic* sem, int32_t* edge_counts_host,
                          void* stream) {
-  if (!g || !sem) return fail(SLM_ERR_INVALID, "slm_gf_bind_semantic: null argument");
-  if (slot < 0 || slot >= (int)g->host.size()) return fail(SLM_ERR_INVALID, "slm_gf_bind_semantic: bad slot");
-  GfSlot& s = g->host[slot];
-  if (!s.bound) return fail(SLM_ERR_UNBOUND, "slm_gf_bind_semantic: slm_gf_bind_frame first");
+  GfSlot* sp = nullptr;
+  if (const int rc = gf_slot("slm_gf_bind_semantic", GF_TEXTS_BIND, g, sem != nullptr, slot, 1, true, &sp)) return rc;
+  GfSlot& s = *sp;
   if (sem->num_classes < 1 || sem->num_classes > SLM_MAX_CLASSES)
     return fail(SLM_ERR_UNSUPPORTED, "slm_gf_bind_semantic: num_classes must be 1..4");
   const slm_frame& f = s.f.base;
@@ -948,16 +1042,13 @@ int slm_gf_bind_semantic(slm_gf* g, int32_t slot, const slm_gf_semantic* sem, in
   s.sem_bound = 1;
   if (edge_counts_host)
     for (int c = 0; c < sem->num_classes; ++c) edge_counts_host[c] = s.edge_off[c + 1] - s.edge_off[c];
-  HIPCHK(hipMemcpyAsync(g->dev + slot, &s, sizeof(GfSlot), hipMemcpyHostToDevice, st));
-  HIPCHK(hipStreamSynchronize(st));
-  return SLM_OK;
+  return gf_upload_slot(g, slot, st);
 }
 
 int slm_gf_bind_flow(slm_gf* g, int32_t slot, const float* flow, void* stream) {
-  if (!g || !flow) return fail(SLM_ERR_INVALID, "slm_gf_bind_flow: null argument");
-  if (slot < 0 || slot >= (int)g->host.size()) return fail(SLM_ERR_INVALID, "slm_gf_bind_flow: bad slot");
-  GfSlot& s = g->host[slot];
-  if (!s.bound) return fail(SLM_ERR_UNBOUND, "slm_gf_bind_flow: slm_gf_bind_frame first");
+  GfSlot* sp = nullptr;
+  if (const int rc = gf_slot("slm_gf_bind_flow", GF_TEXTS_BIND, g, flow != nullptr, slot, 1, true, &sp)) return rc;
+  GfSlot& s = *sp;
   hipStream_t st = (hipStream_t)stream;
   s.flow = flow;
   // the pointer alone: the device copy of the slot also holds the optimiser's step count, which the host copy does not
@@ -968,29 +1059,21 @@ int slm_gf_bind_flow(slm_gf* g, int32_t slot, const float* flow, void* stream) {
 }
 
 int slm_gf_bind_point_grad(slm_gf* g, int32_t slot, const double* grad, void* stream) {
-  if (!g) return fail(SLM_ERR_INVALID, "slm_gf_bind_point_grad: null argument");
-  if (slot < 0 || slot >= (int)g->host.size()) return fail(SLM_ERR_INVALID, "slm_gf_bind_point_grad: bad slot");
-  if (!g->host[slot].bound) return fail(SLM_ERR_UNBOUND, "slm_gf_bind_point_grad: slm_gf_bind_frame first");
+  if (const int rc = gf_slot("slm_gf_bind_point_grad", GF_TEXTS_BIND, g, true, slot, 1, true, nullptr)) return rc;
   if (g->rterm[slot].ctx)
     return fail(SLM_ERR_INVALID, "slm_gf_bind_point_grad: the render loss is bound to the slot (slm_gf_bind_render_loss), "
                                     "which owns its point gradient: clear it first");
-  hipStream_t st = (hipStream_t)stream;
-  g->pgrad_host[slot] = grad;
-  HIPCHK(hipMemcpyAsync(g->pgrad + slot, &g->pgrad_host[slot], sizeof(const double*), hipMemcpyHostToDevice, st));
-  HIPCHK(hipStreamSynchronize(st));
-  return SLM_OK;
+  return gf_publish_pgrad(g, slot, grad, (hipStream_t)stream);
 }
 
 int slm_gf_bind_render_loss(slm_gf* g, int32_t slot, slm_render* r, const slm_render_params* p, const float* radii,
                             const float* colors, int32_t color_stride, const float* target_chw, double weight,
                             int64_t entry_limit, void* stream) {
   const char* who = "slm_gf_bind_render_loss";
-  if (!g) return fail(SLM_ERR_INVALID, "slm_gf_bind_render_loss: null argument");
-  if (slot < 0 || slot >= (int)g->host.size()) return fail(SLM_ERR_INVALID, "slm_gf_bind_render_loss: bad slot");
+  if (const int rc = gf_slot(who, GF_TEXTS_BIND, g, true, slot, 1, false, nullptr)) return rc;
   hipStream_t st = (hipStream_t)stream;
   if (!r) return gf_clear_render(g, slot, st);
-  if (!p || !target_chw) return fail(SLM_ERR_INVALID, "slm_gf_bind_render_loss: null argument");
-  if (!g->host[slot].bound) return fail(SLM_ERR_UNBOUND, "slm_gf_bind_render_loss: slm_gf_bind_frame first");
+  if (const int rc = gf_slot(who, GF_TEXTS_BIND, g, p && target_chw, slot, 1, true, nullptr)) return rc;
   if (g->world > 1)
     return fail(SLM_ERR_UNSUPPORTED, "slm_gf_bind_render_loss: surfels are sharded; the render loss needs every surfel of "
                                         "the frame on one device");
@@ -1029,18 +1112,14 @@ int slm_gf_bind_render_loss(slm_gf* g, int32_t slot, slm_render* r, const slm_re
   t.target = target_chw;
   t.weight = weight;
   t.limit = limit;
-  g->pgrad_host[slot] = t.pgrad;
-  HIPCHK(hipMemcpyAsync(g->pgrad + slot, &g->pgrad_host[slot], sizeof(const double*), hipMemcpyHostToDevice, st));
-  HIPCHK(hipStreamSynchronize(st));
+  if (const int rc = gf_publish_pgrad(g, slot, t.pgrad, st)) return rc;
   t.ctx = r;
   return SLM_OK;
 }
 
 static int gf_render_term(slm_gf* g, int32_t slot, const char* who, const GfRenderTerm** t) {
-  const std::string w(who);
-  if (!g) return fail(SLM_ERR_INVALID, w + ": null argument");
-  if (slot < 0 || slot >= (int)g->host.size()) return fail(SLM_ERR_INVALID, w + ": bad slot");
-  if (!g->rterm[slot].ctx) return fail(SLM_ERR_UNBOUND, w + ": slm_gf_bind_render_loss first");
+  if (const int rc = gf_slot(who, GF_TEXTS_BIND, g, true, slot, 1, false, nullptr)) return rc;
+  if (!g->rterm[slot].ctx) return fail(SLM_ERR_UNBOUND, std::string(who) + ": slm_gf_bind_render_loss first");
   *t = &g->rterm[slot];
   return SLM_OK;
 }
@@ -1074,9 +1153,9 @@ int slm_gf_render_loss_read(slm_gf* g, int32_t slot, float* image, double* grad_
 
 int slm_gf_get_edge_points(slm_gf* g, int32_t slot, int32_t class_id, float* xy_out, int32_t max_points,
                            void* stream) {
-  if (!g || slot < 0 || slot >= (int)g->host.size() || !xy_out)
-    return fail(SLM_ERR_INVALID, "slm_gf_get_edge_points: bad argument");
-  const GfSlot& s = g->host[slot];
+  GfSlot* sp = nullptr;
+  if (const int rc = gf_slot("slm_gf_get_edge_points", GF_TEXTS_EDGE, g, xy_out != nullptr, slot, 1, false, &sp)) return rc;
+  const GfSlot& s = *sp;
   if (!s.bound || !s.sem_bound) return fail(SLM_ERR_UNBOUND, "slm_gf_get_edge_points: no semantic inputs bound");
   if (class_id < 0 || class_id >= s.sem.num_classes)
     return fail(SLM_ERR_INVALID, "slm_gf_get_edge_points: bad class");
@@ -1085,29 +1164,6 @@ int slm_gf_get_edge_points(slm_gf* g, int32_t slot, int32_t class_id, float* xy_
   if (n > 0)
     HIPCHK(hipMemcpyAsync(xy_out, s.edge_xy + s.edge_off[class_id], sizeof(float2) * n, hipMemcpyDeviceToDevice,
                          (hipStream_t)stream));
-  return SLM_OK;
-}
-
-static int gf_dims(slm_gf* g, int first, int n, int* maxN, int* maxReg, int* maxP) {
-  if (!g || first < 0 || n < 1 || first + n > (int)g->host.size())
-    return fail(SLM_ERR_INVALID, "slm_gf: slot range out of bounds");
-  *maxN = *maxReg = *maxP = 0;
-  for (int i = first; i < first + n; ++i) {
-    const GfSlot& s = g->host[i];
-    if (!s.bound) return fail(SLM_ERR_UNBOUND, "slm_gf: slot used before slm_gf_bind_frame");
-    if ((g->cfg.seg_mode || g->cfg.use_bn_morph) && !s.sem_bound)
-      return fail(SLM_ERR_UNBOUND, "slm_gf: semantic terms enabled but slm_gf_bind_semantic was not called");
-    if (g->cfg.corr_mode && !s.flow)
-      return fail(SLM_ERR_UNBOUND, "slm_gf: corr_mode set but slm_gf_bind_flow was not called");
-    if (s.f.base.K != g->host[first].f.base.K)
-      return fail(SLM_ERR_UNSUPPORTED, "slm_gf: the frames of one batch must have the same num_neighbors");
-    *maxN = std::max(*maxN, s.f.base.N);
-    int reg = std::max(s.f.base.J * s.f.base.K_ED, s.f.base.J + 1);
-    if (g->cfg.use_face) reg = std::max(reg, s.f.n_triangles);
-    *maxReg = std::max(*maxReg, reg);
-    *maxP = std::max(*maxP, (s.f.base.J + 1) * 7);
-  }
-  g->batch_K = g->host[first].f.base.K;
   return SLM_OK;
 }
 
@@ -1126,64 +1182,56 @@ int slm_gf_set_shard(slm_gf* g, int32_t rank, int32_t world) {
 }
 
 int slm_gf_eval_morph(slm_gf* g, int32_t n_frames, void* stream) {
-  int maxN, maxReg, maxP;
-  int rc = gf_dims(g, 0, n_frames, &maxN, &maxReg, &maxP);
-  if (rc) return rc;
-  gf_enqueue_morph(g, g->dev, n_frames, maxN, (hipStream_t)stream);
+  GfDims d;
+  if (const int rc = gf_dims(g, 0, n_frames, &d)) return rc;
+  gf_enqueue_morph(g, 0, n_frames, d, (hipStream_t)stream, GF_EVAL_ZERO);
   HIPCHK(hipGetLastError());
   return SLM_OK;
 }
 
 int slm_gf_eval_losses(slm_gf* g, int32_t n_frames, void* stream) {
-  int maxN, maxReg, maxP;
-  int rc = gf_dims(g, 0, n_frames, &maxN, &maxReg, &maxP);
-  if (rc) return rc;
-  gf_enqueue_render(g, 0, n_frames, (hipStream_t)stream);
-  gf_enqueue_losses(g, g->dev, n_frames, maxN, maxReg, (hipStream_t)stream);
+  GfDims d;
+  if (const int rc = gf_dims(g, 0, n_frames, &d)) return rc;
+  gf_enqueue_eval(g, 0, n_frames, d, (hipStream_t)stream, 0);
   HIPCHK(hipGetLastError());
   return SLM_OK;
 }
 
 int slm_gf_step(slm_gf* g, int32_t n_frames, void* stream) {
-  int maxN, maxReg, maxP;
-  int rc = gf_dims(g, 0, n_frames, &maxN, &maxReg, &maxP);
-  if (rc) return rc;
+  GfDims d;
+  if (const int rc = gf_dims(g, 0, n_frames, &d)) return rc;
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(k_gf_step, dim3((maxP + 255) / 256, n_frames), dim3(256), 0, st, g->dev, g->cfg.optimizer,
-                     g->cfg.lr, 1, g->cfg.use_bn_morph, g->cfg.w_bn_morph, 0, 0);
+  gf_launch_step(g, 0, n_frames, d, 1, 0, 0, st);
   hipLaunchKernelGGL(k_gf_advance, dim3(n_frames), dim3(64), 0, st, g->dev, 1);
   HIPCHK(hipGetLastError());
   return SLM_OK;
 }
 
 int slm_gf_get_partial(slm_gf* g, int32_t slot, double* out, void* stream) {
-  int maxN, maxReg, maxP;
-  int rc = gf_dims(g, slot, 1, &maxN, &maxReg, &maxP);
-  if (rc) return rc;
+  GfDims d;
+  if (const int rc = gf_dims(g, slot, 1, &d)) return rc;
   if (!out) return fail(SLM_ERR_INVALID, "slm_gf_get_partial: null output");
   const GfSlot& s = g->host[slot];
   hipStream_t st = (hipStream_t)stream;
-  HIPCHK(hipMemcpyAsync(out, s.grad, sizeof(double) * maxP, hipMemcpyDeviceToDevice, st));
-  HIPCHK(hipMemcpyAsync(out + maxP, s.terms, sizeof(double) * SLM_GF_NTERMS, hipMemcpyDeviceToDevice, st));
+  HIPCHK(hipMemcpyAsync(out, s.grad, sizeof(double) * d.maxP, hipMemcpyDeviceToDevice, st));
+  HIPCHK(hipMemcpyAsync(out + d.maxP, s.terms, sizeof(double) * SLM_GF_NTERMS, hipMemcpyDeviceToDevice, st));
   return SLM_OK;
 }
 
 int slm_gf_set_partial(slm_gf* g, int32_t slot, const double* in, void* stream) {
-  int maxN, maxReg, maxP;
-  int rc = gf_dims(g, slot, 1, &maxN, &maxReg, &maxP);
-  if (rc) return rc;
+  GfDims d;
+  if (const int rc = gf_dims(g, slot, 1, &d)) return rc;
   if (!in) return fail(SLM_ERR_INVALID, "slm_gf_set_partial: null input");
   const GfSlot& s = g->host[slot];
   hipStream_t st = (hipStream_t)stream;
-  HIPCHK(hipMemcpyAsync(s.grad, in, sizeof(double) * maxP, hipMemcpyDeviceToDevice, st));
-  HIPCHK(hipMemcpyAsync(s.terms, in + maxP, sizeof(double) * SLM_GF_NTERMS, hipMemcpyDeviceToDevice, st));
+  HIPCHK(hipMemcpyAsync(s.grad, in, sizeof(double) * d.maxP, hipMemcpyDeviceToDevice, st));
+  HIPCHK(hipMemcpyAsync(s.terms, in + d.maxP, sizeof(double) * SLM_GF_NTERMS, hipMemcpyDeviceToDevice, st));
   return SLM_OK;
 }
 
 int slm_gf_run(slm_gf* g, int32_t n_frames, void* stream) {
-  int maxN, maxReg, maxP;
-  int rc = gf_dims(g, 0, n_frames, &maxN, &maxReg, &maxP);
-  if (rc) return rc;
+  GfDims d;
+  if (const int rc = gf_dims(g, 0, n_frames, &d)) return rc;
   if (g->world > 1)
     return fail(SLM_ERR_UNSUPPORTED,
                    "slm_gf_run: surfels are sharded; drive slm_gf_eval_morph / eval_losses / step with an "
@@ -1194,16 +1242,11 @@ int slm_gf_run(slm_gf* g, int32_t n_frames, void* stream) {
   // runs in front of the first.  With the morphing term THREE: k_gf_morph in front -- its kept count stays in the spread
   // partials, k_gf_data sums the 64 copies itself and the step folds them with the rest (k_gf_zero + k_gf_morph + k_gf_fold +
   // k_gf_data + k_gf_step before: five launches of 5-85 us at configs[4]'s size).  The step counter advances once, behind the loop.
-  const bool morph = g->cfg.use_bn_morph != 0;
   const int n_it = g->cfg.num_iterations;
   for (int it = 0; it < n_it; ++it) {
-    if (it == 0) hipLaunchKernelGGL(k_gf_zero, dim3(32, n_frames), dim3(256), 0, st, g->dev);
-    if (morph) launch_gf_morph(g->dev, n_frames, maxN, st);
-    gf_enqueue_render(g, 0, n_frames, st);   // (nothing without slm_gf_bind_render_loss)
-    gf_enqueue_losses(g, g->dev, n_frames, maxN, maxReg, st, false, morph);   // (the step folds)
-    const int fold = (it + 1 < n_it ? 7 : 3) | (morph ? 8 : 0);
-    hipLaunchKernelGGL(k_gf_step, dim3((maxP + 255) / 256, n_frames), dim3(256), 0, st, g->dev,
-                       g->cfg.optimizer, g->cfg.lr, 1, g->cfg.use_bn_morph, g->cfg.w_bn_morph, fold, it);
+    gf_enqueue_eval(g, 0, n_frames, d, st, GF_EVAL_PASS1 | GF_EVAL_IN_RUN | (it == 0 ? GF_EVAL_ZERO : 0));
+    const int fold = GF_STEP_FOLD | GF_STEP_OWN | (it + 1 < n_it ? GF_STEP_REZERO : 0) | (g->cfg.use_bn_morph ? GF_STEP_MORPH : 0);
+    gf_launch_step(g, 0, n_frames, d, 1, fold, it, st);
   }
   if (n_it > 0) hipLaunchKernelGGL(k_gf_advance, dim3(n_frames), dim3(64), 0, st, g->dev, n_it);
   HIPCHK(hipGetLastError());
@@ -1211,28 +1254,24 @@ int slm_gf_run(slm_gf* g, int32_t n_frames, void* stream) {
 }
 
 int slm_gf_get_deform(slm_gf* g, int32_t slot, double* out, void* stream) {
-  int maxN, maxReg, maxP;
-  int rc = gf_dims(g, slot, 1, &maxN, &maxReg, &maxP);
-  if (rc) return rc;
+  GfDims d;
+  if (const int rc = gf_dims(g, slot, 1, &d)) return rc;
   if (!out) return fail(SLM_ERR_INVALID, "slm_gf_get_deform: null output");
-  HIPCHK(hipMemcpyAsync(out, g->host[slot].dv, sizeof(double) * maxP, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  HIPCHK(hipMemcpyAsync(out, g->host[slot].dv, sizeof(double) * d.maxP, hipMemcpyDeviceToDevice, (hipStream_t)stream));
   return SLM_OK;
 }
 
 int slm_gf_loss_grad(slm_gf* g, int32_t slot, const double* dv, double* terms, double* grad, void* stream) {
-  int maxN, maxReg, maxP;
-  int rc = gf_dims(g, slot, 1, &maxN, &maxReg, &maxP);
-  if (rc) return rc;
+  GfDims d;
+  if (const int rc = gf_dims(g, slot, 1, &d)) return rc;
   if (!dv) return fail(SLM_ERR_INVALID, "slm_gf_loss_grad: null dv");
   hipStream_t st = (hipStream_t)stream;
   const GfSlot& s = g->host[slot];
-  HIPCHK(hipMemcpyAsync(s.dv, dv, sizeof(double) * maxP, hipMemcpyDeviceToDevice, st));
-  gf_enqueue_render(g, slot, 1, st);
-  gf_enqueue_eval(g, g->dev + slot, 1, maxN, maxReg, st);
-  hipLaunchKernelGGL(k_gf_step, dim3((maxP + 255) / 256, 1), dim3(256), 0, st, g->dev + slot, g->cfg.optimizer,
-                     g->cfg.lr, 0, g->cfg.use_bn_morph, g->cfg.w_bn_morph, 0, 0);
+  HIPCHK(hipMemcpyAsync(s.dv, dv, sizeof(double) * d.maxP, hipMemcpyDeviceToDevice, st));
+  gf_enqueue_eval(g, slot, 1, d, st, GF_EVAL_ZERO | GF_EVAL_PASS1);
+  gf_launch_step(g, slot, 1, d, 0, 0, 0, st);   // (no step: the global row's division and the morphing term's mean)
   if (terms) HIPCHK(hipMemcpyAsync(terms, s.terms, sizeof(double) * SLM_GF_NTERMS, hipMemcpyDeviceToDevice, st));
-  if (grad) HIPCHK(hipMemcpyAsync(grad, s.grad, sizeof(double) * maxP, hipMemcpyDeviceToDevice, st));
+  if (grad) HIPCHK(hipMemcpyAsync(grad, s.grad, sizeof(double) * d.maxP, hipMemcpyDeviceToDevice, st));
   HIPCHK(hipGetLastError());
   return SLM_OK;
 }
@@ -1252,9 +1291,9 @@ int slm_apply_update_gf_f64(int32_t N, int32_t J, int32_t K, double* sf_points, 
 }  // extern "C"
 
 int gf_render_slot(slm_gf* g, int32_t slot, GfSlot** dev, int32_t* n_surfels, const char* who) {
-  if (!g || slot < 0 || slot >= (int)g->host.size()) return fail(SLM_ERR_INVALID, std::string(who) + ": bad slot");
-  if (!g->host[slot].bound) return fail(SLM_ERR_UNBOUND, std::string(who) + ": slm_gf_bind_frame first");
+  GfSlot* sp = nullptr;
+  if (const int rc = gf_slot(who, GF_TEXTS_RENDER, g, true, slot, 1, true, &sp)) return rc;
   *dev = g->dev + slot;
-  *n_surfels = g->host[slot].f.base.N;
+  *n_surfels = sp->f.base.N;
   return SLM_OK;
 }

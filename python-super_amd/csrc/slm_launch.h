@@ -11,7 +11,7 @@ void launch_data_grad_pairs(const FrameDev*, int, int, int, double, hipStream_t)
 void launch_data_loss(const FrameDev*, int, int, int, double, int, hipStream_t);
 void launch_data_resid(const FrameDev*, int, int, int, double, double*, uint8_t*, int32_t*, hipStream_t);
 
-// slm_data_v1.hip
+// slm_data_k4.hip
 void launch_data_gram(const FrameDev*, int, int, double, int, hipStream_t, const int* reuse = nullptr);
 void launch_begin_and_gram(const FrameDev*, int, int, double, hipStream_t, const int* reuse, int dag_cut);
 void launch_data_eval(const FrameDev*, int, int, double, int mode, hipStream_t, const int* reuse = nullptr);

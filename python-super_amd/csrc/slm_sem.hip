@@ -99,17 +99,17 @@ __global__ void __launch_bounds__(256) k_gf_morph(GfSlot* __restrict__ slots) {
   double my_x = 0.0, my_y = 0.0;
   if (i < f.N) {
     if (i >= s.shard_lo && i < s.shard_hi && (!s.f.sf_stable || s.f.sf_stable[i])) {
-      struct { d3 P; } k;
+      d3 P;
       if (f.K == SLM_K) {   // (the default: the instantiation the other kernels use, operation for operation)
-        GfSkin k4;
-        gf_skin(s, i, k4);
-        k.P = k4.P;
+        GfSkin<SLM_K> k4;
+        gf_skin<SLM_K>(s, i, k4);
+        P = k4.P;
       } else {
-        k.P = gf_skin_pos(s, i);
+        P = gf_skin_pos(s, i);
       }
       const int H = f.H, W = f.W, C = s.sem.num_classes;
-      const double Ze = k.P.z + 1e-8;
-      const double x = k.P.x * (double)f.fx / Ze + (double)f.cx, y = k.P.y * (double)f.fy / Ze + (double)f.cy;
+      const double Ze = P.z + 1e-8;
+      const double x = P.x * (double)f.fx / Ze + (double)f.cx, y = P.y * (double)f.fy / Ze + (double)f.cy;
       // F.grid_sample(seg_conf, grid) with bilinear taps, zero padding, align_corners=False
       const double gx = x / (double)W * 2.0 - 1.0, gy = y / (double)H * 2.0 - 1.0;
       const double ix = ((gx + 1.0) * (double)W - 1.0) / 2.0, iy = ((gy + 1.0) * (double)H - 1.0) / 2.0;
@@ -228,10 +228,10 @@ __global__ void __launch_bounds__(256) k_gf_morph(GfSlot* __restrict__ slots) {
     s.morph_g[i] = g;
   }
   const double a = block_sum(li_sum, sm), b = block_sum(kept, sm);
-  if (threadIdx.x == 0 && b != 0.0) {   // (spread block partials, slm_gf.h: entries 14 / 15; k_gf_fold sums them into terms[5] / [6])
-    double* part = s.terms.get() + SLM_GF_NTERMS + 16 * (blockIdx.x % GF_NCOPY);
-    atomic_add_f64(part + 14, a);
-    atomic_add_f64(part + 15, b);
+  if (threadIdx.x == 0 && b != 0.0) {   // (spread block partials, slm_gf.h; a fold sums them into terms[5] / [6])
+    double* part = gf_part(s, blockIdx.x % GF_NCOPY);
+    atomic_add_f64(part + GFP_MORPH_SUM, a);
+    atomic_add_f64(part + GFP_MORPH_KEPT, b);
   }
 }
 

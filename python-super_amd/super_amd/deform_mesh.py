@@ -74,21 +74,12 @@ class GraphFit:
                     "super_amd.GraphFit: opt.render_loss needs GraphFit(opt, native_render_loss=True): its gradient is "
                     "the exact derivative of super_amd.renderer's blend, not Pulsar's own backward, which is unpinned "
                     "(pytorch3d has no ROCm build)")
-            if getattr(opt, "renderer", None) != "pulsar":
-                raise NotImplementedError("super_amd.GraphFit: opt.render_loss renders with opt.renderer; "
-                                          f"only 'pulsar' is implemented (got {getattr(opt, 'renderer', None)!r})")
-            if shard_surfels or world is not None:
-                raise NotImplementedError("super_amd.GraphFit: opt.render_loss on surfel-sharded frames")
+            self._refuse_unrenderable("opt.render_loss", shard_surfels or world is not None)
         self.render_loss_weight = float(getattr(opt, "render_loss_weight", 1e-4))
         self.last_render_kept = None
         self.match_render = bool(getattr(opt, "sf_corr", False) and getattr(opt, "sf_corr_match_renderimg", False))
         if self.match_render:
-            # the reference renders with models.renderer, which InitNets only builds for opt.renderer == "pulsar"
-            if getattr(opt, "renderer", None) != "pulsar":
-                raise NotImplementedError("super_amd.GraphFit: opt.sf_corr_match_renderimg renders with opt.renderer; "
-                                          f"only 'pulsar' is implemented (got {getattr(opt, 'renderer', None)!r})")
-            if shard_surfels or world is not None:
-                raise NotImplementedError("super_amd.GraphFit: opt.sf_corr_match_renderimg on surfel-sharded frames")
+            self._refuse_unrenderable("opt.sf_corr_match_renderimg", shard_surfels or world is not None)
         self.render_in_run = bool(render_in_run)
         if self.render_in_run and self.match_render:
             raise NotImplementedError("super_amd.GraphFit: render_in_run with opt.sf_corr_match_renderimg: the flow network "
@@ -103,7 +94,6 @@ class GraphFit:
         # (slm_gf_render_radii), instead of opt.renderer_rad; the radii are not optimised (no radius gradient is asked for)
         self.surfel_radii = bool(getattr(opt, "renderer_surfel_radii", False))
         self.radii_scale = float(getattr(opt, "renderer_radii_scale", 1.0))
-        self._render_radii = None
         self.valid_margin = 1
         self.optim = opt.optimizer
         self.Niter = opt.num_optimize_iterations
@@ -162,6 +152,16 @@ class GraphFit:
         except Exception:
             pass
 
+    def _refuse_unrenderable(self, flag, sharded):
+        """The refusals of a flag that renders the deformed model: the reference renders with models.renderer, which
+        InitNets only builds for opt.renderer == "pulsar", and a render needs every surfel of the frame on one device."""
+        renderer = getattr(self.opt, "renderer", None)
+        if renderer != "pulsar":
+            raise NotImplementedError(f"super_amd.GraphFit: {flag} renders with opt.renderer; "
+                                      f"only 'pulsar' is implemented (got {renderer!r})")
+        if sharded:
+            raise NotImplementedError(f"super_amd.GraphFit: {flag} on surfel-sharded frames")
+
     def infer_flow(self, models, source_img, target_img):
         """(reference ``deform_mesh.py:19-23``) the caller's flow network; the last element of a list output."""
         flow = models.optical_flow(source_img, target_img)   # x, y
@@ -199,6 +199,7 @@ class GraphFit:
             fr.n_triangles = int(tri.shape[1])
         _lib.check(self.lib.slm_gf_bind_frame(self.h, slot, C.byref(fr), _stream_ptr(dev)),
                    "slm_gf_bind_frame")
+        self._keep[slot] = keep      # (what the slot's device pointers refer to; the binds below add to it)
         if self.semantic:
             # src.seg / src.seg_conf (deform_mesh.py:262-264), trg.seg_conf (loss.py:350),
             # inputs[("seg_conf",0)] / inputs[("seg",0)] (deform_mesh.py:136,149)
@@ -235,20 +236,13 @@ class GraphFit:
                     raise ValueError("opt.sf_corr needs models.optical_flow (or flow=...)")   # the reference asserts
                 flow = self.infer_flow(models, src.rgb, inputs[("color", 0)])
             self.flow = flow
-            fl = _as(flow, torch.float32, dev)
-            if tuple(fl.shape) != (1, 2, bf.c.H, bf.c.W):
-                raise ValueError(f"flow must be (1,2,{bf.c.H},{bf.c.W}), got {tuple(fl.shape)}")
-            keep.append(fl)
-            _lib.check(self.lib.slm_gf_bind_flow(self.h, slot, _dev_ptr(fl), _stream_ptr(dev)), "slm_gf_bind_flow")
+            self._bind_flow(slot, flow)
         if self.surfel_radii:      # float32 by surfel row, like Pulsar's vert_rad
             radii = (src.radii.detach() * self.radii_scale).to(device=dev, dtype=torch.float32).contiguous()
             if tuple(radii.shape) != (bf.c.N,):
                 raise ValueError(f"src.radii must be ({bf.c.N},), got {tuple(src.radii.shape)}")
             keep.append(radii)
             self._slot_radii[slot] = radii
-            if slot == 0:
-                self._render_radii = radii
-        self._keep[slot] = keep
         return bf
 
     def forward(self, inputs, src, trg, models=None):
@@ -262,21 +256,26 @@ class GraphFit:
         if self.match_render:
             return self._forward_match_render(inputs, src, trg, models)
         bf = self._bind(0, inputs, src, trg, models)
-        st = _stream_ptr(bf.device)
         if self.sharded:
-            part = torch.empty((bf.J + 1) * 7 + _lib.GF_NTERMS, dtype=torch.float64, device=bf.device)
-            for _ in range(int(self.Niter)):
-                self.eval_morph()
-                if self.cfg.use_bn_morph:
-                    self.exchange_partial(part)      # global kept count before the back-propagation
-                self.eval_losses()
-                self.exchange_partial(part)          # gradient + loss terms
-                self.step()
+            self._iterate(part=torch.empty((bf.J + 1) * 7 + _lib.GF_NTERMS, dtype=torch.float64, device=bf.device))
         else:
-            _lib.check(self.lib.slm_gf_run(self.h, 1, st), "slm_gf_run")
-        out = torch.empty((bf.J + 1, 7), dtype=torch.float64, device=bf.device)
-        _lib.check(self.lib.slm_gf_get_deform(self.h, 0, _dev_ptr(out), st), "slm_gf_get_deform")
-        return out
+            _lib.check(self.lib.slm_gf_run(self.h, 1, self._st()), "slm_gf_run")
+        return self.deform_verts()
+
+    def _iterate(self, before=None, part=None):
+        """The per-iteration loop of every stepwise path: ``before()`` -- what the path binds for this iteration's
+        evaluation -- then the two passes of the evaluation and the step.  ``part``: the frame is surfel-sharded and the
+        partial sums are exchanged through this buffer behind each pass."""
+        for _ in range(int(self.Niter)):
+            if before is not None:
+                before()
+            self.eval_morph()
+            if part is not None and self.cfg.use_bn_morph:
+                self.exchange_partial(part)      # global kept count before the back-propagation
+            self.eval_losses()
+            if part is not None:
+                self.exchange_partial(part)      # gradient + loss terms
+            self.step()
 
     __call__ = forward
 
@@ -284,25 +283,20 @@ class GraphFit:
         """Binds the render loss to ``slot`` as a term of the run (slm_gf_bind_render_loss), after ``_bind`` of the same
         frame: the slot's own ``RenderContext``, ``src.colors``, the radii of ``opt.renderer_surfel_radii`` and
         ``inputs[("color",0)]`` as the target.  ``entry_limit`` 0: from the sizing render."""
-        from .renderer import DEFAULT_RAD, RenderContext, render_params
         bf = self._keep[slot][0]
-        H, W, dev = bf.c.H, bf.c.W, bf.device
-        ctx = self._slot_ctx[slot]
-        if ctx is None or ctx.H < H or ctx.W < W:
-            ctx = self._slot_ctx[slot] = RenderContext(H, W)
-        ctx.reserve(bf.c.N)          # (the frame's bind took the term, and with it the old context, off the slot)
-        ctx.last_n = 0
-        ctx.serial += 1
-        p = render_params(inputs["K"], H, W, 1.0, getattr(self.opt, "renderer_rad", DEFAULT_RAD))
-        colors = src.colors.detach().to(device=dev, dtype=torch.float32).contiguous()
+        dev = bf.device
+        # (the frame's bind took the term, and with it the old context, off the slot)
+        ctx, p = self._fresh_ctx(self._slot_ctx[slot], bf, inputs)
+        self._slot_ctx[slot] = ctx
         tgt = inputs[("color", 0)].detach()
         tgt = tgt.reshape(tgt.shape[-3:]) if tgt.dim() == 4 else tgt
         if tuple(tgt.shape) != (3, p.height, p.width):
             raise ValueError(f'inputs[("color",0)] must be (3,{p.height},{p.width}) or (1,3,{p.height},{p.width}), '
                              f"got {tuple(tgt.shape)}")
         tgt = tgt.to(device=dev, dtype=torch.float32).contiguous()
+        colors = self._colors(slot, src)
         radii = self._slot_radii[slot] if self.surfel_radii else None
-        self._keep[slot] += [colors, tgt]
+        self._keep[slot].append(tgt)
         _lib.check(self.lib.slm_gf_bind_render_loss(
             self.h, slot, ctx.h, C.byref(p), _dev_ptr(radii) if radii is not None else None, _dev_ptr(colors),
             int(colors.stride(0)), _dev_ptr(tgt), self.render_loss_weight, int(entry_limit), _stream_ptr(dev)),
@@ -360,28 +354,20 @@ class GraphFit:
         self.last_render_status = status
         if status[0] is not None:
             self.last_render_kept = status[0][1]
-        outs = []
-        for k in range(n):
-            bf = self._keep[k][0]
-            out = torch.empty((bf.J + 1, 7), dtype=torch.float64, device=bf.device)
-            _lib.check(self.lib.slm_gf_get_deform(self.h, k, _dev_ptr(out), self._st()), "slm_gf_get_deform")
-            outs.append(out)
-        return outs
+        return [self.deform_verts(k) for k in range(n)]
 
     def _forward_match_render(self, inputs, src, trg, models):
         """deform_mesh.py:286-330 with sf_corr_match_renderimg: per iteration render -> flow -> bind -> step."""
         if models is None or not hasattr(models, "optical_flow"):
             raise ValueError("opt.sf_corr needs models.optical_flow")   # the reference asserts
-        bf = self._bind(0, inputs, src, trg, models, defer_flow=True)
-        colors = src.colors.detach().to(device=bf.device, dtype=torch.float32).contiguous()   # bound once per frame
-        self._keep[0].append(colors)
-        for _ in range(int(self.Niter)):
-            img = self.render_deformed(inputs, colors)
-            self.flow = self.infer_flow(models, img, inputs[("color", 0)])
-            self._bind_flow(bf, self.flow)
-            self.eval_morph()
-            self.eval_losses()
-            self.step()
+        self._bind(0, inputs, src, trg, models, defer_flow=True)
+        colors = self._colors(0, src)        # bound once per frame
+
+        def before():
+            self.flow = self.infer_flow(models, self.render_deformed(inputs, colors), inputs[("color", 0)])
+            self._bind_flow(0, self.flow)
+
+        self._iterate(before)
         return self.deform_verts()
 
     def _forward_render_loss(self, inputs, src, trg, models):
@@ -391,17 +377,16 @@ class GraphFit:
             raise ValueError("opt.sf_corr needs models.optical_flow")   # the reference asserts
         # without sf_corr_match_renderimg the flow (sf_corr) is inferred once from src.rgb at the bind (iteration 0)
         bf = self._bind(0, inputs, src, trg, models, defer_flow=self.match_render)
-        colors = src.colors.detach().to(device=bf.device, dtype=torch.float32).contiguous()
-        self._keep[0].append(colors)
-        for _ in range(int(self.Niter)):
+        colors = self._colors(0, src)
+
+        def before():
             img, p = self._render_deformed_hwc(inputs, colors)
             if self.match_render:
                 self.flow = self.infer_flow(models, img.permute(2, 0, 1).unsqueeze(0), inputs[("color", 0)])
-                self._bind_flow(bf, self.flow)
+                self._bind_flow(0, self.flow)
             self._bind_render_grad(bf, inputs, img, p)
-            self.eval_morph()
-            self.eval_losses()
-            self.step()
+
+        self._iterate(before)
         _lib.check(self.lib.slm_gf_bind_point_grad(self.h, 0, None, _stream_ptr(bf.device)), "slm_gf_bind_point_grad")
         return self.deform_verts()
 
@@ -416,12 +401,31 @@ class GraphFit:
                    "slm_gf_bind_point_grad")
         return out
 
-    def _bind_flow(self, bf, flow):
+    def _bind_flow(self, slot, flow):
+        bf = self._keep[slot][0]
         fl = _as(flow, torch.float32, bf.device)
         if tuple(fl.shape) != (1, 2, bf.c.H, bf.c.W):
             raise ValueError(f"flow must be (1,2,{bf.c.H},{bf.c.W}), got {tuple(fl.shape)}")
-        self._keep[0].append(fl)         # read by the next evaluation
-        _lib.check(self.lib.slm_gf_bind_flow(self.h, 0, _dev_ptr(fl), _stream_ptr(bf.device)), "slm_gf_bind_flow")
+        self._keep[slot].append(fl)      # read by the next evaluation
+        _lib.check(self.lib.slm_gf_bind_flow(self.h, slot, _dev_ptr(fl), _stream_ptr(bf.device)), "slm_gf_bind_flow")
+
+    def _colors(self, slot, src):
+        """``src.colors`` as the renderer reads them, (N,3) float32 by surfel row, kept alive with the slot."""
+        colors = src.colors.detach().to(device=self._keep[slot][0].device, dtype=torch.float32).contiguous()
+        self._keep[slot].append(colors)
+        return colors
+
+    def _fresh_ctx(self, ctx, bf, inputs):
+        """(context, render parameters) for a render of the bound frame ``bf``: ``ctx`` if it holds H x W, else a new
+        ``RenderContext``, with room for the frame's surfels and marked fresh (nothing of an earlier render is reused)."""
+        from .renderer import DEFAULT_RAD, RenderContext, render_params
+        H, W = bf.c.H, bf.c.W
+        if ctx is None or ctx.H < H or ctx.W < W:
+            ctx = RenderContext(H, W)
+        ctx.reserve(bf.c.N)
+        ctx.last_n = 0
+        ctx.serial += 1
+        return ctx, render_params(inputs["K"], H, W, 1.0, getattr(self.opt, "renderer_rad", DEFAULT_RAD))
 
     def render_deformed(self, inputs, colors):
         """The current deformed stable surfels of the bound frame (deform_source's new_data, global row included)
@@ -433,19 +437,12 @@ class GraphFit:
         """``render_deformed`` as the (h,w,3) float32 image, with the render parameters.  With
         ``opt.renderer_surfel_radii`` every surfel has its own radius (bound by ``_bind``); ``opt.renderer_rad`` then
         only has to be valid."""
-        from .renderer import DEFAULT_RAD, RenderContext, render_params
         bf = self._keep[0][0]
-        H, W = bf.c.H, bf.c.W
-        if self._render_ctx is None or self._render_ctx.H < H or self._render_ctx.W < W:
-            self._render_ctx = RenderContext(H, W)
-        ctx = self._render_ctx
-        ctx.reserve(bf.c.N)
-        p = render_params(inputs["K"], H, W, 1.0, getattr(self.opt, "renderer_rad", DEFAULT_RAD))
+        ctx, p = self._fresh_ctx(self._render_ctx, bf, inputs)
+        self._render_ctx = ctx
         img = torch.empty((p.height, p.width, 3), dtype=torch.float32, device=bf.device)
-        ctx.last_n = 0
-        ctx.serial += 1
         if self.surfel_radii:
-            _lib.check(self.lib.slm_gf_render_radii(self.h, 0, ctx.h, C.byref(p), _dev_ptr(self._render_radii),
+            _lib.check(self.lib.slm_gf_render_radii(self.h, 0, ctx.h, C.byref(p), _dev_ptr(self._slot_radii[0]),
                                                     _dev_ptr(colors), int(colors.stride(0)), _dev_ptr(img), None, None,
                                                     _stream_ptr(bf.device)), "slm_gf_render_radii")
         else:
@@ -483,10 +480,10 @@ class GraphFit:
         self._all_reduce(buf)
         self.set_partial(buf)
 
-    def deform_verts(self):
-        bf = self._keep[0][0]
+    def deform_verts(self, slot=0):
+        bf = self._keep[slot][0]
         out = torch.empty((bf.J + 1, 7), dtype=torch.float64, device=bf.device)
-        _lib.check(self.lib.slm_gf_get_deform(self.h, 0, _dev_ptr(out), self._st()), "slm_gf_get_deform")
+        _lib.check(self.lib.slm_gf_get_deform(self.h, slot, _dev_ptr(out), _stream_ptr(bf.device)), "slm_gf_get_deform")
         return out
 
     def loss_and_grad(self, inputs, src, trg, deform_verts, models=None, flow=None):
@@ -504,9 +501,7 @@ class GraphFit:
         if self.render_loss:
             # a first evaluation puts deform_verts into the slot, where slm_gf_render reads it
             _lib.check(self.lib.slm_gf_loss_grad(self.h, 0, _dev_ptr(dv), None, None, st), "slm_gf_loss_grad")
-            colors = src.colors.detach().to(device=bf.device, dtype=torch.float32).contiguous()
-            self._keep[0].append(colors)
-            img, p = self._render_deformed_hwc(inputs, colors)
+            img, p = self._render_deformed_hwc(inputs, self._colors(0, src))
             rl = self._bind_render_grad(bf, inputs, img, p)
         _lib.check(self.lib.slm_gf_loss_grad(self.h, 0, _dev_ptr(dv), _dev_ptr(terms), _dev_ptr(grad), st),
                    "slm_gf_loss_grad")

@@ -85,16 +85,24 @@ def test_semantic_edge_points_match_find_edge_region():
         np.testing.assert_array_equal(gf.edge_points(c).cpu().numpy(), ref[c].numpy().astype(np.float32))
 
 
-@pytest.mark.parametrize("tag", ["soft", "hard", "morph"])
-def test_semantic_gradient_at_random_point_vs_autograd_oracle(tag):
+@pytest.mark.parametrize("tag,num_neighbors", [pytest.param("soft", 4, id="soft"), pytest.param("hard", 4, id="hard"),
+                                               pytest.param("morph", 4, id="morph"), ("soft", 3), ("soft", 6)])
+def test_semantic_gradient_at_random_point_vs_autograd_oracle(tag, num_neighbors):
     """Semantic weights / morphing term away from identity, with unstable surfels, against
-    torch autograd on the oracle."""
+    torch autograd on the oracle.  At num_neighbors != 4 k_gf_morph skins with the run-time-K routine: "soft" weighs the
+    morphing term 0.1, where it dominates the loss, so a wrong deformed position there cannot hide under the tolerance."""
     import torch
     from super_amd import synth
     from super_amd.deform_mesh import GraphFit
-    sc = synth.make_scene(N=3000, J=48, H=60, W=80, seed=23, src_border=5, tgt_border=3, tgt_holes=0.01,
-                          semantic=True)
-    rng = np.random.default_rng(5)
+    K = num_neighbors
+    if K == 4:
+        sc = synth.make_scene(N=3000, J=48, H=60, W=80, seed=23, src_border=5, tgt_border=3, tgt_holes=0.01,
+                              semantic=True)
+        rng = np.random.default_rng(5)
+    else:
+        sc = synth.make_scene(N=3000, J=48, H=60, W=80, seed=40 + K, n_neighbors=K, src_border=5, tgt_border=3,
+                              tgt_holes=0.01, semantic=True)
+        rng = np.random.default_rng(K)
     dv0 = np.tile(np.array([1.0, 0, 0, 0, 0, 0, 0]), (sc.J + 1, 1))
     dv0 += np.concatenate([rng.normal(0, 0.01, (sc.J + 1, 4)), rng.normal(0, 0.003, (sc.J + 1, 3))], axis=1)
     opt = _opt(tag)
@@ -102,6 +110,8 @@ def test_semantic_gradient_at_random_point_vs_autograd_oracle(tag):
     pb = gfo.Problem(sc, stable=stable)
     dvt = torch.from_numpy(dv0.copy()).requires_grad_(True)
     loss, terms = gfo.total_loss(pb, dvt, opt)
+    if K != 4:
+        assert float(terms["sf_bn_morph_loss"].detach()) != 0.0 and terms["_matched"] != 0
     gref, = torch.autograd.grad(loss, dvt)
     gref = gref.clone()
     gref[-1] /= sc.J

@@ -27,6 +27,18 @@ def _cases():
         ("slm_gf_create", (C.byref(bad_gf), C.byref(out)), INVALID, b"slm_gf_create: bad argument"),
         ("slm_gf_bind_frame", (None, 0, None, None), INVALID, b"slm_gf_bind_frame: null argument"),
         ("slm_gf_set_shard", (None, 0, 1), INVALID, b"slm_gf_set_shard: bad rank/world"),
+        ("slm_gf_bind_semantic", (None, 0, None, None, None), INVALID, b"slm_gf_bind_semantic: null argument"),
+        ("slm_gf_bind_flow", (None, 0, None, None), INVALID, b"slm_gf_bind_flow: null argument"),
+        ("slm_gf_bind_point_grad", (None, 0, None, None), INVALID, b"slm_gf_bind_point_grad: null argument"),
+        ("slm_gf_get_edge_points", (None, 0, 0, None, 0, None), INVALID, b"slm_gf_get_edge_points: bad argument"),
+        ("slm_gf_eval_morph", (None, 1, None), INVALID, b"slm_gf: slot range out of bounds"),
+        ("slm_gf_eval_losses", (None, 1, None), INVALID, b"slm_gf: slot range out of bounds"),
+        ("slm_gf_step", (None, 1, None), INVALID, b"slm_gf: slot range out of bounds"),
+        ("slm_gf_run", (None, 1, None), INVALID, b"slm_gf: slot range out of bounds"),
+        ("slm_gf_get_partial", (None, 0, None, None), INVALID, b"slm_gf: slot range out of bounds"),
+        ("slm_gf_set_partial", (None, 0, None, None), INVALID, b"slm_gf: slot range out of bounds"),
+        ("slm_gf_get_deform", (None, 0, None, None), INVALID, b"slm_gf: slot range out of bounds"),
+        ("slm_gf_loss_grad", (None, 0, None, None, None, None), INVALID, b"slm_gf: slot range out of bounds"),
         ("slm_apply_update_gf", (0, 1, 9, None, None, None, None, one, one, one, None), UNSUPPORTED,
          b"slm_apply_update_gf: num_neighbors must be in 1..8"),
         ("slm_apply_update_gf_f64", (0, 0, 4, None, None, None, None, one, one, one, None), INVALID,
