@@ -72,13 +72,9 @@ __device__ __forceinline__ void load_diag_tile(const FrameDev& fd, int c, double
 // grid = (wb_cap + 1, n_frames), 256 threads
 __global__ void __launch_bounds__(256) k_panel(const FrameDev* __restrict__ frames, int c,
                                                 double u_override) {
-  extern __shared__ double lds[];
-  double* S = lds;
-  double* M = lds + TILE;
-  double* dinv = lds + 2 * TILE;
-  double* wt = dinv + 4 * 256;   // 3 scratch blocks (inverse_assemble64 runs on at most 3 waves)
-  double* vec = wt + 3 * 256;
-  int* s_ok = reinterpret_cast<int*>(vec + NB);
+  extern __shared__ double lds[];   // PanelLds; of its exchange buffer and ints only s_ok is used (potrf64 + inverse_assemble64)
+  double *S = PanelLds::S(lds), *M = PanelLds::M(lds), *dinv = PanelLds::dinv(lds), *wt = PanelLds::wt(lds), *vec = PanelLds::vec(lds);
+  int* s_ok = PanelLds::s_ok(lds);
   const FrameDev& fd = frames[blockIdx.y];
   if (!fd.bound || fd.st->stopped || c >= fd.nt) return;
   const int d = blockIdx.x;

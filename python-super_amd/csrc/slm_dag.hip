@@ -122,7 +122,6 @@ struct SS {   // scalar snapshot of the slot's buffers
   const int32_t *nd_nodes, *front_kids, *pull_off, *pullmap, *prng_off, *prng;
   const NDFront* fronts;
   int n_fronts;
-  const uint8_t* tile_kind;   // FrameDev::tile_kind (only the factor tasks read it)
   bool cached_ops;            // XCD-affine launch: operand tiles through the XCD's L2 (load_tile_regs2)
 };
 
@@ -133,7 +132,6 @@ struct DagFlags {
   int* pb;
   int* px;
   int* py;
-  int* pk;   // 4 per pivot tile column (unused since the streamed hand-off polls the column's mailbox, slm_tile.h)
 };
 __device__ __forceinline__ DagFlags dag_flags_of(const FrameDev& fd) {
   DagFlags g;
@@ -145,7 +143,6 @@ __device__ __forceinline__ DagFlags dag_flags_of(const FrameDev& fd) {
   g.pb = g.tile + nt;
   g.px = g.pb + np;
   g.py = g.px + np;
-  g.pk = g.py + np;
   return g;
 }
 
@@ -285,8 +282,8 @@ struct TD {
 };
 // kids_done: the front's children were factored by the per-level launches BEFORE this launch (hybrid solve, the fronts
 // at the cut): their update tiles are final -- gathered like any child's, but there is no flag to wait for (nskip)
-__device__ __forceinline__ TD task_deps(const SS& fd, const FS& f, int fi, int type, int r, int s, bool kids_done) {
-  TD d;
+// (d is filled in place: returned by value into a caller's existing TD, all of it is copied through scratch memory)
+__device__ __forceinline__ void task_deps(TD& d, const SS& fd, const FS& f, int fi, int type, int r, int s, bool kids_done) {
   d.type = type; d.r = r; d.s = s; d.diag = (r == s); d.npt = f.npt; d.nb = f.nb; d.c = s;
   d.pcol_self = f.pcol0;
   d.pcol_parent = 0;
@@ -333,7 +330,6 @@ __device__ __forceinline__ TD task_deps(const SS& fd, const FS& f, int fi, int t
     if (fusedf) d.pcol_parent = (int)(uni64(fd.fronts[f.parent].linv_off) / TILE);
     d.n0 = d.n = f.npt + (f.nb > 0 ? (fusedf ? 1 : f.npt) : 0) + f.npt * (f.npt - 1) / 2;
   }
-  return d;
 }
 __device__ __forceinline__ const int* dep_flag(const TD& d, const FS& f, const DagFlags& g, int i) {
   if (d.type <= ND_T_SCHUR) {
@@ -364,7 +360,9 @@ __device__ __forceinline__ const int* dep_flag(const TD& d, const FS& f, const D
         return j == 0 ? g.tile + tile_index(f, s, c) : (j == 1 ? g.py + f.pcol0 + c : g.tile + tile_index(f, s - 1, c));
       }
       i -= 3 * (s - 1);
-      return i < 4 ? g.pk + 4 * (f.pcol0 + s - 1) + i : g.py + f.pcol0 + s - 1;
+      // y_{s-1}.  (The four slots in front of it stand for the 16-pivot rounds of (s-1,s-1): taken from the column's
+      // mailbox, never waited for -- they resolve to the same flag.)
+      return g.py + f.pcol0 + s - 1;
     }
     if (i < 2 * d.kc) {
       const int c = i >> 1, odd = i & 1;
@@ -623,29 +621,88 @@ __device__ __forceinline__ double dag_reduce_rows(double tsum, double* part /* 4
   return part[i] + part[NB + i] + part[2 * NB + i] + part[3 * NB + i];
 }
 
-// S, M, the four diagonal-block inverses, three 16x16 scratch blocks, two vectors, a few ints: 80 960 B -> two
-// workgroups per CU.  `part` (row partials) shares the scratch blocks and the extend-add maps share the
-// diagonal-block inverses: neither is live while a tile is being factored.
-#define DAG_LDS_DOUBLES (2 * TILE + 7 * 256 + 2 * NB + 24)
+// The kernel's dynamic LDS is a DagLds (slm_tile.h): S, M, the four diagonal-block inverses, three 16x16 scratch blocks,
+// vec | yv, the ints: 81 088 B -> two workgroups per CU.  `part` (row partials) shares the scratch blocks and the
+// extend-add maps share the diagonal-block inverses: neither is live while a tile is being factored.
+extern __shared__ double dag_lds[];
 
 // Tile factorisation + inverse as a real call: inlined into the task loop it raises the register demand of the
 // whole kernel beyond 256 VGPRs (every path pays the maximum).  The LDS regions are derived from the dynamic LDS
 // base inside the function, so their address space stays known.
-extern __shared__ double dag_lds[];
 // look_ahead: wave 0 has staged the first diagonal block at dinv + 256 (ld 16) and the waves' row partials lie in wt
 // (factor_inverse64p's look-ahead entry); *la_sum receives their sums (threads < NB)
 __device__ __forceinline__ bool dag_factor_tile(double* g_mail, int* g_early, long long* trc, int nblk, bool look_ahead = false,
                                                 double* la_sum = nullptr) {
-  double* S = dag_lds;
-  double* M = dag_lds + TILE;
-  double* dinv = dag_lds + 2 * TILE;
-  double* wt = dinv + 4 * 256;
-  double* xch = wt + 3 * 256;                   // vec | yv: not live while a tile is being factored
-  int* s_ok = reinterpret_cast<int*>(xch + 2 * NB);
-  int* pf = s_ok + 16;                          // 16 hand-off flags of the trailing waves
   // (ONE inlined copy serves both entries: with two, each of them came out ~1.5 us slower per tile)
-  return factor_inverse64p(S, M, dinv, wt, xch, s_ok, pf, g_mail, g_early, trc, nblk, look_ahead ? dinv + 256 : nullptr,
-                           look_ahead ? wt : nullptr, la_sum);
+  return DagLds::factor(dag_lds, g_mail, g_early, trc, nblk, look_ahead, la_sum);
+}
+
+// ---- what every task starts from: its words and the scalar snapshots of its slot and front -----------------------------
+// (The LDS regions come from DagLds and dag_lds, the lane ids from threadIdx, in each task: as members they cost scratch
+//  memory -- docs/LAB_NOTEBOOK.md, "one task context", table of shapes.)
+struct DagTask {
+  int type, fi, tr_, ts_;   // the task's words: kind, front, tile row and column (BACKB: the column; BACK: 1 = fused form)
+  SS fd;
+  FS f;
+  DagFlags g;
+  double* vecs;             // the front's vector
+  LMState* lmst;
+  long long* trc;           // the task's 24 trace words (nullptr: no trace)
+  int* abort_flag;          // the launch's: kept with the ticket in slot 0's flags
+};
+// the task trace (tools/debug_dag.py): word 0 start, 1 ready (the last operand is there), 2 end, 3 workgroup, 4.. marks
+__device__ __forceinline__ void dag_mark(long long* trc, int k) {
+  if (trc && threadIdx.x == 0) trace_put(trc, k, wall_clock64());
+}
+__device__ __forceinline__ void dag_ready(long long* trc) { dag_mark(trc, 1); }
+__device__ __forceinline__ void dag_end(long long* trc) { dag_mark(trc, 2); }
+// A task re-derives its descriptors from (slot, ticket) itself.  TYPE: the kind where the caller's instantiation fixes it
+// (dag_task_factor: the dependency list folds), -1: from the task word.
+// d, the task's dependency list, is a local of the task and not a member of DagTask: its small arrays are indexed in loops,
+// and one such member keeps the WHOLE struct in scratch memory (+360..408 bytes per lane in four of the five task functions:
+// the same notebook table).
+template <int TYPE = -1>
+__device__ __forceinline__ DagTask dag_task_begin(const FrameDev* __restrict__ frames, int slot, int ti, int cut, int mode, TD& d) {
+  DagTask t;
+  t.abort_flag = unip(frames[0].dag_flags) + 1;
+  const FrameDev& fdr = frames[slot];
+  const int32_t* tasks = unip(cut >= 0 ? fdr.dag_top_tasks : fdr.dag_tasks);
+  const int w0 = uni(tasks[2 * ti]), w1 = uni(tasks[2 * ti + 1]);
+  t.type = TYPE >= 0 ? TYPE : w0 >> 24;   // (TYPE == w0 >> 24: the caller dispatched on it)
+  t.fi = w0 & 0xFFFFFF; t.tr_ = w1 >> 8; t.ts_ = w1 & 255;
+  SS& fd = t.fd;
+  fd.cached_ops = (mode & 1) != 0;
+  fd.ftiles = unip(fdr.ftiles); fd.fvec = unip(fdr.fvec); fd.flinv = unip(fdr.flinv); fd.fmail = unip(fdr.fmail); fd.delta = unip(fdr.delta);
+  fd.nd_nodes = unip(fdr.nd_nodes); fd.front_kids = unip(fdr.front_kids); fd.pull_off = unip(fdr.pull_off);
+  fd.pullmap = unip(fdr.pullmap); fd.prng_off = unip(fdr.prng_off); fd.prng = unip(fdr.prng);
+  fd.fronts = unip(fdr.fronts); fd.n_fronts = uni(fdr.n_fronts);
+  t.f = front_snapshot(fd.fronts[t.fi]);
+  t.g = dag_flags_of(fdr);
+  task_deps(d, fd, t.f, t.fi, t.type, t.tr_, t.ts_, cut >= 0 && uni(fd.fronts[t.fi].depth) == cut);
+  t.vecs = fd.fvec + t.f.vec_off;
+  t.lmst = unip(fdr.st);
+  long long* trc_base = unip(fdr.dag_trace);
+  t.trc = trc_base ? trc_base + 24 * (size_t)ti : nullptr;
+  if (t.trc && threadIdx.x == 0) {
+    trace_put(t.trc, 0, wall_clock64());
+    trace_put(t.trc, 3, blockIdx.x);
+  }
+  return t;
+}
+
+// A PURE-FILL tile (FrameDev::tile_kind: nothing assembled into it, never zeroed) starts from zero: what the load of a
+// task's own tile returned is whatever the previous iteration left there.
+// (tile_kind: only the factor tasks load the pointer, behind the loads of their own tile -- it is waited for)
+__device__ __forceinline__ void dag_zero_pure_fill(const uint8_t* tile_kind, const FS& f, int r, int c, double4_t acc[4]) {
+  if (uni((int)tile_kind[tile_index(f, r, c)]) != 0) {
+#pragma unroll
+    for (int ni = 0; ni < 4; ++ni) acc[ni] = double4_t{0.0, 0.0, 0.0, 0.0};
+  }
+}
+// x of the front's boundary nodes from the global solution (all ancestors are solved) -> xb, n2p doubles of LDS
+__device__ __forceinline__ void dag_gather_boundary(const SS& fd, const FS& f, double* xb) {
+  const int* nodes = fd.nd_nodes + f.nodes_off + f.nv;
+  for (int i = threadIdx.x; i < f.n2p; i += blockDim.x) xb[i] = (i < 7 * f.nb) ? ld1(fd.delta + 7 * nodes[i / 7] + i % 7) : 0.0;
 }
 
 }  // namespace
@@ -670,7 +727,7 @@ __device__ __forceinline__ bool mail_here(double v) { return __double_as_longlon
 #define MAIL_TAKE(MAIL, PD, PL, KB, DINV, LST)                                                                   \
   do {                                                                                                           \
     const int pe_i_ = threadIdx.x & 15, pe_k_ = threadIdx.x >> 4;                                                \
-    int* votes_ = s_ok + 4;                                                                                      \
+    int* votes_ = DagLds::votes(dag_lds);                                                                        \
     int spins_ = 0;                                                                                              \
     long long t0_ = 0;                                                                                           \
     for (;;) {                                                                                                   \
@@ -713,63 +770,30 @@ __device__ __forceinline__ bool mail_here(double v) { return __double_as_longlon
 // slm_front.hip (XCD-aware work lists, operands shared through L2) -- slm_api.hip picks.
 // ---- the tasks.  Each kind is a function of its own (a real call): inlined into one loop, every path pays the
 // register demand of all of them, and the tile factorisation -- the critical path -- ends up spilling.
-// A task re-derives its descriptors from (ticket) itself; LDS regions come from the dynamic LDS base.
+// A task re-derives its descriptors from (ticket) itself (dag_task_begin); LDS regions come from the dynamic LDS base.
 // (DIAG: the POTRF tasks and the COL tasks are instantiations of their own -- 85 KB of code as one function, more than the
 //  instruction cache two CUs share; the pivot chain runs through the smaller one)
 template <bool DIAG>
-__device__ __noinline__ void dag_task_factor(const FrameDev* __restrict__ frames, int n_frames, int slot, int ti, double u_override, int cut, int mode) {
-  double* lds = dag_lds;
-  double* S = lds;                 // tile being factored / B operand staging
-  double* M = lds + TILE;          // inverse of the factored tile / second staging tile
-  double* dinv = lds + 2 * TILE;   // 4 x 256
-  double* wt = dinv + 4 * 256;     // 3 x 256 scratch
-  double* vec = wt + 3 * 256;      // NB
-  double* yv = vec + NB;           // NB
-  double* part = wt;               // 4 * NB row partials (not live during a tile factorisation)
-  int* s_ok = reinterpret_cast<int*>(yv + NB);
-  int* s_task = s_ok + 1;
-  int* s_abort = s_ok + 2;
-  int* s_cnt = s_ok + 3;
-  int2* maps = reinterpret_cast<int2*>(dinv);   // 256 int2: pull maps of the tile being loaded (not live in a factorisation)
+__device__ __noinline__ void dag_task_factor(const FrameDev* __restrict__ frames, int slot, int ti, double u_override, int cut, int mode) {
   const int l = threadIdx.x & 63, w = threadIdx.x >> 6, lr = l & 15, lk = l >> 4;
-  int* abort_flag = unip(frames[0].dag_flags) + 1;
-  (void)s_task; (void)S; (void)M; (void)dinv; (void)vec; (void)yv; (void)part; (void)maps; (void)s_cnt; (void)l; (void)w; (void)lr; (void)lk;
-    const FrameDev& fdr = frames[slot];
-    const int32_t* tasks = unip(cut >= 0 ? fdr.dag_top_tasks : fdr.dag_tasks);
-    const int w0 = uni(tasks[2 * ti]), w1 = uni(tasks[2 * ti + 1]);
-    constexpr int type = DIAG ? ND_T_POTRF : ND_T_COL;   // (= w0 >> 24: the caller dispatched on it)
-    const int fi = w0 & 0xFFFFFF, tr_ = w1 >> 8, ts_ = w1 & 255;
-    SS fd;
-    fd.cached_ops = (mode & 1) != 0;
-    fd.ftiles = unip(fdr.ftiles); fd.fvec = unip(fdr.fvec); fd.flinv = unip(fdr.flinv); fd.fmail = unip(fdr.fmail); fd.delta = unip(fdr.delta);
-    fd.nd_nodes = unip(fdr.nd_nodes); fd.front_kids = unip(fdr.front_kids); fd.pull_off = unip(fdr.pull_off);
-    fd.pullmap = unip(fdr.pullmap); fd.prng_off = unip(fdr.prng_off); fd.prng = unip(fdr.prng);
-    fd.fronts = unip(fdr.fronts); fd.n_fronts = uni(fdr.n_fronts);
-    const FS f = front_snapshot(fd.fronts[fi]);
-    const DagFlags g = dag_flags_of(fdr);
-    const TD d = task_deps(fd, f, fi, type, tr_, ts_, cut >= 0 && uni(fd.fronts[fi].depth) == cut);
-    double* vecs = fd.fvec + f.vec_off;
-    LMState* lmst = unip(fdr.st);
-    long long* trc_base = unip(fdr.dag_trace);
-    long long* trc = trc_base ? trc_base + 24 * (size_t)ti : nullptr;
-    if (trc && threadIdx.x == 0) {
-      trace_put(trc, 0, wall_clock64());
-      trace_put(trc, 3, blockIdx.x);
-    }
-#define DAG_READY() do { if (trc && threadIdx.x == 0) trace_put(trc, 1, wall_clock64()); } while (0)
-#define DAG_END() do { if (trc && threadIdx.x == 0) trace_put(trc, 2, wall_clock64()); } while (0)
-#define DAG_MARK(k) do { if (trc && threadIdx.x == 0) trace_put(trc, (k), wall_clock64()); } while (0)
+  TD d;
+  const DagTask tk = dag_task_begin<DIAG ? ND_T_POTRF : ND_T_COL>(frames, slot, ti, cut, mode, d);
+  const SS& fd = tk.fd; const FS& f = tk.f; const DagFlags& g = tk.g;
+  constexpr int type = DIAG ? ND_T_POTRF : ND_T_COL;
+  const int fi = tk.fi, tr_ = tk.tr_, ts_ = tk.ts_;
+  double *S = DagLds::S(dag_lds), *M = DagLds::M(dag_lds), *dinv = DagLds::dinv(dag_lds), *vec = DagLds::vec(dag_lds), *yv = DagLds::vec2(dag_lds),
+         *part = DagLds::part(dag_lds);
+  int2* maps = DagLds::maps(dag_lds);
+  int *abort_flag = tk.abort_flag, *s_abort = DagLds::s_abort(dag_lds), *s_cnt = DagLds::s_cnt(dag_lds);
+  double* vecs = tk.vecs;
+  LMState* lmst = tk.lmst;
+  long long* trc = tk.trc;
     // The task's own tile and vector rows are final before the launch (assembly; in the hybrid form also the pushes of
     // the per-level launches): requested BEFORE the wait for what the task needs to start, not after it
     double4_t acc[4];
     load_c_frags1(tile_ptr(fd, f, tr_, ts_), acc);
-    // a PURE-FILL tile (FrameDev::tile_kind: nothing assembled into it, never zeroed) starts from zero: what the load
-    // returned is whatever the previous iteration left there
-    fd.tile_kind = unip(fdr.tile_kind);
-    if (uni((int)fd.tile_kind[tile_index(f, tr_, ts_)]) != 0) {
-#pragma unroll
-      for (int ni = 0; ni < 4; ++ni) acc[ni] = double4_t{0.0, 0.0, 0.0, 0.0};
-    }
+    const uint8_t* tile_kind = unip(frames[slot].tile_kind);
+    dag_zero_pure_fill(tile_kind, f, tr_, ts_, acc);
     double bvec = 0.0, tsum = 0.0;
     if (type == ND_T_POTRF && threadIdx.x < NB) bvec = ld1(vecs + (size_t)ts_ * NB + threadIdx.x);
     dag_pull_maps(fd, fi, tr_, ts_, d.np, maps);   // (static plan data: also before the wait)
@@ -791,10 +815,7 @@ __device__ __noinline__ void dag_task_factor(const FrameDev* __restrict__ frames
         // formed here as soon as the factor of column s-1 is out, and goes into the update of (s,s) from LDS
         double4_t accl[4];
         load_c_frags1(tile_ptr(fd, f, s, s - 1), accl);
-        if (uni((int)fd.tile_kind[tile_index(f, s, s - 1)]) != 0) {   // (pure fill: see above)
-#pragma unroll
-          for (int ni = 0; ni < 4; ++ni) accl[ni] = double4_t{0.0, 0.0, 0.0, 0.0};
-        }
+        dag_zero_pure_fill(tile_kind, f, s, s - 1, accl);
         double dummy = 0.0;
         dag_pull<false>(fd, fi, s, s - 1, accl, dummy, d.np2, maps);
         {
@@ -843,7 +864,7 @@ __device__ __noinline__ void dag_task_factor(const FrameDev* __restrict__ frames
 #pragma unroll
           for (int kb = 0; kb < 4; ++kb) {
             MAIL_TAKE(mail, pd, pl, kb, dinv, Lst);
-            if (kb == 3) DAG_READY();
+            if (kb == 3) dag_ready(trc);
             if (kb < 3) MAIL_ISSUE(mail, pd, pl, kb + 1);
             double4_t t4 = accl[kb];
 #pragma unroll
@@ -915,7 +936,7 @@ __device__ __noinline__ void dag_task_factor(const FrameDev* __restrict__ frames
         if (m == 0) return;
       }
       if (diag) {
-        DAG_MARK(4);
+        dag_mark(trc, 4);
         const bool la = s > 0;                             // look-ahead entry of the factorisation (see the last streamed round)
         double t;
         if (!la) {
@@ -947,7 +968,7 @@ __device__ __noinline__ void dag_task_factor(const FrameDev* __restrict__ frames
           wave_sync();
         }
         if (!la) __syncthreads();
-        DAG_MARK(5);
+        dag_mark(trc, 5);
         const bool stream = s + 1 < f.nt;                  // POTRF(s+1) and the column's COL tasks follow the factorisation 16 pivots at a time
         double* linv = fd.flinv + f.linv_off + (size_t)s * TILE;
         const bool ok = dag_factor_tile(stream ? fd.fmail + (size_t)(f.pcol0 + s) * SLM_MAIL_DOUBLES : nullptr,
@@ -956,13 +977,13 @@ __device__ __noinline__ void dag_task_factor(const FrameDev* __restrict__ frames
                                        min(4, (f.n1 - s * NB + 15) >> 4),   // 16-pivot blocks with real pivots (the front's last column: fewer)
                                        la, &t);
         const double bt = bvec - t;                        // threads < NB: right-hand side of row threadIdx.x (minus L(s,s-1) y_{s-1}, below)
-        DAG_MARK(6);
+        dag_mark(trc, 6);
         if (!ok && threadIdx.x == 0) lmst->chol_fail = 1;
 #pragma unroll
         for (int e = 0; e < 16; ++e) st1(linv + threadIdx.x + 256 * e, M[threadIdx.x + 256 * e]);
         dag_publish_begin();
         dag_set_flag(g.tile + tile_index(f, s, s));        // the whole inverse is out: the column's other row solves can start
-        DAG_MARK(7);
+        dag_mark(trc, 7);
         {
           // y_s = L_ss^-1 (b_s - sum_{c<s} L(s,c) y_c), off the factorisation's critical path, under its own flag
           double xy = 0.0;
@@ -994,8 +1015,8 @@ __device__ __noinline__ void dag_task_factor(const FrameDev* __restrict__ frames
         }
         dag_publish_begin();
         dag_set_flag(g.py + f.pcol0 + s);
-        if (s == 0) DAG_READY();
-        DAG_END();
+        if (s == 0) dag_ready(trc);
+        dag_end(trc);
       } else {
         // stage 2: X = acc L_ss^-T, 16 pivots at a time behind the factorisation of (s,s) -- the same streamed row solve
         // as POTRF(s+1) runs on its tile (s+1,s): the row is complete ~3 us after the producer's last pivot instead of
@@ -1010,7 +1031,7 @@ __device__ __noinline__ void dag_task_factor(const FrameDev* __restrict__ frames
 #pragma unroll
           for (int kb = 0; kb < 4; ++kb) {
             MAIL_TAKE(mail, pd, pl, kb, dinv, Lst);
-            if (kb == 3) DAG_READY();
+            if (kb == 3) dag_ready(trc);
             if (kb < 3) MAIL_ISSUE(mail, pd, pl, kb + 1);
             double4_t t4 = acc[kb];
 #pragma unroll
@@ -1036,52 +1057,21 @@ __device__ __noinline__ void dag_task_factor(const FrameDev* __restrict__ frames
         store_c_frags1(tile_ptr(fd, f, r, s), xa);
         dag_publish_begin();
         dag_set_flag(g.tile + tile_index(f, r, s));
-        DAG_END();
+        dag_end(trc);
       }
   }
 }
 
-__device__ __noinline__ void dag_task_schur(const FrameDev* __restrict__ frames, int n_frames, int slot, int ti, double u_override, int cut, int mode) {
-  double* lds = dag_lds;
-  double* S = lds;                 // tile being factored / B operand staging
-  double* M = lds + TILE;          // inverse of the factored tile / second staging tile
-  double* dinv = lds + 2 * TILE;   // 4 x 256
-  double* wt = dinv + 4 * 256;     // 3 x 256 scratch
-  double* vec = wt + 3 * 256;      // NB
-  double* yv = vec + NB;           // NB
-  double* part = wt;               // 4 * NB row partials (not live during a tile factorisation)
-  int* s_ok = reinterpret_cast<int*>(yv + NB);
-  int* s_task = s_ok + 1;
-  int* s_abort = s_ok + 2;
-  int* s_cnt = s_ok + 3;
-  int2* maps = reinterpret_cast<int2*>(dinv);   // 256 int2: pull maps of the tile being loaded (not live in a factorisation)
-  const int l = threadIdx.x & 63, w = threadIdx.x >> 6, lr = l & 15, lk = l >> 4;
-  int* abort_flag = unip(frames[0].dag_flags) + 1;
-  (void)s_task; (void)S; (void)M; (void)dinv; (void)vec; (void)yv; (void)part; (void)maps; (void)s_cnt; (void)l; (void)w; (void)lr; (void)lk;
-    const FrameDev& fdr = frames[slot];
-    const int32_t* tasks = unip(cut >= 0 ? fdr.dag_top_tasks : fdr.dag_tasks);
-    const int w0 = uni(tasks[2 * ti]), w1 = uni(tasks[2 * ti + 1]);
-    const int type = w0 >> 24, fi = w0 & 0xFFFFFF, tr_ = w1 >> 8, ts_ = w1 & 255;
-    SS fd;
-    fd.cached_ops = (mode & 1) != 0;
-    fd.ftiles = unip(fdr.ftiles); fd.fvec = unip(fdr.fvec); fd.flinv = unip(fdr.flinv); fd.fmail = unip(fdr.fmail); fd.delta = unip(fdr.delta);
-    fd.nd_nodes = unip(fdr.nd_nodes); fd.front_kids = unip(fdr.front_kids); fd.pull_off = unip(fdr.pull_off);
-    fd.pullmap = unip(fdr.pullmap); fd.prng_off = unip(fdr.prng_off); fd.prng = unip(fdr.prng);
-    fd.fronts = unip(fdr.fronts); fd.n_fronts = uni(fdr.n_fronts);
-    const FS f = front_snapshot(fd.fronts[fi]);
-    const DagFlags g = dag_flags_of(fdr);
-    const TD d = task_deps(fd, f, fi, type, tr_, ts_, cut >= 0 && uni(fd.fronts[fi].depth) == cut);
-    double* vecs = fd.fvec + f.vec_off;
-    LMState* lmst = unip(fdr.st);
-    long long* trc_base = unip(fdr.dag_trace);
-    long long* trc = trc_base ? trc_base + 24 * (size_t)ti : nullptr;
-    if (trc && threadIdx.x == 0) {
-      trace_put(trc, 0, wall_clock64());
-      trace_put(trc, 3, blockIdx.x);
-    }
-#define DAG_READY() do { if (trc && threadIdx.x == 0) trace_put(trc, 1, wall_clock64()); } while (0)
-#define DAG_END() do { if (trc && threadIdx.x == 0) trace_put(trc, 2, wall_clock64()); } while (0)
-#define DAG_MARK(k) do { if (trc && threadIdx.x == 0) trace_put(trc, (k), wall_clock64()); } while (0)
+__device__ __noinline__ void dag_task_schur(const FrameDev* __restrict__ frames, int slot, int ti, double u_override, int cut, int mode) {
+  TD d;
+  const DagTask tk = dag_task_begin(frames, slot, ti, cut, mode, d);
+  const SS& fd = tk.fd; const FS& f = tk.f; const DagFlags& g = tk.g;
+  const int fi = tk.fi, tr_ = tk.tr_, ts_ = tk.ts_;
+  double *S = DagLds::S(dag_lds), *M = DagLds::M(dag_lds), *yv = DagLds::vec2(dag_lds), *part = DagLds::part(dag_lds);
+  int2* maps = DagLds::maps(dag_lds);
+  int *abort_flag = tk.abort_flag, *s_abort = DagLds::s_abort(dag_lds), *s_cnt = DagLds::s_cnt(dag_lds);
+  double* vecs = tk.vecs;
+  long long* trc = tk.trc;
     // own tile, vector rows and pull maps: final before the launch, requested before the wait (see dag_task_factor)
     double4_t acc[4];
     // A boundary block holds nothing before its Schur task writes it (never read first, never zeroed: k_iter_begin_nd)
@@ -1103,7 +1093,7 @@ __device__ __noinline__ void dag_task_schur(const FrameDev* __restrict__ frames,
         int c = 0, m = 1;
         while (c < f.npt && m > 0) {
           m = dag_wait_prefix(d, f, g, d.n0 + 2 * c, d.n0 + 2 * f.npt, 2, abort_flag, s_abort, s_cnt);
-          if (c + m == f.npt) DAG_READY();
+          if (c + m == f.npt) dag_ready(trc);
           if (dg) dag_accumulate<true>(fd, f, r, r, c, c + m, acc, S, M, yv, tsum);
           else dag_accumulate<false>(fd, f, r, sc, c, c + m, acc, S, M, yv, tsum);
           c += m;
@@ -1119,51 +1109,20 @@ __device__ __noinline__ void dag_task_schur(const FrameDev* __restrict__ frames,
       }
       dag_publish_begin();
       dag_set_flag(g.tile + tile_index(f, r, sc));
-      DAG_END();
+      dag_end(trc);
   }
 }
 
-__device__ __noinline__ void dag_task_backb(const FrameDev* __restrict__ frames, int n_frames, int slot, int ti, double u_override, int cut, int mode) {
-  double* lds = dag_lds;
-  double* S = lds;                 // tile being factored / B operand staging
-  double* M = lds + TILE;          // inverse of the factored tile / second staging tile
-  double* dinv = lds + 2 * TILE;   // 4 x 256
-  double* wt = dinv + 4 * 256;     // 3 x 256 scratch
-  double* vec = wt + 3 * 256;      // NB
-  double* yv = vec + NB;           // NB
-  double* part = wt;               // 4 * NB row partials (not live during a tile factorisation)
-  int* s_ok = reinterpret_cast<int*>(yv + NB);
-  int* s_task = s_ok + 1;
-  int* s_abort = s_ok + 2;
-  int* s_cnt = s_ok + 3;
-  int2* maps = reinterpret_cast<int2*>(dinv);   // 256 int2: pull maps of the tile being loaded (not live in a factorisation)
-  const int l = threadIdx.x & 63, w = threadIdx.x >> 6, lr = l & 15, lk = l >> 4;
-  int* abort_flag = unip(frames[0].dag_flags) + 1;
-  (void)s_task; (void)S; (void)M; (void)dinv; (void)vec; (void)yv; (void)part; (void)maps; (void)s_cnt; (void)l; (void)w; (void)lr; (void)lk;
-    const FrameDev& fdr = frames[slot];
-    const int32_t* tasks = unip(cut >= 0 ? fdr.dag_top_tasks : fdr.dag_tasks);
-    const int w0 = uni(tasks[2 * ti]), w1 = uni(tasks[2 * ti + 1]);
-    const int type = w0 >> 24, fi = w0 & 0xFFFFFF, tr_ = w1 >> 8, ts_ = w1 & 255;
-    SS fd;
-    fd.cached_ops = (mode & 1) != 0;
-    fd.ftiles = unip(fdr.ftiles); fd.fvec = unip(fdr.fvec); fd.flinv = unip(fdr.flinv); fd.fmail = unip(fdr.fmail); fd.delta = unip(fdr.delta);
-    fd.nd_nodes = unip(fdr.nd_nodes); fd.front_kids = unip(fdr.front_kids); fd.pull_off = unip(fdr.pull_off);
-    fd.pullmap = unip(fdr.pullmap); fd.prng_off = unip(fdr.prng_off); fd.prng = unip(fdr.prng);
-    fd.fronts = unip(fdr.fronts); fd.n_fronts = uni(fdr.n_fronts);
-    const FS f = front_snapshot(fd.fronts[fi]);
-    const DagFlags g = dag_flags_of(fdr);
-    const TD d = task_deps(fd, f, fi, type, tr_, ts_, cut >= 0 && uni(fd.fronts[fi].depth) == cut);
-    double* vecs = fd.fvec + f.vec_off;
-    LMState* lmst = unip(fdr.st);
-    long long* trc_base = unip(fdr.dag_trace);
-    long long* trc = trc_base ? trc_base + 24 * (size_t)ti : nullptr;
-    if (trc && threadIdx.x == 0) {
-      trace_put(trc, 0, wall_clock64());
-      trace_put(trc, 3, blockIdx.x);
-    }
-#define DAG_READY() do { if (trc && threadIdx.x == 0) trace_put(trc, 1, wall_clock64()); } while (0)
-#define DAG_END() do { if (trc && threadIdx.x == 0) trace_put(trc, 2, wall_clock64()); } while (0)
-#define DAG_MARK(k) do { if (trc && threadIdx.x == 0) trace_put(trc, (k), wall_clock64()); } while (0)
+__device__ __noinline__ void dag_task_backb(const FrameDev* __restrict__ frames, int slot, int ti, double u_override, int cut, int mode) {
+  const int l = threadIdx.x & 63, w = threadIdx.x >> 6;
+  TD d;
+  const DagTask tk = dag_task_begin(frames, slot, ti, cut, mode, d);
+  const SS& fd = tk.fd; const FS& f = tk.f; const DagFlags& g = tk.g;
+  const int fi = tk.fi, ts_ = tk.ts_;
+  double* S = DagLds::S(dag_lds);
+  int *abort_flag = tk.abort_flag, *s_abort = DagLds::s_abort(dag_lds);
+  double* vecs = tk.vecs;
+  long long* trc = tk.trc;
     // The boundary tiles of this column are final once the front is factored -- long before the parent's solution
     // arrives: wait for THEM first and request the first two, so that the load latency is gone when x comes
     const int c_ = ts_;
@@ -1186,10 +1145,9 @@ __device__ __noinline__ void dag_task_backb(const FrameDev* __restrict__ frames,
       // ================= BACKB(f,c): y_c -= sum over boundary tiles L(r,c)^T x_r ====================
       // (the parent's pivots -- and with them all ancestors' -- are solved: stage 0)
       const int c = ts_;
-      DAG_READY();
+      dag_ready(trc);
       double* xb = S;   // n2p doubles
-      const int* nodes = fd.nd_nodes + f.nodes_off + f.nv;
-      for (int i = threadIdx.x; i < f.n2p; i += blockDim.x) xb[i] = (i < 7 * f.nb) ? ld1(fd.delta + 7 * nodes[i / 7] + i % 7) : 0.0;
+      dag_gather_boundary(fd, f, xb);
       __syncthreads();
       // two tiles being used while the next two are in flight; the partial products of all tiles are summed per thread
       // first, one reduction over the lanes at the end
@@ -1223,51 +1181,20 @@ __device__ __noinline__ void dag_task_backb(const FrameDev* __restrict__ frames,
       }
       dag_publish_begin();
       dag_set_flag(g.pb + f.pcol0 + c);
-      DAG_END();
+      dag_end(trc);
   }
 }
 
-__device__ __noinline__ void dag_task_back(const FrameDev* __restrict__ frames, int n_frames, int slot, int ti, double u_override, int cut, int mode) {
-  double* lds = dag_lds;
-  double* S = lds;                 // tile being factored / B operand staging
-  double* M = lds + TILE;          // inverse of the factored tile / second staging tile
-  double* dinv = lds + 2 * TILE;   // 4 x 256
-  double* wt = dinv + 4 * 256;     // 3 x 256 scratch
-  double* vec = wt + 3 * 256;      // NB
-  double* yv = vec + NB;           // NB
-  double* part = wt;               // 4 * NB row partials (not live during a tile factorisation)
-  int* s_ok = reinterpret_cast<int*>(yv + NB);
-  int* s_task = s_ok + 1;
-  int* s_abort = s_ok + 2;
-  int* s_cnt = s_ok + 3;
-  int2* maps = reinterpret_cast<int2*>(dinv);   // 256 int2: pull maps of the tile being loaded (not live in a factorisation)
-  const int l = threadIdx.x & 63, w = threadIdx.x >> 6, lr = l & 15, lk = l >> 4;
-  int* abort_flag = unip(frames[0].dag_flags) + 1;
-  (void)s_task; (void)S; (void)M; (void)dinv; (void)vec; (void)yv; (void)part; (void)maps; (void)s_cnt; (void)l; (void)w; (void)lr; (void)lk;
-    const FrameDev& fdr = frames[slot];
-    const int32_t* tasks = unip(cut >= 0 ? fdr.dag_top_tasks : fdr.dag_tasks);
-    const int w0 = uni(tasks[2 * ti]), w1 = uni(tasks[2 * ti + 1]);
-    const int type = w0 >> 24, fi = w0 & 0xFFFFFF, tr_ = w1 >> 8, ts_ = w1 & 255;
-    SS fd;
-    fd.cached_ops = (mode & 1) != 0;
-    fd.ftiles = unip(fdr.ftiles); fd.fvec = unip(fdr.fvec); fd.flinv = unip(fdr.flinv); fd.fmail = unip(fdr.fmail); fd.delta = unip(fdr.delta);
-    fd.nd_nodes = unip(fdr.nd_nodes); fd.front_kids = unip(fdr.front_kids); fd.pull_off = unip(fdr.pull_off);
-    fd.pullmap = unip(fdr.pullmap); fd.prng_off = unip(fdr.prng_off); fd.prng = unip(fdr.prng);
-    fd.fronts = unip(fdr.fronts); fd.n_fronts = uni(fdr.n_fronts);
-    const FS f = front_snapshot(fd.fronts[fi]);
-    const DagFlags g = dag_flags_of(fdr);
-    const TD d = task_deps(fd, f, fi, type, tr_, ts_, cut >= 0 && uni(fd.fronts[fi].depth) == cut);
-    double* vecs = fd.fvec + f.vec_off;
-    LMState* lmst = unip(fdr.st);
-    long long* trc_base = unip(fdr.dag_trace);
-    long long* trc = trc_base ? trc_base + 24 * (size_t)ti : nullptr;
-    if (trc && threadIdx.x == 0) {
-      trace_put(trc, 0, wall_clock64());
-      trace_put(trc, 3, blockIdx.x);
-    }
-#define DAG_READY() do { if (trc && threadIdx.x == 0) trace_put(trc, 1, wall_clock64()); } while (0)
-#define DAG_END() do { if (trc && threadIdx.x == 0) trace_put(trc, 2, wall_clock64()); } while (0)
-#define DAG_MARK(k) do { if (trc && threadIdx.x == 0) trace_put(trc, (k), wall_clock64()); } while (0)
+__device__ __noinline__ void dag_task_back(const FrameDev* __restrict__ frames, int slot, int ti, double u_override, int cut, int mode) {
+  const int l = threadIdx.x & 63, w = threadIdx.x >> 6;
+  TD d;
+  const DagTask tk = dag_task_begin(frames, slot, ti, cut, mode, d);
+  const SS& fd = tk.fd; const FS& f = tk.f; const DagFlags& g = tk.g;
+  const int fi = tk.fi, ts_ = tk.ts_;
+  double *S = DagLds::S(dag_lds), *M = DagLds::M(dag_lds);
+  int *abort_flag = tk.abort_flag, *s_abort = DagLds::s_abort(dag_lds);
+  double* vecs = tk.vecs;
+  long long* trc = tk.trc;
     // stage 0 in two steps: the factorisation's outputs (y of every column, the tiles of the pivot block) are there long
     // before the boundary part of the right-hand side (BACKB, which waits for the parent's solution): wait for the
     // former, request the first three tiles of the chain, and only then wait for the latter
@@ -1321,7 +1248,7 @@ __device__ __noinline__ void dag_task_back(const FrameDev* __restrict__ frames, 
       // ================= BACK(f): the chain over the front's pivot columns =========================
       // for c = npt-1 .. 0:  x_c = L_cc^-T (y_c - sum_{r>c} L(r,c)^T x_r).  y / x stay in LDS, the tiles (in the order
       // they are used) stream through registers three ahead: their addresses do not depend on x.
-      DAG_READY();
+      dag_ready(trc);
       double* ya = S;                  // npt * NB: y, overwritten by x column by column
       for (int i = threadIdx.x; i < f.npt * NB; i += blockDim.x) ya[i] = ld1(vecs + i);
       // tiles in the 16-byte-per-lane layout (load_tile_regs2): thread t holds T[n][m], n = (t >> 5) + 8 e, m = 2 (t & 31) + {0, 1};
@@ -1334,8 +1261,7 @@ __device__ __noinline__ void dag_task_back(const FrameDev* __restrict__ frames, 
         // ---- the boundary part (what the BACKB tasks do for the fronts that have them): y_c -= sum_r L(r,c)^T x_r over the
         // boundary tile rows, x of the boundary nodes gathered ONCE from the global solution (all ancestors are solved)
         double* xb = M;   // n2p doubles
-        const int* nodes = fd.nd_nodes + f.nodes_off + f.nv;
-        for (int i = threadIdx.x; i < f.n2p; i += blockDim.x) xb[i] = (i < 7 * f.nb) ? ld1(fd.delta + 7 * nodes[i / 7] + i % 7) : 0.0;
+        dag_gather_boundary(fd, f, xb);
         __syncthreads();   // xb and ya complete
         // the npt x (nt - npt) boundary tiles in column-major order, two in use while the next two are in flight (requests
         // past the end repeat the last tile and count for nothing: unconditional loads keep the wait counts exact)
@@ -1417,7 +1343,7 @@ __device__ __noinline__ void dag_task_back(const FrameDev* __restrict__ frames, 
       }
       dag_publish_begin();
       dag_set_flag(g.px + f.pcol0);    // (column 0 stands for the whole front: what the children's BACKB wait for)
-      DAG_END();
+      dag_end(trc);
     }
 }
 
@@ -1430,9 +1356,7 @@ __device__ __noinline__ void dag_task_back(const FrameDev* __restrict__ frames, 
 // smaller tickets of its own stream only.
 __global__ void __launch_bounds__(256, 2) k_fdag(const FrameDev* __restrict__ frames, int n_frames, int max_tasks,
                                                  double u_override, int cut, int mode) {
-  int* s_ok = reinterpret_cast<int*>(dag_lds + 2 * TILE + 7 * 256 + 2 * NB);
-  int* s_task = s_ok + 1;
-  int* s_abort = s_ok + 2;
+  int *s_task = DagLds::s_task(dag_lds), *s_abort = DagLds::s_abort(dag_lds);
   const FrameDev& fd0 = frames[0];
   if (!fd0.bound || !fd0.nd_ready) return;
   const bool affine = (mode & 1) != 0;
@@ -1452,11 +1376,11 @@ __global__ void __launch_bounds__(256, 2) k_fdag(const FrameDev* __restrict__ fr
     const FrameDev& fq = frames[slot];
     if (!uni(fq.bound) || !uni(fq.nd_ready) || ti >= uni(cut >= 0 ? fq.n_dag_top_tasks : fq.n_dag_tasks)) continue;
     const int type = uni(unip(cut >= 0 ? fq.dag_top_tasks : fq.dag_tasks)[2 * ti]) >> 24;
-    if (type == ND_T_POTRF) dag_task_factor<true>(frames, n_frames, slot, ti, u_override, cut, mode);
-    else if (type == ND_T_COL) dag_task_factor<false>(frames, n_frames, slot, ti, u_override, cut, mode);
-    else if (type == ND_T_SCHUR) dag_task_schur(frames, n_frames, slot, ti, u_override, cut, mode);
-    else if (type == ND_T_BACKB) dag_task_backb(frames, n_frames, slot, ti, u_override, cut, mode);
-    else dag_task_back(frames, n_frames, slot, ti, u_override, cut, mode);
+    if (type == ND_T_POTRF) dag_task_factor<true>(frames, slot, ti, u_override, cut, mode);
+    else if (type == ND_T_COL) dag_task_factor<false>(frames, slot, ti, u_override, cut, mode);
+    else if (type == ND_T_SCHUR) dag_task_schur(frames, slot, ti, u_override, cut, mode);
+    else if (type == ND_T_BACKB) dag_task_backb(frames, slot, ti, u_override, cut, mode);
+    else dag_task_back(frames, slot, ti, u_override, cut, mode);
   }
 }
 

@@ -444,14 +444,7 @@ __global__ void __launch_bounds__(256) k_iter_begin_nd(const FrameDev* __restric
 __global__ void __launch_bounds__(256) k_fpanel(const FrameDev* __restrict__ frames, LevelRef lvl,
                                                  int c, double u_override, WgMap map) {
   extern __shared__ double lds[];
-  double* S = lds;
-  double* M = lds + TILE;
-  double* dinv = lds + 2 * TILE;
-  double* wt = dinv + 4 * 256;   // 3 scratch blocks (inverse_assemble64 runs on at most 3 waves)
-  double* vec = wt + 3 * 256;
-  double* xch = vec + NB;        // 2 NB: exchange buffer of the pipelined tile factorisation
-  int* s_ok = reinterpret_cast<int*>(xch + 2 * NB);
-  int* pf = s_ok + 8;            // its 16 hand-off flags
+  double *S = PanelLds::S(lds), *M = PanelLds::M(lds), *dinv = PanelLds::dinv(lds), *vec = PanelLds::vec(lds);
   WgId wg;
   if (!wg_decode(map, wg)) return;
   const FrameDev& fd = frames[wg.frame];
@@ -497,7 +490,7 @@ __global__ void __launch_bounds__(256) k_fpanel(const FrameDev* __restrict__ fra
   SLM_STAMP(fd, stamp, 1);
   // (factor + inverse in the pipelined form of the task graph; the row blocks d > 0 only need L and the diagonal-block
   //  inverses, which are complete at the same time as with potrf64)
-  const bool ok = factor_inverse64p(S, M, dinv, wt, xch, s_ok, pf, nullptr, nullptr, nullptr, min(4, (f.n1 - c * NB + 15) >> 4));
+  const bool ok = PanelLds::factor(lds, nullptr, nullptr, nullptr, min(4, (f.n1 - c * NB + 15) >> 4));
   SLM_STAMP(fd, stamp, 14);
 
   if (d == 0) {
@@ -529,14 +522,7 @@ __global__ void __launch_bounds__(256) k_fpanel(const FrameDev* __restrict__ fra
 __global__ void __launch_bounds__(256) k_fpotrf(const FrameDev* __restrict__ frames, LevelRef lvl, int c,
                                                  double u_override) {
   extern __shared__ double lds[];
-  double* S = lds;
-  double* M = lds + TILE;
-  double* dinv = lds + 2 * TILE;
-  double* wt = dinv + 4 * 256;   // 3 scratch blocks (inverse_assemble64 runs on at most 3 waves)
-  double* vec = wt + 3 * 256;
-  double* xch = vec + NB;        // 2 NB: exchange buffer of the pipelined tile factorisation
-  int* s_ok = reinterpret_cast<int*>(xch + 2 * NB);
-  int* pf = s_ok + 8;            // its 16 hand-off flags
+  double *S = PanelLds::S(lds), *M = PanelLds::M(lds), *vec = PanelLds::vec(lds);
   const FrameDev& fd = frames[blockIdx.z];
   if (!fd.bound || !fd.nd_ready) return;   // (a stopped slot only wastes the work: no dependent flag load here)
   int fi;
@@ -561,7 +547,7 @@ __global__ void __launch_bounds__(256) k_fpotrf(const FrameDev* __restrict__ fra
     }
   }
   __syncthreads();
-  const bool ok = factor_inverse64p(S, M, dinv, wt, xch, s_ok, pf, nullptr, nullptr, nullptr, min(4, (f.n1 - c * NB + 15) >> 4));
+  const bool ok = PanelLds::factor(lds, nullptr, nullptr, nullptr, min(4, (f.n1 - c * NB + 15) >> 4));
   if (!ok && threadIdx.x == 0) fd.st->chol_fail = 1;
   double* linv = fd.flinv + f.linv_off + (size_t)c * TILE;
   for (int e = threadIdx.x; e < TILE; e += blockDim.x) linv[e] = M[e];
@@ -735,22 +721,14 @@ __device__ __forceinline__ double pull_vec(const FrameDev& fd, const NDTileItem&
 //           X_c = (A(r,c) - sum_{c'<c} X_c' L(c,c')^T) L_cc^-T, results chained in registers
 //           (accumulator layout == next A-fragment layout), rhs row updated at the end.
 // grid k_fL11 = (1, fronts in level, n_frames); k_fL21 = (max boundary tiles, fronts, frames)
-// S (tile being factored; later the B operand of the trailing update), M (its inverse), the four
-// diagonal-block inverses, three 16x16 scratch blocks, two vectors: 80 960 B, two workgroups per CU
-#define L11_LDS_DOUBLES (2 * TILE + 7 * 256 + 2 * NB + 16)   // S, M, dinv, wt, vec | part (= the factorisation's exchange buffer), 32 ints
-
+// LDS: L11Lds (slm_tile.h) -- S is later the B operand of the trailing update; 81 024 B, two workgroups per CU
 __global__ void __launch_bounds__(256, 2) k_fL11(const FrameDev* __restrict__ frames, LevelRef lvl,
                                                double u_override) {
   extern __shared__ double lds[];
-  double* S = lds;
-  double* M = lds + TILE;
-  double* Bl = S;                  // S is dead once its inverse M exists
-  double* dinv = lds + 2 * TILE;
-  double* wt = dinv + 4 * 256;     // 3 blocks: inverse_assemble64 runs on at most 3 waves; diag16 uses 128 doubles
-  double* vec = wt + 3 * 256;      // NB: rhs tile in / y tile out
-  double* part = vec + NB;         // NB scratch
-  int* s_ok = reinterpret_cast<int*>(part + NB);
-  int* pf = s_ok + 8;              // 16 hand-off flags of the pipelined tile factorisation
+  double *S = L11Lds::S(lds), *M = L11Lds::M(lds);
+  double* Bl = L11Lds::Bl(lds);    // S is dead once its inverse M exists
+  double* vec = L11Lds::vec(lds);  // NB: rhs tile in / y tile out
+  double* part = L11Lds::vec2(lds);   // NB scratch
   const FrameDev& fd = frames[blockIdx.z];
   if (!fd.bound || !fd.nd_ready) return;   // (a stopped slot only wastes the work: no dependent flag load here)
   int fi;
@@ -782,7 +760,7 @@ __global__ void __launch_bounds__(256, 2) k_fL11(const FrameDev* __restrict__ fr
     __syncthreads();
     // factor + inverse in the pipelined form of the task graph (wave 0 runs the pivot chain, waves 1-3 trail with the
     // panel / trailing / inverse blocks): 11.7 us per tile against ~14 for potrf64 + inverse_assemble64
-    const bool ok = factor_inverse64p(S, M, dinv, wt, vec, s_ok, pf, nullptr, nullptr, nullptr, min(4, (f.n1 - c * NB + 15) >> 4));
+    const bool ok = L11Lds::factor(lds, nullptr, nullptr, nullptr, min(4, (f.n1 - c * NB + 15) >> 4));
     if (!ok && threadIdx.x == 0) fd.st->chol_fail = 1;
     if (threadIdx.x < NB) vec[threadIdx.x] = rhs_c;
     __syncthreads();

@@ -438,6 +438,63 @@ __device__ __forceinline__ bool factor_inverse64p(double* S, double* M, double* 
   return *s_ok != 0;
 }
 
+// ---- the dynamic LDS of a kernel that factors tiles: ONE description, offsets in doubles from the base ---------------
+//   S | M | dinv (4 blocks of 256) | wt (3 blocks of 256) | NVEC vectors of NB | NINT ints
+// S: the tile being factored, M: its inverse; both double as operand staging tiles (Bl) outside a factorisation.
+// xch, the factorisation's exchange buffer (2 NB), is the LAST TWO vectors: with NVEC == 2 it is vec | vec2, with
+// NVEC == 3 vec survives a factorisation.  Declared aliases -- none of them is live while a tile is being factored:
+//   part (4 NB row partials) over wt, maps (256 int2 extend-add maps) over dinv, Bl over S.
+// The ints: the factorisation's verdict, the task loop's words (slm_dag.hip), four wave votes, and the 16 hand-off flags of
+// the factorisation's trailing waves.  Two workgroups per CU depend on the sizes: they are asserted below.
+template <int NVEC, int NINT = 32>
+struct TileLds {
+  static_assert(NVEC >= 2, "the exchange buffer is the last two vectors");
+  enum : int {   // the regions: sizes and offsets in doubles
+    DINV_DOUBLES = 4 * 256, WT_DOUBLES = 3 * 256,
+    S_AT = 0, M_AT = TILE, DINV_AT = 2 * TILE, WT_AT = DINV_AT + DINV_DOUBLES, VEC_AT = WT_AT + WT_DOUBLES,
+    XCH_AT = VEC_AT + (NVEC - 2) * NB, INT_AT = VEC_AT + NVEC * NB, DOUBLES = INT_AT + NINT / 2
+  };
+  enum : int {   // the int block: indices from INT_AT (INT_VOTES: 4 ints, INT_PF: 16 ints)
+    INT_OK = 0, INT_TASK = 1, INT_ABORT = 2, INT_CNT = 3, INT_VOTES = 4, INT_PF = 8
+  };
+  static_assert(NINT % 2 == 0 && INT_PF + 16 <= NINT, "the int block and pf lie inside the size");
+  static_assert(256 * sizeof(int2) <= DINV_DOUBLES * sizeof(double), "maps (256 int2) fit in dinv");
+  static_assert(4 * NB <= WT_DOUBLES, "part (4 NB) fits in wt");
+  // the regions, from the base of the kernel's dynamic LDS (static, the base an argument: with the base kept in a member the
+  // POTRF task of slm_dag.hip came out with 44 B more scratch per lane -- docs/LAB_NOTEBOOK.md, "one task context")
+  static __device__ __forceinline__ double* S(double* lds) { return lds + S_AT; }
+  static __device__ __forceinline__ double* M(double* lds) { return lds + M_AT; }
+  static __device__ __forceinline__ double* Bl(double* lds) { return S(lds); }
+  static __device__ __forceinline__ double* dinv(double* lds) { return lds + DINV_AT; }
+  static __device__ __forceinline__ int2* maps(double* lds) { return reinterpret_cast<int2*>(dinv(lds)); }
+  static __device__ __forceinline__ double* wt(double* lds) { return lds + WT_AT; }
+  static __device__ __forceinline__ double* part(double* lds) { return wt(lds); }
+  static __device__ __forceinline__ double* vec(double* lds) { return lds + VEC_AT; }
+  static __device__ __forceinline__ double* vec2(double* lds) { return vec(lds) + NB; }
+  static __device__ __forceinline__ double* xch(double* lds) { return lds + XCH_AT; }
+  static __device__ __forceinline__ int* ints(double* lds) { return reinterpret_cast<int*>(lds + INT_AT); }
+  static __device__ __forceinline__ int* s_ok(double* lds) { return ints(lds) + INT_OK; }
+  static __device__ __forceinline__ int* s_task(double* lds) { return ints(lds) + INT_TASK; }
+  static __device__ __forceinline__ int* s_abort(double* lds) { return ints(lds) + INT_ABORT; }
+  static __device__ __forceinline__ int* s_cnt(double* lds) { return ints(lds) + INT_CNT; }
+  static __device__ __forceinline__ int* votes(double* lds) { return ints(lds) + INT_VOTES; }
+  static __device__ __forceinline__ int* pf(double* lds) { return ints(lds) + INT_PF; }
+  // factor_inverse64p on this layout (look_ahead: see there -- the staged block lies at dinv + 256, the row partials in wt)
+  static __device__ __forceinline__ bool factor(double* lds, double* g_mail = nullptr, int* g_early = nullptr, long long* trc = nullptr,
+                                                int nblk = 4, bool look_ahead = false, double* la_sum = nullptr) {
+    return factor_inverse64p(S(lds), M(lds), dinv(lds), wt(lds), xch(lds), s_ok(lds), pf(lds), g_mail, g_early, trc, nblk,
+                             look_ahead ? dinv(lds) + 256 : nullptr, look_ahead ? wt(lds) : nullptr, la_sum);
+  }
+};
+typedef TileLds<3> PanelLds;       // k_fpanel, k_fpotrf, k_panel: vec + the exchange buffer
+typedef TileLds<2> L11Lds;         // k_fL11: vec | part are the exchange buffer
+typedef TileLds<2, 48> DagLds;     // k_fdag: vec | yv are the exchange buffer (48 ints: the launch size it has always had)
+#define PANEL_LDS_DOUBLES (PanelLds::DOUBLES)
+#define L11_LDS_DOUBLES (L11Lds::DOUBLES)
+#define DAG_LDS_DOUBLES (DagLds::DOUBLES)
+static_assert(PANEL_LDS_DOUBLES * 8 == 81536 && L11_LDS_DOUBLES * 8 == 81024 && DAG_LDS_DOUBLES * 8 == 81088,
+              "launch sizes: two workgroups per CU (160 KB of LDS) were measured with these");
+
 // C(64x64) = Cinit + sign * A B^T with B staged in LDS (Bl, ld LD) and the A fragments /
 // C tile of this wave's 16 rows already in registers (loaded by the caller so that the
 // global loads overlap whatever precedes).  Wave w owns rows [16w, 16w+16).
@@ -519,9 +576,6 @@ __device__ __forceinline__ void store_c_frags(double* __restrict__ Cg, const dou
 #pragma unroll
     for (int r = 0; r < 4; ++r) Cg[(16 * w + lr) + (size_t)(16 * ni + lk + 4 * r) * NB] = acc[ni][r];
 }
-
-// S, M, 4 diagonal-block inverses, 3 scratch blocks, one vector: 80 448 B -> two workgroups per CU
-#define PANEL_LDS_DOUBLES (2 * TILE + 7 * 256 + 3 * NB + 16)   // ... + vec, the factorisation's exchange buffer (2 NB), 32 ints: 81 536 B
 
 // Rows [16w,16w+16) of X = A L^-T for one 64x64 tile, blockwise forward substitution on
 // the MFMA with everything in registers: x[kb] / a[kb] are 16x16 blocks in accumulator
