@@ -272,29 +272,36 @@ __global__ void __launch_bounds__(256) k_reg_grad_nd(const FrameDev* __restrict_
   if (use_arap && slot < Ke) {
     // ---- cross block between the nodes of edge j -> k ----
     const int k = frame_in(fd).ed_knn_idx[j * Ke + slot];
-    if (k >= 0 && k < J && k != j) {
+    // A row that lists k more than once (a node KNN table that did not come from a top-k): the lane of the first such slot
+    // writes the block for all of them -- two lanes would read-modify-write the same entries
+    int mult = 0, first = slot;
+    for (int s2 = Ke - 1; s2 >= 0; --s2)
+      if (frame_in(fd).ed_knn_idx[j * Ke + s2] == k) { ++mult; first = s2; }
+    if (k >= 0 && k < J && k != j && first == slot) {
       const NDDest pd = fd.pair_dest[j * Ke + slot];   // block (max(j,k), min(j,k))
       const NDFront fp = fd.fronts[pd.front];
       const int prb = nd_base(fp, pd.prow), pcb = nd_base(fp, pd.pcol);
       const bool k_is_row = ((k > j) != (pd.transpose != 0));   // is node k the ROW node of the stored block?
       double r[3], Jq[3][4];
       nd_arap_edge(fd, j, k, lam_a, r, Jq);
-      // the reverse edge k -> j (if it exists) shares the three (translation, translation) entries:
-      // the edge with the smaller source node writes them for both
-      bool reverse = false;
-      for (int s2 = 0; s2 < Ke; ++s2) reverse = reverse || frame_in(fd).ed_knn_idx[k * Ke + s2] == j;
+      // the reverse edges k -> j (if any) share the three (translation, translation) entries:
+      // the side with the smaller source node writes them for both
+      int rev = 0;
+      for (int s2 = 0; s2 < Ke; ++s2) rev += frame_in(fd).ed_knn_idx[k * Ke + s2] == j;
+      const bool reverse = rev > 0;
+      const double m = (double)mult;
       double* dst[15];
       double add[15];
 #pragma unroll
       for (int c = 0; c < 3; ++c) {
 #pragma unroll
         for (int a = 0; a < 4; ++a) {
-          add[4 * c + a] = -l2 * Jq[c][a];                       // between (k, a) and (j, 4+c)
+          add[4 * c + a] = -l2 * Jq[c][a] * m;                   // between (k, a) and (j, 4+c)
           dst[4 * c + a] = k_is_row ? front_entry(fd, fp, prb + a, pcb + 4 + c) : front_entry(fd, fp, prb + 4 + c, pcb + a);
         }
         const bool mine = !reverse || j < k;
         dst[12 + c] = mine ? front_entry(fd, fp, prb + 4 + c, pcb + 4 + c) : nullptr;   // between (k, 4+c) and (j, 4+c)
-        add[12 + c] = reverse ? -2.0 * l2 : -l2;
+        add[12 + c] = -l2 * (double)(mult + rev);
       }
       // all loads before the first store: the destinations are distinct but the compiler cannot know
       double cur[15];

@@ -1,5 +1,7 @@
 // Host-only harness around the symbolic analysis (python-super_amd/csrc/slm_nd_host.hip): builds the plan of a coupling
-// graph handed over by tools/studies/nd_order_study.py and returns its cost figures.  Study tool, not part of the library.
+// graph handed over by tools/studies/nd_order_study.py and returns its cost figures.  Study tool, not part of the library --
+// but a TEST DEPENDENCY: tests/test_nd_host_sanitized.py (nd_stats, nd_check_*) and tests/solver_graph_cases.py (nd_node_fronts)
+// build this file with slm_nd_host.hip for the host and call it through ctypes; keep those entry points' signatures.
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
@@ -191,6 +193,26 @@ extern "C" int nd_check_frame_dests(int J, int K_ED, const float* pts, const int
       if (reached_is_pure(p.node_front[j], p.node_pos[j], p.node_pos[j])) return 4;
   }
   return 0;
+}
+
+// Where the plan eliminates every node: node_front[j] / node_pos[j] = the front that has node j as a pivot and its local
+// position there, for a graph dissected down to leaf_nodes (0: SLM_ND_LEAF); fronts[3 i] / [3 i + 1] / [3 i + 2] = depth, pivot count
+// and is_leaf of front i.  Fronts are numbered in processing order, deepest level first: the root is the last one.  Returns their number.
+extern "C" int nd_node_fronts(int J, int K_ED, const float* pts, const int32_t* knn, const uint32_t* pairs, int n_pairs,
+                              int leaf_nodes, int32_t* node_front, int32_t* node_pos, int32_t* fronts, int max_fronts) {
+  NDPlanHost p;
+  if (!nd_build_plan(J, K_ED, pts, knn, pairs, n_pairs, p, leaf_nodes)) return -1;
+  for (int j = 0; j < J; ++j) {
+    node_front[j] = p.node_front[j];
+    node_pos[j] = p.node_pos[j];
+  }
+  const int n = (int)p.fronts.size();
+  for (int i = 0; i < n && i < max_fronts; ++i) {
+    fronts[3 * i] = p.fronts[i].depth;
+    fronts[3 * i + 1] = p.fronts[i].nv;
+    fronts[3 * i + 2] = p.fronts[i].is_leaf;
+  }
+  return n;
 }
 
 extern "C" int nd_stats(int J, int K_ED, const float* pts, const int32_t* knn, const uint32_t* pairs, int n_pairs,
