@@ -48,27 +48,6 @@ __global__ void __launch_bounds__(256) k_bandwidth(slm_frame f, int* __restrict_
   if ((threadIdx.x & 63) == 0 && wmax > 0) atomicMax(out, wmax);
 }
 
-// Load the lower triangle of diagonal tile c into LDS with damping u and unit padding rows.
-// All 16 global loads of a thread are issued before the first LDS store (one memory
-// round trip instead of sixteen).
-__device__ __forceinline__ void load_diag_tile(const FrameDev& fd, int c, double u, double* S) {
-  const double* src = fd.band + (size_t)c * (fd.wb + 1) * TILE;
-  double v[16];
-#pragma unroll
-  for (int t = 0; t < 16; ++t) v[t] = src[threadIdx.x + 256 * t];
-#pragma unroll
-  for (int t = 0; t < 16; ++t) {
-    const int e = threadIdx.x + 256 * t;
-    const int i = e % NB, k = e / NB;
-    double x = (i >= k) ? v[t] : 0.0;
-    if (i == k) {
-      const int gi = c * NB + i;
-      x = (gi < fd.P) ? x + u : 1.0;
-    }
-    S[i + k * LD] = x;
-  }
-}
-
 // grid = (wb_cap + 1, n_frames), 256 threads
 __global__ void __launch_bounds__(256) k_panel(const FrameDev* __restrict__ frames, int c,
                                                 double u_override) {
@@ -82,47 +61,20 @@ __global__ void __launch_bounds__(256) k_panel(const FrameDev* __restrict__ fram
   const double u = (u_override >= 0.0) ? u_override : fd.st->u;
   const bool stamp = (c == 8 && blockIdx.y == 0 && d == 1);
   SLM_STAMP(fd, stamp, 0);
-
-  // issue this block's own global loads first so they overlap the factorisation
-  const int l = threadIdx.x & 63, w = threadIdx.x >> 6, lr = l & 15, lk = l >> 4;
-  double* At = fd.band + ((size_t)c * (fd.wb + 1) + d) * TILE;
+  const size_t col = (size_t)c * (fd.wb + 1);
+  double* At = fd.band + (col + d) * TILE;
+  double* yv = fd.rhs + (size_t)c * NB;
   double4_t a[4];
-  if (d > 0) {
-#pragma unroll
-    for (int kb = 0; kb < 4; ++kb)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) a[kb][r] = At[(16 * w + lr) + (size_t)(16 * kb + lk + 4 * r) * NB];
-  } else if (threadIdx.x < NB) {
-    vec[threadIdx.x] = fd.rhs[(size_t)c * NB + threadIdx.x];
-  }
-
-  load_diag_tile(fd, c, u, S);
-  __syncthreads();
+  panel_column_stage(d, At, yv, fd.band + col * TILE, c * NB, fd.P, u, S, vec, a);
   SLM_STAMP(fd, stamp, 1);
   const bool ok = potrf64(S, dinv, wt, s_ok, fd, stamp);
   SLM_STAMP(fd, stamp, 14);
-
   if (d == 0) {
     if (!ok && threadIdx.x == 0) fd.st->chol_fail = 1;
     // full inverse of the diagonal block: used by the substitutions (one parallel matvec each)
     inverse_assemble64(S, M, dinv, wt);
-    double* linv = fd.linv + (size_t)c * TILE;
-    for (int e = threadIdx.x; e < TILE; e += blockDim.x) linv[e] = M[e];
-    // forward substitution of this block row: y_c = L^-1 b_c
-    if (threadIdx.x < NB) {
-      const int i = threadIdx.x;
-      double acc = 0.0;
-      for (int k = 0; k <= i; ++k) acc += M[i + k * LD] * vec[k];
-      fd.rhs[(size_t)c * NB + i] = acc;
-    }
-  } else {
-    // L(c+d, c) = A(c+d, c) L^-T
-    trsm_rows16(S, dinv, a);
-#pragma unroll
-    for (int kb = 0; kb < 4; ++kb)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) At[(16 * w + lr) + (size_t)(16 * kb + lk + 4 * r) * NB] = a[kb][r];
   }
+  panel_column_finish(d, At, yv, fd.linv + (size_t)c * TILE, S, M, dinv, vec, a);
   SLM_STAMP(fd, stamp, 15);
 }
 
@@ -134,6 +86,7 @@ __global__ void __launch_bounds__(256) k_trail(const FrameDev* __restrict__ fram
   if (!fd.bound || fd.st->stopped || c >= fd.nt) return;
   const int ntri = wb_cap * (wb_cap + 1) / 2;
   int t = blockIdx.x;
+  const size_t col = (size_t)c * (fd.wb + 1);
   if (t < ntri) {
     // (a,b), 1 <= b <= a <= wb_cap, row-major over the lower triangle
     int a = (int)((sqrt(8.0 * t + 1.0) - 1.0) * 0.5);
@@ -142,40 +95,16 @@ __global__ void __launch_bounds__(256) k_trail(const FrameDev* __restrict__ fram
     const int b = t - a * (a + 1) / 2;
     const int da = a + 1, db = b + 1;
     if (da > fd.wb || c + da >= fd.nt) return;
-    const size_t col = (size_t)c * (fd.wb + 1);
-    const double* Lr = fd.band + (col + da) * TILE;
-    const double* Ls = fd.band + (col + db) * TILE;
-    double* Ct = fd.band + ((size_t)(c + db) * (fd.wb + 1) + (da - db)) * TILE;
-    // all global loads up front: B tile -> LDS (16 doubles per thread), A fragments and C -> registers
-    double breg[16];
-#pragma unroll
-    for (int e = 0; e < 16; ++e) breg[e] = Ls[threadIdx.x + 256 * e];
-    double areg[16];
-    load_a_frags(Lr, areg);
-    double4_t acc[4];
-    load_c_frags(Ct, acc);
-#pragma unroll
-    for (int e = 0; e < 16; ++e) Bl[threadIdx.x + 256 * e] = breg[e];
-    __syncthreads();
-    tile_ABt_regs<true>(areg, Bl, acc);
-    store_c_frags(Ct, acc);
+    // A(c+da, c+db) -= L(c+da, c) L(c+db, c)^T
+    tile_product<true, false, true>(fd.band + (col + db) * TILE, fd.band + (col + da) * TILE,
+                                    fd.band + ((size_t)(c + db) * (fd.wb + 1) + (da - db)) * TILE, Bl);
   } else {
     // rhs: b_s -= L(s,c) y_c, s = c + db
     const int db = t - ntri + 1;
     if (db > fd.wb || c + db >= fd.nt) return;
     __shared__ double y[NB];
-    __shared__ double part[4][NB];
-    const double* Ls = fd.band + ((size_t)c * (fd.wb + 1) + db) * TILE;
-    if (threadIdx.x < NB) y[threadIdx.x] = fd.rhs[(size_t)c * NB + threadIdx.x];
-    __syncthreads();
-    const int i = threadIdx.x & 63, q = threadIdx.x >> 6;
-    double acc = 0.0;
-#pragma unroll
-    for (int k = 16 * q; k < 16 * q + 16; ++k) acc += Ls[i + k * NB] * y[k];
-    part[q][i] = acc;
-    __syncthreads();
-    if (threadIdx.x < NB)
-      fd.rhs[(size_t)(c + db) * NB + i] -= part[0][i] + part[1][i] + part[2][i] + part[3][i];
+    __shared__ double part[4 * NB];
+    trail_rhs(fd.band + (col + db) * TILE, fd.rhs + (size_t)c * NB, fd.rhs + (size_t)(c + db) * NB, y, part);
   }
 }
 
@@ -189,31 +118,13 @@ __global__ void __launch_bounds__(256) k_backsub(const FrameDev* __restrict__ fr
   if (d > fd.wb || c - d < 0) return;
   __shared__ double y[NB];
   __shared__ double x[NB];
-  __shared__ double part[4][NB];
-  const double* linv = fd.linv + (size_t)c * TILE;
-  if (threadIdx.x < NB) y[threadIdx.x] = fd.rhs[(size_t)c * NB + threadIdx.x];
-  __syncthreads();
-  {
-    // x_c = L^-T y_c : x[k] = sum_{i>=k} Linv[i][k] y[i]
-    const int k = threadIdx.x & 63, q = threadIdx.x >> 6;
-    double acc = 0.0;
-    for (int i = 16 * q; i < 16 * q + 16; ++i) acc += linv[i + k * NB] * y[i];
-    part[q][k] = acc;
-    __syncthreads();
-    if (threadIdx.x < NB) x[k] = part[0][k] + part[1][k] + part[2][k] + part[3][k];
-    __syncthreads();
-  }
+  __shared__ double part[4 * NB];
+  backsub_x(fd.linv + (size_t)c * TILE, fd.rhs + (size_t)c * NB, y, x, part);
   if (d == 0) {
     if (threadIdx.x < NB) fd.delta[(size_t)c * NB + threadIdx.x] = x[threadIdx.x];
   } else {
-    // y_(c-d) -= L(c, c-d)^T x_c ; tile (c, c-d) is at column c-d, offset d
-    const double* Lt = fd.band + ((size_t)(c - d) * (fd.wb + 1) + d) * TILE;
-    const int n = threadIdx.x >> 2, q = threadIdx.x & 3;
-    double acc = 0.0;
-    for (int mrow = 16 * q; mrow < 16 * q + 16; ++mrow) acc += Lt[mrow + n * NB] * x[mrow];
-    acc += __shfl_xor(acc, 1, 64);
-    acc += __shfl_xor(acc, 2, 64);
-    if (q == 0) fd.rhs[(size_t)(c - d) * NB + n] -= acc;
+    // tile (c, c-d) is at column c-d, offset d
+    backsub_update(fd.band + ((size_t)(c - d) * (fd.wb + 1) + d) * TILE, x, fd.rhs + (size_t)(c - d) * NB);
   }
 }
 
@@ -265,11 +176,7 @@ void launch_bandwidth(const slm_frame& f, int* out_dev, hipStream_t st) {
 void launch_band_solve(const FrameDev* frames_dev, int n_frames, int nt_max, int wb_cap,
                        double u_override, hipStream_t st) {
   const size_t lds = PANEL_LDS_DOUBLES * sizeof(double);
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)k_panel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set = true;
-  }
+  if (!ensure_dynamic_lds((const void*)k_panel, lds)) return;   // (sticky HIP error: the caller's hipGetLastError reports it)
   const int ntrail = wb_cap * (wb_cap + 1) / 2 + wb_cap;
   for (int c = 0; c < nt_max; ++c) {
     hipLaunchKernelGGL(k_panel, dim3(wb_cap + 1, n_frames), dim3(256), lds, st, frames_dev, c,

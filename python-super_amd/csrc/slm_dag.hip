@@ -952,18 +952,14 @@ __device__ __noinline__ void dag_task_factor(const FrameDev* __restrict__ frames
 #pragma unroll
             for (int rr = 0; rr < 4; ++rr) {
               const int i = 16 * w + lr, k = 16 * ni + lk + 4 * rr;
-              double x = (i >= k) ? acc[ni][rr] : 0.0;
-              if (i == k) x = (s * NB + i < f.n1) ? x + u : 1.0;
-              S[i + k * LD] = x;
+              S[i + k * LD] = damped_lower(acc[ni][rr], i, k, s * NB, f.n1, u);
             }
         } else {
           // wave 0: its diagonal block on its own (dinv + 256, ld 16: the mailbox copies there are spent)
 #pragma unroll
           for (int rr = 0; rr < 4; ++rr) {
             const int i = lr, k = lk + 4 * rr;
-            double x = (i >= k) ? acc[0][rr] : 0.0;
-            if (i == k) x = (s * NB + i < f.n1) ? x + u : 1.0;
-            dinv[256 + i + 16 * k] = x;
+            dinv[256 + i + 16 * k] = damped_lower(acc[0][rr], i, k, s * NB, f.n1, u);
           }
           wave_sync();
         }
@@ -1456,7 +1452,7 @@ int dag_device_setup(int dev, int* xcd8_out) {
   int xcd8 = tracked ? g_dag_dev[dev].xcd8.load(std::memory_order_acquire) : 2;
   if (n_wg == 0) {
     const size_t lds = DAG_LDS_DOUBLES * sizeof(double);
-    if (hipFuncSetAttribute((const void*)k_fdag, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return 0;   // (the launch would fail: hipGetLastError reports it)
+    if (!ensure_dynamic_lds((const void*)k_fdag, lds)) return 0;   // (the launch would fail: hipGetLastError reports it)
     int cus = 256;
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     const char* e = getenv("SLM_DAG_WG_PER_CU");

@@ -86,6 +86,38 @@ __device__ __forceinline__ bool wg_decode(const WgMap& m, WgId& o) {
   o.frame = pair / m.n_fronts;
   return q < chunk && pair < n_pairs;
 }
+// The prologue of the level kernels: the workgroup's frame, its front of the level and its unit (tile, row, column: the
+// kernel's own meaning), from a WgMap or from the plain 3-D grid; `c` is the pivot tile column the workgroup needs.  False:
+// the workgroup has nothing to do.  (A stopped slot only wastes the work: no dependent flag load here.)
+struct LevelCtx {
+  const FrameDev* fd;
+  const NDFront* f;
+  int unit, front, frame;
+};
+__device__ __forceinline__ bool level_ctx(const FrameDev* __restrict__ frames, const LevelRef& lvl, int c, LevelCtx& o) {
+  const FrameDev& fd = frames[o.frame];
+  if (!fd.bound || !fd.nd_ready) return false;
+  int fi;
+  if (!level_front(fd, lvl, o.front, fi)) return false;
+  o.fd = &fd;
+  o.f = &fd.fronts[fi];
+  return c < o.f->npt;
+}
+__device__ __forceinline__ bool level_begin(const FrameDev* __restrict__ frames, const LevelRef& lvl, int c, LevelCtx& o) {
+  o.unit = blockIdx.x;
+  o.front = blockIdx.y;
+  o.frame = blockIdx.z;
+  return level_ctx(frames, lvl, c, o);
+}
+__device__ __forceinline__ bool level_begin(const FrameDev* __restrict__ frames, const LevelRef& lvl, int c, const WgMap& map,
+                                            LevelCtx& o) {
+  WgId wg;
+  if (!wg_decode(map, wg)) return false;
+  o.unit = wg.unit;
+  o.front = wg.front;
+  o.frame = wg.frame;
+  return level_ctx(frames, lvl, c, o);
+}
 static inline WgMap make_map(int n_units, int n_fronts, int n_frames) {
   return WgMap{n_units, n_fronts, n_frames, (n_fronts * n_frames >= 8) ? 1 : 0};
 }
@@ -452,71 +484,26 @@ __global__ void __launch_bounds__(256) k_fpanel(const FrameDev* __restrict__ fra
                                                  int c, double u_override, WgMap map) {
   extern __shared__ double lds[];
   double *S = PanelLds::S(lds), *M = PanelLds::M(lds), *dinv = PanelLds::dinv(lds), *vec = PanelLds::vec(lds);
-  WgId wg;
-  if (!wg_decode(map, wg)) return;
-  const FrameDev& fd = frames[wg.frame];
-  if (!fd.bound || !fd.nd_ready) return;   // (a stopped slot only wastes the work: no dependent flag load here)
-  int fi;
-  if (!level_front(fd, lvl, wg.front, fi)) return;
-  const NDFront& f = fd.fronts[fi];
-  if (c >= f.npt) return;
-  const int d = wg.unit;
+  LevelCtx cx;
+  if (!level_begin(frames, lvl, c, map, cx)) return;
+  const FrameDev& fd = *cx.fd;
+  const NDFront& f = *cx.f;
+  const int d = cx.unit;
   if (c + d >= f.nt) return;
   const double u = (u_override >= 0.0) ? u_override : fd.st->u;
-
-  const int l = threadIdx.x & 63, w = threadIdx.x >> 6, lr = l & 15, lk = l >> 4;
-  const bool stamp = (c == 1 && wg.frame == 0 && wg.front == 0 && d == 1 && lvl.level == fd.n_levels - 1);
+  const bool stamp = (c == 1 && cx.frame == 0 && cx.front == 0 && d == 1 && lvl.level == fd.n_levels - 1);
   SLM_STAMP(fd, stamp, 0);
   double* At = ftile(fd, f, c + d, c);
   double* yv = fd.fvec + f.vec_off + (size_t)c * NB;
   double4_t a[4];
-  if (d > 0) {
-#pragma unroll
-    for (int kb = 0; kb < 4; ++kb)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) a[kb][r] = At[(16 * w + lr) + (size_t)(16 * kb + lk + 4 * r) * NB];
-  } else if (threadIdx.x < NB) {
-    vec[threadIdx.x] = yv[threadIdx.x];
-  }
-  {
-    // diagonal tile -> LDS: damping on real pivots, identity on the padding rows
-    const double* src = ftile(fd, f, c, c);
-    double v[16];
-#pragma unroll
-    for (int t = 0; t < 16; ++t) v[t] = src[threadIdx.x + 256 * t];
-#pragma unroll
-    for (int t = 0; t < 16; ++t) {
-      const int e = threadIdx.x + 256 * t;
-      const int i = e % NB, k = e / NB;
-      double x = (i >= k) ? v[t] : 0.0;
-      if (i == k) x = (c * NB + i < f.n1) ? x + u : 1.0;
-      S[i + k * LD] = x;
-    }
-  }
-  __syncthreads();
+  panel_column_stage(d, At, yv, ftile(fd, f, c, c), c * NB, f.n1, u, S, vec, a);
   SLM_STAMP(fd, stamp, 1);
   // (factor + inverse in the pipelined form of the task graph; the row blocks d > 0 only need L and the diagonal-block
   //  inverses, which are complete at the same time as with potrf64)
   const bool ok = PanelLds::factor(lds, nullptr, nullptr, nullptr, min(4, (f.n1 - c * NB + 15) >> 4));
   SLM_STAMP(fd, stamp, 14);
-
-  if (d == 0) {
-    if (!ok && threadIdx.x == 0) fd.st->chol_fail = 1;
-    double* linv = fd.flinv + f.linv_off + (size_t)c * TILE;
-    for (int e = threadIdx.x; e < TILE; e += blockDim.x) linv[e] = M[e];
-    if (threadIdx.x < NB) {
-      const int i = threadIdx.x;
-      double acc = 0.0;
-      for (int k = 0; k <= i; ++k) acc += M[i + k * LD] * vec[k];
-      yv[i] = acc;
-    }
-  } else {
-    trsm_rows16(S, dinv, a);
-#pragma unroll
-    for (int kb = 0; kb < 4; ++kb)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) At[(16 * w + lr) + (size_t)(16 * kb + lk + 4 * r) * NB] = a[kb][r];
-  }
+  if (d == 0 && !ok && threadIdx.x == 0) fd.st->chol_fail = 1;
+  panel_column_finish(d, At, yv, fd.flinv + f.linv_off + (size_t)c * TILE, S, M, dinv, vec, a);
   SLM_STAMP(fd, stamp, 15);
 }
 
@@ -529,71 +516,31 @@ __global__ void __launch_bounds__(256) k_fpanel(const FrameDev* __restrict__ fra
 __global__ void __launch_bounds__(256) k_fpotrf(const FrameDev* __restrict__ frames, LevelRef lvl, int c,
                                                  double u_override) {
   extern __shared__ double lds[];
-  double *S = PanelLds::S(lds), *M = PanelLds::M(lds), *vec = PanelLds::vec(lds);
-  const FrameDev& fd = frames[blockIdx.z];
-  if (!fd.bound || !fd.nd_ready) return;   // (a stopped slot only wastes the work: no dependent flag load here)
-  int fi;
-  if (!level_front(fd, lvl, blockIdx.y, fi)) return;
-  const NDFront& f = fd.fronts[fi];
-  if (c >= f.npt) return;
+  double *S = PanelLds::S(lds), *M = PanelLds::M(lds), *dinv = PanelLds::dinv(lds), *vec = PanelLds::vec(lds);
+  LevelCtx cx;
+  if (!level_begin(frames, lvl, c, cx)) return;
+  const FrameDev& fd = *cx.fd;
+  const NDFront& f = *cx.f;
   const double u = (u_override >= 0.0) ? u_override : fd.st->u;
   double* yv = fd.fvec + f.vec_off + (size_t)c * NB;
-  if (threadIdx.x < NB) vec[threadIdx.x] = yv[threadIdx.x];
-  {
-    const double* src = ftile(fd, f, c, c);
-    double v[16];
-#pragma unroll
-    for (int t = 0; t < 16; ++t) v[t] = src[threadIdx.x + 256 * t];
-#pragma unroll
-    for (int t = 0; t < 16; ++t) {
-      const int e = threadIdx.x + 256 * t;
-      const int i = e % NB, k = e / NB;
-      double x = (i >= k) ? v[t] : 0.0;
-      if (i == k) x = (c * NB + i < f.n1) ? x + u : 1.0;
-      S[i + k * LD] = x;
-    }
-  }
-  __syncthreads();
+  double4_t a[4];   // (the d == 0 body: no row tile)
+  panel_column_stage(0, nullptr, yv, ftile(fd, f, c, c), c * NB, f.n1, u, S, vec, a);
   const bool ok = PanelLds::factor(lds, nullptr, nullptr, nullptr, min(4, (f.n1 - c * NB + 15) >> 4));
   if (!ok && threadIdx.x == 0) fd.st->chol_fail = 1;
-  double* linv = fd.flinv + f.linv_off + (size_t)c * TILE;
-  for (int e = threadIdx.x; e < TILE; e += blockDim.x) linv[e] = M[e];
-  if (threadIdx.x < NB) {
-    const int i = threadIdx.x;
-    double acc = 0.0;
-    for (int k = 0; k <= i; ++k) acc += M[i + k * LD] * vec[k];
-    yv[i] = acc;
-  }
+  panel_column_finish(0, nullptr, yv, fd.flinv + f.linv_off + (size_t)c * TILE, S, M, dinv, vec, a);
 }
 
 // grid = (max tiles below, fronts in level, n_frames): block d-1 -> tile (c+d, c)
 __global__ void __launch_bounds__(256) k_ftrsm(const FrameDev* __restrict__ frames, LevelRef lvl, int c, WgMap map) {
   __shared__ double Bl[TILE];
-  WgId wg;
-  if (!wg_decode(map, wg)) return;
-  const FrameDev& fd = frames[wg.frame];
-  if (!fd.bound || !fd.nd_ready) return;   // (a stopped slot only wastes the work: no dependent flag load here)
-  int fi;
-  if (!level_front(fd, lvl, wg.front, fi)) return;
-  const NDFront& f = fd.fronts[fi];
-  if (c >= f.npt) return;
-  const int d = wg.unit + 1;
+  LevelCtx cx;
+  if (!level_begin(frames, lvl, c, map, cx)) return;
+  const FrameDev& fd = *cx.fd;
+  const NDFront& f = *cx.f;
+  const int d = cx.unit + 1;
   if (c + d >= f.nt) return;
   double* At = ftile(fd, f, c + d, c);
-  const double* linv = fd.flinv + f.linv_off + (size_t)c * TILE;
-  double breg[16];
-#pragma unroll
-  for (int e = 0; e < 16; ++e) breg[e] = linv[threadIdx.x + 256 * e];
-  double areg[16];
-  load_a_frags(At, areg);
-#pragma unroll
-  for (int e = 0; e < 16; ++e) Bl[threadIdx.x + 256 * e] = breg[e];
-  __syncthreads();
-  double4_t acc[4];
-#pragma unroll
-  for (int ni = 0; ni < 4; ++ni) acc[ni] = double4_t{0.0, 0.0, 0.0, 0.0};
-  tile_ABt_regs<false, true>(areg, Bl, acc);   // A (L^-1)^T
-  store_c_frags(At, acc);
+  tile_product<false, true, false>(fd.flinv + f.linv_off + (size_t)c * TILE, At, At, Bl);   // A (L^-1)^T
 }
 
 // ---- pull-form extend-add (the data flow of the task graph, slm_dag.hip, in the per-level kernels) ---------------
@@ -736,12 +683,10 @@ __global__ void __launch_bounds__(256, 2) k_fL11(const FrameDev* __restrict__ fr
   double* Bl = L11Lds::Bl(lds);    // S is dead once its inverse M exists
   double* vec = L11Lds::vec(lds);  // NB: rhs tile in / y tile out
   double* part = L11Lds::vec2(lds);   // NB scratch
-  const FrameDev& fd = frames[blockIdx.z];
-  if (!fd.bound || !fd.nd_ready) return;   // (a stopped slot only wastes the work: no dependent flag load here)
-  int fi;
-  if (!level_front(fd, lvl, blockIdx.y, fi)) return;
-  const NDFront& f = fd.fronts[fi];
-  if (f.npt == 0) return;
+  LevelCtx cx;
+  if (!level_begin(frames, lvl, 0, cx)) return;
+  const FrameDev& fd = *cx.fd;
+  const NDFront& f = *cx.f;
   const double u = (u_override >= 0.0) ? u_override : fd.st->u;
   double* vecs = fd.fvec + f.vec_off;
   const int w = threadIdx.x >> 6, l = threadIdx.x & 63, lr = l & 15, lk = l >> 4;
@@ -750,11 +695,10 @@ __global__ void __launch_bounds__(256, 2) k_fL11(const FrameDev* __restrict__ fr
     // ---- diagonal tile: factor + inverse + forward substitution of rhs tile c ----
     double rhs_c = 0.0;
     {
-      const double* src = ftile(fd, f, c, c);
       double v[16];
-#pragma unroll
-      for (int t = 0; t < 16; ++t) v[t] = src[threadIdx.x + 256 * t];
+      tile_to_regs(ftile(fd, f, c, c), v);
       if (threadIdx.x < NB) rhs_c = vecs[(size_t)c * NB + threadIdx.x];   // (kept in a register: vec | part is the factorisation's exchange buffer)
+      // (damped_lower's rule in inline text: through regs_to_diag_tile this kernel spills two more SGPRs, 109 against 107)
 #pragma unroll
       for (int t = 0; t < 16; ++t) {
         const int e = threadIdx.x + 256 * t;
@@ -772,14 +716,7 @@ __global__ void __launch_bounds__(256, 2) k_fL11(const FrameDev* __restrict__ fr
     if (threadIdx.x < NB) vec[threadIdx.x] = rhs_c;
     __syncthreads();
     {
-      double* linv = fd.flinv + f.linv_off + (size_t)c * TILE;
-      for (int e = threadIdx.x; e < TILE; e += blockDim.x) linv[e] = M[e];
-      if (threadIdx.x < NB) {
-        const int i = threadIdx.x;
-        double acc = 0.0;
-        for (int k = 0; k <= i; ++k) acc += M[i + k * LD] * vec[k];
-        part[i] = acc;
-      }
+      commit_pivot(M, vec, fd.flinv + f.linv_off + (size_t)c * TILE, part);   // (y_c through part: vec is still being read)
       __syncthreads();
       if (threadIdx.x < NB) {
         vec[threadIdx.x] = part[threadIdx.x];                       // y_c
@@ -793,30 +730,21 @@ __global__ void __launch_bounds__(256, 2) k_fL11(const FrameDev* __restrict__ fr
       double areg[16];
       load_a_frags(At, areg);
       double4_t acc[4];
-#pragma unroll
-      for (int ni = 0; ni < 4; ++ni) acc[ni] = double4_t{0.0, 0.0, 0.0, 0.0};
+      zero_acc(acc);
       tile_ABt_regs<false, true>(areg, M, acc);
       store_c_frags(At, acc);
       // rhs rows of this wave: sum_col L[row][col] y[col], reduced over the 4 lk lanes
-      double sacc = 0.0;
-#pragma unroll
-      for (int ni = 0; ni < 4; ++ni)
-#pragma unroll
-        for (int rr = 0; rr < 4; ++rr) sacc += acc[ni][rr] * vec[16 * ni + lk + 4 * rr];
-      sacc += __shfl_xor(sacc, 16, 64);
-      sacc += __shfl_xor(sacc, 32, 64);
+      const double sacc = sum_row_lanes(acc_dot_vec(acc, vec, 0.0));
       if (lk == 0) vecs[(size_t)r * NB + 16 * w + lr] -= sacc;
     }
     __syncthreads();   // L(r,c) tiles visible to the whole workgroup
     // ---- trailing update inside the pivot block: A(r,s) -= L(r,c) L(s,c)^T ----
     for (int sc = c + 1; sc < f.npt; ++sc) {
-      const double* Ls = ftile(fd, f, sc, c);
+      // (not tile_product: L(sc,c) is staged once for the whole tile column sc, and the diagonal tile's product is trimmed)
       double breg[16];
-#pragma unroll
-      for (int e = 0; e < 16; ++e) breg[e] = Ls[threadIdx.x + 256 * e];
+      tile_to_regs(ftile(fd, f, sc, c), breg);
       __syncthreads();   // previous users of Bl are done
-#pragma unroll
-      for (int e = 0; e < 16; ++e) Bl[threadIdx.x + 256 * e] = breg[e];
+      regs_to_lds(Bl, breg);
       __syncthreads();
       for (int r = sc; r < f.npt; ++r) {
         double* Ct = ftile(fd, f, r, sc);
@@ -837,21 +765,18 @@ __global__ void __launch_bounds__(256, 2) k_fL11(const FrameDev* __restrict__ fr
 __global__ void __launch_bounds__(256, 3) k_fL21(const FrameDev* __restrict__ frames, LevelRef lvl, WgMap map) {
   __shared__ double Bl[TILE];
   __shared__ double yv[NB];
-  WgId wg;
-  if (!wg_decode(map, wg)) return;
-  const FrameDev& fd = frames[wg.frame];
-  if (!fd.bound || !fd.nd_ready) return;   // (a stopped slot only wastes the work: no dependent flag load here)
-  int fi;
-  if (!level_front(fd, lvl, wg.front, fi)) return;
-  const NDFront& f = fd.fronts[fi];
-  const int r = f.npt + wg.unit;
-  if (f.npt == 0 || r >= f.nt) return;
+  LevelCtx cx;
+  if (!level_begin(frames, lvl, 0, map, cx)) return;
+  const FrameDev& fd = *cx.fd;
+  const NDFront& f = *cx.f;
+  const int r = f.npt + cx.unit;
+  if (r >= f.nt) return;
   const int w = threadIdx.x >> 6, l = threadIdx.x & 63, lr = l & 15, lk = l >> 4;
   double* vecs = fd.fvec + f.vec_off;
   // known-zero parts are skipped: a wave whose 16 rows lie beyond the true boundary size issues no MFMA and stores
   // nothing (those rows of the pivot columns stay zero), and the front's last pivot tile column only counts up to the
   // true pivot count (blocks of 16)
-  const bool wave_on = 16 * w < min(NB, 7 * f.nb - NB * wg.unit);
+  const bool wave_on = 16 * w < min(NB, 7 * f.nb - NB * cx.unit);
   // (X_c' of the earlier columns is re-read from the tile this thread itself stored it to -- the accumulator layout is
   //  the A-fragment layout, element for element -- instead of being held in 32 registers per column: two workgroups
   //  per CU instead of one)
@@ -862,22 +787,16 @@ __global__ void __launch_bounds__(256, 3) k_fL21(const FrameDev* __restrict__ fr
       const int nblk = (ncol + 15) >> 4;                  // 16-column blocks with true pivots (also the inner blocks of X_c L_cc^-T)
       double* At = ftile(fd, f, r, c);
       double4_t acc[4];
-      if (wave_on) {
-        load_c_frags(At, acc);
-      } else {
-#pragma unroll
-        for (int ni = 0; ni < 4; ++ni) acc[ni] = double4_t{0.0, 0.0, 0.0, 0.0};
-      }
+      if (wave_on) load_c_frags(At, acc);
+      else zero_acc(acc);
       // acc -= X_c' L(c,c')^T for the earlier pivot columns
       for (int cp = 0; cp < c; ++cp) {
         const double* Lt = ftile(fd, f, c, cp);
         double breg[16], xreg[16];
-#pragma unroll
-        for (int e = 0; e < 16; ++e) breg[e] = Lt[threadIdx.x + 256 * e];
+        tile_to_regs(Lt, breg);
         if (wave_on) load_a_frags(ftile(fd, f, r, cp), xreg);
         __syncthreads();
-#pragma unroll
-        for (int e = 0; e < 16; ++e) Bl[threadIdx.x + 256 * e] = breg[e];
+        regs_to_lds(Bl, breg);
         __syncthreads();
         if (wave_on) tile_ABt_regs_trim<true>(xreg, Bl, acc, 4, nblk);
       }
@@ -885,11 +804,9 @@ __global__ void __launch_bounds__(256, 3) k_fL21(const FrameDev* __restrict__ fr
       {
         const double* linv = fd.flinv + f.linv_off + (size_t)c * TILE;
         double breg[16];
-#pragma unroll
-        for (int e = 0; e < 16; ++e) breg[e] = linv[threadIdx.x + 256 * e];
+        tile_to_regs(linv, breg);
         __syncthreads();
-#pragma unroll
-        for (int e = 0; e < 16; ++e) Bl[threadIdx.x + 256 * e] = breg[e];
+        regs_to_lds(Bl, breg);
         if (threadIdx.x < NB) yv[threadIdx.x] = vecs[(size_t)c * NB + threadIdx.x];
         __syncthreads();
         double areg[16];
@@ -898,26 +815,16 @@ __global__ void __launch_bounds__(256, 3) k_fL21(const FrameDev* __restrict__ fr
 #pragma unroll
           for (int rr = 0; rr < 4; ++rr) areg[4 * ni + rr] = acc[ni][rr];
         double4_t xa[4];
-#pragma unroll
-        for (int ni = 0; ni < 4; ++ni) xa[ni] = double4_t{0.0, 0.0, 0.0, 0.0};
+        zero_acc(xa);
         if (wave_on) {
           tile_ABt_regs_trim<false, true>(areg, Bl, xa, nblk, nblk);
-#pragma unroll
-          for (int ni = 0; ni < 4; ++ni)
-            if (ni < nblk) {
-#pragma unroll
-              for (int rr = 0; rr < 4; ++rr) At[(16 * w + lr) + (size_t)(16 * ni + lk + 4 * rr) * NB] = xa[ni][rr];
-            }
+          store_c_frags_nblk(At, xa, nblk);
         }
-#pragma unroll
-        for (int ni = 0; ni < 4; ++ni)
-#pragma unroll
-          for (int rr = 0; rr < 4; ++rr) rhs_acc += xa[ni][rr] * yv[16 * ni + lk + 4 * rr];
+        rhs_acc = acc_dot_vec(xa, yv, rhs_acc);
       }
     }
   }
-  rhs_acc += __shfl_xor(rhs_acc, 16, 64);
-  rhs_acc += __shfl_xor(rhs_acc, 32, 64);
+  rhs_acc = sum_row_lanes(rhs_acc);
   if (lk == 0 && wave_on) vecs[(size_t)r * NB + 16 * w + lr] -= rhs_acc;
 }
 
@@ -930,16 +837,12 @@ __global__ void __launch_bounds__(256, 3) k_fL21(const FrameDev* __restrict__ fr
 __global__ void __launch_bounds__(256) k_ftrail(const FrameDev* __restrict__ frames, LevelRef lvl,
                                                  int c, int mcap, int bcap, int ntile_cap, WgMap map) {
   __shared__ double Bl[TILE];
-  WgId wg;
-  if (!wg_decode(map, wg)) return;
-  const FrameDev& fd = frames[wg.frame];
-  if (!fd.bound || !fd.nd_ready) return;   // (a stopped slot only wastes the work: no dependent flag load here)
-  int fi;
-  if (!level_front(fd, lvl, wg.front, fi)) return;
-  const NDFront& f = fd.fronts[fi];
-  if (c >= f.npt) return;
+  LevelCtx cx;
+  if (!level_begin(frames, lvl, c, map, cx)) return;
+  const FrameDev& fd = *cx.fd;
+  const NDFront& f = *cx.f;
   const int m = f.nt - 1 - c;
-  int t = wg.unit;
+  int t = cx.unit;
   if (t < ntile_cap) {
     int db = 1;
     while (db <= bcap && t >= mcap - db + 1) {
@@ -948,38 +851,15 @@ __global__ void __launch_bounds__(256) k_ftrail(const FrameDev* __restrict__ fra
     }
     const int da = db + t;
     if (da > m || c + db >= f.npt) return;
-    const double* Lr = ftile(fd, f, c + da, c);
-    const double* Ls = ftile(fd, f, c + db, c);
-    double* Ct = ftile(fd, f, c + da, c + db);
-    double breg[16];
-#pragma unroll
-    for (int e = 0; e < 16; ++e) breg[e] = Ls[threadIdx.x + 256 * e];
-    double areg[16];
-    load_a_frags(Lr, areg);
-    double4_t acc[4];
-    load_c_frags(Ct, acc);
-#pragma unroll
-    for (int e = 0; e < 16; ++e) Bl[threadIdx.x + 256 * e] = breg[e];
-    __syncthreads();
-    tile_ABt_regs<true>(areg, Bl, acc);
-    store_c_frags(Ct, acc);
+    // A(c+da, c+db) -= L(c+da, c) L(c+db, c)^T
+    tile_product<true, false, true>(ftile(fd, f, c + db, c), ftile(fd, f, c + da, c), ftile(fd, f, c + da, c + db), Bl);
   } else {
     const int db = t - ntile_cap + 1;
     if (db > m) return;
     __shared__ double y[NB];
-    __shared__ double part[4][NB];
-    const double* Ls = ftile(fd, f, c + db, c);
+    __shared__ double part[4 * NB];
     double* vecs = fd.fvec + f.vec_off;
-    if (threadIdx.x < NB) y[threadIdx.x] = vecs[(size_t)c * NB + threadIdx.x];
-    __syncthreads();
-    const int i = threadIdx.x & 63, q = threadIdx.x >> 6;
-    double acc = 0.0;
-#pragma unroll
-    for (int k = 16 * q; k < 16 * q + 16; ++k) acc += Ls[i + k * NB] * y[k];
-    part[q][i] = acc;
-    __syncthreads();
-    if (threadIdx.x < NB)
-      vecs[(size_t)(c + db) * NB + i] -= part[0][i] + part[1][i] + part[2][i] + part[3][i];
+    trail_rhs(ftile(fd, f, c + db, c), vecs + (size_t)c * NB, vecs + (size_t)(c + db) * NB, y, part);
   }
 }
 
@@ -994,7 +874,7 @@ __global__ void __launch_bounds__(256) k_fpull(const FrameDev* __restrict__ fram
   if (!itp) return;
   const FrameDev& fd = *fdp;
   const NDTileItem it = item_snapshot(itp);
-  const int l = threadIdx.x & 63, w = threadIdx.x >> 6, lr = l & 15, lk = l >> 4;
+  const int w = threadIdx.x >> 6;
   // only the 16 x 16 blocks that hold real scalars move: the padding of the last pivot tile column / of the last tile
   // row of the pivots or of the boundary stays zero (nothing maps into it)
   const int vrow = it.r < it.npt ? min(NB, it.n1 - NB * it.r) : min(NB, it.n2 - NB * (it.r - it.npt));
@@ -1006,28 +886,12 @@ __global__ void __launch_bounds__(256) k_fpull(const FrameDev* __restrict__ fram
   // the WHOLE tile (its padding too: the factor kernels read full tiles)
   const bool pure = __builtin_amdgcn_readfirstlane((int)fd.tile_kind[it.pad0]) != 0;
   double4_t acc[4];
-#pragma unroll
-  for (int ni = 0; ni < 4; ++ni) acc[ni] = double4_t{0.0, 0.0, 0.0, 0.0};
-  if (wave_on && !pure) {
-#pragma unroll
-    for (int ni = 0; ni < 4; ++ni)
-      if (ni < nblk) {
-#pragma unroll
-        for (int rr = 0; rr < 4; ++rr) acc[ni][rr] = T[(16 * w + lr) + (size_t)(16 * ni + lk + 4 * rr) * NB];
-      }
-  }
+  zero_acc(acc);
+  if (wave_on && !pure) load_c_frags_nblk(T, acc, nblk);
   __syncthreads();
   if (wave_on) pull_tile(fd, it, maps, acc);
-  if (pure) {
-    store_c_frags(T, acc);
-  } else if (wave_on) {
-#pragma unroll
-    for (int ni = 0; ni < 4; ++ni)
-      if (ni < nblk) {
-#pragma unroll
-        for (int rr = 0; rr < 4; ++rr) T[(16 * w + lr) + (size_t)(16 * ni + lk + 4 * rr) * NB] = acc[ni][rr];
-      }
-  }
+  if (pure) store_c_frags(T, acc);
+  else if (wave_on) store_c_frags_nblk(T, acc, nblk);
   if (it.r == it.c) {
     const double v = pull_vec(fd, it, maps);
     if (threadIdx.x < NB && v != 0.0) fd.fvec[it.vec_off + (size_t)it.c * NB + threadIdx.x] += v;
@@ -1078,8 +942,7 @@ __global__ void __launch_bounds__(256, 3) k_fschur(const FrameDev* __restrict__ 
     if (wave_on) load_a_frags(item_tile(fd, it, r, 0), areg);
   }
   double4_t acc[4];
-#pragma unroll
-  for (int ni = 0; ni < 4; ++ni) acc[ni] = double4_t{0.0, 0.0, 0.0, 0.0};
+  zero_acc(acc);
   __syncthreads();     // maps visible
   if (kids) pull_tile(fd, it, maps, acc);
   for (int c = 0; c < it.npt; ++c) {
@@ -1135,15 +998,7 @@ __global__ void __launch_bounds__(256, 3) k_fschur(const FrameDev* __restrict__ 
   }
   // the update tile, in place (the parent gathers it): only the 16 x 16 blocks that hold boundary scalars -- the padding
   // of the last tile row / column is never read by anything (the pull maps address true scalars only)
-  if (wave_on) {
-    double* Cg = item_tile(fd, it, r, sc);
-#pragma unroll
-    for (int ni = 0; ni < 4; ++ni)
-      if (ni < nblk) {
-#pragma unroll
-        for (int rr = 0; rr < 4; ++rr) Cg[(16 * w + lr) + (size_t)(16 * ni + lk + 4 * rr) * NB] = acc[ni][rr];
-      }
-  }
+  if (wave_on) store_c_frags_nblk(item_tile(fd, it, r, sc), acc, nblk);
   // vector rows: diagonal tiles add the children's rows to v_r (k_fL21 / k_ftrail subtracted sum_c L(r,c) y_c before)
   if (tr == tc && kids) {
     const double v = pull_vec(fd, it, maps);
@@ -1156,28 +1011,20 @@ __global__ void __launch_bounds__(256, 3) k_fschur(const FrameDev* __restrict__ 
 // grid = (max npt, fronts in level, n_frames)
 __global__ void __launch_bounds__(256) k_fback_prep(const FrameDev* __restrict__ frames, LevelRef lvl) {
   extern __shared__ double xb[];   // n2p doubles
-  const FrameDev& fd = frames[blockIdx.z];
-  if (!fd.bound || !fd.nd_ready) return;   // (a stopped slot only wastes the work: no dependent flag load here)
-  int fi;
-  if (!level_front(fd, lvl, blockIdx.y, fi)) return;
-  const NDFront& f = fd.fronts[fi];
-  const int c = blockIdx.x;
-  if (c >= f.npt || f.nb == 0) return;
+  LevelCtx cx;
+  if (!level_begin(frames, lvl, blockIdx.x, cx)) return;
+  const FrameDev& fd = *cx.fd;
+  const NDFront& f = *cx.f;
+  const int c = cx.unit;
+  if (f.nb == 0) return;
   const int* nodes = fd.nd_nodes + f.nodes_off + f.nv;
   for (int i = threadIdx.x; i < f.n2p; i += blockDim.x)
     xb[i] = (i < 7 * f.nb) ? fd.delta[7 * nodes[i / 7] + i % 7] : 0.0;
   __syncthreads();
-  const int n = threadIdx.x >> 2, q = threadIdx.x & 3;
   double acc = 0.0;
-  for (int r = f.npt; r < f.nt; ++r) {
-    const double* Lt = ftile(fd, f, r, c);
-    const double* xr = xb + (size_t)(r - f.npt) * NB;
-#pragma unroll
-    for (int mrow = 16 * q; mrow < 16 * q + 16; ++mrow) acc += Lt[mrow + n * NB] * xr[mrow];
-  }
-  acc += __shfl_xor(acc, 1, 64);
-  acc += __shfl_xor(acc, 2, 64);
-  if (q == 0) fd.fvec[f.vec_off + (size_t)c * NB + n] -= acc;
+  for (int r = f.npt; r < f.nt; ++r) acc = tile_t_vec_lanes(ftile(fd, f, r, c), xb + (size_t)(r - f.npt) * NB, acc);
+  acc = sum_col_lanes(acc);
+  if ((threadIdx.x & 3) == 0) fd.fvec[f.vec_off + (size_t)c * NB + (threadIdx.x >> 2)] -= acc;
 }
 
 // Back substitution, part 2, pivot tile column c = npt-1-step of every front of the level:
@@ -1185,32 +1032,18 @@ __global__ void __launch_bounds__(256) k_fback_prep(const FrameDev* __restrict__
 // grid = (max npt, fronts in level, n_frames)
 __global__ void __launch_bounds__(256) k_fbacksub(const FrameDev* __restrict__ frames, LevelRef lvl,
                                                    int step) {
-  const FrameDev& fd = frames[blockIdx.z];
-  if (!fd.bound || !fd.nd_ready) return;   // (a stopped slot only wastes the work: no dependent flag load here)
-  int fi;
-  if (!level_front(fd, lvl, blockIdx.y, fi)) return;
-  const NDFront& f = fd.fronts[fi];
+  LevelCtx cx;
+  if (!level_begin(frames, lvl, step, cx)) return;   // (column npt - 1 - step exists)
+  const FrameDev& fd = *cx.fd;
+  const NDFront& f = *cx.f;
   const int c = f.npt - 1 - step;
-  if (c < 0) return;
-  const int d = blockIdx.x;
+  const int d = cx.unit;
   if (d > c) return;
   __shared__ double y[NB];
   __shared__ double x[NB];
-  __shared__ double part[4][NB];
+  __shared__ double part[4 * NB];
   double* vecs = fd.fvec + f.vec_off;
-  const double* linv = fd.flinv + f.linv_off + (size_t)c * TILE;
-  if (threadIdx.x < NB) y[threadIdx.x] = vecs[(size_t)c * NB + threadIdx.x];
-  __syncthreads();
-  {
-    const int k = threadIdx.x & 63, q = threadIdx.x >> 6;
-    double acc = 0.0;
-#pragma unroll
-    for (int i = 16 * q; i < 16 * q + 16; ++i) acc += linv[i + k * NB] * y[i];
-    part[q][k] = acc;
-    __syncthreads();
-    if (threadIdx.x < NB) x[k] = part[0][k] + part[1][k] + part[2][k] + part[3][k];
-    __syncthreads();
-  }
+  backsub_x(fd.flinv + f.linv_off + (size_t)c * TILE, vecs + (size_t)c * NB, y, x, part);
   if (d == 0) {
     if (threadIdx.x < NB) {
       const int i = c * NB + threadIdx.x;
@@ -1220,14 +1053,7 @@ __global__ void __launch_bounds__(256) k_fbacksub(const FrameDev* __restrict__ f
       }
     }
   } else {
-    const double* Lt = ftile(fd, f, c, c - d);
-    const int n = threadIdx.x >> 2, q = threadIdx.x & 3;
-    double acc = 0.0;
-#pragma unroll
-    for (int mrow = 16 * q; mrow < 16 * q + 16; ++mrow) acc += Lt[mrow + n * NB] * x[mrow];
-    acc += __shfl_xor(acc, 1, 64);
-    acc += __shfl_xor(acc, 2, 64);
-    if (q == 0) vecs[(size_t)(c - d) * NB + n] -= acc;
+    backsub_update(ftile(fd, f, c, c - d), x, vecs + (size_t)(c - d) * NB);
   }
 }
 
@@ -1263,6 +1089,26 @@ void launch_iter_begin_nd(const FrameDev* fr, int n_frames, hipStream_t st, cons
   hipLaunchKernelGGL(k_iter_begin_nd, dim3(1024, n_frames), dim3(256), 0, st, fr, reuse, dag_cut);
 }
 
+// The dynamic-LDS limit of a kernel, raised once per (kernel, device).  It is a property of a kernel ON a device, and host
+// threads may drive different solvers on one device: the table is per device id, its slots are atomics; a device id beyond
+// the table, or a kernel beyond its slots, sets the attribute on every call instead of aliasing another entry.
+bool ensure_dynamic_lds(const void* kernel, size_t bytes) {
+  static std::atomic<const void*> done[64][8];
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  const bool tracked = dev >= 0 && dev < 64;
+  if (tracked)
+    for (auto& slot : done[dev])
+      if (slot.load(std::memory_order_acquire) == kernel) return true;
+  if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) return false;
+  if (tracked)
+    for (auto& slot : done[dev]) {
+      const void* seen = nullptr;
+      if (slot.compare_exchange_strong(seen, kernel, std::memory_order_acq_rel) || seen == kernel) break;
+    }
+  return true;
+}
+
 // Level schedule shared by all slots of a batch (they may have different plans: the host
 // passes, per level, the maxima over the batch; blocks beyond a front's own size exit).
 // Factorisation launches of levels [0, l_factor_end), back-substitution launches of levels [0, l_back_end), the
@@ -1272,38 +1118,27 @@ void launch_front_levels(const FrameDev* fr, int n_frames, const NDLevelSched* l
                          int l_back_end, double u_override, hipStream_t st) {
   const size_t lds = PANEL_LDS_DOUBLES * sizeof(double);
   const size_t lds11 = L11_LDS_DOUBLES * sizeof(double);
-  // the dynamic-LDS limit is a property of a kernel ON a device: set once per device id
-  // (host threads may drive different solvers on one device: the flags are atomics; a device id beyond the table sets
-  //  the attributes on every call instead of aliasing another device's flag)
-  static std::atomic<bool> attr_set[64];
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  const bool tracked = dev >= 0 && dev < 64;
-  if (!tracked || !attr_set[dev].load(std::memory_order_acquire)) {
-    if (hipFuncSetAttribute((const void*)k_fL11, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds11) != hipSuccess ||
-        hipFuncSetAttribute((const void*)k_fpanel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
-        hipFuncSetAttribute((const void*)k_fpotrf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-      return;   // (sticky HIP error: the caller's hipGetLastError reports it)
-    if (tracked) attr_set[dev].store(true, std::memory_order_release);
-  }
+  if (!ensure_dynamic_lds((const void*)k_fL11, lds11) || !ensure_dynamic_lds((const void*)k_fpanel, lds) ||
+      !ensure_dynamic_lds((const void*)k_fpotrf, lds))
+    return;   // (sticky HIP error: the caller's hipGetLastError reports it)
+  // One workgroup per front (k_fL11 + k_fL21) only pays when a level has enough fronts to fill the
+  // chip: with few fronts the per-column panel launches, which spread a front over its row tiles, have
+  // the shorter critical path (C2: 581 instead of 543 it/s at one frame per launch; the cross-over is
+  // around 128 fronts x frames; 64 since round 3, with k_fL11 at two workgroups per CU and the leaner k_fL21: C2 at 8
+  // frames 2.133 instead of 2.147 ms per solve).  SLM_COMPACT_MIN / SLM_COMPACT_NPT override the thresholds for
+  // experiments (wider pivot blocks than 4 tile columns lose: 2.22 ms with the 5-column level in this form).
+  static const long compact_min = [] {
+    const char* e = getenv("SLM_COMPACT_MIN");
+    return e ? atol(e) : 64L;
+  }();
+  static const int compact_npt = [] {
+    const char* e = getenv("SLM_COMPACT_NPT");
+    return e ? atoi(e) : 4;
+  }();
   for (int l = 0; l < l_factor_end; ++l) {
     const NDLevelSched& s = lv[l];
     if (s.n_fronts <= 0) continue;
     const LevelRef lr{l, s.first, s.n_fronts};
-    // One workgroup per front (k_fL11 + k_fL21) only pays when a level has enough fronts to fill the
-    // chip: with few fronts the per-column panel launches, which spread a front over its row tiles, have
-    // the shorter critical path (C2: 581 instead of 543 it/s at one frame per launch; the cross-over is
-    // around 128 fronts x frames; 64 since round 3, with k_fL11 at two workgroups per CU and the leaner k_fL21: C2 at 8
-    // frames 2.133 instead of 2.147 ms per solve).  SLM_COMPACT_MIN / SLM_COMPACT_NPT override the thresholds for
-    // experiments (wider pivot blocks than 4 tile columns lose: 2.22 ms with the 5-column level in this form).
-    static const long compact_min = [] {
-      const char* e = getenv("SLM_COMPACT_MIN");
-      return e ? atol(e) : 64L;
-    }();
-    static const int compact_npt = [] {
-      const char* e = getenv("SLM_COMPACT_NPT");
-      return e ? atoi(e) : 4;
-    }();
     const bool compact = s.max_npt <= compact_npt && (long)s.n_fronts * n_frames >= compact_min;
     // children's update matrices into the pivot columns (levels whose fronts all are leaves have nothing to gather).
     // A launch of its own: gathering inside k_fL11 / k_fL21 (at the first touch of every pivot-column tile) was built

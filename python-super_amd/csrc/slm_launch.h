@@ -27,6 +27,8 @@ void launch_iter_begin_nd(const FrameDev*, int, hipStream_t, const int* reuse, i
 void launch_front_solve(const FrameDev*, int, const NDLevelSched*, int, double, hipStream_t);
 void launch_front_levels(const FrameDev*, int, const NDLevelSched*, int, int, int, double, hipStream_t);
 
+bool ensure_dynamic_lds(const void* kernel, size_t bytes);   // every kernel with more than 64 KB of dynamic LDS, before its launch
+
 // slm_dag.hip
 int launch_front_solve_dag(const FrameDev*, int, int, double, hipStream_t, int cut, bool reset, bool check);
 int dag_device_setup(int dev, int* xcd8_out);

@@ -1,6 +1,16 @@
 // slm_tile.h -- 64x64 float64 tile kernels shared by the band solver (slm_band.hip) and the
 // multifrontal solver (slm_front.hip): blocked Cholesky of a tile in LDS on the f64 MFMA
 // (v_mfma_f64_16x16x4_f64), triangular solve of a tile against it, tile products.
+// In file order:
+//   blk_mma / blk_load / blk_store, diag16, potrf64, inverse_assemble64, factor_inverse64p    factor a tile, form its inverse
+//   TileLds<NVEC, NINT>                             the dynamic LDS of a kernel that factors tiles
+//   load_a_frags, load_c_frags, store_c_frags, tile_ABt_regs[_trim], trsm_rows16    tile products in registers
+//   damped_lower, tile_to_regs / regs_to_lds / regs_to_diag_tile, stage_diag_tile    staging; the diagonal-tile rule
+//   commit_pivot                                    inverse -> linv, y = L^-1 b
+//   zero_acc, load_c_frags_nblk / store_c_frags_nblk, acc_dot_vec + sum_row_lanes    accumulator-layout access
+//   tile_vec_quarters, tile_t_vec_lanes + sum_col_lanes                 the two tile-times-vector forms
+//   panel_column_stage / panel_column_finish, tile_product, trail_rhs, backsub_x / backsub_update
+//                                                   the tile-column bodies that the band and the per-level kernels share
 #pragma once
 #include "slm_common.h"
 
@@ -606,3 +616,187 @@ __device__ __forceinline__ void trsm_rows16(const double* S, const double* dinv,
   }
 }
 
+// ---------------------------------------------------------------------------------
+// Tile-level building blocks of the per-level kernels (slm_front.hip) and the band solver (slm_band.hip).  Pointers only:
+// nothing here knows of FrameDev, NDFront or the band.  256 threads; l, w, lr, lk as everywhere in this file.
+//
+// The diagonal-tile rule: lower triangle, +u on real pivots, identity on the padding rows.  Entry (i, k) of a tile whose row 0
+// is row `row0` of a block with n_rows real pivots.
+__device__ __forceinline__ double damped_lower(double x, int i, int k, int row0, int n_rows, double u) {
+  x = (i >= k) ? x : 0.0;
+  if (i == k) x = (row0 + i < n_rows) ? x + u : 1.0;
+  return x;
+}
+
+// A tile through registers, 16 doubles per thread: all 16 global loads are issued before the first LDS store (one memory
+// round trip instead of sixteen), and the caller may put further loads between the two halves.
+__device__ __forceinline__ void tile_to_regs(const double* src, double v[16]) {
+#pragma unroll
+  for (int e = 0; e < 16; ++e) v[e] = src[threadIdx.x + 256 * e];
+}
+__device__ __forceinline__ void regs_to_lds(double* Bl, const double v[16]) {
+#pragma unroll
+  for (int e = 0; e < 16; ++e) Bl[threadIdx.x + 256 * e] = v[e];
+}
+// ... the store half for a DIAGONAL tile (damped_lower: row 0 of the tile is row `row0` of n_rows real pivots), and both halves
+__device__ __forceinline__ void regs_to_diag_tile(const double v[16], int row0, int n_rows, double u, double* S) {
+#pragma unroll
+  for (int t = 0; t < 16; ++t) {
+    const int e = threadIdx.x + 256 * t;
+    const int i = e % NB, k = e / NB;
+    S[i + k * LD] = damped_lower(v[t], i, k, row0, n_rows, u);
+  }
+}
+__device__ __forceinline__ void stage_diag_tile(const double* src, int row0, int n_rows, double u, double* S) {
+  double v[16];
+  tile_to_regs(src, v);
+  regs_to_diag_tile(v, row0, n_rows, u, S);
+}
+
+// The pivot commit: the inverse M of a factored diagonal tile goes to linv (global), and threads < NB form y = L^-1 b
+// (b in vec) and store it to y_out (global, or LDS for a caller whose vec is about to be rewritten).
+__device__ __forceinline__ void commit_pivot(const double* M, const double* vec, double* linv, double* y_out) {
+  for (int e = threadIdx.x; e < TILE; e += blockDim.x) linv[e] = M[e];
+  if (threadIdx.x < NB) {
+    const int i = threadIdx.x;
+    double acc = 0.0;
+    for (int k = 0; k <= i; ++k) acc += M[i + k * LD] * vec[k];
+    y_out[i] = acc;
+  }
+}
+
+__device__ __forceinline__ void zero_acc(double4_t acc[4]) {
+#pragma unroll
+  for (int ni = 0; ni < 4; ++ni) acc[ni] = double4_t{0.0, 0.0, 0.0, 0.0};
+}
+// load_c_frags / store_c_frags limited to the first nblk (uniform, 0..4) 16-column blocks; the other registers are left alone
+__device__ __forceinline__ void load_c_frags_nblk(const double* Cg, double4_t acc[4], int nblk) {
+  const int l = threadIdx.x & 63, w = threadIdx.x >> 6, lr = l & 15, lk = l >> 4;
+#pragma unroll
+  for (int ni = 0; ni < 4; ++ni)
+    if (ni < nblk) {
+#pragma unroll
+      for (int rr = 0; rr < 4; ++rr) acc[ni][rr] = Cg[(16 * w + lr) + (size_t)(16 * ni + lk + 4 * rr) * NB];
+    }
+}
+__device__ __forceinline__ void store_c_frags_nblk(double* Cg, const double4_t acc[4], int nblk) {
+  const int l = threadIdx.x & 63, w = threadIdx.x >> 6, lr = l & 15, lk = l >> 4;
+#pragma unroll
+  for (int ni = 0; ni < 4; ++ni)
+    if (ni < nblk) {
+#pragma unroll
+      for (int rr = 0; rr < 4; ++rr) Cg[(16 * w + lr) + (size_t)(16 * ni + lk + 4 * rr) * NB] = acc[ni][rr];
+    }
+}
+
+// Row sums of a tile in accumulator layout against a vector: s + this lane's part of sum_col acc[row][col] y[col] (added
+// term by term to s: a caller that runs over several tiles keeps its summation order), and the sum over the four lanes
+// (lk = 0..3) that share a row -- every one of them ends with the row's value.
+__device__ __forceinline__ double acc_dot_vec(const double4_t acc[4], const double* y, double s) {
+  const int lk = (threadIdx.x & 63) >> 4;
+#pragma unroll
+  for (int ni = 0; ni < 4; ++ni)
+#pragma unroll
+    for (int rr = 0; rr < 4; ++rr) s += acc[ni][rr] * y[16 * ni + lk + 4 * rr];
+  return s;
+}
+__device__ __forceinline__ double sum_row_lanes(double s) {
+  s += __shfl_xor(s, 16, 64);
+  s += __shfl_xor(s, 32, 64);
+  return s;
+}
+
+// Tile times vector, two forms.
+// (1) Quarter partials: thread (i = tid & 63, q = tid >> 6) sums the inner indices [16q, 16q + 16) of (T v)[i] -- or of
+//     (T^T v)[i] -- the partials meet in part (4 NB doubles of LDS); the sum is returned in the threads < NB.
+template <bool TRANSPOSED>
+__device__ __forceinline__ double tile_vec_quarters(const double* T, const double* v, double* part) {
+  const int i = threadIdx.x & 63, q = threadIdx.x >> 6;
+  double acc = 0.0;
+#pragma unroll
+  for (int k = 16 * q; k < 16 * q + 16; ++k) acc += (TRANSPOSED ? T[k + i * NB] : T[i + k * NB]) * v[k];
+  part[q * NB + i] = acc;
+  __syncthreads();
+  return threadIdx.x < NB ? part[i] + part[NB + i] + part[2 * NB + i] + part[3 * NB + i] : 0.0;
+}
+// (2) Four lanes per column: lane q = tid & 3 of column n = tid >> 2 adds the rows [16q, 16q + 16) of (T^T x)[n] to acc (a
+//     caller may run over several tiles); sum_col_lanes then adds the four lanes up.
+__device__ __forceinline__ double tile_t_vec_lanes(const double* T, const double* x, double acc) {
+  const int n = threadIdx.x >> 2, q = threadIdx.x & 3;
+#pragma unroll
+  for (int mrow = 16 * q; mrow < 16 * q + 16; ++mrow) acc += T[mrow + n * NB] * x[mrow];
+  return acc;
+}
+__device__ __forceinline__ double sum_col_lanes(double acc) {
+  acc += __shfl_xor(acc, 1, 64);
+  acc += __shfl_xor(acc, 2, 64);
+  return acc;
+}
+
+// ---------------------------------------------------------------------------------
+// The tile-column bodies of a right-looking blocked Cholesky with the forward substitution riding along, written once for
+// the band solver (k_panel, k_trail, k_backsub) and the fronts (k_fpanel, k_fpotrf, k_ftrsm, k_ftrail, k_fbacksub): the
+// kernels form the addresses and call these.
+//
+// Panel column, workgroup d of tile column c, around the CALLER's factorisation of S (potrf64 + inverse_assemble64 in the
+// band, PanelLds::factor in the fronts).  Before it: this workgroup's own operands first, so that their loads overlap the
+// factorisation (d > 0: the tile At = A(c+d, c) in accumulator layout; d == 0: the right-hand side rows yv -> vec), then
+// the diagonal tile -> S, and the barrier.
+__device__ __forceinline__ void panel_column_stage(int d, const double* At, const double* yv, const double* diag, int row0,
+                                                   int n_rows, double u, double* S, double* vec, double4_t a[4]) {
+  if (d > 0) load_c_frags(At, a);
+  else if (threadIdx.x < NB) vec[threadIdx.x] = yv[threadIdx.x];
+  stage_diag_tile(diag, row0, n_rows, u, S);
+  __syncthreads();
+}
+// Behind it.  d == 0: the pivot commit (M -> linv, y_c = L^-1 b_c -> yv); d > 0: L(c+d, c) = A(c+d, c) L^-T -> At.
+__device__ __forceinline__ void panel_column_finish(int d, double* At, double* yv, double* linv, const double* S, const double* M,
+                                                    const double* dinv, const double* vec, double4_t a[4]) {
+  if (d == 0) {
+    commit_pivot(M, vec, linv, yv);
+  } else {
+    trsm_rows16(S, dinv, a);
+    store_c_frags(At, a);
+  }
+}
+
+// One tile product with every operand fetched up front: B tile -> registers -> Bl (LDS), the A fragments and (ACCUMULATE)
+// the C tile -> registers, barrier, C = [C +] (-)A B^T, store.  The trailing update A(r,s) -= L(r,c) L(s,c)^T
+// (<true, false, true>) and the row solve against a stored inverse, L(c+d,c) = A(c+d,c) (L_cc^-1)^T (<false, true, false>).
+template <bool NEGATE, bool LOWER_B, bool ACCUMULATE>
+__device__ __forceinline__ void tile_product(const double* Bt, const double* At, double* Ct, double* Bl) {
+  double breg[16];
+  tile_to_regs(Bt, breg);
+  double areg[16];
+  load_a_frags(At, areg);
+  double4_t acc[4];
+  if (ACCUMULATE) load_c_frags(Ct, acc);
+  regs_to_lds(Bl, breg);
+  __syncthreads();
+  if (!ACCUMULATE) zero_acc(acc);
+  tile_ABt_regs<NEGATE, LOWER_B>(areg, Bl, acc);
+  store_c_frags(Ct, acc);
+}
+
+// Trailing update of the right-hand side: b_s -= L(s,c) y_c.  y (NB) and part (4 NB) are LDS.
+__device__ __forceinline__ void trail_rhs(const double* Ls, const double* yc, double* bs, double* y, double* part) {
+  if (threadIdx.x < NB) y[threadIdx.x] = yc[threadIdx.x];
+  __syncthreads();
+  const double s = tile_vec_quarters<false>(Ls, y, part);
+  if (threadIdx.x < NB) bs[threadIdx.x] -= s;
+}
+
+// Back-substitution column c: x_c = L_cc^-T y_c into x (every workgroup of the column, redundantly; y, x: NB, part: 4 NB of
+// LDS; x is visible to the workgroup on return).  Workgroup 0 then stores x_c -- the caller's own line -- and workgroup
+// d > 0 updates y_(c-d) -= L(c, c-d)^T x_c.
+__device__ __forceinline__ void backsub_x(const double* linv, const double* yc, double* y, double* x, double* part) {
+  if (threadIdx.x < NB) y[threadIdx.x] = yc[threadIdx.x];
+  __syncthreads();
+  const double s = tile_vec_quarters<true>(linv, y, part);
+  if (threadIdx.x < NB) x[threadIdx.x] = s;
+  __syncthreads();
+}
+__device__ __forceinline__ void backsub_update(const double* Lt, const double* x, double* yr) {
+  const double acc = sum_col_lanes(tile_t_vec_lanes(Lt, x, 0.0));
+  if ((threadIdx.x & 3) == 0) yr[threadIdx.x >> 2] -= acc;
+}

@@ -186,9 +186,9 @@ def identity_beta(J):
 
 @functools.lru_cache(maxsize=None)
 def reference(name, beta="perturbed", opt_kw=()):
-    """(A, b, delta, norm(A, 2)): the oracle's JtJ + U_SOLVE I, jtl and Cholesky solution of a case (or failure case) at the
+    """(A, b, delta, norm(A, 2)): the oracle's JtJ + U_SOLVE I, jtl and Cholesky solution of a case (or failure case, or "split_column") at the
     perturbed (or identity) beta, computed once and read-only"""
-    sc = case(name) if name in _BUILDERS else failure_case(name)
+    sc = case(name) if name in _BUILDERS else (split_column_case() if name == "split_column" else failure_case(name))
     b0 = perturbed_beta(sc.J) if beta == "perturbed" else identity_beta(sc.J)
     JtJ, jtl, _ = orc.normal_equations(orc.Frame.from_scene(sc), b0, orc.default_opt(**dict(opt_kw)))
     A = JtJ + U_SOLVE * np.eye(len(jtl))
@@ -313,3 +313,29 @@ def host_plan(sc, leaf_nodes):
     assert 1 <= n <= len(fronts), n
     return dict(fronts=n, levels=int(fronts[:n, 0].max()) + 1, node_front=node_front, node_pos=node_pos,
                 front_depth=fronts[:n, 0].copy(), front_nv=fronts[:n, 1].copy(), front_is_leaf=fronts[:n, 2].astype(bool))
+
+
+def host_level_schedule(sc):
+    """The per-level launch schedule of the scene's plan at SLM_ND_LEAF (the per-level and hybrid forms), deepest level first
+    as launch_front_levels walks it: a list of (n_fronts, max_npt, max_nt) -- fronts of the level, the most pivot tile columns
+    and the most tile rows (pivot + boundary) of one of them (NDLevelSched, csrc/slm_nd.h)."""
+    import ctypes as C
+    lib = _nd_lib()
+    pts = np.ascontiguousarray(sc.ed_points, np.float32)
+    knn = np.ascontiguousarray(sc.ed_knn_idx, np.int32)
+    pairs = coupled_pairs(sc)
+    stats, fronts = np.zeros(8), np.zeros((sc.J + 1, 4), np.int32)      # per front: depth, pivot nodes, boundary nodes, parent
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    n = lib.nd_stats(sc.J, knn.shape[1], p(pts), p(knn), p(pairs), len(pairs), p(stats), p(fronts), len(fronts), None)
+    assert 1 <= n <= len(fronts), n
+    depth, npt = fronts[:n, 0], (7 * fronts[:n, 1] + 63) // 64
+    nt = npt + (7 * fronts[:n, 2] + 63) // 64
+    return [(int((depth == d).sum()), int(npt[depth == d].max()), int(nt[depth == d].max())) for d in range(int(depth.max()), -1, -1)]
+
+
+@functools.lru_cache(maxsize=None)
+def split_column_case():
+    """A 16 x 24 grid (J = 384, P = 2 688): at 18-node leaves one level of its tree has 16 fronts of up to six tile rows, so an
+    eight-slot batch launches (6 - c) * 16 * 8 = 768 / 640 workgroups for that level's tile columns c = 0 / 1 -- past the 512
+    at which launch_front_levels splits the fused panel column into k_fpotrf + k_ftrsm (tests/test_gpu_solver_graphs.py)."""
+    return _scene(384, 3000, 884)

@@ -162,6 +162,57 @@ def test_every_slot_of_a_batch_matches_its_own_dense_solve(batch, sp):
         _check_against_oracle(f"batch={batch} sp={sp} slot={i} {name}", (beta - sgc.perturbed_beta(sc.J)).reshape(-1), sgc.reference(name))
 
 
+# ------------------------------------------------------------------------------------------- the split panel column
+def test_the_split_panel_column_matches_the_dense_solve_of_the_oracle(tmp_path):
+    """k_fpotrf + k_ftrsm, the split form of a tile column of the per-level launches: launch_front_levels takes it in a level
+    that does not run the compact form when (max_nt - c) * n_fronts * n_frames > 512, which no batch above reaches (deep: at
+    most 8 x 8 x 4 = 256).  Eight slots of sgc.split_column_case() under SLM_COMPACT_MIN=1000000 (no level compact; read once
+    per process, hence the child), solver_path 3, one train-phase iteration at u0 = 0.37 from the perturbed beta: every slot
+    against the oracle's dense solve of the frame, with the two bounds of this file.  That the split form runs -- and the
+    fused one too, in the same solve -- is asserted on the level schedule of the host analysis, so a plan change fails here
+    instead of silently running one form only; the plan the bind built is checked against that schedule."""
+    import os
+    import subprocess
+    import sys
+    sc = sgc.split_column_case()
+    sched = sgc.host_level_schedule(sc)
+    blocks = [(nt - c) * n * 8 for n, npt, nt in sched for c in range(npt)]      # workgroups of a fused panel launch, per tile column
+    print(f"MEASURE split_column levels (n_fronts, max_npt, max_nt) = {sched}, fused panel workgroups per column = {blocks}")
+    assert max(blocks) >= 512 + 128 and min(blocks) <= 512, blocks               # split with room to spare, and fused
+    assert any(nt - c > 1 for n, npt, nt in sched for c in range(npt) if (nt - c) * n * 8 > 512)   # k_ftrsm has tiles to solve
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = str(tmp_path / "split.npz")
+    code = (
+        "import sys, numpy as np, torch\n"
+        f"sys.path[:0] = [{root!r}, {os.path.join(root, 'python-super_amd')!r}, {os.path.join(root, 'tests')!r}]\n"
+        "import solver_graph_cases as sgc\n"
+        "from super_amd import _lib\n"
+        "from super_amd.engine import DeviceFrame, Engine\n"
+        "dev = torch.device('cuda', 0)\n"
+        "sc = sgc.split_column_case()\n"
+        "e = Engine(dev, max_frames=8, num_iterations=1, phase_test=False, u0=sgc.U_SOLVE, solver_path=3)\n"
+        "e.bind_batch([DeviceFrame.from_scene(sc, dev) for _ in range(8)])\n"
+        "bt = torch.from_numpy(np.ascontiguousarray(sgc.perturbed_beta(sc.J))).cuda()\n"
+        "for i in range(8):\n"
+        "    _lib.check(e.lib.slm_set_beta(e.h, i, bt.data_ptr(), e.stream), 'slm_set_beta')\n"
+        "e.run(8)\n"
+        "recs = [e.records(i) for i in range(8)]\n"
+        "info = e.plan_info(0)\n"
+        f"np.savez({out!r}, beta=np.stack([e.beta(i).cpu().numpy() for i in range(8)]), form=e.lib.slm_debug_last_solver_form(e.h),\n"
+        "         ok=[len(r) == 1 and r[0]['status'] == 0 and bool(r[0]['accepted']) and r[0]['u'] == sgc.U_SOLVE for r in recs],\n"
+        "         plan=[int(info['fronts']), int(info['levels'])])\n"
+        "e.close()\n")
+    env = dict(os.environ, SLM_COMPACT_MIN="1000000")
+    run = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=600)
+    assert run.returncode == 0, run.stderr[-2000:]
+    got = np.load(out)
+    assert int(got["form"]) == 0 and got["ok"].all(), (got["form"], got["ok"])
+    assert tuple(got["plan"]) == (sum(n for n, _, _ in sched), len(sched))
+    ref = sgc.reference("split_column")
+    for i in range(8):
+        _check_against_oracle(f"split_column slot={i}", (got["beta"][i] - sgc.perturbed_beta(sc.J)).reshape(-1), ref)
+
+
 # ------------------------------------------------------------------------------------------- failure placement
 ROT = dict(use_arap=False, use_rot=True, u0=0.0)           # sgc.FAIL_OPT_ROT: the chosen node's qx pivot is the ONLY zero pivot
 DATA = dict(use_arap=False, use_rot=False, u0=0.0)         # sgc.FAIL_OPT_DATA: every node has a zero pivot (see solver_graph_cases)
@@ -278,6 +329,10 @@ def test_a_zero_pivot_in_slot_3_leaves_the_other_slots_alone(name, sp, healthy_s
 # batch=mixed sp=4 form=0 levels=[4, 4, 4, 1, 1, 2, 3, 3] fronts=[13, 15, 13, 1, 1, 3, 5, 7]
 # batch=mixed sp=2 form=1 levels=[3, 3, 3, 1, 1, 1, 2, 2] fronts=[5, 7, 5, 1, 1, 1, 3, 3]
 # batch=mixed sp=3 form=0 levels=[4, 4, 4, 1, 1, 2, 3, 3] fronts=[13, 15, 13, 1, 1, 3, 5, 7]
+# split_column (J = 384, P = 2 688, eight slots, SLM_COMPACT_MIN=1000000, sp 3, form 0): levels (n_fronts, max_npt, max_nt) =
+#   [(6, 2, 5), (16, 2, 6), (8, 2, 6), (4, 2, 6), (2, 2, 5), (1, 3, 3)], fused panel workgroups per tile column = [240, 192, 768, 640,
+#   384, 320, 192, 160, 80, 64, 24, 16, 8] (768 and 640 run k_fpotrf + k_ftrsm); every slot forward 3.8e-15, backward 0.000 P eps
+#   (1.7e-16).  With it the file has 126 tests (10.6 s on the MI355X).
 #
 # What the file sees of a wrong factorisation.  On a scratch build the extend-add of child 1 was skipped in the last tile row of
 # every parent tile gathered by the per-level launches (pull_tile in slm_front.hip): 25 of the 125 tests failed, every one of

@@ -1,5 +1,5 @@
 """Diagnostic: ms per LM iteration (bind excluded) for the per-level launch solver (0) and the persistent
-task-graph solver (2), B frames per launch.   python tools/time_solver.py [workload] [B ...]"""
+task-graph solver (2), B frames per launch.   python tools/time_solver.py [workload] [B ...] [--paths=3,0]"""
 import os
 import sys
 import time
@@ -12,6 +12,9 @@ dev = torch.device("cuda", 0)
 wl = sys.argv[1] if len(sys.argv) > 1 else "C2"
 Bs = [int(x) for x in sys.argv[2:] if not x.startswith("-")] or [1, 8]
 PATHS = (3,) if "--launches" in sys.argv else ((2,) if "--dag" in sys.argv else ((4,) if "--hybrid" in sys.argv else (3, 2, 4)))
+for a in sys.argv:
+    if a.startswith("--paths="):        # any list of solver_path values, e.g. --paths=3,0
+        PATHS = tuple(int(x) for x in a[8:].split(","))
 for B in Bs:
     frames = [DeviceFrame.from_scene(synth.make_scene(seed=s, **synth.WORKLOADS[wl]), dev) for s in range(B)]
     for sp in PATHS:
