@@ -247,6 +247,52 @@ int slm_lm_exchange_ptr(slm_solver* s, int32_t slot, int32_t what, double** devi
 int slm_lm_exchange_get(slm_solver* s, int32_t slot, int32_t what, double* out_device, void* stream);
 int slm_lm_exchange_set(slm_solver* s, int32_t slot, int32_t what, const double* in_device, void* stream);
 
+/* -- flow-correspondence term of the LM path (opt.sf_corr; the reference left it commented out, super/LM.py:27-29) ------
+ * A fourth term beside ICP + ARAP + Rot: per surfel i a target point o_i, a target normal n_i and a flag valid_i, FROZEN at
+ * the bind and constant for the whole LM run.  T_i(beta) the skinned surfel, lambda = weight (loss = (lambda ...)^2 like
+ * the other LM terms; GraphFit multiplies the squared sum by its weight instead):
+ *   mode 1 'point-point':  r_i = lambda (T_i - o_i), three rows  lambda [ w_k d(R(q_k)(p - g_k))/dq_k | w_k I3 ] per neighbour
+ *   mode 2 'point-plane':  r_i = lambda n_i.(T_i - o_i), one row, n_i^T times the rows above
+ * No dependence through the projection (the targets do not move with beta).  The loss sum_valid |r_i|^2 is part of the
+ * iteration's loss (accept / reject, slm_iter_record.loss); M_grad / M_loss stay the ICP match counts.
+ *
+ * slm_enable_corr: after slm_create, before the first bind.  mode 0 switches the option off again.  An enabled solver
+ * takes the pair-record form of the data term (k_data_grad_pairs, the form of num_neighbors != 4) for EVERY num_neighbors,
+ * 4 included, for binds and slm_prepare_model, with or without bound correspondences: at num_neighbors 4 that form is
+ * slower than the default tuple-sorted one.  Refusals:
+ *   SLM_ERR_INVALID      "slm_enable_corr: null argument"
+ *                        "slm_enable_corr: mode must be 0 (off), 1 (point-point) or 2 (point-plane)"
+ *                        "slm_enable_corr: weight must be finite"
+ *                        "slm_enable_corr: a slot is already bound; call it after slm_create and before the first bind"
+ *   SLM_ERR_UNSUPPORTED  "slm_enable_corr: needs the pair-record data path (data_path 0 or 2)"
+ *                        "slm_enable_corr: needs a nested-dissection solver_path (0, 2, 3 or 4)"
+ *                        "slm_enable_corr: needs the data term (use_data 1)"
+ *                        "slm_enable_corr: the solver is sharded (slm_set_shard); the term needs every surfel of the frame on one device"
+ *   and, on an enabled solver,
+ *   SLM_ERR_UNSUPPORTED  "slm_set_shard: the correspondence term is enabled (slm_enable_corr); it needs every surfel of the frame on one device"
+ *                        "slm_bind_frame: the correspondence term (slm_enable_corr) needs J < 65536"
+ *
+ * slm_bind_corr_flow: after slm_bind_frame.  flow (2,H,W) float32 device, x then y displacement; the targets are built
+ * on the device exactly as GraphFit's term reads them at zero deformation: (u, v) = the unrounded projection of
+ * sf_points[i] (Z + 1e-8), the flow sampled there grid_sample-style (float32 grid, bilinear, zero padding,
+ * align_corners=False), validity margin 1 on the shifted float coordinates, o / n from the four taps through index_map (all
+ * four mapped).  slm_bind_corr_points copies the caller's targets instead (device pointers: pts (N,3), nrm (N,3) -- may be
+ * null in mode 1 --, valid (N)).  slm_bind_frame clears a slot's correspondences; a slot with none runs without the term.
+ *   SLM_ERR_INVALID      "<fn>: null argument"   "<fn>: bad slot"
+ *                        "slm_bind_corr_points: nrm is required in mode 2 (point-plane)"
+ *   SLM_ERR_UNSUPPORTED  "<fn>: slm_enable_corr first"
+ *   SLM_ERR_UNBOUND      "<fn>: slm_bind_frame first"
+ *
+ * slm_corr_get_targets: the slot's targets back (device pointers, each may be null).  slm_corr_loss: out_device[0] =
+ * sum_valid |r_i|^2 at the slot's current beta, [1] = the kept count; {0, 0} for a slot without correspondences.  Both
+ * refuse like the binds, and slm_corr_get_targets also with
+ *   SLM_ERR_UNBOUND      "slm_corr_get_targets: no correspondences bound to the slot" */
+int slm_enable_corr(slm_solver* s, int32_t mode, double weight);
+int slm_bind_corr_flow(slm_solver* s, int32_t slot, const float* flow, void* stream);
+int slm_bind_corr_points(slm_solver* s, int32_t slot, const double* pts, const double* nrm, const uint8_t* valid, void* stream);
+int slm_corr_get_targets(slm_solver* s, int32_t slot, double* pts, double* nrm, uint8_t* valid, void* stream);
+int slm_corr_loss(slm_solver* s, int32_t slot, double* out_device, void* stream);
+
 /* -- phase timing (bench.py roofline leg) ----------------------------------------- */
 /* With profiling on, slm_run brackets each phase of every LM iteration with HIP events
  * recorded on the launch stream.  Phases: */

@@ -13,6 +13,7 @@
 #include <cstring>
 
 #include "slm_common.h"
+#include "slm_corr.h"
 #include "slm_host.h"
 #include "slm_launch.h"
 #include "slm_prep.h"
@@ -63,6 +64,11 @@ struct PinnedBuf {
 
 constexpr int kLossBlocks = 512;   // data-loss partial sums per slot
 constexpr int kRegBlocksMax = 64;
+// the correspondence term's loss partials (slm_corr.h): SLM_CORR_BLOCKS {sum, 0} pairs right behind the regularisers' pairs
+// of the launch (k_accept sums them with a larger count), the kept counts at a fixed place behind every pair
+constexpr int kCorrBlocks = SLM_CORR_BLOCKS;
+constexpr int kCorrCntPart = 2 * (kRegBlocksMax + kCorrBlocks);
+constexpr size_t kLossPartDoubles = (size_t)2 * (kLossBlocks + kRegBlocksMax + kCorrBlocks) + kCorrBlocks;
 
 // The form of the data term: which plan the bind prepares and which kernels the LM entry points launch.
 enum class DataForm {
@@ -72,10 +78,11 @@ enum class DataForm {
   per_entry,   // data_path 1, J >= 65 536, a K-generic frame on the block-banded solver: k_data_grad<K>'s atomics
 };
 // a frame's form, decided at bind (a plan that comes out empty leaves the slot per_entry: bind_model_part)
-DataForm data_form_of(const slm_config& c, const slm_frame& f) {
+// corr: the solver carries the correspondence term (slm_enable_corr), which adds into the pair records: pairs for every K
+DataForm data_form_of(const slm_config& c, const slm_frame& f, bool corr) {
   if (!c.use_data || f.N <= 0) return DataForm::none;
   if (c.data_path == 1 || f.J >= 65536) return DataForm::per_entry;
-  if (f.K == SLM_K) return DataForm::tuple;
+  if (f.K == SLM_K && !corr) return DataForm::tuple;
   return c.solver_path != 1 ? DataForm::pairs : DataForm::per_entry;
 }
 
@@ -97,6 +104,8 @@ struct Slot {
   FrameDev h{};                 // host mirror of the device descriptor
   size_t cap_beta = 0, cap_vec = 0, cap_band = 0, cap_linv = 0, cap_npk = 0, cap_tpn = 0, cap_tpx = 0, cap_ev = 0;
   V1Plan plan;                  // tuple-sorted assembly buffers (grow-only)
+  CorrDev corr{};               // correspondence term: host mirror of the slot's targets (grow-only buffers)
+  size_t cap_corr_o = 0, cap_corr_n = 0, cap_corr_v = 0;
   PairPlan pplan;               // K-generic pair path (num_neighbors != 4): pair keys, per-surfel pair indices, surfel order
   PlanCache cache;              // nested-dissection plan: host copy; its device mirrors below (grow-only)
   NDDest* d_cur_dests = nullptr;   // PlanCache::frame_dest on the device
@@ -299,6 +308,9 @@ struct slm_solver {
   int* reuse_dev = nullptr;     // per slot: 1 after a rejected iteration -- the next Jacobian pass of the LM loop reuses the
                                 // records of the last one (k_accept writes, k_data_gram / k_iter_begin_nd read)
   int rank = 0, world = 1;      // surfel sharding of every frame (slm_set_shard)
+  int corr_mode = 0;            // slm_enable_corr: 0 off, 1 point-point, 2 point-plane; its weight; the slots' targets on the device
+  double corr_w = 0.0;
+  CorrDev* corr_dev = nullptr;
   bool shard_mode = false;      // slm_set_shard was called (world == 1 included): slots carry the exchange buffers
 };
 namespace {
@@ -540,6 +552,9 @@ int slm_destroy(slm_solver* s) {
     if (sl.flinv) (void)hipFree(sl.flinv);
     if (sl.fmail) (void)hipFree(sl.fmail);
     if (sl.pairbuf) (void)hipFree(sl.pairbuf);
+    if (sl.corr.o) (void)hipFree(sl.corr.o);
+    if (sl.corr.n) (void)hipFree(sl.corr.n);
+    if (sl.corr.valid) (void)hipFree(sl.corr.valid);
     if (sl.d_dag_flags) (void)hipFree(sl.d_dag_flags);
     if (sl.d_dag_trace) (void)hipFree(sl.d_dag_trace);
     if (sl.prep_fork) (void)hipEventDestroy(sl.prep_fork);
@@ -559,6 +574,7 @@ int slm_destroy(slm_solver* s) {
   if (s->frames_dev) (void)hipFree(s->frames_dev);
   if (s->bw_dev) (void)hipFree(s->bw_dev);
   if (s->reuse_dev) (void)hipFree(s->reuse_dev);
+  if (s->corr_dev) (void)hipFree(s->corr_dev);
   if (s->bw_host) (void)hipHostFree(s->bw_host);
   delete s;
   return SLM_OK;
@@ -632,6 +648,8 @@ static int check_model_args(const slm_solver* s, int32_t slot, const slm_frame* 
   if (f->K_ED < 1 || f->K_ED > SLM_MAX_KED)
     return fail(SLM_ERR_UNSUPPORTED, "slm_bind_frame: num_ED_neighbors must be in 1..8");
   if (f->N < 0 || f->J < 1) return fail(SLM_ERR_INVALID, "slm_bind_frame: bad sizes");
+  if (s->corr_mode && f->J >= 65536)   // (the pair keys are a * J + b in 32 bits: such a frame takes the per-entry form)
+    return fail(SLM_ERR_UNSUPPORTED, "slm_bind_frame: the correspondence term (slm_enable_corr) needs J < 65536");
   if (f->N > 0 && f->J < f->K)   // (the reference's top-k of K among J nodes raises; the device checks below assume J >= K)
     return fail(SLM_ERR_INVALID, "slm_bind_frame: fewer nodes (J) than num_neighbors: sf_knn_idx cannot hold K distinct ids");
   if ((f->N > 0 && (!f->sf_points || !f->sf_knn_idx || !f->sf_knn_w)) || !f->ed_points || !f->ed_knn_idx)
@@ -664,8 +682,8 @@ static int reset_slot(slm_solver* s, Slot& sl, const slm_frame* f, hipStream_t s
   HIPCHK(grow(h.rhs, sl.cap_vec, (size_t)nt * SLM_NB));
   if (!h.loss_part) {
     size_t cap = 0;   // (fixed size: allocated once)
-    HIPCHK(grow(h.loss_part, cap, (size_t)2 * (kLossBlocks + kRegBlocksMax)));
-    HIPCHK(hipMemsetAsync(h.loss_part, 0, sizeof(double) * 2 * (kLossBlocks + kRegBlocksMax), st));
+    HIPCHK(grow(h.loss_part, cap, kLossPartDoubles));
+    HIPCHK(hipMemsetAsync(h.loss_part, 0, sizeof(double) * kLossPartDoubles, st));
   }
   if (!h.st) HIPCHK(hipMalloc((void**)&h.st, sizeof(LMState)));
 #ifdef SLM_STAMPS
@@ -692,7 +710,7 @@ static int bind_data_plan(slm_solver* s, Slot& sl, const slm_frame* f, hipStream
   FrameDev& h = sl.h;
   h.v1_ready = 0;
   h.vk_ready = 0;
-  out.form = data_form_of(s->cfg, *f);
+  out.form = data_form_of(s->cfg, *f, s->corr_mode != 0);
   if (out.form == DataForm::tuple) {
     V1Sizes sz;
     HIPCHK(prep_v1(prep, *f, sl.plan, &sz, st));
@@ -985,6 +1003,10 @@ static int bind_target_part(slm_solver* s, int32_t slot, const slm_frame* f, hip
   HIPCHK(grow(h.tgt_px, sl.cap_tpx, (size_t)2 * f->H * f->W));
   launch_pack_target_px(f->H * f->W, f->index_map, f->tgt_valid, f->tgt_points, f->tgt_norms, h.tgt_px, st);
   h.bound = 1;
+  if (s->corr_mode) {   // a new frame: the slot's correspondences belonged to the last one
+    sl.corr.has = 0;
+    HIPCHK(hipMemsetAsync(&s->corr_dev[slot].has, 0, sizeof(int32_t), st));
+  }
   // descriptor -> device through the slot's pinned mirror: no wait for the copy (the mirror always holds the newest
   // host state, and every change of it is followed by another copy on the stream)
   if (!sl.h_pin) HIPCHK(hipHostMalloc((void**)&sl.h_pin, sizeof(FrameDev), hipHostMallocDefault));
@@ -1267,6 +1289,8 @@ namespace {
 struct BatchDims {
   int maxN = 0, maxJKe = 0, nt_max = 0, wb_cap = 0, n_reg_part = 0;
   int max_pos = 0, max_blocks = 0, maxP = 0;
+  bool corr = false;   // some slot of the batch has correspondences bound (the term's Jacobian pass runs)
+  int n_acc_part = 0;  // what k_accept sums behind the data partials: the regularisers' pairs, on an enabled solver the term's too
   int K = 0;        // num_neighbors of the batch's slots (-1: they differ -- refused by the callers of the per-surfel kernels)
   int gram_variants = 0;   // bit0: workgroup-merged records in use, bit1: per-run slab in use
   bool nd = true;   // every slot of the batch has a nested-dissection plan (false: the block-banded solver)
@@ -1305,6 +1329,7 @@ BatchDims dims_of(slm_solver* s, int first, int n, bool band = false) {
       d.max_top_tasks = std::max(d.max_top_tasks, h.n_dag_top_tasks);
     }
     d.maxP = std::max(d.maxP, h.P);
+    d.corr = d.corr || (s->corr_mode && s->slots[i].corr.has);
   }
   d.nd = d.nd && !band;
   // tuple-sorted on either solver; the pair records need the multifrontal one; per-entry atomics otherwise
@@ -1355,6 +1380,7 @@ BatchDims dims_of(slm_solver* s, int first, int n, bool band = false) {
   }
   if (s->cfg.use_arap || s->cfg.use_rot)
     d.n_reg_part = std::min(kRegBlocksMax, (d.maxJKe + 255) / 256);
+  d.n_acc_part = d.n_reg_part + (s->corr_mode ? kCorrBlocks : 0);
   return d;
 }
 
@@ -1426,8 +1452,14 @@ void enqueue_jacobian(slm_solver* s, const FrameDev* fr, int n, const BatchDims&
       if (fused) launch_begin_and_gram(fr, n, d.max_pos, w, st, reuse, dag_cut);
       else launch_data_gram(fr, n, d.max_pos, w, d.gram_variants, st, reuse);
       break;
-    case DataForm::pairs: launch_data_grad_pairs(fr, n, d.maxN, d.K, w, st); break;   // per-pair records (zeroed, then filled)
-    case DataForm::per_entry: launch_data_grad(fr, n, d.maxN, d.K, w, st); break;
+    case DataForm::pairs:   // per-pair records (zeroed, then filled; the correspondence term adds into them)
+      launch_data_grad_pairs(fr, n, d.maxN, d.K, w, st);
+      if (d.corr) launch_corr_grad_pairs(fr, s->corr_dev + (fr - s->frames_dev), n, d.maxN, d.K, s->corr_mode, s->corr_w, st);
+      break;
+    case DataForm::per_entry:
+      launch_data_grad(fr, n, d.maxN, d.K, w, st);
+      if (d.corr) launch_corr_grad(fr, s->corr_dev + (fr - s->frames_dev), n, d.maxN, d.K, s->corr_mode, s->corr_w, st);
+      break;
     case DataForm::none: break;
   }
 }
@@ -1459,6 +1491,10 @@ void enqueue_scatter(slm_solver* s, const FrameDev* fr, int n, const BatchDims& 
 void enqueue_data_loss(slm_solver* s, const FrameDev* fr, int n, const BatchDims& d, hipStream_t st, bool at_beta) {
   if (d.form == DataForm::tuple && !at_beta) launch_data_eval(fr, n, kLossBlocks, s->cfg.w_data, 0, st);
   else if (d.form != DataForm::none) launch_data_loss(fr, n, kLossBlocks, d.K, s->cfg.w_data, at_beta ? 0 : 1, st);
+  // the correspondence term's partials, behind the regularisers' (every slot of an enabled solver: zeros without targets)
+  if (s->corr_mode && d.K >= 1)
+    launch_corr_loss(fr, s->corr_dev + (fr - s->frames_dev), n, d.K, s->corr_mode, s->corr_w, at_beta ? 0 : 1, 2 * d.n_reg_part,
+                     kCorrCntPart, st);
 }
 }  // namespace
 
@@ -1480,6 +1516,9 @@ int slm_set_shard(slm_solver* s, int32_t rank, int32_t world) {
   if (!s || world < 1 || rank < 0 || rank >= world) return fail(SLM_ERR_INVALID, "slm_set_shard: bad rank/world");
   if (s->cfg.data_path != 0 || s->cfg.solver_path == 1)
     return fail(SLM_ERR_UNSUPPORTED, "slm_set_shard: needs data_path 0 and a nested-dissection solver_path (0, 2, 3 or 4)");
+  if (s->corr_mode)
+    return fail(SLM_ERR_UNSUPPORTED, "slm_set_shard: the correspondence term is enabled (slm_enable_corr); it needs every surfel of "
+                                     "the frame on one device");
   s->rank = rank;
   s->world = world;
   s->shard_mode = true;
@@ -1643,7 +1682,7 @@ static void enqueue_lm_iteration(slm_solver* s, int first, int n, const BatchDim
   mark();
   enqueue_data_loss(s, fr, n, d, st, false);
   mark();
-  launch_accept(fr, n, c.phase_test, d.n_reg_part, std::max(c.num_iterations, 1), st, d.accept_reuse, d.accept_eval);
+  launch_accept(fr, n, c.phase_test, d.n_acc_part, std::max(c.num_iterations, 1), st, d.accept_reuse, d.accept_eval);
   mark();
 }
 
@@ -1851,6 +1890,115 @@ int slm_solve(slm_solver* s, int32_t slot, double u, double* delta, int32_t* sta
   HIPCHK(hipMemcpyAsync(delta, h.delta, sizeof(double) * h.P, hipMemcpyDeviceToDevice, st));
   if (status)
     HIPCHK(hipMemcpyAsync(status, &h.st->chol_fail, sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+  HIPCHK(hipGetLastError());
+  return SLM_OK;
+}
+
+
+// ---- flow-correspondence term (include/super_lm.h; kernels in slm_corr.hip) -----------------------------------------
+int slm_enable_corr(slm_solver* s, int32_t mode, double weight) {
+  if (!s) return fail(SLM_ERR_INVALID, "slm_enable_corr: null argument");
+  if (mode < 0 || mode > 2) return fail(SLM_ERR_INVALID, "slm_enable_corr: mode must be 0 (off), 1 (point-point) or 2 (point-plane)");
+  if (!(weight - weight == 0.0)) return fail(SLM_ERR_INVALID, "slm_enable_corr: weight must be finite");
+  if (s->cfg.data_path == 1) return fail(SLM_ERR_UNSUPPORTED, "slm_enable_corr: needs the pair-record data path (data_path 0 or 2)");
+  if (s->cfg.solver_path == 1) return fail(SLM_ERR_UNSUPPORTED, "slm_enable_corr: needs a nested-dissection solver_path (0, 2, 3 or 4)");
+  if (!s->cfg.use_data) return fail(SLM_ERR_UNSUPPORTED, "slm_enable_corr: needs the data term (use_data 1)");
+  if (s->shard_mode)
+    return fail(SLM_ERR_UNSUPPORTED, "slm_enable_corr: the solver is sharded (slm_set_shard); the term needs every surfel of the frame "
+                                     "on one device");
+  for (const Slot& sl : s->slots)
+    if (sl.h.bound || sl.prep_ticket || sl.model_ready)
+      return fail(SLM_ERR_INVALID, "slm_enable_corr: a slot is already bound; call it after slm_create and before the first bind");
+  if (mode && !s->corr_dev) {
+    HIPCHK(hipMalloc((void**)&s->corr_dev, sizeof(CorrDev) * s->slots.size()));
+    HIPCHK(hipMemset(s->corr_dev, 0, sizeof(CorrDev) * s->slots.size()));
+  }
+  s->corr_mode = mode;
+  s->corr_w = mode ? weight : 0.0;
+  return SLM_OK;
+}
+
+// the argument checks the four per-slot entry points share; *out = the slot
+static int corr_slot(const char* fn, slm_solver* s, bool args_ok, int32_t slot, Slot** out) {
+  const std::string pre = std::string(fn) + ": ";
+  if (!s || !args_ok) return fail(SLM_ERR_INVALID, pre + "null argument");
+  if (slot < 0 || slot >= (int)s->slots.size()) return fail(SLM_ERR_INVALID, pre + "bad slot");
+  if (!s->corr_mode) return fail(SLM_ERR_UNSUPPORTED, pre + "slm_enable_corr first");
+  join_prepare(s, slot);
+  if (!s->slots[slot].h.bound) return fail(SLM_ERR_UNBOUND, pre + "slm_bind_frame first");
+  *out = &s->slots[slot];
+  return SLM_OK;
+}
+
+// the slot's target buffers at the bound frame's size, and the descriptor (has = 1) on its way to the device
+static int corr_publish(slm_solver* s, int slot, Slot& sl, hipStream_t st) {
+  sl.corr.has = 1;
+  HIPCHK(hipMemcpyAsync(s->corr_dev + slot, &sl.corr, sizeof(CorrDev), hipMemcpyHostToDevice, st));
+  HIPCHK(hipStreamSynchronize(st));   // (the source is the slot's own mirror, which the next bind rewrites)
+  return SLM_OK;
+}
+static int corr_buffers(Slot& sl) {
+  const size_t N = (size_t)std::max(sl.h.f.N, 1);
+  HIPCHK(grow(sl.corr.o, sl.cap_corr_o, 3 * N));
+  HIPCHK(grow(sl.corr.n, sl.cap_corr_n, 3 * N));
+  HIPCHK(grow(sl.corr.valid, sl.cap_corr_v, N));
+  return SLM_OK;
+}
+
+int slm_bind_corr_flow(slm_solver* s, int32_t slot, const float* flow, void* stream) {
+  Slot* sp = nullptr;
+  int rc = corr_slot("slm_bind_corr_flow", s, flow != nullptr, slot, &sp);
+  if (rc) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  if ((rc = corr_buffers(*sp)) != SLM_OK) return rc;
+  // (the kernel reads the buffers' addresses from the device descriptor: publish first)
+  if ((rc = corr_publish(s, slot, *sp, st)) != SLM_OK) return rc;
+  launch_corr_targets(s->frames_dev, s->corr_dev, slot, sp->h.f.N, flow, st);
+  HIPCHK(hipGetLastError());
+  return SLM_OK;
+}
+
+int slm_bind_corr_points(slm_solver* s, int32_t slot, const double* pts, const double* nrm, const uint8_t* valid, void* stream) {
+  Slot* sp = nullptr;
+  int rc = corr_slot("slm_bind_corr_points", s, pts != nullptr && valid != nullptr, slot, &sp);
+  if (rc) return rc;
+  if (s->corr_mode == 2 && !nrm) return fail(SLM_ERR_INVALID, "slm_bind_corr_points: nrm is required in mode 2 (point-plane)");
+  hipStream_t st = (hipStream_t)stream;
+  if ((rc = corr_buffers(*sp)) != SLM_OK) return rc;
+  const size_t N = (size_t)sp->h.f.N;
+  if (N > 0) {
+    HIPCHK(hipMemcpyAsync(sp->corr.o, pts, sizeof(double) * 3 * N, hipMemcpyDeviceToDevice, st));
+    if (nrm) HIPCHK(hipMemcpyAsync(sp->corr.n, nrm, sizeof(double) * 3 * N, hipMemcpyDeviceToDevice, st));
+    else HIPCHK(hipMemsetAsync(sp->corr.n, 0, sizeof(double) * 3 * N, st));
+    HIPCHK(hipMemcpyAsync(sp->corr.valid, valid, N, hipMemcpyDeviceToDevice, st));
+  }
+  return corr_publish(s, slot, *sp, st);
+}
+
+int slm_corr_get_targets(slm_solver* s, int32_t slot, double* pts, double* nrm, uint8_t* valid, void* stream) {
+  Slot* sp = nullptr;
+  int rc = corr_slot("slm_corr_get_targets", s, true, slot, &sp);
+  if (rc) return rc;
+  if (!sp->corr.has) return fail(SLM_ERR_UNBOUND, "slm_corr_get_targets: no correspondences bound to the slot");
+  hipStream_t st = (hipStream_t)stream;
+  const size_t N = (size_t)sp->h.f.N;
+  if (N > 0) {
+    if (pts) HIPCHK(hipMemcpyAsync(pts, sp->corr.o, sizeof(double) * 3 * N, hipMemcpyDeviceToDevice, st));
+    if (nrm) HIPCHK(hipMemcpyAsync(nrm, sp->corr.n, sizeof(double) * 3 * N, hipMemcpyDeviceToDevice, st));
+    if (valid) HIPCHK(hipMemcpyAsync(valid, sp->corr.valid, N, hipMemcpyDeviceToDevice, st));
+  }
+  return SLM_OK;
+}
+
+int slm_corr_loss(slm_solver* s, int32_t slot, double* out, void* stream) {
+  Slot* sp = nullptr;
+  int rc = corr_slot("slm_corr_loss", s, out != nullptr, slot, &sp);
+  if (rc) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  if ((rc = clear_flags(s, slot, st)) != SLM_OK) return rc;
+  const int part = 2 * kRegBlocksMax;   // (any place behind the regularisers' pairs: every LM iteration rewrites its own)
+  launch_corr_loss(s->frames_dev + slot, s->corr_dev + slot, 1, sp->h.f.K, s->corr_mode, s->corr_w, 0, part, kCorrCntPart, st);
+  launch_corr_loss_out(s->frames_dev, slot, part, kCorrCntPart, out, st);
   HIPCHK(hipGetLastError());
   return SLM_OK;
 }

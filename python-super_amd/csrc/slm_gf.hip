@@ -12,8 +12,8 @@
 // Gradient of the global row is divided by J before the step (deform_mesh.py:326).
 // Local rows: summed per workgroup in an LDS table, then one f64 atomic per entry and touched node; the global row is reduced per block first.
 //
-// Layout of this file: k_gf_zero / k_gf_fold; the samplers (gf_sample, gf_flow_sample); the stages of k_gf_data, each a
-// function with its inputs and outputs in its signature (gf_project, gf_sem_weight, gf_point_plane, gf_corr, gf_row_pass,
+// Layout of this file: k_gf_zero / k_gf_fold; the stages of k_gf_data, each a function with its inputs and outputs in its
+// signature (the samplers gf_sample / gf_flow_sample and gf_project come from slm_gf_sample.h; gf_sem_weight, gf_point_plane, gf_corr, gf_row_pass,
 // gf_table_flush, gf_block_partials) and the kernel that runs them; the node terms (gf_reg_body); k_gf_step; bind / update
 // kernels.  Host: gf_slot (every entry point's argument checks), gf_dims, gf_publish_pgrad, gf_upload_slot, gf_launch_step,
 // gf_enqueue_morph / gf_enqueue_eval (the one evaluation sequence), then the entry points.
@@ -24,6 +24,7 @@
 #include "slm_host.h"
 #include "slm_sem.h"
 #include "slm_lane.h"
+#include "slm_gf_sample.h"
 
 __global__ void __launch_bounds__(256) k_gf_zero(GfSlot* __restrict__ slots) {
   GfSlotDev& s = gf_dev(slots)[blockIdx.y];
@@ -47,81 +48,6 @@ __global__ void __launch_bounds__(64) k_gf_fold(GfSlot* __restrict__ slots, int 
   if (t == 0.0) return;
   if (a < GFP_PP_LOSS) s.grad[7 * s.f.base.J + a] += t;
   else s.terms[gf_part_term(a)] += t;
-}
-
-// 4-tap gather of the target maps at the float pixel (u_, v_) (bilinear_sample, loss.py:9-80, zero fill):
-// false when a tap is unmapped.  o / n = interpolated point / normal, d*u / d*v their derivatives along u / v
-// (autograd through clamp(1 - |tap - x|): d|x|/dx = sign(x) with sign(0) = 0).
-struct GfSample {
-  d3 o, n, dou, dov, dnu, dnv;
-  int rows[4];
-  double wv[4];
-};
-
-__device__ __forceinline__ bool gf_sample(const FrameIn& f, double u_, double v_, GfSample& q) {
-  const double fv = floor(v_), cv = ceil(v_), fu = floor(u_), cu = ceil(u_);
-  const double nn[4] = {fv, fv, cv, cv}, mm[4] = {fu, cu, fu, cu};
-  bool all_ok = true;
-#pragma unroll
-  for (int t = 0; t < 4; ++t) {
-    q.rows[t] = f.index_map[(int)nn[t] * f.W + (int)mm[t]];
-    all_ok = all_ok && q.rows[t] >= 0;
-  }
-  if (!all_ok) return false;
-  d3 o = {0, 0, 0}, n = {0, 0, 0}, dou = {0, 0, 0}, dov = {0, 0, 0}, dnu = {0, 0, 0}, dnv = {0, 0, 0};
-#pragma unroll
-  for (int t = 0; t < 4; ++t) {
-    const double dn = nn[t] - v_, dm = mm[t] - u_;
-    const double an = fmax(1.0 - fabs(dn), 0.0), am = fmax(1.0 - fabs(dm), 0.0);
-    const float* tp = f.tgt_points + 3 * (size_t)q.rows[t];
-    const float* tn = f.tgt_norms + 3 * (size_t)q.rows[t];
-    const d3 Pt = {(double)tp[0], (double)tp[1], (double)tp[2]};
-    const d3 Nt = {(double)tn[0], (double)tn[1], (double)tn[2]};
-    const double wv = an * am;
-    const double sn = dn > 0.0 ? 1.0 : (dn < 0.0 ? -1.0 : 0.0);
-    const double smm = dm > 0.0 ? 1.0 : (dm < 0.0 ? -1.0 : 0.0);
-    const double gu = an * smm, gvv = am * sn;
-    q.wv[t] = wv;
-    o = {o.x + Pt.x * wv, o.y + Pt.y * wv, o.z + Pt.z * wv};
-    n = {n.x + Nt.x * wv, n.y + Nt.y * wv, n.z + Nt.z * wv};
-    dou = {dou.x + Pt.x * gu, dou.y + Pt.y * gu, dou.z + Pt.z * gu};
-    dov = {dov.x + Pt.x * gvv, dov.y + Pt.y * gvv, dov.z + Pt.z * gvv};
-    dnu = {dnu.x + Nt.x * gu, dnu.y + Nt.y * gu, dnu.z + Nt.z * gu};
-    dnv = {dnv.x + Nt.x * gvv, dnv.y + Nt.y * gvv, dnv.z + Nt.z * gvv};
-  }
-  q.o = o; q.n = n; q.dou = dou; q.dov = dov; q.dnu = dnu; q.dnv = dnv;
-  return true;
-}
-
-// The optical flow (2,H,W float32: x then y displacement) at the float pixel (u, v), sampled the way
-// F.grid_sample(flow, grid) does at deform_mesh.py / loss.py:318-323: the grid is float32, bilinear, zero padding,
-// align_corners=False, i.e. position ((g + 1) * size - 1) / 2 in float32; fl = (flow_x, flow_y) and
-// D = [[dfx/du, dfx/dv], [dfy/du, dfy/dv]] (the grid gradient of the same cell, what autograd returns).
-__device__ __forceinline__ void gf_flow_sample(const float* __restrict__ flow, int H, int W, double u, double v,
-                                               double fl[2], double D[4]) {
-  const float gx = (float)(u * 2.0 / (double)W - 1.0), gy = (float)(v * 2.0 / (double)H - 1.0);
-  const float ix = __fsub_rn(__fmul_rn(__fadd_rn(gx, 1.f), 0.5f * (float)W), 0.5f);
-  const float iy = __fsub_rn(__fmul_rn(__fadd_rn(gy, 1.f), 0.5f * (float)H), 0.5f);
-  const float xw = floorf(ix), yn = floorf(iy);
-  const float w = __fsub_rn(ix, xw), e = __fsub_rn(1.f, w), n = __fsub_rn(iy, yn), sth = __fsub_rn(1.f, n);
-  const int x0 = (int)xw, y0 = (int)yn;
-  const bool okx0 = x0 >= 0 && x0 < W, okx1 = x0 + 1 >= 0 && x0 + 1 < W;
-  const bool oky0 = y0 >= 0 && y0 < H, oky1 = y0 + 1 >= 0 && y0 + 1 < H;
-#pragma unroll
-  for (int c = 0; c < 2; ++c) {
-    const float* fc = flow + (size_t)c * H * W;
-    const float nw = (okx0 && oky0) ? fc[(size_t)y0 * W + x0] : 0.f;
-    const float ne = (okx1 && oky0) ? fc[(size_t)y0 * W + x0 + 1] : 0.f;
-    const float sw = (okx0 && oky1) ? fc[(size_t)(y0 + 1) * W + x0] : 0.f;
-    const float se = (okx1 && oky1) ? fc[(size_t)(y0 + 1) * W + x0 + 1] : 0.f;
-    float acc = __fmul_rn(nw, __fmul_rn(e, sth));
-    acc = __fadd_rn(acc, __fmul_rn(ne, __fmul_rn(w, sth)));
-    acc = __fadd_rn(acc, __fmul_rn(sw, __fmul_rn(e, n)));
-    acc = __fadd_rn(acc, __fmul_rn(se, __fmul_rn(w, n)));
-    fl[c] = (double)acc;
-    D[2 * c + 0] = ((double)ne - (double)nw) * (double)sth + ((double)se - (double)sw) * (double)n;
-    D[2 * c + 1] = ((double)sw - (double)nw) * (double)e + ((double)se - (double)ne) * (double)w;
-  }
 }
 
 struct GfRegArgs {
@@ -150,22 +76,6 @@ struct GfDataArgs {
 };
 
 // ---- the stages of k_gf_data, in the order the kernel runs them --------------------------------------------------------------
-// the projection of P and the rows of its Jacobian: (u, v) = (fx X / Ze + cx, fy Y / Ze + cy), Ze = Z + 1e-8 -- the forward
-// divides by Z + 1e-8, and so does its derivative
-struct GfProj {
-  double u, v;
-  d3 Pi0, Pi1;   // du/dP, dv/dP
-};
-__device__ __forceinline__ GfProj gf_project(const FrameIn& f, const d3 P) {
-  const double fx = (double)f.fx, fy = (double)f.fy, cx = (double)f.cx, cy = (double)f.cy;
-  const double Ze = P.z + 1e-8;
-  GfProj pr;
-  pr.Pi0 = {fx / Ze, 0.0, -fx * P.x / (Ze * Ze)};
-  pr.Pi1 = {0.0, fy / Ze, -fy * P.y / (Ze * Ze)};
-  pr.u = P.x * fx / Ze + cx;
-  pr.v = P.y * fy / Ze + cy;
-  return pr;
-}
 
 // G (n + s0 A + s1 B): dL/dP of a residual along n whose sample position moves with P by A = du/dP, B = dv/dP
 __device__ __forceinline__ d3 gf_resid_grad(const double G, const d3 n, const double s0, const double s1, const d3 A, const d3 B) {

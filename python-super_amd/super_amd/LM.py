@@ -130,12 +130,29 @@ class LM_Solver():
     """Drop-in for ``super.LM.LM_Solver``; see module docstring."""
 
     def __init__(self, opt, convs=None, max_frames=1, shard_surfels=False, rank=None, world=None,
-                 all_reduce=None, broadcast=None):
+                 all_reduce=None, broadcast=None, corr_term=False):
         """``LM_Solver(opt, convs)`` as in the reference.  ``shard_surfels=True`` (after
         ``torch.distributed.init_process_group``) splits the surfels of ONE large frame over the GPUs
         of a node: every rank evaluates its share, the block-sparse J^T J / J^T r sums and the loss are
-        all-reduced, every rank solves and takes rank 0's step."""
+        all-reduced, every rank solves and takes rank 0's step.
+        ``corr_term=True`` (opt-in; needs ``opt.sf_corr``) adds the flow-correspondence term the reference left commented
+        out (``super/LM.py:27-29``): weight ``opt.sf_corr_weight``, form ``opt.sf_corr_loss_type``, targets frozen per
+        frame from ``LM(..., flow=)`` or ``LM(..., corr_points=)`` (``slm_enable_corr``, include/super_lm.h).  Without it
+        ``opt.sf_corr`` is ignored by this class and nothing changes."""
         self.opt = opt
+        self.corr_mode = 0
+        if corr_term:
+            if not getattr(opt, "sf_corr", False):
+                raise ValueError("LM_Solver(corr_term=True) needs opt.sf_corr")
+            lt = getattr(opt, "sf_corr_loss_type", "point-point")
+            if lt not in ("point-point", "point-plane"):
+                raise ValueError(f"sf_corr_loss_type {lt!r}")
+            if shard_surfels or world is not None:
+                raise NotImplementedError("LM_Solver: corr_term with shard_surfels is not built (the term needs every "
+                                          "surfel of the frame on one device)")
+            self.corr_mode = 1 if lt == "point-point" else 2
+            self.corr_weight = float(getattr(opt, "sf_corr_weight", 0.001))
+        self.last_corr_kept = None                   # per slot: correspondences kept in the last run (None: slot without)
         self.lib = _lib.load()                       # raises if the HIP library is missing
         self.device = torch.device("cuda", torch.cuda.current_device()) \
             if torch.cuda.is_available() else None
@@ -188,6 +205,8 @@ class LM_Solver():
             out = C.c_void_p()
             _lib.check(self.lib.slm_create(C.byref(cfg), C.byref(out)), "slm_create")
             h = out
+            if self.corr_mode:
+                _lib.check(self.lib.slm_enable_corr(h, self.corr_mode, self.corr_weight), "slm_enable_corr")
             if self.sharded:
                 _lib.check(self.lib.slm_set_shard(h, self.rank, self.world), "slm_set_shard")
             self._solvers[key] = h
@@ -233,6 +252,52 @@ class LM_Solver():
             self._bound[i] = bf
         return bfs
 
+    def _bind_corr(self, h, slot, bf, corr):
+        """The correspondences of a bound slot: a flow (1,2,H,W), a ``(pts, nrm, valid)`` triple, or ``None`` (no term)."""
+        if not self.corr_mode:
+            if corr is not None:
+                raise ValueError("flow / corr_points need LM_Solver(opt, corr_term=True)")
+            return
+        if corr is None:
+            return
+        dev, st = bf.device, _stream_ptr(bf.device)
+        if torch.is_tensor(corr):
+            fl = _as(corr, torch.float32, dev)
+            if tuple(fl.shape) != (1, 2, bf.c.H, bf.c.W):
+                raise ValueError(f"flow must be (1,2,{bf.c.H},{bf.c.W}), got {tuple(fl.shape)}")
+            bf.corr_keep = (fl,)                       # read by the bind's kernel on the stream
+            _lib.check(self.lib.slm_bind_corr_flow(h, slot, _dev_ptr(fl), st), "slm_bind_corr_flow")
+            return
+        pts, nrm, valid = corr
+        N = bf.c.N
+        pts = _as(pts, torch.float64, dev)
+        valid = _as(valid, torch.uint8, dev)
+        nrm = None if nrm is None else _as(nrm, torch.float64, dev)
+        if tuple(pts.shape) != (N, 3) or tuple(valid.shape) != (N,) or (nrm is not None and tuple(nrm.shape) != (N, 3)):
+            raise ValueError(f"corr_points must be ((N,3), (N,3) or None, (N,)) with N = {N}")
+        bf.corr_keep = (pts, nrm, valid)
+        _lib.check(self.lib.slm_bind_corr_points(h, slot, _dev_ptr(pts), None if nrm is None else _dev_ptr(nrm),
+                                                 _dev_ptr(valid), st), "slm_bind_corr_points")
+
+    def corr_targets(self, slot=0, u=10, v=7.5, minimal_loss=1e10):
+        """The bound targets of a slot: (pts (N,3) f64, nrm (N,3) f64, valid (N,) bool) on the device."""
+        h, bf = self._handle(u, v, minimal_loss), self._bound[slot]
+        N, dev = bf.c.N, bf.device
+        pts = torch.empty((N, 3), dtype=torch.float64, device=dev)
+        nrm = torch.empty((N, 3), dtype=torch.float64, device=dev)
+        valid = torch.empty(N, dtype=torch.uint8, device=dev)
+        _lib.check(self.lib.slm_corr_get_targets(h, slot, _dev_ptr(pts), _dev_ptr(nrm), _dev_ptr(valid), _stream_ptr(dev)),
+                   "slm_corr_get_targets")
+        return pts, nrm, valid.bool()
+
+    def corr_loss(self, slot=0, u=10, v=7.5, minimal_loss=1e10):
+        """(sum of squared correspondence residuals at the slot's current beta, kept count)."""
+        h, bf = self._handle(u, v, minimal_loss), self._bound[slot]
+        out = torch.empty(2, dtype=torch.float64, device=bf.device)
+        _lib.check(self.lib.slm_corr_loss(h, slot, _dev_ptr(out), _stream_ptr(bf.device)), "slm_corr_loss")
+        o = out.cpu()
+        return float(o[0]), int(o[1])
+
     def prepare_model(self, sf, slot=0, u=10, v=7.5, minimal_loss=1e10):
         """The model-side half of the NEXT frame's ``loss_term.prepare`` (reference ``super/loss.py:212-220,408-426``),
         ahead of time: call it when the current frame is done with the model -- after ``sf.update`` /
@@ -271,12 +336,14 @@ class LM_Solver():
             raise RuntimeError("cholesky: the input is not positive-definite")
         return x.reshape(b.shape).to(b.dtype)
 
-    def prepareCostTerm(self, sf, inputs, new_data, beta, grad=False):
+    def prepareCostTerm(self, sf, inputs, new_data, beta, grad=False, flow=None, corr_points=None):
         """(reference ``super/LM.py:54-78``) ``grad=True`` -> (dense JtJ (P,P), jtl (P,1));
         ``grad=False`` -> scalar sum of squared residuals.  For inspection / parity: the LM
-        loop itself never materialises the dense matrix."""
+        loop itself never materialises the dense matrix.  With ``corr_term`` the correspondence term
+        of ``flow`` / ``corr_points`` is included."""
         h = self._handle()
         bf = self._bind(h, 0, sf, inputs, new_data)
+        self._bind_corr(h, 0, bf, self._corr_arg(flow, corr_points, required=True))
         st = _stream_ptr(bf.device)
         b64 = _as(beta, torch.float64, bf.device)
         _lib.check(self.lib.slm_set_beta(h, 0, _dev_ptr(b64), st), "slm_set_beta")
@@ -288,21 +355,42 @@ class LM_Solver():
             return jtj, jtl
         out = torch.empty(4, dtype=torch.float64, device=bf.device)
         _lib.check(self.lib.slm_loss(h, 0, _dev_ptr(out), st), "slm_loss")
-        return out[:3].sum()
+        total = out[:3].sum()
+        if self.corr_mode:
+            co = torch.empty(2, dtype=torch.float64, device=bf.device)
+            _lib.check(self.lib.slm_corr_loss(h, 0, _dev_ptr(co), st), "slm_corr_loss")
+            total = total + co[0]
+        return total
 
-    def LM(self, sf, inputs, new_data, u=10, v=7.5, minimal_loss=1e10):
+    def _corr_arg(self, flow, corr_points, required):
+        if flow is not None and corr_points is not None:
+            raise ValueError("give flow or corr_points, not both")
+        corr = flow if flow is not None else corr_points
+        if self.corr_mode and corr is None and required:
+            raise ValueError("LM_Solver(corr_term=True): LM() needs flow= (1,2,H,W) or corr_points=(pts, nrm, valid)")
+        return corr
+
+    def LM(self, sf, inputs, new_data, u=10, v=7.5, minimal_loss=1e10, flow=None, corr_points=None):
         """(reference ``super/LM.py:81-122``) run ``opt.num_optimize_iterations`` damped
-        iterations on the device; returns beta (J,7) float64 on ``sf``'s device."""
-        return self.LM_batch([(sf, inputs, new_data)], u=u, v=v, minimal_loss=minimal_loss)[0]
+        iterations on the device; returns beta (J,7) float64 on ``sf``'s device.  ``flow`` (1,2,H,W), as
+        ``GraphFit.infer_flow`` returns it, or ``corr_points = (pts, nrm, valid)``: the frame's correspondences
+        (``corr_term=True`` only, where one of them is required)."""
+        corr = self._corr_arg(flow, corr_points, required=True)
+        return self.LM_batch([(sf, inputs, new_data, corr)], u=u, v=v, minimal_loss=minimal_loss)[0]
 
     def LM_batch(self, frames, u=10, v=7.5, minimal_loss=1e10):
         """Many independent frames / hypotheses advanced together in the same launches
-        (one slot each).  ``frames`` is a list of ``(sf, inputs, new_data)``."""
+        (one slot each).  ``frames`` is a list of ``(sf, inputs, new_data)``; with ``corr_term`` a fourth
+        element per frame gives its correspondences: a flow, a ``(pts, nrm, valid)`` triple, or ``None``."""
         n = len(frames)
         if n < 1 or n > self.max_frames:
             raise ValueError(f"need 1..{self.max_frames} frames, got {n}")
         h = self._handle(u, v, minimal_loss)
+        corrs = [fr[3] if len(fr) > 3 else None for fr in frames]
+        frames = [tuple(fr[:3]) for fr in frames]
         bfs = self._bind_batch(h, frames) if n > 1 else [self._bind(h, 0, *frames[0])]
+        for i, (bf, corr) in enumerate(zip(bfs, corrs)):
+            self._bind_corr(h, i, bf, corr)
         dev = bfs[0].device
         st = _stream_ptr(dev)
         if self.sharded:
@@ -317,6 +405,8 @@ class LM_Solver():
             recs = self.records(h, i, st)
             self.last_records.append(recs)
             self._report(fr[0], fr[1], recs)
+        if self.corr_mode:
+            self.last_corr_kept = [None if c is None else self.corr_loss(i, u, v, minimal_loss)[1] for i, c in enumerate(corrs)]
         return betas
 
     # ---- one frame sharded over several GPUs ------------------------------------------------
