@@ -296,6 +296,8 @@ struct slm_solver {
   bool hybrid_batches = true;   // solver_path 0, larger batches: per-level launches + task graph for the top levels
   long dag_max_nodes = 8000;    // solver_path 0: launches of at most this many frames x nodes run as ONE task graph (SLM_DAG_MAX_NODES)
   bool fuse_begin = true;       // SLM_FUSE_BEGIN=0 (A/B, tests): k_iter_begin_nd as a launch of its own in front of the Jacobian pass, as in rounds 1-5
+  int gram_wgs = 0;             // SLM_GRAM_WGS (A/B, tests): workgroups per slot of the resident Jacobian pass; 0: one residency over the batch
+  int n_cus = 256;              // compute units of the device (sizes that residency)
   bool pure_fill = true;        // SLM_PURE_FILL=0 (tests): every pivot-column tile is zeroed and read-modify-written, as in rounds 1-4
   bool profile = false;
   std::vector<hipEvent_t> ev_pool;            // recycled events
@@ -511,6 +513,12 @@ int slm_create(const slm_config* cfg, slm_solver** out) {
   if (const char* nr = getenv("SLM_NO_REUSE")) s->no_reuse = atoi(nr) != 0;       // tests: recompute after a reject
   if (const char* pf = getenv("SLM_PURE_FILL")) s->pure_fill = atoi(pf) != 0;     // tests: differential check of the pure-fill tiles
   if (const char* fb = getenv("SLM_FUSE_BEGIN")) s->fuse_begin = atoi(fb) != 0;   // A/B: the zeroing as a launch of its own
+  if (const char* gw = getenv("SLM_GRAM_WGS")) s->gram_wgs = std::min(std::max(atoi(gw), 0), 65535);   // A/B, tests
+  {
+    int dev = 0, cus = 0;
+    (void)hipGetDevice(&dev);
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0) s->n_cus = cus;
+  }
   *out = s;
   return SLM_OK;
 }
@@ -1449,8 +1457,8 @@ void enqueue_jacobian(slm_solver* s, const FrameDev* fr, int n, const BatchDims&
   switch (d.form) {
     case DataForm::tuple:
       if (eval_mode >= 0) launch_data_eval(fr, n, kLossBlocks, w, eval_mode, st, reuse);
-      if (fused) launch_begin_and_gram(fr, n, d.max_pos, w, st, reuse, dag_cut);
-      else launch_data_gram(fr, n, d.max_pos, w, d.gram_variants, st, reuse);
+      if (fused) launch_begin_and_gram(fr, n, w, st, reuse, dag_cut, s->gram_wgs, s->n_cus);
+      else launch_data_gram(fr, n, d.max_pos, w, d.gram_variants, st, reuse, s->gram_wgs, s->n_cus);
       break;
     case DataForm::pairs:   // per-pair records (zeroed, then filled; the correspondence term adds into them)
       launch_data_grad_pairs(fr, n, d.maxN, d.K, w, st);

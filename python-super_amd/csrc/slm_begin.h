@@ -1,7 +1,7 @@
 // slm_begin.h -- start of an LM iteration on the multifrontal path: zero the assembled pivot-column tiles of the fronts, the
 // front vectors, rhs and the counters; reset the task graph's flags and mailboxes.  A device function (round 6) so that it
-// can run as k_iter_begin_nd (slm_front.hip) or as the tail blocks of the Jacobian pass's launch (k_data_gram, slm_data_k4.hip:
-// the two touch disjoint memory -- records vs fronts -- and the zeroing's store stream hides under the Gram pass's arithmetic).
+// can run as k_iter_begin_nd (slm_front.hip) or inside the Jacobian pass's launch (k_data_gram, slm_data_k4.hip: the two
+// touch disjoint memory -- records vs fronts -- and the zeroing's store stream hides under the Gram pass's arithmetic).
 #pragma once
 #include "slm_tile.h"
 
@@ -41,7 +41,9 @@ __device__ __forceinline__ void zero_fronts(const FrameDev& fd, int b, int nb) {
 // 0's flags carry the ticket of the whole batch.
 // reused: this slot's Jacobian pass is skipped (records reused after a rejected step).  gram_sets_count: the Jacobian pass
 // of THIS launch publishes m_grad itself for the slots it runs for (k_data_gram block 0) -- the zeroing must not race it.
-__device__ __forceinline__ void iter_begin_nd_body(const FrameDev& fd, int b, int nb, bool reused, int dag_cut, bool gram_sets_count) {
+// iter_begin_nd_small is everything but the fronts' tiles (zero_fronts): flags, mailboxes, vectors, rhs and counters.  The
+// resident Jacobian pass (k_data_gram) runs it once per workgroup and spreads the tile pieces over its chunks.
+__device__ __forceinline__ void iter_begin_nd_small(const FrameDev& fd, int b, int nb, bool reused, int dag_cut, bool gram_sets_count) {
   if (!fd.bound) return;
   if (dag_cut >= -1 && fd.nd_ready && fd.dag_flags) {
     for (int i = b * blockDim.x + threadIdx.x; i < fd.dag_n_flags; i += nb * blockDim.x) fd.dag_flags[i] = 0;
@@ -58,7 +60,6 @@ __device__ __forceinline__ void iter_begin_nd_body(const FrameDev& fd, int b, in
   const size_t tid = (size_t)b * blockDim.x + threadIdx.x, nthr = (size_t)nb * blockDim.x;
   const double2 z = make_double2(0.0, 0.0);
   if (fd.nd_ready) {
-    zero_fronts(fd, b, nb);
     double2* v2 = reinterpret_cast<double2*>(fd.fvec.get());
     const size_t nv2 = (size_t)fd.zero_vec_doubles / 2;
     for (size_t e = tid; e < nv2; e += nthr) v2[e] = z;
@@ -75,4 +76,8 @@ __device__ __forceinline__ void iter_begin_nd_body(const FrameDev& fd, int b, in
     }
     fd.st->chol_fail = 0;
   }
+}
+__device__ __forceinline__ void iter_begin_nd_body(const FrameDev& fd, int b, int nb, bool reused, int dag_cut, bool gram_sets_count) {
+  iter_begin_nd_small(fd, b, nb, reused, dag_cut, gram_sets_count);
+  if (fd.bound && fd.nd_ready && !fd.st->stopped) zero_fronts(fd, b, nb);
 }

@@ -85,112 +85,188 @@ __global__ void __launch_bounds__(256) k_data_eval(const FrameDev* __restrict__ 
   }
 }
 
-// grid = (ceil(max n_pos / 256), n_frames), 256 threads = 4 waves, one 64-position chunk each
+// The position-indexed streams of one 256-position chunk as one lane holds them: what k_data_gram requests for chunk i + 1
+// before the row / MFMA phase of chunk i.  Weights and point keep the dtype of the state (no conversion, so no wait, at
+// the load).
+struct GramChunk {
+  int my_run;              // lane (l & 15): run of group (l & 15) of the wave's 64 positions, -1 padding / no positions
+  int rec0, nrec;          // MERGE: the chunk's records [rec0, rec0 + nrec)
+  int4 ids;
+  double2 e0, e1;          // {r, c.x}, {c.y, c.z} of the position
+  double2 wa, wb;          // weights, f64 state
+  double px, py, pz;
+  float4 wf;               // weights, f32 state
+  float qx, qy, qz;
+};
+template <bool MERGE>
+__device__ __forceinline__ void gram_chunk_load(const FrameDev& fd, int c, int w, int l, int f64, GramChunk& k) {
+  k.my_run = -1;
+  k.rec0 = k.nrec = 0;
+  k.ids = int4{-1, -1, -1, -1};
+  k.e0 = k.e1 = k.wa = k.wb = make_double2(0.0, 0.0);
+  k.px = k.py = k.pz = 0.0;
+  k.wf = make_float4(0.f, 0.f, 0.f, 0.f);
+  k.qx = k.qy = k.qz = 0.f;
+  if (MERGE) {
+    k.rec0 = fd.wg_first[c];
+    k.nrec = fd.wg_last[c] - k.rec0 + 1;
+  }
+  const int base = (c * 4 + w) * 64;
+  if (base >= fd.n_pos) return;
+  const size_t pos = (size_t)(base + l);
+  k.my_run = fd.grp_run[(base >> 2) + (l & 15)];
+  const double2* e2 = reinterpret_cast<const double2*>(fd.ev_rc.get() + 4 * pos);
+  k.e0 = e2[0];
+  k.e1 = e2[1];
+  k.ids = *reinterpret_cast<const int4*>(fd.s_idx + 4 * pos);
+  if (f64) {
+    const double2* q = reinterpret_cast<const double2*>(static_cast<const double*>(fd.s_w.get()) + 4 * pos);
+    k.wa = q[0];
+    k.wb = q[1];
+    const double* pq = static_cast<const double*>(fd.s_pts.get()) + 3 * pos;
+    k.px = pq[0]; k.py = pq[1]; k.pz = pq[2];
+  } else {
+    k.wf = *reinterpret_cast<const float4*>(static_cast<const float*>(fd.s_w.get()) + 4 * pos);
+    const float* pq = static_cast<const float*>(fd.s_pts.get()) + 3 * pos;
+    k.qx = pq[0]; k.qy = pq[1]; k.qz = pq[2];
+  }
+}
+// record numbers of the wave's runs: entry idx = group * 10 + pair slot, 160 per wave, three per lane
+__device__ __forceinline__ void gram_lidx_load(const FrameDev& fd, int my_run, int l, uint8_t lv[3]) {
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const int idx = l + 64 * k;
+    const int g = idx / 10, e = idx - 10 * g;
+    const int run = __shfl(my_run, g < 16 ? g : 0, 64);
+    lv[k] = (idx < 160 && run >= 0) ? fd.run_lidx[10 * (size_t)run + e] : (uint8_t)0;
+  }
+}
+// 16 KB piece pc of the slot's kind-0 pivot-column tiles (two per tile, as zero_fronts counts them), tile offset `off`
+__device__ __forceinline__ void zero_front_piece(const FrameDev& fd, long long off, int pc) {
+  const dvec2_t zz = {0.0, 0.0};
+  dvec2_t* q = reinterpret_cast<dvec2_t*>(fd.ftiles.get() + off) + (size_t)(pc & 1) * 1024 + threadIdx.x;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) __builtin_nontemporal_store(zz, q + 256 * k);
+}
+
+// grid = (workgroups per slot, n_frames), 256 threads = 4 waves.  RESIDENT: the launch is about one residency
+// (2 workgroups per CU over the slots of the batch); workgroup b of the nwg of a slot walks a contiguous range of the slot's
+// 256-position chunks [wg_lo, wg_hi), one 64-position sub-chunk per wave.  Chunk boundaries, records and slabs are what the
+// plan defines -- the same per chunk as when every chunk had a workgroup of its own.  Software pipeline: chunk i + 1's
+// position-indexed streams (GramChunk) are requested after chunk i's node gathers and land under its row / MFMA / merge
+// phase; its record numbers (run_lidx, which need my_run) are requested after the Gram loop and land under the copy-out.
 // dbg (diagnostic build only): bit0 skip slab stores, bit1 skip MFMA, bit2 skip surfel evaluation
 // The 32-entry rows pass through LDS in two halves of 16 entries (8.7 KB per wave instead of
-// 17 KB: three to four workgroups per CU instead of two); the first half's MFMA operands wait
-// in 16 registers per lane.
+// 17 KB); the first half's MFMA operands wait in 16 registers per lane.
 //
 // MERGE (default): the workgroup's 4 waves add the 7x7 node-pair blocks of their runs (and the
 // 7-entry J^T r pieces of the diagonal pairs) into LDS records keyed by node pair (ds_add_f64),
 // and the workgroup writes one 56-double record per distinct pair -- about 4x fewer HBM bytes
-// than one 768-double Gram per run, and the assemble kernels read contiguous records.
-// BEGIN (round 6): the launch also carries the iteration's zeroing (iter_begin_nd_body, slm_begin.h) -- blocks
-// [n_gram, n_gram + n_begin) of a slot: the Jacobian pass writes records, the zeroing writes fronts / vectors / flags,
-// nothing in common; one launch boundary fewer per iteration and the zeroing's store stream (HBM-bound) runs under the
-// Gram pass (VALU / LDS-bound).
+// than one 768-double Gram per run, and the assemble kernels read contiguous records.  The LDS records are zero when a
+// chunk starts: zeroed once per workgroup, and the thread that copies an entry out re-zeroes it.
+// BEGIN (round 6): the launch also carries the iteration's zeroing (slm_begin.h) -- the Jacobian pass writes records, the
+// zeroing writes fronts / vectors / flags, nothing in common.  Every workgroup does its 1 / nwg of the small parts at once
+// and spreads its share of the fronts' 16 KB pieces over its chunks, stored right after the next chunk's loads are
+// requested: the store stream (HBM-bound) drains under the Gram phase (LDS / MFMA-bound).  A workgroup without chunks
+// (more workgroups than chunks, a reused or unbound slot) only zeroes.
 template <bool MERGE, bool BEGIN = false>
 __global__ void __launch_bounds__(256, 2) k_data_gram(const FrameDev* __restrict__ frames, double lam,
-                                                       int dbg, const int* __restrict__ reuse, int n_gram = 0, int n_begin = 0,
-                                                       int dag_cut = -2) {
-  if (BEGIN && (int)blockIdx.x >= n_gram) {
-    iter_begin_nd_body(frames[blockIdx.y], (int)blockIdx.x - n_gram, n_begin, reuse && reuse[blockIdx.y], dag_cut,
-                       frames[blockIdx.y].v1_ready && frames[blockIdx.y].v2_ready);
-    return;
-  }
+                                                       int dbg, const int* __restrict__ reuse, int dag_cut = -2) {
   __shared__ double rows[4][64 * ROW_STRIDE];
   __shared__ double recs[MERGE ? SLM_LB_MAX * SLM_WREC : 1];
   __shared__ uint8_t lidx[4][MERGE ? 160 : 4];   // per wave: record of each of the 10 node pairs of its 16 groups
   // After a REJECTED step beta is rolled back, so this pass would reproduce the records of the previous iteration
   // entry for entry (reference super/LM.py:114-117 then :96 rebuilds an identical JtJ): the slot keeps them and
-  // k_front_assemble re-reads them.  (The flag sits in an array of its own, indexed by the slot: a load that does not
-  // depend on the descriptor, so it costs the accepted iterations nothing.)
-  if (reuse && reuse[blockIdx.y]) return;
+  // k_front_assemble re-reads them.
+  const bool reused = reuse && reuse[blockIdx.y];
+  if (!BEGIN && reused) return;
   const FrameDev& fd = frames[blockIdx.y];
-  // (no test of st->stopped here: a stopped slot only wastes this pass, and the test would put one more
-  //  dependent load in front of everything)
-  if (!fd.bound || !fd.v1_ready) return;
-  if (MERGE != (fd.v2_ready != 0)) return;   // the host launches both variants when slots differ
+  const int b = blockIdx.x, nwg = gridDim.x;
   const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
-  const int base = (blockIdx.x * 4 + w) * 64;
-  if (blockIdx.x * 256 >= fd.n_pos) return;
-  // the matched count of this pass is the one of the evaluation it consumes (this rank's share of it when sharded)
-  if (blockIdx.x == 0 && threadIdx.x == 0) fd.st->m_grad = fd.st->m_eval;
-  if ((int)blockIdx.x < fd.wg_lo || (int)blockIdx.x >= fd.wg_hi) return;   // another rank's share
-  const bool wact = base < fd.n_pos;
-  const int pos = base + l;
   const int lc = l & 15, lq = l >> 4;
-  // ---- stage 0: everything that only depends on the position is requested at once ----
-  int rec0 = 0, nrec = 0;
-  if (MERGE) {
-    rec0 = fd.wg_first[blockIdx.x];
-    nrec = fd.wg_last[blockIdx.x] - rec0 + 1;
-  }
-  int my_run = -1;
-  int4 ids = {-1, -1, -1, -1};
-  double wk[4] = {0, 0, 0, 0};
-  d3 pp = {0, 0, 0};
-  double2 e0 = make_double2(0.0, 0.0), e1 = make_double2(0.0, 0.0);   // {r, c.x}, {c.y, c.z} of the position
-  if (wact) {
-    my_run = fd.grp_run[(base >> 2) + lc];   // lane (l & 15) holds the run of group (l & 15)
-    const double2* e2 = reinterpret_cast<const double2*>(fd.ev_rc.get() + 4 * (size_t)pos);
-    e0 = e2[0];
-    e1 = e2[1];
-    ids = *reinterpret_cast<const int4*>(fd.s_idx + 4 * (size_t)pos);
-    ld_state4(fd.s_w, (size_t)pos, fd.f.state_f64, wk);
-    pp = ld_state3(fd.s_pts, (size_t)pos, fd.f.state_f64);
-  }
-  // ---- stage 1: record numbers of the wave's runs (needs my_run), in flight with the node gathers ----
-  uint8_t lv0 = 0, lv1 = 0, lv2 = 0;
-  if (MERGE && wact) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      const int idx = l + 64 * k;                      // entry idx = group * 10 + pair slot, 160 per wave
-      const int g = idx / 10, e = idx - 10 * g;
-      const int run = __shfl(my_run, g < 16 ? g : 0, 64);
-      const uint8_t v = (idx < 160 && run >= 0) ? fd.run_lidx[10 * (size_t)run + e] : (uint8_t)0;
-      if (k == 0) lv0 = v; else if (k == 1) lv1 = v; else lv2 = v;
+  const int f64 = fd.f.state_f64;
+  // (no test of st->stopped for the Gram pass: a stopped slot only wastes it)
+  // the slot's chunks of this workgroup: [c0, c1) of the shard window (another rank's share is not touched)
+  int c0 = 0, c1 = 0;
+  if (!reused && fd.bound && fd.v1_ready && MERGE == (fd.v2_ready != 0) && fd.n_pos > 0) {   // the host launches both variants when slots differ
+    // the matched count of this pass is the one of the evaluation it consumes (this rank's share of it when sharded)
+    if (b == 0 && threadIdx.x == 0) fd.st->m_grad = fd.st->m_eval;
+    const int lo = max(fd.wg_lo, 0), hi = min(fd.wg_hi, (fd.n_pos + 255) >> 8);
+    if (hi > lo) {
+      c0 = lo + (int)((long long)(hi - lo) * b / nwg);
+      c1 = lo + (int)((long long)(hi - lo) * (b + 1) / nwg);
     }
   }
-  if (MERGE)
-    for (int i = threadIdx.x; i < nrec * SLM_WREC; i += 256) recs[i] = 0.0;
+  GramChunk cur{}, nxt{};
+  if (c0 < c1) gram_chunk_load<MERGE>(fd, c0, w, l, f64, cur);
+  // the zeroing: pieces pc = b + k nwg, k in [0, znv), of the slot's 2 n_zero_tiles; at most zper (and 64) per chunk
+  int zk = 0, znv = 0, zper = 0;
+  if (BEGIN) {
+    iter_begin_nd_small(fd, b, nwg, reused, dag_cut, fd.v1_ready && fd.v2_ready);
+    if (fd.bound && fd.nd_ready && !fd.st->stopped) {
+      const int np = 2 * fd.n_zero_tiles;
+      znv = b < np ? (np - b + nwg - 1) / nwg : 0;
+      zper = c1 > c0 ? min(64, (znv + (c1 - c0) - 1) / (c1 - c0)) : 0;
+    }
+  }
+  if (MERGE && c0 < c1)
+    for (int i = threadIdx.x; i < SLM_LB_MAX * SLM_WREC; i += 256) recs[i] = 0.0;
   double* myrow = &rows[w][l * ROW_STRIDE];
+  uint8_t lv[3] = {0, 0, 0};
+  if (MERGE && c0 < c1) gram_lidx_load(fd, cur.my_run, l, lv);
 
-  // ---- the surfel's row from the evaluation buffer: no projection, no target access --------------
-  SurfelEval ev;
-  ev.match = false;
-  ev.r = 0.0;
-  ev.id[0] = ev.id[1] = ev.id[2] = ev.id[3] = -1;
-  const bool live = wact && ids.x >= 0;
+  for (int c = c0; c < c1; ++c) {
+    const bool wact = (c * 4 + w) * 64 < fd.n_pos;
+    // tile offsets of the pieces zeroed under this chunk, lane k the k-th: requested with the node gathers
+    int znow = 0;
+    long long zoff = 0;
+    if (BEGIN) {
+      znow = min(zper, znv - zk);
+      if (l < znow) zoff = fd.zero_tiles[(b + (zk + l) * nwg) >> 1];
+    }
+    // ---- the surfel's row from the evaluation buffer: no projection, no target access --------------
+    SurfelEval ev;
+    ev.match = false;
+    ev.r = 0.0;
+    ev.id[0] = ev.id[1] = ev.id[2] = ev.id[3] = -1;
+    const bool live = wact && cur.ids.x >= 0;
 #ifdef SLM_STAMPS
-  if (live && !(dbg & 4))
+    if (live && !(dbg & 4))
 #else
-  if (live)
+    if (live)
 #endif
-  {
-    ev.id[0] = ids.x; ev.id[1] = ids.y; ev.id[2] = ids.z; ev.id[3] = ids.w;
-    // (an unmatched surfel has {r, c} = 0: its row is zero and it adds nothing to the Gram)
-    ev.match = e0.x != 0.0 || e0.y != 0.0 || e1.x != 0.0 || e1.y != 0.0;
-    ev.r = e0.x;
-    if (ev.match) rows_from_c(pp, ev.id, wk, lam, fd.node_pk, {e0.y, e1.x, e1.y}, ev.row);
-  }
-  if (MERGE && wact) {
-    lidx[w][l] = lv0;
-    lidx[w][l + 64] = lv1;
-    if (l + 128 < 160) lidx[w][l + 128] = lv2;
-  }
-  if (MERGE) __syncthreads();   // accumulators zeroed, record numbers in place
-  if (wact) {
+    {
+      ev.id[0] = cur.ids.x; ev.id[1] = cur.ids.y; ev.id[2] = cur.ids.z; ev.id[3] = cur.ids.w;
+      // (an unmatched surfel has {r, c} = 0: its row is zero and it adds nothing to the Gram)
+      ev.match = cur.e0.x != 0.0 || cur.e0.y != 0.0 || cur.e1.x != 0.0 || cur.e1.y != 0.0;
+      ev.r = cur.e0.x;
+      if (ev.match) {
+        double wk[4];
+        d3 pp;
+        if (f64) {
+          wk[0] = cur.wa.x; wk[1] = cur.wa.y; wk[2] = cur.wb.x; wk[3] = cur.wb.y;
+          pp = {cur.px, cur.py, cur.pz};
+        } else {
+          wk[0] = (double)cur.wf.x; wk[1] = (double)cur.wf.y; wk[2] = (double)cur.wf.z; wk[3] = (double)cur.wf.w;
+          pp = {(double)cur.qx, (double)cur.qy, (double)cur.qz};
+        }
+        rows_from_c(pp, ev.id, wk, lam, fd.node_pk, {cur.e0.y, cur.e1.x, cur.e1.y}, ev.row);
+      }
+    }
+    const int my_run = cur.my_run, rec0 = cur.rec0, nrec = cur.nrec;
+    // ---- the next chunk's streams, then this chunk's share of the zeroing: both in flight under the Gram phase ----
+    if (c + 1 < c1) gram_chunk_load<MERGE>(fd, c + 1, w, l, f64, nxt);
+    if (BEGIN) {
+      for (int k = 0; k < znow; ++k) zero_front_piece(fd, __shfl(zoff, k, 64), b + (zk + k) * nwg);
+      zk += znow;
+    }
+    if (MERGE && wact) {
+      lidx[w][l] = lv[0];
+      lidx[w][l + 64] = lv[1];
+      if (l + 128 < 160) lidx[w][l + 128] = lv[2];
+    }
+    if (MERGE) __syncthreads();   // the records are zero again (copy-out of the chunk before), record numbers in place
+    if (wact) {
 
   // canonical slot of neighbour k = number of neighbour ids smaller than id[k]
   int slot[4];
@@ -209,9 +285,9 @@ __global__ void __launch_bounds__(256, 2) k_data_gram(const FrameDev* __restrict
 #pragma unroll
       for (int k = 0; k < 4; ++k)
 #pragma unroll
-        for (int c = 0; c < 7; ++c) {
-          const int e = 7 * slot[k] + c - 16 * half;
-          if (e >= 0 && e < 16) myrow[e] = ev.row[7 * k + c];
+        for (int cc = 0; cc < 7; ++cc) {
+          const int e = 7 * slot[k] + cc - 16 * half;
+          if (e >= 0 && e < 16) myrow[e] = ev.row[7 * k + cc];
         }
       if (half == 1) myrow[28 - 16] = ev.r;
     }
@@ -230,7 +306,7 @@ __global__ void __launch_bounds__(256, 2) k_data_gram(const FrameDev* __restrict
 
   // ---- Gram accumulation per run ---------------------------------------------------
   double4_t g00 = {0, 0, 0, 0}, g10 = {0, 0, 0, 0}, g11 = {0, 0, 0, 0};
-  int cur = -1;
+  int crun = -1;
 
   auto flush = [&](int run, int grp) {
 #ifdef SLM_STAMPS
@@ -270,12 +346,12 @@ __global__ void __launch_bounds__(256, 2) k_data_gram(const FrameDev* __restrict
 #pragma unroll
   for (int g = 0; g < 16; ++g) {
     const int run = __builtin_amdgcn_readlane(my_run, g);
-    if (run != cur) {
-      if (cur >= 0) flush(cur, g - 1);
+    if (run != crun) {
+      if (crun >= 0) flush(crun, g - 1);
       g00 = double4_t{0, 0, 0, 0};
       g10 = double4_t{0, 0, 0, 0};
       g11 = double4_t{0, 0, 0, 0};
-      cur = run;
+      crun = run;
     }
     if (run < 0) continue;
     const double a1 = rows[w][(4 * g + lq) * ROW_STRIDE + lc];
@@ -286,13 +362,28 @@ __global__ void __launch_bounds__(256, 2) k_data_gram(const FrameDev* __restrict
     g10 = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, a0[g], g10, 0, 0, 0);
     g11 = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, a1, g11, 0, 0, 0);
   }
-  if (cur >= 0) flush(cur, 15);
-  }   // wave has positions
-  if (MERGE) {
-    __syncthreads();
-    double* out = fd.wgslab + (size_t)rec0 * SLM_WREC;
-    for (int i = threadIdx.x; i < nrec * SLM_WREC; i += 256) out[i] = recs[i];
+  if (crun >= 0) flush(crun, 15);
+    }   // wave has positions
+    if (MERGE) {
+      // the next chunk's record numbers (its my_run has had the Gram phase to arrive): in flight under the copy-out
+      if (c + 1 < c1) gram_lidx_load(fd, nxt.my_run, l, lv);
+      __syncthreads();
+      // copy-out: the thread that stores an entry re-zeroes it, so the next chunk needs no zero pass and no second barrier
+      double* out = fd.wgslab + (size_t)rec0 * SLM_WREC;
+      for (int i = threadIdx.x; i < nrec * SLM_WREC; i += 256) {
+        out[i] = recs[i];
+        recs[i] = 0.0;
+      }
+    }
+    cur = nxt;
   }
+  if (BEGIN)   // what the chunks did not cover (no chunk at all, or more than 64 pieces per chunk)
+    while (zk < znv) {
+      const int znow = min(64, znv - zk);
+      const long long zoff = l < znow ? fd.zero_tiles[(b + (zk + l) * nwg) >> 1] : 0;
+      for (int k = 0; k < znow; ++k) zero_front_piece(fd, __shfl(zoff, k, 64), b + (zk + k) * nwg);
+      zk += znow;
+    }
 }
 
 // G[i][j], i >= j, from a slab entry (tiles 00, 10, 11; 16x16 row-major each)
@@ -333,30 +424,34 @@ __global__ void __launch_bounds__(256) k_band_assemble(const FrameDev* __restric
   else if (jt) fd.rhs[7 * a + (l - 49)] = -acc;               // jtl = -J^T r, one writer per entry
 }
 
+// Workgroups per slot of the resident Jacobian pass: `wgs` when the solver's knob sets it (SLM_GRAM_WGS), else one
+// residency -- 2 workgroups per CU -- shared by the slots of the batch.
+static int gram_wgs(int wgs, int n_frames, int n_cus) { return wgs > 0 ? wgs : max(1, 2 * n_cus / max(1, n_frames)); }
+
 // variants: bit0 = some slot uses the workgroup-merged records, bit1 = some slot uses the per-run slab
 // The Jacobian pass AND the iteration's zeroing in one launch (every slot of the batch on the workgroup-merged records):
 // what slm_run's loop enqueues instead of k_iter_begin_nd + k_data_gram.
-void launch_begin_and_gram(const FrameDev* frames_dev, int n_frames, int max_pos, double lam, hipStream_t st, const int* reuse,
-                           int dag_cut) {
+void launch_begin_and_gram(const FrameDev* frames_dev, int n_frames, double lam, hipStream_t st, const int* reuse,
+                           int dag_cut, int wgs, int n_cus) {
   int dbg = 0;
 #ifdef SLM_STAMPS
   if (const char* e = getenv("SLM_DBG")) dbg = atoi(e);
 #endif
-  const int n_gram = (max_pos + 255) / 256, n_begin = 1024;
-  hipLaunchKernelGGL((k_data_gram<true, true>), dim3(n_gram + n_begin, n_frames), dim3(256), 0, st, frames_dev, lam, dbg, reuse, n_gram,
-                     n_begin, dag_cut);
+  hipLaunchKernelGGL((k_data_gram<true, true>), dim3(gram_wgs(wgs, n_frames, n_cus), n_frames), dim3(256), 0, st, frames_dev, lam, dbg,
+                     reuse, dag_cut);
 }
 
 void launch_data_gram(const FrameDev* frames_dev, int n_frames, int max_pos, double lam, int variants,
-                      hipStream_t st, const int* reuse) {
+                      hipStream_t st, const int* reuse, int wgs, int n_cus) {
   if (max_pos <= 0) return;
   int dbg = 0;
 #ifdef SLM_STAMPS
   if (const char* e = getenv("SLM_DBG")) dbg = atoi(e);
 #endif
-  const dim3 grid((max_pos + 255) / 256, n_frames);
-  if (variants & 1) hipLaunchKernelGGL(k_data_gram<true>, grid, dim3(256), 0, st, frames_dev, lam, dbg, reuse);
-  if (variants & 2) hipLaunchKernelGGL(k_data_gram<false>, grid, dim3(256), 0, st, frames_dev, lam, dbg, reuse);
+  // (no zeroing to share: a workgroup beyond the chunks of the largest slot would have nothing to do)
+  const dim3 grid(wgs > 0 ? wgs : min(gram_wgs(0, n_frames, n_cus), (max_pos + 255) / 256), n_frames);
+  if (variants & 1) hipLaunchKernelGGL(k_data_gram<true>, grid, dim3(256), 0, st, frames_dev, lam, dbg, reuse, -2);
+  if (variants & 2) hipLaunchKernelGGL(k_data_gram<false>, grid, dim3(256), 0, st, frames_dev, lam, dbg, reuse, -2);
 }
 
 void launch_data_eval(const FrameDev* frames_dev, int n_frames, int n_blocks, double lam, int mode, hipStream_t st,

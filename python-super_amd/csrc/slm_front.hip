@@ -472,7 +472,7 @@ __global__ void __launch_bounds__(256) k_front_load_rhs(const FrameDev* __restri
 // ---- zeroing of the fronts (slm_begin.h) --------------------------------------------------------------------------
 // Start of an iteration on the multifrontal path as a launch of its own: for ALL slots of the batch (one hipMemsetAsync
 // pair per slot cost ~25 us each, back to back).  grid = (blocks, n_frames); contiguous 16 KB pieces per workgroup.
-// (The LM loop's tuple-sorted path runs the same body as the tail blocks of its Jacobian pass instead: launch_data_gram.)
+// (The LM loop's tuple-sorted path spreads the same work over the workgroups of its Jacobian pass instead: launch_begin_and_gram.)
 __global__ void __launch_bounds__(256) k_iter_begin_nd(const FrameDev* __restrict__ frames, const int* __restrict__ reuse, int dag_cut) {
   iter_begin_nd_body(frames[blockIdx.y], blockIdx.x, gridDim.x, reuse && reuse[blockIdx.y], dag_cut, false);
 }

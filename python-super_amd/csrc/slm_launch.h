@@ -12,8 +12,8 @@ void launch_data_loss(const FrameDev*, int, int, int, double, int, hipStream_t);
 void launch_data_resid(const FrameDev*, int, int, int, double, double*, uint8_t*, int32_t*, hipStream_t);
 
 // slm_data_k4.hip
-void launch_data_gram(const FrameDev*, int, int, double, int, hipStream_t, const int* reuse = nullptr);
-void launch_begin_and_gram(const FrameDev*, int, int, double, hipStream_t, const int* reuse, int dag_cut);
+void launch_data_gram(const FrameDev*, int, int, double, int, hipStream_t, const int* reuse, int wgs, int n_cus);
+void launch_begin_and_gram(const FrameDev*, int, double, hipStream_t, const int* reuse, int dag_cut, int wgs, int n_cus);
 void launch_data_eval(const FrameDev*, int, int, double, int mode, hipStream_t, const int* reuse = nullptr);
 void launch_band_assemble(const FrameDev*, int, int, hipStream_t);
 
