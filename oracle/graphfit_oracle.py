@@ -200,7 +200,9 @@ def bn_morph(pb: Problem, sf):
     """Semantic-boundary morphing term (deform_mesh.py:126-194): surfels whose class differs
     from the class of the pixel they project to are pulled towards the 2 nearest boundary pixels
     of their own class; mean over the surfels whose mean squared distance exceeds 15.
-    Returns None when no class contributes a list entry, else the (possibly NaN) mean."""
+    Returns None when no class contributes a list entry, else the (possibly NaN) mean.  ``pb.morph_stats`` records per
+    contributing class (class, boundary pixels, candidate surfels, surfels kept), ``pb.morph_candidates`` the candidates'
+    mask over the stable surfels."""
     Z = sf[:, 2] + 1e-8
     x = sf[:, 0] * pb.fx / Z + pb.cx
     y = sf[:, 1] * pb.fy / Z + pb.cy
@@ -213,6 +215,8 @@ def bn_morph(pb: Problem, sf):
     if pb.edge_pts is None:
         pb.edge_pts = edge_points(pb.img_seg.numpy(), pb.C)
     parts = []
+    pb.morph_stats = []
+    pb.morph_candidates = torch.zeros_like(val)
     for c in range(pb.C):
         cm = (pb.sf_seg == c) & val
         E = pb.edge_pts[c]
@@ -226,6 +230,8 @@ def bn_morph(pb: Problem, sf):
         ok = ~torch.any(kd > dte[:, None], dim=1)
         li = ((E[order][ok] - g[ok][:, None, :]) ** 2).sum(2).mean(1)
         parts.append(li[li > 15])
+        pb.morph_stats.append((c, len(E), int(cm.sum()), int((li > 15).sum())))
+        pb.morph_candidates |= cm
     if not parts:
         return None
     return torch.cat(parts).mean()

@@ -3,6 +3,7 @@ the PyTorch-CPU oracle, through the C ABI.  Needs an MI355X (-m gpu)."""
 import numpy as np
 import pytest
 
+from gf_shape_cases import frames_of
 from helpers import GF_SEMANTIC_VARIANTS, load_golden, ref_opt, torch_frame
 from oracle import graphfit_oracle as gfo
 
@@ -26,16 +27,7 @@ def _opt(tag, **kw):
 
 
 def _frame(sc):
-    import torch
-    sf, inputs, new_data = torch_frame(sc)
-    sf.ED_nodes.triangles = torch.from_numpy(sc.ed_triangles).cuda()
-    sf.ED_nodes.triangles_areas = torch.from_numpy(sc.ed_triangle_areas).cuda().double()
-    if sc.num_classes:
-        sf.seg = torch.from_numpy(sc.sf_seg).cuda()
-        sf.seg_conf = torch.from_numpy(sc.sf_seg_conf).cuda().double()
-        new_data.seg_conf = torch.from_numpy(sc.tgt_seg_conf).cuda().double()
-        inputs[("seg_conf", 0)] = torch.from_numpy(sc.img_seg_conf).cuda().double()[None]
-        inputs[("seg", 0)] = torch.from_numpy(sc.img_seg).cuda()[None, None]
+    inputs, sf, new_data = frames_of(sc)
     return sf, inputs, new_data
 
 

@@ -5,8 +5,8 @@ render_in_run=True) and GraphFit.forward_frames) on the 60 x 80 scene of test_gp
 Tolerances.  Against the CPU loop and between two GPU runs that evaluate the same term: that file's own, 1e-6 of the update's
 size after ten iterations (GraphFit's gradient adds with float64 atomics, so two runs are not bitwise equal).  A slot without
 the term against plain GraphFit(opt): atol 1e-9, the bound test_gpu_graphfit.py holds every GraphFit run to against its golden
-result (no test there compares a batched with a single run; in a mixed batch the slot runs k_gf_data<K, true> with a null point
-gradient instead of k_gf_data<K, false>: the same sums in another atomic order).  The guarded render itself is compared with
+result (batched against single runs: test_gpu_graphfit_shapes.py; in a mixed batch the slot runs k_gf_data<K, true> with a null
+point gradient instead of k_gf_data<K, false>: the same sums in another atomic order).  The guarded render itself is compared with
 slm_gf_render + slm_render_backward bitwise."""
 import numpy as np
 import pytest
