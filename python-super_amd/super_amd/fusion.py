@@ -158,7 +158,7 @@ def fuseInputData(sf, inputs, sfdata):
     cfg = _config(sf, inputs)
     dev = sf.points.device if sf.points.is_cuda else torch.device("cuda", torch.cuda.current_device())
     n, T = int(sf.points.shape[0]), int(sfdata.points.shape[0])
-    cap = n + T
+    cap = max(n + T, 1)       # an empty model and an empty frame still get buffers the library can address
     h, _ = _context(lib, cfg.H, cfg.W, cap, dev)
     model = _Model(sf, cap, dev)
     fr = SlmNewFrame()
@@ -198,7 +198,7 @@ def prepareStableIndexNSwapAllModel(sf, inputs, sfdata):
     dev = sf.points.device if sf.points.is_cuda else torch.device("cuda", torch.cuda.current_device())
     n = int(sf.points.shape[0])
     h, _ = _context(lib, cfg.H, cfg.W, n, dev)
-    model = _Model(sf, n, dev)
+    model = _Model(sf, max(n, 1), dev)       # n = 0 (everything was dropped, or nothing ever added): one spare row, as above
     tracking = bool(getattr(sf, "evaluate_tracking", False)) and hasattr(sf, "track_id")
     keep, new_index, n_keep = None, None, 0
     if tracking and cfg.remove_unstable:

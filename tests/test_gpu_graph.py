@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 
 from oracle import graph_oracle as gro
-from test_graph_oracle import GOLD, SEM_VARIANTS, VARIANTS
+from test_graph_oracle import DEGENERATE_GRIDS, GOLD, SEM_VARIANTS, VARIANTS, degenerate_grid
 
 pytestmark = pytest.mark.gpu
 
@@ -85,3 +85,27 @@ def test_graph_full_size_with_isolated_anchors_matches_oracle():
         ref = gro.direct_deform_graph(sc.valid, sc.index_map, sc.f64("tgt_points"), sc.f64("tgt_norms"), step)
         _check(out, ref)
         assert out["num"] > 100
+
+
+@pytest.mark.parametrize("sem", ["plain", "sem", "hard"])
+@pytest.mark.parametrize("name", list(DEGENERATE_GRIDS))
+def test_degenerate_grids_match_oracle(name, sem):
+    """No anchor at all, a single one, anchors that are never neighbours (every radius the mean of nothing: NaN on both sides),
+    an image whose last column and row are multiples of the step, a step larger than the image, step 1; plain, with node
+    classes, and with class-boundary pruning."""
+    import warnings
+    valid, index_map, points, norms, conf, H, W, step = degenerate_grid(name)
+    seg_conf = None if sem == "plain" else conf
+    out = _run(valid, index_map, points, norms, H, W, step, seg_conf=seg_conf, hard_seg=sem == "hard")
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", RuntimeWarning)          # the oracle takes the mean of nothing
+        ref = gro.direct_deform_graph(valid, index_map, points, norms, step, seg_conf=seg_conf, prune_class_edges=sem == "hard")
+    J = DEGENERATE_GRIDS[name][4]
+    assert out["num"] == J
+    for k, rows in (("edge_index", 2), ("triangles", 3)):
+        assert out[k].dtype == np.int64 and out[k].shape == (rows, ref[k].shape[1])
+    assert out["points"].shape == (J, 3) and out["radii"].shape == (J,)
+    np.testing.assert_array_equal(np.isnan(out["radii"]), np.isnan(ref["radii"]))
+    for k in ("points", "norms", "edges_lens", "triangles_areas"):
+        assert not np.isnan(out[k]).any()
+    _check(out, ref)
