@@ -198,7 +198,16 @@ def project3d_grid(depth, inv_K, K, stereo_T):
     H, W = depth.shape
     cam = backproject(depth.astype(f32), inv_K).reshape(-1, 3)              # (HW,3) float32
     P = (np.asarray(K, f32) @ np.asarray(stereo_T, f32))[:3, :].astype(f32)
-    q = (cam[:, 0:1] * P[:, 0] + cam[:, 1:2] * P[:, 1] + cam[:, 2:3] * P[:, 2] + P[:, 3]).astype(f32)
+    # torch.matmul(P, points) over k = 4: one rounded product, then fused multiply-adds in k order (the reference's grid bit
+    # for bit at every size of tests/depth_edge_cases.py but 17 x 257; with separately rounded products at none)
+    cols = [cam[:, 0], cam[:, 1], cam[:, 2], np.ones(len(cam), f32)]
+    q = []
+    for i in range(3):
+        acc = (np.full(len(cam), P[i, 0], f32) * cols[0]).astype(f32)
+        for k in range(1, 4):
+            acc = _fma32(np.full(len(cam), P[i, k], f32), cols[k], acc)
+        q.append(acc)
+    q = np.stack(q, 1)
     den = (q[:, 2] + f32(1e-7)).astype(f32)
     gx = ((q[:, 0] / den / f32(W - 1) - f32(0.5)) * f32(2)).astype(f32)
     gy = ((q[:, 1] / den / f32(H - 1) - f32(0.5)) * f32(2)).astype(f32)
@@ -217,13 +226,16 @@ def grid_sample_bilinear(img, gx, gy):
     wx0, wy0 = (f32(1) - wx1).astype(f32), (f32(1) - wy1).astype(f32)
     out = np.zeros((C,) + gx.shape, f32)
     bad = ~(np.isfinite(ix) & np.isfinite(iy))
+    # the four taps (nw, ne, sw, se) are accumulated with fused multiply-adds, as the reference's CPU kernel does: 4 % of the
+    # samples still differ from it by one rounding, with separately rounded products 25 %
     for dy, wy in ((0, wy0), (1, wy1)):
         for dx, wx in ((0, wx0), (1, wx1)):
             xx = np.where(bad, -1, x0 + dx).astype(np.int64)
             yy = np.where(bad, -1, y0 + dy).astype(np.int64)
             ok = (xx >= 0) & (xx < W) & (yy >= 0) & (yy < H)
             v = img[:, np.clip(yy, 0, H - 1), np.clip(xx, 0, W - 1)]
-            out += np.where(ok, (wx * wy).astype(f32), f32(0))[None] * v
+            w = np.where(ok & ~bad, (wx * wy).astype(f32), f32(0))
+            out = _fma32(np.broadcast_to(w[None], v.shape), v, out)
     out[:, bad] = np.nan
     return out
 

@@ -21,8 +21,6 @@ sys.path.insert(0, HERE)
 import ref_shim  # noqa: E402
 from super_amd import synth  # noqa: E402
 
-torch.set_num_threads(1)
-
 # variant tag -> reference option overrides
 VARIANTS = {
     "v1": dict(data="superv1"),
@@ -87,6 +85,7 @@ def run_reference(ref, base, okw):
 
 
 def main():
+    torch.set_num_threads(1)          # (here, not at import: tests/depth_edge_cases.py imports this module for make_inputs)
     ref = ref_shim.install_data_loader()
     base = make_inputs()
     g = {"in_" + k: v for k, v in base.items()}

@@ -33,27 +33,34 @@ def run_oracle(g, tag):
                                    stereo_T=g["in_stereo_T"] if ssim else None)
 
 
+def check(out, g, tag):
+    """The oracle's outputs against the reference's ``g[tag + field]`` (also test_depth_edge_cases.py)."""
+    has = lambda k: k in (g.files if hasattr(g, "files") else g)
+    # discrete outputs: bit-exact
+    np.testing.assert_array_equal(out["inval"], g[f"{tag}inval"])
+    np.testing.assert_array_equal(out["valid"], g[f"{tag}valid"])
+    np.testing.assert_array_equal(out["index_map"], g[f"{tag}index_map"])
+    # points: the float32 back-projection is reproduced operation by operation
+    np.testing.assert_array_equal(out["points"], g[f"{tag}points"])
+    np.testing.assert_array_equal(out["colors"], g[f"{tag}colors"])
+    np.testing.assert_allclose(out["norms"], g[f"{tag}norms"], rtol=0, atol=2e-6)
+    np.testing.assert_allclose(out["radii"], g[f"{tag}radii"], rtol=1e-5)
+    np.testing.assert_allclose(out["confs"], g[f"{tag}confs"], rtol=1e-6)
+    if has(f"{tag}seg"):
+        np.testing.assert_array_equal(out["seg"], g[f"{tag}seg"])
+        np.testing.assert_allclose(out["seg_conf"], g[f"{tag}seg_conf"], rtol=1e-12)
+        np.testing.assert_allclose(out["dist2edge"], g[f"{tag}dist2edge"], rtol=0, atol=1e-12)
+    if has(f"{tag}disp_conf"):
+        # warp (Project3D + grid_sample) and the blend are the reference's own; the SSIM kernel inside is the
+        # restatement on both sides (scikit-image absent and unpinned) -- see the oracle's header
+        np.testing.assert_allclose(out["disp_conf"], g[f"{tag}disp_conf"], rtol=0, atol=2e-5)
+
+
 @pytest.mark.parametrize("tag", list(VARIANTS))
 def test_depth_preprocessing_matches_reference(tag):
     g = np.load(GOLD)
     out = run_oracle(g, tag)
-    # discrete outputs: bit-exact
-    np.testing.assert_array_equal(out["inval"], g[f"{tag}_inval"])
-    np.testing.assert_array_equal(out["valid"], g[f"{tag}_valid"])
-    np.testing.assert_array_equal(out["index_map"], g[f"{tag}_index_map"])
-    # points: the float32 back-projection is reproduced operation by operation
-    np.testing.assert_array_equal(out["points"], g[f"{tag}_points"])
-    np.testing.assert_array_equal(out["colors"], g[f"{tag}_colors"])
-    np.testing.assert_allclose(out["norms"], g[f"{tag}_norms"], rtol=0, atol=2e-6)
-    np.testing.assert_allclose(out["radii"], g[f"{tag}_radii"], rtol=1e-5)
-    np.testing.assert_allclose(out["confs"], g[f"{tag}_confs"], rtol=1e-6)
-    if f"{tag}_seg" in g.files:
-        np.testing.assert_array_equal(out["seg"], g[f"{tag}_seg"])
-        np.testing.assert_allclose(out["seg_conf"], g[f"{tag}_seg_conf"], rtol=1e-12)
-        np.testing.assert_allclose(out["dist2edge"], g[f"{tag}_dist2edge"], rtol=0, atol=1e-12)
+    check(out, g, tag + "_")
     if f"{tag}_disp_conf" in g.files:
-        # warp (Project3D + grid_sample) and the blend are the reference's own; the SSIM kernel inside is the
-        # restatement on both sides (scikit-image absent and unpinned) -- see the oracle's header
-        np.testing.assert_allclose(out["disp_conf"], g[f"{tag}_disp_conf"], rtol=0, atol=2e-5)
         assert np.abs(g[f"{tag}_confs"] - g["v2_confs"]).max() > 0.05
     assert 0 < out["valid"].sum() < out["valid"].size

@@ -12,7 +12,9 @@ from test_depth_oracle import GOLD, VARIANTS
 pytestmark = pytest.mark.gpu
 
 
-def _run_gpu(base, okw):
+def _run_gpu(base, okw, mutate=None):
+    """``mutate(inputs)`` may replace entries of the input dict before the call (test_gpu_depth_edges.py); the dict as the call
+    left it comes back under ``"_inputs"``."""
     import torch
     from super_amd.data_loader import depth_preprocessing
     kw = dict(okw)
@@ -34,12 +36,17 @@ def _run_gpu(base, okw):
     if "disable_ssim_conf" in kw:
         inputs["stereo_T"] = torch.from_numpy(base["stereo_T"].copy())[None]
         inputs[("color", 0)] = torch.from_numpy(base["color01"].copy())[None].cuda()
+    if "valid_mask" in base:
+        inputs["valid_mask"] = torch.from_numpy(base["valid_mask"].copy())
+    if mutate is not None:
+        mutate(inputs)
     data, inputs, not_inval = depth_preprocessing(opt, None, inputs, return_valid_map=True)
     out = {k: v.cpu().numpy() for k, v in vars(data).items() if hasattr(v, "cpu")}
     if ("disp_conf", 0) in inputs:
         out["disp_conf"] = inputs[("disp_conf", 0)].cpu().numpy()
     out["inval"] = ~not_inval[0, 0].cpu().numpy()
     out["depth_after"] = inputs[("depth", 0)][0, 0].cpu().numpy()
+    out["_inputs"] = inputs
     return out
 
 
