@@ -15,7 +15,7 @@ import csv
 import json
 
 
-# kernels of each phase of an LM iteration on the nested-dissection path (csrc/slm_api.hip slm_run)
+# kernels of each phase of an LM iteration on the nested-dissection path (csrc/slm_lm.hip slm_run)
 PHASE_KERNELS = {
     "zero": ["k_iter_begin_nd", "k_zero_f22"],
     "data_grad": ["k_data_gram"],

@@ -56,7 +56,8 @@ struct LMState {
                                  // (no fence: a release / acquire at agent scope writes back / invalidates the XCD's whole L2)
 };
 
-// Per-slot descriptor, resident in HBM as an array indexed by blockIdx.y.
+// Per-slot descriptor, resident in HBM as an array indexed by blockIdx.y.  It only carries addresses: the buffers belong
+// to the host's Slot (slm_solver.h).
 struct FrameDev {
   slm_frame f;           // caller's device pointers + sizes
   int32_t P;             // 7*J
@@ -151,7 +152,7 @@ struct FrameDev {
   GP<double> flinv;               // inverses of the diagonal Cholesky blocks of the fronts
   GP<double> fmail;               // task graph: per pivot tile column a mailbox of SLM_MAIL_DOUBLES (slm_tile.h) for the streamed hand-off
   long long zero_tile_doubles;    // leading part of ftiles / all of fvec that k_iter_begin_nd zeroes before an assembly
-  // Pivot-column tiles by what reaches them (round 5; per slot, from the plan's destinations -- slm_api.hip):
+  // Pivot-column tiles by what reaches them (round 5; per slot, from the plan's destinations -- slm_bind.hip):
   //   tile_kind[tile number] = 1: PURE FILL -- no assembled block lands in the tile (data term, ARAP, Rot, node diagonal
   //   blocks) and some child maps into it.  Such a tile is never zeroed; its first toucher -- the pull that gathers the
   //   children's updates (k_fpull, or the tile's own task of the task graph) -- starts from zero and STORES the whole tile.

@@ -1,5 +1,6 @@
 // slm_host.h -- what every stage host of the library shares: the error channel behind slm_last_error(), the
-// num_neighbors dispatch, grow-only device buffers, rocPRIM scratch and the member tables of the stage contexts.
+// num_neighbors dispatch, grow-only device buffers (as a function and as the owning DevBuf / PinnedBuf), rocPRIM scratch
+// and the member tables of the stage contexts.
 // Host code only (device code includes slm_common.h, never this).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -65,6 +66,57 @@ hipError_t grow(T*& p, size_t& cap, size_t need, size_t want) {
   p = static_cast<T*>(q);
   return e;
 }
+
+// The same buffer as an owner: move-only, freed by its destructor.  A struct of these (a slot of the LM solver) needs no
+// release list, and a descriptor only mirrors `p`.
+template <typename T>
+struct DevBuf {
+  T* p = nullptr;
+  size_t cap = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+  ~DevBuf() { if (p) (void)hipFree(p); }
+  hipError_t grow(size_t need, size_t want) { return ::grow(p, cap, need, want); }
+  operator T*() const { return p; }
+};
+
+// Host buffer for per-frame device -> host read-backs, PINNED (hipHostMalloc, grow-only), owned like a DevBuf.  A
+// read-back into pageable memory (a std::vector) goes through the runtime's staging path, and several bind workers doing
+// that at once were seen to block for 5-7 ms together once in ~50 steps (tools/studies/stall_hunt.py: the whole rare
+// stall of a bench step sat in this one hipMemcpyAsync + hipStreamSynchronize); a pinned destination is a plain DMA.
+template <typename T>
+struct PinnedBuf {
+  T* p = nullptr;
+  size_t cap = 0, n = 0;
+  PinnedBuf() = default;
+  PinnedBuf(const PinnedBuf&) = delete;
+  PinnedBuf& operator=(const PinnedBuf&) = delete;
+  PinnedBuf(PinnedBuf&& o) noexcept : p(o.p), cap(o.cap), n(o.n) { o.p = nullptr; o.cap = o.n = 0; }
+  ~PinnedBuf() { if (p) (void)hipHostFree(p); }
+  hipError_t grow(size_t need, size_t want) {
+    if (need <= cap) return hipSuccess;
+    if (p) (void)hipHostFree(p);
+    p = nullptr;
+    cap = n = 0;
+    HIPRET(hipHostMalloc((void**)&p, want * sizeof(T), hipHostMallocDefault));
+    cap = want;
+    return hipSuccess;
+  }
+  hipError_t resize(size_t need) {   // a read-back of `need` elements, with head-room
+    HIPRET(grow(need, need + need / 8 + 16));
+    n = need;
+    return hipSuccess;
+  }
+  T* data() { return p; }
+  const T* data() const { return p; }
+  size_t size() const { return n; }
+  T* begin() { return p; }
+  T* end() { return p + n; }
+  T& operator[](size_t i) { return p[i]; }
+  const T& operator[](size_t i) const { return p[i]; }
+};
 
 // rocPRIM temporary storage (bytes, grow-only, exact): call(nullptr, bytes) reports the size, call(tmp, bytes) runs
 template <typename Call>

@@ -1,5 +1,5 @@
 // slm_launch.h -- the launch functions of the LM solver's kernels, declared once, with their default arguments:
-// slm_api.hip calls them; the file that holds the kernels defines them and includes this too, so its definitions are
+// the LM host (slm_api.hip, slm_bind.hip, slm_lm.hip) calls them; the file that holds the kernels defines them and includes this too, so its definitions are
 // compiled against these declarations (a drifted return type or a repeated default argument does not compile; a
 // drifted parameter list is still only caught when the library is loaded).
 #pragma once

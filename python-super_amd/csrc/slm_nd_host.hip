@@ -27,13 +27,6 @@ struct Builder {
   std::vector<char> side;   // scratch: 1 = A, 2 = B
   std::vector<int> idx_scratch;   // scratch: index of a node inside its boundary layer
   int leaf_max = SLM_ND_LEAF;     // stop bisecting at this many nodes
-  static bool use_cover() {
-    static const bool on = [] {
-      const char* e = getenv("SLM_ND_COVER");
-      return e ? atoi(e) != 0 : true;
-    }();
-    return on;
-  }
 
   int dissect(std::vector<int>& nodes, int depth) {
     const int id = (int)tree.size();
@@ -72,7 +65,7 @@ struct Builder {
     // separator: a minimum vertex cover of the cut edges (Koenig's theorem on the bipartite graph
     // between the two boundary layers) -- never larger than the smaller layer, and usually thinner
     std::vector<int> cover;
-    if (use_cover()) {
+    {
       const int na = (int)SA.size(), nb2 = (int)SB.size();
       for (int i = 0; i < nb2; ++i) idx_scratch[SB[i]] = i;
       std::vector<std::vector<int>> ed(na);
@@ -645,20 +638,7 @@ bool nd_build_plan(int J, int K_ED, const float* pts, const int32_t* ed_knn, con
   // WHOLE tree (the deeper fronts are factored and forward-substituted by the per-level launches before this list runs, so
   // their BACKB / BACK tasks need nothing but their parent's solution)
   out.dag_top_tasks.clear();
-  if (out.dag_cut_depth >= 0) {
-    static const bool legacy_top = getenv("SLM_DAG_TOP_LEGACY") != nullptr;   // (A/B: the whole-tree order filtered by depth)
-    if (legacy_top) {
-      for (size_t k = 0; 2 * k < out.dag_tasks.size(); ++k) {
-        const int w0 = out.dag_tasks[2 * k], type = w0 >> 24;
-        if (out.fronts[w0 & 0xFFFFFF].depth <= out.dag_cut_depth || type == ND_T_BACKB || type == ND_T_BACK) {
-          out.dag_top_tasks.push_back(w0);
-          out.dag_top_tasks.push_back(out.dag_tasks[2 * k + 1]);
-        }
-      }
-    } else {
-      model_list(out.dag_cut_depth, out.dag_top_tasks);
-    }
-  }
+  if (out.dag_cut_depth >= 0) model_list(out.dag_cut_depth, out.dag_top_tasks);
   // ---- destinations of the assembled blocks -------------------------------------------------
   auto dest_of = [&](int a, int bnode, NDDest& d) -> bool {   // block given as (a,b), a >= b by id
     const int e = order[a] < order[bnode] ? a : bnode;          // earlier eliminated -> column

@@ -132,6 +132,45 @@ def test_rebinding_does_not_leak_device_memory():
     assert free[8] - free[-1] <= 4 << 20, (free[8], free[-1])
 
 
+def test_create_destroy_does_not_leak_device_memory():
+    """What slm_destroy releases: rounds of create -> bind -> run -> destroy, cycling through the buffer families of a slot
+    and of the solver, leave the free device memory where it was.  (A coarse guard: it sees a family of about 256 KiB per
+    round; the fine check of the owning buffers is tests/test_host_grow_sanitized.py.)"""
+    import ctypes as C
+    import torch
+    from super_amd import _lib, synth
+    from super_amd.engine import DeviceFrame, Engine
+    dev = torch.device("cuda", 0)
+    k4 = DeviceFrame.from_scene(synth.make_scene(seed=53, **SHAPES[3]), dev)
+    k6 = DeviceFrame.from_scene(synth.make_scene(seed=53, n_neighbors=6, **SHAPES[3]), dev)
+    pts = k4.sf_points.double().contiguous()
+    val = torch.ones(k4.N, dtype=torch.uint8, device=dev)
+    families = ["default", "pairs", "band", "corr", "shard", "dag_trace", "prepared"]
+    free = []
+    for it in range(16):
+        fam = families[it % len(families)]
+        eng = Engine(dev, max_frames=1, num_iterations=2, solver_path=1 if fam == "band" else 0)
+        lib, st = eng.lib, eng.stream
+        if fam == "corr":
+            _lib.check(lib.slm_enable_corr(eng.h, 1, 1.0), "slm_enable_corr")
+        if fam == "shard":
+            _lib.check(lib.slm_set_shard(eng.h, 0, 1), "slm_set_shard")
+        eng.bind(0, k6 if fam == "pairs" else k4)
+        if fam == "corr":
+            _lib.check(lib.slm_bind_corr_points(eng.h, 0, pts.data_ptr(), None, val.data_ptr(), st), "slm_bind_corr_points")
+        if fam == "dag_trace":
+            _lib.check(lib.slm_debug_dag_trace(eng.h, 0, 1, st), "slm_debug_dag_trace")
+        eng.run(1)
+        assert eng.records(0)[0]["status"] == _lib.SLM_ITER_OK, fam   # (the round did run)
+        if fam == "prepared":                                # destroyed with a prepared model still queued
+            cs = k4.c_struct()
+            _lib.check(lib.slm_prepare_model(eng.h, 0, C.byref(cs), st), "slm_prepare_model")
+        eng.close()
+        torch.cuda.synchronize()
+        free.append(torch.cuda.mem_get_info(dev)[0])
+    assert free[4] - free[-1] <= 4 << 20, (free[4], free[-1], free)
+
+
 @pytest.mark.parametrize("optimizer", ["SGD", "Adam"])
 def test_one_graphfit_object_over_frames_of_changing_size_matches_fresh_objects(optimizer):
     """The autograd-path mirror keeps ONE solver handle for the whole sequence (as the reference keeps one GraphFit

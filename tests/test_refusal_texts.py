@@ -58,6 +58,39 @@ def _cases():
         ("slm_knn", (0, 2, 4, 0, None, one, one, one, None), INVALID, b"slm_knn: fewer nodes than K (+ self)"),
         ("slm_create", (C.byref(bad_lm), C.byref(out)), INVALID, b"slm_create: solver_path must be 0..4"),
         ("slm_debug_counters", (None,), INVALID, b"slm_debug_counters: null output"),
+        # the LM host, unit by unit: bind ...
+        ("slm_bind_frame", (None, 0, None, None), INVALID, b"slm_bind_frame: null argument"),
+        ("slm_bind_frames", (None, 0, 1, None, None), INVALID, b"slm_bind_frames: null argument"),
+        ("slm_prepare_model", (None, 0, None, None), INVALID, b"slm_prepare_model: null argument"),
+        ("slm_discard_prepared", (None, 0), INVALID, b"slm_discard_prepared: null argument"),
+        # ... the LM step ...
+        ("slm_run", (None, 1, None), INVALID, b"null solver"),
+        ("slm_set_shard", (None, 0, 1), INVALID, b"slm_set_shard: bad rank/world"),
+        ("slm_lm_exchange_size", (None, 0, 0, None), INVALID, b"slm_lm_exchange_size: null output"),
+        ("slm_lm_exchange_ptr", (None, 0, 0, None, None), INVALID, b"slm_lm_exchange_ptr: null output"),
+        ("slm_lm_grad_local", (None, 1, None), INVALID, b"null solver"),
+        ("slm_assemble", (None, 0, None, None, None), INVALID, b"null solver"),
+        ("slm_loss", (None, 0, None, None), INVALID, b"null solver"),
+        ("slm_solve", (None, 0, 1.0, None, None, None), INVALID, b"null solver"),
+        # ... the solver's getters, setters and diagnostics, and the stateless wrappers
+        ("slm_profile_enable", (None, 1), INVALID, b"slm_profile_enable: null solver"),
+        ("slm_profile_read", (None, None, None), INVALID, b"slm_profile_read: null argument"),
+        ("slm_get_beta", (None, 0, None, None), INVALID, b"null solver"),
+        ("slm_get_records", (None, 0, None, 0, None), INVALID, b"null solver"),
+        ("slm_debug_read", (None, 0, 0, None, 0, None, None), INVALID, b"slm_debug_read: bad argument"),
+        ("slm_debug_read_plan", (None, 0, 0, None, 0, None, None), INVALID, b"slm_debug_read_plan: bad argument"),
+        ("slm_debug_dag_trace", (None, 0, 1, None), INVALID, b"slm_debug_dag_trace: bad argument"),
+        ("slm_debug_dag_abort", (None, 1, None), INVALID, b"null solver"),
+        ("slm_debug_dag_timeout", (-1,), INVALID, b"slm_debug_dag_timeout: negative"),
+        ("slm_solve_dense", (0, None, None, None, None, None), INVALID, b"slm_solve_dense: bad argument"),
+        ("slm_data_residuals", (None, 0, None, None, None, None), INVALID, b"null solver"),
+        ("slm_apply_update", (0, 0, 4, None, None, None, None, one, one, one, None), INVALID,
+         b"slm_apply_update: bad argument"),
+        ("slm_knn_weights", (0, 10, 0, one, one, one, one, None, None), INVALID, b"slm_knn_weights: bad argument"),
+        ("slm_knn_f64", (0, 2, 4, 0, None, one, None, None, one, one, None), INVALID,
+         b"slm_knn_f64: fewer nodes than K (+ self)"),
+        ("slm_knn_weights_f64", (0, 10, 0, one, one, one, 0, None, None, one, None, None), INVALID,
+         b"slm_knn_weights_f64: bad argument"),
     ]
 
 
