@@ -331,7 +331,15 @@ int slm_solve_dense(int32_t P, const double* A_device, const double* b_device, d
                     int32_t* status_device, void* stream);
 /* Per-surfel data-term internals at the current beta: r_device (N) float64
  * (lambda * n.(T(p)-o), 0 where unmatched), match_device (N) uint8,
- * taps_device (N,4) int32 target rows of the four bilinear taps (-1 invalid). */
+ * taps_device (N,4) int32 target rows of the four bilinear taps (-1 invalid).
+ * The match set (every form of the data term uses this rule; tests/data_edge_cases.py sits on its edges): project T(p) with
+ * Z + 1e-8, round (u_, v_) half-to-even; the ROUNDED pixel must satisfy 0 <= v < H-1, 0 <= u < W-1 (so -0.5 <= v_ rounds to
+ * a valid 0, and v_ = H-1.5 rounds down only when H-2 is even) and `valid` is read at that rounded pixel alone, not at the
+ * taps.  The four taps (floor|ceil v_, floor|ceil u_) must all lie inside the image, be mapped (index_map >= 0) and hold
+ * finite points and normals, else the surfel is dropped: a rounded pixel 0 with floor tap -1 is dropped, a valid but
+ * unmapped pixel drops through the taps, an invalid but mapped tap still counts.  On an exactly integer coordinate floor ==
+ * ceil and BOTH coinciding taps carry weight 1 (the reference's sum, kept).  A point behind the camera that projects onto
+ * valid pixels matches; a non-finite projection does not.  taps_device rows are filled where the rounded pixel is valid. */
 int slm_data_residuals(slm_solver* s, int32_t slot, double* r_device, uint8_t* match_device,
                        int32_t* taps_device, void* stream);
 
