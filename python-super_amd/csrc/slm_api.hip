@@ -1,6 +1,7 @@
 // slm_api.hip -- the LM solver as a handle of the C ABI (include/super_lm.h): the error channel and the ABI handshake,
-// slm_create / slm_destroy with the environment knobs, the getters, setters and diagnostics of a solver, and the
-// stateless wrappers.  The bind is slm_bind.hip, the LM step slm_lm.hip; what they share is slm_solver.h.
+// slm_create / slm_destroy with the environment knobs, the getters, setters and diagnostics of a solver, and
+// slm_solve_dense.  The bind is slm_bind.hip, the LM step slm_lm.hip; what they share is slm_solver.h.  (The stateless
+// entry points of the node feeder are slm_nodes.hip.)
 #include <new>
 #include <cstdio>
 
@@ -397,92 +398,6 @@ int slm_data_residuals(slm_solver* s, int32_t slot, double* r, uint8_t* match, i
   if (rc) return rc;
   const FrameDev& h = s->slots[slot].h;
   launch_data_resid(s->frames_dev, slot, h.f.N, h.f.K, s->cfg.w_data, r, match, taps, (hipStream_t)stream);
-  HIPCHK(hipGetLastError());
-  return SLM_OK;
-}
-
-int slm_apply_update(int32_t N, int32_t J, int32_t K, float* sf_points, float* sf_norms,
-                     const int32_t* sf_knn_idx, const float* sf_knn_w, float* ed_points,
-                     float* ed_norms, const double* beta, void* stream) {
-  if (K < 1 || K > 8) return fail(SLM_ERR_UNSUPPORTED, "slm_apply_update: num_neighbors must be in 1..8");
-  if (N < 0 || J < 1 || !ed_points || !ed_norms || !beta || (N > 0 && (!sf_points || !sf_norms ||
-      !sf_knn_idx || !sf_knn_w)))
-    return fail(SLM_ERR_INVALID, "slm_apply_update: bad argument");
-  launch_update(N, J, K, sf_points, sf_norms, sf_knn_idx, sf_knn_w, ed_points, ed_norms, beta,
-                (hipStream_t)stream);
-  HIPCHK(hipGetLastError());
-  return SLM_OK;
-}
-
-int slm_apply_update_f64(int32_t N, int32_t J, int32_t K, double* sf_points, double* sf_norms,
-                         const int32_t* sf_knn_idx, const double* sf_knn_w, double* ed_points,
-                         double* ed_norms, const double* beta, void* stream) {
-  if (K < 1 || K > 8) return fail(SLM_ERR_UNSUPPORTED, "slm_apply_update_f64: num_neighbors must be in 1..8");
-  if (N < 0 || J < 1 || !ed_points || !ed_norms || !beta || (N > 0 && (!sf_points || !sf_norms ||
-      !sf_knn_idx || !sf_knn_w)))
-    return fail(SLM_ERR_INVALID, "slm_apply_update_f64: bad argument");
-  launch_update64(N, J, K, sf_points, sf_norms, sf_knn_idx, sf_knn_w, ed_points, ed_norms, beta,
-                  (hipStream_t)stream);
-  HIPCHK(hipGetLastError());
-  return SLM_OK;
-}
-
-int slm_knn(int32_t Nq, int32_t Nn, int32_t K, int32_t skip_self, const float* q, const float* nodes,
-            int32_t* idx, float* dist, void* stream) {
-  if (Nq < 0 || Nn < 1 || K < 1 || K + (skip_self ? 1 : 0) > 9 || !nodes || !idx || !dist ||
-      (Nq > 0 && !q))
-    return fail(SLM_ERR_INVALID, "slm_knn: bad argument (K + skip_self <= 9)");
-  // fewer nodes than neighbours asked for would leave index -1 / distance inf in the tables that
-  // slm_bind_frame, slm_knn_weights and slm_apply_update index with (the reference's knn_points fails too)
-  if (Nn < K + (skip_self ? 1 : 0))
-    return fail(SLM_ERR_INVALID, "slm_knn: fewer nodes than K (+ self)");
-  launch_knn(Nq, Nn, K, skip_self, q, nodes, idx, dist, (hipStream_t)stream);
-  HIPCHK(hipGetLastError());
-  return SLM_OK;
-}
-
-int slm_knn_weights(int32_t Nq, int32_t K, int32_t radius_mode, const int32_t* idx, const float* dist,
-                    const float* radii, float* w, uint8_t* stable, void* stream) {
-  if (Nq < 0 || K < 1 || K > 9 || !idx || !dist || !radii || !w)
-    return fail(SLM_ERR_INVALID, "slm_knn_weights: bad argument");
-  launch_knn_weights(Nq, K, radius_mode, idx, dist, radii, w, stable, (hipStream_t)stream);
-  HIPCHK(hipGetLastError());
-  return SLM_OK;
-}
-
-int slm_knn_f64(int32_t Nq, int32_t Nn, int32_t K, int32_t skip_self, const double* q, const double* nodes,
-                const int32_t* q_seg, const int32_t* node_seg, int32_t* idx, double* dist, void* stream) {
-  if (Nq < 0 || Nn < 1 || K < 1 || K + (skip_self ? 1 : 0) > 9 || !nodes || !idx || !dist || (Nq > 0 && !q) ||
-      ((q_seg == nullptr) != (node_seg == nullptr)))
-    return fail(SLM_ERR_INVALID, "slm_knn_f64: bad argument (K + skip_self <= 9; both class arrays or none)");
-  if (Nn < K + (skip_self ? 1 : 0)) return fail(SLM_ERR_INVALID, "slm_knn_f64: fewer nodes than K (+ self)");
-  hipStream_t st = (hipStream_t)stream;
-  int* counter = nullptr;
-  if (q_seg) {
-    HIPCHK(hipMalloc((void**)&counter, sizeof(int)));
-    HIPCHK(hipMemsetAsync(counter, 0, sizeof(int), st));
-  }
-  launch_knn64(Nq, Nn, K, skip_self, q, nodes, q_seg, node_seg, idx, dist, counter, st);
-  HIPCHK(hipGetLastError());
-  if (counter) {
-    int n_short = 0;
-    HIPCHK(hipMemcpyAsync(&n_short, counter, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    HIPCHK(hipFree(counter));
-    if (n_short > 0)
-      return fail(SLM_ERR_INVALID, "slm_knn_f64: a class has fewer nodes than the neighbours asked for");
-  }
-  return SLM_OK;
-}
-
-int slm_knn_weights_f64(int32_t Nq, int32_t K, int32_t radius_mode, const int32_t* idx, const double* dist,
-                        const double* radii, int32_t num_classes, const double* q_seg_conf,
-                        const double* node_seg_conf, double* w, uint8_t* stable, void* stream) {
-  if (Nq < 0 || K < 1 || K > 9 || !idx || !dist || !radii || !w || num_classes < 0 || num_classes > SLM_MAX_CLASSES ||
-      (num_classes > 0 && (!q_seg_conf || !node_seg_conf)))
-    return fail(SLM_ERR_INVALID, "slm_knn_weights_f64: bad argument");
-  launch_knn_weights64(Nq, K, radius_mode, idx, dist, radii, num_classes, q_seg_conf, node_seg_conf, w, stable,
-                       (hipStream_t)stream);
   HIPCHK(hipGetLastError());
   return SLM_OK;
 }

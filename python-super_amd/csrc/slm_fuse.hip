@@ -19,7 +19,7 @@
 #include <cstring>
 #include <rocprim/rocprim.hpp>
 
-#include "slm_common.h"
+#include "slm_nodes.h"
 #include "slm_host.h"
 
 #define FU_LAYERS 16
@@ -256,53 +256,8 @@ __global__ void __launch_bounds__(256) k_fu_apply_dead(int n, const uint8_t* __r
 // K = opt.num_neighbors (slm_surfel_model::K; the reference's find_knn / weights are K-generic: super/nodes.py:170-191,466-509)
 #define FU_KMAX 8
 __device__ __forceinline__ int fu_K(const slm_surfel_model& m) { return m.K > 0 ? m.K : 4; }
-template <int KK>
-__device__ __forceinline__ void fu_softmaxk(const double d[KK], const double r[KK], double w[KK]) {
-  double e[KK], mx = -1e300, s = 0.0;
-#pragma unroll
-  for (int k = 0; k < KK; ++k) {
-    e[k] = exp(-d[k] / r[k]);
-    mx = fmax(mx, e[k]);
-  }
-#pragma unroll
-  for (int k = 0; k < KK; ++k) {
-    w[k] = exp(e[k] - mx);
-    s += w[k];
-  }
-#pragma unroll
-  for (int k = 0; k < KK; ++k) w[k] /= s;
-}
 
-// Jensen-Shannon divergence of two class distributions (utils/utils.py:244-254)
-__device__ __forceinline__ double fu_jsd(const double* P, const double* Q, int C) {
-  double a = 0.0, b = 0.0;
-  for (int k = 0; k < C; ++k) {
-    const double M = 0.5 * (P[k] + Q[k]);
-    a += P[k] * log(P[k] / (M + 1e-13) + 1e-13);
-    b += Q[k] * log(Q[k] / (M + 1e-13) + 1e-13);
-  }
-  return 0.5 * (a + b);
-}
-
-// softmax(exp(-JSD)^(1/2) * exp(-d/r)^(1/2)) (nodes.py:472-477, power_arg = (1/2, 1/2))
-template <int KK>
-__device__ __forceinline__ void fu_softmaxk_sem(const double d[KK], const double r[KK], const double js[KK], double w[KK]) {
-  double e[KK], mx = -1e300, s = 0.0;
-#pragma unroll
-  for (int k = 0; k < KK; ++k) {
-    e[k] = sqrt(exp(-js[k])) * sqrt(exp(-d[k] / r[k]));
-    mx = fmax(mx, e[k]);
-  }
-#pragma unroll
-  for (int k = 0; k < KK; ++k) {
-    w[k] = exp(e[k] - mx);
-    s += w[k];
-  }
-#pragma unroll
-  for (int k = 0; k < KK; ++k) w[k] /= s;
-}
-
-// knn_w = softmax(exp(-dist / radius)) at the current positions (nodes.py:466-481)
+// knn_w = softmax(exp(-dist / radius)) at the current positions (nodes.py:466-481; node_softmax_weights, node_jsd: slm_nodes.h)
 template <int KK>
 __global__ void __launch_bounds__(256) k_fu_weights(slm_surfel_model m, slm_fuse_semantic sm) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -324,10 +279,10 @@ __global__ void __launch_bounds__(256) k_fu_weights(slm_surfel_model m, slm_fuse
     double js[KK];
 #pragma unroll
     for (int k = 0; k < KK; ++k)
-      js[k] = fu_jsd(sm.ed_seg_conf + (size_t)C * m.knn_idx[KK * (size_t)i + k], sm.seg_conf + (size_t)C * i, C);
-    fu_softmaxk_sem<KK>(d, r, js, w);
+      js[k] = node_jsd(sm.ed_seg_conf + (size_t)C * m.knn_idx[KK * (size_t)i + k], sm.seg_conf + (size_t)C * i, C);
+    node_softmax_weights(KK, d, r, js, w);
   } else {
-    fu_softmaxk<KK>(d, r, w);
+    node_softmax_weights(KK, d, r, nullptr, w);
   }
 #pragma unroll
   for (int k = 0; k < KK; ++k) m.knn_w[KK * (size_t)i + k] = w[k];
@@ -512,10 +467,10 @@ __global__ void __launch_bounds__(256) k_fu_candidates(slm_fuse_config c, slm_su
     const int C = sm.num_classes;
     double js[KK];
 #pragma unroll
-    for (int k = 0; k < KK; ++k) js[k] = fu_jsd(sm.ed_seg_conf + (size_t)C * bi[k], sm.new_seg_conf + (size_t)C * t, C);
-    fu_softmaxk_sem<KK>(d, r, js, w);
+    for (int k = 0; k < KK; ++k) js[k] = node_jsd(sm.ed_seg_conf + (size_t)C * bi[k], sm.new_seg_conf + (size_t)C * t, C);
+    node_softmax_weights(KK, d, r, js, w);
   } else {
-    fu_softmaxk<KK>(d, r, w);
+    node_softmax_weights(KK, d, r, nullptr, w);
   }
 #pragma unroll
   for (int k = 0; k < KK; ++k) {

@@ -100,6 +100,7 @@ __device__ __forceinline__ double gf_sem_weight(const GfSlotDev& s, const int i,
     den += q[c];
   }
   // JSD(P, Q) = (KL(P|M) + KL(Q|M)) / 2, KL(P|Q) = sum P log(P / (Q + eps) + eps)  (utils.py:244-254)
+  // (node_jsd of slm_nodes.h, kept inline: k_gf_data is register-bound under its launch bounds, Q is normalised in the loop)
   const double eps = 1e-13;
   double k1 = 0.0, k2 = 0.0;
   for (int c = 0; c < C; ++c) {
@@ -562,15 +563,6 @@ __global__ void k_gf_advance(GfSlot* __restrict__ slots, int inc) {
   if (s.bound && threadIdx.x == 0) s.step += inc;
 }
 
-// slm_gf_bind_frame's test of the KNN tables (knn_row_bad for every surfel row, the range of every ed_knn_idx entry):
-// *bad = 1 when the frame must be refused.  Reads the tables only.
-__global__ void __launch_bounds__(256) k_gf_check_knn(int N, int K, int J, const int* __restrict__ knn, int n_ed,
-                                                       const int* __restrict__ ed_knn, int* __restrict__ bad) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < N && knn_row_bad(knn + (size_t)K * i, K, J)) *bad = 1;
-  if (i < n_ed && (unsigned)ed_knn[i] >= (unsigned)J) *bad = 1;
-}
-
 __global__ void __launch_bounds__(256) k_gf_init(GfSlot* __restrict__ slots, int slot) {
   GfSlotDev& s = gf_dev(slots)[slot];
   const int n = (s.f.base.J + 1) * 7;
@@ -582,72 +574,6 @@ __global__ void __launch_bounds__(256) k_gf_init(GfSlot* __restrict__ slots, int
     s.m2[e] = 0.0;
   }
   if (e == 0) s.step = 0;
-}
-
-// Surfels.update, autograd variant (super/nodes.py:193-223): T(p) + b_g (the global ROTATION is
-// applied to the normals only, exactly as the reference does), nodes += b_j + b_g.
-template <typename RT, int KK>
-__global__ void __launch_bounds__(256) k_gf_update_surfels(int N, int J, RT* __restrict__ pts_,
-                                                            RT* __restrict__ nrm_,
-                                                            const int* __restrict__ knn_idx,
-                                                            const RT* __restrict__ knn_w,
-                                                            const RT* __restrict__ ed_pts,
-                                                            const double* __restrict__ dv) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= N) return;
-  RT* pts = pts_ + 3 * (size_t)i - 3 * i;   // 64-bit row offsets below go through these bases
-  RT* nrm = nrm_ + 3 * (size_t)i - 3 * i;
-  const d3 p = {(double)pts[3 * i], (double)pts[3 * i + 1], (double)pts[3 * i + 2]};
-  const d3 n0 = {(double)nrm[3 * i], (double)nrm[3 * i + 1], (double)nrm[3 * i + 2]};
-  int id[KK];
-  double w[KK];
-#pragma unroll
-  for (int k = 0; k < KK; ++k) {
-    id[k] = knn_idx[(size_t)KK * i + k];
-    w[k] = (double)knn_w[(size_t)KK * i + k];
-  }
-  d3 T = {0, 0, 0}, Nn = {0, 0, 0};
-#pragma unroll
-  for (int k = 0; k < KK; ++k) {
-    const double* b = dv + 7 * id[k];
-    const d3 g = {(double)ed_pts[3 * id[k]], (double)ed_pts[3 * id[k] + 1], (double)ed_pts[3 * id[k] + 2]};
-    const d3 qv = {b[1], b[2], b[3]};
-    d3 t = quat_apply(b[0], qv, p - g);
-    t = {t.x + b[4] + g.x, t.y + b[5] + g.y, t.z + b[6] + g.z};
-    T = {T.x + w[k] * t.x, T.y + w[k] * t.y, T.z + w[k] * t.z};
-    d3 rn = quat_apply(b[0], qv, n0);
-    rn = {rn.x + b[4], rn.y + b[5], rn.z + b[6]};   // 7-wide beta: b is added (nodes.py:207-209)
-    Nn = {Nn.x + w[k] * rn.x, Nn.y + w[k] * rn.y, Nn.z + w[k] * rn.z};
-  }
-  const double* bgl = dv + 7 * J;
-  Nn = quat_apply(bgl[0], {bgl[1], bgl[2], bgl[3]}, Nn);
-  const double nl = fmax(sqrt(dot(Nn, Nn)), 1e-12);
-  pts[3 * i] = (RT)(T.x + bgl[4]);
-  pts[3 * i + 1] = (RT)(T.y + bgl[5]);
-  pts[3 * i + 2] = (RT)(T.z + bgl[6]);
-  nrm[3 * i] = (RT)(Nn.x / nl);
-  nrm[3 * i + 1] = (RT)(Nn.y / nl);
-  nrm[3 * i + 2] = (RT)(Nn.z / nl);
-}
-
-template <typename RT>
-__global__ void __launch_bounds__(256) k_gf_update_nodes(int J, RT* __restrict__ ed_pts,
-                                                          RT* __restrict__ ed_nrm,
-                                                          const double* __restrict__ dv) {
-  const int j = blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= J) return;
-  const double* b = dv + 7 * j;
-  const double* bgl = dv + 7 * J;
-  const d3 n0 = {(double)ed_nrm[3 * j], (double)ed_nrm[3 * j + 1], (double)ed_nrm[3 * j + 2]};
-  d3 rn = quat_apply(b[0], {b[1], b[2], b[3]}, n0);
-  rn = quat_apply(bgl[0], {bgl[1], bgl[2], bgl[3]}, rn);
-  const double nl = fmax(sqrt(dot(rn, rn)), 1e-12);
-  ed_pts[3 * j] = (RT)((double)ed_pts[3 * j] + b[4] + bgl[4]);
-  ed_pts[3 * j + 1] = (RT)((double)ed_pts[3 * j + 1] + b[5] + bgl[5]);
-  ed_pts[3 * j + 2] = (RT)((double)ed_pts[3 * j + 2] + b[6] + bgl[6]);
-  ed_nrm[3 * j] = (RT)(rn.x / nl);
-  ed_nrm[3 * j + 1] = (RT)(rn.y / nl);
-  ed_nrm[3 * j + 2] = (RT)(rn.z / nl);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -814,23 +740,6 @@ static void gf_enqueue_eval(slm_gf* g, int first, int n, const GfDims& d, hipStr
   if (!in_run) hipLaunchKernelGGL(k_gf_fold, dim3(1, n), dim3(64), 0, st, slots, (int)GF_FOLD_DATA);
 }
 
-template <typename RT>
-static int apply_update_gf_t(int32_t N, int32_t J, int32_t K, RT* sf_points, RT* sf_norms,
-                             const int32_t* sf_knn_idx, const RT* sf_knn_w, RT* ed_points, RT* ed_norms,
-                             const double* deform, void* stream) {
-  if (K < 1 || K > 8) return fail(SLM_ERR_UNSUPPORTED, "slm_apply_update_gf: num_neighbors must be in 1..8");
-  if (N < 0 || J < 1 || !ed_points || !ed_norms || !deform ||
-      (N > 0 && (!sf_points || !sf_norms || !sf_knn_idx || !sf_knn_w)))
-    return fail(SLM_ERR_INVALID, "slm_apply_update_gf: bad argument");
-  hipStream_t st = (hipStream_t)stream;
-  if (N > 0)
-    SLM_K_DISPATCH(K, hipLaunchKernelGGL((k_gf_update_surfels<RT, KK>), dim3((N + 255) / 256), dim3(256), 0, st, N, J, sf_points, sf_norms,
-                                        sf_knn_idx, sf_knn_w, (const RT*)ed_points, deform));
-  hipLaunchKernelGGL(k_gf_update_nodes<RT>, dim3((J + 255) / 256), dim3(256), 0, st, J, ed_points, ed_norms, deform);
-  HIPCHK(hipGetLastError());
-  return SLM_OK;
-}
-
 extern "C" {
 
 int slm_gf_create(const slm_gf_config* cfg, slm_gf** out) {
@@ -908,13 +817,9 @@ int slm_gf_bind_frame(slm_gf* g, int32_t slot, const slm_gf_frame* fr, void* str
   // The KNN tables as the reference's top-k makes them: distinct ids in [0, J) (k_gf_data's row pass gives every id of a
   // row an LDS slot of its own and indexes the nodes with them).  The flag comes back with the descriptor's wait below.
   int bad_host = 0;
-  {
-    const int n_ed = f.J * f.K_ED, n_thr = n_ed > f.N ? n_ed : f.N;
-    HIPCHK(hipMemsetAsync(g->knn_bad, 0, sizeof(int), st));
-    hipLaunchKernelGGL(k_gf_check_knn, dim3((unsigned)((n_thr + 255) / 256)), dim3(256), 0, st, f.N, f.K, f.J, f.sf_knn_idx, n_ed,
-                       f.ed_knn_idx, g->knn_bad);
-    HIPCHK(hipMemcpyAsync(&bad_host, g->knn_bad, sizeof(int), hipMemcpyDeviceToHost, st));
-  }
+  HIPCHK(hipMemsetAsync(g->knn_bad, 0, sizeof(int), st));
+  launch_check_knn(f, g->knn_bad, st);
+  HIPCHK(hipMemcpyAsync(&bad_host, g->knn_bad, sizeof(int), hipMemcpyDeviceToHost, st));
   if (const int rc = gf_upload_slot(g, slot, st)) return rc;
   if (bad_host) {   // refused: the slot stays unbound, on the device too
     s.bound = 0;
@@ -1184,18 +1089,6 @@ int slm_gf_loss_grad(slm_gf* g, int32_t slot, const double* dv, double* terms, d
   if (grad) HIPCHK(hipMemcpyAsync(grad, s.grad, sizeof(double) * d.maxP, hipMemcpyDeviceToDevice, st));
   HIPCHK(hipGetLastError());
   return SLM_OK;
-}
-
-int slm_apply_update_gf(int32_t N, int32_t J, int32_t K, float* sf_points, float* sf_norms,
-                        const int32_t* sf_knn_idx, const float* sf_knn_w, float* ed_points, float* ed_norms,
-                        const double* deform, void* stream) {
-  return apply_update_gf_t<float>(N, J, K, sf_points, sf_norms, sf_knn_idx, sf_knn_w, ed_points, ed_norms, deform, stream);
-}
-
-int slm_apply_update_gf_f64(int32_t N, int32_t J, int32_t K, double* sf_points, double* sf_norms,
-                            const int32_t* sf_knn_idx, const double* sf_knn_w, double* ed_points, double* ed_norms,
-                            const double* deform, void* stream) {
-  return apply_update_gf_t<double>(N, J, K, sf_points, sf_norms, sf_knn_idx, sf_knn_w, ed_points, ed_norms, deform, stream);
 }
 
 }  // extern "C"

@@ -46,6 +46,11 @@ inline int fail(int code, const std::string& msg) { return fail(code, msg.c_str(
     default: break;                                       \
   }
 
+// the KNN-table check of a bind (slm_nodes.hip): *bad (device, zeroed by the caller) = 1 when a surfel's row of sf_knn_idx
+// repeats an id or any sf_knn_idx / ed_knn_idx entry lies outside [0, J).  Enqueues one launch on `stream` (a hipStream_t,
+// as the C ABI passes it); reads the tables only.
+void launch_check_knn(const slm_frame& f, int* bad, void* stream);
+
 // ---- grow-only device buffers ---------------------------------------------------------------------------------------
 // A buffer of `cap` elements of `esz` bytes that must hold `need`: nothing to do while need <= cap; otherwise the old
 // one is freed and `want` elements are allocated (the caller's head-room rule; need itself for an exact fit).  The

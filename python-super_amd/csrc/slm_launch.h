@@ -47,7 +47,7 @@ void launch_reg_grad(const FrameDev*, int, int, int, double, int, double, hipStr
 void launch_after_solve(const FrameDev*, int, int, int, int, double, int, double, int, hipStream_t);
 void launch_reg_loss(const FrameDev*, int, int, int, double, int, double, int, hipStream_t);
 
-// slm_misc.hip
+// slm_misc.hip (the LM loop's state kernels)
 void launch_init_slot(const FrameDev*, int, int, const slm_config&, hipStream_t);
 void launch_iter_begin(const FrameDev*, int, hipStream_t);
 void launch_pack_nodes(const FrameDev*, int, int, hipStream_t);
@@ -57,12 +57,3 @@ void launch_pack_target_px(int, const int*, const uint8_t*, const float*, const 
 void launch_accept(const FrameDev*, int, int, int, int, hipStream_t, int* reuse = nullptr, int eval_pass = 0);
 void launch_loss_out(const FrameDev*, int, int, double*, hipStream_t);
 void launch_zero_reg_part(const FrameDev*, int, int, hipStream_t);
-void launch_update(int, int, int, float*, float*, const int*, const float*, float*, float*, const double*, hipStream_t);
-void launch_update64(int, int, int, double*, double*, const int*, const double*, double*, double*, const double*,
-                     hipStream_t);
-void launch_knn(int, int, int, int, const float*, const float*, int*, float*, hipStream_t);
-void launch_knn64(int, int, int, int, const double*, const double*, const int*, const int*, int*, double*, int*,
-                  hipStream_t);
-void launch_knn_weights64(int, int, int, const int*, const double*, const double*, int, const double*, const double*,
-                          double*, uint8_t*, hipStream_t);
-void launch_knn_weights(int, int, int, const int*, const float*, const float*, float*, uint8_t*, hipStream_t);

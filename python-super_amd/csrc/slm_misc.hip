@@ -1,5 +1,5 @@
-// slm_misc.hip -- LM loop state kernels (accept/reject on the device), Surfels.update,
-// and the KNN feeder.
+// slm_misc.hip -- the LM loop's state kernels (slot initialisation, iteration begin, trial point, accept/reject on the
+// device, target packing, loss read-out) and their launchers, nothing else.  (The node feeder is slm_nodes.hip.)
 #include "slm_common.h"
 #include "slm_launch.h"
 
@@ -222,272 +222,6 @@ __global__ void k_zero_reg_part(const FrameDev* __restrict__ frames, int n_reg_p
   for (int b = threadIdx.x; b < 2 * n_reg_part; b += blockDim.x) reg[b] = 0.0;
 }
 
-// ---------------------------------------------------------------------------------
-// Surfels.update, LM variant (reference super/nodes.py:193-223): in place, on float32 or float64
-// arrays (RT).  Note the reference rotates the normals with the 7-wide beta, so the translation b_k
-// is ADDED to the rotated normal before blending and normalising (nodes.py:207-213).
-template <typename RT>
-__global__ void __launch_bounds__(256) k_update_surfels(int N, int K, RT* __restrict__ pts,
-                                                         RT* __restrict__ nrm,
-                                                         const int* __restrict__ knn_idx,
-                                                         const RT* __restrict__ knn_w,
-                                                         const RT* __restrict__ ed_pts,
-                                                         const double* __restrict__ beta) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= N) return;
-  const size_t i3 = 3 * (size_t)i;
-  const d3 p = {(double)pts[i3], (double)pts[i3 + 1], (double)pts[i3 + 2]};
-  const d3 n0 = {(double)nrm[i3], (double)nrm[i3 + 1], (double)nrm[i3 + 2]};
-  d3 T = {0, 0, 0}, Nn = {0, 0, 0};
-  // (K = opt.num_neighbors, 1..8; the sums run k = 0, 1, ... like the reference's sum over dim 1)
-  for (int k = 0; k < K; ++k) {
-    const int id = knn_idx[(size_t)K * i + k];
-    const double wk = (double)knn_w[(size_t)K * i + k];
-    const double* b = beta + 7 * id;
-    const d3 g = {(double)ed_pts[3 * id], (double)ed_pts[3 * id + 1], (double)ed_pts[3 * id + 2]};
-    const d3 qv = {b[1], b[2], b[3]};
-    d3 t = quat_apply(b[0], qv, p - g);
-    t = {t.x + b[4] + g.x, t.y + b[5] + g.y, t.z + b[6] + g.z};
-    T = {T.x + wk * t.x, T.y + wk * t.y, T.z + wk * t.z};
-    d3 rn = quat_apply(b[0], qv, n0);
-    rn = {rn.x + b[4], rn.y + b[5], rn.z + b[6]};
-    Nn = {Nn.x + wk * rn.x, Nn.y + wk * rn.y, Nn.z + wk * rn.z};
-  }
-  const double nl = fmax(sqrt(dot(Nn, Nn)), 1e-12);   // F.normalize eps
-  pts[i3] = (RT)T.x;
-  pts[i3 + 1] = (RT)T.y;
-  pts[i3 + 2] = (RT)T.z;
-  nrm[i3] = (RT)(Nn.x / nl);
-  nrm[i3 + 1] = (RT)(Nn.y / nl);
-  nrm[i3 + 2] = (RT)(Nn.z / nl);
-}
-
-// must run AFTER k_update_surfels (which reads the old node positions)
-template <typename RT>
-__global__ void __launch_bounds__(256) k_update_nodes(int J, RT* __restrict__ ed_pts,
-                                                       RT* __restrict__ ed_nrm,
-                                                       const double* __restrict__ beta) {
-  const int j = blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= J) return;
-  const double* b = beta + 7 * j;
-  const d3 n0 = {(double)ed_nrm[3 * j], (double)ed_nrm[3 * j + 1], (double)ed_nrm[3 * j + 2]};
-  const d3 rn = quat_apply(b[0], {b[1], b[2], b[3]}, n0);
-  const double nl = fmax(sqrt(dot(rn, rn)), 1e-12);
-  ed_pts[3 * j] = (RT)((double)ed_pts[3 * j] + b[4]);
-  ed_pts[3 * j + 1] = (RT)((double)ed_pts[3 * j + 1] + b[5]);
-  ed_pts[3 * j + 2] = (RT)((double)ed_pts[3 * j + 2] + b[6]);
-  ed_nrm[3 * j] = (RT)(rn.x / nl);
-  ed_nrm[3 * j + 1] = (RT)(rn.y / nl);
-  ed_nrm[3 * j + 2] = (RT)(rn.z / nl);
-}
-
-// ---------------------------------------------------------------------------------
-// Brute-force KNN (replaces pytorch3d.ops.knn_points as called by utils/utils.py:217):
-// node tiles staged through LDS, every thread keeps its K best in registers
-// (squared L2 in f64, ascending, ties -> lowest index because nodes are visited in order
-// and a candidate replaces only on strictly smaller distance).
-#define KNN_MAXK 9
-#define KNN_TILE 1024
-__global__ void __launch_bounds__(256) k_knn(int Nq, int Nn, int K, int skip_self,
-                                              const float* __restrict__ q, const float* __restrict__ nodes,
-                                              int* __restrict__ idx_out, float* __restrict__ dist_out) {
-  __shared__ float sx[KNN_TILE], sy[KNN_TILE], sz[KNN_TILE];
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  const int KK = K + (skip_self ? 1 : 0);
-  double bd[KNN_MAXK];
-  int bi[KNN_MAXK];
-#pragma unroll
-  for (int k = 0; k < KNN_MAXK; ++k) {
-    bd[k] = 1e300;
-    bi[k] = -1;
-  }
-  double px = 0, py = 0, pz = 0;
-  if (i < Nq) {
-    px = q[3 * i];
-    py = q[3 * i + 1];
-    pz = q[3 * i + 2];
-  }
-  for (int base = 0; base < Nn; base += KNN_TILE) {
-    const int cnt = min(KNN_TILE, Nn - base);
-    __syncthreads();
-    for (int t = threadIdx.x; t < cnt; t += blockDim.x) {
-      sx[t] = nodes[3 * (base + t)];
-      sy[t] = nodes[3 * (base + t) + 1];
-      sz[t] = nodes[3 * (base + t) + 2];
-    }
-    __syncthreads();
-    if (i < Nq) {
-      for (int t = 0; t < cnt; ++t) {
-        const double dx = px - (double)sx[t], dy = py - (double)sy[t], dz = pz - (double)sz[t];
-        const double d2 = dx * dx + dy * dy + dz * dz;
-        if (d2 < bd[KNN_MAXK - 1]) {
-          // insertion into the sorted list (static indexing keeps it in registers)
-          double cd = d2;
-          int ci = base + t;
-#pragma unroll
-          for (int k = 0; k < KNN_MAXK; ++k) {
-            if (cd < bd[k]) {
-              const double td = bd[k];
-              const int ti = bi[k];
-              bd[k] = cd;
-              bi[k] = ci;
-              cd = td;
-              ci = ti;
-            }
-          }
-        }
-      }
-    }
-  }
-  if (i < Nq) {
-    const int off = skip_self ? 1 : 0;
-    for (int k = 0; k < K; ++k) {
-      idx_out[i * K + k] = bi[k + off];
-      dist_out[i * K + k] = (float)sqrt(bd[k + off]);
-    }
-  }
-  (void)KK;
-}
-
-// softmax(exp(-dist/radius)) weights + stability test (reference super/nodes.py:166,182,191)
-__global__ void __launch_bounds__(256) k_knn_weights(int Nq, int K, int radius_mode,
-                                                      const int* __restrict__ idx,
-                                                      const float* __restrict__ dist,
-                                                      const float* __restrict__ radii,
-                                                      float* __restrict__ w_out,
-                                                      uint8_t* __restrict__ stable_io) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= Nq) return;
-  double e[KNN_MAXK];
-  double emax = -1e300;
-  bool any_in = false;
-  for (int k = 0; k < K; ++k) {
-    const double r = (double)radii[radius_mode == 0 ? idx[i * K + k] : i];
-    const double d = (double)dist[i * K + k];
-    any_in = any_in || (d <= r);
-    e[k] = exp(-d / r);
-    emax = fmax(emax, e[k]);
-  }
-  double s = 0.0;
-  for (int k = 0; k < K; ++k) {
-    e[k] = exp(e[k] - emax);
-    s += e[k];
-  }
-  for (int k = 0; k < K; ++k) w_out[i * K + k] = (float)(e[k] / s);
-  if (stable_io && !any_in) stable_io[i] = 0;
-}
-
-// float64 variant of the feeder with the Semantic-SuPer branches (find_knn with num_classes,
-// utils/utils.py:223-242: a query only sees the nodes of its own class; weights with the
-// Jensen-Shannon factor, super/nodes.py:183-189).  counter[0] counts queries that found fewer than
-// K (+ self) nodes of their class -- the reference asserts on those.
-__global__ void __launch_bounds__(256) k_knn64(int Nq, int Nn, int K, int skip_self, const double* __restrict__ q,
-                                                const double* __restrict__ nodes, const int* __restrict__ q_seg,
-                                                const int* __restrict__ node_seg, int* __restrict__ idx_out,
-                                                double* __restrict__ dist_out, int* __restrict__ counter) {
-  __shared__ double sx[KNN_TILE], sy[KNN_TILE], sz[KNN_TILE];
-  __shared__ int sc[KNN_TILE];
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  const bool by_class = q_seg != nullptr && node_seg != nullptr;
-  double bd[KNN_MAXK];
-  int bi[KNN_MAXK];
-#pragma unroll
-  for (int k = 0; k < KNN_MAXK; ++k) {
-    bd[k] = 1e300;
-    bi[k] = -1;
-  }
-  double px = 0, py = 0, pz = 0;
-  int cls = 0;
-  if (i < Nq) {
-    px = q[3 * (size_t)i];
-    py = q[3 * (size_t)i + 1];
-    pz = q[3 * (size_t)i + 2];
-    if (by_class) cls = q_seg[i];
-  }
-  for (int base = 0; base < Nn; base += KNN_TILE) {
-    const int cnt = min(KNN_TILE, Nn - base);
-    __syncthreads();
-    for (int t = threadIdx.x; t < cnt; t += blockDim.x) {
-      sx[t] = nodes[3 * (size_t)(base + t)];
-      sy[t] = nodes[3 * (size_t)(base + t) + 1];
-      sz[t] = nodes[3 * (size_t)(base + t) + 2];
-      if (by_class) sc[t] = node_seg[base + t];
-    }
-    __syncthreads();
-    if (i < Nq) {
-      for (int t = 0; t < cnt; ++t) {
-        if (by_class && sc[t] != cls) continue;
-        const double dx = px - sx[t], dy = py - sy[t], dz = pz - sz[t];
-        const double d2 = dx * dx + dy * dy + dz * dz;
-        if (d2 < bd[KNN_MAXK - 1]) {
-          double cd = d2;
-          int ci = base + t;
-#pragma unroll
-          for (int k = 0; k < KNN_MAXK; ++k) {
-            if (cd < bd[k]) {
-              const double td = bd[k];
-              const int ti = bi[k];
-              bd[k] = cd;
-              bi[k] = ci;
-              cd = td;
-              ci = ti;
-            }
-          }
-        }
-      }
-    }
-  }
-  if (i < Nq) {
-    const int off = skip_self ? 1 : 0;
-    bool short_of = false;
-    for (int k = 0; k < K; ++k) {
-      idx_out[(size_t)i * K + k] = bi[k + off];
-      dist_out[(size_t)i * K + k] = sqrt(bd[k + off]);
-      short_of = short_of || bi[k + off] < 0;
-    }
-    if (short_of && counter) atomicAdd(counter, 1);
-  }
-}
-
-// weights in float64; q_seg_conf / node_seg_conf (C columns) switch on the Jensen-Shannon factor
-__global__ void __launch_bounds__(256) k_knn_weights64(int Nq, int K, int radius_mode, const int* __restrict__ idx,
-                                                        const double* __restrict__ dist, const double* __restrict__ radii,
-                                                        int C, const double* __restrict__ q_seg_conf,
-                                                        const double* __restrict__ node_seg_conf,
-                                                        double* __restrict__ w_out, uint8_t* __restrict__ stable_io) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= Nq) return;
-  double e[KNN_MAXK];
-  double emax = -1e300;
-  bool any_in = false;
-  for (int k = 0; k < K; ++k) {
-    const int j = idx[(size_t)i * K + k];
-    const double r = radii[radius_mode == 0 ? j : i];
-    const double d = dist[(size_t)i * K + k];
-    any_in = any_in || (d <= r);
-    e[k] = exp(-d / r);
-    if (C > 0) {
-      const double* P = node_seg_conf + (size_t)C * j;
-      const double* Q = q_seg_conf + (size_t)C * i;
-      double a = 0.0, b = 0.0;
-      for (int c = 0; c < C; ++c) {
-        const double M = 0.5 * (P[c] + Q[c]);
-        a += P[c] * log(P[c] / (M + 1e-13) + 1e-13);
-        b += Q[c] * log(Q[c] / (M + 1e-13) + 1e-13);
-      }
-      e[k] = sqrt(exp(-0.5 * (a + b))) * sqrt(e[k]);
-    }
-    emax = fmax(emax, e[k]);
-  }
-  double s = 0.0;
-  for (int k = 0; k < K; ++k) {
-    e[k] = exp(e[k] - emax);
-    s += e[k];
-  }
-  for (int k = 0; k < K; ++k) w_out[(size_t)i * K + k] = e[k] / s;
-  if (stable_io && !any_in) stable_io[i] = 0;
-}
-
 // ---- host launchers --------------------------------------------------------------
 void launch_init_slot(const FrameDev* frames_dev, int slot, int J, const slm_config& cfg,
                       hipStream_t st) {
@@ -533,50 +267,3 @@ void launch_zero_reg_part(const FrameDev* frames_dev, int n_frames, int n_reg_pa
   hipLaunchKernelGGL(k_zero_reg_part, dim3(1, n_frames), dim3(256), 0, st, frames_dev, n_reg_part);
 }
 
-template <typename RT>
-static void launch_update_t(int N, int J, int K, RT* pts, RT* nrm, const int* knn_idx, const RT* knn_w,
-                            RT* ed_pts, RT* ed_nrm, const double* beta, hipStream_t st) {
-  if (N > 0)
-    hipLaunchKernelGGL(k_update_surfels<RT>, dim3((N + 255) / 256), dim3(256), 0, st, N, K, pts, nrm,
-                       knn_idx, knn_w, (const RT*)ed_pts, beta);
-  if (J > 0)
-    hipLaunchKernelGGL(k_update_nodes<RT>, dim3((J + 255) / 256), dim3(256), 0, st, J, ed_pts, ed_nrm,
-                       beta);
-}
-void launch_update(int N, int J, int K, float* pts, float* nrm, const int* knn_idx, const float* knn_w,
-                   float* ed_pts, float* ed_nrm, const double* beta, hipStream_t st) {
-  launch_update_t<float>(N, J, K, pts, nrm, knn_idx, knn_w, ed_pts, ed_nrm, beta, st);
-}
-void launch_update64(int N, int J, int K, double* pts, double* nrm, const int* knn_idx, const double* knn_w,
-                     double* ed_pts, double* ed_nrm, const double* beta, hipStream_t st) {
-  launch_update_t<double>(N, J, K, pts, nrm, knn_idx, knn_w, ed_pts, ed_nrm, beta, st);
-}
-
-void launch_knn(int Nq, int Nn, int K, int skip_self, const float* q, const float* nodes, int* idx,
-                float* dist, hipStream_t st) {
-  if (Nq <= 0) return;
-  hipLaunchKernelGGL(k_knn, dim3((Nq + 255) / 256), dim3(256), 0, st, Nq, Nn, K, skip_self, q, nodes,
-                     idx, dist);
-}
-
-void launch_knn64(int Nq, int Nn, int K, int skip_self, const double* q, const double* nodes, const int* q_seg,
-                  const int* node_seg, int* idx, double* dist, int* counter, hipStream_t st) {
-  if (Nq <= 0) return;
-  hipLaunchKernelGGL(k_knn64, dim3((Nq + 255) / 256), dim3(256), 0, st, Nq, Nn, K, skip_self, q, nodes, q_seg,
-                     node_seg, idx, dist, counter);
-}
-
-void launch_knn_weights64(int Nq, int K, int radius_mode, const int* idx, const double* dist, const double* radii,
-                          int C, const double* q_conf, const double* node_conf, double* w, uint8_t* stable,
-                          hipStream_t st) {
-  if (Nq <= 0) return;
-  hipLaunchKernelGGL(k_knn_weights64, dim3((Nq + 255) / 256), dim3(256), 0, st, Nq, K, radius_mode, idx, dist,
-                     radii, C, q_conf, node_conf, w, stable);
-}
-
-void launch_knn_weights(int Nq, int K, int radius_mode, const int* idx, const float* dist,
-                        const float* radii, float* w, uint8_t* stable, hipStream_t st) {
-  if (Nq <= 0) return;
-  hipLaunchKernelGGL(k_knn_weights, dim3((Nq + 255) / 256), dim3(256), 0, st, Nq, K, radius_mode,
-                     idx, dist, radii, w, stable);
-}

@@ -75,15 +75,6 @@ __global__ void __launch_bounds__(256) k_tuple_keys(int N, int J, const int* __r
   ids[i] = i;
 }
 
-// the same row test on its own, for the frames that do not take the tuple-sorted path (data_path 1, J >= 65536), and the
-// range test of the node KNN table (n_ed = J * K_ED entries)
-__global__ void __launch_bounds__(256) k_check_knn(int N, int K, int J, const int* __restrict__ knn, long long n_ed,
-                                                    const int* __restrict__ ed_knn, int* __restrict__ bad) {
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < N && knn_row_bad(knn + (size_t)K * i, K, J)) *bad = 1;
-  if (i < n_ed && (unsigned)ed_knn[i] >= (unsigned)J) *bad = 1;
-}
-
 __global__ void __launch_bounds__(256) k_padded_counts(const int* __restrict__ d_nt,
                                                         const int* __restrict__ tcount,
                                                         int* __restrict__ pc) {
@@ -1134,13 +1125,13 @@ static hipError_t read_scal(PrepBuffers* p, int n, hipStream_t st) {
   return hipStreamSynchronize(st);
 }
 
+// the row test of k_tuple_keys on its own, for the frames that do not take the tuple-sorted path (data_path 1,
+// J >= 65536), and the range test of the node KNN table
 hipError_t prep_check_knn(PrepBuffers* p, const slm_frame& f, bool* bad, hipStream_t st) {
   *bad = false;
   if (f.N <= 0) return hipSuccess;
   HIPRET(hipMemsetAsync(p->scal + SC_BAD_KNN, 0, sizeof(int), st));
-  const long long n_ed = (long long)f.J * f.K_ED, n_thr = n_ed > f.N ? n_ed : (long long)f.N;
-  hipLaunchKernelGGL(k_check_knn, dim3((unsigned)((n_thr + 255) / 256)), dim3(256), 0, st, f.N, f.K, f.J, f.sf_knn_idx, n_ed,
-                     f.ed_knn_idx, p->scal + SC_BAD_KNN);
+  launch_check_knn(f, p->scal + SC_BAD_KNN, st);
   HIPRET(hipMemcpyAsync(p->scal_host + SC_BAD_KNN, p->scal + SC_BAD_KNN, sizeof(int), hipMemcpyDeviceToHost, st));
   HIPRET(hipStreamSynchronize(st));
   *bad = p->scal_host[SC_BAD_KNN] != 0;
