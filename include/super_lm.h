@@ -69,7 +69,7 @@ enum {
  * the five structs that carry pointers or were extended (returns SLM_OK or SLM_ERR_INVALID with the mismatch in
  * slm_last_error()).  Bindings call it once after loading the library (super_amd/_lib.py does). */
 #define SLM_ABI_VERSION 3
-#define SLM_PLAN_INFO_DOUBLES 14
+#define SLM_PLAN_INFO_DOUBLES 16
 int slm_abi_version(void);
 int slm_abi_check(int32_t abi_version, int32_t sizeof_slm_config, int32_t sizeof_slm_frame, int32_t sizeof_slm_gf_config,
                   int32_t sizeof_slm_gf_frame, int32_t sizeof_slm_iter_record);
@@ -214,7 +214,10 @@ int slm_get_records(slm_solver* s, int32_t slot, slm_iter_record* host_out, int3
  * [8] workgroup-merged (workgroup, pair) records (0: one Gram per run in HBM), [9] padded positions,
  * [10] FLOPs of one factorisation without the padding of the fronts to 64, [11] tasks of the task-graph solver,
  * [12] pivot-column tiles of the fronts, [13] of them PURE FILL: no assembled block reaches them, some child maps into
- *      them -- neither zeroed per iteration nor read by their first toucher (0 with SLM_PURE_FILL=0). */
+ *      them -- neither zeroed per iteration nor read by their first toucher (0 with SLM_PURE_FILL=0),
+ * [14] the preparation that built the slot's tuple-sorted plan (0 none / pair-record form, 1 binned, 2 rocPRIM pipeline),
+ * [15] the largest bin the last build of that plan saw (surfels per smallest node, pair entries per larger node; 0 under
+ *      the rocPRIM pipeline). */
 int slm_get_plan_info(slm_solver* s, int32_t slot, double* info_out, int32_t capacity);
 
 /* -- one LARGE frame sharded over the GPUs of a node ----------------
@@ -919,7 +922,7 @@ int slm_debug_read(slm_solver* s, int32_t slot, int32_t what, double* host_out, 
  * HOST memory as raw bytes (synchronises `stream`): what = 0 s_idx, 1 grp_run, 2 run_nodes, 3 s_w, 4 blk_key, 5 blk_start,
  * 6 blk_entry, 7 wg_first, 8 wg_last, 9 run_lidx, 10 blk2_start, 11 blk2_entry, 12 s_pts.  *n_bytes receives the array's
  * length; at most max_bytes are copied.  (tests/test_gpu_prepare_binned.py: the binned preparation against the rocPRIM
- * pipeline, array by array.) */
+ * pipeline, array by array; tests/test_gpu_prep_plan.py: both against the NumPy construction of tests/prep_plan_model.py.) */
 int slm_debug_read_plan(slm_solver* s, int32_t slot, int32_t what, void* host_out, int64_t max_bytes, int64_t* n_bytes,
                         void* stream);
 

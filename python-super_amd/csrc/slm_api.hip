@@ -268,6 +268,8 @@ int slm_get_plan_info(slm_solver* s, int32_t slot, double* out_caller, int32_t c
   out[7] = h.n_blocks;
   out[8] = h.v1_ready && h.v2_ready ? h.n_wblk : 0;
   out[9] = h.n_pos;
+  out[14] = h.v1_ready ? sl.prep_kind : 0;
+  out[15] = h.v1_ready ? sl.prep_max_bin : 0;
   for (int i = 0; i < capacity; ++i) out_caller[i] = i < SLM_PLAN_INFO_DOUBLES ? out[i] : 0.0;
   return SLM_OK;
 }

@@ -149,6 +149,8 @@ static int bind_data_plan(slm_solver* s, Slot& sl, const slm_frame* f, hipStream
   FrameDev& h = sl.h;
   h.v1_ready = 0;
   h.vk_ready = 0;
+  sl.prep_kind = 0;
+  sl.prep_max_bin = 0;
   out.form = data_form_of(s->cfg, *f, s->corr_mode != 0);
   if (out.form == DataForm::tuple) {
     V1Sizes sz;
@@ -174,6 +176,8 @@ static int bind_data_plan(slm_solver* s, Slot& sl, const slm_frame* f, hipStream
       HIPCHK(grow(sl.ev_rc, (size_t)4 * sz.n_pos));   // evaluation buffer {r, c} per position
       h.ev_rc = sl.ev_rc.p;
       h.v1_ready = 1;
+      sl.prep_kind = sz.prep_kind;
+      sl.prep_max_bin = sz.max_bin;
       // workgroup-merged records (default); data_path 2 keeps the per-run slab
       h.v2_ready = 0;
       if (s->cfg.data_path == 0 && sz.n_wblk > 0 && sz.max_wblk_per_wg <= SLM_LB_MAX) {

@@ -48,6 +48,8 @@ struct PlanSizes {
 struct V1Sizes : PlanSizes {
   int n_tuples = 0, n_pos = 0, n_runs = 0;
   int n_wblk = 0, max_wblk_per_wg = 0;   // v2 records; v2 is usable when max_wblk_per_wg <= SLM_LB_MAX
+  int prep_kind = 0;                     // the builder the plan came from: 1 binned preparation, 2 rocPRIM pipeline (0: no plan)
+  int max_bin = 0;                       // binned preparation: the largest bin of the build (SC_MAXBIN); 0 under the rocPRIM pipeline
 };
 
 // ---- K-generic pair plan (any opt.num_neighbors in 1..8; reference super/loss.py:213-220 is K-generic) ----------------

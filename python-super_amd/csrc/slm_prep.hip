@@ -406,7 +406,8 @@ __global__ void k_totals3(const int* __restrict__ scal, int* __restrict__ blk2_s
 // binned by that node (count -> one-block scan -> scatter) and every bin is sorted by ONE workgroup in LDS (bitonic,
 // <= BIN_CAP items), which also finds the distinct keys of its bin.  Bins are contiguous and ascending, so the result is
 // the stable device-wide sort of the rocPRIM pipeline ITEM FOR ITEM -- the plan, and with it every floating-point
-// summation order downstream, is unchanged (tests/test_gpu_prepare_binned.py compares the plans array by array).
+// summation order downstream, is unchanged (tests/test_gpu_prepare_binned.py compares the plans array by array;
+// tests/test_gpu_prep_plan.py compares both with the NumPy construction of tests/prep_plan_model.py, on frames at BIN_CAP).
 // 19 launches per frame.  A bin that does not fit (degenerate inputs: thousands of surfels on one node) sends the slot's
 // plan to the rocPRIM pipeline for good (V1Plan::legacy).
 #define BIN_CAP 1024
@@ -1421,12 +1422,16 @@ hipError_t prep_v1(PrepBuffers* p, const slm_frame& f, V1Plan& plan, V1Sizes* ou
   if (!force_legacy && !plan.legacy) {
     HIPRET(prep_v1_binned(p, f, plan, out, &r, st));
     if (r == Built::retry) HIPRET(prep_v1_binned(p, f, plan, out, &r, st));
-    if (r != Built::legacy) return hipSuccess;
+    if (r != Built::legacy) {
+      if (out->n_tuples > 0) { out->prep_kind = 1; out->max_bin = p->scal_host[SC_MAXBIN]; }
+      return hipSuccess;
+    }
     plan.legacy = true;
     plan.nt_hint = 0;
   }
   HIPRET(prep_v1_legacy(p, f, plan, out, &r, st));
   if (r == Built::retry) HIPRET(prep_v1_legacy(p, f, plan, out, &r, st));
+  if (out->n_tuples > 0) out->prep_kind = 2;   // (max_bin stays 0: this pipeline has no bins)
   return hipSuccess;
 }
 

@@ -71,6 +71,7 @@ struct Slot {
   DevBuf<uint8_t> d_tile_kind;     // FrameDev::tile_kind / zero_tiles (slm_common.h): per tile 1 = pure fill; the tiles to zero
   DevBuf<long long> d_zero_tiles;
   int n_piv_tiles = 0, n_pure_tiles = 0;  // pivot-column tiles of the plan / of them pure fill (slm_get_plan_info)
+  int prep_kind = 0, prep_max_bin = 0;    // the preparation that built the tuple-sorted plan (V1Sizes), its largest bin (slm_get_plan_info)
   std::vector<uint8_t> h_tile_kind;      // host sources of the two uploads (kept: the copies are asynchronous)
   std::vector<long long> h_zero_tiles;
   DevBuf<int32_t> d_ints;          // the plan's int32 arrays, one behind the other (kPlanInts)

@@ -81,11 +81,20 @@ def _run(legacy):
     return json.loads(line[len("RESULT "):])
 
 
+WHICH = ("preparation", "largest_bin")      # plan_info: the builder of the plan (1 binned, 2 rocPRIM pipeline) and its largest bin
+
+
+def _sizes(info):
+    return {k: v for k, v in info.items() if k not in WHICH}
+
+
 def test_binned_preparation_gives_the_rocprim_plan_array_for_array():
     new, old = _run(False), _run(True)
     assert new.keys() == old.keys()
     for key in new:
-        assert new[key]["info"] == old[key]["info"], key
+        assert _sizes(new[key]["info"]) == _sizes(old[key]["info"]) and set(WHICH) <= set(new[key]["info"]), key
+        assert new[key]["info"]["preparation"] == 1 and 0 < new[key]["info"]["largest_bin"] <= 1024, (key, new[key]["info"])
+        assert old[key]["info"]["preparation"] == 2 and old[key]["info"]["largest_bin"] == 0, (key, old[key]["info"])
         for what, (n_bytes, sha) in new[key]["plan"].items():
             assert [n_bytes, sha] == old[key]["plan"][what], (key, "plan array", what, n_bytes, old[key]["plan"][what][0])
         assert new[key]["info"]["tuples"] > 0 and new[key]["info"]["merged_records"] > 0
@@ -106,15 +115,18 @@ def test_a_bin_that_does_not_fit_falls_back_to_the_rocprim_pipeline():
     eng = Engine(dev, num_iterations=2)
     fr = DeviceFrame.from_scene(sc, dev)
     eng.bind(0, fr)
+    assert eng.plan_info(0)["preparation"] == 2 and eng.plan_info(0)["largest_bin"] == 0
     eng.run(1)
     b0 = eng.beta(0).cpu().numpy()
     eng.bind(0, fr)
+    assert eng.plan_info(0)["preparation"] == 2
     eng.run(1)
     b1 = eng.beta(0).cpu().numpy()
     assert [r["status"] for r in eng.records(0)] == [0, 0]
     assert np.abs(b0 - b1).max() < 1e-9 and np.isfinite(b0).all()
     small = synth.make_scene(N=3000, J=48, H=60, W=80, seed=7, src_border=5, tgt_border=3)
     eng.bind(0, DeviceFrame.from_scene(small, dev))            # the slot stays on the rocPRIM pipeline: still correct
+    assert eng.plan_info(0)["preparation"] == 2 and eng.plan_info(0)["largest_bin"] == 0
     eng.run(1)
     assert [r["status"] for r in eng.records(0)] == [0, 0]
     eng.close()
