@@ -670,7 +670,10 @@ __device__ __forceinline__ double pull_vec(const FrameDev& fd, const NDTileItem&
 // tile column.
 //   k_fL11  one workgroup per front factors the whole pivot block L11 (all npt tile columns:
 //           tile Cholesky + inverse, row solves and trailing updates inside the block, forward
-//           substitution of the pivot rows), looping over its tiles through LDS / L2;
+//           substitution of the pivot rows), looping over its tiles through LDS / L2.  What one step of a column makes for
+//           the next stays on chip: L(c+1,c) goes from the row solve's accumulators to LDS, where the trailing update reads
+//           it as B and as A; every tile is still stored to global memory, for k_fL21, k_fschur, the back substitution and
+//           the next column's own staging;
 //   k_fL21  one workgroup per boundary row tile r solves its whole row against L11:
 //           X_c = (A(r,c) - sum_{c'<c} X_c' L(c,c')^T) L_cc^-T, results chained in registers
 //           (accumulator layout == next A-fragment layout), rhs row updated at the end.
@@ -678,11 +681,7 @@ __device__ __forceinline__ double pull_vec(const FrameDev& fd, const NDTileItem&
 // LDS: L11Lds (slm_tile.h) -- S is later the B operand of the trailing update; 81 024 B, two workgroups per CU
 __global__ void __launch_bounds__(256, 2) k_fL11(const FrameDev* __restrict__ frames, LevelRef lvl,
                                                double u_override) {
-  extern __shared__ double lds[];
-  double *S = L11Lds::S(lds), *M = L11Lds::M(lds);
-  double* Bl = L11Lds::Bl(lds);    // S is dead once its inverse M exists
-  double* vec = L11Lds::vec(lds);  // NB: rhs tile in / y tile out
-  double* part = L11Lds::vec2(lds);   // NB scratch
+  extern __shared__ double lds0[];
   LevelCtx cx;
   if (!level_begin(frames, lvl, 0, cx)) return;
   const FrameDev& fd = *cx.fd;
@@ -690,29 +689,54 @@ __global__ void __launch_bounds__(256, 2) k_fL11(const FrameDev* __restrict__ fr
   const double u = (u_override >= 0.0) ? u_override : fd.st->u;
   double* vecs = fd.fvec + f.vec_off;
   const int w = threadIdx.x >> 6, l = threadIdx.x & 63, lr = l & 15, lk = l >> 4;
+  const int npt = f.npt, n1 = f.n1;
+  // The LDS base through an opaque zero, once per phase of a column: every lane's LDS addresses (some sixty VGPRs for the
+  // factorisation alone) are then formed in the phase that uses them, instead of once in front of the loop and kept in
+  // registers across it -- that is what lets an operand wait in registers across the commit (239 VGPRs without, 210 with).
+  auto lds_here = [&]() {
+    int zero = 0;
+    asm volatile("" : "+s"(zero));
+    return lds0 + zero;
+  };
 
-  for (int c = 0; c < f.npt; ++c) {
+  double rhs_c = 0.0;   // rhs tile c (kept in a register: vec | part is the factorisation's exchange buffer)
+  for (int c = 0; c < npt; ++c) {
+    const bool more = c + 1 < npt;
+    double* lds = lds_here();
     // ---- diagonal tile: factor + inverse + forward substitution of rhs tile c ----
-    double rhs_c = 0.0;
     {
+      double* S = L11Lds::S(lds);
       double v[16];
       tile_to_regs(ftile(fd, f, c, c), v);
-      if (threadIdx.x < NB) rhs_c = vecs[(size_t)c * NB + threadIdx.x];   // (kept in a register: vec | part is the factorisation's exchange buffer)
+      if (c == 0 && threadIdx.x < NB) rhs_c = vecs[threadIdx.x];   // (a later column's was loaded behind the row solves)
       // (damped_lower's rule in inline text: through regs_to_diag_tile this kernel spills two more SGPRs, 109 against 107)
 #pragma unroll
       for (int t = 0; t < 16; ++t) {
         const int e = threadIdx.x + 256 * t;
         const int i = e % NB, k = e / NB;
         double x = (i >= k) ? v[t] : 0.0;
-        if (i == k) x = (c * NB + i < f.n1) ? x + u : 1.0;
+        if (i == k) x = (c * NB + i < n1) ? x + u : 1.0;
         S[i + k * LD] = x;
       }
     }
     __syncthreads();
     // factor + inverse in the pipelined form of the task graph (wave 0 runs the pivot chain, waves 1-3 trail with the
     // panel / trailing / inverse blocks): 11.7 us per tile against ~14 for potrf64 + inverse_assemble64
-    const bool ok = L11Lds::factor(lds, nullptr, nullptr, nullptr, min(4, (f.n1 - c * NB + 15) >> 4));
+    const bool ok = factor_inverse64p(L11Lds::S(lds), L11Lds::M(lds), L11Lds::dinv(lds), L11Lds::wt(lds), L11Lds::xch(lds), L11Lds::s_ok(lds),
+                                      L11Lds::pf(lds), nullptr, nullptr, nullptr, min(4, (n1 - c * NB + 15) >> 4));
     if (!ok && threadIdx.x == 0) fd.st->chol_fail = 1;
+    lds = lds_here();
+    double* M = L11Lds::M(lds);
+    double* Bl = L11Lds::Bl(lds);    // S is dead once its inverse M exists
+    double* vec = L11Lds::vec(lds);  // NB: rhs tile in / y tile out
+    double* part = L11Lds::vec2(lds);   // NB scratch
+    // The first row solve's operand was final before this column started: its load goes out here, ahead of the commit and its
+    // barriers (the same lanes stored it, in the same layout)
+    double areg[16];
+    if (more) {
+      load_a_frags(ftile(fd, f, npt - 1, c), areg);
+      __builtin_amdgcn_sched_barrier(0);
+    }
     if (threadIdx.x < NB) vec[threadIdx.x] = rhs_c;
     __syncthreads();
     {
@@ -725,31 +749,38 @@ __global__ void __launch_bounds__(256, 2) k_fL11(const FrameDev* __restrict__ fr
       __syncthreads();
     }
     // ---- row solves inside the pivot block: L(r,c) = A(r,c) L_cc^-T, rhs_r -= L(r,c) y_c ----
-    for (int r = c + 1; r < f.npt; ++r) {
+    // (bottom up: row c+1 last, whose result is handed on through LDS)
+    for (int r = npt - 1; r > c; --r) {
       double* At = ftile(fd, f, r, c);
-      double areg[16];
-      load_a_frags(At, areg);
+      if (r < npt - 1) load_a_frags(At, areg);
       double4_t acc[4];
       zero_acc(acc);
       tile_ABt_regs<false, true>(areg, M, acc);
-      store_c_frags(At, acc);
       // rhs rows of this wave: sum_col L[row][col] y[col], reduced over the 4 lk lanes
       const double sacc = sum_row_lanes(acc_dot_vec(acc, vec, 0.0));
+      store_c_frags(At, acc);
+      // L(c+1,c) stays on chip: Bl is the B operand of tile column c+1's trailing update and the A operand of its diagonal tile
+      if (r == c + 1) acc_to_lds(Bl, acc);
       if (lk == 0) vecs[(size_t)r * NB + 16 * w + lr] -= sacc;
     }
-    __syncthreads();   // L(r,c) tiles visible to the whole workgroup
+    __syncthreads();   // L(r,c) tiles and rhs rows visible to the whole workgroup, Bl complete, M dead
+    if (more && threadIdx.x < NB) rhs_c = vecs[(size_t)(c + 1) * NB + threadIdx.x];
     // ---- trailing update inside the pivot block: A(r,s) -= L(r,c) L(s,c)^T ----
-    for (int sc = c + 1; sc < f.npt; ++sc) {
+    lds = lds_here();
+    Bl = L11Lds::Bl(lds);
+    for (int sc = c + 1; sc < npt; ++sc) {
       // (not tile_product: L(sc,c) is staged once for the whole tile column sc, and the diagonal tile's product is trimmed)
-      double breg[16];
-      tile_to_regs(ftile(fd, f, sc, c), breg);
-      __syncthreads();   // previous users of Bl are done
-      regs_to_lds(Bl, breg);
-      __syncthreads();
-      for (int r = sc; r < f.npt; ++r) {
+      if (sc > c + 1) {
+        double breg[16];
+        tile_to_regs(ftile(fd, f, sc, c), breg);
+        __syncthreads();   // previous users of Bl are done
+        regs_to_lds(Bl, breg);
+        __syncthreads();
+      }
+      for (int r = sc; r < npt; ++r) {
         double* Ct = ftile(fd, f, r, sc);
-        double areg[16];
-        load_a_frags(ftile(fd, f, r, c), areg);
+        if (r == c + 1) load_a_frags(Bl, areg);   // L(c+1,c) from its LDS copy (same leading dimension)
+        else load_a_frags(ftile(fd, f, r, c), areg);
         double4_t acc[4];
         load_c_frags(Ct, acc);
         // (a diagonal tile is only ever read in its lower triangle: wave w leaves the blocks right of its own alone)

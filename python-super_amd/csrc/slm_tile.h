@@ -6,6 +6,7 @@
 //   TileLds<NVEC, NINT>                             the dynamic LDS of a kernel that factors tiles
 //   load_a_frags, load_c_frags, store_c_frags, tile_ABt_regs[_trim], trsm_rows16    tile products in registers
 //   damped_lower, tile_to_regs / regs_to_lds / regs_to_diag_tile, stage_diag_tile    staging; the diagonal-tile rule
+//   acc_to_lds                                      a product's result straight to an LDS tile
 //   commit_pivot                                    inverse -> linv, y = L^-1 b
 //   zero_acc, load_c_frags_nblk / store_c_frags_nblk, acc_dot_vec + sum_row_lanes    accumulator-layout access
 //   tile_vec_quarters, tile_t_vec_lanes + sum_col_lanes                 the two tile-times-vector forms
@@ -651,6 +652,19 @@ __device__ __forceinline__ void stage_diag_tile(const double* src, int row0, int
   double v[16];
   tile_to_regs(src, v);
   regs_to_diag_tile(v, row0, n_rows, u, S);
+}
+
+// A tile from the accumulators of the product that formed it (wave w rows 16w.., see load_c_frags) to an LDS tile, without the
+// round trip through global memory (the B operand of a following product).  Per store the 16 lanes of a quarter wave write 16
+// consecutive doubles of one column, as in regs_to_lds.  (The lane's own address once, the 16 elements at constant offsets
+// from it: formed from the element's column, each store has an address register of its own.)
+__device__ __forceinline__ void acc_to_lds(double* Bl, const double4_t acc[4]) {
+  const int l = threadIdx.x & 63, w = threadIdx.x >> 6, lr = l & 15, lk = l >> 4;
+  double* mine = Bl + (16 * w + lr) + lk * LD;
+#pragma unroll
+  for (int ni = 0; ni < 4; ++ni)
+#pragma unroll
+    for (int rr = 0; rr < 4; ++rr) mine[(16 * ni + 4 * rr) * LD] = acc[ni][rr];
 }
 
 // The pivot commit: the inverse M of a factored diagonal tile goes to linv (global), and threads < NB form y = L^-1 b
