@@ -296,6 +296,49 @@ int slm_bind_corr_points(slm_solver* s, int32_t slot, const double* pts, const d
 int slm_corr_get_targets(slm_solver* s, int32_t slot, double* pts, double* nrm, uint8_t* valid, void* stream);
 int slm_corr_loss(slm_solver* s, int32_t slot, double* out_device, void* stream);
 
+/* -- per-residual weights of the LM path's point-to-plane term (reference super/loss.py:347-399, on the first-order path:
+ * slm_gf_config seg_mode / pp_max) ---------------------------------------------------------------------------------------
+ * Opt-in.  For every surfel i of the match set (unchanged), with e = T_i(beta) - o, s_i = (n.e)^2 (no lambda):
+ *   seg_mode 1 (hard) / 2 (soft): conf = sum over the residual's four taps of wv_t tgt_seg_conf[row_t, :], q = softmax(conf)
+ *     (the reference softmaxes the sampled confidences again); hard w_i = [sf_seg[i] == argmax q] (the first maximum wins),
+ *     soft w_i = exp(-0.1 JSD(sf_seg_conf[i], q)) in the eps = 1e-13 form of the reference.  pp_max is ignored, like there.
+ *   seg_mode 0 with pp_max > 0: w_i = [s_i < pp_max]  (the reference's max = 2e-5 for RAFT-stereo depth).
+ * The weights are constants of the linearisation: the Jacobian pass uses row_i sqrt(w_i) and r_i sqrt(w_i) with w_i at beta,
+ * the loss pass sums w_i r_i^2 with w_i and the match set fresh at the trial point.  M_grad / M_loss stay the match-set
+ * counts: a surfel of weight 0 is matched and contributes nothing.  The reference's Huber weight is not built: on squared
+ * residuals in m^2 its formula is the constant huber_th, and no reference caller passes it.
+ *
+ * slm_enable_data_weights: after slm_create, before the first bind.  (0, 0.0) switches the option off again.  An enabled
+ * solver takes the pair-record form of the data term for every num_neighbors, 4 included (as slm_enable_corr, with which it
+ * may be combined; slm_set_shard is allowed too: the weight is local to a surfel).  It refuses with
+ *   SLM_ERR_INVALID      "slm_enable_data_weights: null argument"
+ *                        "slm_enable_data_weights: seg_mode must be 0 (none), 1 (hard) or 2 (soft)"
+ *                        "slm_enable_data_weights: pp_max must be finite and >= 0"
+ *                        "slm_enable_data_weights: a slot is already bound; call it after slm_create and before the first bind"
+ *   SLM_ERR_UNSUPPORTED  "slm_enable_data_weights: needs the pair-record data path (data_path 0 or 2)"
+ *                        "slm_enable_data_weights: needs a nested-dissection solver_path (0, 2, 3 or 4)"
+ *                        "slm_enable_data_weights: needs the data term (use_data 1)"
+ * and on an enabled solver
+ *   SLM_ERR_UNSUPPORTED  "slm_bind_frame: the data weights (slm_enable_data_weights) need J < 65536"
+ *
+ * slm_bind_data_semantic: after slm_bind_frame.  Device pointers, read in place like the frame's own (they must stay valid
+ * and unchanged while the slot is used): sf_seg (N) int32, sf_seg_conf (N,C) float32, tgt_seg_conf (T,C) float32, rows as
+ * the target table's.  slm_bind_frame / slm_bind_frames clear a slot's semantic inputs.  It refuses with
+ *   SLM_ERR_INVALID      "<fn>: null argument"   "<fn>: bad slot"
+ *   SLM_ERR_UNSUPPORTED  "<fn>: slm_enable_data_weights first"
+ *                        "slm_bind_data_semantic: num_classes must be in 1..SLM_MAX_CLASSES (4)"
+ *   SLM_ERR_UNBOUND      "<fn>: slm_bind_frame first"
+ * With seg_mode != 0, slm_run, slm_loss, slm_assemble, slm_solve, slm_lm_grad_local, slm_lm_loss_local and slm_data_weights
+ * over a slot without the inputs return (there is no silent unweighted run)
+ *   SLM_ERR_UNBOUND      "<fn>: slot <i> has no semantic inputs; call slm_bind_data_semantic after slm_bind_frame"
+ *
+ * slm_data_weights: w_device (N) float64 = w_i at the slot's current beta, 0 for unmatched surfels: the diagnostic twin of
+ * slm_data_residuals, which stays unweighted.  Refuses like slm_bind_data_semantic. */
+int slm_enable_data_weights(slm_solver* s, int32_t seg_mode, double pp_max);
+int slm_bind_data_semantic(slm_solver* s, int32_t slot, int32_t num_classes, const int32_t* sf_seg, const float* sf_seg_conf,
+                           const float* tgt_seg_conf, void* stream);
+int slm_data_weights(slm_solver* s, int32_t slot, double* w_device, void* stream);
+
 /* -- phase timing (bench.py roofline leg) ----------------------------------------- */
 /* With profiling on, slm_run brackets each phase of every LM iteration with HIP events
  * recorded on the launch stream.  Phases: */

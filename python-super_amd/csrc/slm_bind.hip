@@ -14,7 +14,8 @@ static const char* const kBadKnn =
     "slm_bind_frame: a KNN index (sf_knn_idx or ed_knn_idx) lies outside [0, J) or a surfel's row of sf_knn_idx repeats an id";
 
 // a frame's form, decided at bind (a plan that comes out empty leaves the slot per_entry: bind_model_part)
-// corr: the solver carries the correspondence term (slm_enable_corr), which adds into the pair records: pairs for every K
+// corr: the solver carries the correspondence term (slm_enable_corr), which adds into the pair records, or the per-residual
+// weights (slm_enable_data_weights), whose kernels are the pair form's: pairs for every K
 static DataForm data_form_of(const slm_config& c, const slm_frame& f, bool corr) {
   if (!c.use_data || f.N <= 0) return DataForm::none;
   if (c.data_path == 1 || f.J >= 65536) return DataForm::per_entry;
@@ -84,6 +85,8 @@ static int check_model_args(const slm_solver* s, int32_t slot, const slm_frame* 
   if (f->N < 0 || f->J < 1) return fail(SLM_ERR_INVALID, "slm_bind_frame: bad sizes");
   if (s->corr_mode && f->J >= 65536)   // (the pair keys are a * J + b in 32 bits: such a frame takes the per-entry form)
     return fail(SLM_ERR_UNSUPPORTED, "slm_bind_frame: the correspondence term (slm_enable_corr) needs J < 65536");
+  if (s->weights_on && f->J >= 65536)   // (the same: the weighted kernels are those of the pair form)
+    return fail(SLM_ERR_UNSUPPORTED, "slm_bind_frame: the data weights (slm_enable_data_weights) need J < 65536");
   if (f->N > 0 && f->J < f->K)   // (the reference's top-k of K among J nodes raises; the device checks below assume J >= K)
     return fail(SLM_ERR_INVALID, "slm_bind_frame: fewer nodes (J) than num_neighbors: sf_knn_idx cannot hold K distinct ids");
   if ((f->N > 0 && (!f->sf_points || !f->sf_knn_idx || !f->sf_knn_w)) || !f->ed_points || !f->ed_knn_idx)
@@ -151,7 +154,7 @@ static int bind_data_plan(slm_solver* s, Slot& sl, const slm_frame* f, hipStream
   h.vk_ready = 0;
   sl.prep_kind = 0;
   sl.prep_max_bin = 0;
-  out.form = data_form_of(s->cfg, *f, s->corr_mode != 0);
+  out.form = data_form_of(s->cfg, *f, s->corr_mode != 0 || s->weights_on);
   if (out.form == DataForm::tuple) {
     V1Sizes sz;
     HIPCHK(prep_v1(prep, *f, sl.plan, &sz, st));
@@ -452,6 +455,10 @@ static int bind_target_part(slm_solver* s, int32_t slot, const slm_frame* f, hip
   if (s->corr_mode) {   // a new frame: the slot's correspondences belonged to the last one
     sl.corr.has = 0;
     HIPCHK(hipMemsetAsync(&s->corr_dev[slot].has, 0, sizeof(int32_t), st));
+  }
+  if (s->weights_on) {   // and so did its semantic inputs
+    sl.wdev.has = 0;
+    HIPCHK(hipMemsetAsync(&s->w_dev[slot].has, 0, sizeof(int32_t), st));
   }
   // descriptor -> device through the slot's pinned mirror: no wait for the copy (the mirror always holds the newest
   // host state, and every change of it is followed by another copy on the stream)

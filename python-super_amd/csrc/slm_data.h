@@ -22,6 +22,70 @@ struct SurfelEvalT {
 };
 typedef SurfelEvalT<SLM_K> SurfelEval;
 
+// ---- per-residual weights of the term (slm_enable_data_weights, include/super_lm.h; reference super/loss.py:347-399) ----
+// The semantic inputs of a slot, resident in HBM as an array beside the FrameDev array (same index); the caller's own
+// arrays, read in place like the frame's.
+struct DataWeightDev {
+  GP<int32_t> sf_seg;        // (N) class of every surfel
+  GP<float> sf_seg_conf;     // (N,C) class distribution of every surfel
+  GP<float> tgt_seg_conf;    // (T,C) class scores of the target rows
+  int32_t C;                 // 1..SLM_MAX_CLASSES
+  int32_t has;               // 1 once slm_bind_data_semantic ran for the bound frame
+};
+// What a weighted kernel is launched with: the descriptors (null with seg_mode 0), seg_mode 1 hard / 2 soft semantic
+// weight, 0 with pp_max > 0: the truncation (squared residuals >= pp_max weigh 0).
+struct DataWArgs {
+  const DataWeightDev* wd;
+  double pp_max;
+  int32_t seg_mode, pad;
+};
+
+// w of a matched surfel: s = (n.e)^2 without lambda; rows / wv = the four taps and their bilinear weights.  seg_mode != 0:
+// gf_sem_weight of slm_gf.hip on conf = sum_t wv_t tgt_seg_conf[row_t] (softmaxed again, loss.py:357; the first maximum
+// wins), pp_max ignored like the reference; seg_mode 0: [s < pp_max].  A slot without semantic inputs is refused by the
+// host before any launch (weights_check, slm_lm.hip); the device reads it as weight 1.
+__device__ __forceinline__ double data_weight(const DataWArgs& a, const DataWeightDev* __restrict__ wd, const int i, const double s,
+                                              const int rows[4], const double wv[4]) {
+  if (a.seg_mode == 0) return (a.pp_max > 0.0 && !(s < a.pp_max)) ? 0.0 : 1.0;
+  if (!wd || !wd->has) return 1.0;
+  const int C = wd->C;
+  double conf[SLM_MAX_CLASSES] = {0, 0, 0, 0};
+  const float* __restrict__ tc = wd->tgt_seg_conf;
+#pragma unroll
+  for (int t = 0; t < 4; ++t)
+#pragma unroll
+    for (int c = 0; c < SLM_MAX_CLASSES; ++c)
+      if (c < C) conf[c] += (double)tc[(size_t)rows[t] * C + c] * wv[t];
+  double mx = conf[0];
+  int am = 0;
+#pragma unroll
+  for (int c = 1; c < SLM_MAX_CLASSES; ++c)
+    if (c < C && conf[c] > mx) {
+      mx = conf[c];
+      am = c;
+    }
+  if (a.seg_mode == 1) return (wd->sf_seg[i] == am) ? 1.0 : 0.0;
+  double q[SLM_MAX_CLASSES], den = 0.0;
+#pragma unroll
+  for (int c = 0; c < SLM_MAX_CLASSES; ++c) {
+    q[c] = c < C ? exp(conf[c] - mx) : 0.0;
+    den += q[c];
+  }
+  // JSD(P, Q) = (KL(P|M) + KL(Q|M)) / 2, KL(P|Q) = sum P log(P / (Q + eps) + eps)  (utils.py:244-254)
+  const double eps = 1e-13;
+  const float* __restrict__ sc = wd->sf_seg_conf;
+  double k1 = 0.0, k2 = 0.0;
+#pragma unroll
+  for (int c = 0; c < SLM_MAX_CLASSES; ++c)
+    if (c < C) {
+      const double pc = (double)sc[(size_t)i * C + c], qc = q[c] / den;
+      const double m = 0.5 * (pc + qc);
+      k1 += pc * log(pc / (m + eps) + eps);
+      k2 += qc * log(qc / (m + eps) + eps);
+    }
+  return exp(-0.1 * (0.5 * (k1 + k2)));
+}
+
 // The 28 Jacobian-row entries of a surfel from c (reference super/loss.py:258-288): lambda * [w_k c^T dR(q_k)(p - g_k)/dq_k | w_k c]
 // for its four nodes.  Needs the surfel and its nodes only -- no projection, no target table.
 __device__ __forceinline__ void rows_from_c(const d3 p, const int id[4], const double w[4], double lam,
@@ -54,10 +118,16 @@ __device__ __forceinline__ void rows_from_c(const d3 p, const int id[4], const d
 // PX: the target taps come from the per-pixel table (FrameDev::tgt_px): one 32-byte gather per tap, the validity of the
 // rounded pixel from the tap that IS that pixel; out.taps is not filled (the evaluation pass of the LM loop does not
 // need the row numbers).  Same values, same sums: the match set and the residuals are those of the row-table form.
-template <int MODE, int KK, bool PX = false>
+// WT: the weighted variant (row-table form only): *wt = the surfel's weight at this point (data_weight; 0 when unmatched),
+// from the taps and tap weights of the residual.  The caller scales row and r by its square root.
+template <int MODE, int KK, bool PX = false, bool WT = false>
 __device__ __forceinline__ void eval_surfel_coreT(const FrameDev& fd, const d3 p, const int id[KK], const double w[KK],
-                                                  double lam, const double* __restrict__ npk, SurfelEvalT<KK>& out) {
+                                                  double lam, const double* __restrict__ npk, SurfelEvalT<KK>& out,
+                                                  const DataWArgs* wa = nullptr, const DataWeightDev* wd = nullptr, int i = 0,
+                                                  double* wt = nullptr) {
+  static_assert(!(WT && PX), "the weighted variant reads the taps' row numbers");
   const FrameIn& f = frame_in(fd);
+  if constexpr (WT) *wt = 0.0;
 
   double qw[KK];
   d3 qv[KK], dk[KK];
@@ -162,6 +232,13 @@ __device__ __forceinline__ void eval_surfel_coreT(const FrameDev& fd, const d3 p
   const d3 e = T - o;
   out.match = true;
   out.r = lam * dot(n, e);
+  if constexpr (WT) {
+    double wv[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) wv[t] = fmax(1.0 - fabs(nn[t] - v_), 0.0) * fmax(1.0 - fabs(mm[t] - u_), 0.0);
+    const double ne = dot(n, e);
+    *wt = data_weight(*wa, wd, i, ne * ne, out.taps, wv);
+  }
   if (!MODE) return;
 
   // ---- c = n^T (I - A) + e^T B, A = do/d(u,v) Pi, B = dn/d(u,v) Pi (loss.py:257-281) ----
@@ -209,6 +286,21 @@ __device__ __forceinline__ void eval_surfel_at(const FrameDev& fd, const void* _
   ld_state4(sf_w, (size_t)i, fd.f.state_f64, w);
   eval_surfel_core<MODE>(fd, ld_state3(sf_pts, (size_t)i, fd.f.state_f64),
                          *reinterpret_cast<const int4*>(sf_idx + 4 * (size_t)i), w, lam, npk, out);
+}
+
+// surfel i of the caller's own arrays, weighted (any KK takes the K-generic loads): wt = its weight
+template <int MODE, int KK>
+__device__ __forceinline__ void eval_surfel_w(const FrameDev& fd, double lam, const double* npk, int i, SurfelEvalT<KK>& out,
+                                              const DataWArgs& wa, const DataWeightDev* wd, double& wt) {
+  const FrameIn& f = frame_in(fd);
+  double wk[KK];
+  int idk[KK];
+#pragma unroll
+  for (int k = 0; k < KK; ++k) {
+    idk[k] = f.sf_knn_idx[(size_t)KK * i + k];
+    wk[k] = ld_state1(f.sf_knn_w, (size_t)KK * i + k, fd.f.state_f64);
+  }
+  eval_surfel_coreT<MODE, KK, false, true>(fd, ld_state3(f.sf_points, (size_t)i, fd.f.state_f64), idk, wk, lam, npk, out, &wa, wd, i, &wt);
 }
 
 // surfel i of the caller's own arrays with KK neighbours per surfel (rows of KK ids / weights)

@@ -6,9 +6,12 @@
 #include "slm_common.h"
 
 // slm_data.hip
-void launch_data_grad(const FrameDev*, int, int, int, double, hipStream_t);
-void launch_data_grad_pairs(const FrameDev*, int, int, int, double, hipStream_t);
-void launch_data_loss(const FrameDev*, int, int, int, double, int, hipStream_t);
+// (wa: the weighted variant of an enabled solver, slm_enable_data_weights; null: the kernels as they always were)
+struct DataWArgs;
+void launch_data_grad(const FrameDev*, int, int, int, double, hipStream_t, const DataWArgs* wa = nullptr);
+void launch_data_grad_pairs(const FrameDev*, int, int, int, double, hipStream_t, const DataWArgs* wa = nullptr);
+void launch_data_loss(const FrameDev*, int, int, int, double, int, hipStream_t, const DataWArgs* wa = nullptr);
+void launch_data_weights(const FrameDev*, int slot, int N, int K, double lam, const DataWArgs& wa, double* w, hipStream_t);
 void launch_data_resid(const FrameDev*, int, int, int, double, double*, uint8_t*, int32_t*, hipStream_t);
 
 // slm_data_k4.hip

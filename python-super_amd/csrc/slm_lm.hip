@@ -1,7 +1,7 @@
 // slm_lm.hip -- the LM step of the LM host: the dimensions of a batch of bound slots, the choice of the solver's form,
 // the stages of an iteration in the batch's data form (enqueue_*), and the entry points made of them: slm_run, the
 // sharded step with its exchange, the parity entry points (slm_assemble / slm_loss / slm_solve) and the
-// flow-correspondence term.  Host side only orchestrates launches.
+// flow-correspondence term and the per-residual data weights.  Host side only orchestrates launches.
 #include "slm_solver.h"
 
 namespace {
@@ -9,6 +9,8 @@ struct BatchDims {
   int maxN = 0, maxJKe = 0, nt_max = 0, wb_cap = 0, n_reg_part = 0;
   int max_pos = 0, max_blocks = 0, maxP = 0;
   bool corr = false;   // some slot of the batch has correspondences bound (the term's Jacobian pass runs)
+  bool weights = false;   // the solver carries per-residual data weights (slm_enable_data_weights): the weighted kernels run
+  DataWArgs wargs{};      // ... with these arguments (the batch's first semantic descriptor, seg_mode, pp_max)
   int n_acc_part = 0;  // what k_accept sums behind the data partials: the regularisers' pairs, on an enabled solver the term's too
   int K = 0;        // num_neighbors of the batch's slots (-1: they differ -- refused by the callers of the per-surfel kernels)
   int gram_variants = 0;   // bit0: workgroup-merged records in use, bit1: per-run slab in use
@@ -100,6 +102,8 @@ BatchDims dims_of(slm_solver* s, int first, int n, bool band = false) {
   if (s->cfg.use_arap || s->cfg.use_rot)
     d.n_reg_part = std::min(kRegBlocksMax, (d.maxJKe + 255) / 256);
   d.n_acc_part = d.n_reg_part + (s->corr_mode ? kCorrBlocks : 0);
+  d.weights = s->weights_on;
+  d.wargs = DataWArgs{s->w_seg_mode ? s->w_dev.p + first : nullptr, s->w_pp_max, s->w_seg_mode, 0};
   return d;
 }
 }  // namespace
@@ -175,11 +179,11 @@ void enqueue_jacobian(slm_solver* s, const FrameDev* fr, int n, const BatchDims&
       else launch_data_gram(fr, n, d.max_pos, w, d.gram_variants, st, reuse, s->gram_wgs, s->n_cus);
       break;
     case DataForm::pairs:   // per-pair records (zeroed, then filled; the correspondence term adds into them)
-      launch_data_grad_pairs(fr, n, d.maxN, d.K, w, st);
+      launch_data_grad_pairs(fr, n, d.maxN, d.K, w, st, d.weights ? &d.wargs : nullptr);
       if (d.corr) launch_corr_grad_pairs(fr, s->corr_dev + (fr - s->frames_dev), n, d.maxN, d.K, s->corr_mode, s->corr_w, st);
       break;
     case DataForm::per_entry:
-      launch_data_grad(fr, n, d.maxN, d.K, w, st);
+      launch_data_grad(fr, n, d.maxN, d.K, w, st, d.weights ? &d.wargs : nullptr);
       if (d.corr) launch_corr_grad(fr, s->corr_dev + (fr - s->frames_dev), n, d.maxN, d.K, s->corr_mode, s->corr_w, st);
       break;
     case DataForm::none: break;
@@ -212,13 +216,24 @@ void enqueue_scatter(slm_solver* s, const FrameDev* fr, int n, const BatchDims& 
 // pass) or, `at_beta` (slm_loss), k_data_loss at beta for every form.
 void enqueue_data_loss(slm_solver* s, const FrameDev* fr, int n, const BatchDims& d, hipStream_t st, bool at_beta) {
   if (d.form == DataForm::tuple && !at_beta) launch_data_eval(fr, n, kLossBlocks, s->cfg.w_data, 0, st);
-  else if (d.form != DataForm::none) launch_data_loss(fr, n, kLossBlocks, d.K, s->cfg.w_data, at_beta ? 0 : 1, st);
+  else if (d.form != DataForm::none)
+    launch_data_loss(fr, n, kLossBlocks, d.K, s->cfg.w_data, at_beta ? 0 : 1, st, d.weights ? &d.wargs : nullptr);
   // the correspondence term's partials, behind the regularisers' (every slot of an enabled solver: zeros without targets)
   if (s->corr_mode && d.K >= 1)
     launch_corr_loss(fr, s->corr_dev + (fr - s->frames_dev), n, d.K, s->corr_mode, s->corr_w, at_beta ? 0 : 1, 2 * d.n_reg_part,
                      kCorrCntPart, st);
 }
 }  // namespace
+
+// With a semantic weight on, every slot of [first, first + n) needs its semantic inputs: no silent unweighted run.
+static int weights_check(const slm_solver* s, const char* fn, int first, int n) {
+  if (!s->w_seg_mode) return SLM_OK;
+  for (int i = first; i < first + n; ++i)
+    if (!s->slots[i].wdev.has)
+      return fail(SLM_ERR_UNBOUND, std::string(fn) + ": slot " + std::to_string(i) +
+                                       " has no semantic inputs; call slm_bind_data_semantic after slm_bind_frame");
+  return SLM_OK;
+}
 
 extern "C" {
 
@@ -253,9 +268,10 @@ int slm_set_shard(slm_solver* s, int32_t rank, int32_t world) {
   return SLM_OK;
 }
 
-static int shard_dims(slm_solver* s, int n_frames, BatchDims& d) {
+static int shard_dims(slm_solver* s, int n_frames, BatchDims& d, const char* fn = nullptr) {
   int rc = check_slots(s, 0, n_frames);
   if (rc) return rc;
+  if (fn && (rc = weights_check(s, fn, 0, n_frames)) != SLM_OK) return rc;
   d = dims_of(s, 0, n_frames);
   if (!d.nd || (d.form != DataForm::tuple && d.form != DataForm::pairs))
     return fail(SLM_ERR_UNSUPPORTED, "sharded LM step: every slot needs a multifrontal data path (tuple-sorted or K-generic) and the ND solver");
@@ -264,7 +280,7 @@ static int shard_dims(slm_solver* s, int n_frames, BatchDims& d) {
 
 int slm_lm_grad_local(slm_solver* s, int32_t n_frames, void* stream) {
   BatchDims d;
-  int rc = shard_dims(s, n_frames, d);
+  int rc = shard_dims(s, n_frames, d, "slm_lm_grad_local");
   if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
   const FrameDev* fr = s->frames_dev;
@@ -289,7 +305,7 @@ int slm_lm_solve(slm_solver* s, int32_t n_frames, void* stream) {
 
 int slm_lm_loss_local(slm_solver* s, int32_t n_frames, void* stream) {
   BatchDims d;
-  int rc = shard_dims(s, n_frames, d);
+  int rc = shard_dims(s, n_frames, d, "slm_lm_loss_local");
   if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
   const FrameDev* fr = s->frames_dev;
@@ -415,6 +431,7 @@ int slm_run(slm_solver* s, int32_t n_frames, void* stream) {
     return fail(SLM_ERR_UNSUPPORTED,
                 "slm_run: the frame is sharded; drive slm_lm_grad_local / slm_lm_solve / slm_lm_loss_local / "
                 "slm_lm_accept with the exchanges between them");
+  if ((rc = weights_check(s, "slm_run", 0, n_frames)) != SLM_OK) return rc;
   hipStream_t st = (hipStream_t)stream;
   const slm_config& c = s->cfg;
   BatchDims d = dims_of(s, 0, n_frames);
@@ -448,6 +465,7 @@ static int clear_flags(slm_solver* s, int slot, hipStream_t st) {
 int slm_assemble(slm_solver* s, int32_t slot, double* jtj_dense, double* jtl, void* stream) {
   int rc = check_slots(s, slot, 1);
   if (rc) return rc;
+  if ((rc = weights_check(s, "slm_assemble", slot, 1)) != SLM_OK) return rc;
   hipStream_t st = (hipStream_t)stream;
   rc = clear_flags(s, slot, st);
   if (rc) return rc;
@@ -470,6 +488,7 @@ int slm_loss(slm_solver* s, int32_t slot, double* out, void* stream) {
   int rc = check_slots(s, slot, 1);
   if (rc) return rc;
   if (!out) return fail(SLM_ERR_INVALID, "slm_loss: null output");
+  if ((rc = weights_check(s, "slm_loss", slot, 1)) != SLM_OK) return rc;
   hipStream_t st = (hipStream_t)stream;
   rc = clear_flags(s, slot, st);
   if (rc) return rc;
@@ -487,6 +506,7 @@ int slm_solve(slm_solver* s, int32_t slot, double u, double* delta, int32_t* sta
   int rc = check_slots(s, slot, 1);
   if (rc) return rc;
   if (!delta || !(u >= 0.0)) return fail(SLM_ERR_INVALID, "slm_solve: bad argument");
+  if ((rc = weights_check(s, "slm_solve", slot, 1)) != SLM_OK) return rc;
   hipStream_t st = (hipStream_t)stream;
   rc = clear_flags(s, slot, st);
   if (rc) return rc;
@@ -613,6 +633,73 @@ int slm_corr_loss(slm_solver* s, int32_t slot, double* out, void* stream) {
   const int part = 2 * kRegBlocksMax;   // (any place behind the regularisers' pairs: every LM iteration rewrites its own)
   launch_corr_loss(s->frames_dev + slot, s->corr_dev + slot, 1, sp->h.f.K, s->corr_mode, s->corr_w, 0, part, kCorrCntPart, st);
   launch_corr_loss_out(s->frames_dev, slot, part, kCorrCntPart, out, st);
+  HIPCHK(hipGetLastError());
+  return SLM_OK;
+}
+
+
+// ---- per-residual weights of the data term (include/super_lm.h; the weighted kernels in slm_data.hip) -----------------
+int slm_enable_data_weights(slm_solver* s, int32_t seg_mode, double pp_max) {
+  if (!s) return fail(SLM_ERR_INVALID, "slm_enable_data_weights: null argument");
+  if (seg_mode < 0 || seg_mode > 2) return fail(SLM_ERR_INVALID, "slm_enable_data_weights: seg_mode must be 0 (none), 1 (hard) or 2 (soft)");
+  if (!(pp_max - pp_max == 0.0) || pp_max < 0.0) return fail(SLM_ERR_INVALID, "slm_enable_data_weights: pp_max must be finite and >= 0");
+  if (s->cfg.data_path == 1)
+    return fail(SLM_ERR_UNSUPPORTED, "slm_enable_data_weights: needs the pair-record data path (data_path 0 or 2)");
+  if (s->cfg.solver_path == 1)
+    return fail(SLM_ERR_UNSUPPORTED, "slm_enable_data_weights: needs a nested-dissection solver_path (0, 2, 3 or 4)");
+  if (!s->cfg.use_data) return fail(SLM_ERR_UNSUPPORTED, "slm_enable_data_weights: needs the data term (use_data 1)");
+  for (const Slot& sl : s->slots)
+    if (sl.h.bound || sl.prep_ticket || sl.model_ready)
+      return fail(SLM_ERR_INVALID, "slm_enable_data_weights: a slot is already bound; call it after slm_create and before the first bind");
+  const bool on = seg_mode != 0 || pp_max > 0.0;
+  if (on && !s->w_dev) {
+    HIPCHK(s->w_dev.grow(s->slots.size(), s->slots.size()));
+    HIPCHK(hipMemset(s->w_dev, 0, sizeof(DataWeightDev) * s->slots.size()));
+  }
+  s->weights_on = on;
+  s->w_seg_mode = seg_mode;
+  s->w_pp_max = seg_mode ? 0.0 : pp_max;   // (ignored with a semantic weight, like the reference)
+  return SLM_OK;
+}
+
+// the argument checks of the two per-slot entry points; *out = the slot
+static int weights_slot(const char* fn, slm_solver* s, bool args_ok, int32_t slot, Slot** out) {
+  const std::string pre = std::string(fn) + ": ";
+  if (!s || !args_ok) return fail(SLM_ERR_INVALID, pre + "null argument");
+  if (slot < 0 || slot >= (int)s->slots.size()) return fail(SLM_ERR_INVALID, pre + "bad slot");
+  if (!s->weights_on) return fail(SLM_ERR_UNSUPPORTED, pre + "slm_enable_data_weights first");
+  join_prepare(s, slot);
+  if (!s->slots[slot].h.bound) return fail(SLM_ERR_UNBOUND, pre + "slm_bind_frame first");
+  *out = &s->slots[slot];
+  return SLM_OK;
+}
+
+int slm_bind_data_semantic(slm_solver* s, int32_t slot, int32_t num_classes, const int32_t* sf_seg, const float* sf_seg_conf,
+                           const float* tgt_seg_conf, void* stream) {
+  Slot* sp = nullptr;
+  int rc = weights_slot("slm_bind_data_semantic", s, sf_seg != nullptr && sf_seg_conf != nullptr && tgt_seg_conf != nullptr, slot, &sp);
+  if (rc) return rc;
+  if (num_classes < 1 || num_classes > SLM_MAX_CLASSES)
+    return fail(SLM_ERR_UNSUPPORTED, "slm_bind_data_semantic: num_classes must be in 1..SLM_MAX_CLASSES (4)");
+  hipStream_t st = (hipStream_t)stream;
+  sp->wdev.sf_seg = const_cast<int32_t*>(sf_seg);
+  sp->wdev.sf_seg_conf = const_cast<float*>(sf_seg_conf);
+  sp->wdev.tgt_seg_conf = const_cast<float*>(tgt_seg_conf);
+  sp->wdev.C = num_classes;
+  sp->wdev.has = 1;
+  HIPCHK(hipMemcpyAsync(s->w_dev + slot, &sp->wdev, sizeof(DataWeightDev), hipMemcpyHostToDevice, st));
+  HIPCHK(hipStreamSynchronize(st));   // (the source is the slot's own mirror, which the next bind rewrites)
+  return SLM_OK;
+}
+
+int slm_data_weights(slm_solver* s, int32_t slot, double* w_device, void* stream) {
+  Slot* sp = nullptr;
+  int rc = weights_slot("slm_data_weights", s, w_device != nullptr, slot, &sp);
+  if (rc) return rc;
+  if ((rc = weights_check(s, "slm_data_weights", slot, 1)) != SLM_OK) return rc;
+  const FrameDev& h = sp->h;
+  const DataWArgs wa{s->w_seg_mode ? s->w_dev.p : nullptr, s->w_pp_max, s->w_seg_mode, 0};
+  launch_data_weights(s->frames_dev, slot, h.f.N, h.f.K, s->cfg.w_data, wa, w_device, (hipStream_t)stream);
   HIPCHK(hipGetLastError());
   return SLM_OK;
 }

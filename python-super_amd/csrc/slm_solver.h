@@ -1,6 +1,6 @@
 // slm_solver.h -- internal to the LM host (slm_api.hip, slm_bind.hip, slm_lm.hip): what a solver and its slots hold, and
 // the few functions that cross those units.  Device memory is owned by DevBuf / PinnedBuf members (slm_host.h); the
-// descriptors (FrameDev, CorrDev) only mirror addresses.
+// descriptors (FrameDev, CorrDev, DataWeightDev) only mirror addresses.
 #pragma once
 #include <algorithm>
 #include <atomic>
@@ -10,6 +10,7 @@
 
 #include "slm_common.h"
 #include "slm_corr.h"
+#include "slm_data.h"
 #include "slm_host.h"
 #include "slm_launch.h"
 #include "slm_prep.h"
@@ -58,6 +59,7 @@ struct Slot {
   CorrDev corr{};               // correspondence term: host mirror of the slot's targets, which are
   DevBuf<double> corr_o, corr_n;
   DevBuf<uint8_t> corr_valid;
+  DataWeightDev wdev{};         // data weights: host mirror of the slot's semantic inputs (the caller's arrays, none owned)
   PairPlan pplan;               // K-generic pair path (num_neighbors != 4): pair keys, per-surfel pair indices, surfel order
   PlanCache cache;              // nested-dissection plan: host copy; its device mirrors below (grow-only)
   DevBuf<NDDest> d_cur_dests;   // PlanCache::frame_dest on the device
@@ -130,6 +132,10 @@ struct slm_solver {
   int corr_mode = 0;            // slm_enable_corr: 0 off, 1 point-point, 2 point-plane; its weight; the slots' targets on the device
   double corr_w = 0.0;
   DevBuf<CorrDev> corr_dev;
+  bool weights_on = false;      // slm_enable_data_weights: seg_mode != 0 or pp_max > 0; the slots' semantic inputs on the device
+  int w_seg_mode = 0;
+  double w_pp_max = 0.0;
+  DevBuf<DataWeightDev> w_dev;
   bool shard_mode = false;      // slm_set_shard was called (world == 1 included): slots carry the exchange buffers
 };
 

@@ -130,7 +130,7 @@ class LM_Solver():
     """Drop-in for ``super.LM.LM_Solver``; see module docstring."""
 
     def __init__(self, opt, convs=None, max_frames=1, shard_surfels=False, rank=None, world=None,
-                 all_reduce=None, broadcast=None, corr_term=False):
+                 all_reduce=None, broadcast=None, corr_term=False, weighted_data=False):
         """``LM_Solver(opt, convs)`` as in the reference.  ``shard_surfels=True`` (after
         ``torch.distributed.init_process_group``) splits the surfels of ONE large frame over the GPUs
         of a node: every rank evaluates its share, the block-sparse J^T J / J^T r sums and the loss are
@@ -138,8 +138,21 @@ class LM_Solver():
         ``corr_term=True`` (opt-in; needs ``opt.sf_corr``) adds the flow-correspondence term the reference left commented
         out (``super/LM.py:27-29``): weight ``opt.sf_corr_weight``, form ``opt.sf_corr_loss_type``, targets frozen per
         frame from ``LM(..., flow=)`` or ``LM(..., corr_points=)`` (``slm_enable_corr``, include/super_lm.h).  Without it
-        ``opt.sf_corr`` is ignored by this class and nothing changes."""
+        ``opt.sf_corr`` is ignored by this class and nothing changes.
+        ``weighted_data=True`` (opt-in) puts the reference's per-residual weights of the first-order path on the
+        point-to-plane term (``slm_enable_data_weights``, include/super_lm.h): ``opt.sf_soft_seg_point_plane`` /
+        ``opt.sf_hard_seg_point_plane`` (soft wins; the term is then on also without ``opt.sf_point_plane``, whose place the
+        reference gives them) read ``sf.seg``, ``sf.seg_conf`` and ``new_data.seg_conf`` of every frame, and
+        ``opt.depth_model == "raft_stereo"`` truncates at 2e-5.  Without the flag those options are ignored by this class
+        exactly as before."""
         self.opt = opt
+        self.seg_mode, self.pp_max = 0, 0.0
+        if weighted_data:
+            soft = bool(getattr(opt, "sf_soft_seg_point_plane", False))
+            hard = bool(getattr(opt, "sf_hard_seg_point_plane", False))
+            self.seg_mode = 2 if soft else (1 if hard else 0)
+            self.pp_max = 2e-5 if getattr(opt, "depth_model", None) == "raft_stereo" else 0.0
+        self.weighted = bool(self.seg_mode or self.pp_max > 0.0)
         self.corr_mode = 0
         if corr_term:
             if not getattr(opt, "sf_corr", False):
@@ -186,7 +199,7 @@ class LM_Solver():
         c = SlmConfig()
         c.num_iterations = int(o.num_optimize_iterations)
         c.phase_test = 1 if o.phase == "test" else 0
-        c.use_data, c.use_arap, c.use_rot = int(bool(o.sf_point_plane)), int(bool(o.mesh_arap)), \
+        c.use_data, c.use_arap, c.use_rot = int(bool(o.sf_point_plane) or bool(self.seg_mode)), int(bool(o.mesh_arap)), \
             int(bool(o.mesh_rot))
         c.max_frames = self.max_frames
         c.data_path = int(getattr(o, "slm_data_path", 0))
@@ -207,6 +220,8 @@ class LM_Solver():
             h = out
             if self.corr_mode:
                 _lib.check(self.lib.slm_enable_corr(h, self.corr_mode, self.corr_weight), "slm_enable_corr")
+            if self.weighted:
+                _lib.check(self.lib.slm_enable_data_weights(h, self.seg_mode, self.pp_max), "slm_enable_data_weights")
             if self.sharded:
                 _lib.check(self.lib.slm_set_shard(h, self.rank, self.world), "slm_set_shard")
             self._solvers[key] = h
@@ -279,6 +294,39 @@ class LM_Solver():
         _lib.check(self.lib.slm_bind_corr_points(h, slot, _dev_ptr(pts), None if nrm is None else _dev_ptr(nrm),
                                                  _dev_ptr(valid), st), "slm_bind_corr_points")
 
+    def _bind_semantic(self, h, slot, bf, sf, new_data):
+        """The semantic inputs of a bound slot (``weighted_data`` with a semantic weight): ``sf.seg`` (N,), ``sf.seg_conf``
+        (N,C), ``new_data.seg_conf`` (T,C)."""
+        if not self.seg_mode:
+            return
+        dev, N, T = bf.device, bf.c.N, bf.c.T
+        got = {}
+        for name, obj, attr in (("sf.seg", sf, "seg"), ("sf.seg_conf", sf, "seg_conf"), ("new_data.seg_conf", new_data, "seg_conf")):
+            t = getattr(obj, attr, None)
+            if t is None:
+                raise ValueError(f"LM_Solver(weighted_data=True): {name} is missing")
+            got[name] = t
+        sc, tc = got["sf.seg_conf"], got["new_data.seg_conf"]
+        if got["sf.seg"].numel() != N or got["sf.seg"].dim() > 2:
+            raise ValueError(f"LM_Solver(weighted_data=True): sf.seg must be ({N},), got {tuple(got['sf.seg'].shape)}")
+        if sc.dim() != 2 or sc.shape[0] != N or not 1 <= sc.shape[1] <= _lib.SLM_MAX_CLASSES:
+            raise ValueError(f"LM_Solver(weighted_data=True): sf.seg_conf must be ({N}, C) with C in 1..{_lib.SLM_MAX_CLASSES}, "
+                             f"got {tuple(sc.shape)}")
+        if tc.dim() != 2 or tuple(tc.shape) != (T, sc.shape[1]):
+            raise ValueError(f"LM_Solver(weighted_data=True): new_data.seg_conf must be ({T}, {sc.shape[1]}), got {tuple(tc.shape)}")
+        seg = _as(got["sf.seg"].reshape(-1), torch.int32, dev)
+        sc, tc = _as(sc, torch.float32, dev), _as(tc, torch.float32, dev)
+        bf.sem_keep = (seg, sc, tc)                    # read in place by the library while the slot is used
+        _lib.check(self.lib.slm_bind_data_semantic(h, slot, int(sc.shape[1]), _dev_ptr(seg), _dev_ptr(sc), _dev_ptr(tc),
+                                                   _stream_ptr(dev)), "slm_bind_data_semantic")
+
+    def data_weights(self, slot=0, u=10, v=7.5, minimal_loss=1e10):
+        """The weights w_i (N,) float64 of a bound slot at its current beta, 0 for unmatched surfels (``weighted_data``)."""
+        h, bf = self._handle(u, v, minimal_loss), self._bound[slot]
+        w = torch.empty(bf.c.N, dtype=torch.float64, device=bf.device)
+        _lib.check(self.lib.slm_data_weights(h, slot, _dev_ptr(w), _stream_ptr(bf.device)), "slm_data_weights")
+        return w
+
     def corr_targets(self, slot=0, u=10, v=7.5, minimal_loss=1e10):
         """The bound targets of a slot: (pts (N,3) f64, nrm (N,3) f64, valid (N,) bool) on the device."""
         h, bf = self._handle(u, v, minimal_loss), self._bound[slot]
@@ -344,6 +392,7 @@ class LM_Solver():
         h = self._handle()
         bf = self._bind(h, 0, sf, inputs, new_data)
         self._bind_corr(h, 0, bf, self._corr_arg(flow, corr_points, required=True))
+        self._bind_semantic(h, 0, bf, sf, new_data)
         st = _stream_ptr(bf.device)
         b64 = _as(beta, torch.float64, bf.device)
         _lib.check(self.lib.slm_set_beta(h, 0, _dev_ptr(b64), st), "slm_set_beta")
@@ -391,6 +440,7 @@ class LM_Solver():
         bfs = self._bind_batch(h, frames) if n > 1 else [self._bind(h, 0, *frames[0])]
         for i, (bf, corr) in enumerate(zip(bfs, corrs)):
             self._bind_corr(h, i, bf, corr)
+            self._bind_semantic(h, i, bf, frames[i][0], frames[i][2])
         dev = bfs[0].device
         st = _stream_ptr(dev)
         if self.sharded:
