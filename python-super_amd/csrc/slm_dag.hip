@@ -47,6 +47,24 @@
 #include <atomic>
 #include <cstdlib>
 
+#include <hip/hip_runtime.h>
+
+// The thread index of THIS file -- the tile helpers of slm_tile.h as compiled here included -- passes through an empty asm.
+// Every task kind is compiled into k_fdag's ticket loop.  Whatever depends on the lane alone (LDS addresses, tile offsets,
+// the lane masks of the factorisation) does not change from ticket to ticket, so the
+// compiler forms all of it once in front of the loop and keeps it across -- 256 VGPRs, 177 of them spilled, 254 scratch loads
+// inside the tasks.  Behind the asm these are values of the task that uses them: the asm is not `volatile`, so equal copies
+// inside a task are still merged, but it is not speculated out of a branch of the loop that need not run.  With it k_fdag
+// takes 232 VGPRs and no scratch memory (docs/LAB_NOTEBOOK.md, "k_fdag: the task kinds in the ticket loop").
+struct DagThreadIdx { unsigned x; };
+__device__ __forceinline__ DagThreadIdx dag_thread_idx() {
+  unsigned t = __builtin_amdgcn_workitem_id_x();
+  asm("" : "+v"(t));
+  __builtin_assume(t < 256u);   // (every kernel of this file is launched with at most 256 threads)
+  return DagThreadIdx{t};
+}
+#define threadIdx dag_thread_idx()
+
 #include "slm_tile.h"
 #include "slm_lane.h"
 #include "slm_launch.h"
@@ -272,11 +290,16 @@ __device__ __forceinline__ void store_tile_lds2(double* L, const double r[16]) {
 //   Stage 0 = everything but the last operand column (and the diagonal factor): what the task needs to START.
 // BACKB(f,c): [x of the parent's column 0]
 // BACK(f,c):  [y_c][boundary part subtracted (fronts with a boundary)][L(r,c), c < r < npt] | chain: x_r, r = npt-1 .. c+1
+// (One TDKid per child, as two NAMED members: arrays indexed by the child number are indexed by a variable once the
+//  compiler has merged the two children's paths of dep_flag, and then the whole TD lives in scratch memory.)
+struct TDKid {
+  int np, pr0, pc0, pnc;                 // gathered child tiles: count, first tile row / column, columns
+  int np2, pc2, pnc2;                    // POTRF(s > 0): the same for its second tile (s, s-1) (same tile rows)
+  int ctile0, cnt, cnpt;                 // the child's tile numbering
+};
 struct TD {
   int type, r, s, kc, diag;
-  int np[2], pr0[2], pc0[2], pnc[2];     // gathered child tiles: count, first tile row / column, columns
-  int np2[2], pc2[2], pnc2[2];           // POTRF(s > 0): the same for its second tile (s, s-1) (same tile rows)
-  int ctile0[2], cnt[2], cnpt[2];        // the children's tile numbering
+  TDKid k0, k1;
   int n0, n, nskip;                      // flags needed to start / all flags / leading flags that need no wait
   int pcol_self, pcol_parent, nb, npt, c;
 };
@@ -287,30 +310,31 @@ __device__ __forceinline__ void task_deps(TD& d, const SS& fd, const FS& f, int 
   d.type = type; d.r = r; d.s = s; d.diag = (r == s); d.npt = f.npt; d.nb = f.nb; d.c = s;
   d.pcol_self = f.pcol0;
   d.pcol_parent = 0;
-  d.np[0] = d.np[1] = 0;
+  d.k0.np = d.k1.np = 0;
   d.kc = 0;
-  d.np2[0] = d.np2[1] = 0;
+  d.k0.np2 = d.k1.np2 = 0;
   d.nskip = 0;
   if (type <= ND_T_SCHUR) {
     const int32_t* pr = fd.prng + uni(fd.prng_off[fi]);
     const bool two = type == ND_T_POTRF && s > 0;
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
+    auto kid = [&](int k, TDKid& o) {
       const int ch = uni(fd.front_kids[2 * fi + k]);
       const int rr = ch >= 0 ? uni(pr[2 * r + k]) : -1, cc = ch >= 0 ? uni(pr[2 * s + k]) : -1;
       const int c2 = (ch >= 0 && two) ? uni(pr[2 * (s - 1) + k]) : -1;
-      d.pr0[k] = d.pc0[k] = d.pc2[k] = 0; d.pnc[k] = d.pnc2[k] = 1; d.ctile0[k] = d.cnt[k] = d.cnpt[k] = 0;
+      o.pr0 = o.pc0 = o.pc2 = 0; o.pnc = o.pnc2 = 1; o.ctile0 = o.cnt = o.cnpt = 0;
       if (rr >= 0 && (cc >= 0 || c2 >= 0)) {
         const NDFront& cf = fd.fronts[ch];
-        d.ctile0[k] = uni(cf.tile_first); d.cnt[k] = uni(cf.nt); d.cnpt[k] = uni(cf.npt);
-        d.pr0[k] = rr & 255;
+        o.ctile0 = uni(cf.tile_first); o.cnt = uni(cf.nt); o.cnpt = uni(cf.npt);
+        o.pr0 = rr & 255;
         const int nr = (rr >> 8) - (rr & 255) + 1;
-        if (cc >= 0) { d.pc0[k] = cc & 255; d.pnc[k] = (cc >> 8) - (cc & 255) + 1; d.np[k] = nr * d.pnc[k]; }
-        if (c2 >= 0) { d.pc2[k] = c2 & 255; d.pnc2[k] = (c2 >> 8) - (c2 & 255) + 1; d.np2[k] = nr * d.pnc2[k]; }
+        if (cc >= 0) { o.pc0 = cc & 255; o.pnc = (cc >> 8) - (cc & 255) + 1; o.np = nr * o.pnc; }
+        if (c2 >= 0) { o.pc2 = c2 & 255; o.pnc2 = (c2 >> 8) - (c2 & 255) + 1; o.np2 = nr * o.pnc2; }
       }
-    }
+    };
+    kid(0, d.k0);
+    kid(1, d.k1);
     d.kc = type == ND_T_SCHUR ? f.npt : s;
-    const int npull = d.np[0] + d.np[1] + d.np2[0] + d.np2[1];
+    const int npull = d.k0.np + d.k1.np + d.k0.np2 + d.k1.np2;
     d.n0 = npull;                 // to start: the children's update tiles; the operand columns are consumed as they come
     if (kids_done) d.nskip = npull;
     if (type == ND_T_POTRF)       // per column c < s-1: L(s,c), y_c, L(s-1,c); then 4 slots for the 16-pivot rounds of (s-1,s-1)
@@ -331,28 +355,23 @@ __device__ __forceinline__ void task_deps(TD& d, const SS& fd, const FS& f, int 
     d.n0 = d.n = f.npt + (f.nb > 0 ? (fusedf ? 1 : f.npt) : 0) + f.npt * (f.npt - 1) / 2;
   }
 }
+// the flag of gathered child tile i: pc0 / pnc = the first column and the column count of the gathered range
+__device__ __forceinline__ const int* kid_flag(const TDKid& k, const DagFlags& g, int pc0, int pnc, int i) {
+  const int cr = k.cnpt + k.pr0 + i / pnc;
+  int cc = k.cnpt + pc0 + i % pnc;
+  if (cc > cr) cc = cr;            // lower triangle only (a duplicate flag in the list is harmless)
+  return g.tile + k.ctile0 + cc * k.cnt - cc * (cc - 1) / 2 + (cr - cc);
+}
 __device__ __forceinline__ const int* dep_flag(const TD& d, const FS& f, const DagFlags& g, int i) {
   if (d.type <= ND_T_SCHUR) {
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      if (i < d.np[k]) {
-        const int cr = d.cnpt[k] + d.pr0[k] + i / d.pnc[k];
-        int cc = d.cnpt[k] + d.pc0[k] + i % d.pnc[k];
-        if (cc > cr) cc = cr;            // lower triangle only (a duplicate flag in the list is harmless)
-        return g.tile + d.ctile0[k] + cc * d.cnt[k] - cc * (cc - 1) / 2 + (cr - cc);
-      }
-      i -= d.np[k];
-    }
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      if (i < d.np2[k]) {
-        const int cr = d.cnpt[k] + d.pr0[k] + i / d.pnc2[k];
-        int cc = d.cnpt[k] + d.pc2[k] + i % d.pnc2[k];
-        if (cc > cr) cc = cr;
-        return g.tile + d.ctile0[k] + cc * d.cnt[k] - cc * (cc - 1) / 2 + (cr - cc);
-      }
-      i -= d.np2[k];
-    }
+    if (i < d.k0.np) return kid_flag(d.k0, g, d.k0.pc0, d.k0.pnc, i);
+    i -= d.k0.np;
+    if (i < d.k1.np) return kid_flag(d.k1, g, d.k1.pc0, d.k1.pnc, i);
+    i -= d.k1.np;
+    if (i < d.k0.np2) return kid_flag(d.k0, g, d.k0.pc2, d.k0.pnc2, i);
+    i -= d.k0.np2;
+    if (i < d.k1.np2) return kid_flag(d.k1, g, d.k1.pc2, d.k1.pnc2, i);
+    i -= d.k1.np2;
     if (d.type == ND_T_POTRF) {
       const int s = d.s;
       if (i < 3 * (s - 1)) {
@@ -439,13 +458,13 @@ __device__ __forceinline__ int dag_wait_prefix(const TD& d, const FS& f, const D
 // .x = the child's boundary scalar that maps there (-1: none), .y = the BYTE offset of that row (resp. column) inside the
 // child's update block -- an entry's address is block + row offset + column offset (one add per gather instead of the
 // tile arithmetic: 1 KB of code per pulled tile instead of 5).  Static plan data, written before the task's wait.
-__device__ __forceinline__ void dag_pull_maps(const SS& fd, int fi, int r, int s, const int np[2], int2* maps) {
+__device__ __forceinline__ void dag_pull_maps(const SS& fd, int fi, int r, int s, int np0, int np1, int2* maps) {
   const int l = threadIdx.x & 63, w = threadIdx.x >> 6;
-  if (np[0] == 0 && np[1] == 0) return;
+  if (np0 == 0 && np1 == 0) return;
   __syncthreads();   // earlier readers of maps are done
 #pragma unroll
   for (int k = 0; k < 2; ++k) {
-    if (np[k] == 0) continue;
+    if ((k == 0 ? np0 : np1) == 0) continue;
     const int ch = uni(fd.front_kids[2 * fi + k]);
     const int32_t* pm = fd.pullmap + uni(fd.pull_off[ch]);
     const int cnpt = uni(fd.fronts[ch].npt), cnt = uni(fd.fronts[ch].nt);
@@ -463,19 +482,19 @@ __device__ __forceinline__ void dag_pull_maps(const SS& fd, int fi, int r, int s
 }
 
 template <bool VEC>
-__device__ __forceinline__ void dag_pull(const SS& fd, int fi, int r, int s, double4_t acc[4], double& bvec, const int np[2],
+__device__ __forceinline__ void dag_pull(const SS& fd, int fi, int r, int s, double4_t acc[4], double& bvec, int np0, int np1,
                                          int2* maps, bool maps_loaded = false) {
   const int l = threadIdx.x & 63, w = threadIdx.x >> 6, lr = l & 15, lk = l >> 4;
-  if (np[0] == 0 && np[1] == 0) return;
+  if (np0 == 0 && np1 == 0) return;
   // both children's maps first (or already in LDS: dag_pull_maps before the task's wait), then ALL gathers in flight
   // together (scattered 8-byte sc1 loads: one latency instead of two), then the sums in the fixed order child 0, child 1
-  if (!maps_loaded) dag_pull_maps(fd, fi, r, s, np, maps);
+  if (!maps_loaded) dag_pull_maps(fd, fi, r, s, np0, np1, maps);
   double v[2][16], bv[2] = {0.0, 0.0};
 #pragma unroll
   for (int k = 0; k < 2; ++k) {
 #pragma unroll
     for (int e = 0; e < 16; ++e) v[k][e] = 0.0;
-    if (np[k] == 0) continue;
+    if ((k == 0 ? np0 : np1) == 0) continue;
     const int ch = uni(fd.front_kids[2 * fi + k]);
     const long long cbase = uni64(fd.fronts[ch].f22_base);   // the child's update tiles live in its boundary block
     const char* ct = reinterpret_cast<const char*>(fd.ftiles + cbase);
@@ -626,9 +645,8 @@ __device__ __forceinline__ double dag_reduce_rows(double tsum, double* part /* 4
 // extend-add maps share the diagonal-block inverses: neither is live while a tile is being factored.
 extern __shared__ double dag_lds[];
 
-// Tile factorisation + inverse as a real call: inlined into the task loop it raises the register demand of the
-// whole kernel beyond 256 VGPRs (every path pays the maximum).  The LDS regions are derived from the dynamic LDS
-// base inside the function, so their address space stays known.
+// Tile factorisation + inverse.  The LDS regions are derived from the dynamic LDS base inside the function, so their
+// address space stays known.
 // look_ahead: wave 0 has staged the first diagonal block at dinv + 256 (ld 16) and the waves' row partials lie in wt
 // (factor_inverse64p's look-ahead entry); *la_sum receives their sums (threads < NB)
 __device__ __forceinline__ bool dag_factor_tile(double* g_mail, int* g_early, long long* trc, int nblk, bool look_ahead = false,
@@ -656,8 +674,8 @@ __device__ __forceinline__ void dag_mark(long long* trc, int k) {
 }
 __device__ __forceinline__ void dag_ready(long long* trc) { dag_mark(trc, 1); }
 __device__ __forceinline__ void dag_end(long long* trc) { dag_mark(trc, 2); }
-// A task re-derives its descriptors from (slot, ticket) itself.  TYPE: the kind where the caller's instantiation fixes it
-// (dag_task_factor: the dependency list folds), -1: from the task word.
+// A task re-derives its descriptors from (slot, ticket) itself.  TYPE: the kind, fixed by every caller (the dependency list
+// folds to the kind's part), -1: from the task word.
 // d, the task's dependency list, is a local of the task and not a member of DagTask: its small arrays are indexed in loops,
 // and one such member keeps the WHOLE struct in scratch memory (+360..408 bytes per lane in four of the five task functions:
 // the same notebook table).
@@ -768,13 +786,19 @@ __device__ __forceinline__ bool mail_here(double v) { return __double_as_longlon
 // the narrow top of the tree idle until their turn, and every operand tile is fetched from L2 / MALL by the task
 // that needs it.  Larger batches are bandwidth- and occupancy-bound and run the per-level launches of
 // slm_front.hip (XCD-aware work lists, operands shared through L2) -- slm_api.hip picks.
-// ---- the tasks.  Each kind is a function of its own (a real call): inlined into one loop, every path pays the
-// register demand of all of them, and the tile factorisation -- the critical path -- ends up spilling.
+// ---- the tasks.  Each kind is a function of its own in the source and ALL are compiled into the ticket loop.  As calls
+// (through round 7) the four large kinds saved and restored the callee-saved registers they use on every task -- 56 to 121
+// scratch stores per lane in front of a task's first request and as many loads behind its last store, the POTRF chain
+// included -- and three of them kept their dependency list in scratch memory.  Inlined as they were, every path paid for
+// the lane-only values of all kinds (round 2's loss); with the thread index of this file opaque per task (top of the file)
+// the loop takes 232 VGPRs, no scratch memory and no stack.
 // A task re-derives its descriptors from (ticket) itself (dag_task_begin); LDS regions come from the dynamic LDS base.
-// (DIAG: the POTRF tasks and the COL tasks are instantiations of their own -- 85 KB of code as one function, more than the
+// Each kind fixes its TYPE for dag_task_begin: with the kind read from the task word the dependency list does not fold
+// and stays in scratch memory.
+// (DIAG: the POTRF tasks and the COL tasks are instantiations of their own -- 85 KB of code as one body, more than the
 //  instruction cache two CUs share; the pivot chain runs through the smaller one)
 template <bool DIAG>
-__device__ __noinline__ void dag_task_factor(const FrameDev* __restrict__ frames, int slot, int ti, double u_override, int cut, int mode) {
+__device__ __forceinline__ void dag_task_factor(const FrameDev* __restrict__ frames, int slot, int ti, double u_override, int cut, int mode) {
   const int l = threadIdx.x & 63, w = threadIdx.x >> 6, lr = l & 15, lk = l >> 4;
   TD d;
   const DagTask tk = dag_task_begin<DIAG ? ND_T_POTRF : ND_T_COL>(frames, slot, ti, cut, mode, d);
@@ -796,7 +820,7 @@ __device__ __noinline__ void dag_task_factor(const FrameDev* __restrict__ frames
     dag_zero_pure_fill(tile_kind, f, tr_, ts_, acc);
     double bvec = 0.0, tsum = 0.0;
     if (type == ND_T_POTRF && threadIdx.x < NB) bvec = ld1(vecs + (size_t)ts_ * NB + threadIdx.x);
-    dag_pull_maps(fd, fi, tr_, ts_, d.np, maps);   // (static plan data: also before the wait)
+    dag_pull_maps(fd, fi, tr_, ts_, d.k0.np, d.k1.np, maps);   // (static plan data: also before the wait)
     // stage 0: what the task needs to start
     if (!dag_wait_deps(d, f, g, d.nskip, d.n0, abort_flag, s_abort)) return;
 
@@ -807,8 +831,8 @@ __device__ __noinline__ void dag_task_factor(const FrameDev* __restrict__ frames
       const double u = (u_override >= 0.0 || !diag) ? u_override : lmst->u;   // requested now, used after the updates
       // (stage 0: the children's update tiles and the operand columns c < s-1)
       // the children's contributions to this tile (and to the vector rows of a diagonal tile)
-      if (diag) dag_pull<true>(fd, fi, r, s, acc, bvec, d.np, maps, true);
-      else dag_pull<false>(fd, fi, r, s, acc, bvec, d.np, maps, true);
+      if (diag) dag_pull<true>(fd, fi, r, s, acc, bvec, d.k0.np, d.k1.np, maps, true);
+      else dag_pull<false>(fd, fi, r, s, acc, bvec, d.k0.np, d.k1.np, maps, true);
       double4_t xl[4];   // POTRF(s > 0): L(s, s-1), rows of this wave (for its product with y_{s-1} after the factorisation)
       if (diag && s > 0) {
         // POTRF(s) owns the tile (s, s-1) too: L(s,s-1) = (A(s,s-1) - sum_{c<s-1} L(s,c) L(s-1,c)^T) L_{s-1,s-1}^-T is
@@ -817,7 +841,7 @@ __device__ __noinline__ void dag_task_factor(const FrameDev* __restrict__ frames
         load_c_frags1(tile_ptr(fd, f, s, s - 1), accl);
         dag_zero_pure_fill(tile_kind, f, s, s - 1, accl);
         double dummy = 0.0;
-        dag_pull<false>(fd, fi, s, s - 1, accl, dummy, d.np2, maps);
+        dag_pull<false>(fd, fi, s, s - 1, accl, dummy, d.k0.np2, d.k1.np2, maps);
         {
           // columns c < s-2: both tiles at once, as the columns come.  The last column, c = s-2, is split: its L(s-1,c)
           // is the tile POTRF(s-1) itself produces (out only when that task starts factoring), so everything that
@@ -1058,9 +1082,9 @@ __device__ __noinline__ void dag_task_factor(const FrameDev* __restrict__ frames
   }
 }
 
-__device__ __noinline__ void dag_task_schur(const FrameDev* __restrict__ frames, int slot, int ti, double u_override, int cut, int mode) {
+__device__ __forceinline__ void dag_task_schur(const FrameDev* __restrict__ frames, int slot, int ti, double u_override, int cut, int mode) {
   TD d;
-  const DagTask tk = dag_task_begin(frames, slot, ti, cut, mode, d);
+  const DagTask tk = dag_task_begin<ND_T_SCHUR>(frames, slot, ti, cut, mode, d);
   const SS& fd = tk.fd; const FS& f = tk.f; const DagFlags& g = tk.g;
   const int fi = tk.fi, tr_ = tk.tr_, ts_ = tk.ts_;
   double *S = DagLds::S(dag_lds), *M = DagLds::M(dag_lds), *yv = DagLds::vec2(dag_lds), *part = DagLds::part(dag_lds);
@@ -1075,7 +1099,7 @@ __device__ __noinline__ void dag_task_schur(const FrameDev* __restrict__ frames,
     for (int ni = 0; ni < 4; ++ni) acc[ni] = double4_t{0.0, 0.0, 0.0, 0.0};
     double bvec = 0.0, tsum = 0.0;
     if (tr_ == ts_ && threadIdx.x < NB) bvec = ld1(vecs + (size_t)tr_ * NB + threadIdx.x);
-    dag_pull_maps(fd, fi, tr_, ts_, d.np, maps);
+    dag_pull_maps(fd, fi, tr_, ts_, d.k0.np, d.k1.np, maps);
     // stage 0: what the task needs to start
     if (!dag_wait_deps(d, f, g, d.nskip, d.n0, abort_flag, s_abort)) return;
 
@@ -1083,8 +1107,8 @@ __device__ __noinline__ void dag_task_schur(const FrameDev* __restrict__ frames,
       // ================= SCHUR(f,r,s): update tile of the boundary block, stored in place =============
       const int r = tr_, sc = ts_;
       const bool dg = r == sc;
-      if (dg) dag_pull<true>(fd, fi, r, sc, acc, bvec, d.np, maps, true);
-      else dag_pull<false>(fd, fi, r, sc, acc, bvec, d.np, maps, true);
+      if (dg) dag_pull<true>(fd, fi, r, sc, acc, bvec, d.k0.np, d.k1.np, maps, true);
+      else dag_pull<false>(fd, fi, r, sc, acc, bvec, d.k0.np, d.k1.np, maps, true);
       {
         int c = 0, m = 1;
         while (c < f.npt && m > 0) {
@@ -1109,10 +1133,10 @@ __device__ __noinline__ void dag_task_schur(const FrameDev* __restrict__ frames,
   }
 }
 
-__device__ __noinline__ void dag_task_backb(const FrameDev* __restrict__ frames, int slot, int ti, double u_override, int cut, int mode) {
+__device__ __forceinline__ void dag_task_backb(const FrameDev* __restrict__ frames, int slot, int ti, double u_override, int cut, int mode) {
   const int l = threadIdx.x & 63, w = threadIdx.x >> 6;
   TD d;
-  const DagTask tk = dag_task_begin(frames, slot, ti, cut, mode, d);
+  const DagTask tk = dag_task_begin<ND_T_BACKB>(frames, slot, ti, cut, mode, d);
   const SS& fd = tk.fd; const FS& f = tk.f; const DagFlags& g = tk.g;
   const int fi = tk.fi, ts_ = tk.ts_;
   double* S = DagLds::S(dag_lds);
@@ -1181,10 +1205,10 @@ __device__ __noinline__ void dag_task_backb(const FrameDev* __restrict__ frames,
   }
 }
 
-__device__ __noinline__ void dag_task_back(const FrameDev* __restrict__ frames, int slot, int ti, double u_override, int cut, int mode) {
+__device__ __forceinline__ void dag_task_back(const FrameDev* __restrict__ frames, int slot, int ti, double u_override, int cut, int mode) {
   const int l = threadIdx.x & 63, w = threadIdx.x >> 6;
   TD d;
-  const DagTask tk = dag_task_begin(frames, slot, ti, cut, mode, d);
+  const DagTask tk = dag_task_begin<ND_T_BACK>(frames, slot, ti, cut, mode, d);
   const SS& fd = tk.fd; const FS& f = tk.f; const DagFlags& g = tk.g;
   const int fi = tk.fi, ts_ = tk.ts_;
   double *S = DagLds::S(dag_lds), *M = DagLds::M(dag_lds);
@@ -1481,8 +1505,8 @@ int dag_last_mode() { return g_last_dag_mode.load(std::memory_order_relaxed); }
 
 // (TWO workgroups per CU since round 5 -- 248 VGPRs, 2 x 81 088 B of LDS: the bottom of the tree and the Schur tasks of a
 //  batch are short of workgroups, not of registers: C2 one frame per launch 0.830 -> 0.804 ms per LM iteration, eight frames
-//  2.462 -> 2.445; the build limited to 256 registers is itself 1 % faster at one workgroup per CU -- less scratch in the
-//  task functions' prologues.  Tickets make any grid size deadlock-free)
+//  2.462 -> 2.445; the build limited to 256 registers is itself 1 % faster at one workgroup per CU.  Tickets make any grid
+//  size deadlock-free)
 // Returns the launch's mode word (bit 0: XCD-affine ticket streams), -1 when nothing was launched.
 int launch_front_solve_dag(const FrameDev* fr, int n_frames, int max_tasks, double u_override, hipStream_t st, int cut, bool reset, bool check) {
   if (max_tasks <= 0) return -1;
