@@ -339,6 +339,58 @@ int slm_bind_data_semantic(slm_solver* s, int32_t slot, int32_t num_classes, con
                            const float* tgt_seg_conf, void* stream);
 int slm_data_weights(slm_solver* s, int32_t slot, double* w_device, void* stream);
 
+/* -- triangle-area face term of the LM path (opt.mesh_face; the reference has only the first-order form,
+ * super/deform_mesh.py:51-60, which slm_gf_config.use_face carries) ---------------------------------------------------
+ * Opt-in.  Per triangle t of the slot's mesh with node ids (i0, i1, i2): v_a = g_a + beta[i_a, 4:7] (node position plus
+ * translation; rotations do not enter, and the LM path has no global row), e1 = v1 - v0, e2 = v2 - v0, c = e1 x e2,
+ * A = sqrt(|c|^2 + 1e-13) / 2 and
+ *   r_t = lambda (A - A0_t),   one row with nine non-zeros on the columns 7 i_a + 4..6:
+ *   dA/dv1 = (e2 x c) / 4A,  dA/dv2 = (c x e1) / 4A,  dA/dv0 = -(dA/dv1 + dA/dv2)
+ * A0_t is the caller's area, taken as given.  The constant keeps a degenerate triangle finite (A >= 1.58e-7, gradient 0).
+ * lambda = weight multiplies the RESIDUAL, as for every LM term: loss = sum_t r_t^2 = lambda^2 sum (A - A0)^2.  GraphFit
+ * multiplies the squared sum by its weight instead, so slm_gf_config.w_face = lambda^2 gives the same objective.  The loss
+ * at the trial point is part of the iteration's loss (accept / reject, slm_iter_record.loss); M_grad / M_loss stay the ICP
+ * match counts.  All arithmetic is float64.  The six node pairs of a triangle are in general neither surfel-KNN pairs nor
+ * node-KNN edges: the bind adds them to the frame's coupled pairs (slm_get_plan_info [7] counts them), so the cached
+ * symbolic plan is rebuilt when a mesh brings new pairs.
+ *
+ * slm_enable_face: after slm_create, before the first bind.  A weight of 0 switches the option off again.  An enabled
+ * solver takes the pair-record form of the data term for every num_neighbors, 4 included (as slm_enable_corr and
+ * slm_enable_data_weights, with which it may be combined).  Refusals:
+ *   SLM_ERR_INVALID      "slm_enable_face: null argument"
+ *                        "slm_enable_face: weight must be finite"
+ *                        "slm_enable_face: a slot is already bound; call it after slm_create and before the first bind"
+ *   SLM_ERR_UNSUPPORTED  "slm_enable_face: needs the pair-record data path (data_path 0 or 2)"
+ *                        "slm_enable_face: needs a nested-dissection solver_path (0, 2, 3 or 4)"
+ *                        "slm_enable_face: needs the data term (use_data 1)"
+ *                        "slm_enable_face: the solver is sharded (slm_set_shard); the term's mesh is not sharded"
+ *   and, on an enabled solver,
+ *   SLM_ERR_UNSUPPORTED  "slm_set_shard: the face term is enabled (slm_enable_face); its mesh is not sharded"
+ *                        "slm_bind_frame: the face term (slm_enable_face) needs J < 65536"
+ *
+ * slm_set_face_mesh: after slm_enable_face, before the slot's slm_bind_frame / slm_bind_frames / slm_prepare_model.  tri is
+ * device (3, F) int32 (row a = vertex a of every triangle), areas device (F) float64; both are COPIED on `stream` into
+ * buffers the slot owns, because the mesh outlives a frame: it stays with the slot over later binds until replaced.
+ * n_triangles = 0 clears it (tri / areas may then be null), and a slot without a mesh runs without the term.  The call
+ * leaves the slot unbound and drops a model prepared ahead: bind again.  A frame without surfels (N = 0) runs without the
+ * term.  Refusals:
+ *   SLM_ERR_INVALID      "slm_set_face_mesh: null argument"   "slm_set_face_mesh: bad slot"
+ *                        "slm_set_face_mesh: n_triangles must be >= 0"
+ *   SLM_ERR_UNSUPPORTED  "slm_set_face_mesh: slm_enable_face first"
+ * The ids are checked where J is known: a bind or a prepared model whose mesh has an id outside [0, J), or a triangle that
+ * repeats an id, is refused, the slot stays unbound and nothing is read out of bounds:
+ *   SLM_ERR_INVALID      "slm_bind_frame: a triangle of the slot's face mesh (slm_set_face_mesh) has a node id outside [0, J) or repeats an id"
+ *
+ * slm_face_loss: out_device[0] = sum_t r_t^2 at the slot's current beta, [1] = the triangle count; {0, 0} for a slot
+ * without a mesh.  The diagnostic twin of slm_corr_loss.  Refusals:
+ *   SLM_ERR_INVALID      "slm_face_loss: null argument"   "slm_face_loss: bad slot"
+ *   SLM_ERR_UNSUPPORTED  "slm_face_loss: slm_enable_face first"
+ *   SLM_ERR_UNBOUND      "slm_face_loss: slm_bind_frame first"
+ * Not built: the term on the tuple-sorted MFMA assembly, on sharded frames and for J >= 65536. */
+int slm_enable_face(slm_solver* s, double weight);
+int slm_set_face_mesh(slm_solver* s, int32_t slot, int32_t n_triangles, const int32_t* tri, const double* areas, void* stream);
+int slm_face_loss(slm_solver* s, int32_t slot, double* out_device, void* stream);
+
 /* -- phase timing (bench.py roofline leg) ----------------------------------------- */
 /* With profiling on, slm_run brackets each phase of every LM iteration with HIP events
  * recorded on the launch stream.  Phases: */

@@ -235,7 +235,7 @@ int slm_destroy(slm_solver* s) {
       if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : s->ev_pool) (void)hipEventDestroy(e);
   if (s->drain_event) (void)hipEventDestroy(s->drain_event);
-  delete s;   // (the solver's own arrays: frames_dev, bw_dev, bw_host, reuse_dev, corr_dev)
+  delete s;   // (the solver's own arrays: frames_dev, bw_dev, bw_host, reuse_dev, corr_dev, face_dev)
   return SLM_OK;
 }
 

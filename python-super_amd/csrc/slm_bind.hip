@@ -12,6 +12,8 @@
 // what the reference could never have been given (its KNN ids come from a top-k: distinct and inside [0, J))
 static const char* const kBadKnn =
     "slm_bind_frame: a KNN index (sf_knn_idx or ed_knn_idx) lies outside [0, J) or a surfel's row of sf_knn_idx repeats an id";
+static const char* const kBadFace =
+    "slm_bind_frame: a triangle of the slot's face mesh (slm_set_face_mesh) has a node id outside [0, J) or repeats an id";
 
 // a frame's form, decided at bind (a plan that comes out empty leaves the slot per_entry: bind_model_part)
 // corr: the solver carries the correspondence term (slm_enable_corr), which adds into the pair records, or the per-residual
@@ -30,6 +32,7 @@ int ensure_band(slm_solver* s, int slot, hipStream_t st) {
   if (sl.band_ready) return SLM_OK;
   FrameDev& h = sl.h;
   launch_bandwidth(h.f, s->bw_dev, st);
+  if (s->face_on && sl.face.ready) launch_face_bandwidth(sl.face.tri, sl.face.n_tri, s->bw_dev, st);   // (ids checked by the bind)
   HIPCHK(hipMemcpyAsync(s->bw_host.data(), s->bw_dev, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   if (s->bw_host[1]) return fail(SLM_ERR_INVALID, kBadKnn);
@@ -87,6 +90,8 @@ static int check_model_args(const slm_solver* s, int32_t slot, const slm_frame* 
     return fail(SLM_ERR_UNSUPPORTED, "slm_bind_frame: the correspondence term (slm_enable_corr) needs J < 65536");
   if (s->weights_on && f->J >= 65536)   // (the same: the weighted kernels are those of the pair form)
     return fail(SLM_ERR_UNSUPPORTED, "slm_bind_frame: the data weights (slm_enable_data_weights) need J < 65536");
+  if (s->face_on && f->J >= 65536)   // (the same: the term adds into the pair records)
+    return fail(SLM_ERR_UNSUPPORTED, "slm_bind_frame: the face term (slm_enable_face) needs J < 65536");
   if (f->N > 0 && f->J < f->K)   // (the reference's top-k of K among J nodes raises; the device checks below assume J >= K)
     return fail(SLM_ERR_INVALID, "slm_bind_frame: fewer nodes (J) than num_neighbors: sf_knn_idx cannot hold K distinct ids");
   if ((f->N > 0 && (!f->sf_points || !f->sf_knn_idx || !f->sf_knn_w)) || !f->ed_points || !f->ed_knn_idx)
@@ -122,8 +127,8 @@ static int reset_slot(slm_solver* s, Slot& sl, const slm_frame* f, hipStream_t s
   h.rhs = sl.rhs.p;
   // the buffers of one size for good: allocated by the slot's first bind (st, dbg and rec exactly, outside the counters)
   if (!sl.loss_part) {
-    HIPCHK(grow(sl.loss_part, kLossPartDoubles));
-    HIPCHK(hipMemsetAsync(sl.loss_part, 0, sizeof(double) * kLossPartDoubles, st));
+    HIPCHK(grow(sl.loss_part, loss_part_doubles(s)));
+    HIPCHK(hipMemsetAsync(sl.loss_part, 0, sizeof(double) * loss_part_doubles(s), st));
   }
   HIPCHK(sl.st.grow(1, 1));
 #ifdef SLM_STAMPS
@@ -154,7 +159,9 @@ static int bind_data_plan(slm_solver* s, Slot& sl, const slm_frame* f, hipStream
   h.vk_ready = 0;
   sl.prep_kind = 0;
   sl.prep_max_bin = 0;
-  out.form = data_form_of(s->cfg, *f, s->corr_mode != 0 || s->weights_on);
+  sl.face.ready = 0;
+  sl.face.tri_pidx = nullptr;
+  out.form = data_form_of(s->cfg, *f, s->corr_mode != 0 || s->weights_on || s->face_on);
   if (out.form == DataForm::tuple) {
     V1Sizes sz;
     HIPCHK(prep_v1(prep, *f, sl.plan, &sz, st));
@@ -198,8 +205,11 @@ static int bind_data_plan(slm_solver* s, Slot& sl, const slm_frame* f, hipStream
     // the coupled-pair list and every surfel's pair indices from one sort (prep_pairs), the multifrontal solver on that
     // list, the data term through per-pair records (pairbuf)
     PairSizes sz;
-    HIPCHK(prep_pairs(prep, *f, sl.pplan, &sz, st));
+    // (the face term's mesh joins the pair list: its six pairs per triangle get records, destinations and a place in the fronts)
+    const FaceMesh mesh = s->face_on ? FaceMesh{sl.face.tri, sl.face.n_tri} : FaceMesh();
+    HIPCHK(prep_pairs(prep, *f, sl.pplan, &sz, st, mesh));
     if (sz.bad_knn) return fail(SLM_ERR_INVALID, kBadKnn);
+    if (sz.bad_face) return fail(SLM_ERR_INVALID, kBadFace);
     out.knn_hash = sz.knn_hash;
     out.graph_hash = sz.graph_hash;
     bt_mark(BT_DATA_PLAN);
@@ -209,6 +219,10 @@ static int bind_data_plan(slm_solver* s, Slot& sl, const slm_frame* f, hipStream
       h.sf_pidx = sl.pplan.sf_pidx;
       h.sf_perm = sl.pplan.sf_perm;
       h.vk_ready = 1;
+      if (mesh.n_tri > 0) {
+        sl.face.tri_pidx = sl.pplan.tri_pidx;
+        sl.face.ready = 1;
+      }
     }
   } else if (out.form == DataForm::per_entry) {
     // the per-entry atomics dereference the tables too: same refusal
@@ -459,6 +473,11 @@ static int bind_target_part(slm_solver* s, int32_t slot, const slm_frame* f, hip
   if (s->weights_on) {   // and so did its semantic inputs
     sl.wdev.has = 0;
     HIPCHK(hipMemsetAsync(&s->w_dev[slot].has, 0, sizeof(int32_t), st));
+  }
+  if (s->face_on) {   // the slot's mesh as this bind's plan placed it (through a pinned mirror, like the descriptor below)
+    HIPCHK(sl.face_pin.grow(1, 1));
+    memcpy(sl.face_pin.data(), &sl.face, sizeof(FaceDev));
+    HIPCHK(hipMemcpyAsync(s->face_dev + slot, sl.face_pin.data(), sizeof(FaceDev), hipMemcpyHostToDevice, st));
   }
   // descriptor -> device through the slot's pinned mirror: no wait for the copy (the mirror always holds the newest
   // host state, and every change of it is followed by another copy on the stream)

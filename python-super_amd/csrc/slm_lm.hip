@@ -1,7 +1,7 @@
 // slm_lm.hip -- the LM step of the LM host: the dimensions of a batch of bound slots, the choice of the solver's form,
 // the stages of an iteration in the batch's data form (enqueue_*), and the entry points made of them: slm_run, the
 // sharded step with its exchange, the parity entry points (slm_assemble / slm_loss / slm_solve) and the
-// flow-correspondence term and the per-residual data weights.  Host side only orchestrates launches.
+// flow-correspondence term, the face term and the per-residual data weights.  Host side only orchestrates launches.
 #include "slm_solver.h"
 
 namespace {
@@ -9,6 +9,8 @@ struct BatchDims {
   int maxN = 0, maxJKe = 0, nt_max = 0, wb_cap = 0, n_reg_part = 0;
   int max_pos = 0, max_blocks = 0, maxP = 0;
   bool corr = false;   // some slot of the batch has correspondences bound (the term's Jacobian pass runs)
+  int max_tri = 0;     // most triangles of a slot's face mesh (0: no slot has one, the face term's Jacobian pass does not run)
+  int face_part = 0;   // doubles from the regularisers' partials to the face term's
   bool weights = false;   // the solver carries per-residual data weights (slm_enable_data_weights): the weighted kernels run
   DataWArgs wargs{};      // ... with these arguments (the batch's first semantic descriptor, seg_mode, pp_max)
   int n_acc_part = 0;  // what k_accept sums behind the data partials: the regularisers' pairs, on an enabled solver the term's too
@@ -51,6 +53,7 @@ BatchDims dims_of(slm_solver* s, int first, int n, bool band = false) {
     }
     d.maxP = std::max(d.maxP, h.P);
     d.corr = d.corr || (s->corr_mode && s->slots[i].corr.has);
+    if (s->face_on && s->slots[i].face.ready) d.max_tri = std::max(d.max_tri, s->slots[i].face.n_tri);
   }
   d.nd = d.nd && !band;
   // tuple-sorted on either solver; the pair records need the multifrontal one; per-entry atomics otherwise
@@ -102,6 +105,8 @@ BatchDims dims_of(slm_solver* s, int first, int n, bool band = false) {
   if (s->cfg.use_arap || s->cfg.use_rot)
     d.n_reg_part = std::min(kRegBlocksMax, (d.maxJKe + 255) / 256);
   d.n_acc_part = d.n_reg_part + (s->corr_mode ? kCorrBlocks : 0);
+  d.face_part = 2 * d.n_acc_part;
+  if (s->face_on) d.n_acc_part += kFaceBlocks;
   d.weights = s->weights_on;
   d.wargs = DataWArgs{s->w_seg_mode ? s->w_dev.p + first : nullptr, s->w_pp_max, s->w_seg_mode, 0};
   return d;
@@ -181,10 +186,12 @@ void enqueue_jacobian(slm_solver* s, const FrameDev* fr, int n, const BatchDims&
     case DataForm::pairs:   // per-pair records (zeroed, then filled; the correspondence term adds into them)
       launch_data_grad_pairs(fr, n, d.maxN, d.K, w, st, d.weights ? &d.wargs : nullptr);
       if (d.corr) launch_corr_grad_pairs(fr, s->corr_dev + (fr - s->frames_dev), n, d.maxN, d.K, s->corr_mode, s->corr_w, st);
+      if (d.max_tri) launch_face_grad(fr, s->face_dev + (fr - s->frames_dev), n, d.max_tri, s->face_w, st);
       break;
     case DataForm::per_entry:
       launch_data_grad(fr, n, d.maxN, d.K, w, st, d.weights ? &d.wargs : nullptr);
       if (d.corr) launch_corr_grad(fr, s->corr_dev + (fr - s->frames_dev), n, d.maxN, d.K, s->corr_mode, s->corr_w, st);
+      if (d.max_tri) launch_face_grad_band(fr, s->face_dev + (fr - s->frames_dev), n, d.max_tri, s->face_w, st);
       break;
     case DataForm::none: break;
   }
@@ -221,7 +228,9 @@ void enqueue_data_loss(slm_solver* s, const FrameDev* fr, int n, const BatchDims
   // the correspondence term's partials, behind the regularisers' (every slot of an enabled solver: zeros without targets)
   if (s->corr_mode && d.K >= 1)
     launch_corr_loss(fr, s->corr_dev + (fr - s->frames_dev), n, d.K, s->corr_mode, s->corr_w, at_beta ? 0 : 1, 2 * d.n_reg_part,
-                     kCorrCntPart, st);
+                     corr_cnt_part(s), st);
+  // the face term's, behind those (likewise: zeros without a mesh)
+  if (s->face_on) launch_face_loss(fr, s->face_dev + (fr - s->frames_dev), n, s->face_w, at_beta ? 0 : 1, d.face_part, st);
 }
 }  // namespace
 
@@ -256,6 +265,8 @@ int slm_set_shard(slm_solver* s, int32_t rank, int32_t world) {
   if (s->corr_mode)
     return fail(SLM_ERR_UNSUPPORTED, "slm_set_shard: the correspondence term is enabled (slm_enable_corr); it needs every surfel of "
                                      "the frame on one device");
+  if (s->face_on)
+    return fail(SLM_ERR_UNSUPPORTED, "slm_set_shard: the face term is enabled (slm_enable_face); its mesh is not sharded");
   s->rank = rank;
   s->world = world;
   s->shard_mode = true;
@@ -631,8 +642,75 @@ int slm_corr_loss(slm_solver* s, int32_t slot, double* out, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   if ((rc = clear_flags(s, slot, st)) != SLM_OK) return rc;
   const int part = 2 * kRegBlocksMax;   // (any place behind the regularisers' pairs: every LM iteration rewrites its own)
-  launch_corr_loss(s->frames_dev + slot, s->corr_dev + slot, 1, sp->h.f.K, s->corr_mode, s->corr_w, 0, part, kCorrCntPart, st);
-  launch_corr_loss_out(s->frames_dev, slot, part, kCorrCntPart, out, st);
+  launch_corr_loss(s->frames_dev + slot, s->corr_dev + slot, 1, sp->h.f.K, s->corr_mode, s->corr_w, 0, part, corr_cnt_part(s), st);
+  launch_corr_loss_out(s->frames_dev, slot, part, corr_cnt_part(s), out, st);
+  HIPCHK(hipGetLastError());
+  return SLM_OK;
+}
+
+
+// ---- triangle-area face term (include/super_lm.h; kernels in slm_face.hip) -------------------------------------------
+int slm_enable_face(slm_solver* s, double weight) {
+  if (!s) return fail(SLM_ERR_INVALID, "slm_enable_face: null argument");
+  if (!(weight - weight == 0.0)) return fail(SLM_ERR_INVALID, "slm_enable_face: weight must be finite");
+  if (s->cfg.data_path == 1) return fail(SLM_ERR_UNSUPPORTED, "slm_enable_face: needs the pair-record data path (data_path 0 or 2)");
+  if (s->cfg.solver_path == 1) return fail(SLM_ERR_UNSUPPORTED, "slm_enable_face: needs a nested-dissection solver_path (0, 2, 3 or 4)");
+  if (!s->cfg.use_data) return fail(SLM_ERR_UNSUPPORTED, "slm_enable_face: needs the data term (use_data 1)");
+  if (s->shard_mode)
+    return fail(SLM_ERR_UNSUPPORTED, "slm_enable_face: the solver is sharded (slm_set_shard); the term's mesh is not sharded");
+  for (const Slot& sl : s->slots)
+    if (sl.h.bound || sl.prep_ticket || sl.model_ready || sl.loss_part)   // (loss_part: the first bind sizes it for the term)
+      return fail(SLM_ERR_INVALID, "slm_enable_face: a slot is already bound; call it after slm_create and before the first bind");
+  const bool on = weight != 0.0;
+  if (on && !s->face_dev) {
+    HIPCHK(s->face_dev.grow(s->slots.size(), s->slots.size()));
+    HIPCHK(hipMemset(s->face_dev, 0, sizeof(FaceDev) * s->slots.size()));
+  }
+  s->face_on = on;
+  s->face_w = on ? weight : 0.0;
+  return SLM_OK;
+}
+
+int slm_set_face_mesh(slm_solver* s, int32_t slot, int32_t n_triangles, const int32_t* tri, const double* areas, void* stream) {
+  if (!s || (n_triangles > 0 && (!tri || !areas))) return fail(SLM_ERR_INVALID, "slm_set_face_mesh: null argument");
+  if (slot < 0 || slot >= (int)s->slots.size()) return fail(SLM_ERR_INVALID, "slm_set_face_mesh: bad slot");
+  if (n_triangles < 0) return fail(SLM_ERR_INVALID, "slm_set_face_mesh: n_triangles must be >= 0");
+  if (!s->face_on) return fail(SLM_ERR_UNSUPPORTED, "slm_set_face_mesh: slm_enable_face first");
+  hipStream_t st = (hipStream_t)stream;
+  Slot& sl = s->slots[slot];
+  // the slot's plan holds the pairs of the mesh it was bound with: a queued preparation is settled and dropped, and the
+  // slot is unbound until its next bind
+  join_prepare(s, slot);
+  sl.model_ready = false;
+  sl.h.bound = 0;
+  sl.face = FaceDev{};
+  const size_t F = (size_t)n_triangles;
+  if (F > 0) {
+    HIPCHK(grow(sl.face_tri, 3 * F));
+    HIPCHK(grow(sl.face_areas, F));
+    HIPCHK(hipMemcpyAsync(sl.face_tri, tri, sizeof(int32_t) * 3 * F, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(sl.face_areas, areas, sizeof(double) * F, hipMemcpyDeviceToDevice, st));
+    sl.face.tri = sl.face_tri.p;
+    sl.face.areas = sl.face_areas.p;
+    sl.face.n_tri = n_triangles;
+  }
+  HIPCHK(hipMemsetAsync(s->face_dev + slot, 0, sizeof(FaceDev), st));   // (ready = 0 on the device until the bind publishes it)
+  HIPCHK(hipMemsetAsync(&s->frames_dev[slot].bound, 0, sizeof(int32_t), st));
+  return SLM_OK;
+}
+
+int slm_face_loss(slm_solver* s, int32_t slot, double* out, void* stream) {
+  if (!s || !out) return fail(SLM_ERR_INVALID, "slm_face_loss: null argument");
+  if (slot < 0 || slot >= (int)s->slots.size()) return fail(SLM_ERR_INVALID, "slm_face_loss: bad slot");
+  if (!s->face_on) return fail(SLM_ERR_UNSUPPORTED, "slm_face_loss: slm_enable_face first");
+  join_prepare(s, slot);
+  if (!s->slots[slot].h.bound) return fail(SLM_ERR_UNBOUND, "slm_face_loss: slm_bind_frame first");
+  hipStream_t st = (hipStream_t)stream;
+  int rc = clear_flags(s, slot, st);
+  if (rc != SLM_OK) return rc;
+  const int part = face_direct_part();   // (any place among the pairs, in front of the kept counts: every LM iteration rewrites its own)
+  launch_face_loss(s->frames_dev + slot, s->face_dev + slot, 1, s->face_w, 0, part, st);
+  launch_face_loss_out(s->frames_dev, s->face_dev, slot, part, out, st);
   HIPCHK(hipGetLastError());
   return SLM_OK;
 }

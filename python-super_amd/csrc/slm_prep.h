@@ -44,6 +44,7 @@ struct PlanSizes {
   int n_blocks = 0;
   uint64_t knn_hash = 0, graph_hash = 0;
   bool bad_knn = false;          // a KNN index outside [0, J) or a surfel's repeated id was seen: the frame must be refused
+  bool bad_face = false;         // prep_pairs with a mesh: a triangle id outside [0, J) or a triangle that repeats an id, likewise
 };
 struct V1Sizes : PlanSizes {
   int n_tuples = 0, n_pos = 0, n_runs = 0;
@@ -64,11 +65,19 @@ struct PairPlan {
   int32_t* blk_key = nullptr;    // (n_blocks) sorted pair keys
   int32_t* sf_pidx = nullptr;    // (N, K(K+1)/2) pair index of every (surfel, canonical slot)
   int32_t* sf_perm = nullptr;    // (N) surfel ids in neighbour-set order
-  size_t cap_key = 0, cap_pidx = 0, cap_perm = 0;
+  int32_t* tri_pidx = nullptr;   // (F, 6) face term: pair index of every triangle's six node pairs (FaceDev::tri_pidx, slm_face.h)
+  size_t cap_key = 0, cap_pidx = 0, cap_perm = 0, cap_tpidx = 0;
 };
 using PairSizes = PlanSizes;
+// The mesh of the face term (slm_set_face_mesh): tri (3, F) device node ids.  The six node pairs of every triangle join the
+// frame's pair list before the sort, so that the pair keys, their hash, the symbolic analysis and the block destinations
+// cover them like any surfel's pair; plan.tri_pidx then locates them.  The ids are checked here (PlanSizes::bad_face).
+struct FaceMesh {
+  const int32_t* tri = nullptr;
+  int n_tri = 0;
+};
 // Stream-synchronising (one read-back).  f.K in 1..8, f.J < 65536.
-hipError_t prep_pairs(PrepBuffers*, const slm_frame& f, PairPlan& plan, PairSizes* out, hipStream_t st);
+hipError_t prep_pairs(PrepBuffers*, const slm_frame& f, PairPlan& plan, PairSizes* out, hipStream_t st, FaceMesh mesh = FaceMesh());
 void pairplan_free(PairPlan& plan);
 
 PrepBuffers* prep_create();

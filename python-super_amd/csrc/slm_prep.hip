@@ -43,6 +43,7 @@ enum {
   SC_BAD_KNN,          // a bad KNN index or row was seen
   SC_MAXBIN,           // binned preparation: largest bin
   SC_STATE,            // binned preparation: ST_*
+  SC_BAD_FACE,         // prep_pairs with a mesh: a bad triangle was seen
   SC_COUNT
 };
 enum { ST_OK = 0, ST_LEGACY = 1, ST_MISS = 2 };   // a bin exceeds the LDS sort: rocPRIM pipeline / a hinted plan-buffer bound did not hold
@@ -384,6 +385,51 @@ __global__ void __launch_bounds__(256) k_pair_index(int N, int J, int n_blocks, 
   okey[i] = k64;
   if (KK > 4) okey2[i] = k64b;
   oid[i] = i;
+}
+// ---- the face term's mesh in the pair plan (FaceMesh, slm_prep.h) ----
+// the six pair keys of every triangle behind the surfels' keys: diagonals of vertex 0, 1, 2, then (0,1), (0,2), (1,2).  A
+// triangle with an id outside [0, J) or a repeated id is reported through *bad and keyed as the pair (0, 0) meanwhile (as
+// k_pair_keys: nothing downstream reads out of bounds before the host has seen the flag).
+__device__ __forceinline__ void tri_keys(const int* __restrict__ tri, int F, int t, int J, unsigned key[6], bool& bad) {
+  int a = tri[t], b = tri[(size_t)F + t], c = tri[2 * (size_t)F + t];
+  bad = (unsigned)a >= (unsigned)J || (unsigned)b >= (unsigned)J || (unsigned)c >= (unsigned)J || a == b || a == c || b == c;
+  if (bad) a = b = c = 0;
+  const unsigned uj = (unsigned)J;
+  key[0] = (unsigned)a * uj + (unsigned)a;
+  key[1] = (unsigned)b * uj + (unsigned)b;
+  key[2] = (unsigned)c * uj + (unsigned)c;
+  key[3] = (unsigned)max(a, b) * uj + (unsigned)min(a, b);
+  key[4] = (unsigned)max(a, c) * uj + (unsigned)min(a, c);
+  key[5] = (unsigned)max(b, c) * uj + (unsigned)min(b, c);
+}
+__global__ void __launch_bounds__(256) k_face_keys(int F, int J, const int* __restrict__ tri, unsigned* __restrict__ keys, int* __restrict__ bad) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= F) return;
+  unsigned key[6];
+  bool b;
+  tri_keys(tri, F, t, J, key, b);
+  if (b) *bad = 1;
+#pragma unroll
+  for (int e = 0; e < 6; ++e) keys[6 * (size_t)t + e] = key[e];
+}
+// position of each of a triangle's six pairs in the sorted unique list (as k_pair_index; the host has seen the bad flag clear)
+__global__ void __launch_bounds__(256) k_face_index(int F, int J, int n_blocks, const int* __restrict__ tri, const unsigned* __restrict__ ukeys,
+                                                     int* __restrict__ tpidx) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= F) return;
+  unsigned key[6];
+  bool b;
+  tri_keys(tri, F, t, J, key, b);
+#pragma unroll
+  for (int e = 0; e < 6; ++e) {
+    int lo = 0, hi = n_blocks - 1;
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (ukeys[mid] < key[e]) lo = mid + 1;
+      else hi = mid;
+    }
+    tpidx[6 * (size_t)t + e] = lo;
+  }
 }
 __global__ void __launch_bounds__(256) k_gather_keys(int N, const unsigned long long* __restrict__ keys, const int* __restrict__ order,
                                                       unsigned long long* __restrict__ out) {
@@ -1071,7 +1117,7 @@ constexpr DevArray kPlanArrays[] = {
     A(wg_last, cap_wg), A(run_lidx, cap_lidx), A(blk2_start, cap_b2start), A(blk2_entry, cap_b2entry), A(wgslab, cap_wgslab)};
 #undef A
 #define A(name, cap) ARR(PairPlan, name, cap)
-constexpr DevArray kPairPlanArrays[] = {A(blk_key, cap_key), A(sf_pidx, cap_pidx), A(sf_perm, cap_perm)};
+constexpr DevArray kPairPlanArrays[] = {A(blk_key, cap_key), A(sf_pidx, cap_pidx), A(sf_perm, cap_perm), A(tri_pidx, cap_tpidx)};
 #undef A
 }  // namespace
 
@@ -1082,6 +1128,10 @@ PrepBuffers* prep_create() {
     prep_destroy(p);
     return nullptr;
   }
+  // The mirror starts zeroed: a build copies back only the words it uses (the rocPRIM pipeline: up to SC_BAD_KNN), and
+  // read_built also tests SC_BAD_FACE, which only a prep_pairs build with a mesh -- on a solver with the face term enabled,
+  // where no tuple-sorted build ever runs -- can raise, behind its own read-back of the whole block.
+  memset(p->scal_host, 0, 32 * sizeof(int));
   return p;
 }
 
@@ -1190,7 +1240,8 @@ enum class Built { done, refused, retry, legacy };
 // The one reader of the status block that a build has copied back (sh; state: its SC_STATE, or what stands for it).
 static Built read_built(const int* sh, int state, PlanSizes* out) {
   out->bad_knn = sh[SC_BAD_KNN] != 0;
-  if (out->bad_knn) return Built::refused;   // the caller refuses the frame
+  out->bad_face = sh[SC_BAD_FACE] != 0;
+  if (out->bad_knn || out->bad_face) return Built::refused;   // the caller refuses the frame
   if (state == ST_LEGACY) return Built::legacy;
   if (state == ST_MISS) return Built::retry;
   out->n_blocks = sh[SC_NBLOCKS];
@@ -1437,10 +1488,11 @@ hipError_t prep_v1(PrepBuffers* p, const slm_frame& f, V1Plan& plan, V1Sizes* ou
 
 // ---- K-generic pair plan ---------------------------------------------------------------------------------------------
 // (SLM_K_DISPATCH's default is dead code here: prep_pairs, the only user, returns early for K outside 1..8)
-hipError_t prep_pairs(PrepBuffers* p, const slm_frame& f, PairPlan& plan, PairSizes* out, hipStream_t st) {
+hipError_t prep_pairs(PrepBuffers* p, const slm_frame& f, PairPlan& plan, PairSizes* out, hipStream_t st, FaceMesh mesh) {
   *out = PairSizes();
   if (f.N <= 0 || f.K < 1 || f.K > 8 || f.J >= 65536) return hipSuccess;
-  const size_t N = (size_t)f.N, NP = (size_t)f.K * (f.K + 1) / 2, n = N * NP;
+  const size_t N = (size_t)f.N, NP = (size_t)f.K * (f.K + 1) / 2, n_sf = N * NP;
+  const size_t F = mesh.tri && mesh.n_tri > 0 ? (size_t)mesh.n_tri : 0, n = n_sf + 6 * F;   // (no mesh: exactly the surfels' keys, as ever)
   HIPRET(GROW(p, kPrepArrays, cap_g, n));
   if (!p->gcnt) HIPRET(hipMalloc((void**)&p->gcnt, sizeof(unsigned)));
   // key bits: a*J + b < J*J
@@ -1459,6 +1511,7 @@ hipError_t prep_pairs(PrepBuffers* p, const slm_frame& f, PairPlan& plan, PairSi
   const dim3 blk(256);
   SLM_K_DISPATCH(f.K, hipLaunchKernelGGL(k_pair_keys<KK>, dim3((unsigned)((f.N + 255) / 256)), blk, 0, st, f.N, f.J, f.sf_knn_idx,
                                               p->gk, p->scal + SC_BAD_KNN));
+  if (F) hipLaunchKernelGGL(k_face_keys, dim3((unsigned)((F + 255) / 256)), blk, 0, st, (int)F, f.J, mesh.tri, p->gk + n_sf, p->scal + SC_BAD_FACE);
   size_t b1 = p->gtmp.cap, b2 = p->gtmp.cap;
   HIPRET(rocprim::radix_sort_keys(p->gtmp.buf, b1, p->gk, p->gsk, n, 0, bits, st));
   HIPRET(rocprim::unique(p->gtmp.buf, b2, p->gsk, p->gk, p->gcnt, n, rocprim::equal_to<unsigned>(), st));
@@ -1467,14 +1520,21 @@ hipError_t prep_pairs(PrepBuffers* p, const slm_frame& f, PairPlan& plan, PairSi
   hipLaunchKernelGGL(k_plan_hash, dim3(16), blk, 0, st, f.J, f.K_ED, f.ed_knn_idx, reinterpret_cast<const int32_t*>(p->gk), p->scal,
                      reinterpret_cast<unsigned long long*>(p->scal + SC_KNN_HASH));
   HIPRET(read_scal(p, SC_COUNT, st));
+  // (the mesh's flag is read here, behind this build's own read-back of the whole block, and only when a mesh was keyed: the
+  //  tuple-sorted builds neither zero nor copy that word)
+  out->bad_face = F > 0 && p->scal_host[SC_BAD_FACE] != 0;
+  if (out->bad_face) return hipSuccess;   // the caller refuses the frame
   if (read_built(p->scal_host, ST_OK, out) != Built::done || out->n_blocks <= 0) return hipSuccess;
   HIPRET(GROW(&plan, kPairPlanArrays, cap_key, (size_t)out->n_blocks));
-  HIPRET(GROW(&plan, kPairPlanArrays, cap_pidx, n));
+  HIPRET(GROW(&plan, kPairPlanArrays, cap_pidx, n_sf));
   HIPRET(GROW(&plan, kPairPlanArrays, cap_perm, N));
+  if (F) HIPRET(GROW(&plan, kPairPlanArrays, cap_tpidx, 6 * F));
   HIPRET(hipMemcpyAsync(plan.blk_key, p->gk, sizeof(unsigned) * (size_t)out->n_blocks, hipMemcpyDeviceToDevice, st));
   SLM_K_DISPATCH(f.K, hipLaunchKernelGGL(k_pair_index<KK>, dim3((unsigned)((N + 255) / 256)), blk, 0, st, f.N, f.J, out->n_blocks,
                                               f.sf_knn_idx, reinterpret_cast<const unsigned*>(plan.blk_key), plan.sf_pidx,
                                               p->keys, p->tkeys, p->ids));
+  if (F) hipLaunchKernelGGL(k_face_index, dim3((unsigned)((F + 255) / 256)), blk, 0, st, (int)F, f.J, out->n_blocks, mesh.tri,
+                            reinterpret_cast<const unsigned*>(plan.blk_key), plan.tri_pidx);
   size_t b3 = p->gtmp.cap;
   if (f.K <= 4) {
     HIPRET(rocprim::radix_sort_pairs(p->gtmp.buf, b3, p->keys, p->skeys, p->ids, plan.sf_perm, N, 0, 64, st));

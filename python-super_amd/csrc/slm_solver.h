@@ -1,6 +1,6 @@
 // slm_solver.h -- internal to the LM host (slm_api.hip, slm_bind.hip, slm_lm.hip): what a solver and its slots hold, and
 // the few functions that cross those units.  Device memory is owned by DevBuf / PinnedBuf members (slm_host.h); the
-// descriptors (FrameDev, CorrDev, DataWeightDev) only mirror addresses.
+// descriptors (FrameDev, CorrDev, FaceDev, DataWeightDev) only mirror addresses.
 #pragma once
 #include <algorithm>
 #include <atomic>
@@ -11,6 +11,7 @@
 #include "slm_common.h"
 #include "slm_corr.h"
 #include "slm_data.h"
+#include "slm_face.h"
 #include "slm_host.h"
 #include "slm_launch.h"
 #include "slm_prep.h"
@@ -23,6 +24,10 @@ constexpr int kRegBlocksMax = 64;
 constexpr int kCorrBlocks = SLM_CORR_BLOCKS;
 constexpr int kCorrCntPart = 2 * (kRegBlocksMax + kCorrBlocks);
 constexpr size_t kLossPartDoubles = (size_t)2 * (kLossBlocks + kRegBlocksMax + kCorrBlocks) + kCorrBlocks;
+// the face term's loss partials (slm_face.h): SLM_FACE_BLOCKS {sum, 0} pairs behind the correspondence term's pairs of the
+// launch.  Only a solver with the term enabled (slm_enable_face) has room for them: its slots' loss_part is that much longer
+// and the correspondence term's kept counts sit that much further back (corr_cnt_part).
+constexpr int kFaceBlocks = SLM_FACE_BLOCKS;
 
 // The form of the data term: which plan the bind prepares and which kernels the LM entry points launch.
 enum class DataForm {
@@ -59,6 +64,10 @@ struct Slot {
   CorrDev corr{};               // correspondence term: host mirror of the slot's targets, which are
   DevBuf<double> corr_o, corr_n;
   DevBuf<uint8_t> corr_valid;
+  FaceDev face{};               // face term: host mirror of the slot's mesh descriptor; the mesh itself is the slot's own copy
+  DevBuf<int32_t> face_tri;
+  DevBuf<double> face_areas;
+  PinnedBuf<FaceDev> face_pin;  // pinned mirror of `face` for the asynchronous upload of a bind
   DataWeightDev wdev{};         // data weights: host mirror of the slot's semantic inputs (the caller's arrays, none owned)
   PairPlan pplan;               // K-generic pair path (num_neighbors != 4): pair keys, per-surfel pair indices, surfel order
   PlanCache cache;              // nested-dissection plan: host copy; its device mirrors below (grow-only)
@@ -136,8 +145,17 @@ struct slm_solver {
   int w_seg_mode = 0;
   double w_pp_max = 0.0;
   DevBuf<DataWeightDev> w_dev;
+  bool face_on = false;         // slm_enable_face with a non-zero weight; its weight; the slots' meshes on the device
+  double face_w = 0.0;
+  DevBuf<FaceDev> face_dev;
   bool shard_mode = false;      // slm_set_shard was called (world == 1 included): slots carry the exchange buffers
 };
+
+// where the correspondence term's kept counts and the face term's partials of a direct call (slm_corr_loss, slm_face_loss)
+// sit behind the regularisers' pairs, and the doubles of a slot's loss_part
+inline int corr_cnt_part(const slm_solver* s) { return kCorrCntPart + (s->face_on ? 2 * kFaceBlocks : 0); }
+inline int face_direct_part() { return 2 * (kRegBlocksMax + kCorrBlocks); }
+inline size_t loss_part_doubles(const slm_solver* s) { return kLossPartDoubles + (s->face_on ? 2 * (size_t)kFaceBlocks : 0); }
 
 // diagnostics (slm_debug_counters, slm_api.hip): device reallocations and symbolic analyses since the library was loaded
 extern std::atomic<long long> g_reallocs, g_realloc_bytes, g_plan_builds, g_plan_reuses, g_plan_fill_hits;   // (binds may run on worker threads)

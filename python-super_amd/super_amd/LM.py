@@ -130,7 +130,7 @@ class LM_Solver():
     """Drop-in for ``super.LM.LM_Solver``; see module docstring."""
 
     def __init__(self, opt, convs=None, max_frames=1, shard_surfels=False, rank=None, world=None,
-                 all_reduce=None, broadcast=None, corr_term=False, weighted_data=False):
+                 all_reduce=None, broadcast=None, corr_term=False, weighted_data=False, face_term=False):
         """``LM_Solver(opt, convs)`` as in the reference.  ``shard_surfels=True`` (after
         ``torch.distributed.init_process_group``) splits the surfels of ONE large frame over the GPUs
         of a node: every rank evaluates its share, the block-sparse J^T J / J^T r sums and the loss are
@@ -144,8 +144,25 @@ class LM_Solver():
         ``opt.sf_hard_seg_point_plane`` (soft wins; the term is then on also without ``opt.sf_point_plane``, whose place the
         reference gives them) read ``sf.seg``, ``sf.seg_conf`` and ``new_data.seg_conf`` of every frame, and
         ``opt.depth_model == "raft_stereo"`` truncates at 2e-5.  Without the flag those options are ignored by this class
-        exactly as before."""
+        exactly as before.
+        ``face_term=True`` (opt-in; needs ``opt.mesh_face``) adds the triangle-area face term of the reference's published
+        runs (``super/deform_mesh.py:51-60``, there on the first-order path only) in its Gauss-Newton form
+        (``slm_enable_face``, include/super_lm.h): ``sf.ED_nodes.triangles`` (3, F) and ``sf.ED_nodes.triangles_areas`` (F,)
+        of every frame, weight ``opt.mesh_face_weight`` on the RESIDUAL (GraphFit weighs the squared sum: its
+        ``mesh_face_weight`` = this one squared).  Without the flag ``opt.mesh_face`` is ignored by this class exactly as
+        before."""
         self.opt = opt
+        self.face_on = False
+        if face_term:
+            if not getattr(opt, "mesh_face", False):
+                raise ValueError("LM_Solver(face_term=True) needs opt.mesh_face")
+            if shard_surfels or world is not None:
+                raise NotImplementedError("LM_Solver: face_term with shard_surfels is not built (the term's mesh is not sharded)")
+            self.face_on = True
+            self.face_weight = float(getattr(opt, "mesh_face_weight", 1.0))
+        self._face_sent = {}                         # (handle, slot) -> stamp of the mesh tensors the slot holds
+        self._face_loss_of = None                    # (n, u, v, minimal_loss) of the last run; its losses once they were asked for
+        self._face_loss = None
         self.seg_mode, self.pp_max = 0, 0.0
         if weighted_data:
             soft = bool(getattr(opt, "sf_soft_seg_point_plane", False))
@@ -222,6 +239,8 @@ class LM_Solver():
                 _lib.check(self.lib.slm_enable_corr(h, self.corr_mode, self.corr_weight), "slm_enable_corr")
             if self.weighted:
                 _lib.check(self.lib.slm_enable_data_weights(h, self.seg_mode, self.pp_max), "slm_enable_data_weights")
+            if self.face_on:
+                _lib.check(self.lib.slm_enable_face(h, self.face_weight), "slm_enable_face")
             if self.sharded:
                 _lib.check(self.lib.slm_set_shard(h, self.rank, self.world), "slm_set_shard")
             self._solvers[key] = h
@@ -250,7 +269,55 @@ class LM_Solver():
             _lib.check(self.lib.slm_discard_prepared(prepared[0], slot), "slm_discard_prepared")
         return BoundFrame(sf, inputs, new_data, state=state, model=mv)
 
+    def _face_mesh(self, h, slot, sf):
+        """The slot's mesh of the face term, before its bind / ``prepare_model``: sent again when the tensors changed
+        (pointer, shape, dtype or version counter), kept by the library otherwise.  The stamp cannot tell a tensor that was
+        freed and whose address a NEW tensor of the same shape, dtype and version took over from the old one (``ModelView``
+        has the same limit): a caller that rebuilds the mesh tensors per frame and lets the old ones go should keep a
+        reference to the previous pair until the next ``LM``, or write into the same tensors in place."""
+        if not self.face_on:
+            return
+        ed = sf.ED_nodes
+        tri, areas = getattr(ed, "triangles", None), getattr(ed, "triangles_areas", None)
+        if tri is None or areas is None:
+            raise ValueError("LM_Solver(face_term=True): sf.ED_nodes.triangles / triangles_areas are missing")
+        if tri.dim() != 2 or tri.shape[0] != 3 or areas.numel() != tri.shape[1]:
+            raise ValueError(f"LM_Solver(face_term=True): triangles must be (3, F) and triangles_areas (F,), got "
+                             f"{tuple(tri.shape)} and {tuple(areas.shape)}")
+        stamp = ModelView._stamp((tri, areas))
+        if self._face_sent.get((h.value, slot)) == stamp:
+            return
+        dev = sf.points.device
+        t32, a64 = _as(tri, torch.int32, dev), _as(areas.reshape(-1), torch.float64, dev)
+        F = int(t32.shape[1])                         # (copied by the library on the stream: t32 / a64 may go afterwards)
+        _lib.check(self.lib.slm_set_face_mesh(h, slot, F, _dev_ptr(t32) if F else None, _dev_ptr(a64) if F else None,
+                                              _stream_ptr(dev)), "slm_set_face_mesh")
+        self._face_sent[(h.value, slot)] = stamp
+
+    @property
+    def last_face_loss(self):
+        """Per slot of the last ``LM`` / ``LM_batch``: (sum of squared face residuals at the returned beta, triangle count);
+        ``None`` without ``face_term`` or before a run.  Evaluated when first read, in one device-to-host copy for all slots:
+        a caller that never reads it pays no launch and no host wait per frame."""
+        if self._face_loss is None and self._face_loss_of is not None:
+            n, u, v, ml = self._face_loss_of
+            h, dev = self._handle(u, v, ml), self._bound[0].device
+            out = torch.empty((n, 2), dtype=torch.float64, device=dev)
+            for i in range(n):
+                _lib.check(self.lib.slm_face_loss(h, i, _dev_ptr(out[i]), _stream_ptr(dev)), "slm_face_loss")
+            self._face_loss = [(float(a), int(b)) for a, b in out.cpu().tolist()]
+        return self._face_loss
+
+    def face_loss(self, slot=0, u=10, v=7.5, minimal_loss=1e10):
+        """(sum of squared face residuals at the slot's current beta, triangle count)."""
+        h, bf = self._handle(u, v, minimal_loss), self._bound[slot]
+        out = torch.empty(2, dtype=torch.float64, device=bf.device)
+        _lib.check(self.lib.slm_face_loss(h, slot, _dev_ptr(out), _stream_ptr(bf.device)), "slm_face_loss")
+        o = out.cpu()
+        return float(o[0]), int(o[1])
+
     def _bind(self, h, slot, sf, inputs, new_data):
+        self._face_mesh(h, slot, sf)
         bf = self._frame(h, slot, sf, inputs, new_data)
         _lib.check(self.lib.slm_bind_frame(h, slot, C.byref(bf.c), _stream_ptr(bf.device)),
                    "slm_bind_frame")
@@ -260,6 +327,8 @@ class LM_Solver():
     def _bind_batch(self, h, frames):
         """The frames of a batch bound CONCURRENTLY (``slm_bind_frames``: one host thread, stream and scratch set per frame
         inside the library, forked from and joined into the caller's stream) -- slots 0 .. len(frames) - 1."""
+        for i, fr in enumerate(frames):
+            self._face_mesh(h, i, fr[0])
         bfs = [self._frame(h, i, *fr) for i, fr in enumerate(frames)]
         arr = (SlmFrame * len(bfs))(*[bf.c for bf in bfs])
         _lib.check(self.lib.slm_bind_frames(h, 0, len(bfs), arr, _stream_ptr(bfs[0].device)), "slm_bind_frames")
@@ -356,6 +425,7 @@ class LM_Solver():
         order.  When the model changes after all -- other tensors or an in-place write, seen in the tensors' version
         counters -- the next ``LM()`` drops the preparation (``slm_discard_prepared``) and prepares in full."""
         h = self._handle(u, v, minimal_loss)
+        self._face_mesh(h, slot, sf)
         mv = ModelView(sf, state=getattr(self.opt, "slm_state_dtype", None))
         fr = SlmFrame()
         mv.fill(fr)
@@ -409,6 +479,10 @@ class LM_Solver():
             co = torch.empty(2, dtype=torch.float64, device=bf.device)
             _lib.check(self.lib.slm_corr_loss(h, 0, _dev_ptr(co), st), "slm_corr_loss")
             total = total + co[0]
+        if self.face_on:
+            fo = torch.empty(2, dtype=torch.float64, device=bf.device)
+            _lib.check(self.lib.slm_face_loss(h, 0, _dev_ptr(fo), st), "slm_face_loss")
+            total = total + fo[0]
         return total
 
     def _corr_arg(self, flow, corr_points, required):
@@ -457,6 +531,7 @@ class LM_Solver():
             self._report(fr[0], fr[1], recs)
         if self.corr_mode:
             self.last_corr_kept = [None if c is None else self.corr_loss(i, u, v, minimal_loss)[1] for i, c in enumerate(corrs)]
+        self._face_loss_of, self._face_loss = ((n, u, v, minimal_loss) if self.face_on else None), None
         return betas
 
     # ---- one frame sharded over several GPUs ------------------------------------------------

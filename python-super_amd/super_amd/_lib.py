@@ -43,6 +43,7 @@ EXPORTS = [
     "slm_gf_bind_render_loss", "slm_gf_render_loss_status", "slm_gf_render_loss_read",
     "slm_enable_corr", "slm_bind_corr_flow", "slm_bind_corr_points", "slm_corr_get_targets", "slm_corr_loss",
     "slm_enable_data_weights", "slm_bind_data_semantic", "slm_data_weights",
+    "slm_enable_face", "slm_set_face_mesh", "slm_face_loss",
 ]
 
 
@@ -248,6 +249,9 @@ def load():
         "slm_enable_data_weights": [vp, i32, dbl],
         "slm_bind_data_semantic": [vp, i32, i32, vp, vp, vp, vp],
         "slm_data_weights": [vp, i32, vp, vp],
+        "slm_enable_face": [vp, dbl],
+        "slm_set_face_mesh": [vp, i32, i32, vp, vp, vp],
+        "slm_face_loss": [vp, i32, vp, vp],
         "slm_graph_init": [i32, i32, i32, vp, vp, vp, vp, C.POINTER(SlmGraphOutputs), C.POINTER(C.c_int32), vp],
         "slm_graph_init_semantic": [i32, i32, i32, vp, vp, vp, vp, i32, vp, i32, C.POINTER(SlmGraphOutputs), vp, vp,
                                     C.POINTER(C.c_int32), vp],
