@@ -793,8 +793,113 @@ __global__ void __launch_bounds__(256, 2) k_fL11(const FrameDev* __restrict__ fr
   }
 }
 
+// One boundary row tile of k_fL21 (below), for a wave that owns true rows (ON) and for one whose 16 rows lie beyond the true
+// boundary size: that one only moves its share of the B stream and meets the barriers -- the same ones, in the same loops.
+template <bool ON>
+__device__ __forceinline__ void fl21_row(const FrameDev& fd, const NDFront& f, const int r, const int w, double* Bl, double* yv) {
+  const int l = threadIdx.x & 63, lr = l & 15, lk = l >> 4;
+  double* vecs = fd.fvec + f.vec_off;
+  const double* linv = fd.flinv + f.linv_off;
+  const int npt = f.npt;
+  // The B operands of the row's products -- column 0: Linv_0; column 1: L(1,0), Linv_1; ... -- are ONE stream of half tiles
+  // through LDS (BHalfStream, slm_tile.h): one barrier per half, and the next half -- of this product or the first of the
+  // next one -- in flight during the MFMAs.  A(r,0), the first half of Linv_0 and y_0 are requested before anything waits;
+  // y_c comes with the first half of Linv_c.  The A side stays at its point of use: A(r,c) at the top of its column, X_c' of
+  // a left-looking term right behind the MFMAs of the term before it.  Requested a product (or a half product) ahead it
+  // cost time at three workgroups per CU, and a whole product ahead needs two (docs/LAB_NOTEBOOK.md, "`k_fL21`: the row
+  // solves' B operands as one stream").
+  // (X_c' of the earlier columns is re-read from the tile this thread itself stored it to -- the accumulator layout is
+  //  the A-fragment layout, element for element -- instead of being held in 32 registers per column.  Only X_0 for the
+  //  product right behind its own solve, (1,0), is taken from the accumulators.)
+  // (every tile address through an opaque zero of its phase: the lanes' addresses are then formed where they are used and not
+  //  in front of the loops, to be kept in registers across them -- as in k_fL11)
+  auto zero_here = []() {
+    int zero = 0;
+    asm volatile("" : "+s"(zero));
+    return zero;
+  };
+  BHalfStream bs;
+  double4_t acc[4];     // A(r,c) minus the left-looking terms
+  double xreg[16];      // the A fragments of the next left-looking product to run
+  double ynext = 0.0;
+  bs.request(linv, 0);
+  if (threadIdx.x < NB) ynext = vecs[threadIdx.x];
+  if (ON) load_c_frags(ftile(fd, f, r, 0), acc);
+  else zero_acc(acc);
+  __builtin_amdgcn_sched_barrier(0);
+  double rhs_acc = 0.0;
+  for (int c = 0; c < npt; ++c) {
+    const int ncol = min(NB, f.n1 - NB * c);            // true pivots of this tile column
+    const int nblk = (ncol + 15) >> 4;                  // 16-column blocks with true pivots (also the inner blocks of X_c L_cc^-T)
+    const bool more = c + 1 < npt;
+    if (c > 0) {
+      if (ON) load_c_frags(ftile(fd, f, r, c), acc);
+      else zero_acc(acc);
+      __builtin_amdgcn_sched_barrier(0);
+      if (ON && c > 1) load_a_frags(ftile(fd, f, r, 0), xreg);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    // acc -= X_c' L(c,c')^T for the earlier pivot columns
+    for (int cp = 0; cp < c; ++cp) {
+      const int z = zero_here();
+      const bool last = cp + 1 == c;
+      bs.put(Bl + z, 0);
+      bs.request(ftile(fd, f, c, cp) + z, 1);
+      __syncthreads();
+      if (ON) tile_ABt_half_trim<true, false, 0>(xreg, Bl + z, acc, 4, nblk);
+      const int z1 = zero_here();
+      bs.put(Bl + z1, 1);
+      bs.request((last ? linv + (size_t)c * TILE : ftile(fd, f, c, cp + 1)) + z1, 0);
+      if (last && threadIdx.x < NB) ynext = vecs[(size_t)c * NB + threadIdx.x];
+      __syncthreads();
+      if (ON) tile_ABt_half_trim<true, false, 1>(xreg, Bl + z1, acc, 4, nblk);
+      if (!last && ON) {
+        load_a_frags(ftile(fd, f, r, cp + 1) + z1, xreg);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    }
+    // X_c = acc L_cc^-T
+    {
+      // (a second half also where only a barrier is left of it: the halves of Bl must alternate while the stream goes on)
+      const bool two = nblk > 2 || more;
+      const int z = zero_here();
+      bs.put(Bl + z, 0);
+      if (threadIdx.x < NB) yv[threadIdx.x] = ynext;    // (y_(c-1) was last read two barriers ago)
+      if (two) bs.request(linv + (size_t)c * TILE + z, 1);
+      __syncthreads();
+      double areg[16];
+#pragma unroll
+      for (int ni = 0; ni < 4; ++ni)
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) areg[4 * ni + rr] = acc[ni][rr];
+      double4_t xa[4];
+      zero_acc(xa);
+      if (ON) tile_ABt_half_trim<false, true, 0>(areg, Bl + z, xa, nblk, nblk);
+      if (two) {
+        const int z1 = zero_here();
+        bs.put(Bl + z1, 1);
+        if (more) bs.request(ftile(fd, f, c + 1, 0) + z1, 0);
+        __syncthreads();
+        if (ON) tile_ABt_half_trim<false, true, 1>(areg, Bl + z1, xa, nblk, nblk);
+      }
+      const int z2 = zero_here();
+      if (ON) store_c_frags_nblk(ftile(fd, f, r, c) + z2, xa, nblk);
+      __builtin_amdgcn_sched_barrier(0);
+      rhs_acc = acc_dot_vec(xa, yv + z2, rhs_acc);
+      if (more && c == 0) {   // column 1 follows its own solve: X_0 from the accumulators
+#pragma unroll
+        for (int ni = 0; ni < 4; ++ni)
+#pragma unroll
+          for (int rr = 0; rr < 4; ++rr) xreg[4 * ni + rr] = xa[ni][rr];
+      }
+    }
+  }
+  rhs_acc = sum_row_lanes(rhs_acc);
+  if (lk == 0 && ON) vecs[(size_t)r * NB + 16 * w + lr] -= rhs_acc;
+}
+
 __global__ void __launch_bounds__(256, 3) k_fL21(const FrameDev* __restrict__ frames, LevelRef lvl, WgMap map) {
-  __shared__ double Bl[TILE];
+  __shared__ __attribute__((aligned(16))) double Bl[TILE];
   __shared__ double yv[NB];
   LevelCtx cx;
   if (!level_begin(frames, lvl, 0, map, cx)) return;
@@ -802,61 +907,13 @@ __global__ void __launch_bounds__(256, 3) k_fL21(const FrameDev* __restrict__ fr
   const NDFront& f = *cx.f;
   const int r = f.npt + cx.unit;
   if (r >= f.nt) return;
-  const int w = threadIdx.x >> 6, l = threadIdx.x & 63, lr = l & 15, lk = l >> 4;
-  double* vecs = fd.fvec + f.vec_off;
   // known-zero parts are skipped: a wave whose 16 rows lie beyond the true boundary size issues no MFMA and stores
   // nothing (those rows of the pivot columns stay zero), and the front's last pivot tile column only counts up to the
   // true pivot count (blocks of 16)
-  const bool wave_on = 16 * w < min(NB, 7 * f.nb - NB * cx.unit);
-  // (X_c' of the earlier columns is re-read from the tile this thread itself stored it to -- the accumulator layout is
-  //  the A-fragment layout, element for element -- instead of being held in 32 registers per column: two workgroups
-  //  per CU instead of one)
-  double rhs_acc = 0.0;
-  for (int c = 0; c < f.npt; ++c) {
-    {
-      const int ncol = min(NB, f.n1 - NB * c);            // true pivots of this tile column
-      const int nblk = (ncol + 15) >> 4;                  // 16-column blocks with true pivots (also the inner blocks of X_c L_cc^-T)
-      double* At = ftile(fd, f, r, c);
-      double4_t acc[4];
-      if (wave_on) load_c_frags(At, acc);
-      else zero_acc(acc);
-      // acc -= X_c' L(c,c')^T for the earlier pivot columns
-      for (int cp = 0; cp < c; ++cp) {
-        const double* Lt = ftile(fd, f, c, cp);
-        double breg[16], xreg[16];
-        tile_to_regs(Lt, breg);
-        if (wave_on) load_a_frags(ftile(fd, f, r, cp), xreg);
-        __syncthreads();
-        regs_to_lds(Bl, breg);
-        __syncthreads();
-        if (wave_on) tile_ABt_regs_trim<true>(xreg, Bl, acc, 4, nblk);
-      }
-      // X_c = acc L_cc^-T
-      {
-        const double* linv = fd.flinv + f.linv_off + (size_t)c * TILE;
-        double breg[16];
-        tile_to_regs(linv, breg);
-        __syncthreads();
-        regs_to_lds(Bl, breg);
-        if (threadIdx.x < NB) yv[threadIdx.x] = vecs[(size_t)c * NB + threadIdx.x];
-        __syncthreads();
-        double areg[16];
-#pragma unroll
-        for (int ni = 0; ni < 4; ++ni)
-#pragma unroll
-          for (int rr = 0; rr < 4; ++rr) areg[4 * ni + rr] = acc[ni][rr];
-        double4_t xa[4];
-        zero_acc(xa);
-        if (wave_on) {
-          tile_ABt_regs_trim<false, true>(areg, Bl, xa, nblk, nblk);
-          store_c_frags_nblk(At, xa, nblk);
-        }
-        rhs_acc = acc_dot_vec(xa, yv, rhs_acc);
-      }
-    }
-  }
-  rhs_acc = sum_row_lanes(rhs_acc);
-  if (lk == 0 && wave_on) vecs[(size_t)r * NB + 16 * w + lr] -= rhs_acc;
+  // (the wave number as a scalar: the two forms are a branch, not a lane mask)
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (16 * w < min(NB, 7 * f.nb - NB * cx.unit)) fl21_row<true>(fd, f, r, w, Bl, yv);
+  else fl21_row<false>(fd, f, r, w, Bl, yv);
 }
 
 // Trailing update of tile column c, restricted to the PIVOT tile columns that are still to be

@@ -5,6 +5,7 @@
 //   blk_mma / blk_load / blk_store, diag16, potrf64, inverse_assemble64, factor_inverse64p    factor a tile, form its inverse
 //   TileLds<NVEC, NINT>                             the dynamic LDS of a kernel that factors tiles
 //   load_a_frags, load_c_frags, store_c_frags, tile_ABt_regs[_trim], trsm_rows16    tile products in registers
+//   tile_ABt_half_trim, BHalfStream                 a tile product as two half products, its B operand streamed through LDS
 //   damped_lower, tile_to_regs / regs_to_lds / regs_to_diag_tile, stage_diag_tile    staging; the diagonal-tile rule
 //   acc_to_lds                                      a product's result straight to an LDS tile
 //   commit_pivot                                    inverse -> linv, y = L^-1 b
@@ -579,6 +580,62 @@ __device__ __forceinline__ void tile_ABt_regs_trim(const double areg[16], const 
     default: tile_ABt_regs_nblk<NEGATE, 4, LOWER_B>(areg, Bl, acc, kblk); break;
   }
 }
+
+// ... and one HALF of it at a time (HALF 0: the inner blocks 0 and 1 = inner columns 0..31, HALF 1: blocks 2 and 3), for a B
+// operand that passes through LDS in half tiles (BHalfStream below).  HALF 0 then HALF 1 issue the MFMAs of
+// tile_ABt_regs_trim in the same order.
+template <bool NEGATE, int NBLK, bool LOWER_B, int HALF>
+__device__ __forceinline__ void tile_ABt_half_nblk(const double areg[16], const double* Bl, double4_t acc[4], int kblk) {
+  const int l = threadIdx.x & 63, lr = l & 15, lk = l >> 4;
+#pragma unroll
+  for (int kb = 2 * HALF; kb < 2 * HALF + 2; ++kb) {
+    if (kb < kblk) {
+#pragma unroll
+      for (int k4 = 0; k4 < 4; ++k4) {
+        const int ks = 4 * kb + k4;
+        const double a = NEGATE ? -areg[ks] : areg[ks];
+#pragma unroll
+        for (int ni = LOWER_B ? kb : 0; ni < NBLK; ++ni) {
+          const double b = Bl[(16 * ni + lr) + (4 * ks + lk) * LD];
+          acc[ni] = __builtin_amdgcn_mfma_f64_16x16x4f64(b, a, acc[ni], 0, 0, 0);
+        }
+        if (k4 == 1) __builtin_amdgcn_sched_barrier(0);   // (the operand reads of two k-steps at a time ahead of their MFMAs)
+      }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+template <bool NEGATE, bool LOWER_B, int HALF>
+__device__ __forceinline__ void tile_ABt_half_trim(const double areg[16], const double* Bl, double4_t acc[4], int kblk,
+                                                   int nblk) {
+  switch (nblk) {
+    case 1: tile_ABt_half_nblk<NEGATE, 1, LOWER_B, HALF>(areg, Bl, acc, kblk); break;
+    case 2: tile_ABt_half_nblk<NEGATE, 2, LOWER_B, HALF>(areg, Bl, acc, kblk); break;
+    case 3: tile_ABt_half_nblk<NEGATE, 3, LOWER_B, HALF>(areg, Bl, acc, kblk); break;
+    default: tile_ABt_half_nblk<NEGATE, 4, LOWER_B, HALF>(areg, Bl, acc, kblk); break;
+  }
+}
+
+// The B operand of a run of tile products as a stream of HALF tiles (32 inner columns = 2048 contiguous doubles of a
+// column-major tile) through one LDS tile: 16 bytes per lane and instruction, the next half in flight (v) while the current one
+// is on the MFMA.  Per half: put() the half that has arrived into its side of Bl, request() the one after it -- which may be
+// the first half of the NEXT product's tile -- one __syncthreads(), the MFMAs.  The halves alternate 0, 1, 0, 1, ...: a side of
+// Bl is rewritten two halves after it was read, with the barrier of the half between them in between.  Tiles and Bl: 16-byte
+// aligned.  256 threads.
+typedef double double2_t __attribute__((ext_vector_type(2)));
+struct BHalfStream {
+  double2_t v[4];
+  __device__ __forceinline__ void request(const double* tile, int half) {
+    const double2_t* src = reinterpret_cast<const double2_t*>(tile) + half * (TILE / 4);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = src[threadIdx.x + 256 * e];
+  }
+  __device__ __forceinline__ void put(double* Bl, int half) const {
+    double2_t* dst = reinterpret_cast<double2_t*>(Bl) + half * (TILE / 4);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) dst[threadIdx.x + 256 * e] = v[e];
+  }
+};
 
 __device__ __forceinline__ void store_c_frags(double* __restrict__ Cg, const double4_t acc[4]) {
   const int l = threadIdx.x & 63, w = threadIdx.x >> 6, lr = l & 15, lk = l >> 4;
