@@ -127,8 +127,9 @@ static int reset_slot(slm_solver* s, Slot& sl, const slm_frame* f, hipStream_t s
   h.rhs = sl.rhs.p;
   // the buffers of one size for good: allocated by the slot's first bind (st, dbg and rec exactly, outside the counters)
   if (!sl.loss_part) {
-    HIPCHK(grow(sl.loss_part, loss_part_doubles(s)));
-    HIPCHK(hipMemsetAsync(sl.loss_part, 0, sizeof(double) * loss_part_doubles(s), st));
+    const size_t n_part = loss_parts(s, 0).doubles;
+    HIPCHK(grow(sl.loss_part, n_part));
+    HIPCHK(hipMemsetAsync(sl.loss_part, 0, sizeof(double) * n_part, st));
   }
   HIPCHK(sl.st.grow(1, 1));
 #ifdef SLM_STAMPS

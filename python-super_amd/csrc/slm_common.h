@@ -347,6 +347,23 @@ __device__ __forceinline__ void atomic_add_f64(double* p, double v) {
   unsafeAtomicAdd(p, v);
 }
 
+// per-entry assembly of one residual row (NR = 7 K entries on the nodes id[0..K)): row^T row into the lower band, -row^T r
+// into rhs.  Only takes pointers: a row in LDS is indexed in place, a private one goes to scratch (k_data_grad).
+template <int NR>
+__device__ __forceinline__ void band_scatter_row(const FrameDev& fd, const int* id, const double* row, double r) {
+#pragma unroll 1
+  for (int a = 0; a < NR; ++a) {
+    const int ia = 7 * id[a / 7] + a % 7;
+    const double ja = row[a];
+    atomic_add_f64(fd.rhs + ia, -ja * r);
+#pragma unroll 1
+    for (int b = 0; b < NR; ++b) {
+      const int ib = 7 * id[b / 7] + b % 7;
+      if (ia >= ib) atomic_add_f64(band_entry(fd, ia, ib), ja * row[b]);
+    }
+  }
+}
+
 __device__ __forceinline__ double wave_sum(double x) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) x += __shfl_down(x, o, 64);
@@ -366,4 +383,13 @@ __device__ __forceinline__ double block_sum(double x, double* smem /* >= 16 doub
   }
   __syncthreads();
   return r;
+}
+
+// Loss partial of block blockIdx.x of a term behind the regularisers' (slm_solver.h LossParts): the pair {s, 0} at `part`
+// doubles behind the start of the regularisers' partials -- k_accept adds both members of every pair to the loss.  A slot
+// without the term's inputs stores zeros, so k_accept may sum the pairs of every slot of an enabled solver.  Thread 0 only.
+__device__ __forceinline__ void term_loss_store(const FrameDev& fd, int part, double s) {
+  double* reg = fd.loss_part + 2 * (size_t)fd.n_loss_part;
+  reg[part + 2 * blockIdx.x] = s;
+  reg[part + 2 * blockIdx.x + 1] = 0.0;
 }

@@ -12,13 +12,12 @@ struct CorrDev {
   int32_t pad;
 };
 
-#define SLM_CORR_BLOCKS 64   // loss partials of the term per slot: behind the regularisers' in FrameDev::loss_part
+#define SLM_CORR_BLOCKS 64   // loss partials of the term per slot (LossParts, slm_solver.h)
 
-// corr_part: doubles from the start of the regularisers' partials (loss_part + 2 n_loss_part) to the term's; cnt_part: the
-// same to its kept counts.  mode 1 point-point, 2 point-plane; lam = the term's weight.
+// corr_part / cnt_part: where the term's loss pairs and its kept counts go (LossParts, slm_solver.h).  mode 1 point-point,
+// 2 point-plane; lam = the term's weight.
 void launch_corr_targets(const FrameDev*, const CorrDev*, int slot, int N, const float* flow, hipStream_t);
 void launch_corr_grad_pairs(const FrameDev*, const CorrDev*, int n_frames, int max_pos, int K, int mode, double lam, hipStream_t);
 void launch_corr_grad(const FrameDev*, const CorrDev*, int n_frames, int maxN, int K, int mode, double lam, hipStream_t);
 void launch_corr_loss(const FrameDev*, const CorrDev*, int n_frames, int K, int mode, double lam, int use_delta, int corr_part,
                       int cnt_part, hipStream_t);
-void launch_corr_loss_out(const FrameDev*, int slot, int corr_part, int cnt_part, double* out, hipStream_t);

@@ -6,7 +6,7 @@
 //                         between k_data_grad_pairs and k_pair_scatter
 //   k_corr_grad         : the same into the band with per-entry atomics (slm_assemble, slots without a multifrontal plan)
 //   k_corr_loss         : sum_valid |r|^2 at beta or at the trial point, per-block partials behind the regularisers'
-//   k_corr_loss_out     : the partials of one slot summed in a fixed order (slm_corr_loss)
+//                         (read out for slm_corr_loss by k_term_loss_out, slm_misc.hip)
 //
 // Residuals (lambda = weight): mode 1 r = lambda (T(p) - o), three rows lambda [w_k c^T dR(q_k)(p - g_k)/dq_k | w_k c] with
 // c = e_x, e_y, e_z; mode 2 r = lambda n.(T(p) - o), the one row with c = n.  The targets do not move with beta: nothing
@@ -14,6 +14,7 @@
 #include "slm_corr.h"
 #include "slm_gf_sample.h"
 #include "slm_host.h"
+#include "slm_pairs.h"
 
 // the skinning state of surfel i at the node table npk: neighbours, T(p) - o, the target normal
 template <int KK>
@@ -82,28 +83,20 @@ __global__ void __launch_bounds__(256) k_corr_targets(const FrameDev* __restrict
   cd.valid[i] = ok ? 1 : 0;
 }
 
-// The term's share of the pair records, in the manner of k_data_grad_pairs (slm_data.hip): one wave per 64 positions of
-// sf_perm, the rows of its surfels in LDS in the canonical neighbour order with the residual as one more column (A = [row | r]),
-// per RUN of surfels with one neighbour set the lower tile pairs of A^T A on v_mfma_f64_16x16x4_f64, lane = record entry
-// atomics into pairbuf.  NC rows per surfel (mode 1: the three components; mode 2: one): k-row NC * position + component, so
-// a run of positions [rs, re) is the run of k-rows [NC rs, NC re) and the component rows are simply further k-rows of the
-// same Gram.  The plan (blk_key, sf_pidx, sf_perm) is built from all surfels, so every block the term needs has a record.
+// The term's share of the pair records: skin, the NC rows of a surfel with a correspondence (mode 1: the three components;
+// mode 2: one) into the wave's LDS, then the run Gram -- the design and the record order are above PairLds (slm_pairs.h).
 // The matched count behind the records (SLM_VK_TAIL) is the ICP term's: not touched here.
 // grid = (ceil(max N / 64), n_frames), ONE wave per workgroup
 template <int KK, int NC>
 __global__ void __launch_bounds__(64) k_corr_grad_pairs(const FrameDev* __restrict__ frames, const CorrDev* __restrict__ corr,
                                                          double lam) {
-  typedef double double4_t __attribute__((ext_vector_type(4)));
-  constexpr int NP = KK * (KK + 1) / 2, NR = 7 * KK, NCOL = NR + 1, NT = (NCOL + 15) / 16, NTP = NT * (NT + 1) / 2;
-  constexpr int LDR = 16 * NT + 1;   // odd row stride
+  typedef PairLds<KK, NC> L;
   constexpr int MODE = NC == 3 ? 1 : 2;
-  __shared__ double s_row[NC * 64 * LDR];
-  __shared__ int s_pi[64 * NP];
-  __shared__ int s_cid[64 * KK];
+  __shared__ L lds;
   const FrameDev& fd = frames[blockIdx.y];
   const CorrDev& cd = corr[blockIdx.y];
   if (!fd.bound || fd.st->stopped || fd.f.K != KK || !fd.vk_ready || !cd.has) return;
-  const int l = threadIdx.x, lr = l & 15, lk = l >> 4;
+  const int l = threadIdx.x;
   const int pos = blockIdx.x * 64 + l;
   bool on = false;
   int i = 0;
@@ -113,113 +106,35 @@ __global__ void __launch_bounds__(64) k_corr_grad_pairs(const FrameDev* __restri
   }
   const unsigned long long m = __ballot(on);
   if (!m) return;
-  {
-#pragma unroll
-    for (int comp = 0; comp < NC; ++comp) {
-      double* rw = s_row + (NC * l + comp) * LDR;
-#pragma unroll
-      for (int c = 0; c < 16 * NT; ++c) rw[c] = 0.0;
-    }
-    if (on) {
-      CorrSkin<KK> sk;
-      corr_skin<KK>(fd, cd, fd.node_pk, i, sk);
-#pragma unroll
-      for (int k = 0; k < KK; ++k) {
-        int rank = 0;   // (canonical slot: the ids are distinct, slm_bind_frame refuses a row that repeats one)
-#pragma unroll
-        for (int j = 0; j < KK; ++j) rank += (sk.id[j] < sk.id[k]) ? 1 : 0;
-        s_cid[l * KK + rank] = sk.id[k];
-        const double lw = lam * sk.w[k];
-#pragma unroll
-        for (int comp = 0; comp < NC; ++comp) {
-          const d3 c = corr_c(MODE, comp, sk.n);
-          double jq[4];
-          quat_jac_row(sk.qw[k], sk.qv[k], sk.dk[k], c, jq);
-          double* rw = s_row + (NC * l + comp) * LDR + 7 * rank;
-          rw[0] = lw * jq[0];
-          rw[1] = lw * jq[1];
-          rw[2] = lw * jq[2];
-          rw[3] = lw * jq[3];
-          rw[4] = lw * c.x;
-          rw[5] = lw * c.y;
-          rw[6] = lw * c.z;
-        }
-      }
-#pragma unroll
-      for (int comp = 0; comp < NC; ++comp) s_row[(NC * l + comp) * LDR + NR] = lam * dot(corr_c(MODE, comp, sk.n), sk.e);
-#pragma unroll
-      for (int sl = 0; sl < NP; ++sl) s_pi[l * NP + sl] = fd.sf_pidx[(size_t)NP * i + sl];
-    }
-  }
-  __syncthreads();
-  // runs: a surfel with a correspondence starts one when its neighbour set differs from the previous such surfel's
-  bool start = false;
+  pair_zero_rows(lds, l);
   if (on) {
-    const unsigned long long below = m & ((1ull << l) - 1ull);
-    if (!below) start = true;
-    else {
-      const int pl = 63 - __builtin_clzll(below);
+    CorrSkin<KK> sk;
+    corr_skin<KK>(fd, cd, fd.node_pk, i, sk);
 #pragma unroll
-      for (int k = 0; k < KK; ++k) start = start || (s_cid[l * KK + k] != s_cid[pl * KK + k]);
-    }
-  }
-  unsigned long long starts = __ballot(start);
-  // accumulators -> LDS -> RECORD order (lane e < 56 owns entry e of every pair record), as k_data_grad_pairs
-  __shared__ double s_g[16 * NT * LDR];
-  double* pb = fd.pairbuf;
-  const int eca = l / 7, ecb = l - 7 * eca;
-  while (starts) {
-    const int rs = __builtin_ctzll(starts);   // uniform
-    starts &= starts - 1;
-    const int re = starts ? __builtin_ctzll(starts) : 64;
-    const int qs = NC * rs, qe = NC * re;     // the run's k-rows
-    double4_t acc[NTP];
+    for (int k = 0; k < KK; ++k) {
+      const int rank = pair_rank<KK>(sk.id, k);
+      lds.s_cid[l * KK + rank] = sk.id[k];
+      const double lw = lam * sk.w[k];
 #pragma unroll
-    for (int tp = 0; tp < NTP; ++tp) acc[tp] = double4_t{0.0, 0.0, 0.0, 0.0};
-    for (int ks = qs >> 2; ks <= (qe - 1) >> 2; ++ks) {
-      const int q = 4 * ks + lk;
-      const bool inrun = q >= qs && q < qe;
-      double v[NT], vm[NT];
-#pragma unroll
-      for (int t = 0; t < NT; ++t) {
-        v[t] = s_row[q * LDR + 16 * t + lr];
-        vm[t] = inrun ? v[t] : 0.0;
+      for (int comp = 0; comp < NC; ++comp) {
+        const d3 c = corr_c(MODE, comp, sk.n);
+        double jq[4];
+        quat_jac_row(sk.qw[k], sk.qv[k], sk.dk[k], c, jq);
+        double* rw = lds.s_row + (NC * l + comp) * L::LDR + 7 * rank;
+        rw[0] = lw * jq[0];
+        rw[1] = lw * jq[1];
+        rw[2] = lw * jq[2];
+        rw[3] = lw * jq[3];
+        rw[4] = lw * c.x;
+        rw[5] = lw * c.y;
+        rw[6] = lw * c.z;
       }
-      int tp = 0;
-#pragma unroll
-      for (int ti = 0; ti < NT; ++ti)
-#pragma unroll
-        for (int tj = 0; tj <= ti; ++tj, ++tp) acc[tp] = __builtin_amdgcn_mfma_f64_16x16x4f64(vm[tj], v[ti], acc[tp], 0, 0, 0);
     }
-    {
-      int tp = 0;
 #pragma unroll
-      for (int ti = 0; ti < NT; ++ti)
-#pragma unroll
-        for (int tj = 0; tj <= ti; ++tj, ++tp)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) s_g[(16 * ti + lr) * LDR + 16 * tj + lk + 4 * r] = acc[tp][r];
-    }
-    __syncthreads();
-    const int* pi = s_pi + rs * NP;
-    int sl = 0;
-#pragma unroll 1
-    for (int ra = 0; ra < KK; ++ra)
-#pragma unroll 1
-      for (int rb = 0; rb <= ra; ++rb, ++sl) {
-        double val = 0.0;
-        bool put = false;
-        if (l < 49) {
-          put = ra > rb || eca >= ecb;   // (a diagonal pair's block is symmetric: its lower part is what is placed)
-          val = s_g[(7 * ra + eca) * LDR + 7 * rb + ecb];
-        } else if (l < 56 && ra == rb) {
-          put = true;
-          val = s_g[NR * LDR + 7 * rb + (l - 49)];
-        }
-        if (put) atomic_add_f64(pb + (size_t)pi[sl] * SLM_WREC + l, val);
-      }
-    __syncthreads();   // s_g is rewritten by the next run
+    for (int comp = 0; comp < NC; ++comp) lds.s_row[(NC * l + comp) * L::LDR + L::NR] = lam * dot(corr_c(MODE, comp, sk.n), sk.e);
+    pair_load_pidx(lds, fd, l, i);
   }
+  pair_gram(lds, fd.pairbuf, on, m);
 }
 
 // per-entry form (k_data_grad's sums): row^T row into the lower band, -row^T r into rhs.  The row and its node ids sit in
@@ -260,24 +175,13 @@ __global__ void __launch_bounds__(64) k_corr_grad(const FrameDev* __restrict__ f
       row[7 * k + 5] = lw * c.y;
       row[7 * k + 6] = lw * c.z;
     }
-#pragma unroll 1
-    for (int a = 0; a < NR; ++a) {
-      const int ia = 7 * id[a / 7] + a % 7;
-      const double ja = row[a];
-      atomic_add_f64(fd.rhs + ia, -ja * r);
-#pragma unroll 1
-      for (int b = 0; b < NR; ++b) {
-        const int ib = 7 * id[b / 7] + b % 7;
-        if (ia >= ib) atomic_add_f64(band_entry(fd, ia, ib), ja * row[b]);
-      }
-    }
+    band_scatter_row<NR>(fd, id, row, r);
   }
 }
 
-// grid = (SLM_CORR_BLOCKS, n_frames); grid-stride over surfels.  Block b of a slot writes reg[corr_part + 2 b] = its sum
-// and reg[corr_part + 2 b + 1] = 0 (reg = the regularisers' partials: k_accept adds both slots of a pair to the loss) and
-// its kept count to reg[cnt_part + b]; a slot without correspondences writes zeros, so k_accept may sum the slots of every
-// slot of an enabled solver.
+// grid = (SLM_CORR_BLOCKS, n_frames); grid-stride over surfels.  Block b of a slot stores its sum as the pair b at corr_part
+// (term_loss_store) and its kept count to reg[cnt_part + b], reg = the regularisers' partials; a slot without
+// correspondences stores zeros.
 template <int KK>
 __global__ void __launch_bounds__(256) k_corr_loss(const FrameDev* __restrict__ frames, const CorrDev* __restrict__ corr, int mode,
                                                     double lam, int use_delta, int corr_part, int cnt_part) {
@@ -305,32 +209,12 @@ __global__ void __launch_bounds__(256) k_corr_loss(const FrameDev* __restrict__ 
   const double s = block_sum(acc, sm);
   const double c = block_sum((double)cnt, sm);
   if (threadIdx.x == 0) {
-    double* reg = fd.loss_part + 2 * (size_t)fd.n_loss_part;
-    reg[corr_part + 2 * blockIdx.x] = s;
-    reg[corr_part + 2 * blockIdx.x + 1] = 0.0;
-    reg[cnt_part + blockIdx.x] = c;
+    term_loss_store(fd, corr_part, s);
+    fd.loss_part[2 * (size_t)fd.n_loss_part + cnt_part + blockIdx.x] = c;
   }
 }
 
-// out[0] = the term's loss, out[1] = its kept count: the partials of slot `slot` in a fixed order.  one block of 64 threads
-__global__ void __launch_bounds__(64) k_corr_loss_out(const FrameDev* __restrict__ frames, int slot, int corr_part, int cnt_part,
-                                                       double* __restrict__ out) {
-  const FrameDev& fd = frames[slot];
-  const double* reg = fd.loss_part + 2 * (size_t)fd.n_loss_part;
-  double s = 0.0, c = 0.0;
-  for (int b = threadIdx.x; b < SLM_CORR_BLOCKS; b += blockDim.x) {
-    s += reg[corr_part + 2 * b];
-    c += reg[cnt_part + b];
-  }
-  s = wave_sum(s);
-  c = wave_sum(c);
-  if (threadIdx.x == 0) {
-    out[0] = s;
-    out[1] = c;
-  }
-}
-
-// ---- host launchers (called from slm_api.hip) ------------------------------------
+// ---- host launchers (called from slm_lm.hip, slm_terms.hip) ------------------------------------
 void launch_corr_targets(const FrameDev* frames_dev, const CorrDev* corr_dev, int slot, int N, const float* flow, hipStream_t st) {
   if (N <= 0) return;
   hipLaunchKernelGGL(k_corr_targets, dim3((N + 255) / 256), dim3(256), 0, st, frames_dev, corr_dev, slot, flow);
@@ -359,8 +243,4 @@ void launch_corr_loss(const FrameDev* frames_dev, const CorrDev* corr_dev, int n
   const dim3 grid(SLM_CORR_BLOCKS, n_frames);
   SLM_K_DISPATCH(K, hipLaunchKernelGGL(k_corr_loss<KK>, grid, dim3(256), 0, st, frames_dev, corr_dev, mode, lam, use_delta, corr_part,
                                        cnt_part));
-}
-
-void launch_corr_loss_out(const FrameDev* frames_dev, int slot, int corr_part, int cnt_part, double* out, hipStream_t st) {
-  hipLaunchKernelGGL(k_corr_loss_out, dim3(1), dim3(64), 0, st, frames_dev, slot, corr_part, cnt_part, out);
 }

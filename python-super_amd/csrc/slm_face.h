@@ -13,12 +13,10 @@ struct FaceDev {
   int32_t ready;                // 1 once a bind has checked the ids against J and placed the six pairs in the slot's plan
 };
 
-#define SLM_FACE_BLOCKS 16   // loss partials of the term per slot: behind the correspondence term's in FrameDev::loss_part
+#define SLM_FACE_BLOCKS 16   // loss partials of the term per slot (LossParts, slm_solver.h)
 
-// face_part: doubles from the start of the regularisers' partials (loss_part + 2 n_loss_part) to the term's; lam = the
-// term's weight.
+// face_part: where the term's loss pairs go (LossParts, slm_solver.h); lam = the term's weight.
 void launch_face_grad(const FrameDev*, const FaceDev*, int n_frames, int max_tri, double lam, hipStream_t);
 void launch_face_grad_band(const FrameDev*, const FaceDev*, int n_frames, int max_tri, double lam, hipStream_t);
 void launch_face_loss(const FrameDev*, const FaceDev*, int n_frames, double lam, int use_delta, int face_part, hipStream_t);
-void launch_face_loss_out(const FrameDev*, const FaceDev*, int slot, int face_part, double* out, hipStream_t);
 void launch_face_bandwidth(const int32_t* tri, int n_tri, int* out, hipStream_t);

@@ -5,7 +5,7 @@
 //                        between k_data_grad_pairs and k_pair_scatter
 //   k_face_grad_band   : the same into the band with per-entry atomics (slm_assemble)
 //   k_face_loss        : sum_t r_t^2 at beta or at the trial point, per-block partials behind the correspondence term's
-//   k_face_loss_out    : the partials of one slot summed in a fixed order (slm_face_loss)
+//                        (read out for slm_face_loss by k_term_loss_out, slm_misc.hip)
 //   k_face_bandwidth   : tile half-bandwidth the mesh's pairs need (ensure_band)
 //
 // Residual of triangle t with nodes (i0, i1, i2), lambda = weight: v_a = g_a + beta[a, 4:7] (rotations do not enter),
@@ -118,9 +118,8 @@ __global__ void __launch_bounds__(64) k_face_grad_band(const FrameDev* __restric
   }
 }
 
-// grid = (SLM_FACE_BLOCKS, n_frames); grid-stride over triangles.  Block b of a slot writes reg[face_part + 2 b] = its sum
-// and reg[face_part + 2 b + 1] = 0 (reg = the regularisers' partials: k_accept adds both slots of a pair to the loss); a
-// slot without a mesh writes zeros, so k_accept may sum the slots of every slot of an enabled solver.
+// grid = (SLM_FACE_BLOCKS, n_frames); grid-stride over triangles.  Block b of a slot stores its sum as the pair b at face_part
+// (term_loss_store); a slot without a mesh stores zeros.
 __global__ void __launch_bounds__(256) k_face_loss(const FrameDev* __restrict__ frames, const FaceDev* __restrict__ face, double lam,
                                                     int use_delta, int face_part) {
   __shared__ double sm[16];
@@ -137,26 +136,7 @@ __global__ void __launch_bounds__(256) k_face_loss(const FrameDev* __restrict__ 
     }
   }
   const double s = block_sum(acc, sm);
-  if (threadIdx.x == 0) {
-    double* reg = fd.loss_part + 2 * (size_t)fd.n_loss_part;
-    reg[face_part + 2 * blockIdx.x] = s;
-    reg[face_part + 2 * blockIdx.x + 1] = 0.0;
-  }
-}
-
-// out[0] = the term's loss, out[1] = its triangle count: the partials of slot `slot` in a fixed order.  one wave
-__global__ void __launch_bounds__(64) k_face_loss_out(const FrameDev* __restrict__ frames, const FaceDev* __restrict__ face, int slot,
-                                                       int face_part, double* __restrict__ out) {
-  const FrameDev& fd = frames[slot];
-  const double* reg = fd.loss_part + 2 * (size_t)fd.n_loss_part;
-  double s = 0.0;
-  for (int b = threadIdx.x; b < SLM_FACE_BLOCKS; b += blockDim.x) s += reg[face_part + 2 * b];
-  s = wave_sum(s);
-  if (threadIdx.x == 0) {
-    const bool on = face[slot].ready != 0;
-    out[0] = on ? s : 0.0;
-    out[1] = on ? (double)face[slot].n_tri : 0.0;
-  }
+  if (threadIdx.x == 0) term_loss_store(fd, face_part, s);
 }
 
 // max over the triangles of tile(7 hi + 6) - tile(7 lo), as k_bandwidth's over the KNN tables (nothing indexes with the ids)
@@ -172,7 +152,7 @@ __global__ void __launch_bounds__(256) k_face_bandwidth(const int32_t* __restric
   if ((threadIdx.x & 63) == 0 && wmax > 0) atomicMax(out, wmax);
 }
 
-// ---- host launchers (called from slm_lm.hip, slm_bind.hip) ---------------------------
+// ---- host launchers (called from slm_lm.hip, slm_terms.hip, slm_bind.hip) ---------------------------
 void launch_face_grad(const FrameDev* frames_dev, const FaceDev* face_dev, int n_frames, int max_tri, double lam, hipStream_t st) {
   if (max_tri <= 0) return;
   const long long n = 6ll * max_tri;
@@ -187,10 +167,6 @@ void launch_face_grad_band(const FrameDev* frames_dev, const FaceDev* face_dev, 
 void launch_face_loss(const FrameDev* frames_dev, const FaceDev* face_dev, int n_frames, double lam, int use_delta, int face_part,
                       hipStream_t st) {
   hipLaunchKernelGGL(k_face_loss, dim3(SLM_FACE_BLOCKS, n_frames), dim3(256), 0, st, frames_dev, face_dev, lam, use_delta, face_part);
-}
-
-void launch_face_loss_out(const FrameDev* frames_dev, const FaceDev* face_dev, int slot, int face_part, double* out, hipStream_t st) {
-  hipLaunchKernelGGL(k_face_loss_out, dim3(1), dim3(64), 0, st, frames_dev, face_dev, slot, face_part, out);
 }
 
 void launch_face_bandwidth(const int32_t* tri, int n_tri, int* out, hipStream_t st) {

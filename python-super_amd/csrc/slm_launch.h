@@ -1,5 +1,5 @@
 // slm_launch.h -- the launch functions of the LM solver's kernels, declared once, with their default arguments:
-// the LM host (slm_api.hip, slm_bind.hip, slm_lm.hip) calls them; the file that holds the kernels defines them and includes this too, so its definitions are
+// the LM host (slm_api.hip, slm_bind.hip, slm_lm.hip, slm_terms.hip) calls them; the file that holds the kernels defines them and includes this too, so its definitions are
 // compiled against these declarations (a drifted return type or a repeated default argument does not compile; a
 // drifted parameter list is still only caught when the library is loaded).
 #pragma once
@@ -59,4 +59,7 @@ void launch_pack_target(int, const float*, const float*, float4*, hipStream_t);
 void launch_pack_target_px(int, const int*, const uint8_t*, const float*, const float*, float4*, hipStream_t);
 void launch_accept(const FrameDev*, int, int, int, int, hipStream_t, int* reuse = nullptr, int eval_pass = 0);
 void launch_loss_out(const FrameDev*, int, int, double*, hipStream_t);
+// (a term's pairs at `part` and its nb kept counts at cnt_part or, with a FaceDev array, its mesh's triangle count)
+struct FaceDev;
+void launch_term_loss_out(const FrameDev*, int slot, int part, int nb, int cnt_part, const FaceDev* face, double* out, hipStream_t);
 void launch_zero_reg_part(const FrameDev*, int, int, hipStream_t);

@@ -1,7 +1,7 @@
 // slm_lm.hip -- the LM step of the LM host: the dimensions of a batch of bound slots, the choice of the solver's form,
 // the stages of an iteration in the batch's data form (enqueue_*), and the entry points made of them: slm_run, the
-// sharded step with its exchange, the parity entry points (slm_assemble / slm_loss / slm_solve) and the
-// flow-correspondence term, the face term and the per-residual data weights.  Host side only orchestrates launches.
+// sharded step with its exchange and the parity entry points (slm_assemble / slm_loss / slm_solve).  The entry points of
+// the opt-in terms are slm_terms.hip.  Host side only orchestrates launches.
 #include "slm_solver.h"
 
 namespace {
@@ -10,10 +10,11 @@ struct BatchDims {
   int max_pos = 0, max_blocks = 0, maxP = 0;
   bool corr = false;   // some slot of the batch has correspondences bound (the term's Jacobian pass runs)
   int max_tri = 0;     // most triangles of a slot's face mesh (0: no slot has one, the face term's Jacobian pass does not run)
-  int face_part = 0;   // doubles from the regularisers' partials to the face term's
+  const CorrDev* corr_dev = nullptr;   // the batch's first descriptors of the two terms (null: the term is off)
+  const FaceDev* face_dev = nullptr;
+  LossParts parts{};   // where the terms' loss partials sit, and what k_accept sums behind the data partials
   bool weights = false;   // the solver carries per-residual data weights (slm_enable_data_weights): the weighted kernels run
   DataWArgs wargs{};      // ... with these arguments (the batch's first semantic descriptor, seg_mode, pp_max)
-  int n_acc_part = 0;  // what k_accept sums behind the data partials: the regularisers' pairs, on an enabled solver the term's too
   int K = 0;        // num_neighbors of the batch's slots (-1: they differ -- refused by the callers of the per-surfel kernels)
   int gram_variants = 0;   // bit0: workgroup-merged records in use, bit1: per-run slab in use
   bool nd = true;   // every slot of the batch has a nested-dissection plan (false: the block-banded solver)
@@ -104,9 +105,9 @@ BatchDims dims_of(slm_solver* s, int first, int n, bool band = false) {
   }
   if (s->cfg.use_arap || s->cfg.use_rot)
     d.n_reg_part = std::min(kRegBlocksMax, (d.maxJKe + 255) / 256);
-  d.n_acc_part = d.n_reg_part + (s->corr_mode ? kCorrBlocks : 0);
-  d.face_part = 2 * d.n_acc_part;
-  if (s->face_on) d.n_acc_part += kFaceBlocks;
+  d.parts = loss_parts(s, d.n_reg_part);
+  if (s->corr_mode) d.corr_dev = s->corr_dev + first;
+  if (s->face_on) d.face_dev = s->face_dev + first;
   d.weights = s->weights_on;
   d.wargs = DataWArgs{s->w_seg_mode ? s->w_dev.p + first : nullptr, s->w_pp_max, s->w_seg_mode, 0};
   return d;
@@ -185,13 +186,13 @@ void enqueue_jacobian(slm_solver* s, const FrameDev* fr, int n, const BatchDims&
       break;
     case DataForm::pairs:   // per-pair records (zeroed, then filled; the correspondence term adds into them)
       launch_data_grad_pairs(fr, n, d.maxN, d.K, w, st, d.weights ? &d.wargs : nullptr);
-      if (d.corr) launch_corr_grad_pairs(fr, s->corr_dev + (fr - s->frames_dev), n, d.maxN, d.K, s->corr_mode, s->corr_w, st);
-      if (d.max_tri) launch_face_grad(fr, s->face_dev + (fr - s->frames_dev), n, d.max_tri, s->face_w, st);
+      if (d.corr) launch_corr_grad_pairs(fr, d.corr_dev, n, d.maxN, d.K, s->corr_mode, s->corr_w, st);
+      if (d.max_tri) launch_face_grad(fr, d.face_dev, n, d.max_tri, s->face_w, st);
       break;
     case DataForm::per_entry:
       launch_data_grad(fr, n, d.maxN, d.K, w, st, d.weights ? &d.wargs : nullptr);
-      if (d.corr) launch_corr_grad(fr, s->corr_dev + (fr - s->frames_dev), n, d.maxN, d.K, s->corr_mode, s->corr_w, st);
-      if (d.max_tri) launch_face_grad_band(fr, s->face_dev + (fr - s->frames_dev), n, d.max_tri, s->face_w, st);
+      if (d.corr) launch_corr_grad(fr, d.corr_dev, n, d.maxN, d.K, s->corr_mode, s->corr_w, st);
+      if (d.max_tri) launch_face_grad_band(fr, d.face_dev, n, d.max_tri, s->face_w, st);
       break;
     case DataForm::none: break;
   }
@@ -227,20 +228,26 @@ void enqueue_data_loss(slm_solver* s, const FrameDev* fr, int n, const BatchDims
     launch_data_loss(fr, n, kLossBlocks, d.K, s->cfg.w_data, at_beta ? 0 : 1, st, d.weights ? &d.wargs : nullptr);
   // the correspondence term's partials, behind the regularisers' (every slot of an enabled solver: zeros without targets)
   if (s->corr_mode && d.K >= 1)
-    launch_corr_loss(fr, s->corr_dev + (fr - s->frames_dev), n, d.K, s->corr_mode, s->corr_w, at_beta ? 0 : 1, 2 * d.n_reg_part,
-                     corr_cnt_part(s), st);
+    launch_corr_loss(fr, d.corr_dev, n, d.K, s->corr_mode, s->corr_w, at_beta ? 0 : 1, d.parts.corr, d.parts.corr_cnt, st);
   // the face term's, behind those (likewise: zeros without a mesh)
-  if (s->face_on) launch_face_loss(fr, s->face_dev + (fr - s->frames_dev), n, s->face_w, at_beta ? 0 : 1, d.face_part, st);
+  if (s->face_on) launch_face_loss(fr, d.face_dev, n, s->face_w, at_beta ? 0 : 1, d.parts.face, st);
 }
 }  // namespace
 
 // With a semantic weight on, every slot of [first, first + n) needs its semantic inputs: no silent unweighted run.
-static int weights_check(const slm_solver* s, const char* fn, int first, int n) {
+int weights_check(const slm_solver* s, const char* fn, int first, int n) {
   if (!s->w_seg_mode) return SLM_OK;
   for (int i = first; i < first + n; ++i)
     if (!s->slots[i].wdev.has)
       return fail(SLM_ERR_UNBOUND, std::string(fn) + ": slot " + std::to_string(i) +
                                        " has no semantic inputs; call slm_bind_data_semantic after slm_bind_frame");
+  return SLM_OK;
+}
+
+int clear_flags(slm_solver* s, int slot, hipStream_t st) {
+  // stopped / counters live at the tail of LMState: zero {iter..pad}
+  LMState* p = s->slots[slot].h.st;
+  HIPCHK(hipMemsetAsync(&p->stopped, 0, sizeof(int32_t) * 4, st));
   return SLM_OK;
 }
 
@@ -431,7 +438,7 @@ static void enqueue_lm_iteration(slm_solver* s, int first, int n, const BatchDim
   mark();
   enqueue_data_loss(s, fr, n, d, st, false);
   mark();
-  launch_accept(fr, n, c.phase_test, d.n_acc_part, std::max(c.num_iterations, 1), st, d.accept_reuse, d.accept_eval);
+  launch_accept(fr, n, c.phase_test, d.parts.n_acc_part, std::max(c.num_iterations, 1), st, d.accept_reuse, d.accept_eval);
   mark();
 }
 
@@ -463,13 +470,6 @@ int slm_run(slm_solver* s, int32_t n_frames, void* stream) {
   // wrote none (per-entry atomics) leaves nothing to reuse.
   if (!d.accept_reuse) HIPCHK(hipMemsetAsync(s->reuse_dev, 0, sizeof(int) * n_frames, st));
   HIPCHK(hipGetLastError());
-  return SLM_OK;
-}
-
-static int clear_flags(slm_solver* s, int slot, hipStream_t st) {
-  // stopped / counters live at the tail of LMState: zero {iter..pad}
-  LMState* p = s->slots[slot].h.st;
-  HIPCHK(hipMemsetAsync(&p->stopped, 0, sizeof(int32_t) * 4, st));
   return SLM_OK;
 }
 
@@ -532,252 +532,6 @@ int slm_solve(slm_solver* s, int32_t slot, double u, double* delta, int32_t* sta
   HIPCHK(hipMemcpyAsync(delta, h.delta, sizeof(double) * h.P, hipMemcpyDeviceToDevice, st));
   if (status)
     HIPCHK(hipMemcpyAsync(status, &h.st->chol_fail, sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-  HIPCHK(hipGetLastError());
-  return SLM_OK;
-}
-
-
-// ---- flow-correspondence term (include/super_lm.h; kernels in slm_corr.hip) -----------------------------------------
-int slm_enable_corr(slm_solver* s, int32_t mode, double weight) {
-  if (!s) return fail(SLM_ERR_INVALID, "slm_enable_corr: null argument");
-  if (mode < 0 || mode > 2) return fail(SLM_ERR_INVALID, "slm_enable_corr: mode must be 0 (off), 1 (point-point) or 2 (point-plane)");
-  if (!(weight - weight == 0.0)) return fail(SLM_ERR_INVALID, "slm_enable_corr: weight must be finite");
-  if (s->cfg.data_path == 1) return fail(SLM_ERR_UNSUPPORTED, "slm_enable_corr: needs the pair-record data path (data_path 0 or 2)");
-  if (s->cfg.solver_path == 1) return fail(SLM_ERR_UNSUPPORTED, "slm_enable_corr: needs a nested-dissection solver_path (0, 2, 3 or 4)");
-  if (!s->cfg.use_data) return fail(SLM_ERR_UNSUPPORTED, "slm_enable_corr: needs the data term (use_data 1)");
-  if (s->shard_mode)
-    return fail(SLM_ERR_UNSUPPORTED, "slm_enable_corr: the solver is sharded (slm_set_shard); the term needs every surfel of the frame "
-                                     "on one device");
-  for (const Slot& sl : s->slots)
-    if (sl.h.bound || sl.prep_ticket || sl.model_ready)
-      return fail(SLM_ERR_INVALID, "slm_enable_corr: a slot is already bound; call it after slm_create and before the first bind");
-  if (mode && !s->corr_dev) {
-    HIPCHK(s->corr_dev.grow(s->slots.size(), s->slots.size()));
-    HIPCHK(hipMemset(s->corr_dev, 0, sizeof(CorrDev) * s->slots.size()));
-  }
-  s->corr_mode = mode;
-  s->corr_w = mode ? weight : 0.0;
-  return SLM_OK;
-}
-
-// the argument checks the four per-slot entry points share; *out = the slot
-static int corr_slot(const char* fn, slm_solver* s, bool args_ok, int32_t slot, Slot** out) {
-  const std::string pre = std::string(fn) + ": ";
-  if (!s || !args_ok) return fail(SLM_ERR_INVALID, pre + "null argument");
-  if (slot < 0 || slot >= (int)s->slots.size()) return fail(SLM_ERR_INVALID, pre + "bad slot");
-  if (!s->corr_mode) return fail(SLM_ERR_UNSUPPORTED, pre + "slm_enable_corr first");
-  join_prepare(s, slot);
-  if (!s->slots[slot].h.bound) return fail(SLM_ERR_UNBOUND, pre + "slm_bind_frame first");
-  *out = &s->slots[slot];
-  return SLM_OK;
-}
-
-// the slot's target buffers at the bound frame's size, and the descriptor (has = 1) on its way to the device
-static int corr_publish(slm_solver* s, int slot, Slot& sl, hipStream_t st) {
-  sl.corr.has = 1;
-  HIPCHK(hipMemcpyAsync(s->corr_dev + slot, &sl.corr, sizeof(CorrDev), hipMemcpyHostToDevice, st));
-  HIPCHK(hipStreamSynchronize(st));   // (the source is the slot's own mirror, which the next bind rewrites)
-  return SLM_OK;
-}
-static int corr_buffers(Slot& sl) {
-  const size_t N = (size_t)std::max(sl.h.f.N, 1);
-  HIPCHK(grow(sl.corr_o, 3 * N));
-  HIPCHK(grow(sl.corr_n, 3 * N));
-  HIPCHK(grow(sl.corr_valid, N));
-  sl.corr.o = sl.corr_o.p;
-  sl.corr.n = sl.corr_n.p;
-  sl.corr.valid = sl.corr_valid.p;
-  return SLM_OK;
-}
-
-int slm_bind_corr_flow(slm_solver* s, int32_t slot, const float* flow, void* stream) {
-  Slot* sp = nullptr;
-  int rc = corr_slot("slm_bind_corr_flow", s, flow != nullptr, slot, &sp);
-  if (rc) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  if ((rc = corr_buffers(*sp)) != SLM_OK) return rc;
-  // (the kernel reads the buffers' addresses from the device descriptor: publish first)
-  if ((rc = corr_publish(s, slot, *sp, st)) != SLM_OK) return rc;
-  launch_corr_targets(s->frames_dev, s->corr_dev, slot, sp->h.f.N, flow, st);
-  HIPCHK(hipGetLastError());
-  return SLM_OK;
-}
-
-int slm_bind_corr_points(slm_solver* s, int32_t slot, const double* pts, const double* nrm, const uint8_t* valid, void* stream) {
-  Slot* sp = nullptr;
-  int rc = corr_slot("slm_bind_corr_points", s, pts != nullptr && valid != nullptr, slot, &sp);
-  if (rc) return rc;
-  if (s->corr_mode == 2 && !nrm) return fail(SLM_ERR_INVALID, "slm_bind_corr_points: nrm is required in mode 2 (point-plane)");
-  hipStream_t st = (hipStream_t)stream;
-  if ((rc = corr_buffers(*sp)) != SLM_OK) return rc;
-  const size_t N = (size_t)sp->h.f.N;
-  if (N > 0) {
-    HIPCHK(hipMemcpyAsync(sp->corr.o, pts, sizeof(double) * 3 * N, hipMemcpyDeviceToDevice, st));
-    if (nrm) HIPCHK(hipMemcpyAsync(sp->corr.n, nrm, sizeof(double) * 3 * N, hipMemcpyDeviceToDevice, st));
-    else HIPCHK(hipMemsetAsync(sp->corr.n, 0, sizeof(double) * 3 * N, st));
-    HIPCHK(hipMemcpyAsync(sp->corr.valid, valid, N, hipMemcpyDeviceToDevice, st));
-  }
-  return corr_publish(s, slot, *sp, st);
-}
-
-int slm_corr_get_targets(slm_solver* s, int32_t slot, double* pts, double* nrm, uint8_t* valid, void* stream) {
-  Slot* sp = nullptr;
-  int rc = corr_slot("slm_corr_get_targets", s, true, slot, &sp);
-  if (rc) return rc;
-  if (!sp->corr.has) return fail(SLM_ERR_UNBOUND, "slm_corr_get_targets: no correspondences bound to the slot");
-  hipStream_t st = (hipStream_t)stream;
-  const size_t N = (size_t)sp->h.f.N;
-  if (N > 0) {
-    if (pts) HIPCHK(hipMemcpyAsync(pts, sp->corr.o, sizeof(double) * 3 * N, hipMemcpyDeviceToDevice, st));
-    if (nrm) HIPCHK(hipMemcpyAsync(nrm, sp->corr.n, sizeof(double) * 3 * N, hipMemcpyDeviceToDevice, st));
-    if (valid) HIPCHK(hipMemcpyAsync(valid, sp->corr.valid, N, hipMemcpyDeviceToDevice, st));
-  }
-  return SLM_OK;
-}
-
-int slm_corr_loss(slm_solver* s, int32_t slot, double* out, void* stream) {
-  Slot* sp = nullptr;
-  int rc = corr_slot("slm_corr_loss", s, out != nullptr, slot, &sp);
-  if (rc) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  if ((rc = clear_flags(s, slot, st)) != SLM_OK) return rc;
-  const int part = 2 * kRegBlocksMax;   // (any place behind the regularisers' pairs: every LM iteration rewrites its own)
-  launch_corr_loss(s->frames_dev + slot, s->corr_dev + slot, 1, sp->h.f.K, s->corr_mode, s->corr_w, 0, part, corr_cnt_part(s), st);
-  launch_corr_loss_out(s->frames_dev, slot, part, corr_cnt_part(s), out, st);
-  HIPCHK(hipGetLastError());
-  return SLM_OK;
-}
-
-
-// ---- triangle-area face term (include/super_lm.h; kernels in slm_face.hip) -------------------------------------------
-int slm_enable_face(slm_solver* s, double weight) {
-  if (!s) return fail(SLM_ERR_INVALID, "slm_enable_face: null argument");
-  if (!(weight - weight == 0.0)) return fail(SLM_ERR_INVALID, "slm_enable_face: weight must be finite");
-  if (s->cfg.data_path == 1) return fail(SLM_ERR_UNSUPPORTED, "slm_enable_face: needs the pair-record data path (data_path 0 or 2)");
-  if (s->cfg.solver_path == 1) return fail(SLM_ERR_UNSUPPORTED, "slm_enable_face: needs a nested-dissection solver_path (0, 2, 3 or 4)");
-  if (!s->cfg.use_data) return fail(SLM_ERR_UNSUPPORTED, "slm_enable_face: needs the data term (use_data 1)");
-  if (s->shard_mode)
-    return fail(SLM_ERR_UNSUPPORTED, "slm_enable_face: the solver is sharded (slm_set_shard); the term's mesh is not sharded");
-  for (const Slot& sl : s->slots)
-    if (sl.h.bound || sl.prep_ticket || sl.model_ready || sl.loss_part)   // (loss_part: the first bind sizes it for the term)
-      return fail(SLM_ERR_INVALID, "slm_enable_face: a slot is already bound; call it after slm_create and before the first bind");
-  const bool on = weight != 0.0;
-  if (on && !s->face_dev) {
-    HIPCHK(s->face_dev.grow(s->slots.size(), s->slots.size()));
-    HIPCHK(hipMemset(s->face_dev, 0, sizeof(FaceDev) * s->slots.size()));
-  }
-  s->face_on = on;
-  s->face_w = on ? weight : 0.0;
-  return SLM_OK;
-}
-
-int slm_set_face_mesh(slm_solver* s, int32_t slot, int32_t n_triangles, const int32_t* tri, const double* areas, void* stream) {
-  if (!s || (n_triangles > 0 && (!tri || !areas))) return fail(SLM_ERR_INVALID, "slm_set_face_mesh: null argument");
-  if (slot < 0 || slot >= (int)s->slots.size()) return fail(SLM_ERR_INVALID, "slm_set_face_mesh: bad slot");
-  if (n_triangles < 0) return fail(SLM_ERR_INVALID, "slm_set_face_mesh: n_triangles must be >= 0");
-  if (!s->face_on) return fail(SLM_ERR_UNSUPPORTED, "slm_set_face_mesh: slm_enable_face first");
-  hipStream_t st = (hipStream_t)stream;
-  Slot& sl = s->slots[slot];
-  // the slot's plan holds the pairs of the mesh it was bound with: a queued preparation is settled and dropped, and the
-  // slot is unbound until its next bind
-  join_prepare(s, slot);
-  sl.model_ready = false;
-  sl.h.bound = 0;
-  sl.face = FaceDev{};
-  const size_t F = (size_t)n_triangles;
-  if (F > 0) {
-    HIPCHK(grow(sl.face_tri, 3 * F));
-    HIPCHK(grow(sl.face_areas, F));
-    HIPCHK(hipMemcpyAsync(sl.face_tri, tri, sizeof(int32_t) * 3 * F, hipMemcpyDeviceToDevice, st));
-    HIPCHK(hipMemcpyAsync(sl.face_areas, areas, sizeof(double) * F, hipMemcpyDeviceToDevice, st));
-    sl.face.tri = sl.face_tri.p;
-    sl.face.areas = sl.face_areas.p;
-    sl.face.n_tri = n_triangles;
-  }
-  HIPCHK(hipMemsetAsync(s->face_dev + slot, 0, sizeof(FaceDev), st));   // (ready = 0 on the device until the bind publishes it)
-  HIPCHK(hipMemsetAsync(&s->frames_dev[slot].bound, 0, sizeof(int32_t), st));
-  return SLM_OK;
-}
-
-int slm_face_loss(slm_solver* s, int32_t slot, double* out, void* stream) {
-  if (!s || !out) return fail(SLM_ERR_INVALID, "slm_face_loss: null argument");
-  if (slot < 0 || slot >= (int)s->slots.size()) return fail(SLM_ERR_INVALID, "slm_face_loss: bad slot");
-  if (!s->face_on) return fail(SLM_ERR_UNSUPPORTED, "slm_face_loss: slm_enable_face first");
-  join_prepare(s, slot);
-  if (!s->slots[slot].h.bound) return fail(SLM_ERR_UNBOUND, "slm_face_loss: slm_bind_frame first");
-  hipStream_t st = (hipStream_t)stream;
-  int rc = clear_flags(s, slot, st);
-  if (rc != SLM_OK) return rc;
-  const int part = face_direct_part();   // (any place among the pairs, in front of the kept counts: every LM iteration rewrites its own)
-  launch_face_loss(s->frames_dev + slot, s->face_dev + slot, 1, s->face_w, 0, part, st);
-  launch_face_loss_out(s->frames_dev, s->face_dev, slot, part, out, st);
-  HIPCHK(hipGetLastError());
-  return SLM_OK;
-}
-
-
-// ---- per-residual weights of the data term (include/super_lm.h; the weighted kernels in slm_data.hip) -----------------
-int slm_enable_data_weights(slm_solver* s, int32_t seg_mode, double pp_max) {
-  if (!s) return fail(SLM_ERR_INVALID, "slm_enable_data_weights: null argument");
-  if (seg_mode < 0 || seg_mode > 2) return fail(SLM_ERR_INVALID, "slm_enable_data_weights: seg_mode must be 0 (none), 1 (hard) or 2 (soft)");
-  if (!(pp_max - pp_max == 0.0) || pp_max < 0.0) return fail(SLM_ERR_INVALID, "slm_enable_data_weights: pp_max must be finite and >= 0");
-  if (s->cfg.data_path == 1)
-    return fail(SLM_ERR_UNSUPPORTED, "slm_enable_data_weights: needs the pair-record data path (data_path 0 or 2)");
-  if (s->cfg.solver_path == 1)
-    return fail(SLM_ERR_UNSUPPORTED, "slm_enable_data_weights: needs a nested-dissection solver_path (0, 2, 3 or 4)");
-  if (!s->cfg.use_data) return fail(SLM_ERR_UNSUPPORTED, "slm_enable_data_weights: needs the data term (use_data 1)");
-  for (const Slot& sl : s->slots)
-    if (sl.h.bound || sl.prep_ticket || sl.model_ready)
-      return fail(SLM_ERR_INVALID, "slm_enable_data_weights: a slot is already bound; call it after slm_create and before the first bind");
-  const bool on = seg_mode != 0 || pp_max > 0.0;
-  if (on && !s->w_dev) {
-    HIPCHK(s->w_dev.grow(s->slots.size(), s->slots.size()));
-    HIPCHK(hipMemset(s->w_dev, 0, sizeof(DataWeightDev) * s->slots.size()));
-  }
-  s->weights_on = on;
-  s->w_seg_mode = seg_mode;
-  s->w_pp_max = seg_mode ? 0.0 : pp_max;   // (ignored with a semantic weight, like the reference)
-  return SLM_OK;
-}
-
-// the argument checks of the two per-slot entry points; *out = the slot
-static int weights_slot(const char* fn, slm_solver* s, bool args_ok, int32_t slot, Slot** out) {
-  const std::string pre = std::string(fn) + ": ";
-  if (!s || !args_ok) return fail(SLM_ERR_INVALID, pre + "null argument");
-  if (slot < 0 || slot >= (int)s->slots.size()) return fail(SLM_ERR_INVALID, pre + "bad slot");
-  if (!s->weights_on) return fail(SLM_ERR_UNSUPPORTED, pre + "slm_enable_data_weights first");
-  join_prepare(s, slot);
-  if (!s->slots[slot].h.bound) return fail(SLM_ERR_UNBOUND, pre + "slm_bind_frame first");
-  *out = &s->slots[slot];
-  return SLM_OK;
-}
-
-int slm_bind_data_semantic(slm_solver* s, int32_t slot, int32_t num_classes, const int32_t* sf_seg, const float* sf_seg_conf,
-                           const float* tgt_seg_conf, void* stream) {
-  Slot* sp = nullptr;
-  int rc = weights_slot("slm_bind_data_semantic", s, sf_seg != nullptr && sf_seg_conf != nullptr && tgt_seg_conf != nullptr, slot, &sp);
-  if (rc) return rc;
-  if (num_classes < 1 || num_classes > SLM_MAX_CLASSES)
-    return fail(SLM_ERR_UNSUPPORTED, "slm_bind_data_semantic: num_classes must be in 1..SLM_MAX_CLASSES (4)");
-  hipStream_t st = (hipStream_t)stream;
-  sp->wdev.sf_seg = const_cast<int32_t*>(sf_seg);
-  sp->wdev.sf_seg_conf = const_cast<float*>(sf_seg_conf);
-  sp->wdev.tgt_seg_conf = const_cast<float*>(tgt_seg_conf);
-  sp->wdev.C = num_classes;
-  sp->wdev.has = 1;
-  HIPCHK(hipMemcpyAsync(s->w_dev + slot, &sp->wdev, sizeof(DataWeightDev), hipMemcpyHostToDevice, st));
-  HIPCHK(hipStreamSynchronize(st));   // (the source is the slot's own mirror, which the next bind rewrites)
-  return SLM_OK;
-}
-
-int slm_data_weights(slm_solver* s, int32_t slot, double* w_device, void* stream) {
-  Slot* sp = nullptr;
-  int rc = weights_slot("slm_data_weights", s, w_device != nullptr, slot, &sp);
-  if (rc) return rc;
-  if ((rc = weights_check(s, "slm_data_weights", slot, 1)) != SLM_OK) return rc;
-  const FrameDev& h = sp->h;
-  const DataWArgs wa{s->w_seg_mode ? s->w_dev.p : nullptr, s->w_pp_max, s->w_seg_mode, 0};
-  launch_data_weights(s->frames_dev, slot, h.f.N, h.f.K, s->cfg.w_data, wa, w_device, (hipStream_t)stream);
   HIPCHK(hipGetLastError());
   return SLM_OK;
 }

@@ -1,6 +1,7 @@
 // slm_misc.hip -- the LM loop's state kernels (slot initialisation, iteration begin, trial point, accept/reject on the
 // device, target packing, loss read-out) and their launchers, nothing else.  (The node feeder is slm_nodes.hip.)
 #include "slm_common.h"
+#include "slm_face.h"
 #include "slm_launch.h"
 
 // ---------------------------------------------------------------------------------
@@ -215,6 +216,31 @@ __global__ void __launch_bounds__(256) k_loss_out(const FrameDev* __restrict__ f
   }
 }
 
+// out[0] = the loss of a term, out[1] = its count (slm_corr_loss, slm_face_loss): the nb pairs of slot `slot` at `part`
+// behind the regularisers' partials (term_loss_store) summed in a fixed order; the count is the sum of the nb kept counts at
+// cnt_part or, with `face`, the triangles of the slot's mesh (no mesh: both 0).  one wave
+__global__ void __launch_bounds__(64) k_term_loss_out(const FrameDev* __restrict__ frames, int slot, int part, int nb, int cnt_part,
+                                                       const FaceDev* __restrict__ face, double* __restrict__ out) {
+  const FrameDev& fd = frames[slot];
+  const double* reg = fd.loss_part + 2 * (size_t)fd.n_loss_part;
+  double s = 0.0, c = 0.0;
+  for (int b = threadIdx.x; b < nb; b += blockDim.x) {
+    s += reg[part + 2 * b];
+    if (!face) c += reg[cnt_part + b];
+  }
+  s = wave_sum(s);
+  c = wave_sum(c);
+  if (threadIdx.x == 0) {
+    if (face) {
+      const bool on = face[slot].ready != 0;
+      s = on ? s : 0.0;
+      c = on ? (double)face[slot].n_tri : 0.0;
+    }
+    out[0] = s;
+    out[1] = c;
+  }
+}
+
 __global__ void k_zero_reg_part(const FrameDev* __restrict__ frames, int n_reg_part) {
   const FrameDev& fd = frames[blockIdx.y];
   if (!fd.bound) return;
@@ -261,6 +287,11 @@ void launch_accept(const FrameDev* frames_dev, int n_frames, int phase_test, int
 void launch_loss_out(const FrameDev* frames_dev, int slot, int n_reg_part, double* out,
                      hipStream_t st) {
   hipLaunchKernelGGL(k_loss_out, dim3(1), dim3(256), 0, st, frames_dev, slot, n_reg_part, out);
+}
+
+void launch_term_loss_out(const FrameDev* frames_dev, int slot, int part, int nb, int cnt_part, const FaceDev* face_dev, double* out,
+                          hipStream_t st) {
+  hipLaunchKernelGGL(k_term_loss_out, dim3(1), dim3(64), 0, st, frames_dev, slot, part, nb, cnt_part, face_dev, out);
 }
 
 void launch_zero_reg_part(const FrameDev* frames_dev, int n_frames, int n_reg_part, hipStream_t st) {

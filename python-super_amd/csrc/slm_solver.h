@@ -1,6 +1,7 @@
-// slm_solver.h -- internal to the LM host (slm_api.hip, slm_bind.hip, slm_lm.hip): what a solver and its slots hold, and
-// the few functions that cross those units.  Device memory is owned by DevBuf / PinnedBuf members (slm_host.h); the
-// descriptors (FrameDev, CorrDev, FaceDev, DataWeightDev) only mirror addresses.
+// slm_solver.h -- internal to the LM host (slm_api.hip, slm_bind.hip, slm_lm.hip, slm_terms.hip): what a solver and its slots
+// hold, where the loss partials of its terms sit (LossParts), and the few functions that cross those units.  Device memory
+// is owned by DevBuf / PinnedBuf members (slm_host.h); the descriptors (FrameDev, CorrDev, FaceDev, DataWeightDev) only
+// mirror addresses.
 #pragma once
 #include <algorithm>
 #include <atomic>
@@ -19,15 +20,7 @@
 
 constexpr int kLossBlocks = 512;   // data-loss partial sums per slot
 constexpr int kRegBlocksMax = 64;
-// the correspondence term's loss partials (slm_corr.h): SLM_CORR_BLOCKS {sum, 0} pairs right behind the regularisers' pairs
-// of the launch (k_accept sums them with a larger count), the kept counts at a fixed place behind every pair
-constexpr int kCorrBlocks = SLM_CORR_BLOCKS;
-constexpr int kCorrCntPart = 2 * (kRegBlocksMax + kCorrBlocks);
-constexpr size_t kLossPartDoubles = (size_t)2 * (kLossBlocks + kRegBlocksMax + kCorrBlocks) + kCorrBlocks;
-// the face term's loss partials (slm_face.h): SLM_FACE_BLOCKS {sum, 0} pairs behind the correspondence term's pairs of the
-// launch.  Only a solver with the term enabled (slm_enable_face) has room for them: its slots' loss_part is that much longer
-// and the correspondence term's kept counts sit that much further back (corr_cnt_part).
-constexpr int kFaceBlocks = SLM_FACE_BLOCKS;
+constexpr int kCorrBlocks = SLM_CORR_BLOCKS, kFaceBlocks = SLM_FACE_BLOCKS;   // loss partials of the terms per slot (LossParts)
 
 // The form of the data term: which plan the bind prepares and which kernels the LM entry points launch.
 enum class DataForm {
@@ -151,11 +144,32 @@ struct slm_solver {
   bool shard_mode = false;      // slm_set_shard was called (world == 1 included): slots carry the exchange buffers
 };
 
-// where the correspondence term's kept counts and the face term's partials of a direct call (slm_corr_loss, slm_face_loss)
-// sit behind the regularisers' pairs, and the doubles of a slot's loss_part
-inline int corr_cnt_part(const slm_solver* s) { return kCorrCntPart + (s->face_on ? 2 * kFaceBlocks : 0); }
-inline int face_direct_part() { return 2 * (kRegBlocksMax + kCorrBlocks); }
-inline size_t loss_part_doubles(const slm_solver* s) { return kLossPartDoubles + (s->face_on ? 2 * (size_t)kFaceBlocks : 0); }
+// Where the terms' loss partials sit in a slot's loss_part: every offset in doubles from the start of the regularisers'
+// partials (loss_part + 2 n_loss_part).  An LM launch packs its {sum, 0} pairs -- the n_reg_part of the regularisers, then
+// the correspondence term's kCorrBlocks, then the face term's kFaceBlocks, each only on a solver with the term enabled --
+// so that k_accept sums them as n_acc_part pairs.  A direct call (slm_corr_loss, slm_face_loss) stores its pairs at a fixed
+// place behind kRegBlocksMax pairs (any place among the pairs would do: every LM iteration rewrites its own).  The
+// correspondence term's kept counts sit behind every pair; only a solver with the face term has room for that term's pairs,
+// its counts sit that much further back and its slots' loss_part is that much longer.
+struct LossParts {
+  int corr, face;                  // the terms' pairs of an LM launch
+  int corr_direct, face_direct;    // ... of a direct call
+  int corr_cnt;                    // the correspondence term's kCorrBlocks kept counts
+  int n_acc_part;                  // pairs k_accept sums behind the data partials
+  size_t doubles;                  // of a slot's loss_part (kLossBlocks data pairs in front)
+};
+inline LossParts loss_parts(const slm_solver* s, int n_reg_part) {
+  LossParts p;
+  p.corr = 2 * n_reg_part;
+  p.n_acc_part = n_reg_part + (s->corr_mode ? kCorrBlocks : 0);
+  p.face = 2 * p.n_acc_part;
+  if (s->face_on) p.n_acc_part += kFaceBlocks;
+  p.corr_direct = 2 * kRegBlocksMax;
+  p.face_direct = p.corr_direct + 2 * kCorrBlocks;
+  p.corr_cnt = p.face_direct + (s->face_on ? 2 * kFaceBlocks : 0);
+  p.doubles = (size_t)2 * kLossBlocks + p.corr_cnt + kCorrBlocks;
+  return p;
+}
 
 // diagnostics (slm_debug_counters, slm_api.hip): device reallocations and symbolic analyses since the library was loaded
 extern std::atomic<long long> g_reallocs, g_realloc_bytes, g_plan_builds, g_plan_reuses, g_plan_fill_hits;   // (binds may run on worker threads)
@@ -170,13 +184,17 @@ hipError_t grow(DevBuf<T>& b, size_t need) {
   return b.grow(need, want);
 }
 
-// What crosses the three units (hidden: the library's dynamic symbols stay the C ABI and what they were).
+// What crosses the four units (hidden: the library's dynamic symbols stay the C ABI and what they were).
 #pragma GCC visibility push(hidden)
 // slm_api.hip: the slots [first, first + n) are bound and may share a launch (waits for their queued preparations)
 int check_slots(slm_solver* s, int first, int n);
 // slm_bind.hip: waits for the slot's queued slm_prepare_model; the block-banded storage of a slot on demand
 void join_prepare(slm_solver* s, int slot);
 int ensure_band(slm_solver* s, int slot, hipStream_t st);
-// slm_lm.hip: which form of the solver a launch of n frames of J nodes takes (the bind sizes the plan's leaves by it)
+// slm_lm.hip: which form of the solver a launch of n frames of J nodes takes (the bind sizes the plan's leaves by it);
+// the stopped flag and counters of a slot cleared ahead of a parity entry point; with a semantic weight on, every slot of
+// [first, first + n) has its semantic inputs (fn: the refused entry point's name)
 bool solve_is_task_graph(const slm_solver* s, int n, int J);
+int clear_flags(slm_solver* s, int slot, hipStream_t st);
+int weights_check(const slm_solver* s, const char* fn, int first, int n);
 #pragma GCC visibility pop

@@ -60,7 +60,7 @@ def test_exports_signatures_and_abi_version(lib):
 
 def test_every_refusal_text_is_listed_in_the_header_and_raised_by_the_library():
     header = open(HEADER).read()
-    source = "".join(open(os.path.join(CSRC, f)).read() for f in ("slm_lm.hip", "slm_bind.hip"))
+    source = "".join(open(os.path.join(CSRC, f)).read() for f in ("slm_lm.hip", "slm_terms.hip", "slm_bind.hip"))
     source = re.sub(r'"\s*\n\s*"', "", source)               # adjacent string literals are one text
     pre = "slm_enable_face: "
     for t in (pre + "null argument", pre + "weight must be finite",
