@@ -391,6 +391,67 @@ int slm_enable_face(slm_solver* s, double weight);
 int slm_set_face_mesh(slm_solver* s, int32_t slot, int32_t n_triangles, const int32_t* tri, const double* areas, void* stream);
 int slm_face_loss(slm_solver* s, int32_t slot, double* out_device, void* stream);
 
+/* -- semantic boundary-morph term of the LM path (opt.sf_bn_morph; the reference has only the first-order form,
+ * super/deform_mesh.py:126-194, which slm_gf_config.use_bn_morph carries) ---------------------------------------------
+ * Opt-in.  All arithmetic is float64.  T = T_i(beta) is the skinned surfel i; it projects to
+ *   x = T.x fx / Ze + cx,  y = T.y fy / Ze + cy,  Ze = T.z + 1e-8   (fx .. cy: the frame's float32 values widened).
+ * Surfel i is a CANDIDATE when argmax_c grid_sample(img_seg_conf)(x, y) != sf_seg[i] (bilinear taps, zero padding,
+ * align_corners=False, the first maximum wins), the normalised coordinates are strictly inside (-1, 1) and its class has at
+ * least 2 boundary pixels (a single pixel counts as no boundary).  The boundary lists per class are those of
+ * slm_gf_bind_semantic (find_edge_region, kernel 3, margin 1, row-major), built once per slm_bind_morph.  e1, e2 are the two
+ * nearest boundary pixels of the surfel's own class in (distance, list position) order, d1 <= d2 their squared distances.  A
+ * candidate is KEPT when !(sqrt(d1) > dte || sqrt(d2) > dte) with dte = min(x, y, W - x, H - y) and l_i = (d1 + d2) / 2 > 15.
+ * n = the kept surfels of the slot.  lambda = weight multiplies the RESIDUAL, as for every LM term:
+ *   loss = lambda^2 / n sum_kept l_i   (the reference's mean times the weight; slm_gf_config.w_bn_morph = lambda^2 gives the
+ *   same objective).  n = 0: the term contributes nothing -- the one departure: the reference's mean over an empty selection
+ *   is NaN, which would reject every LM step.
+ * The selection, the targets m_i = (e1 + e2) / 2 and n are constants of the linearisation (the rule slm_enable_data_weights
+ * states for its weights).  Each kept surfel gives two rows r_i = lambda / sqrt(n) ((x, y) - m_i),
+ *   x row: c = (fx / Ze, 0, -fx T.x / Ze^2),  y row: c = (0, fy / Ze, -fy T.y / Ze^2),
+ *   per neighbour k: lambda / sqrt(n) w_k [c^T dR(q_k)(p - g_k)/dq_k | c]   (the correspondence term's rows with this c).
+ * The loss pass at the trial point evaluates everything afresh there -- new selection, new n, and the full l_i including the
+ * constant |e1 - e2|^2 / 4 -- so accept / reject sees the reference's loss; slm_iter_record.loss includes the term, M_grad /
+ * M_loss stay the ICP match counts.  The term couples only a surfel's own K nodes: no new pairs, no plan changes.
+ *
+ * slm_enable_morph: after slm_create, before the first bind.  A weight of 0 switches the option off again.  An enabled
+ * solver takes the pair-record form of the data term for every num_neighbors, 4 included (as slm_enable_corr,
+ * slm_enable_face and slm_enable_data_weights, with which it may be combined).  Refusals:
+ *   SLM_ERR_INVALID      "slm_enable_morph: null argument"
+ *                        "slm_enable_morph: weight must be finite"
+ *                        "slm_enable_morph: a slot is already bound; call it after slm_create and before the first bind"
+ *   SLM_ERR_UNSUPPORTED  "slm_enable_morph: needs the pair-record data path (data_path 0 or 2)"
+ *                        "slm_enable_morph: needs a nested-dissection solver_path (0, 2, 3 or 4)"
+ *                        "slm_enable_morph: needs the data term (use_data 1)"
+ *                        "slm_enable_morph: the solver is sharded (slm_set_shard); the term needs every surfel of the frame on one device"
+ *   and, on an enabled solver,
+ *   SLM_ERR_UNSUPPORTED  "slm_set_shard: the boundary-morph term is enabled (slm_enable_morph); it needs every surfel of the frame on one device"
+ *                        "slm_bind_frame: the boundary-morph term (slm_enable_morph) needs J < 65536"
+ *
+ * slm_bind_morph: after slm_bind_frame.  Device pointers: img_seg (H,W) int32 is read by this call only (the boundary lists
+ * are built here, with a size read-back: the host waits for `stream`); img_seg_conf (C,H,W) float32 and sf_seg (N) int32 are
+ * read in place like the frame's own (they must stay valid while the slot is used).  edge_counts_host (C) or null receives
+ * the boundary-list lengths.  slm_bind_frame(s) clears the slot's inputs: a slot without them runs without the term.
+ *   SLM_ERR_INVALID      "slm_bind_morph: null argument"   "slm_bind_morph: bad slot"
+ *   SLM_ERR_UNSUPPORTED  "slm_bind_morph: slm_enable_morph first"
+ *                        "slm_bind_morph: num_classes must be in 1..SLM_MAX_CLASSES (4)"
+ *   SLM_ERR_UNBOUND      "slm_bind_morph: slm_bind_frame first"
+ *
+ * slm_morph_loss: out_device[0] = the term's loss at the slot's current beta, [1] = kept n, [2] = candidates; {0, 0, 0} for
+ * a slot without inputs.  slm_morph_targets: the selection at the slot's current beta -- kept (N) uint8, target_xy (N,2)
+ * float64 (m_i; zeros where not kept), li (N) float64 (l_i; zero where not kept), all device, each may be null.  Refusals
+ * (<fn> = either):
+ *   SLM_ERR_INVALID      "<fn>: null argument"   "<fn>: bad slot"
+ *   SLM_ERR_UNSUPPORTED  "<fn>: slm_enable_morph first"
+ *   SLM_ERR_UNBOUND      "<fn>: slm_bind_frame first"   "slm_morph_targets: slm_bind_morph first"
+ * Not built: the term on the tuple-sorted MFMA assembly, on sharded frames, for J >= 65536 and without the data term. */
+int slm_enable_morph(slm_solver* s, double weight);
+int slm_bind_morph(slm_solver* s, int32_t slot, int32_t num_classes, const int32_t* img_seg /*(H,W)*/,
+                   const float* img_seg_conf /*(C,H,W)*/, const int32_t* sf_seg /*(N)*/,
+                   int32_t* edge_counts_host /*(C) or null*/, void* stream);
+int slm_morph_loss(slm_solver* s, int32_t slot, double* out_device /*[3]: loss, kept n, candidates*/, void* stream);
+int slm_morph_targets(slm_solver* s, int32_t slot, uint8_t* kept /*(N)*/, double* target_xy /*(N,2)*/,
+                      double* li /*(N)*/, void* stream);
+
 /* -- phase timing (bench.py roofline leg) ----------------------------------------- */
 /* With profiling on, slm_run brackets each phase of every LM iteration with HIP events
  * recorded on the launch stream.  Phases: */

@@ -220,6 +220,7 @@ int slm_destroy(slm_solver* s) {
   for (Slot& sl : s->slots) {   // what a slot holds beside its DevBuf / PinnedBuf members
     plan_free(sl.plan);
     pairplan_free(sl.pplan);
+    sem_free(sl.morph_edges);
     if (sl.prep_fork) (void)hipEventDestroy(sl.prep_fork);
     if (sl.prep_done) (void)hipEventDestroy(sl.prep_done);
   }
@@ -235,7 +236,7 @@ int slm_destroy(slm_solver* s) {
       if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : s->ev_pool) (void)hipEventDestroy(e);
   if (s->drain_event) (void)hipEventDestroy(s->drain_event);
-  delete s;   // (the solver's own arrays: frames_dev, bw_dev, bw_host, reuse_dev, corr_dev, face_dev)
+  delete s;   // (the solver's own arrays: frames_dev, bw_dev, bw_host, reuse_dev, corr_dev, face_dev, morph_dev)
   return SLM_OK;
 }
 

@@ -92,6 +92,8 @@ static int check_model_args(const slm_solver* s, int32_t slot, const slm_frame* 
     return fail(SLM_ERR_UNSUPPORTED, "slm_bind_frame: the data weights (slm_enable_data_weights) need J < 65536");
   if (s->face_on && f->J >= 65536)   // (the same: the term adds into the pair records)
     return fail(SLM_ERR_UNSUPPORTED, "slm_bind_frame: the face term (slm_enable_face) needs J < 65536");
+  if (s->morph_on && f->J >= 65536)   // (the same)
+    return fail(SLM_ERR_UNSUPPORTED, "slm_bind_frame: the boundary-morph term (slm_enable_morph) needs J < 65536");
   if (f->N > 0 && f->J < f->K)   // (the reference's top-k of K among J nodes raises; the device checks below assume J >= K)
     return fail(SLM_ERR_INVALID, "slm_bind_frame: fewer nodes (J) than num_neighbors: sf_knn_idx cannot hold K distinct ids");
   if ((f->N > 0 && (!f->sf_points || !f->sf_knn_idx || !f->sf_knn_w)) || !f->ed_points || !f->ed_knn_idx)
@@ -162,7 +164,7 @@ static int bind_data_plan(slm_solver* s, Slot& sl, const slm_frame* f, hipStream
   sl.prep_max_bin = 0;
   sl.face.ready = 0;
   sl.face.tri_pidx = nullptr;
-  out.form = data_form_of(s->cfg, *f, s->corr_mode != 0 || s->weights_on || s->face_on);
+  out.form = data_form_of(s->cfg, *f, s->corr_mode != 0 || s->weights_on || s->face_on || s->morph_on);
   if (out.form == DataForm::tuple) {
     V1Sizes sz;
     HIPCHK(prep_v1(prep, *f, sl.plan, &sz, st));
@@ -474,6 +476,10 @@ static int bind_target_part(slm_solver* s, int32_t slot, const slm_frame* f, hip
   if (s->weights_on) {   // and so did its semantic inputs
     sl.wdev.has = 0;
     HIPCHK(hipMemsetAsync(&s->w_dev[slot].has, 0, sizeof(int32_t), st));
+  }
+  if (s->morph_on) {   // and the inputs of the boundary-morph term: the slot runs without the term until slm_bind_morph
+    sl.morph.has = 0;
+    HIPCHK(hipMemsetAsync(&s->morph_dev[slot].has, 0, sizeof(int32_t), st));
   }
   if (s->face_on) {   // the slot's mesh as this bind's plan placed it (through a pinned mirror, like the descriptor below)
     HIPCHK(sl.face_pin.grow(1, 1));

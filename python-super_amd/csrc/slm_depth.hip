@@ -443,11 +443,8 @@ int slm_depth_preprocess(slm_depth* d, const slm_depth_config* cfg, const slm_de
   if (n_valid_host) *n_valid_host = T;
   // 4. distance to the class boundaries
   if (in->seg && out->dist2edge && out->points && out->seg && T > 0) {
-    slm_gf_semantic sem{};
-    sem.num_classes = cfg->num_classes;
-    sem.img_seg = in->seg;
     int32_t off[SLM_MAX_CLASSES + 1];
-    HIPCHK(sem_extract_edges(d->sem, sem, H, W, off, st));
+    HIPCHK(sem_extract_edges(d->sem, cfg->num_classes, in->seg, H, W, off, st));
     hipLaunchKernelGGL(k_dp_dist2edge, dim3((T + 255) / 256), blk, 0, st, *cfg, T, out->points, out->seg,
                        d->sem.edge_xy, off[0], off[1], off[2], off[3], off[4], out->dist2edge);
   }

@@ -849,7 +849,7 @@ int slm_gf_bind_semantic(slm_gf* g, int32_t slot, const slm_gf_semantic* sem, in
   s.sem = *sem;
   for (int c = 0; c <= SLM_MAX_CLASSES; ++c) s.edge_off[c] = 0;
   if (need_morph) {
-    HIPCHK(sem_extract_edges(sc, *sem, f.H, f.W, s.edge_off, st));
+    HIPCHK(sem_extract_edges(sc, sem->num_classes, sem->img_seg, f.H, f.W, s.edge_off, st));
     HIPCHK(sem_ensure_morph(sc, f.N));
   }
   s.edge_xy = sc.edge_xy;

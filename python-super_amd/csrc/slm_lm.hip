@@ -10,8 +10,10 @@ struct BatchDims {
   int max_pos = 0, max_blocks = 0, maxP = 0;
   bool corr = false;   // some slot of the batch has correspondences bound (the term's Jacobian pass runs)
   int max_tri = 0;     // most triangles of a slot's face mesh (0: no slot has one, the face term's Jacobian pass does not run)
-  const CorrDev* corr_dev = nullptr;   // the batch's first descriptors of the two terms (null: the term is off)
+  bool morph = false;  // some slot of the batch has the boundary-morph term's inputs bound (its selection and Jacobian pass run)
+  const CorrDev* corr_dev = nullptr;   // the batch's first descriptors of the terms (null: the term is off)
   const FaceDev* face_dev = nullptr;
+  const MorphDev* morph_dev = nullptr;
   LossParts parts{};   // where the terms' loss partials sit, and what k_accept sums behind the data partials
   bool weights = false;   // the solver carries per-residual data weights (slm_enable_data_weights): the weighted kernels run
   DataWArgs wargs{};      // ... with these arguments (the batch's first semantic descriptor, seg_mode, pp_max)
@@ -54,6 +56,7 @@ BatchDims dims_of(slm_solver* s, int first, int n, bool band = false) {
     }
     d.maxP = std::max(d.maxP, h.P);
     d.corr = d.corr || (s->corr_mode && s->slots[i].corr.has);
+    d.morph = d.morph || (s->morph_on && s->slots[i].morph.has);
     if (s->face_on && s->slots[i].face.ready) d.max_tri = std::max(d.max_tri, s->slots[i].face.n_tri);
   }
   d.nd = d.nd && !band;
@@ -108,6 +111,7 @@ BatchDims dims_of(slm_solver* s, int first, int n, bool band = false) {
   d.parts = loss_parts(s, d.n_reg_part);
   if (s->corr_mode) d.corr_dev = s->corr_dev + first;
   if (s->face_on) d.face_dev = s->face_dev + first;
+  if (s->morph_on) d.morph_dev = s->morph_dev + first;
   d.weights = s->weights_on;
   d.wargs = DataWArgs{s->w_seg_mode ? s->w_dev.p + first : nullptr, s->w_pp_max, s->w_seg_mode, 0};
   return d;
@@ -188,11 +192,19 @@ void enqueue_jacobian(slm_solver* s, const FrameDev* fr, int n, const BatchDims&
       launch_data_grad_pairs(fr, n, d.maxN, d.K, w, st, d.weights ? &d.wargs : nullptr);
       if (d.corr) launch_corr_grad_pairs(fr, d.corr_dev, n, d.maxN, d.K, s->corr_mode, s->corr_w, st);
       if (d.max_tri) launch_face_grad(fr, d.face_dev, n, d.max_tri, s->face_w, st);
+      if (d.morph) {   // (the selection at beta and its count n first: constants of the linearisation)
+        launch_morph_select(fr, d.morph_dev, n, d.maxN, d.K, s->morph_w, 0, -1, nullptr, st);
+        launch_morph_grad_pairs(fr, d.morph_dev, n, d.maxN, d.K, s->morph_w, st);
+      }
       break;
     case DataForm::per_entry:
       launch_data_grad(fr, n, d.maxN, d.K, w, st, d.weights ? &d.wargs : nullptr);
       if (d.corr) launch_corr_grad(fr, d.corr_dev, n, d.maxN, d.K, s->corr_mode, s->corr_w, st);
       if (d.max_tri) launch_face_grad_band(fr, d.face_dev, n, d.max_tri, s->face_w, st);
+      if (d.morph) {
+        launch_morph_select(fr, d.morph_dev, n, d.maxN, d.K, s->morph_w, 0, -1, nullptr, st);
+        launch_morph_grad(fr, d.morph_dev, n, d.maxN, d.K, s->morph_w, st);
+      }
       break;
     case DataForm::none: break;
   }
@@ -231,6 +243,9 @@ void enqueue_data_loss(slm_solver* s, const FrameDev* fr, int n, const BatchDims
     launch_corr_loss(fr, d.corr_dev, n, d.K, s->corr_mode, s->corr_w, at_beta ? 0 : 1, d.parts.corr, d.parts.corr_cnt, st);
   // the face term's, behind those (likewise: zeros without a mesh)
   if (s->face_on) launch_face_loss(fr, d.face_dev, n, s->face_w, at_beta ? 0 : 1, d.parts.face, st);
+  // the boundary-morph term's, behind those: a fresh selection there, then the fold (alone when no slot has inputs: zeros)
+  if (s->morph_on && d.K >= 1)
+    launch_morph_select(fr, d.morph_dev, n, d.morph ? d.maxN : 0, d.K, s->morph_w, at_beta ? 0 : 1, d.parts.morph, nullptr, st);
 }
 }  // namespace
 
@@ -274,6 +289,9 @@ int slm_set_shard(slm_solver* s, int32_t rank, int32_t world) {
                                      "the frame on one device");
   if (s->face_on)
     return fail(SLM_ERR_UNSUPPORTED, "slm_set_shard: the face term is enabled (slm_enable_face); its mesh is not sharded");
+  if (s->morph_on)
+    return fail(SLM_ERR_UNSUPPORTED, "slm_set_shard: the boundary-morph term is enabled (slm_enable_morph); it needs every surfel of "
+                                     "the frame on one device");
   s->rank = rank;
   s->world = world;
   s->shard_mode = true;

@@ -38,6 +38,38 @@ struct PairLds {
   int s_cid[64 * KK];            // its node ids, ascending
 };
 
+// The skinning state of surfel i at the node table npk (node_pk or node_pk_try): its neighbours, their rotations, p - g_k
+// and the skinned position T(p).  What the terms whose rows are c^T dT/dbeta (the correspondence term, the semantic
+// boundary-morph term) evaluate before they choose their c.
+template <int KK>
+struct PairSkin {
+  int id[KK];
+  double w[KK], qw[KK];
+  d3 qv[KK], dk[KK];
+  d3 T;
+};
+template <int KK>
+__device__ __forceinline__ void pair_skin(const FrameDev& fd, const double* __restrict__ npk, int i, PairSkin<KK>& s) {
+  const FrameIn& f = frame_in(fd);
+  const d3 p = ld_state3(f.sf_points, (size_t)i, fd.f.state_f64);
+  d3 T = {0.0, 0.0, 0.0};
+#pragma unroll
+  for (int k = 0; k < KK; ++k) {
+    s.id[k] = f.sf_knn_idx[(size_t)KK * i + k];
+    s.w[k] = ld_state1(f.sf_knn_w, (size_t)KK * i + k, fd.f.state_f64);
+    const double2* nq = reinterpret_cast<const double2*>(npk + (size_t)SLM_NPK * s.id[k]);
+    const double2 n0 = nq[0], n1 = nq[1], n2 = nq[2], n3 = nq[3], n4 = nq[4];
+    const d3 g = {n3.y, n4.x, n4.y};
+    s.qw[k] = n0.x;
+    s.qv[k] = {n0.y, n1.x, n1.y};
+    s.dk[k] = p - g;
+    d3 t = quat_apply(s.qw[k], s.qv[k], s.dk[k]);
+    t = {t.x + n2.x + g.x, t.y + n2.y + g.y, t.z + n3.x + g.z};
+    T = {T.x + s.w[k] * t.x, T.y + s.w[k] * t.y, T.z + s.w[k] * t.z};
+  }
+  s.T = T;
+}
+
 // canonical slot of neighbour k of a surfel (the ids are distinct: slm_bind_frame refuses a row that repeats one)
 template <int KK>
 __device__ __forceinline__ int pair_rank(const int (&id)[KK], int k) {

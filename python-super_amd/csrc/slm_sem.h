@@ -15,8 +15,9 @@ struct SemScratch {
   size_t cap_flags = 0, cap_sel = 0, cap_tmp = 0, cap_edge = 0, cap_morph = 0;
 };
 
-// boundary pixels of every class of sem.img_seg -> sc.edge_xy, edge_off[0..C]; synchronises st
-hipError_t sem_extract_edges(SemScratch& sc, const slm_gf_semantic& sem, int H, int W, int32_t* edge_off,
+// boundary pixels of every class of img_seg (H,W), classes 0..num_classes-1 -> sc.edge_xy, edge_off[0..C]; synchronises st
+// (GraphFit's semantic bind, the depth preprocessing and the LM path's morphing term, slm_bind_morph)
+hipError_t sem_extract_edges(SemScratch& sc, int num_classes, const int32_t* img_seg, int H, int W, int32_t* edge_off,
                              hipStream_t st);
 hipError_t sem_ensure_morph(SemScratch& sc, int N);
 void sem_free(SemScratch& sc);

@@ -13,6 +13,7 @@
 
 #include "slm_host.h"
 #include "slm_sem.h"
+#include "slm_sem_search.h"
 
 namespace {
 
@@ -45,14 +46,14 @@ __global__ void __launch_bounds__(256) k_edge_pack(int n, int HW, int W, const i
 
 }  // namespace
 
-hipError_t sem_extract_edges(SemScratch& sc, const slm_gf_semantic& sem, int H, int W, int32_t* edge_off,
+hipError_t sem_extract_edges(SemScratch& sc, int num_classes, const int32_t* img_seg, int H, int W, int32_t* edge_off,
                              hipStream_t st) {
-  const int C = sem.num_classes;
+  const int C = num_classes;
   const size_t HW = (size_t)H * W, n = HW * C;
   HIPRET(grow(sc.flags, sc.cap_flags, n, n));
   if (!sc.counts) HIPRET(hipMalloc((void**)&sc.counts, sizeof(int32_t) * (SLM_MAX_CLASSES + 1)));
   HIPRET(hipMemsetAsync(sc.counts, 0, sizeof(int32_t) * (SLM_MAX_CLASSES + 1), st));
-  hipLaunchKernelGGL(k_edge_flags, dim3((HW + 255) / 256), dim3(256), 0, st, H, W, C, sem.img_seg, sc.flags,
+  hipLaunchKernelGGL(k_edge_flags, dim3((HW + 255) / 256), dim3(256), 0, st, H, W, C, img_seg, sc.flags,
                      sc.counts);
   int32_t h[SLM_MAX_CLASSES + 1];
   HIPRET(hipMemcpyAsync(h, sc.counts, sizeof(h), hipMemcpyDeviceToHost, st));
@@ -81,7 +82,8 @@ void sem_free(SemScratch& sc) {
   sc = SemScratch();
 }
 
-// grid = (ceil(maxN/256), n_frames)
+// grid = (ceil(maxN/256), n_frames).  The class sampling, the search and the keep test are slm_sem_search.h's, shared with the
+// LM path's form of the term (k_morph_select, slm_morph.hip).
 __global__ void __launch_bounds__(256) k_gf_morph(GfSlot* __restrict__ slots) {
   __shared__ double sm[16];
   GfSlotDev& s = gf_dev(slots)[blockIdx.y];
@@ -90,10 +92,8 @@ __global__ void __launch_bounds__(256) k_gf_morph(GfSlot* __restrict__ slots) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   double li_sum = 0.0, kept = 0.0;
   // candidates of this workgroup (surfels whose projected class differs from their own), searched cooperatively below
-  __shared__ int n_cand;
-  __shared__ double c_x[256], c_y[256], c_d1[256], c_d2[256];
-  __shared__ int c_e0[256], c_e1[256], c_i1[256], c_i2[256];
-  if (threadIdx.x == 0) n_cand = 0;
+  __shared__ SemCandLds cand;
+  if (threadIdx.x == 0) cand.n_cand = 0;
   __syncthreads();
   int my_cand = -1, my_W = 0, my_H = 0;
   double my_x = 0.0, my_y = 0.0;
@@ -110,31 +110,8 @@ __global__ void __launch_bounds__(256) k_gf_morph(GfSlot* __restrict__ slots) {
       const int H = f.H, W = f.W, C = s.sem.num_classes;
       const double Ze = P.z + 1e-8;
       const double x = P.x * (double)f.fx / Ze + (double)f.cx, y = P.y * (double)f.fy / Ze + (double)f.cy;
-      // F.grid_sample(seg_conf, grid) with bilinear taps, zero padding, align_corners=False
-      const double gx = x / (double)W * 2.0 - 1.0, gy = y / (double)H * 2.0 - 1.0;
-      const double ix = ((gx + 1.0) * (double)W - 1.0) / 2.0, iy = ((gy + 1.0) * (double)H - 1.0) / 2.0;
-      const double x0 = floor(ix), y0 = floor(iy);
-      const double wnw = (x0 + 1.0 - ix) * (y0 + 1.0 - iy), wne = (ix - x0) * (y0 + 1.0 - iy);
-      const double wsw = (x0 + 1.0 - ix) * (iy - y0), wse = (ix - x0) * (iy - y0);
-      const bool inx0 = x0 >= 0.0 && x0 <= (double)(W - 1), inx1 = x0 + 1.0 >= 0.0 && x0 + 1.0 <= (double)(W - 1);
-      const bool iny0 = y0 >= 0.0 && y0 <= (double)(H - 1), iny1 = y0 + 1.0 >= 0.0 && y0 + 1.0 <= (double)(H - 1);
-      int best = 0;
-      double bestv = 0.0;
-      if (gx > -4.0 && gx < 4.0 && gy > -4.0 && gy < 4.0) {   // far outside: all taps are padding
-        const int xi = (int)x0, yi = (int)y0;
-        for (int c = 0; c < C; ++c) {
-          const float* img = s.sem.img_seg_conf + (size_t)c * H * W;
-          double v = 0.0;
-          if (inx0 && iny0) v += (double)img[yi * W + xi] * wnw;
-          if (inx1 && iny0) v += (double)img[yi * W + xi + 1] * wne;
-          if (inx0 && iny1) v += (double)img[(yi + 1) * W + xi] * wsw;
-          if (inx1 && iny1) v += (double)img[(yi + 1) * W + xi + 1] * wse;
-          if (c == 0 || v > bestv) {
-            bestv = v;
-            best = c;
-          }
-        }
-      }
+      double gx, gy;
+      const int best = sem_sample_class(s.sem.img_seg_conf, C, H, W, x, y, gx, gy);
       const int cls = s.sem.sf_seg[i];
       const bool val = best != cls && gx > -1.0 && gx < 1.0 && gy > -1.0 && gy < 1.0;
       if (val && cls >= 0 && cls < C) {
@@ -142,11 +119,11 @@ __global__ void __launch_bounds__(256) k_gf_morph(GfSlot* __restrict__ slots) {
         if (e1 - e0 >= 2) {      // a single boundary pixel has no 2nd neighbour: treated as no boundary
           s.terms[7] = 1.0;      // the class contributes a list entry (same value from every writer)
           // a candidate: its search is done by the WHOLE workgroup below
-          const int k = atomicAdd(&n_cand, 1);
-          c_x[k] = x;
-          c_y[k] = y;
-          c_e0[k] = e0;
-          c_e1[k] = e1;
+          const int k = atomicAdd(&cand.n_cand, 1);
+          cand.x[k] = x;
+          cand.y[k] = y;
+          cand.e0[k] = e0;
+          cand.e1[k] = e1;
           my_cand = k;
           my_x = x;
           my_y = y;
@@ -157,69 +134,16 @@ __global__ void __launch_bounds__(256) k_gf_morph(GfSlot* __restrict__ slots) {
     }
   }
   __syncthreads();
-  // ---- the two nearest boundary pixels of every candidate's class: the mismatching surfels are a thin band along the class
-  // boundaries (a few per cent), so one lane per surfel scanning ~1 000-2 000 boundary pixels left 60 lanes of its wave idle for
-  // the whole scan (534 us per launch at C4, 80 % of the Semantic-SuPer step).  The workgroup's WAVES take its candidates one
-  // after the other (wave w the candidates w, w + 4, ...): 64 lanes scan the class's list strided, each keeps its two nearest
-  // in (distance, list position) order -- the order of the sequential scan with strict <, i.e. find_knn's lowest index on
-  // ties -- and a butterfly merge gives the candidate's answer to lane 0.  (First form of round 6: the whole workgroup per
-  // candidate, 256 lanes + a four-way merge through LDS behind two barriers per candidate -- the butterfly and the barriers
-  // were issued by four waves for one candidate: 68 us per launch at C4.)
-  {
-    const int nc = n_cand;
-    const int l = threadIdx.x & 63, w = threadIdx.x >> 6;
-    for (int k = w; k < nc; k += 4) {
-      const double x = c_x[k], y = c_y[k];
-      const int e0 = c_e0[k], e1 = c_e1[k];
-      double d1 = 1e300, d2 = 1e300;
-      int i1 = 0x7fffffff, i2 = 0x7fffffff;
-      for (int e = e0 + l; e < e1; e += 64) {
-        const float2 q = s.edge_xy[e];
-        const double dx = x - (double)q.x, dy = y - (double)q.y;
-        const double d = dx * dx + dy * dy;
-        if (d < d1) {
-          d2 = d1; i2 = i1;
-          d1 = d; i1 = e;
-        } else if (d < d2) {
-          d2 = d; i2 = e;
-        }
-      }
-      // merge of two sorted pairs under (distance, index) order
-      auto before = [](double da, int ia, double db, int ib) { return da < db || (da == db && ia < ib); };
-      auto merge = [&](double od1, int oi1, double od2, int oi2) {
-        // the two smallest of {(d1,i1) <= (d2,i2)} and {(od1,oi1) <= (od2,oi2)}
-        if (before(od1, oi1, d1, i1)) {
-          // other's first leads: second is min(mine first, other's second)
-          if (before(od2, oi2, d1, i1)) { d2 = od2; i2 = oi2; }
-          else { d2 = d1; i2 = i1; }
-          d1 = od1; i1 = oi1;
-        } else if (before(od1, oi1, d2, i2)) {
-          d2 = od1; i2 = oi1;
-        }
-      };
-#pragma unroll
-      for (int off = 32; off >= 1; off >>= 1) {
-        const double od1 = __shfl_xor(d1, off, 64), od2 = __shfl_xor(d2, off, 64);
-        const int oi1 = __shfl_xor(i1, off, 64), oi2 = __shfl_xor(i2, off, 64);
-        merge(od1, oi1, od2, oi2);
-      }
-      if (l == 0) {
-        c_d1[k] = d1; c_d2[k] = d2;
-        c_i1[k] = i1; c_i2[k] = i2;
-      }
-    }
-  }
+  sem_search_candidates(cand, s.edge_xy);
   __syncthreads();
   if (i < f.N) {
     double2 g = make_double2(0.0, 0.0);
     if (my_cand >= 0) {
-      const double x = my_x, y = my_y, d1 = c_d1[my_cand], d2 = c_d2[my_cand];
-      const float2 p1 = s.edge_xy[c_i1[my_cand]], p2 = s.edge_xy[c_i2[my_cand]];
+      const double x = my_x, y = my_y, d1 = cand.d1[my_cand], d2 = cand.d2[my_cand];
+      const float2 p1 = s.edge_xy[cand.i1[my_cand]], p2 = s.edge_xy[cand.i2[my_cand]];
       // drop surfels closer to the image border than to the class boundary
-      const double dte = fmin(fmin(fmin(x, y), (double)my_W - x), (double)my_H - y);
-      const bool ok = !(sqrt(d1) > dte || sqrt(d2) > dte);
-      const double li = (d1 + d2) / 2.0;
-      if (ok && li > 15.0) {
+      double li;
+      if (sem_morph_keep(x, y, my_W, my_H, d1, d2, li)) {
         li_sum = li;
         kept = 1.0;
         g = make_double2(-(((double)p1.x - x) + ((double)p2.x - x)), -(((double)p1.y - y) + ((double)p2.y - y)));

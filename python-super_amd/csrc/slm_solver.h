@@ -1,7 +1,7 @@
 // slm_solver.h -- internal to the LM host (slm_api.hip, slm_bind.hip, slm_lm.hip, slm_terms.hip): what a solver and its slots
 // hold, where the loss partials of its terms sit (LossParts), and the few functions that cross those units.  Device memory
-// is owned by DevBuf / PinnedBuf members (slm_host.h); the descriptors (FrameDev, CorrDev, FaceDev, DataWeightDev) only
-// mirror addresses.
+// is owned by DevBuf / PinnedBuf members (slm_host.h); the descriptors (FrameDev, CorrDev, FaceDev, MorphDev, DataWeightDev)
+// only mirror addresses.
 #pragma once
 #include <algorithm>
 #include <atomic>
@@ -15,12 +15,15 @@
 #include "slm_face.h"
 #include "slm_host.h"
 #include "slm_launch.h"
+#include "slm_morph.h"
 #include "slm_prep.h"
+#include "slm_sem.h"
 #include "slm_workers.h"
 
 constexpr int kLossBlocks = 512;   // data-loss partial sums per slot
 constexpr int kRegBlocksMax = 64;
-constexpr int kCorrBlocks = SLM_CORR_BLOCKS, kFaceBlocks = SLM_FACE_BLOCKS;   // loss partials of the terms per slot (LossParts)
+// loss partials of the terms per slot (LossParts)
+constexpr int kCorrBlocks = SLM_CORR_BLOCKS, kFaceBlocks = SLM_FACE_BLOCKS, kMorphBlocks = SLM_MORPH_BLOCKS;
 
 // The form of the data term: which plan the bind prepares and which kernels the LM entry points launch.
 enum class DataForm {
@@ -61,6 +64,11 @@ struct Slot {
   DevBuf<int32_t> face_tri;
   DevBuf<double> face_areas;
   PinnedBuf<FaceDev> face_pin;  // pinned mirror of `face` for the asynchronous upload of a bind
+  MorphDev morph{};             // boundary-morph term: host mirror of the slot's descriptor (the caller's semantic inputs, none
+  SemScratch morph_edges;       // owned), the slot's own boundary lists (slm_bind_morph; released by slm_destroy) and the
+                                // arrays every selection rewrites
+  DevBuf<uint8_t> morph_kept;
+  DevBuf<double> morph_target, morph_li, morph_part, morph_stat;
   DataWeightDev wdev{};         // data weights: host mirror of the slot's semantic inputs (the caller's arrays, none owned)
   PairPlan pplan;               // K-generic pair path (num_neighbors != 4): pair keys, per-surfel pair indices, surfel order
   PlanCache cache;              // nested-dissection plan: host copy; its device mirrors below (grow-only)
@@ -141,18 +149,22 @@ struct slm_solver {
   bool face_on = false;         // slm_enable_face with a non-zero weight; its weight; the slots' meshes on the device
   double face_w = 0.0;
   DevBuf<FaceDev> face_dev;
+  bool morph_on = false;        // slm_enable_morph with a non-zero weight; its weight; the slots' inputs on the device
+  double morph_w = 0.0;
+  DevBuf<MorphDev> morph_dev;
   bool shard_mode = false;      // slm_set_shard was called (world == 1 included): slots carry the exchange buffers
 };
 
 // Where the terms' loss partials sit in a slot's loss_part: every offset in doubles from the start of the regularisers'
 // partials (loss_part + 2 n_loss_part).  An LM launch packs its {sum, 0} pairs -- the n_reg_part of the regularisers, then
-// the correspondence term's kCorrBlocks, then the face term's kFaceBlocks, each only on a solver with the term enabled --
-// so that k_accept sums them as n_acc_part pairs.  A direct call (slm_corr_loss, slm_face_loss) stores its pairs at a fixed
-// place behind kRegBlocksMax pairs (any place among the pairs would do: every LM iteration rewrites its own).  The
-// correspondence term's kept counts sit behind every pair; only a solver with the face term has room for that term's pairs,
-// its counts sit that much further back and its slots' loss_part is that much longer.
+// the correspondence term's kCorrBlocks, then the face term's kFaceBlocks, then the boundary-morph term's kMorphBlocks, each
+// only on a solver with the term enabled -- so that k_accept sums them as n_acc_part pairs.  A direct call (slm_corr_loss,
+// slm_face_loss) stores its pairs at a fixed place behind kRegBlocksMax pairs (any place among the pairs would do: every LM
+// iteration rewrites its own).  The correspondence term's kept counts sit behind every pair; only a solver with the face
+// term has room for that term's pairs, its counts sit that much further back and its slots' loss_part is that much longer;
+// the boundary-morph term's pair likewise (a direct call of that term writes its caller's array, no pair).
 struct LossParts {
-  int corr, face;                  // the terms' pairs of an LM launch
+  int corr, face, morph;           // the terms' pairs of an LM launch
   int corr_direct, face_direct;    // ... of a direct call
   int corr_cnt;                    // the correspondence term's kCorrBlocks kept counts
   int n_acc_part;                  // pairs k_accept sums behind the data partials
@@ -164,9 +176,11 @@ inline LossParts loss_parts(const slm_solver* s, int n_reg_part) {
   p.n_acc_part = n_reg_part + (s->corr_mode ? kCorrBlocks : 0);
   p.face = 2 * p.n_acc_part;
   if (s->face_on) p.n_acc_part += kFaceBlocks;
+  p.morph = 2 * p.n_acc_part;
+  if (s->morph_on) p.n_acc_part += kMorphBlocks;
   p.corr_direct = 2 * kRegBlocksMax;
   p.face_direct = p.corr_direct + 2 * kCorrBlocks;
-  p.corr_cnt = p.face_direct + (s->face_on ? 2 * kFaceBlocks : 0);
+  p.corr_cnt = p.face_direct + (s->face_on ? 2 * kFaceBlocks : 0) + (s->morph_on ? 2 * kMorphBlocks : 0);
   p.doubles = (size_t)2 * kLossBlocks + p.corr_cnt + kCorrBlocks;
   return p;
 }

@@ -1,7 +1,7 @@
 // slm_terms.hip -- the entry points of the LM path's opt-in terms (include/super_lm.h): the flow-correspondence term
-// (kernels in slm_corr.hip), the triangle-area face term (slm_face.hip) and the per-residual weights of the data term (the
-// weighted kernels in slm_data.hip).  Enabling, binding a slot's inputs and the parity read-outs; the LM step that runs the
-// terms is slm_lm.hip.  Host side only orchestrates launches.
+// (kernels in slm_corr.hip), the triangle-area face term (slm_face.hip), the semantic boundary-morph term (slm_morph.hip)
+// and the per-residual weights of the data term (the weighted kernels in slm_data.hip).  Enabling, binding a slot's inputs
+// and the parity read-outs; the LM step that runs the terms is slm_lm.hip.  Host side only orchestrates launches.
 #include "slm_solver.h"
 
 namespace {
@@ -183,6 +183,96 @@ int slm_face_loss(slm_solver* s, int32_t slot, double* out, void* stream) {
   launch_face_loss(s->frames_dev + slot, s->face_dev + slot, 1, s->face_w, 0, part, st);
   launch_term_loss_out(s->frames_dev, slot, part, kFaceBlocks, -1, s->face_dev, out, st);   // (the count: the mesh's triangles)
   HIPCHK(hipGetLastError());
+  return SLM_OK;
+}
+
+// ---- semantic boundary-morph term (include/super_lm.h; kernels in slm_morph.hip) --------------------------------------
+int slm_enable_morph(slm_solver* s, double weight) {
+  if (!s) return fail(SLM_ERR_INVALID, "slm_enable_morph: null argument");
+  if (!(weight - weight == 0.0)) return fail(SLM_ERR_INVALID, "slm_enable_morph: weight must be finite");
+  if (s->cfg.data_path == 1) return fail(SLM_ERR_UNSUPPORTED, "slm_enable_morph: needs the pair-record data path (data_path 0 or 2)");
+  if (s->cfg.solver_path == 1) return fail(SLM_ERR_UNSUPPORTED, "slm_enable_morph: needs a nested-dissection solver_path (0, 2, 3 or 4)");
+  if (!s->cfg.use_data) return fail(SLM_ERR_UNSUPPORTED, "slm_enable_morph: needs the data term (use_data 1)");
+  if (s->shard_mode)
+    return fail(SLM_ERR_UNSUPPORTED, "slm_enable_morph: the solver is sharded (slm_set_shard); the term needs every surfel of the frame "
+                                     "on one device");
+  for (const Slot& sl : s->slots)
+    if (sl.h.bound || sl.prep_ticket || sl.model_ready || sl.loss_part)   // (loss_part: the first bind sizes it for the term)
+      return fail(SLM_ERR_INVALID, "slm_enable_morph: a slot is already bound; call it after slm_create and before the first bind");
+  const bool on = weight != 0.0;
+  if (on && !s->morph_dev) {
+    HIPCHK(s->morph_dev.grow(s->slots.size(), s->slots.size()));
+    HIPCHK(hipMemset(s->morph_dev, 0, sizeof(MorphDev) * s->slots.size()));
+  }
+  s->morph_on = on;
+  s->morph_w = on ? weight : 0.0;
+  return SLM_OK;
+}
+
+int slm_bind_morph(slm_solver* s, int32_t slot, int32_t num_classes, const int32_t* img_seg, const float* img_seg_conf,
+                   const int32_t* sf_seg, int32_t* edge_counts_host, void* stream) {
+  Slot* sp = nullptr;
+  int rc = term_slot("slm_bind_morph", s, img_seg != nullptr && img_seg_conf != nullptr && sf_seg != nullptr, slot, s && s->morph_on,
+                     "slm_enable_morph", &sp);
+  if (rc) return rc;
+  if (num_classes < 1 || num_classes > SLM_MAX_CLASSES)
+    return fail(SLM_ERR_UNSUPPORTED, "slm_bind_morph: num_classes must be in 1..SLM_MAX_CLASSES (4)");
+  hipStream_t st = (hipStream_t)stream;
+  Slot& sl = *sp;
+  const slm_frame& f = sl.h.f;
+  // the boundary lists of the frame's classes, once per bind (a size read-back: the host waits for the stream here)
+  HIPCHK(sem_extract_edges(sl.morph_edges, num_classes, img_seg, f.H, f.W, sl.morph.edge_off, st));
+  const size_t N = (size_t)std::max(f.N, 1);
+  HIPCHK(grow(sl.morph_kept, N));
+  HIPCHK(grow(sl.morph_target, 2 * N));
+  HIPCHK(grow(sl.morph_li, N));
+  HIPCHK(grow(sl.morph_part, 3 * ((N + 255) / 256)));
+  HIPCHK(grow(sl.morph_stat, 4));
+  HIPCHK(hipMemsetAsync(sl.morph_stat, 0, sizeof(double) * 4, st));
+  sl.morph.img_seg_conf = img_seg_conf;
+  sl.morph.sf_seg = sf_seg;
+  sl.morph.edge_xy = sl.morph_edges.edge_xy;
+  sl.morph.kept = sl.morph_kept.p;
+  sl.morph.target = sl.morph_target.p;
+  sl.morph.li = sl.morph_li.p;
+  sl.morph.part = sl.morph_part.p;
+  sl.morph.stat = sl.morph_stat.p;
+  sl.morph.C = num_classes;
+  sl.morph.has = 1;
+  HIPCHK(hipMemcpyAsync(s->morph_dev + slot, &sl.morph, sizeof(MorphDev), hipMemcpyHostToDevice, st));
+  HIPCHK(hipStreamSynchronize(st));   // (the source is the slot's own mirror, which the next bind rewrites)
+  if (edge_counts_host)
+    for (int c = 0; c < num_classes; ++c) edge_counts_host[c] = sl.morph.edge_off[c + 1] - sl.morph.edge_off[c];
+  return SLM_OK;
+}
+
+int slm_morph_loss(slm_solver* s, int32_t slot, double* out, void* stream) {
+  Slot* sp = nullptr;
+  int rc = term_slot("slm_morph_loss", s, out != nullptr, slot, s && s->morph_on, "slm_enable_morph", &sp);
+  if (rc) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  if ((rc = clear_flags(s, slot, st)) != SLM_OK) return rc;
+  // (a slot without inputs: the fold alone, which stores {0, 0, 0})
+  launch_morph_select(s->frames_dev + slot, s->morph_dev + slot, 1, sp->morph.has ? sp->h.f.N : 0, sp->h.f.K, s->morph_w, 0, -1, out, st);
+  HIPCHK(hipGetLastError());
+  return SLM_OK;
+}
+
+int slm_morph_targets(slm_solver* s, int32_t slot, uint8_t* kept, double* target_xy, double* li, void* stream) {
+  Slot* sp = nullptr;
+  int rc = term_slot("slm_morph_targets", s, true, slot, s && s->morph_on, "slm_enable_morph", &sp);
+  if (rc) return rc;
+  if (!sp->morph.has) return fail(SLM_ERR_UNBOUND, "slm_morph_targets: slm_bind_morph first");
+  hipStream_t st = (hipStream_t)stream;
+  if ((rc = clear_flags(s, slot, st)) != SLM_OK) return rc;
+  const size_t N = (size_t)sp->h.f.N;
+  launch_morph_select(s->frames_dev + slot, s->morph_dev + slot, 1, sp->h.f.N, sp->h.f.K, s->morph_w, 0, -1, nullptr, st);
+  HIPCHK(hipGetLastError());
+  if (N > 0) {
+    if (kept) HIPCHK(hipMemcpyAsync(kept, sp->morph.kept, N, hipMemcpyDeviceToDevice, st));
+    if (target_xy) HIPCHK(hipMemcpyAsync(target_xy, sp->morph.target, sizeof(double) * 2 * N, hipMemcpyDeviceToDevice, st));
+    if (li) HIPCHK(hipMemcpyAsync(li, sp->morph.li, sizeof(double) * N, hipMemcpyDeviceToDevice, st));
+  }
   return SLM_OK;
 }
 

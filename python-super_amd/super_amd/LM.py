@@ -130,7 +130,8 @@ class LM_Solver():
     """Drop-in for ``super.LM.LM_Solver``; see module docstring."""
 
     def __init__(self, opt, convs=None, max_frames=1, shard_surfels=False, rank=None, world=None,
-                 all_reduce=None, broadcast=None, corr_term=False, weighted_data=False, face_term=False):
+                 all_reduce=None, broadcast=None, corr_term=False, weighted_data=False, face_term=False,
+                 morph_term=False):
         """``LM_Solver(opt, convs)`` as in the reference.  ``shard_surfels=True`` (after
         ``torch.distributed.init_process_group``) splits the surfels of ONE large frame over the GPUs
         of a node: every rank evaluates its share, the block-sparse J^T J / J^T r sums and the loss are
@@ -150,8 +151,27 @@ class LM_Solver():
         (``slm_enable_face``, include/super_lm.h): ``sf.ED_nodes.triangles`` (3, F) and ``sf.ED_nodes.triangles_areas`` (F,)
         of every frame, weight ``opt.mesh_face_weight`` on the RESIDUAL (GraphFit weighs the squared sum: its
         ``mesh_face_weight`` = this one squared).  Without the flag ``opt.mesh_face`` is ignored by this class exactly as
+        before.
+        ``morph_term=True`` (opt-in; needs ``opt.sf_bn_morph``) adds the semantic boundary-morph term of Semantic-SuPer
+        (``super/deform_mesh.py:126-194``, there on the first-order path only) in its Gauss-Newton form
+        (``slm_enable_morph``, include/super_lm.h): ``inputs[("seg",0)]``, ``inputs[("seg_conf",0)]`` and ``sf.seg`` of every
+        frame, ``opt.num_classes`` classes, weight ``opt.sf_bn_morph_weight`` on the RESIDUAL (GraphFit weighs the mean: its
+        ``sf_bn_morph_weight`` = this one squared).  Without the flag ``opt.sf_bn_morph`` is ignored by this class exactly as
         before."""
         self.opt = opt
+        self.morph_on = False
+        if morph_term:
+            if not getattr(opt, "sf_bn_morph", False):
+                raise ValueError("LM_Solver(morph_term=True) needs opt.sf_bn_morph")
+            if shard_surfels or world is not None:
+                raise NotImplementedError("LM_Solver: morph_term with shard_surfels is not built (the term needs every "
+                                          "surfel of the frame on one device)")
+            self.morph_on = True
+            self.morph_weight = float(getattr(opt, "sf_bn_morph_weight", 1.0))
+            self.morph_classes = int(opt.num_classes)
+        self._morph_loss_of = None                   # (n, u, v, minimal_loss) of the last run; its losses once they were asked for
+        self._morph_loss = None
+        self.last_edge_counts = None                 # per slot: the boundary-list lengths per class of the last bind
         self.face_on = False
         if face_term:
             if not getattr(opt, "mesh_face", False):
@@ -241,6 +261,8 @@ class LM_Solver():
                 _lib.check(self.lib.slm_enable_data_weights(h, self.seg_mode, self.pp_max), "slm_enable_data_weights")
             if self.face_on:
                 _lib.check(self.lib.slm_enable_face(h, self.face_weight), "slm_enable_face")
+            if self.morph_on:
+                _lib.check(self.lib.slm_enable_morph(h, self.morph_weight), "slm_enable_morph")
             if self.sharded:
                 _lib.check(self.lib.slm_set_shard(h, self.rank, self.world), "slm_set_shard")
             self._solvers[key] = h
@@ -389,6 +411,63 @@ class LM_Solver():
         _lib.check(self.lib.slm_bind_data_semantic(h, slot, int(sc.shape[1]), _dev_ptr(seg), _dev_ptr(sc), _dev_ptr(tc),
                                                    _stream_ptr(dev)), "slm_bind_data_semantic")
 
+    def _bind_morph(self, h, slot, bf, sf, inputs):
+        """The inputs of the boundary-morph term of a bound slot (``morph_term``): ``inputs[("seg",0)]`` (1,1,H,W) -- or
+        (1,C,H,W) scores, whose argmax over the channels is taken as ``find_edge_region`` does --, ``inputs[("seg_conf",0)]``
+        (1,C,H,W) and ``sf.seg`` (N,).  Returns the boundary-list lengths per class."""
+        if not self.morph_on:
+            return None
+        dev, N, H, W, nc = bf.device, bf.c.N, bf.c.H, bf.c.W, self.morph_classes
+        pre = "LM_Solver(morph_term=True): "
+        iseg = inputs.get(("seg", 0)) if hasattr(inputs, "get") else None
+        iconf = inputs.get(("seg_conf", 0)) if hasattr(inputs, "get") else None
+        seg = getattr(sf, "seg", None)
+        for name, t in (('inputs[("seg",0)]', iseg), ('inputs[("seg_conf",0)]', iconf), ("sf.seg", seg)):
+            if t is None:
+                raise ValueError(pre + name + " is missing")
+        if iseg.dim() != 4 or tuple(iseg.shape[2:]) != (H, W) or iseg.shape[0] != 1:
+            raise ValueError(pre + f'inputs[("seg",0)] must be (1,1,{H},{W}), got {tuple(iseg.shape)}')
+        if tuple(iconf.shape) != (1, nc, H, W):
+            raise ValueError(pre + f'inputs[("seg_conf",0)] must be (1,{nc},{H},{W}), got {tuple(iconf.shape)}')
+        if seg.numel() != N or seg.dim() > 2:
+            raise ValueError(pre + f"sf.seg must be ({N},), got {tuple(seg.shape)}")
+        if iseg.shape[1] > 1:
+            iseg = torch.argmax(iseg, dim=1, keepdim=True)
+        iseg = _as(iseg[0, 0], torch.int32, dev)
+        iconf = _as(iconf[0], torch.float32, dev)
+        seg = _as(seg.reshape(-1), torch.int32, dev)
+        bf.morph_keep = (iseg, iconf, seg)             # read in place by the library while the slot is used
+        counts = (C.c_int32 * _lib.SLM_MAX_CLASSES)()
+        _lib.check(self.lib.slm_bind_morph(h, slot, nc, _dev_ptr(iseg), _dev_ptr(iconf), _dev_ptr(seg), counts,
+                                           _stream_ptr(dev)), "slm_bind_morph")
+        return list(counts)[:nc]
+
+    @property
+    def last_morph_loss(self):
+        """Per slot of the last ``LM`` / ``LM_batch``: (the term's loss at the returned beta, kept surfels, candidates);
+        ``None`` without ``morph_term`` or before a run.  Evaluated when first read, in one device-to-host copy for all
+        slots: a caller that never reads it pays no launch and no host wait per frame."""
+        if self._morph_loss is None and self._morph_loss_of is not None:
+            n, u, v, ml = self._morph_loss_of
+            h, dev = self._handle(u, v, ml), self._bound[0].device
+            out = torch.empty((n, 3), dtype=torch.float64, device=dev)
+            for i in range(n):
+                _lib.check(self.lib.slm_morph_loss(h, i, _dev_ptr(out[i]), _stream_ptr(dev)), "slm_morph_loss")
+            self._morph_loss = [(float(a), int(b), int(c)) for a, b, c in out.cpu().tolist()]
+        return self._morph_loss
+
+    def morph_targets(self, slot=0, u=10, v=7.5, minimal_loss=1e10):
+        """The term's selection of a bound slot at its current beta: (kept (N,) bool, targets (N,2) f64, l_i (N,) f64) on
+        the device."""
+        h, bf = self._handle(u, v, minimal_loss), self._bound[slot]
+        N, dev = bf.c.N, bf.device
+        kept = torch.empty(N, dtype=torch.uint8, device=dev)
+        tgt = torch.empty((N, 2), dtype=torch.float64, device=dev)
+        li = torch.empty(N, dtype=torch.float64, device=dev)
+        _lib.check(self.lib.slm_morph_targets(h, slot, _dev_ptr(kept), _dev_ptr(tgt), _dev_ptr(li), _stream_ptr(dev)),
+                   "slm_morph_targets")
+        return kept.bool(), tgt, li
+
     def data_weights(self, slot=0, u=10, v=7.5, minimal_loss=1e10):
         """The weights w_i (N,) float64 of a bound slot at its current beta, 0 for unmatched surfels (``weighted_data``)."""
         h, bf = self._handle(u, v, minimal_loss), self._bound[slot]
@@ -463,6 +542,7 @@ class LM_Solver():
         bf = self._bind(h, 0, sf, inputs, new_data)
         self._bind_corr(h, 0, bf, self._corr_arg(flow, corr_points, required=True))
         self._bind_semantic(h, 0, bf, sf, new_data)
+        self._bind_morph(h, 0, bf, sf, inputs)
         st = _stream_ptr(bf.device)
         b64 = _as(beta, torch.float64, bf.device)
         _lib.check(self.lib.slm_set_beta(h, 0, _dev_ptr(b64), st), "slm_set_beta")
@@ -483,6 +563,10 @@ class LM_Solver():
             fo = torch.empty(2, dtype=torch.float64, device=bf.device)
             _lib.check(self.lib.slm_face_loss(h, 0, _dev_ptr(fo), st), "slm_face_loss")
             total = total + fo[0]
+        if self.morph_on:
+            mo = torch.empty(3, dtype=torch.float64, device=bf.device)
+            _lib.check(self.lib.slm_morph_loss(h, 0, _dev_ptr(mo), st), "slm_morph_loss")
+            total = total + mo[0]
         return total
 
     def _corr_arg(self, flow, corr_points, required):
@@ -515,6 +599,8 @@ class LM_Solver():
         for i, (bf, corr) in enumerate(zip(bfs, corrs)):
             self._bind_corr(h, i, bf, corr)
             self._bind_semantic(h, i, bf, frames[i][0], frames[i][2])
+        if self.morph_on:
+            self.last_edge_counts = [self._bind_morph(h, i, bf, frames[i][0], frames[i][1]) for i, bf in enumerate(bfs)]
         dev = bfs[0].device
         st = _stream_ptr(dev)
         if self.sharded:
@@ -532,6 +618,7 @@ class LM_Solver():
         if self.corr_mode:
             self.last_corr_kept = [None if c is None else self.corr_loss(i, u, v, minimal_loss)[1] for i, c in enumerate(corrs)]
         self._face_loss_of, self._face_loss = ((n, u, v, minimal_loss) if self.face_on else None), None
+        self._morph_loss_of, self._morph_loss = ((n, u, v, minimal_loss) if self.morph_on else None), None
         return betas
 
     # ---- one frame sharded over several GPUs ------------------------------------------------

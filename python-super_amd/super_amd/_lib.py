@@ -44,6 +44,7 @@ EXPORTS = [
     "slm_enable_corr", "slm_bind_corr_flow", "slm_bind_corr_points", "slm_corr_get_targets", "slm_corr_loss",
     "slm_enable_data_weights", "slm_bind_data_semantic", "slm_data_weights",
     "slm_enable_face", "slm_set_face_mesh", "slm_face_loss",
+    "slm_enable_morph", "slm_bind_morph", "slm_morph_loss", "slm_morph_targets",
 ]
 
 
@@ -252,6 +253,10 @@ def load():
         "slm_enable_face": [vp, dbl],
         "slm_set_face_mesh": [vp, i32, i32, vp, vp, vp],
         "slm_face_loss": [vp, i32, vp, vp],
+        "slm_enable_morph": [vp, dbl],
+        "slm_bind_morph": [vp, i32, i32, vp, vp, vp, C.POINTER(C.c_int32), vp],
+        "slm_morph_loss": [vp, i32, vp, vp],
+        "slm_morph_targets": [vp, i32, vp, vp, vp, vp],
         "slm_graph_init": [i32, i32, i32, vp, vp, vp, vp, C.POINTER(SlmGraphOutputs), C.POINTER(C.c_int32), vp],
         "slm_graph_init_semantic": [i32, i32, i32, vp, vp, vp, vp, i32, vp, i32, C.POINTER(SlmGraphOutputs), vp, vp,
                                     C.POINTER(C.c_int32), vp],
