@@ -1082,6 +1082,88 @@ int slm_debug_read(slm_solver* s, int32_t slot, int32_t what, double* host_out, 
 int slm_debug_read_plan(slm_solver* s, int32_t slot, int32_t what, void* host_out, int64_t max_bytes, int64_t* n_bytes,
                         void* stream);
 
+/* =====================================================================================
+ * Global rigid pre-alignment of the LM path: T_g ahead of the node solve.
+ * The first-order path carries the reference's global row T_g (super/deform_mesh.py:213-223); the LM path has none and
+ * must explain bulk motion of the scene against the camera with its per-node transforms.  This stage estimates
+ * T_g = (q, t) by the reference's own LM loop (super/LM.py:81-122) run on ONE node at the origin -- every surfel attached
+ * to it with weight 1, K = 1, beta_g = (q, t) started at identity -- with the terms
+ *   data  r_i = w_data n.(T(p_i) - o),  T(p) = R(q) p + t  (the un-normalised quaternion formula of the node solve)
+ *   Rot   w_rot (1 - |q|^2), in float32 like the node solve's; ALWAYS on here (without it |q| is a free scale)
+ * and the rules of the node solve's data term (see slm_data_residuals: projection with Z + 1e-8, validity on the rounded
+ * pixel, four taps, NaN drop, the integer-coordinate double tap; c = n(I - A) + e B with the plain Z in dPi; the row
+ * w_data [c dR(q)p/dq | c]).  The data term is the plain one: no semantic weights, no truncation.  u, v, minimal_loss,
+ * accept / reject under phase_test and the fresh match set of the loss at the trial point are LM()'s.  The caller then
+ * moves the model by T_g (slm_rigid_transform) and runs the unchanged node LM on the moved model.
+ *
+ * A free-standing context (like slm_depth / slm_fuse / slm_render): independent of slm_solver, the caller's arrays are read
+ * in place, nothing is bound.  Of each slm_frame the stage reads N, T, H, W, fx .. cy, sf_points, state_f64 and the four
+ * target fields; the KNN and node fields are ignored and may be null.
+ *
+ * The sums (the 7 x 7 normal equations, the loss, the match count) have a FIXED order: every 256 consecutive surfels give
+ * one partial (lane butterflies, then the four waves through LDS), one wave adds the partials in index order.  No float
+ * atomics; two runs give the same bits, whatever grid the launch chose.  One pass over the surfels per iteration yields the
+ * loss at the trial point AND the normal equations there (the next iteration's, if the step is accepted); a one-wave kernel
+ * accepts or rejects, damps, factors (Cholesky), solves and writes the next trial point and the record: two launches per
+ * iteration, no host synchronisation, the frame index a grid dimension.
+ *
+ * slm_rigid_run: the whole loop for frames[0 .. n_frames) (an array in HOST memory, copied by the call) into slots
+ *   [0, n_frames).  N = 0 or T = 0 is not an error: the result is identity, every record has M_grad = 0; so does a frame
+ *   where nothing matches (its system is the Rot term plus u I: positive definite, zero right-hand side).  A failed
+ *   factorisation (a pivot that is not > 0, NaN included) records SLM_ITER_SOLVER_FAILED for that iteration and ends that
+ *   frame's loop like LM()'s break (later records SLM_ITER_NOT_RUN); the other frames of the batch go on.
+ * slm_rigid_get: Tg7_device[7] = (q / |q|, t) of the slot's last run.  slm_rigid_get_beta: the raw 7 doubles.
+ * slm_rigid_get_records: synchronises `stream`, copies min(max_records, num_iterations of the last run) records to HOST
+ *   memory; *n_out (may be null) receives that count.
+ * slm_rigid_assemble: the normal equations and the loss of ONE frame at a given point (what slm_assemble / slm_loss are
+ *   to the solver): JtJ49 (7,7) row-major symmetric, jtl7 = -J^T r, loss_M = {sum of squared residuals, matched count};
+ *   each output is device memory and may be null.  Uses a slot of its own: the results of a run are kept.
+ * slm_rigid_transform: in place on (n,3) device arrays, float64 (f64 != 0) or float32: p <- R(q) p + t,
+ *   n <- R(q) n / max(|R(q) n|, 1e-12) (F.normalize: a zero normal stays zero); norms may be null.  For surfels and nodes.
+ *
+ * Refusals (<fn> = the entry point):
+ *   SLM_ERR_INVALID    "<fn>: null argument"
+ *                      "slm_rigid_create: max_frames must be >= 1"
+ *                      "slm_rigid_run: n_frames must be in 1..max_frames"
+ *                      "<fn>: num_iterations must be >= 0"           (slm_rigid_run, slm_rigid_assemble)
+ *                      "<fn>: H and W must be >= 2"
+ *                      "<fn>: N and T must be >= 0"
+ *                      "<fn>: N > 0 needs sf_points"
+ *                      "<fn>: T > 0 needs tgt_points, tgt_norms, index_map and tgt_valid"
+ *                      "<fn>: bad slot"                              (slm_rigid_get, _get_beta, _get_records)
+ *                      "slm_rigid_get_records: max_records must be >= 0"
+ *                      "slm_rigid_transform: n must be >= 0"
+ *                      "slm_rigid_abi_check: caller's slm_rigid_config has <a> bytes, the library's <b>"
+ *   SLM_ERR_NO_DEVICE  "slm_rigid_create: no HIP device visible"
+ * ===================================================================================== */
+typedef struct slm_rigid slm_rigid; /* opaque */
+
+typedef struct slm_rigid_config {
+  int32_t num_iterations;   /* opt.num_optimize_iterations */
+  int32_t phase_test;       /* opt.phase == "test": accept/reject; 0 = "train": always accept */
+  double w_data;            /* opt.sf_point_plane_weight */
+  double w_rot;             /* opt.mesh_rot_weight */
+  double u0;                /* LM(..., u=10) */
+  double v;                 /* LM(..., v=7.5) */
+  double minimal_loss0;     /* LM(..., minimal_loss=1e10) */
+} slm_rigid_config;
+
+/* The handshake of this stage's one struct (slm_abi_check keeps its signature: the stage is an addition to ABI 3, no
+ * existing struct or entry point changed); bindings call it once after loading the library (super_amd/_lib.py does). */
+int slm_rigid_abi_check(int32_t sizeof_slm_rigid_config);
+int slm_rigid_create(int32_t max_frames, slm_rigid** out);
+int slm_rigid_destroy(slm_rigid* r);
+int slm_rigid_run(slm_rigid* r, const slm_rigid_config* cfg, int32_t n_frames, const slm_frame* frames /*host array*/,
+                  void* stream);
+int slm_rigid_get(slm_rigid* r, int32_t slot, double* Tg7_device, void* stream);
+int slm_rigid_get_beta(slm_rigid* r, int32_t slot, double* beta7_device, void* stream);
+int slm_rigid_get_records(slm_rigid* r, int32_t slot, slm_iter_record* host_out, int32_t max_records, int32_t* n_out,
+                          void* stream);
+int slm_rigid_assemble(slm_rigid* r, const slm_rigid_config* cfg, const slm_frame* frame, const double* beta7_device,
+                       double* JtJ49_device, double* jtl7_device, double* loss_M_device /*[2]*/, void* stream);
+int slm_rigid_transform(int32_t n, void* points, void* norms /*may be null*/, int32_t f64, const double* Tg7_device,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -131,7 +131,7 @@ class LM_Solver():
 
     def __init__(self, opt, convs=None, max_frames=1, shard_surfels=False, rank=None, world=None,
                  all_reduce=None, broadcast=None, corr_term=False, weighted_data=False, face_term=False,
-                 morph_term=False):
+                 morph_term=False, global_rigid=False):
         """``LM_Solver(opt, convs)`` as in the reference.  ``shard_surfels=True`` (after
         ``torch.distributed.init_process_group``) splits the surfels of ONE large frame over the GPUs
         of a node: every rank evaluates its share, the block-sparse J^T J / J^T r sums and the loss are
@@ -157,8 +157,24 @@ class LM_Solver():
         (``slm_enable_morph``, include/super_lm.h): ``inputs[("seg",0)]``, ``inputs[("seg_conf",0)]`` and ``sf.seg`` of every
         frame, ``opt.num_classes`` classes, weight ``opt.sf_bn_morph_weight`` on the RESIDUAL (GraphFit weighs the mean: its
         ``sf_bn_morph_weight`` = this one squared).  Without the flag ``opt.sf_bn_morph`` is ignored by this class exactly as
-        before."""
+        before.
+        ``global_rigid=True`` (opt-in) runs the global rigid pre-alignment ahead of the node solve (``super_amd.rigid``,
+        ``slm_rigid_*`` in include/super_lm.h): ``LM()`` / ``LM_batch()`` first estimate ``T_g`` of every frame
+        (``RigidAlign``: the plain, unweighted point-to-plane term plus the Rot term, whatever terms the node solve
+        carries), then MOVE ``sf`` BY IT (``rigid_update``: ``sf.points``, ``sf.norms``, ``sf.ED_nodes.points`` and
+        ``.norms`` are replaced by the moved tensors), then run exactly what they run without the flag on the moved
+        model.  They still return (J,7): ``Surfels.update(deform)`` after them completes the frame.  ``last_rigid`` holds
+        the ``T_g`` of the last call.  Not built with ``shard_surfels``; ``prepare_model()`` is refused (the model moves
+        after the target arrives: a plan prepared ahead would be sorted from stale points).  Without the flag nothing
+        changes."""
         self.opt = opt
+        self.global_rigid = bool(global_rigid)
+        if self.global_rigid and (shard_surfels or world is not None):
+            raise NotImplementedError("LM_Solver: global_rigid with shard_surfels is not built (the stage needs every "
+                                      "surfel of the frame on one device)")
+        self._rigid = None                           # RigidAlign, made at the first run
+        self.last_rigid = None                       # per frame of the last LM / LM_batch: T_g (7,) float64 on the device
+        self.last_rigid_records = None
         self.morph_on = False
         if morph_term:
             if not getattr(opt, "sf_bn_morph", False):
@@ -503,6 +519,9 @@ class LM_Solver():
         Optional: ``LM()`` alone does everything, as the reference does.  Not for surfel-sharded solvers' first bind
         order.  When the model changes after all -- other tensors or an in-place write, seen in the tensors' version
         counters -- the next ``LM()`` drops the preparation (``slm_discard_prepared``) and prepares in full."""
+        if self.global_rigid:
+            raise NotImplementedError("LM_Solver.prepare_model: not with global_rigid (LM() moves the model after the "
+                                      "target arrives: a plan prepared ahead would be sorted from stale points)")
         h = self._handle(u, v, minimal_loss)
         self._face_mesh(h, slot, sf)
         mv = ModelView(sf, state=getattr(self.opt, "slm_state_dtype", None))
@@ -595,6 +614,7 @@ class LM_Solver():
         h = self._handle(u, v, minimal_loss)
         corrs = [fr[3] if len(fr) > 3 else None for fr in frames]
         frames = [tuple(fr[:3]) for fr in frames]
+        rigid_recs = self._rigid_stage(frames, u, v, minimal_loss) if self.global_rigid else [None] * n
         bfs = self._bind_batch(h, frames) if n > 1 else [self._bind(h, 0, *frames[0])]
         for i, (bf, corr) in enumerate(zip(bfs, corrs)):
             self._bind_corr(h, i, bf, corr)
@@ -614,7 +634,7 @@ class LM_Solver():
             betas.append(beta)
             recs = self.records(h, i, st)
             self.last_records.append(recs)
-            self._report(fr[0], fr[1], recs)
+            self._report(fr[0], fr[1], recs, rigid_recs[i])
         if self.corr_mode:
             self.last_corr_kept = [None if c is None else self.corr_loss(i, u, v, minimal_loss)[1] for i, c in enumerate(corrs)]
         self._face_loss_of, self._face_loss = ((n, u, v, minimal_loss) if self.face_on else None), None
@@ -665,7 +685,21 @@ class LM_Solver():
         return [dict(loss=r.loss, u=r.u, accepted=bool(r.accepted), status=int(r.status),
                      M_grad=int(r.M_grad), M_loss=int(r.M_loss)) for r in arr[:n]]
 
-    def _report(self, sf, inputs, recs):
+    def _rigid_stage(self, frames, u, v, minimal_loss):
+        """The rigid pre-alignment of every frame: ``T_g`` into ``last_rigid``, every ``sf`` moved by its own."""
+        from .rigid import RigidAlign, rigid_update
+        if len({id(fr[0]) for fr in frames}) != len(frames):
+            raise ValueError("LM_Solver(global_rigid=True): the frames of a batch must not share an sf object (each is "
+                             "moved by its own T_g)")
+        if self._rigid is None:
+            self._rigid = RigidAlign(self.opt, max_frames=self.max_frames)
+        self.last_rigid = self._rigid.align_batch(frames, u=u, v=v, minimal_loss=minimal_loss)
+        self.last_rigid_records = self._rigid.last_records
+        for fr, tg in zip(frames, self.last_rigid):
+            rigid_update(fr[0], tg)
+        return self.last_rigid_records
+
+    def _report(self, sf, inputs, recs, rigid_recs=None):
         for r in recs:
             if r["status"] == _lib.SLM_ITER_SOLVER_FAILED:
                 print("\t\tSolver failed: Ill-posed system!")        # super/LM.py:102
@@ -675,4 +709,6 @@ class LM_Solver():
         logger = getattr(sf, "logger", None)                         # defect D1: may be absent
         if self.opt.phase == "test" and logger is not None and done:
             fid = inputs["ID"].item() if "ID" in inputs else -1
-            logger.info(f"{fid} loss: {done[-1]['loss']}")
+            rdone = [r for r in (rigid_recs or []) if r["status"] == _lib.SLM_ITER_OK and r["accepted"]]
+            stage = f" (rigid stage: {rdone[-1]['loss']})" if rdone else ""
+            logger.info(f"{fid} loss: {done[-1]['loss']}{stage}")

@@ -45,6 +45,8 @@ EXPORTS = [
     "slm_enable_data_weights", "slm_bind_data_semantic", "slm_data_weights",
     "slm_enable_face", "slm_set_face_mesh", "slm_face_loss",
     "slm_enable_morph", "slm_bind_morph", "slm_morph_loss", "slm_morph_targets",
+    "slm_rigid_abi_check", "slm_rigid_create", "slm_rigid_destroy", "slm_rigid_run", "slm_rigid_get", "slm_rigid_get_beta",
+    "slm_rigid_get_records", "slm_rigid_assemble", "slm_rigid_transform",
 ]
 
 
@@ -157,6 +159,11 @@ class SlmRenderParams(C.Structure):
                 ("bg", C.c_float * 3), ("pad", C.c_int32)]
 
 
+class SlmRigidConfig(C.Structure):
+    _fields_ = [("num_iterations", C.c_int32), ("phase_test", C.c_int32), ("w_data", C.c_double), ("w_rot", C.c_double),
+                ("u0", C.c_double), ("v", C.c_double), ("minimal_loss0", C.c_double)]
+
+
 class SlmIterRecord(C.Structure):
     _fields_ = [("loss", C.c_double), ("u", C.c_double), ("accepted", C.c_int32),
                 ("status", C.c_int32), ("M_grad", C.c_int32), ("M_loss", C.c_int32)]
@@ -257,6 +264,15 @@ def load():
         "slm_bind_morph": [vp, i32, i32, vp, vp, vp, C.POINTER(C.c_int32), vp],
         "slm_morph_loss": [vp, i32, vp, vp],
         "slm_morph_targets": [vp, i32, vp, vp, vp, vp],
+        "slm_rigid_abi_check": [i32],
+        "slm_rigid_create": [i32, C.POINTER(vp)],
+        "slm_rigid_destroy": [vp],
+        "slm_rigid_run": [vp, C.POINTER(SlmRigidConfig), i32, C.POINTER(SlmFrame), vp],
+        "slm_rigid_get": [vp, i32, vp, vp],
+        "slm_rigid_get_beta": [vp, i32, vp, vp],
+        "slm_rigid_get_records": [vp, i32, C.POINTER(SlmIterRecord), i32, C.POINTER(C.c_int32), vp],
+        "slm_rigid_assemble": [vp, C.POINTER(SlmRigidConfig), C.POINTER(SlmFrame), vp, vp, vp, vp, vp],
+        "slm_rigid_transform": [i32, vp, vp, i32, vp, vp],
         "slm_graph_init": [i32, i32, i32, vp, vp, vp, vp, C.POINTER(SlmGraphOutputs), C.POINTER(C.c_int32), vp],
         "slm_graph_init_semantic": [i32, i32, i32, vp, vp, vp, vp, i32, vp, i32, C.POINTER(SlmGraphOutputs), vp, vp,
                                     C.POINTER(C.c_int32), vp],
@@ -301,6 +317,8 @@ def load():
     # ABI handshake: the struct mirrors above must be the library's own layouts
     rc = lib.slm_abi_check(SLM_ABI_VERSION, C.sizeof(SlmConfig), C.sizeof(SlmFrame), C.sizeof(SlmGfConfig),
                            C.sizeof(SlmGfFrame), C.sizeof(SlmIterRecord))
+    if rc == SLM_OK:
+        rc = lib.slm_rigid_abi_check(C.sizeof(SlmRigidConfig))   # the rigid stage's struct: an addition to the same ABI
     if rc != SLM_OK:
         raise SuperLMError(lib.slm_last_error().decode(errors="replace"))
     _lib = lib
