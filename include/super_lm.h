@@ -605,7 +605,8 @@ int slm_gf_create(const slm_gf_config* cfg, slm_gf** out);
 int slm_gf_destroy(slm_gf* g);
 /* Binds device pointers to `slot` and resets deform_verts to identity, optimiser state to 0.  The KNN tables are
  * checked as slm_bind_frame checks them (distinct sf_knn_idx ids per row, every id in [0, J), J >= K): SLM_ERR_INVALID
- * and an unbound slot otherwise.  Stream-synchronising. */
+ * and an unbound slot otherwise.  A frame with N = 0 (node terms only) may leave sf_points, sf_knn_idx and sf_knn_w
+ * NULL.  Stream-synchronising. */
 int slm_gf_bind_frame(slm_gf* g, int32_t slot, const slm_gf_frame* frame, void* stream);
 /* After slm_gf_bind_frame: binds the semantic inputs of the slot and extracts, per class, the
  * class-boundary pixels of img_seg in row-major order (find_edge_region with kernel 3 +
@@ -638,7 +639,18 @@ int slm_gf_run(slm_gf* g, int32_t n_frames, void* stream);
  *     slm_gf_step
  * on every rank; the partial state is [(J+1)*7 gradient | SLM_GF_NTERMS terms] doubles, moved with
  * slm_gf_get_partial / slm_gf_set_partial (device to device) so that the collective runs on the
- * caller's own buffer (torch.distributed all_reduce = RCCL over xGMI). */
+ * caller's own buffer (torch.distributed all_reduce = RCCL over xGMI).
+ * What the terms hold: behind slm_gf_eval_morph a rank's own morphing sum [5], kept count [6] and candidates flag [7],
+ * the rest 0; behind the first all-reduce [5..7] are the frame's (the flag: the number of ranks with a candidate).
+ * slm_gf_eval_losses back-propagates with that count, adds the rank's own [0..4], [8], [9] and, on every rank but 0,
+ * clears [5..7] again: both exchanges sum the WHOLE state, and rank 0's copy alone carries the frame's morphing entries
+ * through the second.  Behind the second all-reduce every entry is the frame's; slm_gf_step turns [5] into the weighted
+ * mean and [7] into 0 / 1, so a slm_gf_get_partial behind the step reads the terms slm_gf_loss_grad documents, the same
+ * on every rank.  slm_gf_set_shard unbinds every slot (the shard bounds are fixed at the bind): bind the frames again.
+ * slm_gf_run refuses a sharded context with world > 1, and so does slm_gf_loss_grad with the morphing term when terms
+ * or grad is asked for (one rank cannot take the mean; null terms and grad, which only set deform_verts, stay allowed):
+ *   SLM_ERR_UNSUPPORTED  "slm_gf_loss_grad: surfels are sharded and the boundary-morph term is on; its mean needs the global kept count: drive slm_gf_eval_morph / eval_losses with an all-reduce of slm_gf_get_partial behind each (null terms and grad only set deform_verts)"
+ * Without the term slm_gf_loss_grad returns the rank's partial sums (the global row divided by J). */
 int slm_gf_set_shard(slm_gf* g, int32_t rank, int32_t world);
 int slm_gf_eval_morph(slm_gf* g, int32_t n_frames, void* stream);
 int slm_gf_eval_losses(slm_gf* g, int32_t n_frames, void* stream);

@@ -19,7 +19,10 @@ enum GfPart {
 #define GF_PART_DOUBLES (GF_NPART * GF_NCOPY)
 // which of the partials a launch folds: k_gf_fold's `which`
 enum GfFoldWhich { GF_FOLD_DATA = 1,     // the entries of k_gf_data / k_gf_reg (0..13)
-                   GF_FOLD_MORPH = 2 };  // those of k_gf_morph (14, 15)
+                   GF_FOLD_MORPH = 2,    // those of k_gf_morph (14, 15)
+                   GF_FOLD_DROP_MORPH = 4 };   // terms[5..7] = 0: a sharded rank other than 0 behind its back-propagation -- the
+                                               // entries hold the GLOBAL sum, count and flag since the first exchange, and the
+                                               // second exchange sums the whole block again (rank 0 alone keeps them)
 // k_gf_step's `fold` (see there)
 enum GfStepFold { GF_STEP_FOLD = 1,      // it sums the partials of k_gf_data / k_gf_reg itself (no k_gf_fold launch)
                   GF_STEP_OWN = 2,       // it owns them: clears what it summed and ASSIGNS the loss terms

@@ -42,7 +42,10 @@ __global__ void __launch_bounds__(64) k_gf_fold(GfSlot* __restrict__ slots, int 
   GfSlotDev& s = gf_dev(slots)[blockIdx.y];
   if (!s.bound) return;
   const int a = threadIdx.x;
-  if (a >= GF_NPART) return;
+  if (a >= GF_NPART) {   // (threads behind the partials' entries: no fold writes terms[5..7] in a launch with DROP_MORPH)
+    if ((which & GF_FOLD_DROP_MORPH) && a < GF_NPART + 3) s.terms[5 + a - GF_NPART] = 0.0;
+    return;
+  }
   if (!(which & (a < GFP_MORPH_SUM ? GF_FOLD_DATA : GF_FOLD_MORPH))) return;
   const double t = gf_part_fold(s, a, true);
   if (t == 0.0) return;
@@ -522,6 +525,7 @@ __global__ void __launch_bounds__(256) k_gf_step(GfSlot* __restrict__ slots, int
     }
     s.terms[5] = s.terms[7] != 0.0 ? (kept > 0.0 ? w_morph * li / kept : nan("")) : 0.0;
     if ((fold & (GF_STEP_REZERO | GF_STEP_MORPH)) == (GF_STEP_REZERO | GF_STEP_MORPH)) s.terms[7] = 0.0;
+    else if (s.terms[7] != 0.0) s.terms[7] = 1.0;   // (sharded: the exchanges summed the ranks' flags)
   }
   if (e >= n) return;
   double g = s.grad[e];
@@ -737,7 +741,11 @@ static void gf_enqueue_eval(slm_gf* g, int first, int n, const GfDims& d, hipStr
   } else if (reg) {
     hipLaunchKernelGGL(k_gf_reg, dim3(nr, n), dim3(256), 0, st, slots, A.ra);
   }
-  if (!in_run) hipLaunchKernelGGL(k_gf_fold, dim3(1, n), dim3(64), 0, st, slots, (int)GF_FOLD_DATA);
+  // sharded, the morphing term on: terms[5..7] are global since the exchange behind pass 1 and k_gf_data has read the kept
+  // count by now; every rank but 0 clears them, so that the exchange behind this pass -- a sum of the whole block -- leaves
+  // the true sum, count and flag on every rank and not `world` times them
+  const int drop = (g->rank != 0 && c.use_bn_morph) ? (int)GF_FOLD_DROP_MORPH : 0;
+  if (!in_run) hipLaunchKernelGGL(k_gf_fold, dim3(1, n), dim3(64), 0, st, slots, (int)GF_FOLD_DATA | drop);
 }
 
 extern "C" {
@@ -790,7 +798,8 @@ int slm_gf_bind_frame(slm_gf* g, int32_t slot, const slm_gf_frame* fr, void* str
   if (f.K < 1 || f.K > 8) return fail(SLM_ERR_UNSUPPORTED, "slm_gf_bind_frame: num_neighbors must be in 1..8");
   if (f.K_ED < 1 || f.K_ED > SLM_MAX_KED || f.N < 0 || f.J < 1 || f.H < 4 || f.W < 4)
     return fail(SLM_ERR_INVALID, "slm_gf_bind_frame: bad sizes");
-  if (!f.sf_points || !f.sf_knn_idx || !f.sf_knn_w || !f.ed_points || !f.ed_knn_idx || !f.tgt_points ||
+  // (a frame without surfels has node terms only: its surfel arrays are empty and may be null, as in slm_gf_bind_semantic)
+  if ((f.N > 0 && (!f.sf_points || !f.sf_knn_idx || !f.sf_knn_w)) || !f.ed_points || !f.ed_knn_idx || !f.tgt_points ||
       !f.tgt_norms || !f.index_map || (g->cfg.use_arap && !fr->ed_knn_w) ||
       (g->cfg.use_face && (!fr->ed_triangles || !fr->ed_triangle_areas)))
     return fail(SLM_ERR_INVALID, "slm_gf_bind_frame: null device pointer");
@@ -1080,6 +1089,11 @@ int slm_gf_loss_grad(slm_gf* g, int32_t slot, const double* dv, double* terms, d
   GfDims d;
   if (const int rc = gf_dims(g, slot, 1, &d)) return rc;
   if (!dv) return fail(SLM_ERR_INVALID, "slm_gf_loss_grad: null dv");
+  if (g->world > 1 && g->cfg.use_bn_morph && (terms || grad))
+    return fail(SLM_ERR_UNSUPPORTED,
+                   "slm_gf_loss_grad: surfels are sharded and the boundary-morph term is on; its mean needs the global kept "
+                   "count: drive slm_gf_eval_morph / eval_losses with an all-reduce of slm_gf_get_partial behind each (null "
+                   "terms and grad only set deform_verts)");
   hipStream_t st = (hipStream_t)stream;
   const GfSlot& s = g->host[slot];
   HIPCHK(hipMemcpyAsync(s.dv, dv, sizeof(double) * d.maxP, hipMemcpyDeviceToDevice, st));

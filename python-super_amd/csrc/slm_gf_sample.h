@@ -55,10 +55,15 @@ __device__ __forceinline__ bool gf_sample(const FrameIn& f, double u_, double v_
 __device__ __forceinline__ void gf_flow_sample(const float* __restrict__ flow, int H, int W, double u, double v,
                                                double fl[2], double D[4]) {
   const float gx = (float)(u * 2.0 / (double)W - 1.0), gy = (float)(v * 2.0 / (double)H - 1.0);
-  const float ix = __fsub_rn(__fmul_rn(__fadd_rn(gx, 1.f), 0.5f * (float)W), 0.5f);
-  const float iy = __fsub_rn(__fmul_rn(__fadd_rn(gy, 1.f), 0.5f * (float)H), 0.5f);
+  // The float32 arithmetic is spelt out with fmaf where torch's CPU kernel fuses -- the position (g + 1) * size / 2 - 1 / 2 and
+  // every tap behind the first of the blend -- and nowhere else.  (It used to be written with __fmul_rn / __fadd_rn /
+  // __fsub_rn, which are plain operators here: under -ffp-contract=fast the compiler fused the position, and the blend of
+  // one channel but not of the other, so the sample agreed with neither an unfused nor a fused reading of the reference.
+  // Restated in NumPy, the form below gives F.grid_sample's bits on every sample of the 60 x 80 test frames.)
+  const float ix = fmaf(gx + 1.f, 0.5f * (float)W, -0.5f);
+  const float iy = fmaf(gy + 1.f, 0.5f * (float)H, -0.5f);
   const float xw = floorf(ix), yn = floorf(iy);
-  const float w = __fsub_rn(ix, xw), e = __fsub_rn(1.f, w), n = __fsub_rn(iy, yn), sth = __fsub_rn(1.f, n);
+  const float w = ix - xw, e = 1.f - w, n = iy - yn, sth = 1.f - n;
   const int x0 = (int)xw, y0 = (int)yn;
   const bool okx0 = x0 >= 0 && x0 < W, okx1 = x0 + 1 >= 0 && x0 + 1 < W;
   const bool oky0 = y0 >= 0 && y0 < H, oky1 = y0 + 1 >= 0 && y0 + 1 < H;
@@ -69,10 +74,10 @@ __device__ __forceinline__ void gf_flow_sample(const float* __restrict__ flow, i
     const float ne = (okx1 && oky0) ? fc[(size_t)y0 * W + x0 + 1] : 0.f;
     const float sw = (okx0 && oky1) ? fc[(size_t)(y0 + 1) * W + x0] : 0.f;
     const float se = (okx1 && oky1) ? fc[(size_t)(y0 + 1) * W + x0 + 1] : 0.f;
-    float acc = __fmul_rn(nw, __fmul_rn(e, sth));
-    acc = __fadd_rn(acc, __fmul_rn(ne, __fmul_rn(w, sth)));
-    acc = __fadd_rn(acc, __fmul_rn(sw, __fmul_rn(e, n)));
-    acc = __fadd_rn(acc, __fmul_rn(se, __fmul_rn(w, n)));
+    float acc = nw * (e * sth);
+    acc = fmaf(ne, w * sth, acc);
+    acc = fmaf(sw, e * n, acc);
+    acc = fmaf(se, w * n, acc);
     fl[c] = (double)acc;
     D[2 * c + 0] = ((double)ne - (double)nw) * (double)sth + ((double)se - (double)sw) * (double)n;
     D[2 * c + 1] = ((double)sw - (double)nw) * (double)e + ((double)se - (double)ne) * (double)w;

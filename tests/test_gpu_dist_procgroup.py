@@ -25,6 +25,19 @@ def _worker(rank, world, port, mode, name, tmp):
     torch.cuda.set_device(0)
     dist.init_process_group("gloo", rank=rank, world_size=world)
     try:
+        if mode == "gfsem":
+            # the semantic workload through GraphFit._iterate with its exchange buffer: both exchanges of every iteration
+            # (softadam -- soft-seg point-plane, face, boundary morph; Adam -- on the short-list scene of gf_shape_cases.py)
+            import gf_shape_cases as cases
+            import gf_shard_cases as shard
+            from super_amd.deform_mesh import GraphFit
+            case = shard.PROCGROUP.case
+            assert world == shard.PROCGROUP.world
+            gf = GraphFit(cases.opt_of(case.tag), shard_surfels=True)
+            assert (gf.rank, gf.world) == (rank, world) and gf.cfg.use_bn_morph and gf.cfg.seg_mode == 2
+            dv = gf(*cases.case_frame(case)).cpu().numpy()
+            np.savez(os.path.join(tmp, f"rank{rank}.npz"), dv=dv)
+            return
         from helpers import load_golden, ref_opt, torch_frame
         g, sc, opt = load_golden(name)
         sf, inputs, new_data = torch_frame(sc)
@@ -103,3 +116,17 @@ def test_surfel_sharded_graphfit_under_a_process_group(tmp_path):
     r0, r1 = _spawn("gf", "s60x80_j48", tmp_path)
     np.testing.assert_array_equal(r0["dv"], r1["dv"])
     np.testing.assert_allclose(r0["dv"], g["gf_sgd_final"], rtol=0, atol=1e-9)
+
+
+def test_surfel_sharded_semantic_graphfit_under_a_process_group(tmp_path):
+    """GraphFit._iterate with ``part`` and super_amd.dist.default_collectives, which the emulated ranks of
+    test_gpu_graphfit_sharded.py never enter: the exchange behind pass 1 (the morphing term's global kept count) and the
+    one behind pass 2, ten Adam steps."""
+    import gf_shape_cases as cases
+    import gf_shard_cases as shard
+    case = shard.PROCGROUP.case
+    r0, r1 = _spawn("gfsem", "", tmp_path)
+    want, atol = cases.oracle_final(case), cases.dv_atol(case)
+    print(case.id, "two gloo ranks: err", np.abs(r0["dv"] - want).max(), "atol", atol, "step", cases.step_of(want))
+    np.testing.assert_array_equal(r0["dv"], r1["dv"])
+    np.testing.assert_allclose(r0["dv"], want, rtol=0, atol=atol)

@@ -67,3 +67,37 @@ def test_refusal_texts_with_a_solver():
              b"slm_gf: semantic terms enabled but slm_gf_bind_semantic was not called")
     _refused(lib, "slm_gf_eval_losses", (gs.h, 1, None), UNBOUND,
              b"slm_gf: semantic terms enabled but slm_gf_bind_semantic was not called")
+
+
+def test_loss_grad_refuses_the_morph_term_on_a_sharded_handle():
+    """One rank cannot evaluate the term's mean: the kept count it divides by is global only behind the first exchange."""
+    import torch
+    import gf_shape_cases as cases
+    from super_amd.LM import _dev_ptr
+    from super_amd._lib import GF_NTERMS, SuperLMError
+    from super_amd.deform_mesh import GraphFit
+    case = cases.Case("morph", 257, 12, 4, 84, semantic=True)
+    frame = cases.case_frame(case)
+    text = (b"slm_gf_loss_grad: surfels are sharded and the boundary-morph term is on; its mean needs the global kept "
+            b"count: drive slm_gf_eval_morph / eval_losses with an all-reduce of slm_gf_get_partial behind each (null "
+            b"terms and grad only set deform_verts)")
+    dv = torch.from_numpy(cases.perturbed_dv(case)).cuda()
+    terms = torch.zeros(GF_NTERMS, dtype=torch.float64, device="cuda")
+    grad = torch.zeros_like(dv)
+    gf = GraphFit(cases.opt_of("morph"), rank=1, world=2, all_reduce=lambda t: None)
+    gf.bind(*frame)
+    lib, h = gf.lib, gf.h
+    _refused(lib, "slm_gf_loss_grad", (h, 0, _dev_ptr(dv), _dev_ptr(terms), _dev_ptr(grad), None), UNSUPPORTED, text)
+    _refused(lib, "slm_gf_loss_grad", (h, 0, _dev_ptr(dv), _dev_ptr(terms), None, None), UNSUPPORTED, text)
+    _refused(lib, "slm_gf_loss_grad", (h, 0, _dev_ptr(dv), None, _dev_ptr(grad), None), UNSUPPORTED, text)
+    with pytest.raises(SuperLMError, match="surfels are sharded and the boundary-morph term is on"):
+        gf.loss_and_grad(*frame, dv)
+    # the form that only sets deform_verts stays
+    assert lib.slm_gf_loss_grad(h, 0, _dev_ptr(dv), None, None, None) == 0
+    torch.testing.assert_close(gf.deform_verts(), dv, rtol=0, atol=0)
+    # allowed: a world of one rank (the same protocol, the whole sums), and more ranks without the term
+    one = GraphFit(cases.opt_of("morph"), rank=0, world=1, all_reduce=lambda t: None)
+    t, matched, _ = one.loss_and_grad(*frame, dv)
+    assert matched > 0 and "sf_bn_morph_loss" in t
+    hard = GraphFit(cases.opt_of("hard"), rank=1, world=2, all_reduce=lambda t: None)
+    assert hard.loss_and_grad(*frame, dv)[1] > 0
