@@ -234,7 +234,18 @@ int slm_get_plan_info(slm_solver* s, int32_t slot, double* info_out, int32_t cap
  *       -> all-reduce(sum) of SLM_X_DATA_LOSS     (1024 doubles)
  *     slm_lm_accept       accept / reject, record
  * with slm_lm_exchange_get / _set moving the buffers device to device to and from the caller's
- * tensor (torch.distributed = RCCL over xGMI on the GPU box). */
+ * tensor (torch.distributed = RCCL over xGMI on the GPU box).
+ * The shares are fixed at the bind: with N surfels, lo = N*rank/world and hi = N*(rank+1)/world in integers,
+ *   pair-record form (slm_enable_data_weights, or num_neighbors != 4): the Jacobian pass takes positions [lo, hi) of the
+ *     neighbour-set-ordered surfel list, the loss pass surfels [lo, hi) of the caller's order -- two different partitions of
+ *     the same frame, each summed over the ranks by its own exchange;
+ *   tuple-sorted form (num_neighbors == 4, unweighted): both passes take the rank's 256-position workgroups of the
+ *     tuple-sorted list.
+ * A rank whose share holds no surfel, no matched surfel or only weights 0 adds exactly nothing and ends on the same beta.
+ * A frame without surfels (N == 0) has no multifrontal data plan and is refused at the bind (SLM_ERR_UNSUPPORTED).
+ * slm_set_shard on a handle with bound slots unbinds them (SLM_ERR_UNBOUND, "slot used before slm_bind_frame", until
+ * they are bound again).  slm_run refuses a handle with world > 1.  The parity entry points on a sharded handle: see
+ * slm_assemble / slm_loss below. */
 #define SLM_X_PAIR_BLOCKS 0
 #define SLM_X_DELTA 1
 #define SLM_X_DATA_LOSS 2
@@ -476,7 +487,13 @@ int slm_profile_read(slm_solver* s, double* ms_out, int64_t* count_out);
 int slm_assemble(slm_solver* s, int32_t slot, double* jtj_dense_device, double* jtl_device,
                  void* stream);
 /* Sum of squared residuals per term at the slot's current beta:
- * out_device[0..2] = data, arap, rot; out_device[3] = matched count (as double). */
+ * out_device[0..2] = data, arap, rot; out_device[3] = matched count (as double).
+ * On a sharded handle (slm_set_shard, world > 1) slm_assemble and slm_loss return THIS RANK'S PARTIAL: its share of the
+ * data term plus every regulariser in full.  slm_loss: data loss and matched count of the surfels [N*rank/world,
+ * N*(rank+1)/world) of the caller's order, in either data form.  slm_assemble: the data blocks of the same window in the
+ * pair-record form, of the rank's workgroups of tuple positions in the tuple-sorted form.  Over the ranks the data parts
+ * sum to the frame's; the regularisers are counted world times (sum_r A_r - (world - 1) A_reg is the frame's system).
+ * slm_solve on such a handle solves that partial system: it is no step of the frame. */
 int slm_loss(slm_solver* s, int32_t slot, double* out_device, void* stream);
 /* Assemble at the current beta, add u to the diagonal, Cholesky-solve; writes delta (P).
  * status_device (int32) receives SLM_ITER_OK or SLM_ITER_SOLVER_FAILED. */

@@ -35,10 +35,13 @@ __global__ void __launch_bounds__(256) k_data_grad(const FrameDev* __restrict__ 
   SurfelEvalT<KK> ev;
   ev.match = false;
   [[maybe_unused]] double wt = 1.0;
+  // [sf_lo, sf_hi) = all surfels unless the frame is sharded over several GPUs (slm_assemble on a sharded handle: the
+  // rank's share in the caller's order, as k_data_loss has it)
+  const bool mine = i >= fd.sf_lo && i < fd.sf_hi;
   if constexpr (WT) {
-    if (i < fd.f.N) eval_surfel_weighted<1, KK>(fd, lam, fd.node_pk, i, ev, wt, wa...);
+    if (mine) eval_surfel_weighted<1, KK>(fd, lam, fd.node_pk, i, ev, wt, wa...);
   } else {
-    if (i < fd.f.N) eval_surfel<1, KK>(fd, lam, fd.node_pk, i, ev);
+    if (mine) eval_surfel<1, KK>(fd, lam, fd.node_pk, i, ev);
   }
 
   // matched-surfel count: one atomic per wave

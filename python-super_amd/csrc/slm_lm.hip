@@ -358,6 +358,9 @@ int slm_lm_accept(slm_solver* s, int32_t n_frames, void* stream) {
   BatchDims d;
   int rc = shard_dims(s, n_frames, d);
   if (rc) return rc;
+  // k_accept sums d.n_reg_part partial pairs behind the data partials here, where slm_run sums d.parts.n_acc_part.  The two
+  // are equal only while no opt-in term puts partials behind the regularisers': the correspondence, face and morph terms
+  // all refuse a sharded solver (slm_set_shard, slm_enable_*).  A term that learns to shard must change this argument.
   launch_accept(s->frames_dev, n_frames, s->cfg.phase_test, d.n_reg_part, std::max(s->cfg.num_iterations, 1), (hipStream_t)stream,
                 d.accept_reuse, d.accept_eval);   // (slm_lm_loss_local ran k_data_eval)
   HIPCHK(hipGetLastError());

@@ -661,21 +661,34 @@ class LM_Solver():
 
     def _run_sharded(self, h, n, dev):
         """The LM loop with the three exchanges per iteration (see include/super_lm.h)."""
+        for _ in self._sharded_stages(h, n, dev):
+            pass
+
+    def _sharded_stages(self, h, n, dev):
+        """The stages of ``_run_sharded``, one per ``next()``: a stage is this rank's launches up to and including the
+        collective that follows them (a driver that holds several ranks in one process steps them alternately; the
+        collectives it injects then see every rank's buffer before the next stage reads it).  The pair records and the data
+        loss are exchanged whenever the solver carries the data term -- ``opt.sf_point_plane`` or a semantic weight, which
+        puts the term on without it (``_config``: use_data)."""
         st = _stream_ptr(dev)
         lib = self.lib
-        pair = [self.exchange_view(h, i, _lib.SLM_X_PAIR_BLOCKS, dev) for i in range(n)] if self.opt.sf_point_plane else []
+        data = bool(self.opt.sf_point_plane) or bool(self.seg_mode)
+        pair = [self.exchange_view(h, i, _lib.SLM_X_PAIR_BLOCKS, dev) for i in range(n)] if data else []
         delta = [self.exchange_view(h, i, _lib.SLM_X_DELTA, dev) for i in range(n)]
-        loss = [self.exchange_view(h, i, _lib.SLM_X_DATA_LOSS, dev) for i in range(n)] if self.opt.sf_point_plane else []
+        loss = [self.exchange_view(h, i, _lib.SLM_X_DATA_LOSS, dev) for i in range(n)] if data else []
         for _ in range(int(self.opt.num_optimize_iterations)):
             _lib.check(lib.slm_lm_grad_local(h, n, st), "slm_lm_grad_local")
-            if self.opt.sf_point_plane:
+            if data:
                 self._exchange(h, n, _lib.SLM_X_PAIR_BLOCKS, self._all_reduce, pair)
+            yield "grad"
             _lib.check(lib.slm_lm_solve(h, n, st), "slm_lm_solve")
             self._exchange(h, n, _lib.SLM_X_DELTA, self._broadcast, delta)
+            yield "solve"
             _lib.check(lib.slm_lm_loss_local(h, n, st), "slm_lm_loss_local")
-            if self.opt.sf_point_plane:
+            if data:
                 self._exchange(h, n, _lib.SLM_X_DATA_LOSS, self._all_reduce, loss)
-            _lib.check(lib.slm_lm_accept(h, n, st), "slm_lm_accept")
+            yield "loss"
+            _lib.check(lib.slm_lm_accept(h, n, st), "slm_lm_accept")      # (reads the summed loss: behind the yield)
 
     # ---- helpers -----------------------------------------------------------------------
     def records(self, h, slot, stream):

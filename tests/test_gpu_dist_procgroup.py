@@ -38,6 +38,19 @@ def _worker(rank, world, port, mode, name, tmp):
             dv = gf(*cases.case_frame(case)).cpu().numpy()
             np.savez(os.path.join(tmp, f"rank{rank}.npz"), dv=dv)
             return
+        if mode == "lmw":
+            # the weighted data term (soft weights, num_neighbors 6: the pair form) through LM_Solver._run_sharded with the
+            # mirror's own collectives in place on the library's buffers
+            import test_gpu_lm_weights as tw
+            from super_amd.LM import LM_Solver
+            lm = LM_Solver(tw._opt(6, sf_soft_seg_point_plane=True), shard_surfels=True, weighted_data=True)
+            assert (lm.rank, lm.world, lm.seg_mode) == (rank, world, 2)
+            beta = lm.LM(*tw._sem_frame("k6")).cpu().numpy()
+            recs = lm.last_records[0]
+            np.savez(os.path.join(tmp, f"rank{rank}.npz"), beta=beta, loss=np.array([r["loss"] for r in recs]),
+                     accepted=np.array([r["accepted"] for r in recs]), status=np.array([r["status"] for r in recs]),
+                     M_grad=np.array([r["M_grad"] for r in recs]), M_loss=np.array([r["M_loss"] for r in recs]))
+            return
         from helpers import load_golden, ref_opt, torch_frame
         g, sc, opt = load_golden(name)
         sf, inputs, new_data = torch_frame(sc)
@@ -130,3 +143,28 @@ def test_surfel_sharded_semantic_graphfit_under_a_process_group(tmp_path):
     print(case.id, "two gloo ranks: err", np.abs(r0["dv"] - want).max(), "atol", atol, "step", cases.step_of(want))
     np.testing.assert_array_equal(r0["dv"], r1["dv"])
     np.testing.assert_allclose(r0["dv"], want, rtol=0, atol=atol)
+
+
+def test_surfel_sharded_weighted_lm_under_a_process_group(tmp_path):
+    """``LM_Solver(opt, shard_surfels=True, weighted_data=True)``: soft weights at num_neighbors 6 on the 1200-surfel scene of
+    test_gpu_lm_weights.py -- both ranks bitwise equal, the unsharded run's beta to 1e-9 (summation order), its counts and
+    accept flags, the model's trace."""
+    import lm_weight_model as lwm
+    import test_gpu_lm_weights as tw
+    from super_amd.LM import LM_Solver
+    r0, r1 = _spawn("lmw", "", tmp_path)
+    assert (r0["status"] == 0).all() and (r1["status"] == 0).all()
+    for k in ("beta", "loss", "accepted", "M_grad", "M_loss"):
+        np.testing.assert_array_equal(r0[k], r1[k], err_msg=k)
+    lm = LM_Solver(tw._opt(6, sf_soft_seg_point_plane=True), weighted_data=True)
+    want_beta = lm.LM(*tw._sem_frame("k6")).cpu().numpy()
+    want = lm.last_records[0]
+    print("two gloo ranks, soft K = 6: sharded - unsharded beta", np.abs(r0["beta"] - want_beta).max())
+    np.testing.assert_allclose(r0["beta"], want_beta, rtol=0, atol=1e-9)
+    np.testing.assert_allclose(r0["loss"], [x["loss"] for x in want], rtol=1e-9)
+    assert list(r0["accepted"]) == [x["accepted"] for x in want]
+    assert list(r0["M_grad"]) == [x["M_grad"] for x in want] and list(r0["M_loss"]) == [x["M_loss"] for x in want]
+    model_beta, trace = tw._model_trace("k6", tw._sem("k6"), 2, 0.0)
+    np.testing.assert_allclose(r0["loss"], [t["loss"] for t in trace], rtol=1e-6, atol=1e-12)
+    assert list(r0["M_grad"]) == [t["M_grad"] for t in trace]
+    np.testing.assert_allclose(r0["beta"], model_beta, rtol=0, atol=1e-4)

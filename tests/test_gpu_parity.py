@@ -282,51 +282,16 @@ def test_nd_multifrontal_solve_matches_band_and_numpy(name):
 def _run_emulated_ranks(name, world, extra_iterations=0):
     """One frame split over `world` ranks (one solver context each on this GPU; the all-reduce of
     the J^T J / J^T r pair blocks and of the loss partials and the broadcast of delta are emulated by
-    combining the ranks' exchange buffers).  Returns (golden, opt, betas per rank, records per rank)."""
-    import torch
-    from super_amd import _lib
-    from super_amd.LM import LM_Solver, _dev_ptr, _stream_ptr
+    combining the ranks' exchange buffers: lm_shard_cases.Ranks, the driver test_gpu_lm_sharded.py shares).
+    Returns (golden, opt, betas per rank, records per rank)."""
+    import lm_shard_cases as lc
     g, sc, opt = load_golden(name)
-    sf, inputs, new_data = torch_frame(sc)
     o = ref_opt(opt)
     o.num_optimize_iterations = int(o.num_optimize_iterations) + extra_iterations
-    ranks = [LM_Solver(o, rank=r, world=world, all_reduce=lambda t: None, broadcast=lambda t: None)
-             for r in range(world)]
-    hs = [lm._handle() for lm in ranks]
-    bfs = [lm._bind(h, 0, sf, inputs, new_data) for lm, h in zip(ranks, hs)]
-    dev = bfs[0].device
-    st = _stream_ptr(dev)
-    lib = ranks[0].lib
-
-    def exchange(what, combine):
-        bufs = [lm.exchange_buffer(h, 0, what, dev) for lm, h in zip(ranks, hs)]
-        for h, b in zip(hs, bufs):
-            _lib.check(lib.slm_lm_exchange_get(h, 0, what, _dev_ptr(b), st), "get")
-        out = combine(bufs)
-        for h in hs:
-            _lib.check(lib.slm_lm_exchange_set(h, 0, what, _dev_ptr(out), st), "set")
-
-    for _ in range(int(o.num_optimize_iterations)):
-        for h in hs:
-            _lib.check(lib.slm_lm_grad_local(h, 1, st), "grad_local")
-        if o.sf_point_plane:
-            exchange(_lib.SLM_X_PAIR_BLOCKS, lambda b: torch.stack(b).sum(0))
-        for h in hs:
-            _lib.check(lib.slm_lm_solve(h, 1, st), "solve")
-        exchange(_lib.SLM_X_DELTA, lambda b: b[0].clone())
-        for h in hs:
-            _lib.check(lib.slm_lm_loss_local(h, 1, st), "loss_local")
-        if o.sf_point_plane:
-            exchange(_lib.SLM_X_DATA_LOSS, lambda b: torch.stack(b).sum(0))
-        for h in hs:
-            _lib.check(lib.slm_lm_accept(h, 1, st), "accept")
-    betas = []
-    for lm, h, bf in zip(ranks, hs, bfs):
-        beta = torch.empty((bf.J, 7), dtype=torch.float64, device=dev)
-        _lib.check(lib.slm_get_beta(h, 0, _dev_ptr(beta), st), "get_beta")
-        betas.append(beta.cpu().numpy())
-    recs = [lm.records(h, 0, st) for lm, h in zip(ranks, hs)]
-    return g, o, betas, recs
+    R = lc.Ranks([sc], None, world, iters=int(o.num_optimize_iterations), exchange_data=bool(o.sf_point_plane), **lc._engine_kw(o))
+    out = R.run()
+    R.close()
+    return g, o, [res[0][0] for res in out], [res[0][1] for res in out]
 
 
 @pytest.mark.parametrize("name,world", [("s60x80_j48", 2), ("s120x160_j108", 3), ("s60x80_j48_reject", 4)])
