@@ -1107,7 +1107,15 @@ int slm_debug_read(slm_solver* s, int32_t slot, int32_t what, double* host_out, 
  * HOST memory as raw bytes (synchronises `stream`): what = 0 s_idx, 1 grp_run, 2 run_nodes, 3 s_w, 4 blk_key, 5 blk_start,
  * 6 blk_entry, 7 wg_first, 8 wg_last, 9 run_lidx, 10 blk2_start, 11 blk2_entry, 12 s_pts.  *n_bytes receives the array's
  * length; at most max_bytes are copied.  (tests/test_gpu_prepare_binned.py: the binned preparation against the rocPRIM
- * pipeline, array by array; tests/test_gpu_prep_plan.py: both against the NumPy construction of tests/prep_plan_model.py.) */
+ * pipeline, array by array; tests/test_gpu_prep_plan.py: both against the NumPy construction of tests/prep_plan_model.py.)
+ * A slot without that plan refuses 0..12 with SLM_ERR_UNSUPPORTED "slm_debug_read_plan: the slot has no tuple-sorted plan".
+ * what = 13..16 read the pair plan of a slot on the pair-record form (num_neighbors != 4, or an enabled slm_enable_corr /
+ * _data_weights / _face / _morph), all int32: 13 blk_key (coupled pairs: the ascending distinct keys max(a,b) * J + min(a,b),
+ * unsigned), 14 sf_pidx (N, K(K+1)/2: the position in blk_key of the pair (c[ra], c[rb]) at slot ra(ra+1)/2 + rb, c the
+ * surfel's ids ascending), 15 sf_perm (N: the surfels in lexicographic order of c, ties by surfel id), 16 tri_pidx (F, 6: the
+ * positions of a face-mesh triangle's pairs -- the diagonals of vertex 0, 1, 2, then (0,1), (0,2), (1,2); length 0 without a
+ * mesh).  A slot without a pair plan refuses them with SLM_ERR_UNSUPPORTED "slm_debug_read_plan: the slot has no pair plan".
+ * (tests/test_gpu_pair_plan.py: against the NumPy construction of tests/pair_plan_model.py.) */
 int slm_debug_read_plan(slm_solver* s, int32_t slot, int32_t what, void* host_out, int64_t max_bytes, int64_t* n_bytes,
                         void* stream);
 

@@ -107,9 +107,13 @@ int slm_debug_read_plan(slm_solver* s, int32_t slot, int32_t what, void* host_ou
   if (rc) return rc;
   const Slot& sl = s->slots[slot];
   const FrameDev& h = sl.h;
-  if (!h.v1_ready) return fail(SLM_ERR_UNSUPPORTED, "slm_debug_read_plan: the slot has no tuple-sorted plan");
+  const bool pair = what >= 13 && what <= 16;   // an array of the pair plan (prep_pairs), on a slot of the pair-record form
+  if (pair && !h.vk_ready) return fail(SLM_ERR_UNSUPPORTED, "slm_debug_read_plan: the slot has no pair plan");
+  if (!pair && !h.v1_ready) return fail(SLM_ERR_UNSUPPORTED, "slm_debug_read_plan: the slot has no tuple-sorted plan");
   const size_t esz = h.f.state_f64 ? 8 : 4;
   const size_t n_wg = (size_t)h.n_pos / 256 + ((h.n_pos % 256) ? 1 : 0);
+  const size_t n_slots = (size_t)h.f.K * (h.f.K + 1) / 2;   // canonical pair slots of a surfel
+  const bool mesh = sl.face.ready != 0;                     // the bind keyed a face mesh: tri_pidx is the slot's
   const void* src = nullptr;
   size_t n = 0;
   switch (what) {
@@ -126,6 +130,10 @@ int slm_debug_read_plan(slm_solver* s, int32_t slot, int32_t what, void* host_ou
     case 10: src = h.v2_ready ? h.blk2_start.get() : nullptr; n = h.v2_ready ? sizeof(int32_t) * ((size_t)h.n_blocks + 1) : 0; break;
     case 11: src = h.v2_ready ? h.blk2_entry.get() : nullptr; n = h.v2_ready ? sizeof(int32_t) * (size_t)h.n_wblk : 0; break;
     case 12: src = h.s_pts.get(); n = esz * 3 * (size_t)h.n_pos; break;
+    case 13: src = h.blk_key.get(); n = sizeof(int32_t) * (size_t)h.n_blocks; break;
+    case 14: src = h.sf_pidx.get(); n = sizeof(int32_t) * n_slots * (size_t)h.f.N; break;
+    case 15: src = h.sf_perm.get(); n = sizeof(int32_t) * (size_t)h.f.N; break;
+    case 16: src = mesh ? sl.face.tri_pidx.get() : nullptr; n = mesh ? sizeof(int32_t) * 6 * (size_t)sl.face.n_tri : 0; break;
     default: return fail(SLM_ERR_INVALID, "slm_debug_read_plan: unknown array");
   }
   *n_bytes = (int64_t)n;
