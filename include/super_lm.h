@@ -1129,7 +1129,7 @@ int slm_debug_read_plan(slm_solver* s, int32_t slot, int32_t what, void* host_ou
  *   Rot   w_rot (1 - |q|^2), in float32 like the node solve's; ALWAYS on here (without it |q| is a free scale)
  * and the rules of the node solve's data term (see slm_data_residuals: projection with Z + 1e-8, validity on the rounded
  * pixel, four taps, NaN drop, the integer-coordinate double tap; c = n(I - A) + e B with the plain Z in dPi; the row
- * w_data [c dR(q)p/dq | c]).  The data term is the plain one: no semantic weights, no truncation.  u, v, minimal_loss,
+ * w_data [c dR(q)p/dq | c]).  The data term is the plain one unless slm_rigid_set_terms asks for more (below).  u, v, minimal_loss,
  * accept / reject under phase_test and the fresh match set of the loss at the trial point are LM()'s.  The caller then
  * moves the model by T_g (slm_rigid_transform) and runs the unchanged node LM on the moved model.
  *
@@ -1200,6 +1200,57 @@ int slm_rigid_assemble(slm_rigid* r, const slm_rigid_config* cfg, const slm_fram
                        double* JtJ49_device, double* jtl7_device, double* loss_M_device /*[2]*/, void* stream);
 int slm_rigid_transform(int32_t n, void* points, void* norms /*may be null*/, int32_t f64, const double* Tg7_device,
                         void* stream);
+
+/* -- opt-in terms of the rigid stage (additions to ABI 3; a context that never calls them runs the plain stage) ----------
+ * The plain stage sees point-to-plane rows only: motion ALONG a near-planar surface is invisible to it, and a tool that
+ * crosses the view pulls T_g with it.  Two terms of the node solve can be carried by the stage:
+ *   correspondence rows  (slm_enable_corr's modes and weight): a surfel with valid_i adds, for one node at the origin with
+ *       weight 1, the rows corr_weight [c dR(q)p/dq | c] with residual corr_weight c.(R(q)p + t - o_i); c = e_x, e_y, e_z in
+ *       mode 1 (point-point), c = n_i in mode 2 (point-plane).  The targets do not move with beta_g.  A surfel adds these
+ *       rows whether or not the data term matches it, and the other way round.
+ *   data weights  (slm_enable_data_weights's seg_mode and pp_max): every matched data row and its residual are scaled by
+ *       sqrt(w_i), w_i evaluated at the point of the pass from s_i = (n.e)^2 without w_data -- seg_mode 1 hard / 2 soft
+ *       semantic weight (pp_max then ignored), seg_mode 0 with pp_max > 0 the truncation [s_i < pp_max].  Weight 0 is
+ *       matched and contributes nothing: M_grad / M_loss stay the match set's counts.
+ * The iteration's loss is weighted data + correspondence + Rot; one pass still yields the loss at the trial point and the
+ * normal equations there, both with w at that point.  The sums keep their fixed order (same partials, same reduction):
+ * two runs give the same bits.
+ *
+ * slm_rigid_set_terms: the context's terms for later slm_rigid_run / slm_rigid_assemble calls; (0, 0, 0, 0) is the plain
+ *   stage.  EVERY call clears every slot's inputs.
+ * slm_rigid_set_corr / slm_rigid_set_semantic: register DEVICE arrays that later runs of that slot read in place -- pts
+ *   (N,3), nrm (N,3; may be null in mode 1), valid (N); sf_seg (N), sf_seg_conf (N,C), tgt_seg_conf (T,C).  Slots
+ *   [0, max_frames) are slm_rigid_run's, slot max_frames is slm_rigid_assemble's own.  Null pts / null sf_seg clears the
+ *   slot's inputs.  A slot without correspondences runs without that term; with seg_mode != 0 a run or assemble over a slot
+ *   without semantic inputs is refused: there is no silent unweighted run.
+ * slm_rigid_corr_targets: the targets slm_bind_corr_flow builds, for a raw frame and without a context: the unrounded
+ *   projection of sf_points, the flow (2,H,W float32) sampled grid_sample-style, margin 1, all four taps mapped and finite;
+ *   zeros where invalid.  Reads N, H, W, the intrinsics, sf_points, state_f64 and the target tables.  pts, nrm (N,3), valid
+ *   (N) are device memory.
+ * slm_rigid_get_terms: out4_device = {sum w r^2 of the data rows, matched count, sum |r_c|^2 of the correspondence rows,
+ *   count of surfels that contributed them} of the sums kept at the slot's beta (slot max_frames: at the point of the last
+ *   slm_rigid_assemble).
+ *
+ * Refusals:
+ *   SLM_ERR_INVALID      "<fn>: null argument"
+ *                        "<fn>: bad slot"                 (slm_rigid_set_corr, _set_semantic, _get_terms: outside [0, max_frames])
+ *                        "slm_rigid_set_terms: corr_mode must be 0 (none), 1 (point-point) or 2 (point-plane)"
+ *                        "slm_rigid_set_terms: corr_weight must be finite"
+ *                        "slm_rigid_set_terms: seg_mode must be 0 (none), 1 (hard) or 2 (soft)"
+ *                        "slm_rigid_set_terms: pp_max must be finite and >= 0"
+ *                        "slm_rigid_set_corr: the correspondence term is off; call slm_rigid_set_terms with corr_mode 1 or 2 first"
+ *                        "slm_rigid_set_corr: corr_mode 2 (point-plane) needs nrm"
+ *                        "slm_rigid_set_semantic: the semantic weight is off; call slm_rigid_set_terms with seg_mode 1 or 2 first"
+ *                        "slm_rigid_corr_targets: T must be > 0"
+ *                        the frame texts of slm_rigid_run, with <fn> = slm_rigid_corr_targets
+ *   SLM_ERR_UNSUPPORTED  "slm_rigid_set_semantic: num_classes must be in 1..SLM_MAX_CLASSES (4)"
+ *   SLM_ERR_UNBOUND      "<fn>: slot <k> has no semantic inputs; call slm_rigid_set_semantic"   (slm_rigid_run, _assemble) */
+int slm_rigid_set_terms(slm_rigid* r, int32_t corr_mode, double corr_weight, int32_t seg_mode, double pp_max);
+int slm_rigid_set_corr(slm_rigid* r, int32_t slot, const double* pts, const double* nrm, const uint8_t* valid);
+int slm_rigid_set_semantic(slm_rigid* r, int32_t slot, int32_t num_classes, const int32_t* sf_seg,
+                           const float* sf_seg_conf, const float* tgt_seg_conf);
+int slm_rigid_corr_targets(const slm_frame* frame, const float* flow, double* pts, double* nrm, uint8_t* valid, void* stream);
+int slm_rigid_get_terms(slm_rigid* r, int32_t slot, double* out4_device, void* stream);
 
 #ifdef __cplusplus
 }

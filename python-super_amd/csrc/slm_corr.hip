@@ -44,25 +44,7 @@ __global__ void __launch_bounds__(256) k_corr_targets(const FrameDev* __restrict
   const FrameIn& f = frame_in(fd);
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= f.N) return;
-  const d3 p = ld_state3(f.sf_points, (size_t)i, fd.f.state_f64);
-  const GfProj pr = gf_project(f, p);
-  double fl[2], D[4];
-  gf_flow_sample(flow, f.H, f.W, pr.u, pr.v, fl, D);
-  const double uc = pr.u + fl[0], vc = pr.v + fl[1];
-  // margin 1 on the shifted float coordinates (false for NaN): every tap of gf_sample is inside the image
-  bool ok = vc >= 1.0 && vc < (double)(f.H - 2) && uc >= 1.0 && uc < (double)(f.W - 2);
-  GfSample q;
-  if (ok) ok = gf_sample(f, uc, vc, q);
-  if (ok) ok = q.o.x == q.o.x && q.o.y == q.o.y && q.o.z == q.o.z && q.n.x == q.n.x && q.n.y == q.n.y && q.n.z == q.n.z;
-  double* o = cd.o.get() + 3 * (size_t)i;
-  double* n = cd.n.get() + 3 * (size_t)i;
-  o[0] = ok ? q.o.x : 0.0;
-  o[1] = ok ? q.o.y : 0.0;
-  o[2] = ok ? q.o.z : 0.0;
-  n[0] = ok ? q.n.x : 0.0;
-  n[1] = ok ? q.n.y : 0.0;
-  n[2] = ok ? q.n.z : 0.0;
-  cd.valid[i] = ok ? 1 : 0;
+  corr_target_of(f, i, flow, cd.o.get(), cd.n.get(), cd.valid.get());
 }
 
 // The term's share of the pair records: skin, the NC rows of a surfel with a correspondence (mode 1: the three components;

@@ -15,10 +15,19 @@
 //               Cholesky, solves, writes the next trial point and the record.
 // So the loss of iteration i and the normal equations of iteration i + 1 come from ONE pass (same point, same match set),
 // an iteration is two launches, nothing synchronises with the host and the frame index is blockIdx.y / blockIdx.x.
+//
+// Opt-in terms (slm_rigid_set_terms): k_rg_pass<CM, WT> adds the flow-correspondence rows of slm_corr.hip for one node at the
+// origin (CM 1 point-point, 2 point-plane) and / or scales the data rows by the per-residual weight of slm_data.h (WT); the
+// partial keeps its layout (two of its three free places take the term's sum of squares and count), k_rg_step its sum.
+// <0, false> is the plain stage.  k_rg_corr_targets builds the targets of a raw frame from a flow (corr_target_of, slm_corr.h).
 #include <algorithm>
 #include <string>
 
+#include <vector>
+
 #include "slm_common.h"
+#include "slm_corr.h"
+#include "slm_data.h"
 #include "slm_host.h"
 #include "slm_lane.h"
 
@@ -27,6 +36,8 @@
 #define RG_NV 40          // doubles per partial in HBM (padded)
 #define RG_R2 35
 #define RG_M 36
+#define RG_RC 37          // the opt-in terms (slm_rigid_set_terms): sum |r_c|^2 of the correspondence rows ...
+#define RG_KC 38          // ... and the count of surfels that contributed them; 0 in the plain stage
 #define RG_MAX_GRID 512   // workgroups of k_rg_pass per frame: beyond 512 * 256 surfels a workgroup takes a second chunk
 #define RG_INIT_BATCH 8   // frames handed to one k_rg_init launch (as kernel arguments)
 
@@ -45,7 +56,19 @@ struct RigidSlot {
   GP<slm_iter_record> rec;   // (num_iterations)
 };
 
+// The inputs of a slot's opt-in terms, resident in HBM beside the slots (same index): the caller's arrays, read in place.
+struct RigidTerms {
+  GP<const double> o;        // (N,3) correspondence targets; null: the slot runs without the term
+  GP<const double> n;        // (N,3) their normals (mode 2)
+  GP<const uint8_t> valid;   // (N)
+  DataWeightDev wd;          // semantic inputs of the weighted data term (has = 0: none)
+};
+
 struct slm_rigid {
+  int corr_mode = 0, seg_mode = 0;     // slm_rigid_set_terms; all zero: the plain stage
+  double corr_weight = 0.0, pp_max = 0.0;
+  std::vector<RigidTerms> terms_h;     // host mirror, max_frames + 1
+  DevBuf<RigidTerms> terms;            // written by k_rg_init on the run's stream
   int max_frames = 0;
   int last_iters = 0;                  // num_iterations of the last slm_rigid_run
   DevBuf<RigidSlot> slots;             // max_frames + 1: the last one belongs to slm_rigid_assemble
@@ -58,11 +81,20 @@ namespace {
 
 struct RgInitArgs {
   slm_frame f[RG_INIT_BATCH];
+  RigidTerms t[RG_INIT_BATCH];
+};
+
+// what the pass variants with terms are launched with
+struct RgTermArgs {
+  const RigidTerms* terms;   // indexed like the slots of the launch
+  double corr_lam;
+  DataWArgs wa;              // wa.wd stays null: the descriptor is the slot's RigidTerms::wd
 };
 
 // grid = (frames of this launch), block = 64: slot first + blockIdx.x <- the frame, beta = trial = beta0 (identity when
 // null), fresh LM state and records
-__global__ void __launch_bounds__(64) k_rg_init(RigidSlot* __restrict__ slots, int first, RgInitArgs a, slm_rigid_config cfg,
+__global__ void __launch_bounds__(64) k_rg_init(RigidSlot* __restrict__ slots, RigidTerms* __restrict__ terms, int first, RgInitArgs a,
+                                                slm_rigid_config cfg,
                                                 double* part, size_t part_stride, slm_iter_record* rec, size_t rec_stride,
                                                 const double* __restrict__ beta0) {
   const int k = blockIdx.x;
@@ -86,6 +118,7 @@ __global__ void __launch_bounds__(64) k_rg_init(RigidSlot* __restrict__ slots, i
   if (threadIdx.x == 0) {
     const slm_frame& f = a.f[k];
     s.f = f;
+    terms[first + k] = a.t[k];
     s.u = cfg.u0;
     s.v = cfg.v;
     s.minimal_loss = cfg.minimal_loss0;
@@ -102,11 +135,11 @@ __global__ void __launch_bounds__(64) k_rg_init(RigidSlot* __restrict__ slots, i
 // The data term of one surfel at beta_g = (qw, qv, tr): eval_surfel_coreT<1, 1> of slm_data.h for a node at the origin with
 // weight 1 (T = R(q) p + t; adding g = 0 and scaling by w = 1 are exact), reading the target through index_map and the raw
 // (T,3) tables.  A row number outside [0, T) counts as unmapped (the reference would raise; nothing is read out of bounds).
-// Returns the match flag; r and row[7] = lam [c dR(q)p/dq | c] are set when matched.
-__device__ __forceinline__ bool rg_eval(const FrameIn& f, const d3 p, const double qw, const d3 qv, const d3 tr, const double lam,
-                                        double& r, double row[7]) {
-  d3 T = quat_apply(qw, qv, p);
-  T = {T.x + tr.x, T.y + tr.y, T.z + tr.z};
+// Returns the match flag; r and row[7] = lam [c dR(q)p/dq | c] are set when matched.  TAPS (the weighted variants): also the
+// four tap rows, their bilinear weights and ne = n.e without lambda, what data_weight (slm_data.h) reads.
+template <bool TAPS>
+__device__ __forceinline__ bool rg_eval(const FrameIn& f, const d3 T, const d3 p, const double qw, const d3 qv, const double lam,
+                                        double& r, double row[7], int taps[4], double tapw[4], double& ne) {
 
   // ---- projection + validity on ROUNDED coordinates ----
   const double fx = (double)f.fx, fy = (double)f.fy, cx = (double)f.cx, cy = (double)f.cy;
@@ -153,6 +186,10 @@ __device__ __forceinline__ bool rg_eval(const FrameIn& f, const d3 p, const doub
     const d3 P = {(double)tp[t][0], (double)tp[t][1], (double)tp[t][2]};
     const d3 Nn = {(double)tn[t][0], (double)tn[t][1], (double)tn[t][2]};
     const double wv = an * am;
+    if (TAPS) {
+      taps[t] = rows[t];
+      tapw[t] = wv;
+    }
     o = {o.x + P.x * wv, o.y + P.y * wv, o.z + P.z * wv};
     n = {n.x + Nn.x * wv, n.y + Nn.y * wv, n.z + Nn.z * wv};
     const double sn = dn >= 0.0 ? 1.0 : -1.0, sm = dm >= 0.0 ? 1.0 : -1.0;
@@ -166,7 +203,12 @@ __device__ __forceinline__ bool rg_eval(const FrameIn& f, const d3 p, const doub
   if (!(o.x == o.x && o.y == o.y && o.z == o.z && n.x == n.x && n.y == n.y && n.z == n.z)) return false;
 
   const d3 e = T - o;
-  r = lam * dot(n, e);
+  if (TAPS) {
+    ne = dot(n, e);
+    r = lam * ne;
+  } else {
+    r = lam * dot(n, e);
+  }
   // ---- c = n^T (I - A) + e^T B, A = do/d(u,v) Pi, B = dn/d(u,v) Pi ----
   const double Z = T.z;   // no epsilon in dPi
   const d3 Pi0 = {fx / Z, 0.0, -fx * T.x / (Z * Z)};
@@ -187,7 +229,14 @@ __device__ __forceinline__ bool rg_eval(const FrameIn& f, const d3 p, const doub
 }
 
 // grid = (min(chunks of the largest frame, RG_MAX_GRID), frames), block = RG_CHUNK
-__global__ void __launch_bounds__(RG_CHUNK) k_rg_pass(const RigidSlot* __restrict__ slots, double lam) {
+// CM: correspondence rows (slm_rigid_set_terms) 0 none / 1 point-point / 2 point-plane; WT: the data rows carry the
+// per-residual weight of data_weight (slm_data.h).  <0, false> is the plain stage: what a context without terms launches.
+// A surfel with valid_i adds the rows lam_c [c dR(q)p/dq | c], r = lam_c c.(R(q)p + t - o_i), c = e_x, e_y, e_z (CM 1) or n_i
+// (CM 2), into the same 28 + 7 sums, one row at a time through the data row's registers, whether or not the data term matched
+// it; their sum of squares and the count of such surfels go to RG_RC / RG_KC.  WT: row and r scaled by sqrt(w), w at this
+// point from s = (n.e)^2 without lambda; the match count stays the match set's (weight 0 is matched and adds nothing).
+template <int CM, bool WT>
+__global__ void __launch_bounds__(RG_CHUNK) k_rg_pass(const RigidSlot* __restrict__ slots, double lam, RgTermArgs ta) {
   __shared__ double s_part[4 * 48];
   const RigidSlot& s = slots[blockIdx.y];
   if (s.stopped) return;
@@ -205,8 +254,19 @@ __global__ void __launch_bounds__(RG_CHUNK) k_rg_pass(const RigidSlot* __restric
 #pragma unroll
     for (int a = 0; a < 48; ++a) vals[a] = 0.0;
     if (i < N) {
-      double r, row[7];
-      if (rg_eval(f, ld_state3(f.sf_points, (size_t)i, f64), qw, qv, tr, lam, r, row)) {
+      double r, row[7], ne = 0.0;
+      int taps[4];
+      double tapw[4];
+      const d3 p = ld_state3(f.sf_points, (size_t)i, f64);
+      d3 T = quat_apply(qw, qv, p);
+      T = {T.x + tr.x, T.y + tr.y, T.z + tr.z};
+      if (rg_eval<WT>(f, T, p, qw, qv, lam, r, row, taps, tapw, ne)) {
+        if (WT) {
+          const double sw = sqrt(data_weight(ta.wa, &ta.terms[blockIdx.y].wd, (int)i, ne * ne, taps, tapw));
+          r *= sw;
+#pragma unroll
+          for (int a = 0; a < 7; ++a) row[a] *= sw;
+        }
         int e = 0;
 #pragma unroll
         for (int a = 0; a < 7; ++a)
@@ -216,6 +276,42 @@ __global__ void __launch_bounds__(RG_CHUNK) k_rg_pass(const RigidSlot* __restric
         for (int a = 0; a < 7; ++a) vals[28 + a] = row[a] * r;
         vals[RG_R2] = r * r;
         vals[RG_M] = 1.0;
+      }
+      if (CM != 0) {
+        const RigidTerms& tm = ta.terms[blockIdx.y];
+        const double* __restrict__ co = tm.o;
+        if (co && tm.valid[i]) {
+          const d3 ec = {T.x - co[3 * (size_t)i], T.y - co[3 * (size_t)i + 1], T.z - co[3 * (size_t)i + 2]};
+          d3 nc3 = {0.0, 0.0, 0.0};
+          if (CM == 2) {
+            const double* __restrict__ cn = tm.n;
+            nc3 = {cn[3 * (size_t)i], cn[3 * (size_t)i + 1], cn[3 * (size_t)i + 2]};
+          }
+          const double cl = ta.corr_lam;
+#pragma unroll
+          for (int comp = 0; comp < (CM == 1 ? 3 : 1); ++comp) {
+            const d3 c = CM == 2 ? nc3 : d3{comp == 0 ? 1.0 : 0.0, comp == 1 ? 1.0 : 0.0, comp == 2 ? 1.0 : 0.0};
+            double jq[4];
+            quat_jac_row(qw, qv, p, c, jq);
+            row[0] = cl * jq[0];
+            row[1] = cl * jq[1];
+            row[2] = cl * jq[2];
+            row[3] = cl * jq[3];
+            row[4] = cl * c.x;
+            row[5] = cl * c.y;
+            row[6] = cl * c.z;
+            r = cl * dot(c, ec);
+            int e = 0;
+#pragma unroll
+            for (int a = 0; a < 7; ++a)
+#pragma unroll
+              for (int b = a; b < 7; ++b) vals[e++] += row[a] * row[b];
+#pragma unroll
+            for (int a = 0; a < 7; ++a) vals[28 + a] += row[a] * r;
+            vals[RG_RC] += r * r;
+          }
+          vals[RG_KC] = 1.0;
+        }
       }
     }
     // lane 4 a of a wave receives the wave's sum of value a of each group of 16 (col_reduce16)
@@ -352,7 +448,7 @@ __global__ void __launch_bounds__(64) k_rg_step(RigidSlot* __restrict__ slots, i
 #pragma unroll
     for (int c = 0; c < 7; ++c) tb[c] = s.trial[c];
     rg_rot(tb, lam_r, rr, jq);
-    const double loss = P[RG_R2] + rr * rr;
+    const double loss = (P[RG_R2] + P[RG_RC]) + rr * rr;   // weighted data + correspondence (0 without the term) + Rot
     const double u_used = s.u;
     int acc = 1;
     if (phase_test) {
@@ -388,6 +484,8 @@ __global__ void __launch_bounds__(64) k_rg_step(RigidSlot* __restrict__ slots, i
       G[c] = P[c];
       s.G[c] = P[c];
     }
+    s.G[RG_RC] = P[RG_RC];
+    s.G[RG_KC] = P[RG_KC];
   } else {
 #pragma unroll
     for (int c = 0; c < RG_NS; ++c) G[c] = s.G[c];
@@ -413,12 +511,13 @@ __global__ void __launch_bounds__(64) k_rg_step(RigidSlot* __restrict__ slots, i
 }
 
 // grid = 1, block = 64: the system and the loss of the pass that just ran at the slot's trial point (slm_rigid_assemble)
-__global__ void __launch_bounds__(64) k_rg_assemble_out(const RigidSlot* __restrict__ slots, int slot, double lam_r,
+__global__ void __launch_bounds__(64) k_rg_assemble_out(RigidSlot* __restrict__ slots, int slot, double lam_r,
                                                         double* __restrict__ jtj, double* __restrict__ jtl,
                                                         double* __restrict__ loss_m) {
   __shared__ double P[RG_NV];
-  const RigidSlot& s = slots[slot];
+  RigidSlot& s = slots[slot];
   rg_reduce(s, P);
+  if (threadIdx.x < RG_NV) s.G[threadIdx.x] = P[threadIdx.x];   // the sums at the point: what slm_rigid_get_terms reads
   if (threadIdx.x != 0) return;
   double b[7], A[7][7], rhs[7], rot_r;
 #pragma unroll
@@ -433,7 +532,7 @@ __global__ void __launch_bounds__(64) k_rg_assemble_out(const RigidSlot* __restr
 #pragma unroll
     for (int a = 0; a < 7; ++a) jtl[a] = rhs[a];
   if (loss_m) {
-    loss_m[0] = P[RG_R2] + rot_r * rot_r;
+    loss_m[0] = (P[RG_R2] + P[RG_RC]) + rot_r * rot_r;
     loss_m[1] = P[RG_M];
   }
 }
@@ -453,6 +552,25 @@ __global__ void __launch_bounds__(64) k_rg_get(const RigidSlot* __restrict__ slo
   }
 #pragma unroll
   for (int c = 0; c < 7; ++c) out[c] = b[c];
+}
+
+// out[4] <- {sum w r^2, matched count, sum |r_c|^2, kept count} of the sums kept at the slot's beta
+__global__ void __launch_bounds__(64) k_rg_get_terms(const RigidSlot* __restrict__ slots, int slot, double* __restrict__ out) {
+  if (threadIdx.x != 0) return;
+  const RigidSlot& s = slots[slot];
+  out[0] = s.G[RG_R2];
+  out[1] = s.G[RG_M];
+  out[2] = s.G[RG_RC];
+  out[3] = s.G[RG_KC];
+}
+
+// grid = (ceil(N / 256)): the correspondence targets of a raw frame from the flow (2,H,W) (corr_target_of, slm_corr.h)
+__global__ void __launch_bounds__(256) k_rg_corr_targets(slm_frame fr, const float* __restrict__ flow, double* __restrict__ o,
+                                                          double* __restrict__ n, uint8_t* __restrict__ valid) {
+  const FrameIn& f = reinterpret_cast<const FrameIn&>(fr);
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= f.N) return;
+  corr_target_of(f, i, flow, o, n, valid);
 }
 
 // p <- R(q) p + t, nrm <- F.normalize(R(q) nrm), in place; T float or double
@@ -517,15 +635,51 @@ void launch_init(slm_rigid* r, int first, int n, const slm_frame* frames, const 
   for (int b = 0; b < n; b += RG_INIT_BATCH) {
     RgInitArgs a = {};
     const int m = std::min(RG_INIT_BATCH, n - b);
-    for (int k = 0; k < m; ++k) a.f[k] = frames[b + k];
-    hipLaunchKernelGGL(k_rg_init, dim3(m), dim3(64), 0, st, r->slots.p, first + b, a, cfg, r->part.p,
+    for (int k = 0; k < m; ++k) {
+      a.f[k] = frames[b + k];
+      a.t[k] = r->terms_h[first + b + k];
+    }
+    hipLaunchKernelGGL(k_rg_init, dim3(m), dim3(64), 0, st, r->slots.p, r->terms.p, first + b, a, cfg, r->part.p,
                        r->cap_chunks * RG_NV, r->rec.p, r->cap_iters, beta0);
   }
 }
 
+// the pass of slots [first, first + n): the plain kernel unless the context carries terms that a slot of the launch uses
 void launch_pass(slm_rigid* r, int first, int n, size_t max_chunks, double lam, hipStream_t st) {
   const unsigned gx = (unsigned)std::max<size_t>(1, std::min<size_t>(max_chunks, RG_MAX_GRID));
-  hipLaunchKernelGGL(k_rg_pass, dim3(gx, n), dim3(RG_CHUNK), 0, st, r->slots.p + first, lam);
+  const dim3 grid(gx, n), blk(RG_CHUNK);
+  int cm = 0;
+  if (r->corr_mode)
+    for (int k = first; k < first + n; ++k)
+      if (r->terms_h[k].o.get()) cm = r->corr_mode;
+  const bool wt = r->seg_mode != 0 || r->pp_max > 0.0;
+  RgTermArgs ta = {};
+  ta.terms = r->terms.p + first;
+  ta.corr_lam = r->corr_weight;
+  ta.wa.wd = nullptr;
+  ta.wa.pp_max = r->pp_max;
+  ta.wa.seg_mode = r->seg_mode;
+  const RigidSlot* sl = r->slots.p + first;
+#define RG_PASS(CM, WT) hipLaunchKernelGGL((k_rg_pass<CM, WT>), grid, blk, 0, st, sl, lam, ta)
+  if (!wt) {
+    if (cm == 0) RG_PASS(0, false);
+    else if (cm == 1) RG_PASS(1, false);
+    else RG_PASS(2, false);
+  } else {
+    if (cm == 0) RG_PASS(0, true);
+    else if (cm == 1) RG_PASS(1, true);
+    else RG_PASS(2, true);
+  }
+#undef RG_PASS
+}
+
+// with a semantic weight every slot of the call needs its inputs: no silent unweighted run
+int check_semantic(const char* fn, const slm_rigid* r, int first, int n) {
+  if (!r->seg_mode) return SLM_OK;
+  for (int k = first; k < first + n; ++k)
+    if (!r->terms_h[k].wd.has)
+      return fail(SLM_ERR_UNBOUND, std::string(fn) + ": slot " + std::to_string(k) + " has no semantic inputs; call slm_rigid_set_semantic");
+  return SLM_OK;
 }
 
 }  // namespace
@@ -546,8 +700,11 @@ int slm_rigid_create(int32_t max_frames, slm_rigid** out) {
   slm_rigid* r = new slm_rigid();
   r->max_frames = max_frames;
   const size_t ns = (size_t)max_frames + 1;
+  r->terms_h.assign(ns, RigidTerms{});
   hipError_t e = r->slots.grow(ns, ns);
   if (e == hipSuccess) e = hipMemset(r->slots.p, 0, sizeof(RigidSlot) * ns);
+  if (e == hipSuccess) e = r->terms.grow(ns, ns);
+  if (e == hipSuccess) e = hipMemset(r->terms.p, 0, sizeof(RigidTerms) * ns);
   if (e == hipSuccess) e = ensure(r, 64, 10);
   if (e == hipSuccess) {   // every slot reads as a finished run at identity before its first run
     slm_rigid_config cfg = {};
@@ -577,6 +734,7 @@ int slm_rigid_run(slm_rigid* r, const slm_rigid_config* cfg, int32_t n_frames, c
     if (const int rc = check_frame("slm_rigid_run", frames[k])) return rc;
     max_chunks = std::max(max_chunks, frame_chunks(frames[k]));
   }
+  if (const int rc = check_semantic("slm_rigid_run", r, 0, n_frames)) return rc;
   HIPCHK(ensure(r, max_chunks, (size_t)cfg->num_iterations));
   hipStream_t st = (hipStream_t)stream;
   const int n_iter = cfg->num_iterations;
@@ -626,6 +784,7 @@ int slm_rigid_assemble(slm_rigid* r, const slm_rigid_config* cfg, const slm_fram
   if (!r || !cfg || !frame || !beta7_device) return fail(SLM_ERR_INVALID, "slm_rigid_assemble: null argument");
   if (cfg->num_iterations < 0) return fail(SLM_ERR_INVALID, "slm_rigid_assemble: num_iterations must be >= 0");
   if (const int rc = check_frame("slm_rigid_assemble", *frame)) return rc;
+  if (const int rc = check_semantic("slm_rigid_assemble", r, r->max_frames, 1)) return rc;
   const size_t chunks = frame_chunks(*frame);
   HIPCHK(ensure(r, chunks, 0));
   hipStream_t st = (hipStream_t)stream;
@@ -636,6 +795,79 @@ int slm_rigid_assemble(slm_rigid* r, const slm_rigid_config* cfg, const slm_fram
   launch_pass(r, slot, 1, chunks, cfg->w_data, st);
   hipLaunchKernelGGL(k_rg_assemble_out, dim3(1), dim3(64), 0, st, r->slots.p, slot, cfg->w_rot, JtJ49_device, jtl7_device,
                      loss_M_device);
+  HIPCHK(hipGetLastError());
+  return SLM_OK;
+}
+
+int slm_rigid_set_terms(slm_rigid* r, int32_t corr_mode, double corr_weight, int32_t seg_mode, double pp_max) {
+  if (!r) return fail(SLM_ERR_INVALID, "slm_rigid_set_terms: null argument");
+  if (corr_mode < 0 || corr_mode > 2)
+    return fail(SLM_ERR_INVALID, "slm_rigid_set_terms: corr_mode must be 0 (none), 1 (point-point) or 2 (point-plane)");
+  if (!(corr_weight - corr_weight == 0.0)) return fail(SLM_ERR_INVALID, "slm_rigid_set_terms: corr_weight must be finite");
+  if (seg_mode < 0 || seg_mode > 2) return fail(SLM_ERR_INVALID, "slm_rigid_set_terms: seg_mode must be 0 (none), 1 (hard) or 2 (soft)");
+  if (!(pp_max - pp_max == 0.0) || pp_max < 0.0) return fail(SLM_ERR_INVALID, "slm_rigid_set_terms: pp_max must be finite and >= 0");
+  r->corr_mode = corr_mode;
+  r->corr_weight = corr_weight;
+  r->seg_mode = seg_mode;
+  r->pp_max = pp_max;
+  r->terms_h.assign((size_t)r->max_frames + 1, RigidTerms{});   // every call clears every slot's inputs
+  return SLM_OK;
+}
+
+int slm_rigid_set_corr(slm_rigid* r, int32_t slot, const double* pts, const double* nrm, const uint8_t* valid) {
+  if (!r) return fail(SLM_ERR_INVALID, "slm_rigid_set_corr: null argument");
+  if (slot < 0 || slot > r->max_frames) return fail(SLM_ERR_INVALID, "slm_rigid_set_corr: bad slot");
+  if (!r->corr_mode) return fail(SLM_ERR_INVALID, "slm_rigid_set_corr: the correspondence term is off; call slm_rigid_set_terms with corr_mode 1 or 2 first");
+  RigidTerms& t = r->terms_h[slot];
+  if (!pts) {   // clears
+    t.o = nullptr;
+    t.n = nullptr;
+    t.valid = nullptr;
+    return SLM_OK;
+  }
+  if (!valid) return fail(SLM_ERR_INVALID, "slm_rigid_set_corr: null argument");
+  if (r->corr_mode == 2 && !nrm) return fail(SLM_ERR_INVALID, "slm_rigid_set_corr: corr_mode 2 (point-plane) needs nrm");
+  t.o = pts;
+  t.n = nrm;
+  t.valid = valid;
+  return SLM_OK;
+}
+
+int slm_rigid_set_semantic(slm_rigid* r, int32_t slot, int32_t num_classes, const int32_t* sf_seg, const float* sf_seg_conf,
+                           const float* tgt_seg_conf) {
+  if (!r) return fail(SLM_ERR_INVALID, "slm_rigid_set_semantic: null argument");
+  if (slot < 0 || slot > r->max_frames) return fail(SLM_ERR_INVALID, "slm_rigid_set_semantic: bad slot");
+  if (!r->seg_mode) return fail(SLM_ERR_INVALID, "slm_rigid_set_semantic: the semantic weight is off; call slm_rigid_set_terms with seg_mode 1 or 2 first");
+  DataWeightDev& w = r->terms_h[slot].wd;
+  if (!sf_seg) {   // clears
+    w = DataWeightDev{};
+    return SLM_OK;
+  }
+  if (!sf_seg_conf || !tgt_seg_conf) return fail(SLM_ERR_INVALID, "slm_rigid_set_semantic: null argument");
+  if (num_classes < 1 || num_classes > SLM_MAX_CLASSES)
+    return fail(SLM_ERR_UNSUPPORTED, "slm_rigid_set_semantic: num_classes must be in 1..SLM_MAX_CLASSES (4)");
+  w.sf_seg = const_cast<int32_t*>(sf_seg);
+  w.sf_seg_conf = const_cast<float*>(sf_seg_conf);
+  w.tgt_seg_conf = const_cast<float*>(tgt_seg_conf);
+  w.C = num_classes;
+  w.has = 1;
+  return SLM_OK;
+}
+
+int slm_rigid_corr_targets(const slm_frame* frame, const float* flow, double* pts, double* nrm, uint8_t* valid, void* stream) {
+  if (!frame || !flow || !pts || !nrm || !valid) return fail(SLM_ERR_INVALID, "slm_rigid_corr_targets: null argument");
+  if (const int rc = check_frame("slm_rigid_corr_targets", *frame)) return rc;
+  if (frame->N == 0) return SLM_OK;
+  if (frame->T == 0) return fail(SLM_ERR_INVALID, "slm_rigid_corr_targets: T must be > 0");
+  hipLaunchKernelGGL(k_rg_corr_targets, dim3((frame->N + 255) / 256), dim3(256), 0, (hipStream_t)stream, *frame, flow, pts, nrm, valid);
+  HIPCHK(hipGetLastError());
+  return SLM_OK;
+}
+
+int slm_rigid_get_terms(slm_rigid* r, int32_t slot, double* out4_device, void* stream) {
+  if (!r || !out4_device) return fail(SLM_ERR_INVALID, "slm_rigid_get_terms: null argument");
+  if (slot < 0 || slot > r->max_frames) return fail(SLM_ERR_INVALID, "slm_rigid_get_terms: bad slot");
+  hipLaunchKernelGGL(k_rg_get_terms, dim3(1), dim3(64), 0, (hipStream_t)stream, r->slots.p, slot, out4_device);
   HIPCHK(hipGetLastError());
   return SLM_OK;
 }

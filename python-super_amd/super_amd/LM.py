@@ -126,12 +126,60 @@ class BoundFrame:
         self.c = fr
 
 
+def corr_tensors(corr, N, dev):
+    """``corr_points = (pts, nrm, valid)`` as the library reads it: (N,3) float64, (N,3) float64 or ``None``, (N,) uint8"""
+    pts, nrm, valid = corr
+    pts = _as(pts, torch.float64, dev)
+    valid = _as(valid, torch.uint8, dev)
+    nrm = None if nrm is None else _as(nrm, torch.float64, dev)
+    if tuple(pts.shape) != (N, 3) or tuple(valid.shape) != (N,) or (nrm is not None and tuple(nrm.shape) != (N, 3)):
+        raise ValueError(f"corr_points must be ((N,3), (N,3) or None, (N,)) with N = {N}")
+    return pts, nrm, valid
+
+
+def semantic_tensors(who, sf, new_data, N, T, dev):
+    """The semantic inputs of a weighted data term as the library reads them: ``sf.seg`` (N,) int32, ``sf.seg_conf`` (N,C)
+    and ``new_data.seg_conf`` (T,C) float32; ``who`` names the class in the refusals."""
+    got = {}
+    for name, obj, attr in (("sf.seg", sf, "seg"), ("sf.seg_conf", sf, "seg_conf"), ("new_data.seg_conf", new_data, "seg_conf")):
+        t = getattr(obj, attr, None)
+        if t is None:
+            raise ValueError(f"{who}(weighted_data=True): {name} is missing")
+        got[name] = t
+    sc, tc = got["sf.seg_conf"], got["new_data.seg_conf"]
+    if got["sf.seg"].numel() != N or got["sf.seg"].dim() > 2:
+        raise ValueError(f"{who}(weighted_data=True): sf.seg must be ({N},), got {tuple(got['sf.seg'].shape)}")
+    if sc.dim() != 2 or sc.shape[0] != N or not 1 <= sc.shape[1] <= _lib.SLM_MAX_CLASSES:
+        raise ValueError(f"{who}(weighted_data=True): sf.seg_conf must be ({N}, C) with C in 1..{_lib.SLM_MAX_CLASSES}, "
+                         f"got {tuple(sc.shape)}")
+    if tc.dim() != 2 or tuple(tc.shape) != (T, sc.shape[1]):
+        raise ValueError(f"{who}(weighted_data=True): new_data.seg_conf must be ({T}, {sc.shape[1]}), got {tuple(tc.shape)}")
+    return _as(got["sf.seg"].reshape(-1), torch.int32, dev), _as(sc, torch.float32, dev), _as(tc, torch.float32, dev)
+
+
+def data_weight_options(opt):
+    """(seg_mode, pp_max) that ``weighted_data=True`` reads from ``opt``: soft wins over hard; raft_stereo truncates at 2e-5"""
+    soft = bool(getattr(opt, "sf_soft_seg_point_plane", False))
+    hard = bool(getattr(opt, "sf_hard_seg_point_plane", False))
+    return (2 if soft else (1 if hard else 0)), (2e-5 if getattr(opt, "depth_model", None) == "raft_stereo" else 0.0)
+
+
+def corr_options(who, opt):
+    """(mode, weight) that ``corr_term=True`` reads from ``opt``"""
+    if not getattr(opt, "sf_corr", False):
+        raise ValueError(f"{who}(corr_term=True) needs opt.sf_corr")
+    lt = getattr(opt, "sf_corr_loss_type", "point-point")
+    if lt not in ("point-point", "point-plane"):
+        raise ValueError(f"sf_corr_loss_type {lt!r}")
+    return (1 if lt == "point-point" else 2), float(getattr(opt, "sf_corr_weight", 0.001))
+
+
 class LM_Solver():
     """Drop-in for ``super.LM.LM_Solver``; see module docstring."""
 
     def __init__(self, opt, convs=None, max_frames=1, shard_surfels=False, rank=None, world=None,
                  all_reduce=None, broadcast=None, corr_term=False, weighted_data=False, face_term=False,
-                 morph_term=False, global_rigid=False):
+                 morph_term=False, global_rigid=False, rigid_terms=False):
         """``LM_Solver(opt, convs)`` as in the reference.  ``shard_surfels=True`` (after
         ``torch.distributed.init_process_group``) splits the surfels of ONE large frame over the GPUs
         of a node: every rank evaluates its share, the block-sparse J^T J / J^T r sums and the loss are
@@ -161,14 +209,23 @@ class LM_Solver():
         ``global_rigid=True`` (opt-in) runs the global rigid pre-alignment ahead of the node solve (``super_amd.rigid``,
         ``slm_rigid_*`` in include/super_lm.h): ``LM()`` / ``LM_batch()`` first estimate ``T_g`` of every frame
         (``RigidAlign``: the plain, unweighted point-to-plane term plus the Rot term, whatever terms the node solve
-        carries), then MOVE ``sf`` BY IT (``rigid_update``: ``sf.points``, ``sf.norms``, ``sf.ED_nodes.points`` and
-        ``.norms`` are replaced by the moved tensors), then run exactly what they run without the flag on the moved
+        carries -- unless ``rigid_terms``, below), then MOVE ``sf`` BY IT (``rigid_update``: ``sf.points``, ``sf.norms``,
+        ``sf.ED_nodes.points`` and ``.norms`` are replaced by the moved tensors), then run exactly what they run without the flag on the moved
         model.  They still return (J,7): ``Surfels.update(deform)`` after them completes the frame.  ``last_rigid`` holds
         the ``T_g`` of the last call.  Not built with ``shard_surfels``; ``prepare_model()`` is refused (the model moves
         after the target arrives: a plan prepared ahead would be sorted from stale points).  Without the flag nothing
-        changes."""
+        changes.
+        ``rigid_terms=True`` (opt-in; needs ``global_rigid`` and at least one of ``corr_term`` / ``weighted_data`` in
+        effect) lets the stage carry whichever of those two terms the solver carries (``slm_rigid_set_terms``).  Given a
+        flow, the correspondence targets are then built ONCE, on the UNMOVED model (``RigidAlign.corr_targets``), used by
+        the stage and handed to the node solve as ``corr_points``: they are points of the target frame and do not move
+        with the model.  Without it the stage is the plain one and the node solve samples the flow at the projections of
+        the moved model, as before."""
         self.opt = opt
         self.global_rigid = bool(global_rigid)
+        self.rigid_terms = bool(rigid_terms)
+        if self.rigid_terms and not self.global_rigid:
+            raise ValueError("LM_Solver(rigid_terms=True) needs global_rigid=True")
         if self.global_rigid and (shard_surfels or world is not None):
             raise NotImplementedError("LM_Solver: global_rigid with shard_surfels is not built (the stage needs every "
                                       "surfel of the frame on one device)")
@@ -201,24 +258,19 @@ class LM_Solver():
         self._face_loss = None
         self.seg_mode, self.pp_max = 0, 0.0
         if weighted_data:
-            soft = bool(getattr(opt, "sf_soft_seg_point_plane", False))
-            hard = bool(getattr(opt, "sf_hard_seg_point_plane", False))
-            self.seg_mode = 2 if soft else (1 if hard else 0)
-            self.pp_max = 2e-5 if getattr(opt, "depth_model", None) == "raft_stereo" else 0.0
+            self.seg_mode, self.pp_max = data_weight_options(opt)
         self.weighted = bool(self.seg_mode or self.pp_max > 0.0)
         self.corr_mode = 0
         if corr_term:
-            if not getattr(opt, "sf_corr", False):
-                raise ValueError("LM_Solver(corr_term=True) needs opt.sf_corr")
-            lt = getattr(opt, "sf_corr_loss_type", "point-point")
-            if lt not in ("point-point", "point-plane"):
-                raise ValueError(f"sf_corr_loss_type {lt!r}")
+            mode, weight = corr_options("LM_Solver", opt)
             if shard_surfels or world is not None:
                 raise NotImplementedError("LM_Solver: corr_term with shard_surfels is not built (the term needs every "
                                           "surfel of the frame on one device)")
-            self.corr_mode = 1 if lt == "point-point" else 2
-            self.corr_weight = float(getattr(opt, "sf_corr_weight", 0.001))
+            self.corr_mode, self.corr_weight = mode, weight
         self.last_corr_kept = None                   # per slot: correspondences kept in the last run (None: slot without)
+        if self.rigid_terms and not (self.corr_mode or self.weighted):
+            raise ValueError("LM_Solver(rigid_terms=True) needs corr_term=True or weighted_data=True (with a weight that "
+                             "opt turns on)")
         self.lib = _lib.load()                       # raises if the HIP library is missing
         self.device = torch.device("cuda", torch.cuda.current_device()) \
             if torch.cuda.is_available() else None
@@ -390,13 +442,7 @@ class LM_Solver():
             bf.corr_keep = (fl,)                       # read by the bind's kernel on the stream
             _lib.check(self.lib.slm_bind_corr_flow(h, slot, _dev_ptr(fl), st), "slm_bind_corr_flow")
             return
-        pts, nrm, valid = corr
-        N = bf.c.N
-        pts = _as(pts, torch.float64, dev)
-        valid = _as(valid, torch.uint8, dev)
-        nrm = None if nrm is None else _as(nrm, torch.float64, dev)
-        if tuple(pts.shape) != (N, 3) or tuple(valid.shape) != (N,) or (nrm is not None and tuple(nrm.shape) != (N, 3)):
-            raise ValueError(f"corr_points must be ((N,3), (N,3) or None, (N,)) with N = {N}")
+        pts, nrm, valid = corr_tensors(corr, bf.c.N, dev)
         bf.corr_keep = (pts, nrm, valid)
         _lib.check(self.lib.slm_bind_corr_points(h, slot, _dev_ptr(pts), None if nrm is None else _dev_ptr(nrm),
                                                  _dev_ptr(valid), st), "slm_bind_corr_points")
@@ -406,23 +452,8 @@ class LM_Solver():
         (N,C), ``new_data.seg_conf`` (T,C)."""
         if not self.seg_mode:
             return
-        dev, N, T = bf.device, bf.c.N, bf.c.T
-        got = {}
-        for name, obj, attr in (("sf.seg", sf, "seg"), ("sf.seg_conf", sf, "seg_conf"), ("new_data.seg_conf", new_data, "seg_conf")):
-            t = getattr(obj, attr, None)
-            if t is None:
-                raise ValueError(f"LM_Solver(weighted_data=True): {name} is missing")
-            got[name] = t
-        sc, tc = got["sf.seg_conf"], got["new_data.seg_conf"]
-        if got["sf.seg"].numel() != N or got["sf.seg"].dim() > 2:
-            raise ValueError(f"LM_Solver(weighted_data=True): sf.seg must be ({N},), got {tuple(got['sf.seg'].shape)}")
-        if sc.dim() != 2 or sc.shape[0] != N or not 1 <= sc.shape[1] <= _lib.SLM_MAX_CLASSES:
-            raise ValueError(f"LM_Solver(weighted_data=True): sf.seg_conf must be ({N}, C) with C in 1..{_lib.SLM_MAX_CLASSES}, "
-                             f"got {tuple(sc.shape)}")
-        if tc.dim() != 2 or tuple(tc.shape) != (T, sc.shape[1]):
-            raise ValueError(f"LM_Solver(weighted_data=True): new_data.seg_conf must be ({T}, {sc.shape[1]}), got {tuple(tc.shape)}")
-        seg = _as(got["sf.seg"].reshape(-1), torch.int32, dev)
-        sc, tc = _as(sc, torch.float32, dev), _as(tc, torch.float32, dev)
+        dev = bf.device
+        seg, sc, tc = semantic_tensors("LM_Solver", sf, new_data, bf.c.N, bf.c.T, dev)
         bf.sem_keep = (seg, sc, tc)                    # read in place by the library while the slot is used
         _lib.check(self.lib.slm_bind_data_semantic(h, slot, int(sc.shape[1]), _dev_ptr(seg), _dev_ptr(sc), _dev_ptr(tc),
                                                    _stream_ptr(dev)), "slm_bind_data_semantic")
@@ -614,7 +645,7 @@ class LM_Solver():
         h = self._handle(u, v, minimal_loss)
         corrs = [fr[3] if len(fr) > 3 else None for fr in frames]
         frames = [tuple(fr[:3]) for fr in frames]
-        rigid_recs = self._rigid_stage(frames, u, v, minimal_loss) if self.global_rigid else [None] * n
+        rigid_recs = self._rigid_stage(frames, corrs, u, v, minimal_loss) if self.global_rigid else [None] * n
         bfs = self._bind_batch(h, frames) if n > 1 else [self._bind(h, 0, *frames[0])]
         for i, (bf, corr) in enumerate(zip(bfs, corrs)):
             self._bind_corr(h, i, bf, corr)
@@ -698,15 +729,26 @@ class LM_Solver():
         return [dict(loss=r.loss, u=r.u, accepted=bool(r.accepted), status=int(r.status),
                      M_grad=int(r.M_grad), M_loss=int(r.M_loss)) for r in arr[:n]]
 
-    def _rigid_stage(self, frames, u, v, minimal_loss):
-        """The rigid pre-alignment of every frame: ``T_g`` into ``last_rigid``, every ``sf`` moved by its own."""
+    def _rigid_stage(self, frames, corrs, u, v, minimal_loss):
+        """The rigid pre-alignment of every frame: ``T_g`` into ``last_rigid``, every ``sf`` moved by its own.  With
+        ``rigid_terms`` the stage carries the solver's terms, and a flow in ``corrs`` is REPLACED by the targets built from
+        it on the unmoved model (what the node solve is then bound with)."""
         from .rigid import RigidAlign, rigid_update
         if len({id(fr[0]) for fr in frames}) != len(frames):
             raise ValueError("LM_Solver(global_rigid=True): the frames of a batch must not share an sf object (each is "
                              "moved by its own T_g)")
         if self._rigid is None:
-            self._rigid = RigidAlign(self.opt, max_frames=self.max_frames)
-        self.last_rigid = self._rigid.align_batch(frames, u=u, v=v, minimal_loss=minimal_loss)
+            self._rigid = RigidAlign(self.opt, max_frames=self.max_frames,
+                                     corr_term=self.rigid_terms and bool(self.corr_mode),
+                                     weighted_data=self.rigid_terms and self.weighted)
+        stage = frames
+        if self.rigid_terms:
+            if self.corr_mode:
+                for i, (fr, corr) in enumerate(zip(frames, corrs)):
+                    if torch.is_tensor(corr):
+                        corrs[i] = self._rigid.corr_targets(*fr, corr)
+            stage = [fr + (corr if self.corr_mode else None,) for fr, corr in zip(frames, corrs)]
+        self.last_rigid = self._rigid.align_batch(stage, u=u, v=v, minimal_loss=minimal_loss)
         self.last_rigid_records = self._rigid.last_records
         for fr, tg in zip(frames, self.last_rigid):
             rigid_update(fr[0], tg)

@@ -47,6 +47,7 @@ EXPORTS = [
     "slm_enable_morph", "slm_bind_morph", "slm_morph_loss", "slm_morph_targets",
     "slm_rigid_abi_check", "slm_rigid_create", "slm_rigid_destroy", "slm_rigid_run", "slm_rigid_get", "slm_rigid_get_beta",
     "slm_rigid_get_records", "slm_rigid_assemble", "slm_rigid_transform",
+    "slm_rigid_set_terms", "slm_rigid_set_corr", "slm_rigid_set_semantic", "slm_rigid_corr_targets", "slm_rigid_get_terms",
 ]
 
 
@@ -273,6 +274,11 @@ def load():
         "slm_rigid_get_records": [vp, i32, C.POINTER(SlmIterRecord), i32, C.POINTER(C.c_int32), vp],
         "slm_rigid_assemble": [vp, C.POINTER(SlmRigidConfig), C.POINTER(SlmFrame), vp, vp, vp, vp, vp],
         "slm_rigid_transform": [i32, vp, vp, i32, vp, vp],
+        "slm_rigid_set_terms": [vp, i32, dbl, i32, dbl],
+        "slm_rigid_set_corr": [vp, i32, vp, vp, vp],
+        "slm_rigid_set_semantic": [vp, i32, i32, vp, vp, vp],
+        "slm_rigid_corr_targets": [C.POINTER(SlmFrame), vp, vp, vp, vp, vp],
+        "slm_rigid_get_terms": [vp, i32, vp, vp],
         "slm_graph_init": [i32, i32, i32, vp, vp, vp, vp, C.POINTER(SlmGraphOutputs), C.POINTER(C.c_int32), vp],
         "slm_graph_init_semantic": [i32, i32, i32, vp, vp, vp, vp, i32, vp, i32, C.POINTER(SlmGraphOutputs), vp, vp,
                                     C.POINTER(C.c_int32), vp],

@@ -12,6 +12,11 @@ surfels, 480 x 640) by default, one and eight frames per run, the model rigidly 
               refusal text
 
     python tools/time_rigid.py [--workload C2] [--frames 1 8] [--reps 10] [--only rigid lm] [--out FILE]
+                               [--corr MODE] [--weights {hard,soft,trunc}]
+
+``--corr 1|2`` / ``--weights`` put the stage's opt-in terms (``slm_rigid_set_terms``) on ``rigid`` and ``floor``: point-point /
+point-plane correspondence rows with targets built from a smooth synthetic flow by ``slm_rigid_corr_targets`` (weight 1),
+and the hard / soft semantic weight (a scene with semantic fields) or the 2e-5 truncation on the data rows.
 
 HIP events around every timed call after a warm-up call, median and maximum over --reps.  The frames of a run are the same
 scene in every slot.  Kernel times: run it under ``rocprofv3 --kernel-trace --stats -- python tools/time_rigid.py --only
@@ -62,6 +67,8 @@ def main():
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--only", nargs="+", default=CONFIGS, choices=CONFIGS)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--corr", type=int, default=0, choices=[0, 1, 2], metavar="MODE")
+    ap.add_argument("--weights", default=None, choices=["hard", "soft", "trunc"])
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("time_rigid.py needs a HIP device (no CPU fallback)")
@@ -70,12 +77,42 @@ def main():
     dims = dict(N=3000, J=48, H=60, W=80, src_border=5, tgt_border=3) if a.workload == "tiny" else dict(synth.WORKLOADS[a.workload])
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
-    sc = synth.make_scene(seed=0, **dims)
+    semantic = a.weights in ("hard", "soft")
+    sc = synth.make_scene(seed=0, **dims, **(dict(semantic=True, num_classes=3) if semantic else {}))
     sc = dataclasses.replace(sc, sf_points=displaced(sc.sf_points.astype(np.float64)).astype(np.float32))
     lib = _lib.load()
     stream = lambda: torch.cuda.current_stream(dev).cuda_stream
     cfg = _lib.SlmRigidConfig(num_iterations=ITERS, phase_test=1, w_data=1.0, w_rot=1.0, u0=10.0, v=7.5, minimal_loss0=1e10)
-    out = {"workload": a.workload, "N": sc.N, "J": sc.J, "H": sc.H, "W": sc.W, "iterations": ITERS, "results": {}}
+    out = {"workload": a.workload, "N": sc.N, "J": sc.J, "H": sc.H, "W": sc.W, "iterations": ITERS, "corr": a.corr,
+           "weights": a.weights, "results": {}}
+    seg_mode = {"hard": 1, "soft": 2}.get(a.weights, 0)
+    pp_max = 2e-5 if a.weights == "trunc" else 0.0
+    keep = []                                                  # the term inputs, read in place by the runs
+
+    def set_terms(h, cs):
+        """the stage's opt-in terms of every slot: targets from a smooth flow, the scene's semantic fields"""
+        if not (a.corr or seg_mode or pp_max):
+            return
+        _lib.check(lib.slm_rigid_set_terms(h, a.corr, 1.0, seg_mode, pp_max), "slm_rigid_set_terms")
+        t = lambda x, dt: torch.from_numpy(np.ascontiguousarray(x)).to(dev, dt)
+        for slot, c in enumerate(cs):
+            if a.corr:
+                flow = t(synth.smooth_flow(sc.H, sc.W, 11, amp=(2.0, 1.5)), torch.float32)
+                pts = torch.zeros((sc.N, 3), dtype=torch.float64, device=dev)
+                nrm, valid = torch.zeros_like(pts), torch.zeros(sc.N, dtype=torch.uint8, device=dev)
+                full = _lib.SlmFrame()
+                C.memmove(C.byref(full), C.byref(c), C.sizeof(full))
+                full.N = sc.N                                  # (floor: the arrays cover the whole model)
+                _lib.check(lib.slm_rigid_corr_targets(C.byref(full), flow.data_ptr(), pts.data_ptr(), nrm.data_ptr(),
+                                                      valid.data_ptr(), stream()), "slm_rigid_corr_targets")
+                _lib.check(lib.slm_rigid_set_corr(h, slot, pts.data_ptr(), nrm.data_ptr(), valid.data_ptr()), "slm_rigid_set_corr")
+                keep.append((flow, pts, nrm, valid))
+            if seg_mode:
+                seg, scf, tcf = t(sc.sf_seg, torch.int32), t(sc.sf_seg_conf, torch.float32), t(sc.tgt_seg_conf, torch.float32)
+                _lib.check(lib.slm_rigid_set_semantic(h, slot, int(scf.shape[1]), seg.data_ptr(), scf.data_ptr(), tcf.data_ptr()),
+                           "slm_rigid_set_semantic")
+                keep.append((seg, scf, tcf))
+        torch.cuda.synchronize()
 
     def rigid_records(h, slot):
         arr, got = (_lib.SlmIterRecord * ITERS)(), C.c_int32(0)
@@ -92,6 +129,7 @@ def main():
             arr = (_lib.SlmFrame * n)(*cs)
             h = C.c_void_p()
             _lib.check(lib.slm_rigid_create(n, C.byref(h)), "slm_rigid_create")
+            set_terms(h, cs)
             med, mx = timed(lambda: _lib.check(lib.slm_rigid_run(h, C.byref(cfg), n, arr, stream()), "slm_rigid_run"), a.reps)
             recs = rigid_records(h, 0)
             out["results"][f"{name}_b{n}"] = {
@@ -99,6 +137,10 @@ def main():
                 "frames_per_run": n, "surfels": int(cs[0].N), "launches": 2 * (ITERS + 1) + (n + 7) // 8,
                 "accepted": sum(r["accepted"] for r in recs), "matched": recs[0]["M"],
                 "first_loss": recs[0]["loss"], "final_loss": min(r["loss"] for r in recs if r["accepted"])}
+            if a.corr or seg_mode or pp_max:
+                t4 = torch.empty(4, dtype=torch.float64, device=dev)
+                _lib.check(lib.slm_rigid_get_terms(h, 0, t4.data_ptr(), stream()), "slm_rigid_get_terms")
+                out["results"][f"{name}_b{n}"]["terms"] = t4.cpu().tolist()
             lib.slm_rigid_destroy(h)
         if "lm" in a.only:
             e = Engine(dev, max_frames=n, num_iterations=ITERS)
